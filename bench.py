@@ -7,15 +7,20 @@ features already resident in HBM, plans (dst-sorted CSR) built before the timed 
 value = edges traversed per second, whole job = n_gpus * 2 * E' / step time (ranks are independent replicas with
 different feature batches: weak scaling, no data-path collective — SURVEY.md §8e).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload products|arxiv|batched|rowpart] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload products|arxiv|batched|rowpart] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras] [--cpu-baseline-full]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher environment re-executes itself under torch.distributed.run with N
 ranks on 127.0.0.1 (one process per GPU, RCCL); it exits non-zero — never degrades to one rank — if the node has fewer GPUs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline needs: set-up (graph,
+plan, placement calibration), W warm-up steps, EXACTLY K timed steps, the outputs of the last timed step if --dump-outputs is
+given (DIR/<name>.npy, float32, at most 64 MB in all: a fixed seeded sample of rows where an output is larger), and the line.
+--full adds everything else to the line, measured after the timed steps:
   roofline     — the dominant kernel's algorithmic bytes / its average duration measured with HIP events on the launch
                  stream inside the timed region, against the 8 TB/s HBM peak (MI355X_MICROARCH.md)
+  extras       — per-kernel and per-layer times, the other configs of BASELINE.json, placement and protocol side lines
   cpu_baseline — the CPU oracle (a port of the reference's algorithm; Julia is not installed) timed on the host, rank 0,
                  N=1 only, on a bounded sample: the same two layers on a 1/32-scale products-shaped graph, plus the GCN layer
                  once on the full products-shaped graph (the same workload as the GPU side).
@@ -223,12 +228,35 @@ def timed_region(step, steps, warmup, barrier, dist, device="cuda", before=None,
     return dt, out
 
 
-def batched_setup(rank, world, dist, G=8192, forward_factory=None, device=None):
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed step returned in its last step, one DIR/<name>.npy each (float32; float64 stays float64),
+    so that two builds can be compared output for output.  Each array gets an equal share of DUMP_LIMIT_BYTES; a larger one is cut to
+    a fixed sample of whole rows — numpy default_rng(0), sorted, the same rows in every run of the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // len(arrays)          # (4 KB per file for the .npy header)
+    for name, a in arrays.items():
+        a = a.detach()
+        if a.dtype != torch.float64:
+            a = a.to(torch.float32)
+        if a.numel() * a.element_size() > share:
+            rows = share // (a[0].numel() * a.element_size())
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))
+            a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+
+
+def batched_setup(rank, world, dist, G=8192, forward_factory=None, device=None, full=True):
     """BASELINE.json config 5 on this rank: its shard of the G synthetic graphs batched on the device, the model, and the static part of
     the exchange (gnnmp.parallel.ShardPlan: send / receive buffers and the inverse permutation, built ONCE).  Returns step() — model
     forward + one all-gather of the (G_r, 2) logits + one index_select, device work only — and the problem sizes.
     forward_factory(members, xs) -> callable returning the (len(members), 2) logits: the HIP product by default; the CPU dry-run of
-    this very code path (tests/test_parallel_gloo.py, world 2 over gloo) passes the oracle's."""
+    this very code path (tests/test_parallel_gloo.py, world 2 over gloo) passes the oracle's.  full=False skips the side lines
+    (per-batch preparation, new batch every step, training step) that the HIP forward otherwise measures here."""
     import numpy as np
     import torch
     from gnnmp import synth
@@ -245,105 +273,106 @@ def batched_setup(rank, world, dist, G=8192, forward_factory=None, device=None):
                                gnnmp.GlobalPool("mean"), gnnmp.Dense((128, 2), seed=23))
         g.plan(False)
         model(g, g.x)
-        # per-batch constants — outside the timed steps — measured on a SECOND batch object of the same graphs once the library is warm:
-        # the plan of the batched graph and the chain jobs (a training loop pays both once per NEW batch)
-        g2 = gnnmp.batch_arrays([members[i] for i in mine], [xs[i] for i in mine])
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        g2.plan(False)
-        torch.cuda.synchronize(); t1 = time.perf_counter()
-        model(g2, g2.x)
-        torch.cuda.synchronize(); t2 = time.perf_counter()
-        model(g2, g2.x)
-        torch.cuda.synchronize(); t3 = time.perf_counter()
-        batched_setup.prep_ms = {"plan_ms": (t1 - t0) * 1e3, "chain_jobs_ms": ((t2 - t1) - (t3 - t2)) * 1e3,
-                                 "what": "the reference's own way per new batch: MLUtils.batch on the host + upload (not timed here) + "
-                                         "gnnmp_plan_create (sort) + gnnmp_chain_jobs_create (host packing)"}
-        del g2
-        # The loop the reference's example runs (graph_classification_tudataset.jl:70-71, 97-104): a NEW batch every step, here from the
-        # device-resident dataset (gnnmp.GraphDataset / DataLoader: plan by gnnmp_plan_select, features by one gather, wave jobs packed
-        # on the device by gnnmp_chain_jobs_pack — no sort, no host synchronisation).  Every step is a fresh shuffle of the G members.
-        ds = gnnmp.GraphDataset.from_members([members[i] for i in mine], [xs[i] for i in mine])
-        loader = gnnmp.DataLoader(ds, batchsize=len(mine), shuffle=True, seed=7)
+        if full:     # side lines of --full: nothing here is part of the step
+            # per-batch constants — outside the timed steps — measured on a SECOND batch object of the same graphs once the library is warm:
+            # the plan of the batched graph and the chain jobs (a training loop pays both once per NEW batch)
+            g2 = gnnmp.batch_arrays([members[i] for i in mine], [xs[i] for i in mine])
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            g2.plan(False)
+            torch.cuda.synchronize(); t1 = time.perf_counter()
+            model(g2, g2.x)
+            torch.cuda.synchronize(); t2 = time.perf_counter()
+            model(g2, g2.x)
+            torch.cuda.synchronize(); t3 = time.perf_counter()
+            batched_setup.prep_ms = {"plan_ms": (t1 - t0) * 1e3, "chain_jobs_ms": ((t2 - t1) - (t3 - t2)) * 1e3,
+                                     "what": "the reference's own way per new batch: MLUtils.batch on the host + upload (not timed here) + "
+                                             "gnnmp_plan_create (sort) + gnnmp_chain_jobs_create (host packing)"}
+            del g2
+            # The loop the reference's example runs (graph_classification_tudataset.jl:70-71, 97-104): a NEW batch every step, here from the
+            # device-resident dataset (gnnmp.GraphDataset / DataLoader: plan by gnnmp_plan_select, features by one gather, wave jobs packed
+            # on the device by gnnmp_chain_jobs_pack — no sort, no host synchronisation).  Every step is a fresh shuffle of the G members.
+            ds = gnnmp.GraphDataset.from_members([members[i] for i in mine], [xs[i] for i in mine])
+            loader = gnnmp.DataLoader(ds, batchsize=len(mine), shuffle=True, seed=7)
 
-        def epochs(n, run_model):
-            torch.cuda.synchronize(); ta = time.perf_counter()
-            for _ in range(n):
-                for gb in loader:
-                    if run_model:
-                        yb = model(gb, gb.x)
-                    else:
-                        gnnmp.layers.ChainJobs(gb._cache["node_ptr"], gb.num_graphs, gb._cache["member_stats"])
-            torch.cuda.synchronize()
-            return (time.perf_counter() - ta) / n * 1e3
-
-        epochs(5, True)
-        t_new = epochs(50, True)
-        t_prep = epochs(50, False)
-        # the same loop with the loader's prefetch (round 6): batch k + 1 — plan, features, wave jobs — prepared on a side stream beside
-        # batch k's step; same batches, same logits (tests/test_plan_batch.py)
-        loader_single = loader
-        loader = gnnmp.DataLoader(ds, batchsize=len(mine), shuffle=True, seed=7, prefetch=True, prepare=gnnmp.layers.chain_prepare)
-        epochs(5, True)
-        t_new_prefetch = epochs(50, True)
-        loader = loader_single
-
-        def prep_sync(n):          # one batch at a time, synchronised: the latency of one preparation (nothing to overlap with)
-            tot = 0.0
-            for _ in range(n):
-                torch.cuda.synchronize(); ta = time.perf_counter()
-                for gb in loader:
-                    jb = gnnmp.layers.ChainJobs(gb._cache["node_ptr"], gb.num_graphs, gb._cache["member_stats"])
-                torch.cuda.synchronize(); tot += time.perf_counter() - ta
-                del gb, jb
-            return tot / n * 1e3
-        batched_setup.new_batch = {
-            "batched_new_batch_every_step_ms": t_new_prefetch, "batched_new_batch_every_step_ms_single_stream": t_new,
-            "prep_only_ms_pipelined": t_prep, "prep_only_ms_synchronised": prep_sync(20),
-            "what": "per step: shuffle on the host, ONE upload of the permutation (64 KB), gnnmp_plan_select (2 launches), gnnmp_gather_f32 "
-                    "of the features, gnnmp_chain_jobs_pack (1 launch), then the fused chain (2 launches); no host synchronisation in "
-                    "the loop (the host prepares step k + 1 while the device runs step k); the first figure with the preparation of "
-                    "step k + 1 on a side stream beside step k's kernels (DataLoader(prefetch = True)), the second with everything on one stream"}
-        del loader, loader_single, ds
-        # The TRAINING step of the same model on the same batch (the reference example is a training script,
-        # graph_classification_tudataset.jl:97-104): forward layer by layer with stored activations, every pullback a libgnnmp adjoint
-        # kernel (gnnmp/backward.py), torch for the loss and Adam.  There is no fused backward chain: reported, not claimed.
-        try:
-            import torch.nn.functional as F
-            from gnnmp.backward import dense_ad, global_pool_ad, graph_chain_ad, graph_conv_ad
-            c1, c2, poolL, head = model.layers
-            tparams = [c1.weight1, c1.weight2, c1.bias, c2.weight1, c2.weight2, c2.bias, head.weight, head.bias]
-            saved = [p.detach().clone() for p in tparams]
-            for p in tparams:
-                p.requires_grad_(True)
-            opt = torch.optim.Adam(tparams, lr=1e-3, fused=True)
-            Yb = torch.from_numpy(np.random.default_rng(8).integers(0, 2, g.num_graphs)).cuda()
-
-            def train_steps(n, chain=True):
+            def epochs(n, run_model):
                 torch.cuda.synchronize(); ta = time.perf_counter()
                 for _ in range(n):
-                    opt.zero_grad(set_to_none=True)
-                    lg = graph_chain_ad(model, g, g.x) if chain else dense_ad(head, global_pool_ad(poolL, g, graph_conv_ad(c2, g, graph_conv_ad(c1, g, g.x))))
-                    F.cross_entropy(lg, Yb).backward()
-                    opt.step()
+                    for gb in loader:
+                        if run_model:
+                            yb = model(gb, gb.x)
+                        else:
+                            gnnmp.layers.ChainJobs(gb._cache["node_ptr"], gb.num_graphs, gb._cache["member_stats"])
                 torch.cuda.synchronize()
                 return (time.perf_counter() - ta) / n * 1e3
-            train_steps(3)
-            t_train = train_steps(20)
-            train_steps(3, chain=False)
-            t_layers = train_steps(20, chain=False)
-            with torch.no_grad():
-                for p, v in zip(tparams, saved):
-                    p.copy_(v)
-            for p in tparams:
-                p.requires_grad_(False)
-                p.grad = None
-            batched_setup.train = {"train_step_ms": t_train, "train_step_ms_layer_by_layer_adjoints": t_layers,
-                                   "what": "forward (activations stored) + cross-entropy + the chain's scheduled pullback "
-                                           "(gnnmp.backward.graph_chain_ad: pool-grad + relu' in one pass, both weight gradients of a "
-                                           "GraphConv from one read of dz, the x-pullback's sum and relu' in the row kernel's epilogue) "
-                                           "+ Adam on the static batch; bit-identical gradients to the layer-by-layer adjoints"}
-        except Exception as e:      # the side line must not take the bench line with it
-            batched_setup.train = {"error": repr(e)}
+
+            epochs(5, True)
+            t_new = epochs(50, True)
+            t_prep = epochs(50, False)
+            # the same loop with the loader's prefetch (round 6): batch k + 1 — plan, features, wave jobs — prepared on a side stream beside
+            # batch k's step; same batches, same logits (tests/test_plan_batch.py)
+            loader_single = loader
+            loader = gnnmp.DataLoader(ds, batchsize=len(mine), shuffle=True, seed=7, prefetch=True, prepare=gnnmp.layers.chain_prepare)
+            epochs(5, True)
+            t_new_prefetch = epochs(50, True)
+            loader = loader_single
+
+            def prep_sync(n):          # one batch at a time, synchronised: the latency of one preparation (nothing to overlap with)
+                tot = 0.0
+                for _ in range(n):
+                    torch.cuda.synchronize(); ta = time.perf_counter()
+                    for gb in loader:
+                        jb = gnnmp.layers.ChainJobs(gb._cache["node_ptr"], gb.num_graphs, gb._cache["member_stats"])
+                    torch.cuda.synchronize(); tot += time.perf_counter() - ta
+                    del gb, jb
+                return tot / n * 1e3
+            batched_setup.new_batch = {
+                "batched_new_batch_every_step_ms": t_new_prefetch, "batched_new_batch_every_step_ms_single_stream": t_new,
+                "prep_only_ms_pipelined": t_prep, "prep_only_ms_synchronised": prep_sync(20),
+                "what": "per step: shuffle on the host, ONE upload of the permutation (64 KB), gnnmp_plan_select (2 launches), gnnmp_gather_f32 "
+                        "of the features, gnnmp_chain_jobs_pack (1 launch), then the fused chain (2 launches); no host synchronisation in "
+                        "the loop (the host prepares step k + 1 while the device runs step k); the first figure with the preparation of "
+                        "step k + 1 on a side stream beside step k's kernels (DataLoader(prefetch = True)), the second with everything on one stream"}
+            del loader, loader_single, ds
+            # The TRAINING step of the same model on the same batch (the reference example is a training script,
+            # graph_classification_tudataset.jl:97-104): forward layer by layer with stored activations, every pullback a libgnnmp adjoint
+            # kernel (gnnmp/backward.py), torch for the loss and Adam.  There is no fused backward chain: reported, not claimed.
+            try:
+                import torch.nn.functional as F
+                from gnnmp.backward import dense_ad, global_pool_ad, graph_chain_ad, graph_conv_ad
+                c1, c2, poolL, head = model.layers
+                tparams = [c1.weight1, c1.weight2, c1.bias, c2.weight1, c2.weight2, c2.bias, head.weight, head.bias]
+                saved = [p.detach().clone() for p in tparams]
+                for p in tparams:
+                    p.requires_grad_(True)
+                opt = torch.optim.Adam(tparams, lr=1e-3, fused=True)
+                Yb = torch.from_numpy(np.random.default_rng(8).integers(0, 2, g.num_graphs)).cuda()
+
+                def train_steps(n, chain=True):
+                    torch.cuda.synchronize(); ta = time.perf_counter()
+                    for _ in range(n):
+                        opt.zero_grad(set_to_none=True)
+                        lg = graph_chain_ad(model, g, g.x) if chain else dense_ad(head, global_pool_ad(poolL, g, graph_conv_ad(c2, g, graph_conv_ad(c1, g, g.x))))
+                        F.cross_entropy(lg, Yb).backward()
+                        opt.step()
+                    torch.cuda.synchronize()
+                    return (time.perf_counter() - ta) / n * 1e3
+                train_steps(3)
+                t_train = train_steps(20)
+                train_steps(3, chain=False)
+                t_layers = train_steps(20, chain=False)
+                with torch.no_grad():
+                    for p, v in zip(tparams, saved):
+                        p.copy_(v)
+                for p in tparams:
+                    p.requires_grad_(False)
+                    p.grad = None
+                batched_setup.train = {"train_step_ms": t_train, "train_step_ms_layer_by_layer_adjoints": t_layers,
+                                       "what": "forward (activations stored) + cross-entropy + the chain's scheduled pullback "
+                                               "(gnnmp.backward.graph_chain_ad: pool-grad + relu' in one pass, both weight gradients of a "
+                                               "GraphConv from one read of dz, the x-pullback's sum and relu' in the row kernel's epilogue) "
+                                               "+ Adam on the static batch; bit-identical gradients to the layer-by-layer adjoints"}
+            except Exception as e:      # the side line must not take the bench line with it
+                batched_setup.train = {"error": repr(e)}
         forward = lambda: model(g, g.x)                      # noqa: E731
         device = torch.device("cuda", torch.cuda.current_device())
     else:
@@ -363,9 +392,11 @@ def run_batched(args, rank, world, dist, barrier):
     GraphConv(128=>128,relu), GlobalPool(mean), Dense(128=>2)), member graphs sharded by graph across the ranks
     (gnnmp.parallel), one all-gather of the (G_r, 2) logits per step.  Total work is fixed: strong scaling."""
     import torch
-    step, G, n_tot, e_tot = batched_setup(rank, world, dist)
+    step, G, n_tot, e_tot = batched_setup(rank, world, dist, full=args.full)
     dt, out = timed_region(step, args.steps, args.warmup, barrier, dist)
     assert out.shape == (G, 2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     result = {
         "metric": "graphs/sec (fwd) batched graph classification, GraphConv x2 + GlobalPool(mean) + Dense",
         "value": G / (dt / args.steps), "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -429,6 +460,8 @@ def run_rowpart(args, rank, world, dist, barrier):
 
     dt, out = timed_region(step, args.steps, args.warmup, barrier, dist)
     assert out.shape == (N, D)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gcn_conv_2": out})
     Ep = E + N
     result = {
         "metric": "edges/sec (fwd) 2 x GCNConv, ogbn-products-shape, one graph row-partitioned across the GPUs",
@@ -491,15 +524,23 @@ def main():
     ap.add_argument("--workload", default="products", choices=["products", "arxiv", "batched", "rowpart"],
                     help="products (default, the BASELINE.json metric) | arxiv | batched (config 5: 8192 graphs sharded "
                          "by graph across the ranks, one RCCL all-gather of logits per step; strong scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything the headline does not need: roofline and per-kernel times, "
+                         "the CPU baseline, the other configs and side lines (extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all: a fixed seeded sample of "
+                         "rows where an output is larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="also time the GATConv leg of the CPU baseline once at FULL products size (~40 s of one core and ~110 GB of host "
-                         "memory for the reference path's (C,H,E') temporaries; skipped below 256 GiB available)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (other configs, 8d protocol)")
+                    help="with --full: also time the GATConv leg of the CPU baseline once at FULL products size (~40 s of one core and "
+                         "~110 GB of host memory for the reference path's (C,H,E') temporaries; skipped below 256 GiB available)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements (other configs, 8d protocol)")
     ap.add_argument("--no-placement", action="store_true", help="fresh output allocations per layer call instead of gnnmp.placement's persistent, placement-tuned buffers")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ and "MASTER_ADDR" in os.environ
     if args.gpus > 1 and not launched:
@@ -552,7 +593,7 @@ def main():
     x_host = synth.features(N, D, seed=1 + rank)
     x = torch.from_numpy(x_host).cuda()
     sd, td = torch.from_numpy(s).cuda(), torch.from_numpy(t).cuda()
-    keep_host = rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "products"
+    keep_host = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload == "products"
     if not keep_host:
         del s, t, x_host
     torch.cuda.synchronize()
@@ -634,13 +675,14 @@ def main():
         placement_calibration = {"placed_ms_per_step": cal_placed, "plain_ms_per_step": cal_plain,
                                  "timed_region_runs": "placed (arena)" if use_arena else "plain allocations (the arena lost the calibration on this box)"}
 
-    # ---- events around the two candidate dominant kernels (recorded on the launch stream) --------------------
+    # ---- events around the two candidate dominant kernels (recorded on the launch stream; --full only) ---------
     lib = L.load()
-    step()
-    out_p = torch.empty((N, D), dtype=torch.float32, device="cuda")
-    Wx = gnnmp.dense(x, gat.dense_x_weight)
-    a_hc = gat.a_hc               # keep alive: raw pointers below
-    out_g = torch.empty((N, H * C), dtype=torch.float32, device="cuda")
+    if args.full:
+        step()
+        out_p = torch.empty((N, D), dtype=torch.float32, device="cuda")
+        Wx = gnnmp.dense(x, gat.dense_x_weight)
+        a_hc = gat.a_hc               # keep alive: raw pointers below
+        out_g = torch.empty((N, H * C), dtype=torch.float32, device="cuda")
 
     def k_propagate():
         L.check(lib.gnnmp_propagate_slots_f32(plan.handle, L.SUM, L.ptr(x), None, L.ptr(c_slot), L.ptr(cvec),
@@ -660,10 +702,42 @@ def main():
     # HIP events around the step's kernels INSIDE the timed region, on the stream they are launched on (gnnmp._lib.EventProbe: two
     # event records per launch, ~1 us each): roofline.avg_ms below is the in-step duration, the one a rocprofv3 kernel trace of this
     # command shows — not the kernel timed alone back to back (the two differed by 8 %)
-    probe = L.EventProbe()
-    dt, _ = timed_region(step, args.steps, 0, barrier, dist, before=lambda: L.set_probe(probe), after=lambda: L.set_probe(None))
+    # (--full only: a plain run times the step bare)
+    probe = L.EventProbe() if args.full else None
+    dt, out = timed_region(step, args.steps, 0, barrier, dist, before=(lambda: L.set_probe(probe)) if probe else None,
+                           after=(lambda: L.set_probe(None)) if probe else None)
     ms_per_step = dt / args.steps * 1e3
     value = world * 2 * Ep / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gcn_conv": out[0], "gat_conv": out[1]})
+    del out
+    result = {
+        "metric": ("edges/sec (fwd) GCNConv+GATConv, ogbn-products-shape; achieved HBM GB/s vs peak" if args.workload == "products" else
+                   "edges/sec (fwd) GCNConv+GATConv, ogbn-arxiv-shape (BASELINE.json configs 2 + 3; not the headline metric)"),
+        "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}-shape power-law graph N={N} E={E} (+N self loops, E'={Ep}), D={D}: "
+                               f"GCNConv({D}=>{D},relu) fwd + GATConv({D}=>{C},heads={H},relu) fwd per step; "
+                               f"edges counted = 2*E' per GPU",
+                   "parallelism": f"replicas x{world} (independent feature batches, no collective)",
+                   "index": "Int64 1-based COO as held by GNNGraph; plan = dst-sorted CSR (4-byte slots) built once",
+                   "output_buffers": ("input features and layer outputs in the placement arena: every gather kernel's output in a placement class other "
+                                      "than its gathered matrix's (gnnmp/placement.py, csrc/arena.hip); outputs persistent per layer"
+                                      if (not args.no_placement and args.workload == "products" and use_arena) else
+                                      "fresh allocation per call" + ("" if args.no_placement else " (the placement arena lost its calibration against plain allocations on this box: extras.placement.calibration)")),
+                   "arithmetic": "fp32 operands, accumulation and results; aggregation in fp32 in the reference's edge order; the dense "
+                                 "contraction of the GAT layer (dense_x) runs on the bf16 matrix core as an exact 3-plane split of every fp32 "
+                                 "operand (six bf16 MFMAs per product, fp32 accumulate, dropped terms < 2^-21 of a product, truncation "
+                                 "split: a one-signed bias of that size), GCN's W through fp32 MFMA"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     instep = {}
     for name in ("fused_conv", "gat_conv", "dense"):
         ts = sorted(probe.times_ms(name))
@@ -987,28 +1061,8 @@ def main():
                                     "scaling": "strong", "parallelism": f"graph-parallel x{world}: shard by graph, one all-gather of "
                                     f"(G_r, 2) logits per step (gnnmp.parallel.ShardPlan: no host work in the step)"}
 
-    result = {
-        "metric": ("edges/sec (fwd) GCNConv+GATConv, ogbn-products-shape; achieved HBM GB/s vs peak" if args.workload == "products" else
-                   "edges/sec (fwd) GCNConv+GATConv, ogbn-arxiv-shape (BASELINE.json configs 2 + 3; not the headline metric)"),
-        "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload}-shape power-law graph N={N} E={E} (+N self loops, E'={Ep}), D={D}: "
-                               f"GCNConv({D}=>{D},relu) fwd + GATConv({D}=>{C},heads={H},relu) fwd per step; "
-                               f"edges counted = 2*E' per GPU",
-                   "parallelism": f"replicas x{world} (independent feature batches, no collective)",
-                   "index": "Int64 1-based COO as held by GNNGraph; plan = dst-sorted CSR (4-byte slots) built once",
-                   "output_buffers": ("input features and layer outputs in the placement arena: every gather kernel's output in a placement class other "
-                                      "than its gathered matrix's (gnnmp/placement.py, csrc/arena.hip); outputs persistent per layer"
-                                      if (not args.no_placement and args.workload == "products" and use_arena) else
-                                      "fresh allocation per call" + ("" if args.no_placement else " (the placement arena lost its calibration against plain allocations on this box: extras.placement.calibration)")),
-                   "arithmetic": "fp32 operands, accumulation and results; aggregation in fp32 in the reference's edge order; the dense "
-                                 "contraction of the GAT layer (dense_x) runs on the bf16 matrix core as an exact 3-plane split of every fp32 "
-                                 "operand (six bf16 MFMAs per product, fp32 accumulate, dropped terms < 2^-21 of a product, truncation "
-                                 "split: a one-signed bias of that size), GCN's W through fp32 MFMA"},
-        "roofline": roofline,
-        "extras": extras,
-    }
+    result["roofline"] = roofline
+    result["extras"] = extras
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline((s, t, x_host) if keep_host else None, full_gat=args.cpu_baseline_full)

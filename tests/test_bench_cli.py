@@ -48,3 +48,34 @@ def test_byte_models():
         assert doc["products"][k]["hbm_read_bytes"] > 0 and doc["products"][k]["round"] == doc["_round"]
         t, src = bench.traffic_from_profiles("products", k)
         assert t == doc["products"][k]["hbm_read_bytes"] + doc["products"][k]["hbm_write_bytes"] and src["round"] == doc["_round"]
+
+
+def test_full_and_dump_outputs_are_options():
+    r = run("--help")
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_stay_within_64_mb_and_sample_the_same_rows(tmp_path):
+    """--dump-outputs at the products shape: float32 files, at most 64 MB in all, larger outputs cut to a fixed sample of whole rows
+    (the same rows in every run), small ones written whole"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    N = 2449029
+    a, b = torch.randn(N, 100), torch.randn(N, 128, dtype=torch.float64)
+    small = torch.arange(20, dtype=torch.float32).reshape(10, 2)
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), {"gcn_conv": a, "gat_conv": b, "logits": small})
+    files = sorted(os.listdir(tmp_path / "one"))
+    assert files == ["gat_conv.npy", "gcn_conv.npy", "logits.npy"]
+    assert sum(os.path.getsize(tmp_path / "one" / f) for f in files) <= 64_000_000
+    for f in files:
+        x, y = np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f)
+        assert np.array_equal(x, y)
+    ya, yb = np.load(tmp_path / "one" / "gcn_conv.npy"), np.load(tmp_path / "one" / "gat_conv.npy")
+    assert ya.dtype == np.float32 and yb.dtype == np.float64 and ya.shape[1] == 100 and 0 < ya.shape[0] < N
+    ia = np.sort(np.random.default_rng(0).choice(N, ya.shape[0], replace=False))
+    assert np.array_equal(ya, a.numpy()[ia])
+    assert np.array_equal(np.load(tmp_path / "one" / "logits.npy"), small.numpy())

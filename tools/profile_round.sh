@@ -9,7 +9,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-extras"
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-extras"
 run() {  # name, rocprof args..., -- command in $CMD
     local name=$1; shift
     rm -rf "/tmp/prof_$name"
