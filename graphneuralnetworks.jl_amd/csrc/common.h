@@ -95,7 +95,9 @@ enum Knob {
                                // 128: split rows folded by a second kernel (csr_combine / gat_fused_combine) as in rounds 1-4 instead of
                                // by the last chunk to arrive inside the row kernel (round 5, use_fold); 512: dense_wreg from 4 096 rows
                                // on (default 32 768: below that its eight-wave blocks are too few) — so that small tests reach it
-    KNOB_COUNT = 20
+    KNOB_TGCN = 20,            // TGCN recurrence (temporal.hip): 0 = auto (the one-launch kernel for out <= 128), < 0 = the per-step path
+                               // (dense launches + the step pointwise kernels, every out) — read by the host layer (gnnmp/layers_temporal.py)
+    KNOB_COUNT = 21
 };
 int knob(int k);
 int device_cus();   // compute units of the current device, queried once (hipDeviceGetAttribute costs microseconds per call)

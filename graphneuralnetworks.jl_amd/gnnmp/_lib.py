@@ -46,6 +46,7 @@ SYMBOLS = (
     "gnnmp_row_normalize_f32", "gnnmp_row_normalize_grad_f32", "gnnmp_propagate_cg_f32", "gnnmp_gru_pointwise_f32", "gnnmp_propagate_nn_f32", "gnnmp_gmm_weights_f32", "gnnmp_row_sqnorm_normalize_f32", "gnnmp_lstm_pointwise_f32", "gnnmp_rowdot_f32",
     "gnnmp_plan_reset_counters",
     "gnnmp_propagate_f64", "gnnmp_gather_f64", "gnnmp_scatter_f64",
+    "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
@@ -173,6 +174,10 @@ def load():
         "gnnmp_propagate_f64": [vp, i, i, vp, vp, vp, vp, vp, i64, vp],
         "gnnmp_gather_f64": [vp, vp, i, i, i64, vp, i64, vp],
         "gnnmp_scatter_f64": [vp, i, vp, vp, i64, vp],
+        "gnnmp_tgcn_recurrence_f32": [vp, vp, vp, vp, i64, vp, vp, i64, i64, i64, vp],
+        "gnnmp_tgcn_recurrence_grad_f32": [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, vp],
+        "gnnmp_tgcn_step_f32": [i, vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp],
+        "gnnmp_tgcn_step_grad_f32": [i, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp],
     }
     for name, args in sig.items():
         try:
@@ -265,6 +270,7 @@ def set_probe(p):
     _probe = p
 
 
+KNOB_TGCN = 20                            # csrc/common.h: 0 = auto, < 0 = TGCN's per-step path
 KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.cpp g_knobs)
 _knobs = {}
 

@@ -187,7 +187,10 @@ class _DenseFn(torch.autograd.Function):
 
 
 def dense_ad(l, x):
-    """differentiable gnnmp.Dense forward: gradients w.r.t. x, l.weight, l.bias"""
+    """differentiable gnnmp.Dense forward: gradients w.r.t. x, l.weight, l.bias (x [..., in]: leading dimensions flattened to rows)"""
+    if x.dim() != 2:
+        lead = tuple(x.shape[:-1])
+        return _DenseFn.apply(x.reshape(-1, x.shape[-1]), l.weight, l.bias, l.sigma).reshape(*lead, l.weight.shape[0])
     return _DenseFn.apply(x, l.weight, l.bias, l.sigma)
 
 

@@ -40,8 +40,12 @@ def _act_code(sigma):
 
 def dense(x, W, bias=None, sigma=None, x2=None, W2=None, out=None):
     """act(W * x (+ W2 * x2) (+ bias)) on the MFMA kernel.  W: [Dout, Din] (Julia (out, in)); W/W2 may be column
-    slices of a wider matrix (sage_conv's `weight * vcat(xi, m)`): only the last stride must be 1."""
+    slices of a wider matrix (sage_conv's `weight * vcat(xi, m)`): only the last stride must be 1.  Like Flux.Dense, x may have extra
+    leading dimensions ([..., in] -> [..., out], flattened to rows; e.g. a TGCN's [N, T, out])."""
     assert x.dtype == torch.float32 and W.dtype == torch.float32
+    if x.dim() != 2 and x2 is None and out is None:
+        lead = tuple(x.shape[:-1])
+        return dense(x.reshape(-1, x.shape[-1]), W, bias, sigma).reshape(*lead, W.shape[0])
     x = x.contiguous()
     N, D1 = x.shape
     Dout = W.shape[0]

@@ -799,6 +799,39 @@ int gnnmp_dense_grad_w_f32(const float *dz, const float *x, int64_t N, int64_t D
                            float *db, float *workspace, int64_t workspace_floats, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * TGCN's recurrence (GraphNeuralNetworks/src/layers/temporalconv.jl:809-849 TGCNCell, scanned over time by GNNRecurrence :121-135).
+ * The cell's three graph convolutions depend on x_t only, so the caller computes them for all T steps up front and passes the input
+ * halves of the three Dense layers, P[n][t] = (W_z[:, 1:out] conv_z + b_z, W_r[:, 1:out] conv_r + b_r, W_h[:, 1:out] conv_h + b_h),
+ * [N][T][3 out].  What remains per step is node-local (U_g = W_g[:, out+1:2out], the state half of dense_g):
+ *   z = σ(P_z + U_z h), r = σ(P_r + U_r h), h~ = tanh(P_h + U_h (r .* h)), h' = (1 - z) .* h + z .* h~     (:840-849)
+ *   gnnmp_tgcn_recurrence_f32       all T steps in ONE launch, 16 nodes a wave, the state in registers, U in LDS, fp32 MFMA.
+ *                                   U_zr [2 out][out] = (U_z; U_r), U_h [out][out], row-major.  h0: [N][out] (h0_stride = out), one
+ *                                   vector for every node (h0_stride = 0) or NULL (zeros: initialstates).  y [N][T][out]; gates
+ *                                   [N][T][3 out] = (z, r, h~) for the pullback, or NULL.  1 <= out <= 128, else GNNMP_EINVAL.
+ *   gnnmp_tgcn_recurrence_grad_f32  the reverse-time pullback in ONE launch, given dy [N][T][out] and the forward's y / gates / h0:
+ *                                   dP [N][T][3 out] (the pre-activation gate gradients = ΔP), S [N][T][2 out] = (h_{t-1}, r .* h_{t-1})
+ *                                   (nullable: the operands of ΔU_zr = ΔP_zr' h_{t-1}, ΔU_h = ΔP_h' (r .* h_{t-1}) over N T rows, e.g.
+ *                                   gnnmp_dense_grad_w_f32), dh0 [N][out] (nullable).
+ * No atomics: every output element is written by one lane, run-to-run identical.  The per-step halves of the same arithmetic (any out;
+ * the caller runs U's products per step with gnnmp_dense_f32, t = the step, arrays as above, a / drh / part / dah / dzr contiguous):
+ *   gnnmp_tgcn_step_f32       phase 0: z, r = σ(P_zr[t] + a) -> gates[t], hout = r .* h;  a = h U_zr' [N][2D]
+ *                             phase 1: h~ = tanh(P_h[t] + a) -> gates[t], h' -> y[t] and hout;  a = (r .* h) U_h' [N][D]
+ *                             h: the state (row stride ldh; NULL = zeros)
+ *   gnnmp_tgcn_step_grad_f32  phase 0: Δh = dy[t] + carry (nullable); ΔP_z, ΔP_h -> dP[t], dah = ΔP_h, dzr[:, 0:D] = ΔP_z, part = Δh (1 - z)
+ *                             phase 1: drh = ΔP_h U_h; ΔP_r -> dP[t], dzr[:, D:2D]; part += drh .* r; S[t] (nullable)
+ *                             (then carry = part + dzr U_zr for step t - 1) */
+int gnnmp_tgcn_recurrence_f32(const float *P, const float *U_zr, const float *U_h, const float *h0, int64_t h0_stride, float *y,
+                              float *gates, int64_t N, int64_t T, int64_t out, gnnmp_stream_t stream);
+int gnnmp_tgcn_recurrence_grad_f32(const float *dy, const float *y, const float *gates, const float *U_zr, const float *U_h,
+                                   const float *h0, int64_t h0_stride, float *dP, float *S, float *dh0, int64_t N, int64_t T,
+                                   int64_t out, gnnmp_stream_t stream);
+int gnnmp_tgcn_step_f32(int phase, const float *P, const float *a, const float *h, int64_t ldh, float *gates, float *hout, float *y,
+                        int64_t N, int64_t T, int64_t t, int64_t D, gnnmp_stream_t stream);
+int gnnmp_tgcn_step_grad_f32(int phase, const float *dy, const float *carry, const float *gates, const float *h, int64_t ldh,
+                             const float *drh, float *dP, float *dah, float *dzr, float *part, float *S, int64_t N, int64_t T, int64_t t,
+                             int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
  * (GraphNeuralNetworks/perf/bench_gnn.jl:9-10: `B = rand(100, n)`; it asserts isequal(propagate(e_mul_xj, g, +; xj = B, e), B * A)).  The
  * seam's methods and their leaves exist for `double` too — the same plan, the same walk, the same order of operations as the `_f32` entry
