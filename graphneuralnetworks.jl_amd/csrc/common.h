@@ -97,7 +97,9 @@ enum Knob {
                                // on (default 32 768: below that its eight-wave blocks are too few) — so that small tests reach it
     KNOB_TGCN = 20,            // TGCN recurrence (temporal.hip): 0 = auto (the one-launch kernel for out <= 128), < 0 = the per-step path
                                // (dense launches + the step pointwise kernels, every out) — read by the host layer (gnnmp/layers_temporal.py)
-    KNOB_COUNT = 21
+    KNOB_EDGE_DOT_GRAD = 21,   // adjoint of the per-edge dot product (linkpred.hip): 0 = auto (the fused kernel for D <= 256), < 0 = two
+                               // w_mul_xj propagates (plan and transposed plan) plus an add — read by the host (gnnmp/linkpred.py)
+    KNOB_COUNT = 22
 };
 int knob(int k);
 int device_cus();   // compute units of the current device, queried once (hipDeviceGetAttribute costs microseconds per call)

@@ -47,6 +47,7 @@ SYMBOLS = (
     "gnnmp_plan_reset_counters",
     "gnnmp_propagate_f64", "gnnmp_gather_f64", "gnnmp_scatter_f64",
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
+    "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
@@ -178,6 +179,9 @@ def load():
         "gnnmp_tgcn_recurrence_grad_f32": [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, vp],
         "gnnmp_tgcn_step_f32": [i, vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp],
         "gnnmp_tgcn_step_grad_f32": [i, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp],
+        "gnnmp_negative_sample": [vp, vp, i, i, i64, i64, i64, i, i, u64, vp, vp, i64, ctypes.POINTER(i64), vp],
+        "gnnmp_rand_edge_split": [vp, vp, i, i, i64, i, i64, u64, vp, vp, vp, vp, vp],
+        "gnnmp_edge_dot_grad_f32": [vp, vp, vp, vp, vp, vp, vp, i64, vp],
     }
     for name, args in sig.items():
         try:
@@ -271,6 +275,7 @@ def set_probe(p):
 
 
 KNOB_TGCN = 20                            # csrc/common.h: 0 = auto, < 0 = TGCN's per-step path
+KNOB_EDGE_DOT_GRAD = 21                   # csrc/common.h: 0 = auto, < 0 = the edge-dot adjoint as two propagates (gnnmp/linkpred.py)
 KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.cpp g_knobs)
 _knobs = {}
 

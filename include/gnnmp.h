@@ -832,6 +832,48 @@ int gnnmp_tgcn_step_grad_f32(int phase, const float *dy, const float *carry, con
                              int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Link prediction (GraphNeuralNetworks/examples/link_prediction_pubmed.jl).  The reference runs both graph transforms on the CPU
+ * (edge_index copied to the host and back); here they stay on the device.  Random draws are counter based: the same seed gives the
+ * same result, but it is NOT Julia's RNG stream, so parity with the reference is distributional.  Indices keep the input's width and
+ * base.  Integers only at the seam: the reference's Float64 formulas are evaluated inside.
+ *
+ *   gnnmp_negative_sample   negative_sample(g; num_neg_edges, bidirected, max_trials) — GNNGraphs/src/transform.jl:890-929.
+ *                           Positives: g's n_edges edges plus a self loop on every node (E' = n_edges + n_nodes); codes
+ *                           (s-1) n + t, maxid = n^2.  bidirected: num_neg_edges / 2 first.  pneg = 1 - E' / (2 maxid),
+ *                           p = min(1, num_neg / (pneg maxid) * 1.1) (pneg = 0: p = 1; n_nodes = 0: nothing to draw, no edges);
+ *                           p < 0 or num_neg_edges < 0: GNNMP_EINVAL.  Each of up to max_trials trials draws randsubseq(1:maxid, p)
+ *                           (ascending), drops the positives and the codes kept so far, appends the rest; once num_neg codes are kept
+ *                           the list is cut to its first num_neg (the last trial's LOWEST codes) and the trials stop.  Writes the
+ *                           decoded pairs, followed by the swapped pairs when bidirected, to s_out / t_out; *total (host) = edges
+ *                           written, possibly fewer than asked for (as in the reference) when the trials run out.  capacity >=
+ *                           (bidirected ? 2 (num_neg_edges / 2) : num_neg_edges), else GNNMP_EINVAL.  Work and memory
+ *                           O(n_edges + candidates), never O(n^2): the code space is cut into chunks walked by geometric gaps, the
+ *                           positives sorted once (device radix sort).  Synchronisations: 1 (the positives' sort) + 1 per trial (its
+ *                           kept count), + 1 per further trial (the sort of the codes kept so far); the outputs are complete on return.
+ *   gnnmp_rand_edge_split   rand_edge_split(g, frac; bidirected) — GNNGraphs/src/transform.jl:945-968.  ne = bidirected ? n_edges / 2 :
+ *                           n_edges; size1 = round(ne frac) (computed by the caller: round half to even); eids = a uniformly random
+ *                           permutation of 1:ne (radix sort of counter-based keys).  Not bidirected: part 1 = edges eids[1:size1] in
+ *                           permutation order, part 2 the rest.  Bidirected: the edges with s < t, compacted in edge order, are
+ *                           indexed instead, and each part is written as [s; t], [t; s] — s1 / t1 hold 2 size1 entries, s2 / t2
+ *                           2 (ne - size1).  Fewer than ne edges with s < t: GNNMP_EBOUNDS (the reference's BoundsError).
+ *                           Synchronisations: 1 (the permutation's sort) + 1 when bidirected.
+ *   gnnmp_edge_dot_grad_f32 the adjoint of z_k = <xi[t_k], xj[s_k]> (apply_edges(xi_dot_xj, g, xi, xj), GNNlib/src/msgpass.jl:172;
+ *                           DotDecoder, GNNlib/src/layers/basic.jl:1-3) w.r.t. the node features, given dz[n_edges] in original edge
+ *                           order:  dxi[v] = Σ_{k: t_k = v} dz_k xj[s_k]  (walks the plan's row v),  dxj[u] = Σ_{k: s_k = u} dz_k
+ *                           xi[t_k]  (the transposed plan's row u), in edge order, each row summed in registers and written once: no
+ *                           atomics, reruns are bit-identical.  Alias mode, dxi == dxj (requires xi == xj): dx[v] = (in-edge sum) +
+ *                           (out-edge sum), one launch.  Either output may be NULL in split mode.  Plans without added self loops
+ *                           (else GNNMP_EINVAL); D <= 256, else GNNMP_EUNSUPPORTED (compose two w_mul_xj propagates with w = dz).
+ * ---------------------------------------------------------------------------------------------- */
+int gnnmp_negative_sample(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int64_t n_nodes,
+                          int64_t num_neg_edges, int bidirected, int max_trials, uint64_t seed, void *s_out, void *t_out,
+                          int64_t capacity, int64_t *total, gnnmp_stream_t stream);
+int gnnmp_rand_edge_split(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int bidirected, int64_t size1,
+                          uint64_t seed, void *s1, void *t1, void *s2, void *t2, gnnmp_stream_t stream);
+int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_transposed, const float *xi, const float *xj, const float *dz,
+                            float *dxi, float *dxj, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
  * (GraphNeuralNetworks/perf/bench_gnn.jl:9-10: `B = rand(100, n)`; it asserts isequal(propagate(e_mul_xj, g, +; xj = B, e), B * A)).  The
  * seam's methods and their leaves exist for `double` too — the same plan, the same walk, the same order of operations as the `_f32` entry
