@@ -569,7 +569,10 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const 
         return fail(GNNMP_EINVAL, "gat_conv_grad: null pointer");
     const int D = (int)(H * C);
     int vec = pick_vec(D, Wx_src, dWx_src);
-    if (((reinterpret_cast<uintptr_t>(Wx_dst) | reinterpret_cast<uintptr_t>(dout)) & (4 * vec - 1)) != 0) vec = 1;
+    // every array read or written with Vec<VEC> enters the decision (grad2's out / oplus included: an under-aligned one narrows the
+    // lanes like any other array, the header promises alignment for `line` only); dWx_dst is written by a scalar kernel
+    if (((reinterpret_cast<uintptr_t>(Wx_dst) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(outk) |
+          reinterpret_cast<uintptr_t>(oplus)) & (4 * vec - 1)) != 0) vec = 1;
     if ((reinterpret_cast<uintptr_t>(line) & 15) != 0) return fail(GNNMP_EINVAL, "gat_conv_grad: line must be 16-byte aligned");
     while (vec > 1 && (C % vec) != 0) vec >>= 1;
     int lph = (int)(C / vec);
@@ -611,8 +614,6 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const 
     g.bias = bias;
     g.oplus = oplus;
     g.pplus = pplus;
-    if (oplus && ((reinterpret_cast<uintptr_t>(outk) | reinterpret_cast<uintptr_t>(oplus)) & (4 * vec - 1)) != 0)
-        return fail(GNNMP_EINVAL, "gat_conv_grad2: out / oplus not aligned like Wx");
     if (drop_p > 0.0f) {   // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
         if (vec == 4) return launch_gat_bwd<4, 0, true>(g, plan, plan_t, dWx_dst, da, stream);
         if (vec == 2) return launch_gat_bwd<2, 0, true>(g, plan, plan_t, dWx_dst, da, stream);

@@ -728,7 +728,9 @@ static int attn_conv_impl(gnnmp_graph_t *plan, int mode, const float *Q, const f
     if (Q == K && plan->n_src != plan->n_dst) return fail(GNNMP_EINVAL, "attn_conv: bipartite plan needs a separate Q");
     const int D = (int)(H * C);
     int vec = pick_vec(D, K, out);
-    if (((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(V)) & (4 * vec - 1)) != 0) vec = 1;
+    // every array the kernel touches with Vec<VEC> loads / stores enters the decision: K and out above, Q, V and the training forward's
+    // oplus here (bias, stats, pplus and escore are scalar accesses and need none)
+    if (((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(oplus)) & (4 * vec - 1)) != 0) vec = 1;
     while (vec > 1 && (C % vec) != 0) vec >>= 1;
     int lph = (int)(C / vec);
     const int lanes = D / vec;

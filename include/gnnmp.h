@@ -453,7 +453,12 @@ int gnnmp_gat_conv_edge_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
 /* Training forward of the same path: as gnnmp_gat_conv_f32, and additionally saves the neighbourhood-softmax statistics
  * stats[i][h] = (m_i, den_i) — the running maximum of the logits and Σ_j exp(l_ij - m_i) — 8 bytes per destination and
  * head instead of the reference's (H, E') α array that Zygote keeps alive for the pullback.  The feature row must fit one
- * wave (H*C / v lanes <= 64 with v = 4, 2 or 1 floats per lane as C's divisibility allows; GNNMP_EUNSUPPORTED otherwise).
+ * wave (H*C / v lanes <= 64 with v = 4, 2 or 1 floats per lane as C's divisibility AND the alignment of the [.][H*C] arrays allow:
+ * v = 4 needs C % 4 == 0 and every such array of the call 16-byte aligned, v = 2 needs C % 2 == 0 and 8-byte alignment, any float-aligned
+ * pointer runs with v = 1; GNNMP_EUNSUPPORTED otherwise — so a row of more than 64 floats is refused when a pointer is under-aligned
+ * for the v it needs).  The same rule holds for every one-pass attention entry point and pullback below (gnnmp_gat_conv_edge_f32 /
+ * _train_f32 / _drop_f32, gnnmp_attn_conv_f32 / _drop_f32, gnnmp_gat_conv_grad_f32 / _grad2_f32 / _grad_drop_f32, gnnmp_attn_conv_grad_f32 /
+ * _grad_drop_f32: out, oplus, dout and the [.][H*C] gradient arrays count); gnnmp_gat_conv_f32 falls back to the three-pass kernels instead.
  * Head widths whose lane count is a power of two reduce with DPP butterflies; any other width (C = 7 classes, ...) is
  * supported too, summing the head's lanes one by one. */
 int gnnmp_gat_conv_stats_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
@@ -757,7 +762,9 @@ int gnnmp_edge_dot_f32(const float *a_dst, const float *b_src, const void *src, 
                        gnnmp_stream_t stream);
 /* The same per-edge dot products walked in the plan's destination-sorted order (the destination row stays in registers
  * for all of its edges: half the traffic); out[n_edges] is written in ORIGINAL edge order, plan-added self loops
- * produce no output.  D * 4 bytes must fit one wave of 16-byte lanes (D <= 256), else GNNMP_EUNSUPPORTED. */
+ * produce no output.  The row must fit one wave of the widest lanes D and the two feature pointers admit — 16-byte lanes (D <= 256) when
+ * D % 4 == 0 and a_dst, b_src are 16-byte aligned, 8-byte lanes (D <= 128) when D % 2 == 0 and both are 8-byte aligned, 4-byte lanes
+ * (D <= 64) otherwise — else GNNMP_EUNSUPPORTED (gnnmp_edge_dot_f32 takes any D and any float-aligned pointer). */
 int gnnmp_edge_dot_plan_f32(gnnmp_graph_t *plan, const float *a_dst, const float *b_src, float *out,
                             int64_t D, gnnmp_stream_t stream);
 /* Adjoint of propagate(copy_xj, g, max|min) w.r.t. xj on the transposed plan:

@@ -1,0 +1,1781 @@
+"""Helpers of tests/test_abi_memory_contract.py: the header parser, the guarded slab every device array of a call is carved from, and the
+case table over the C ABI (one builder per export: its arguments at a given shape, the role of every array, the float64 / exact reference).
+
+Everything here calls libgnnmp.so through ctypes with raw pointers INTO the slab — never through the Python wrappers, which allocate
+their own outputs.  Plans (opaque, library-owned) are the only objects created outside the slab."""
+import ctypes
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "gnnmp.h")
+
+OK, EINVAL, EBOUNDS, EUNSUPPORTED = 0, -1, -2, -5
+SUM, MEAN, MAX, MIN = 0, 1, 2, 3
+SPLIT_BOUND = 6e-7      # tests/test_dense_split.py: error of the split-bf16 dense core relative to sum_k |w_k x_k|
+RTOL = 1e-5             # the parity tests' bound, relative to the reference's scale
+RTOL64 = 1e-12          # the same for the Float64 entry points (tests/test_float64.py)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# include/gnnmp.h
+# ------------------------------------------------------------------------------------------------------------------------------------
+HANDLE_TYPES = ("gnnmp_graph_t", "gnnmp_arena_t", "gnnmp_chain_jobs_t")
+# pointer parameters the header documents as HOST memory (results of calls that synchronise, host tables of device pointers)
+HOST_PARAMS = {"result", "result_host", "total", "n_new", "cls", "info", "ptr"}
+
+
+def parse_header(path=HEADER):
+    """{export: [(name, is_pointer, is_const, type text)]} for every function the header declares, and its #define constants"""
+    text = open(path).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {m.group(1): m.group(2) for m in re.finditer(r"#define\s+(GNNMP_\w+)\s+(-?\d+)", text)}
+    decls = {}
+    for m in re.finditer(r"\b(?:int64_t|int|void \*|const char \*)\s*(gnnmp_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        name, params = m.group(1), " ".join(m.group(2).split())
+        out = []
+        if params != "void":
+            for p in params.split(","):
+                p = p.strip()
+                pname = re.search(r"(\w+)\s*(?:\[\d*\])?$", p).group(1)
+                is_ptr = "*" in p or "[" in p
+                out.append((pname, is_ptr, p.startswith("const"), p))
+        decls[name] = out
+    return decls, defines
+
+
+def is_host_param(export, pname):
+    return pname in HOST_PARAMS
+
+
+def device_pointer_params(export, decl):
+    """[(name, is_const)] of the parameters that are device arrays (not handles, not the stream, not documented host memory)"""
+    out = []
+    for pname, is_ptr, is_const, text in decl:
+        if not is_ptr or any(h in text for h in HANDLE_TYPES) or is_host_param(export, pname):
+            continue
+        out.append((pname, is_const))
+    return out
+
+
+def must_be_covered(decls, symbols):
+    """the exports the case table owes: in SYMBOLS, take a stream, and write through a device pointer"""
+    need = []
+    for name in symbols:
+        decl = decls.get(name)
+        if not decl or not any("gnnmp_stream_t" in p[3] for p in decl):
+            continue
+        if any(not c for _, c in device_pointer_params(name, decl)):
+            need.append(name)
+    return need
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the slab
+# ------------------------------------------------------------------------------------------------------------------------------------
+# 8 bytes, little endian: the float32 at an even word is the quiet NaN 0x7fc0beef, at an odd word 0x7ff8beef, the float64 at any 8-byte
+# offset 0x7ff8beef7fc0beef (quiet NaN) — fixed payloads; read as integers every word is odd and far outside any index the tests use
+PATTERN = np.frombuffer((0x7ff8beef7fc0beef).to_bytes(8, "little"), np.uint8)
+GUARD_MIN = 4096
+# shifts of an array's start, in bytes: 16-byte aligned but not 128, 8 but not 16, 4 only (taken in whole elements: a shift smaller than
+# the element is skipped for that array)
+SHIFTS = {"a16": 16, "a8": 8, "a4": 4}
+
+
+class Arr:
+    """one device array of a call.  role: 'in' (const T *: must come back bit for bit), 'out' (every element written), 'inout'
+    (initialised by the caller, then compared), 'scratch' (caller-supplied work space: only its guards are checked)"""
+
+    def __init__(self, name, role, data=None, shape=None, dtype=np.float32):
+        assert role in ("in", "out", "inout", "scratch")
+        self.name, self.role = name, role
+        if data is not None:
+            self.data = np.ascontiguousarray(data)
+            self.shape, self.dtype = self.data.shape, self.data.dtype
+        else:
+            assert role in ("out", "scratch")
+            self.data = None
+            self.shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+            self.dtype = np.dtype(dtype)
+        self.dtype = np.dtype(self.dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        self.off = None
+
+
+class E:
+    """what the reference says about one output.  value: the expected array (compared over its own length: `prefix` outputs are longer
+    buffers of which only the first len(value) / prefix elements are owed); tol: 'exact' | 'rel' | 'mag' (mag: |err| <= SPLIT_BOUND * mag,
+    and 'rel'); exact_rows: boolean row mask that must be bit-equal even when tol is 'rel'; pred(got) -> None | message"""
+
+    def __init__(self, value=None, tol="rel", prefix=None, pred=None, exact_rows=None, mag=None, rows=None, scale=0.0):
+        self.value, self.tol, self.prefix, self.pred, self.exact_rows, self.mag = value, tol, prefix, pred, exact_rows, mag
+        # scale: a floor for "the reference's scale" where the reference is a DIFFERENCE of float64 terms that may cancel to exactly zero
+        # (the softmax pullback's α (g - Σ α g) on a one-edge row): rounding error lives on the scale of the terms, and the case states it
+        self.scale = scale                         # a float, or one floor per row of the output
+        self.rows = rows      # boolean row mask: only these rows are compared (every element must still have been written)
+
+
+def _round_up(v, m):
+    return (v + m - 1) // m * m
+
+
+class Slab:
+    def __init__(self, arrs, device="cuda", shifts=None, guard=GUARD_MIN):
+        import torch
+        shifts = shifts or {}
+        guard = _round_up(max(GUARD_MIN, int(guard)), 256)
+        self.arrs = {}
+        off = 0
+        for a in arrs:
+            assert a.name not in self.arrs, a.name
+            sh = int(shifts.get(a.name, 0))
+            assert sh % a.dtype.itemsize == 0, "shifts are whole elements"
+            off += guard
+            a.off = off + sh
+            off = _round_up(a.off + a.nbytes, 256)
+            self.arrs[a.name] = a
+        self.total = off + guard
+        self.pattern = np.tile(PATTERN, self.total // 8)
+        host = self.pattern.copy()
+        for a in arrs:
+            if a.role in ("in", "inout"):
+                host[a.off:a.off + a.nbytes] = a.data.reshape(-1).view(np.uint8)
+        self.before = host
+        self.t = torch.from_numpy(host.copy()).to(device)
+        assert self.t.data_ptr() % 256 == 0 or device == "cpu"
+
+    def ptr(self, name):
+        return ctypes.c_void_p(self.t.data_ptr() + self.arrs[name].off)
+
+    def _where(self, byte):
+        best = None
+        for a in self.arrs.values():
+            if a.off <= byte < a.off + max(a.nbytes, 1):
+                return f"inside {a.role} array '{a.name}' (element {(byte - a.off) // a.dtype.itemsize})"
+            d = byte - (a.off + a.nbytes) if byte >= a.off + a.nbytes else a.off - byte
+            side = "after" if byte >= a.off + a.nbytes else "before"
+            if best is None or d < best[0]:
+                best = (d, f"{d} bytes {side} array '{a.name}'" if side == "before" else f"{d} bytes past the end of array '{a.name}'")
+        return "in a guard band, " + best[1]
+
+    def get(self, after, name):
+        a = self.arrs[name]
+        return after[a.off:a.off + a.nbytes].view(a.dtype).reshape(a.shape)
+
+    def check(self, expected, untouched=False):
+        """problems (list of strings) after the call.  expected: {name: E | ndarray}.  untouched: the call refused with a status —
+        nothing at all may have been written"""
+        after = self.t.cpu().numpy()
+        problems = []
+        owned = np.zeros(self.total, bool)
+        if not untouched:
+            for a in self.arrs.values():
+                if a.role != "in":
+                    owned[a.off:a.off + a.nbytes] = True
+        bad = np.flatnonzero((after != self.before) & ~owned)
+        if bad.size:
+            problems.append(f"{bad.size} stray byte(s) written, first {self._where(int(bad[0]))}"
+                            + (" (the call returned an error status)" if untouched else ""))
+        if untouched:
+            return problems
+        for name, exp in expected.items():
+            a = self.arrs[name]
+            if not isinstance(exp, E):
+                exp = E(exp, tol="rel")
+            got = self.get(after, name)
+            flat = got.reshape(-1)
+            if exp.prefix is not None:
+                flat = flat[:int(exp.prefix)]
+            elif exp.value is not None:
+                v = np.asarray(exp.value)
+                assert v.size == flat.size, f"{name}: reference has {v.size} elements, the buffer {flat.size}"
+            if a.role == "out":
+                u = {1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+                pat = self.pattern[a.off:a.off + flat.size * a.dtype.itemsize].view(u)
+                unwritten = np.flatnonzero(flat.view(u) == pat)
+                if unwritten.size:
+                    problems.append(f"output '{name}': {unwritten.size} of {flat.size} element(s) never written, first at element {int(unwritten[0])}")
+                    continue
+            if exp.pred is not None:
+                msg = exp.pred(flat if exp.prefix is not None else got)
+                if msg:
+                    problems.append(f"output '{name}': {msg}")
+            if exp.value is not None:
+                gv, rv = flat.reshape(np.asarray(exp.value).shape), np.asarray(exp.value)
+                if exp.rows is not None:
+                    gv, rv = gv[exp.rows], rv[exp.rows]
+                msg = compare(gv, rv, exp)
+                if msg:
+                    problems.append(f"output '{name}': {msg}")
+        missing = [a.name for a in self.arrs.values() if a.role in ("out", "inout") and a.name not in expected]
+        assert not missing, f"no reference for {missing}"
+        return problems
+
+
+def compare(got, ref, exp):
+    if got.dtype.kind in "iu" or exp.tol == "exact":
+        same = got == ref.astype(got.dtype)
+        if got.dtype.kind == "f":
+            same = same | ((got != got) & (ref != ref))
+        if not np.all(same):
+            i = int(np.flatnonzero(~same.reshape(-1))[0])
+            return f"{int((~same).sum())} element(s) differ from the reference (exact), first at {i}: {got.reshape(-1)[i]!r} != {ref.reshape(-1)[i]!r}"
+        return None
+    g, r = got.astype(np.float64), ref.astype(np.float64)
+    if exp.exact_rows is not None and exp.exact_rows.any():
+        rows = exp.exact_rows
+        if not np.array_equal(got[rows], ref[rows].astype(got.dtype), equal_nan=True):
+            return "rows the plan does not split are not bit-equal to the oracle"
+    inf = ~np.isfinite(r)
+    if inf.any():
+        if not np.array_equal(g[inf], r[inf], equal_nan=True):
+            return "non-finite entries of the reference (identities of empty rows) differ"
+        g, r = np.where(inf, 0.0, g), np.where(inf, 0.0, r)
+    if not np.all(np.isfinite(g)):
+        return f"{int((~np.isfinite(g)).sum())} non-finite element(s) where the reference is finite"
+    rtol = RTOL64 if got.dtype == np.float64 else RTOL
+    floor = np.asarray(exp.scale, np.float64)
+    if floor.ndim:                                   # one floor per row
+        floor = floor.reshape(floor.shape + (1,) * (r.ndim - floor.ndim))
+    scale = np.maximum(max(float(np.abs(r).max()) if r.size else 0.0, 1e-30), floor)
+    rel = np.abs(g - r) / scale
+    if r.size and float(rel.max()) > rtol:
+        return f"max error {float(np.abs(g - r).max()):.3e} is {float(rel.max()):.2e} of the reference's scale (bound {rtol:g})"
+    if np.linalg.norm(g - r) > rtol * max(np.linalg.norm(r), float(floor.max()) * np.sqrt(max(r.size, 1)), 1e-30):
+        return f"differs from the reference norm-wise by more than {rtol:g}"
+    if exp.tol == "mag":
+        rel = float((np.abs(g - r) / np.maximum(exp.mag, 1e-30)).max()) if r.size else 0.0
+        if rel > SPLIT_BOUND:
+            return f"error {rel:.2e} of sum|w||x| exceeds SPLIT_BOUND {SPLIT_BOUND:g}"
+    return None
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# graphs and plans
+# ------------------------------------------------------------------------------------------------------------------------------------
+class Graph:
+    """COO edge index, 1-based int64 (as the reference holds it)"""
+
+    def __init__(self, name, s, t, n_src, n_dst=None, thr=None, want_split=None):
+        self.name = name
+        self.s, self.t = np.asarray(s, np.int64), np.asarray(t, np.int64)
+        self.n_src, self.n_dst = int(n_src), int(n_src if n_dst is None else n_dst)
+        self.E = len(self.s)
+        self.thr, self.want_split = thr, want_split      # hub graph: the threshold it was built for and the rows that must be split
+
+    @property
+    def n(self):
+        assert self.n_src == self.n_dst
+        return self.n_src
+
+    def order(self):
+        """slot order of the plan: stable sort by destination"""
+        return np.argsort(self.t, kind="stable")
+
+    def indeg(self):
+        return np.bincount(self.t - 1, minlength=self.n_dst)
+
+
+class Pl:
+    """a plan argument: the plan of `g` (transposed: of the reversed edge index), with or without plan-added self loops"""
+
+    def __init__(self, g, T=False, loops=False):
+        self.g, self.T, self.loops = g, T, loops
+
+
+class HostOut:
+    def __init__(self, name, ctype=ctypes.c_int64):
+        self.name, self.ctype = name, ctype
+
+
+STREAM = object()
+
+
+def random_graph(name, n, E, seed, n_dst=None):
+    rng = np.random.default_rng(seed)
+    nd = n if n_dst is None else n_dst
+    return Graph(name, rng.integers(1, n + 1, E), rng.integers(1, nd + 1, E), n, nd)
+
+
+def hub_graph(thr, n=40, seed=5):
+    """isolated destinations first, last and interior; one row exactly at the long-row threshold, one just above, one hub of five
+    times the threshold (it spans chunks); the rest short"""
+    rng = np.random.default_rng(seed)
+    deg = rng.integers(1, 7, n)
+    deg[[0, n // 2, n - 1]] = 0
+    deg[5], deg[6], deg[7] = thr, thr + 1, 5 * thr
+    t = np.repeat(np.arange(1, n + 1), deg)
+    perm = rng.permutation(len(t))
+    t = t[perm]
+    s = rng.integers(1, n + 1, len(t))
+    return Graph("hub", s, t, n, thr=int(thr), want_split=2)
+
+
+class Plans:
+    """plans of one test: created on first use, destroyed together (a new Plans has new plans, hence fresh workspaces)"""
+
+    def __init__(self, lib, stream=None):
+        self.lib, self.live, self.stream = lib, {}, stream
+
+    def get(self, p):
+        import torch
+        key = (id(p.g), p.T, p.loops)
+        if key in self.live:
+            return self.live[key][0]
+        g = p.g
+        s, t, ns, nd = (g.t, g.s, g.n_dst, g.n_src) if p.T else (g.s, g.t, g.n_src, g.n_dst)
+        sd, td = torch.from_numpy(s.copy()).cuda(), torch.from_numpy(t.copy()).cuda()
+        h = ctypes.c_void_p()
+        rc = self.lib.gnnmp_plan_create(ctypes.byref(h), ctypes.c_void_p(sd.data_ptr()), ctypes.c_void_p(td.data_ptr()), 8, 1, ns, nd, len(s),
+                                        1 if p.loops else 0, 1, self.stream)
+        assert rc == OK, self.lib.gnnmp_last_error()
+        if g.thr is not None and not p.T and not p.loops:
+            info = (ctypes.c_int64 * 8)()
+            assert self.lib.gnnmp_plan_info(h, info) == OK
+            assert info[7] == g.thr, f"the hub graph was built for threshold {g.thr}, the plan reports {info[7]}"
+            assert info[5] == g.want_split, f"{info[5]} rows split, {g.want_split} intended"
+        self.live[key] = (h, sd, td)
+        return h
+
+    def close(self):
+        for h, _, _ in self.live.values():
+            self.lib.gnnmp_plan_destroy(h)
+        self.live = {}
+
+
+def plan_threshold(lib, n_edges):
+    """the long-row threshold the library picks for a plan of about n_edges slots (gnnmp_plan_info's info[7])"""
+    import torch
+    s = torch.ones(max(n_edges, 1), dtype=torch.int64, device="cuda")
+    h = ctypes.c_void_p()
+    assert lib.gnnmp_plan_create(ctypes.byref(h), ctypes.c_void_p(s.data_ptr()), ctypes.c_void_p(s.data_ptr()), 8, 1, 1, 1, s.numel(), 0, 0, None) == OK
+    info = (ctypes.c_int64 * 8)()
+    assert lib.gnnmp_plan_info(h, info) == OK
+    lib.gnnmp_plan_destroy(h)
+    return int(info[7])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# a case and its run
+# ------------------------------------------------------------------------------------------------------------------------------------
+class Case:
+    def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None):
+        self.export, self.sid, self.args, self.ref, self.guard, self.status = export, sid, args, ref, guard, status
+        self.knobs = knobs or {}                   # gnnmp_tune settings for the call (reset to 0 after it)
+        self.align_status = align_status or {}     # {array name: status the header documents for an under-aligned pointer}
+        self.arrs = [a for a in args if isinstance(a, Arr)]
+        self.uses_plan = any(isinstance(a, Pl) for a in args)
+
+
+def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):
+    """one call with every array inside a fresh slab.  Returns (status, slab, host results)"""
+    import torch
+    slab = Slab(case.arrs, device, shifts, case.guard)
+    host, cargs = {}, []
+    for a in case.args:
+        if isinstance(a, Arr):
+            cargs.append(slab.ptr(a.name))
+        elif isinstance(a, Pl):
+            cargs.append(plans.get(a))
+        elif isinstance(a, HostOut):
+            v = a.ctype(-12345)
+            host[a.name] = v
+            cargs.append(ctypes.byref(v))
+        elif a is STREAM:
+            cargs.append(None if stream is None else ctypes.c_void_p(stream.cuda_stream))
+        else:
+            cargs.append(a)
+    if stream is not None:
+        torch.cuda.synchronize()       # the default stream is idle while the side stream works
+    for k, v in case.knobs.items():
+        assert lib.gnnmp_tune(k, v) == OK
+    try:
+        rc = getattr(lib, case.export)(*cargs)
+        torch.cuda.synchronize()
+    finally:
+        for k in case.knobs:
+            lib.gnnmp_tune(k, 0)
+    return rc, slab, {k: v.value for k, v in host.items()}
+
+
+def verify(case, rc, slab, host):
+    """problems of one finished call against the case's reference"""
+    if rc != case.status:
+        return [f"{case.export} returned status {rc}, expected {case.status}"]
+    if rc != OK:
+        return slab.check({}, untouched=True)
+    return slab.check(case.ref(host))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the case table
+# ------------------------------------------------------------------------------------------------------------------------------------
+import zlib
+
+DS = (1, 2, 3, 4, 6, 7, 100, 127, 128, 129, 260)      # every vector decision and tail
+IDX = ((8, 1), (4, 1), (8, 0), (4, 0))                   # (idx_bytes, index_base)
+f32, f64 = np.float32, np.float64
+
+
+def rng_of(*key):
+    return np.random.default_rng(zlib.crc32(repr(key).encode()))
+
+
+def F(rng, *shape, dtype=f32):
+    return rng.uniform(-1.0, 1.0, shape).astype(dtype)
+
+
+def IX(idx1, ib, base):
+    """a 1-based index array in the width and base of the call"""
+    return (np.asarray(idx1, np.int64) - 1 + base).astype(np.int64 if ib == 8 else np.int32)
+
+
+def seg_sum(idx0, vals, n):
+    out = np.zeros((n,) + vals.shape[1:], f64)
+    np.add.at(out, idx0, vals)
+    return out
+
+
+def sigmoid(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
+def act64(code, x):
+    if code == 0:
+        return x
+    if code == 1:
+        return np.maximum(x, 0.0)
+    if code == 2:
+        return np.log1p(np.exp(-np.abs(x))) + np.maximum(x, 0.0)
+    if code == 3:
+        return np.tanh(x)
+    return x * sigmoid(x)
+
+
+class Ctx:
+    """the graphs every plan-taking case runs on.  thr: the plan's long-row threshold (read from the library on the GPU; the header's
+    GNNMP_MIN_LONG_ROW for the CPU dry run of the table)"""
+
+    def __init__(self, thr):
+        self.thr = int(thr)
+        self.hub = hub_graph(self.thr)
+        self.e0 = Graph("edgeless", [], [], 5)
+        self.one = Graph("one", [1, 1], [1, 1], 1)
+        self.r31 = random_graph("n31", 31, 90, 1)
+        self.r33 = random_graph("n33", 33, 100, 2)
+        self.r300 = random_graph("n300", 300, 900, 3)
+        self.cache = {}                                 # graphs a builder makes for itself (plans are keyed on the Graph object)
+
+    def graph_shapes(self, Ds=DS, small=(3, 128), align=(3, 6, 128), ws=(4,)):
+        """(graph, D, tags): every width on the hub graph, two widths on the others"""
+        first = True
+        for D in Ds:
+            tags = set()
+            if D in align:
+                tags.add("align")
+            if D in ws:
+                tags.add("ws")
+            if first:
+                tags.add("side")
+                first = False
+            yield self.hub, D, tags
+        for g in (self.e0, self.one, self.r31, self.r33, self.r300):
+            for D in small:
+                if D in Ds:
+                    yield g, D, set()
+
+    def short_rows(self, g, loops=False):
+        return (g.indeg() + (1 if loops else 0)) <= self.thr
+
+
+def row_shapes(Ds=DS, small=(3, 128), align=(3, 6, 128)):
+    first = True
+    for D in Ds:
+        tags = {"align"} if D in align else set()
+        if first:
+            tags.add("side")
+            first = False
+        yield 33, D, tags
+    for N in (1, 31, 300):
+        for D in small:
+            if D in Ds:
+                yield N, D, set()
+
+
+def mk(export, sid, tags, args, ref, **kw):
+    c = Case(export, sid, args, ref, **kw)
+    c.tags = set(tags)
+    return c
+
+
+def orc():
+    from oracle import oracle as o
+    o.build()
+    return o
+
+
+TABLE = {}
+
+
+def cases_of(export):
+    def deco(fn):
+        TABLE[export] = fn
+        return fn
+    return deco
+
+
+# ---- leaves ----------------------------------------------------------------------------------------------------------------------
+def _gather(export, dt):
+    def build(ctx):
+        k = 0
+        for K, D, tags in row_shapes():
+            for ib, base in (IDX if D == 3 and K == 33 else (IDX[k % 4],)):
+                k += 1
+                r = rng_of(export, K, D, ib, base)
+                n = 50
+                x = F(r, n, D, dtype=dt)
+                idx1 = r.integers(1, n + 1, K)
+                ref = lambda host, x=x, idx1=idx1: {"out": E(orc().gather(x, idx1), "exact")}
+                yield mk(export, f"K{K}_D{D}_i{ib}b{base}", tags if (ib, base) == IDX[(k - 1) % 4] else (),
+                         [Arr("x", "in", x), Arr("idx", "in", IX(idx1, ib, base)), ib, base, K, Arr("out", "out", shape=(K, D), dtype=dt), D, STREAM], ref)
+    return build
+
+
+TABLE["gnnmp_gather_f32"] = _gather("gnnmp_gather_f32", f32)
+TABLE["gnnmp_gather_f64"] = _gather("gnnmp_gather_f64", f64)
+
+
+@cases_of("gnnmp_edge_sub_f32")
+def _(ctx):
+    for k, (K, D, tags) in enumerate(row_shapes()):
+        ib, base = IDX[k % 4]
+        r = rng_of("edge_sub", K, D)
+        n = 40
+        xi, xj = F(r, n, D), F(r, n, D)
+        s1, t1 = r.integers(1, n + 1, K), r.integers(1, n + 1, K)
+        flag = k % 2
+        d = xi.astype(f64)[t1 - 1] - xj.astype(f64)[s1 - 1]
+        ref = lambda host, d=d, flag=flag: {"out": -d if flag else d}
+        yield mk("gnnmp_edge_sub_f32", f"K{K}_D{D}_f{flag}", tags,
+                 [Arr("xi", "in", xi), Arr("xj", "in", xj), Arr("s", "in", IX(s1, ib, base)), Arr("t", "in", IX(t1, ib, base)), ib, base, K, flag,
+                  Arr("out", "out", shape=(K, D)), D, STREAM], ref)
+
+
+def _scatter(export, dt):
+    def build(ctx):
+        for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+            aggr = k % 4
+            r = rng_of(export, g.name, D)
+            m = F(r, g.E, D, dtype=dt)
+            def ref(host, g=g, m=m, aggr=aggr):
+                v = orc().scatter(aggr, m, g.t, g.n_dst)
+                return {"out": E(v, "rel" if aggr in (SUM, MEAN) else "exact", exact_rows=ctx.short_rows(g))}
+            yield mk(export, f"{g.name}_D{D}_a{aggr}", tags, [Pl(g), aggr, Arr("m", "in", m), Arr("out", "out", shape=(g.n_dst, D), dtype=dt), D, STREAM], ref)
+    return build
+
+
+TABLE["gnnmp_scatter_f32"] = _scatter("gnnmp_scatter_f32", f32)
+TABLE["gnnmp_scatter_f64"] = _scatter("gnnmp_scatter_f64", f64)
+
+
+@cases_of("gnnmp_scatter_atomic_f32")
+def _(ctx):
+    for k, (K, D, tags) in enumerate(row_shapes()):
+        ib, base = IDX[k % 4]
+        aggr = (SUM, MAX, MIN)[k % 3]
+        r = rng_of("scatter_atomic", K, D)
+        n = 7
+        m = F(r, K, D)
+        idx1 = r.integers(1, n + 1, K)
+        init = np.full((n, D), {SUM: 0.0, MAX: -np.inf, MIN: np.inf}[aggr], f32)
+        def ref(host, m=m, idx1=idx1, aggr=aggr, init=init, n=n):
+            out = init.astype(f64)
+            fn = {SUM: np.add, MAX: np.maximum, MIN: np.minimum}[aggr]
+            fn.at(out, idx1 - 1, m.astype(f64))
+            return {"out": out}
+        yield mk("gnnmp_scatter_atomic_f32", f"K{K}_D{D}_a{aggr}", tags,
+                 [aggr, Arr("m", "in", m), Arr("idx", "in", IX(idx1, ib, base)), ib, base, K, Arr("out", "inout", init), D, STREAM], ref)
+
+
+@cases_of("gnnmp_edge_dot_f32")
+def _(ctx):
+    for k, (K, D, tags) in enumerate(row_shapes()):
+        ib, base = IDX[k % 4]
+        r = rng_of("edge_dot", K, D)
+        n = 40
+        a, b = F(r, n, D), F(r, n, D)
+        s1, t1 = r.integers(1, n + 1, K), r.integers(1, n + 1, K)
+        v = (a.astype(f64)[t1 - 1] * b.astype(f64)[s1 - 1]).sum(1)
+        yield mk("gnnmp_edge_dot_f32", f"K{K}_D{D}", tags,
+                 [Arr("a_dst", "in", a), Arr("b_src", "in", b), Arr("src", "in", IX(s1, ib, base)), Arr("dst", "in", IX(t1, ib, base)), ib, base, K, D,
+                  Arr("out", "out", shape=(K,)), STREAM], lambda host, v=v: {"out": v})
+
+
+@cases_of("gnnmp_edge_dot_plan_f32")
+def _(ctx):
+    for g, D, tags in ctx.graph_shapes():
+        r = rng_of("edge_dot_plan", g.name, D)
+        a, b = F(r, g.n_dst, D), F(r, g.n_src, D)
+        v = (a.astype(f64)[g.t - 1] * b.astype(f64)[g.s - 1]).sum(1)
+        yield mk("gnnmp_edge_dot_plan_f32", f"{g.name}_D{D}", tags,
+                 [Pl(g), Arr("a_dst", "in", a), Arr("b_src", "in", b), Arr("out", "out", shape=(g.E,)), D, STREAM], lambda host, v=v: {"out": v},
+                 # the header: the row must fit one wave at the widest lane D and the two pointers admit, else GNNMP_EUNSUPPORTED
+                 status=EUNSUPPORTED if g.E and -(-D // (4 if D % 4 == 0 else 2 if D % 2 == 0 else 1)) > 64 else OK,
+                 align_status={"a_dst": EUNSUPPORTED, "b_src": EUNSUPPORTED})
+
+
+@cases_of("gnnmp_edge_dot_grad_f32")
+def _(ctx):
+    for g, D, tags in ctx.graph_shapes():
+        r = rng_of("edge_dot_grad", g.name, D)
+        xi, xj, dz = F(r, g.n, D), F(r, g.n, D), F(r, g.E)
+        def ref(host, g=g, xi=xi, xj=xj, dz=dz):
+            z = dz.astype(f64)[:, None]
+            return {"dxi": seg_sum(g.t - 1, z * xj.astype(f64)[g.s - 1], g.n), "dxj": seg_sum(g.s - 1, z * xi.astype(f64)[g.t - 1], g.n)}
+        yield mk("gnnmp_edge_dot_grad_f32", f"{g.name}_D{D}", tags,
+                 [Pl(g), Pl(g, T=True), Arr("xi", "in", xi), Arr("xj", "in", xj), Arr("dz", "in", dz), Arr("dxi", "out", shape=(g.n, D)),
+                  Arr("dxj", "out", shape=(g.n, D)), D, STREAM], ref, status=EUNSUPPORTED if D > 256 else OK)
+
+
+# ---- propagate -------------------------------------------------------------------------------------------------------------------
+def _prop_ref(ctx, g, aggr, x, w, ss, sd):
+    """the reference's materialised sequence xj .* cout' -> propagate -> x .* cin' (float32 oracle, bit-exact on unsplit rows)"""
+    o = orc()
+    xs = o.scale_rows(x, ss) if ss is not None and x.dtype == f32 else (x if ss is None else x * ss[:, None])
+    y = o.propagate(aggr, g.s, g.t, g.n_src, xs, w, n_dst=g.n_dst)
+    if sd is not None:
+        y = o.scale_rows(y, sd) if y.dtype == f32 else y * sd[:, None]
+    # max / min: every bit on every row, split rows included (tests/test_gpu_parity.py, tests/test_float64.py); + / mean: every bit on the
+    # rows the plan does not split, the parity bound on the split ones
+    return E(y, "exact" if aggr in (MAX, MIN) else "rel", exact_rows=ctx.short_rows(g))
+
+
+def _propagate(export, dt):
+    def build(ctx):
+        for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+            msg, aggr, scaled = ((0, SUM, False), (1, SUM, True), (0, MAX, False), (0, MEAN, False), (1, MIN, False), (0, SUM, True))[k % 6]
+            r = rng_of(export, g.name, D)
+            x = F(r, g.n_src, D, dtype=dt)
+            w = F(r, g.E, dtype=dt) if msg else None
+            ss = (0.5 + r.random(g.n_src)).astype(dt) if scaled else None
+            sd = (0.5 + r.random(g.n_dst)).astype(dt) if scaled else None
+            ref = lambda host, g=g, aggr=aggr, x=x, w=w, ss=ss, sd=sd: {"out": _prop_ref(ctx, g, aggr, x, w, ss, sd)}
+            yield mk(export, f"{g.name}_D{D}_m{msg}a{aggr}s{int(scaled)}", tags,
+                     [Pl(g), msg, aggr, Arr("xj", "in", x), Arr("w", "in", w) if msg else None, Arr("scale_src", "in", ss) if scaled else None,
+                      Arr("scale_dst", "in", sd) if scaled else None, Arr("out", "out", shape=(g.n_dst, D), dtype=dt), D, STREAM], ref)
+    return build
+
+
+TABLE["gnnmp_propagate_f32"] = _propagate("gnnmp_propagate_f32", f32)
+TABLE["gnnmp_propagate_f64"] = _propagate("gnnmp_propagate_f64", f64)
+
+
+def _slots(export, with_act):
+    def build(ctx):
+        for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+            aggr = (SUM, MEAN, MAX)[k % 3]
+            scaled = aggr == SUM
+            r = rng_of(export, g.name, D)
+            x, w = F(r, g.n_src, D), F(r, g.E)
+            ss = (0.5 + r.random(g.n_src)).astype(f32) if scaled else None
+            sd = (0.5 + r.random(g.n_dst)).astype(f32) if scaled else None
+            order = g.order()
+            w_slot = w[order]
+            ss_slot = ss[g.s[order] - 1] if scaled else None
+            bias = F(r, D) if with_act and k % 2 == 0 else None
+            act = k % 2 if with_act else 0
+            def ref(host, g=g, aggr=aggr, x=x, w=w, ss=ss, sd=sd, bias=bias, act=act):
+                e = _prop_ref(ctx, g, aggr, x, w, ss, sd)
+                if with_act:
+                    v = e.value if bias is None else (e.value + bias[None, :]).astype(f32)
+                    e.value = np.maximum(v, 0) if act else v
+                return {"out": e}
+            args = [Pl(g), aggr, Arr("xj", "in", x), Arr("w_slot", "in", w_slot), Arr("ss_slot", "in", ss_slot) if scaled else None,
+                    Arr("scale_dst", "in", sd) if scaled else None]
+            if with_act:
+                args += [Arr("bias", "in", bias) if bias is not None else None, act]
+            yield mk(export, f"{g.name}_D{D}_a{aggr}", tags, args + [Arr("out", "out", shape=(g.n_dst, D)), D, STREAM], ref)
+    return build
+
+
+TABLE["gnnmp_propagate_slots_f32"] = _slots("gnnmp_propagate_slots_f32", False)
+TABLE["gnnmp_propagate_slots_act_f32"] = _slots("gnnmp_propagate_slots_act_f32", True)
+
+
+@cases_of("gnnmp_plan_slot_gather_f32")
+def _(ctx):
+    for k, g in enumerate((ctx.hub, ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300)):
+        for by in (0, 1):
+            r = rng_of("slot_gather", g.name, by)
+            v = F(r, g.E if by else g.n_src)
+            order = g.order()
+            val = v[order] if by else v[g.s[order] - 1]
+            yield mk("gnnmp_plan_slot_gather_f32", f"{g.name}_by{by}", {"align", "ws"} | ({"side"} if k == 0 and by == 0 else set()) if g is ctx.hub else (),
+                     [Pl(g), by, Arr("v", "in", v), Arr("out_slot", "out", shape=(g.E,)), STREAM], lambda host, val=val: {"out_slot": E(val, "exact")})
+
+
+@cases_of("gnnmp_propagate_emul_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+        aggr = (SUM, MEAN, MAX, MIN)[k % 4]
+        r = rng_of("emul", g.name, D)
+        x, e = F(r, g.n_src, D), F(r, g.E, D)
+        ref = lambda host, g=g, aggr=aggr, x=x, e=e: {"out": orc().scatter(aggr, e.astype(f64) * x.astype(f64)[g.s - 1], g.t, g.n_dst)}
+        yield mk("gnnmp_propagate_emul_f32", f"{g.name}_D{D}_a{aggr}", tags,
+                 [Pl(g), aggr, Arr("xj", "in", x), Arr("e", "in", e), Arr("out", "out", shape=(g.n_dst, D)), D, STREAM], ref)
+
+
+@cases_of("gnnmp_propagate_gated_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+        aggr = (SUM, MEAN, MAX)[k % 3]
+        r = rng_of("gated", g.name, D)
+        gi, bv = F(r, g.n_dst, D), F(r, g.n_src, 2 * D)
+        def ref(host, g=g, aggr=aggr, gi=gi, bv=bv, D=D):
+            b = bv.astype(f64)[g.s - 1]
+            return {"out": orc().scatter(aggr, sigmoid(gi.astype(f64)[g.t - 1] + b[:, :D]) * b[:, D:], g.t, g.n_dst)}
+        yield mk("gnnmp_propagate_gated_f32", f"{g.name}_D{D}_a{aggr}", tags,
+                 [Pl(g), aggr, Arr("gate_i", "in", gi), Arr("bv_j", "in", bv), Arr("out", "out", shape=(g.n_dst, D)), D, STREAM], ref)
+
+
+@cases_of("gnnmp_propagate_cg_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+        act = (2, 0, 1, 3)[k % 4]
+        has_e = k % 2 == 0
+        r = rng_of("cg", g.name, D)
+        fi, fj = F(r, g.n_dst, 2 * D), F(r, g.n_src, 2 * D)
+        fe = F(r, g.E, 2 * D) if has_e else None
+        def ref(host, g=g, fi=fi, fj=fj, fe=fe, act=act, D=D):
+            z = fi.astype(f64)[g.t - 1] + fj.astype(f64)[g.s - 1] + (fe.astype(f64) if fe is not None else 0.0)
+            return {"out": seg_sum(g.t - 1, sigmoid(z[:, :D]) * act64(act, z[:, D:]), g.n_dst)}
+        yield mk("gnnmp_propagate_cg_f32", f"{g.name}_D{D}_act{act}", tags,
+                 [Pl(g), Arr("fs_i", "in", fi), Arr("fs_j", "in", fj), Arr("fs_e", "in", fe) if has_e else None, act,
+                  Arr("out", "out", shape=(g.n_dst, D)), D, STREAM], ref)
+
+
+@cases_of("gnnmp_propagate_nn_f32")
+def _(ctx):
+    shapes = [(ctx.hub, 3, 5, {"align", "side", "ws"}), (ctx.hub, 4, 4, {"align"}), (ctx.hub, 7, 2, ()), (ctx.hub, 1, 1, ()), (ctx.hub, 6, 33, {"align"}),
+              (ctx.e0, 3, 4, ()), (ctx.one, 4, 3, ()), (ctx.r31, 2, 6, ()), (ctx.r33, 5, 3, ()), (ctx.r300, 4, 8, ())]
+    for k, (g, Din, Dout, tags) in enumerate(shapes):
+        aggr = (SUM, MEAN, MAX)[k % 3]
+        r = rng_of("nn", g.name, Din, Dout)
+        x, we = F(r, g.n_src, Din), F(r, g.E, Dout * Din)
+        def ref(host, g=g, x=x, we=we, Din=Din, Dout=Dout, aggr=aggr):
+            W = we.astype(f64).reshape(g.E, Din, Dout)               # element (o, c) of edge k at we[k][o + Dout * c]
+            msg = np.einsum("kco,kc->ko", W, x.astype(f64)[g.s - 1])
+            return {"out": orc().scatter(aggr, msg, g.t, g.n_dst)}
+        yield mk("gnnmp_propagate_nn_f32", f"{g.name}_{Din}x{Dout}_a{aggr}", tags,
+                 [Pl(g), aggr, Arr("xj", "in", x), Arr("we", "in", we), Arr("out", "out", shape=(g.n_dst, Dout)), Din, Dout, STREAM], ref)
+
+
+@cases_of("gnnmp_propagate_add_mask_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+        aggr = (SUM, MEAN)[k % 2]
+        r = rng_of("add_mask", g.name, D)
+        x, add, my = F(r, g.n_src, D), F(r, g.n_dst, D), F(r, g.n_dst, D)
+        sd = (1.0 / np.maximum(g.indeg(), 1)).astype(f32) if aggr == MEAN else None
+        has_add, has_mask = k % 3 != 1, k % 3 != 2
+        def ref(host, g=g, x=x, add=add, my=my, sd=sd, has_add=has_add, has_mask=has_mask):
+            y = seg_sum(g.t - 1, x.astype(f64)[g.s - 1], g.n_dst)
+            if sd is not None:
+                y = y * sd.astype(f64)[:, None]
+            if has_add:
+                y = y + add.astype(f64)
+            return {"out": np.where(my > 0, y, 0.0) if has_mask else y}
+        # MEAN is `+` with scale_dst = 1 / count, as the header describes it
+        yield mk("gnnmp_propagate_add_mask_f32", f"{g.name}_D{D}_a{aggr}", tags,
+                 [Pl(g), SUM, Arr("xj", "in", x), Arr("scale_dst", "in", sd) if sd is not None else None, Arr("addend", "in", add) if has_add else None,
+                  Arr("mask_y", "in", my) if has_mask else None, Arr("out", "out", shape=(g.n_dst, D)), D, STREAM], ref)
+
+
+@cases_of("gnnmp_propagate_maxmin_grad_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes()):
+        aggr = (MAX, MIN)[k % 2]
+        r = rng_of("maxmin_grad", g.name, D)
+        x, dy = np.round(F(r, g.n, D) * 4) / 4, F(r, g.n, D)          # quarter steps: ties happen, and all of them receive Δ
+        x = x.astype(f32)
+        y = orc().propagate(aggr, g.s, g.t, g.n, x)
+        def ref(host, g=g, x=x, y=y, dy=dy):
+            hit = x[g.s - 1] == y[g.t - 1]
+            return {"dx": seg_sum(g.s - 1, np.where(hit, dy.astype(f64)[g.t - 1], 0.0), g.n)}
+        yield mk("gnnmp_propagate_maxmin_grad_f32", f"{g.name}_D{D}_a{aggr}", tags,
+                 [Pl(g, T=True), Arr("x", "in", x), Arr("y", "in", y), Arr("dy", "in", dy), Arr("dx", "out", shape=(g.n, D)), D, STREAM], ref)
+
+
+@cases_of("gnnmp_degree_f32")
+def _(ctx):
+    for k, g in enumerate((ctx.hub, ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300)):
+        for weighted in (0, 1):
+            w = F(rng_of("degree", g.name), g.E) if weighted else None
+            def ref(host, g=g, w=w):
+                return {"deg": E(orc().degree(g.t, g.n_dst, w), "exact" if w is None else "rel", exact_rows=None if w is None else ctx.short_rows(g))}
+            yield mk("gnnmp_degree_f32", f"{g.name}_w{weighted}", ({"align", "ws"} | ({"side"} if not weighted else set())) if g is ctx.hub else (),
+                     [Pl(g), Arr("w", "in", w) if weighted else None, Arr("deg", "out", shape=(g.n_dst,)), STREAM], ref)
+
+
+# ---- pointwise -------------------------------------------------------------------------------------------------------------------
+NS = ((1, ()), (3, {"align"}), (6, {"align"}), (31, ()), (33, ()), (128, {"align", "side"}), (1025, ()), (70001, ()))
+
+
+@cases_of("gnnmp_inv_sqrt_f32")
+def _(ctx):
+    for n, tags in NS:
+        d = (1.0 + rng_of("inv_sqrt", n).integers(0, 50, n)).astype(f32)
+        yield mk("gnnmp_inv_sqrt_f32", f"n{n}", tags, [Arr("deg", "in", d), Arr("out", "out", shape=(n,)), n, STREAM],
+                 lambda host, d=d: {"out": E(orc().inv_sqrt(d), "exact")})
+
+
+@cases_of("gnnmp_add_f32")
+def _(ctx):
+    for n, tags in NS:
+        r = rng_of("add", n)
+        a, b = F(r, n), F(r, n)
+        yield mk("gnnmp_add_f32", f"n{n}", tags, [Arr("a", "in", a), Arr("b", "in", b), Arr("out", "out", shape=(n,)), n, STREAM],
+                 lambda host, a=a, b=b: {"out": a.astype(f64) + b})
+
+
+@cases_of("gnnmp_axpy_f32")
+def _(ctx):
+    for n, tags in NS:
+        r = rng_of("axpy", n)
+        x, y = F(r, n), F(r, n)
+        yield mk("gnnmp_axpy_f32", f"n{n}", tags, [1.25, Arr("x", "in", x), Arr("y", "in", y), Arr("out", "out", shape=(n,)), n, STREAM],
+                 lambda host, x=x, y=y: {"out": 1.25 * x.astype(f64) + y})
+
+
+@cases_of("gnnmp_act_grad_f32")
+def _(ctx):
+    for k, (n, tags) in enumerate(NS):
+        r = rng_of("act_grad", n)
+        dy, y = F(r, n), F(r, n)
+        act = k % 2
+        yield mk("gnnmp_act_grad_f32", f"n{n}_act{act}", tags, [Arr("dy", "in", dy), Arr("y", "in", y), act, Arr("dz", "out", shape=(n,)), n, STREAM],
+                 lambda host, dy=dy, y=y, act=act: {"dz": E(np.where(y > 0, dy, 0).astype(f32) if act else dy, "exact")})
+
+
+@cases_of("gnnmp_mul_rows_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        Da = 1 if k % 2 == 0 else D
+        r = rng_of("mul_rows", N, D)
+        a, b = F(r, N, Da), F(r, N, D)
+        yield mk("gnnmp_mul_rows_f32", f"N{N}_D{D}_Da{Da}", tags, [Arr("a", "in", a), Da, Arr("b", "in", b), Arr("out", "out", shape=(N, D)), N, D, STREAM],
+                 lambda host, a=a, b=b: {"out": a.astype(f64) * b})
+
+
+@cases_of("gnnmp_bias_act_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        act = k % 5
+        r = rng_of("bias_act", N, D)
+        x = F(r, N, D)
+        bias = F(r, D) if k % 3 else None
+        yield mk("gnnmp_bias_act_f32", f"N{N}_D{D}_act{act}", tags,
+                 [Arr("x", "in", x), Arr("bias", "in", bias) if bias is not None else None, act, Arr("out", "out", shape=(N, D)), N, D, STREAM],
+                 lambda host, x=x, bias=bias, act=act: {"out": act64(act, x.astype(f64) + (0.0 if bias is None else bias.astype(f64)))})
+
+
+@cases_of("gnnmp_rowdot_f32")
+def _(ctx):
+    for N, D, tags in row_shapes():
+        r = rng_of("rowdot", N, D)
+        a, b = F(r, N, D), F(r, N, D)
+        yield mk("gnnmp_rowdot_f32", f"N{N}_D{D}", tags, [Arr("a", "in", a), Arr("b", "in", b), Arr("out", "out", shape=(N,)), N, D, STREAM],
+                 lambda host, a=a, b=b: {"out": (a.astype(f64) * b).sum(1)})
+
+
+@cases_of("gnnmp_row_normalize_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        x = F(rng_of("row_normalize", N, D), N, D) + f32(0.05)
+        keep = k % 2 == 0
+        def ref(host, x=x, keep=keep):
+            nrm = np.sqrt((x.astype(f64) ** 2).sum(1))
+            out = {"xn": x / nrm[:, None]}
+            if keep:
+                out["rnorm"] = nrm
+            return out
+        yield mk("gnnmp_row_normalize_f32", f"N{N}_D{D}_r{int(keep)}", tags,
+                 [Arr("x", "in", x), Arr("xn", "out", shape=(N, D)), Arr("rnorm", "out", shape=(N,)) if keep else None, N, D, STREAM], ref)
+
+
+@cases_of("gnnmp_row_normalize_grad_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        r = rng_of("row_normalize_grad", N, D)
+        x = F(r, N, D) + f32(0.05)
+        nrm = np.sqrt((x.astype(f64) ** 2).sum(1))
+        xn, rn = (x / nrm[:, None]).astype(f32), nrm.astype(f32)
+        dq, dk, base = F(r, N, D), F(r, N, D), F(r, N, D)
+        has_k, has_b, has_q = k % 2 == 0, k % 3 == 0, k % 2 == 1
+        def ref(host, xn=xn, rn=rn, dq=dq, dk=dk, base=base, has_k=has_k, has_b=has_b, has_q=has_q):
+            dn = dq.astype(f64) + (dk if has_k else 0.0)
+            x64 = xn.astype(f64)
+            dx = (dn - x64 * (x64 * dn).sum(1, keepdims=True)) / rn.astype(f64)[:, None] + (base if has_b else 0.0)
+            out = {"dx": dx}
+            if has_q:
+                out["qdot"] = 0.5 * (x64 * dq).sum(1)
+            return out
+        yield mk("gnnmp_row_normalize_grad_f32", f"N{N}_D{D}_{int(has_k)}{int(has_b)}{int(has_q)}", tags,
+                 [Arr("dq", "in", dq), Arr("dk", "in", dk) if has_k else None, Arr("xn", "in", xn), Arr("rnorm", "in", rn),
+                  Arr("base", "in", base) if has_b else None, Arr("dx", "out", shape=(N, D)), Arr("qdot", "out", shape=(N,)) if has_q else None, 0.5, N, D, STREAM], ref)
+
+
+@cases_of("gnnmp_row_sqnorm_normalize_f32")
+def _(ctx):
+    for N, D, tags in row_shapes():
+        x = F(rng_of("row_sqnorm", N, D), N, D)
+        def ref(host, x=x):
+            sq = (x.astype(f64) ** 2).sum(1)
+            return {"sq": sq, "xn": x / (np.sqrt(sq) + 1e-6)[:, None]}
+        yield mk("gnnmp_row_sqnorm_normalize_f32", f"N{N}_D{D}", tags,
+                 [Arr("x", "in", x), Arr("sq", "out", shape=(N,)), Arr("xn", "out", shape=(N, D)), 1e-6, N, D, STREAM], ref)
+
+
+HC = ((3, 7, {"align", "side"}), (3, 6, {"align"}), (5, 4, {"align"}), (1, 1, ()), (2, 33, ()), (8, 8, ()))     # (H, C): C odd, C % 4 == 2, C % 4 == 0; H not a power of two
+
+
+@cases_of("gnnmp_head_mean_f32")
+def _(ctx):
+    for k, (H, C, tags) in enumerate(HC):
+        for N in ((33,) if k else (1, 31, 33, 300)):
+            r = rng_of("head_mean", H, C, N)
+            y, bias = F(r, N, H, C), F(r, C)
+            act = k % 2
+            yield mk("gnnmp_head_mean_f32", f"N{N}_H{H}_C{C}", tags if N == 33 else (),
+                     [Arr("y", "in", y), Arr("bias", "in", bias), act, Arr("out", "out", shape=(N, C)), N, H, C, STREAM],
+                     lambda host, y=y, bias=bias, act=act: {"out": act64(act, y.astype(f64).mean(1) + bias)})
+
+
+@cases_of("gnnmp_head_mean_grad_f32")
+def _(ctx):
+    for k, (H, C, tags) in enumerate(HC):
+        for N in ((33,) if k else (1, 31, 33, 300)):
+            dz = F(rng_of("head_mean_grad", H, C, N), N, C)
+            yield mk("gnnmp_head_mean_grad_f32", f"N{N}_H{H}_C{C}", tags if N == 33 else (),
+                     [Arr("dz", "in", dz), Arr("dy", "out", shape=(N, H, C)), N, H, C, STREAM],
+                     lambda host, dz=dz, H=H: {"dy": np.repeat(dz.astype(f64)[:, None, :] / H, H, 1)})
+
+
+@cases_of("gnnmp_gmm_weights_f32")
+def _(ctx):
+    for k, (E_, ein, K, C, tags) in enumerate(((33, 3, 2, 5, {"align", "side"}), (1, 1, 1, 1, ()), (31, 2, 3, 4, {"align"}), (300, 4, 3, 6, {"align"}), (33, 5, 1, 7, ()))):
+        r = rng_of("gmm", E_, ein, K, C)
+        e, mu, si = F(r, E_, ein), F(r, K, ein), F(r, K, ein)
+        def ref(host, e=e, mu=mu, si=si, C=C):
+            # exp(+Σ ...) exactly as the reference writes it (conv.jl:379-385; oracle/more_layers.py gmm_conv)
+            w = np.exp((((e.astype(f64)[:, None, :] - mu.astype(f64)[None]) ** 2 / 2) * si.astype(f64)[None] ** 2).sum(-1))
+            return {"out": np.repeat(w[:, :, None], C, 2).reshape(len(e), -1)}
+        yield mk("gnnmp_gmm_weights_f32", f"E{E_}_{ein}_{K}_{C}", tags,
+                 [Arr("e", "in", e), Arr("mu", "in", mu), Arr("sigma_inv", "in", si), Arr("out", "out", shape=(E_, K * C)), E_, ein, K, C, STREAM], ref)
+
+
+@cases_of("gnnmp_gru_pointwise_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        r = rng_of("gru", N, D)
+        gx, gh, h = F(r, N, 3 * D), F(r, N, 3 * D), F(r, N, D)
+        b = F(r, 3 * D) if k % 2 == 0 else None
+        def ref(host, gx=gx, gh=gh, h=h, b=b, D=D):
+            bb = np.zeros(3 * D) if b is None else b.astype(f64)
+            X, Hh = gx.astype(f64) + bb, gh.astype(f64)
+            rr = sigmoid(X[:, :D] + Hh[:, :D])
+            z = sigmoid(X[:, D:2 * D] + Hh[:, D:2 * D])
+            ht = np.tanh(X[:, 2 * D:] + rr * Hh[:, 2 * D:])
+            return {"out": (1 - z) * ht + z * h}
+        yield mk("gnnmp_gru_pointwise_f32", f"N{N}_D{D}", tags,
+                 [Arr("gx", "in", gx), Arr("gh", "in", gh), Arr("b", "in", b) if b is not None else None, Arr("h", "in", h), Arr("out", "out", shape=(N, D)), N, D, STREAM], ref)
+
+
+@cases_of("gnnmp_lstm_pointwise_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        r = rng_of("lstm", N, D)
+        gx, gh, c = F(r, N, 4 * D), F(r, N, 4 * D), F(r, N, D)
+        b = F(r, 4 * D) if k % 2 == 0 else None
+        def ref(host, gx=gx, gh=gh, c=c, b=b, D=D):
+            g = gx.astype(f64) + gh + (0.0 if b is None else b.astype(f64))
+            i, f, cc, o = (g[:, j * D:(j + 1) * D] for j in range(4))
+            cn = sigmoid(f) * c + sigmoid(i) * np.tanh(cc)
+            return {"c_out": cn, "h_out": sigmoid(o) * np.tanh(cn)}
+        yield mk("gnnmp_lstm_pointwise_f32", f"N{N}_D{D}", tags,
+                 [Arr("gx", "in", gx), Arr("gh", "in", gh), Arr("b", "in", b) if b is not None else None, Arr("c", "in", c),
+                  Arr("h_out", "out", shape=(N, D)), Arr("c_out", "out", shape=(N, D)), N, D, STREAM], ref)
+
+
+# ---- pooling ---------------------------------------------------------------------------------------------------------------------
+def _segments(r, N, G):
+    """a sorted 1-based indicator with an empty first / interior / last segment when G allows"""
+    ids = np.sort(r.integers(2 if G > 3 else 1, (G - 1 if G > 3 else G) + 1, N))
+    if G > 4:
+        ids[ids == G // 2] = G // 2 + 1
+    return np.sort(ids)
+
+
+def _pool(export, ptr_form):
+    def build(ctx):
+        for k, (N, D, tags) in enumerate(row_shapes()):
+            aggr = k % 4
+            ib, base = IDX[k % 4]
+            G = 1 if N == 1 else 9
+            r = rng_of(export, N, D)
+            x = F(r, N, D)
+            ids = _segments(r, N, G)
+            ref = lambda host, aggr=aggr, ids=ids, x=x, G=G: {"out": E(orc().scatter(aggr, x, ids, G), "rel" if aggr < 2 else "exact")}
+            if ptr_form:
+                seg_ptr = np.searchsorted(ids, np.arange(1, G + 2)).astype(np.int64)
+                args = [aggr, Arr("x", "in", x), Arr("seg_ptr", "in", seg_ptr), Arr("out", "out", shape=(G, D)), D, N, G, STREAM]
+            else:
+                args = [aggr, Arr("x", "in", x), Arr("seg_ids", "in", IX(ids, ib, base)), ib, base, Arr("out", "out", shape=(G, D)), D, N, G, STREAM]
+            yield mk(export, f"N{N}_D{D}_a{aggr}", tags, args, ref)
+    return build
+
+
+TABLE["gnnmp_segment_pool_f32"] = _pool("gnnmp_segment_pool_f32", False)
+TABLE["gnnmp_segment_pool_ptr_f32"] = _pool("gnnmp_segment_pool_ptr_f32", True)
+
+
+@cases_of("gnnmp_segment_bounds")
+def _(ctx):
+    for k, N in enumerate((1, 31, 33, 300, 5000)):
+        ib, base = IDX[k % 4]
+        G = 1 if N == 1 else 9
+        ids = _segments(rng_of("bounds", N), N, G)
+        v = np.searchsorted(ids, np.arange(1, G + 2)).astype(np.int64)
+        yield mk("gnnmp_segment_bounds", f"N{N}", {"align"} | ({"side"} if k == 2 else set()),
+                 [Arr("seg_ids", "in", IX(ids, ib, base)), ib, base, N, G, Arr("seg_ptr", "out", shape=(G + 1,), dtype=np.int64), STREAM],
+                 lambda host, v=v: {"seg_ptr": E(v, "exact")})
+
+
+@cases_of("gnnmp_pool_grad_act_f32")
+def _(ctx):
+    for k, (N, D, tags) in enumerate(row_shapes()):
+        ib, base = IDX[k % 4]
+        act, has_inv = k % 2, k % 3 == 0
+        G = 1 if N == 1 else 9
+        r = rng_of("pool_grad", N, D)
+        ids = _segments(r, N, G)
+        dpool, y, inv = F(r, G, D), F(r, N, D), (0.1 + r.random(G)).astype(f32)
+        def ref(host, ids=ids, dpool=dpool, y=y, inv=inv, act=act, has_inv=has_inv):
+            v = dpool.astype(f64)[ids - 1] * (inv.astype(f64)[ids - 1][:, None] if has_inv else 1.0)
+            return {"dz": np.where(y > 0, v, 0.0) if act else v}
+        yield mk("gnnmp_pool_grad_act_f32", f"N{N}_D{D}_act{act}", tags,
+                 [Arr("dpool", "in", dpool), Arr("graph_indicator", "in", IX(ids, ib, base)), ib, base, Arr("inv_count", "in", inv) if has_inv else None,
+                  Arr("y", "in", y), act, Arr("dz", "out", shape=(N, D)), N, G, D, STREAM], ref)
+
+
+# ---- softmax and attention -------------------------------------------------------------------------------------------------------
+@cases_of("gnnmp_edge_softmax_f32")
+def _(ctx):
+    for g, H, tags in ctx.graph_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129), small=(3, 4), ws=(3,)):
+        lg = F(rng_of("edge_softmax", g.name, H), g.E, H) * f32(3)
+        yield mk("gnnmp_edge_softmax_f32", f"{g.name}_H{H}", tags, [Pl(g), Arr("logits", "in", lg), Arr("alpha", "out", shape=(g.E, H)), H, STREAM],
+                 lambda host, g=g, lg=lg: {"alpha": orc().softmax_edge_neighbors(g.t, g.n_dst, lg)})
+
+
+@cases_of("gnnmp_segment_softmax_f32")
+def _(ctx):
+    from oracle import graphwise
+    for k, (K, D, tags) in enumerate(row_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129))):
+        G = 1 if K == 1 else 9
+        r = rng_of("segment_softmax", K, D)
+        if ("seg", K) not in ctx.cache:                 # one graph per K: the wide call and the small one share its plan
+            gi = rng_of("segment_graph", K).permutation(_segments(rng_of("segment_ids", K), K, G))     # an UNSORTED indicator: the plan route takes any
+            ctx.cache["seg", K] = Graph(f"seg{K}", np.arange(1, K + 1), gi, K, G)
+        g = ctx.cache["seg", K]
+        gi = g.t
+        x = F(r, K, D) * f32(3)
+        den_add = float(np.finfo(f32).eps) if k % 2 else 0.0
+        yield mk("gnnmp_segment_softmax_f32", f"K{K}_D{D}", tags | ({"ws"} if (K, D) == (33, 4) else set()), [Pl(g), Arr("x", "in", x), Arr("out", "out", shape=(K, D)), D, den_add, STREAM],
+                 lambda host, x=x, gi=gi, G=G, den_add=den_add: {"out": graphwise._segment_softmax(x, gi, G, den_add)})
+
+
+@cases_of("gnnmp_gat_node_scores_f32")
+def _(ctx):
+    for k, (H, C, tags) in enumerate(HC):
+        for N in ((33,) if k else (1, 31, 33, 300)):
+            r = rng_of("node_scores", H, C, N)
+            Wx, a = F(r, N, H, C), F(r, H, 2 * C)
+            which = k % 3            # both outputs, dst only, src only
+            def ref(host, Wx=Wx, a=a, C=C, which=which):
+                out = {}
+                if which != 2:
+                    out["score_dst"] = (a.astype(f64)[None, :, :C] * Wx).sum(-1)
+                if which != 1:
+                    out["score_src"] = (a.astype(f64)[None, :, C:] * Wx).sum(-1)
+                return out
+            yield mk("gnnmp_gat_node_scores_f32", f"N{N}_H{H}_C{C}_{which}", tags if N == 33 else (),
+                     [Arr("Wx", "in", Wx), Arr("a", "in", a), Arr("score_dst", "out", shape=(N, H)) if which != 2 else None,
+                      Arr("score_src", "out", shape=(N, H)) if which != 1 else None, N, H, C, STREAM], ref)
+
+
+def lrelu(x, slope):
+    return np.where(x > 0, x, slope * x)
+
+
+def attn_ref(g, loops, mode, Q, K, V, a, slope, scale, H, C, bias=None, act=0, escore=None, keep=None, p=0.0, dout=None, split_dst=False):
+    """float64 restatement of the one-pass attention and of its pullback (the softmax rrule written out): a dict of every array the
+    forward and backward entry points produce"""
+    s, t = g.s - 1, g.t - 1
+    if loops:
+        s, t = np.concatenate([s, np.arange(g.n)]), np.concatenate([t, np.arange(g.n)])
+    nd, ns = g.n_dst, g.n_src
+    Q, K, V = (np.asarray(v, f64).reshape(-1, H, C) for v in (Q, K, V))
+    a = None if a is None else np.asarray(a, f64)
+    Qt, Ks = Q[t], K[s]
+    z = u = None
+    if mode == 0:
+        z = (a[None, :, :C] * Qt).sum(-1) + (a[None, :, C:] * Ks).sum(-1)
+        if escore is not None:
+            z = z + np.asarray(escore, f64)
+        l = lrelu(z, slope)
+    elif mode == 1:
+        u = Qt + Ks
+        l = (a[None] * lrelu(u, slope)).sum(-1)
+    elif mode == 2:
+        l = (Qt * Ks).sum(-1) / scale
+    else:
+        l = scale * (Qt * Ks).sum(-1) / (np.sqrt((Qt ** 2).sum(-1)) * np.sqrt((Ks ** 2).sum(-1)))
+    m = np.full((nd, H), -np.inf)
+    np.maximum.at(m, t, l)
+    ex = np.exp(l - m[t])
+    den = seg_sum(t, ex, nd)
+    alpha = ex / den[t]
+    kk = np.ones_like(alpha) if keep is None else np.asarray(keep, f64)[: len(t)] / (1.0 - p)
+    ka = kk * alpha
+    o = seg_sum(t, ka[..., None] * V[s], nd)
+    res = {"alpha": alpha, "stats": np.stack([m, den], -1), "o": o,
+           "out": act64(act, o.reshape(nd, H * C) + (0.0 if bias is None else np.asarray(bias, f64)))}
+    if mode == 0:
+        pos = (z > 0).astype(f64)
+        res["oplus"] = seg_sum(t, (alpha * pos)[..., None] * V[s], nd).reshape(nd, H * C)
+        res["pplus"] = seg_sum(t, alpha * pos, nd)
+    if dout is None:
+        return res
+    do = np.asarray(dout, f64).reshape(nd, H, C)
+    ge = kk * (do[t] * V[s]).sum(-1)
+    Dm = seg_sum(t, alpha * ge, nd)
+    dl = alpha * (ge - Dm[t])
+    # dl is a difference of two terms that cancel exactly on a one-edge row: the scale its rounding error lives on, times the O(1) factors
+    # every gradient entry multiplies it with
+    big = max([1.0] + [float(np.abs(v).max()) for v in (a, Q, K) if v is not None and v.size])
+    term = big * (np.abs(alpha * ge) + np.abs(alpha * Dm[t])).max(-1) if len(t) else np.zeros(0)
+    row_t, row_s = np.zeros(nd), np.zeros(ns)
+    np.maximum.at(row_t, t, term)                    # per destination row / per source row: the largest cancelling term among its edges
+    np.maximum.at(row_s, s, term)
+    res.update(gscale=float(term.max()) if len(t) else 0.0, gscale_t=row_t, gscale_s=row_s)
+    dV = seg_sum(s, ka[..., None] * do[t], ns)
+    if mode == 0:
+        dz = dl * np.where(z > 0, 1.0, slope)
+        dsd, dss = seg_sum(t, dz, nd), seg_sum(s, dz, ns)
+        dsrc = dV + dss[..., None] * a[None, :, C:]
+        ddst = dsd[..., None] * a[None, :, :C]
+        res.update(dsd=dsd, dss=dss, da=np.concatenate([(dsd[..., None] * Q).sum(0), (dss[..., None] * K).sum(0)], -1))
+        if split_dst:
+            res.update(dWx_src=dsrc.reshape(ns, H * C), dWx_dst=ddst.reshape(nd, H * C))
+        else:
+            res.update(dWx_src=(dsrc + ddst).reshape(ns, H * C))
+    elif mode == 1:
+        du = dl[..., None] * a[None] * np.where(u > 0, 1.0, slope)
+        res.update(dQ=seg_sum(t, du, nd).reshape(nd, H * C), dK=(seg_sum(s, du, ns) + dV).reshape(ns, H * C),
+                   da=(dl[..., None] * lrelu(u, slope)).sum(0))
+    elif mode == 2:
+        res.update(dQ=seg_sum(t, (dl / scale)[..., None] * Ks, nd).reshape(nd, H * C), dK=seg_sum(s, (dl / scale)[..., None] * Qt, ns).reshape(ns, H * C),
+                   dV=dV.reshape(ns, H * C))
+    return res
+
+
+ATT_HC = ((3, 7), (3, 6), (5, 4), (8, 16), (1, 1), (1, 33), (2, 8))     # (8, 16): 128 floats fit a wave only with 8- or 16-byte lanes
+WIDE = ("Wx_src", "out", "oplus", "dout", "dWx_src", "Q", "K", "V", "dQ", "dK", "dV", "dA")
+
+
+def att_align(H, C, base=None):
+    """the statuses the header documents for an under-aligned pointer of the one-pass attention: `line` must be 16-byte aligned
+    (GNNMP_EINVAL, pullbacks only); a [.][H*C] array that is under-aligned for the lane width the row needs to fit one wave is refused
+    with GNNMP_EUNSUPPORTED — only possible for rows of more than 64 floats"""
+    d = dict(base or {})
+    if H * C > 64:
+        d.update({n: EUNSUPPORTED for n in WIDE})
+    return d
+
+
+def att_shapes(ctx, loops):
+    """(graph, H, C, tags): every head shape on the hub graph, two on the others (the edgeless graph only where the plan adds self loops
+    or no statistics are written)"""
+    for k, (H, C) in enumerate(ATT_HC):
+        yield ctx.hub, H, C, ({"align"} if k < 4 else set()) | ({"side", "ws"} if k == 0 else set())
+    for g in (ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300):
+        for H, C in ((3, 7), (2, 8)):
+            yield g, H, C, set()
+
+
+def nonempty(g, loops):
+    return np.ones(g.n_dst, bool) if loops else g.indeg() > 0
+
+
+def _gat_forward(export, kind):
+    """kind: conv | edge | stats | train | drop"""
+    def build(ctx):
+        loops = kind in ("stats", "drop")
+        for k, (g, H, C, tags) in enumerate(att_shapes(ctx, loops)):
+            r = rng_of(export, g.name, H, C)
+            Wx, a = F(r, g.n, H * C), F(r, H, 2 * C)
+            bias = F(r, H * C) if k % 2 == 0 else None
+            act, slope, p, seed = k % 2, 0.2, 0.25, 0x1234567890ABCDEF + k
+            Etot = g.E + (g.n if loops else 0)
+            esc = F(r, g.E, H) if kind == "edge" else None
+            keep = orc().dropout_keep(seed, p, Etot, H) if kind == "drop" else None
+            def ref(host, g=g, H=H, C=C, Wx=Wx, a=a, bias=bias, act=act, esc=esc, keep=keep, loops=loops):
+                R = attn_ref(g, loops, 0, Wx, Wx, Wx, a, slope, 1.0, H, C, bias, act, esc, keep, p if keep is not None else 0.0)
+                ne = nonempty(g, loops)
+                out = {"out": R["out"]}
+                if kind in ("stats", "train", "drop"):
+                    out["stats"] = E(R["stats"], rows=ne)        # an empty row's (m, den) is written, but the header gives it no value
+                if kind == "train":
+                    out["oplus"], out["pplus"] = R["oplus"], R["pplus"]
+                return out
+            args = [Pl(g, loops=loops), Arr("Wx_src", "in", Wx), None, Arr("a", "in", a)]
+            if kind == "edge":
+                args.append(Arr("edge_score", "in", esc))
+            args.append(slope)
+            if kind == "drop":
+                args += [p, seed]
+            args += [Arr("bias", "in", bias) if bias is not None else None, act, Arr("out", "out", shape=(g.n, H * C))]
+            if kind in ("stats", "train", "drop"):
+                args.append(Arr("stats", "out", shape=(g.n, H, 2)))
+            if kind == "train":
+                args += [Arr("oplus", "out", shape=(g.n, H * C)), Arr("pplus", "out", shape=(g.n, H))]
+            yield mk(export, f"{g.name}_H{H}_C{C}", tags, args + [H, C, STREAM], ref, align_status={} if kind == "conv" else att_align(H, C))
+    return build
+
+
+for _kind in ("conv", "edge", "stats", "train", "drop"):
+    _name = "gnnmp_gat_conv_f32" if _kind == "conv" else f"gnnmp_gat_conv_{_kind}_f32"
+    TABLE[_name] = _gat_forward(_name, _kind)
+
+
+@cases_of("gnnmp_gat_aggregate_f32")
+def _(ctx):
+    for k, (g, H, C, tags) in enumerate(att_shapes(ctx, False)):
+        r = rng_of("gat_aggregate", g.name, H, C)
+        Wx, sd, ss = F(r, g.n, H * C), F(r, g.n, H), F(r, g.n, H)
+        bias = F(r, H * C) if k % 2 else None
+        act, want_alpha = k % 2, k % 3 != 2
+        def ref(host, g=g, H=H, C=C, Wx=Wx, sd=sd, ss=ss, bias=bias, act=act, want_alpha=want_alpha):
+            s, t = g.s - 1, g.t - 1
+            l = lrelu(sd.astype(f64)[t] + ss.astype(f64)[s], 0.2)
+            m = np.full((g.n, H), -np.inf)
+            np.maximum.at(m, t, l)
+            ex = np.exp(l - m[t])
+            alpha = ex / seg_sum(t, ex, g.n)[t]
+            o = seg_sum(t, alpha[..., None] * Wx.astype(f64).reshape(-1, H, C)[s], g.n).reshape(g.n, H * C)
+            out = {"out": act64(act, o + (0.0 if bias is None else bias.astype(f64)))}
+            if want_alpha:
+                out["alpha_out"] = alpha
+            return out
+        yield mk("gnnmp_gat_aggregate_f32", f"{g.name}_H{H}_C{C}", tags,
+                 [Pl(g), Arr("Wx_src", "in", Wx), Arr("score_dst", "in", sd), Arr("score_src", "in", ss), 0.2, Arr("bias", "in", bias) if bias is not None else None,
+                  act, Arr("out", "out", shape=(g.n, H * C)), Arr("alpha_out", "out", shape=(g.E, H)) if want_alpha else None, H, C, STREAM], ref)
+
+
+def _attn_conv(export, drop):
+    def build(ctx):
+        for k, (g, H, C, tags) in enumerate(att_shapes(ctx, True)):
+            mode = (1, 2, 3, 1)[k % 4] if not drop else 1
+            if mode == 3:
+                H, C = 1, H * C
+            loops = True
+            r = rng_of(export, g.name, H, C, mode)
+            Q, K, V, a = F(r, g.n, H * C), F(r, g.n, H * C), F(r, g.n, H * C), F(r, H, C)
+            sepV = mode == 2
+            bias = F(r, H * C) if k % 2 == 0 else None
+            act, slope, scale, p, seed = k % 2, 0.2, 1.7, 0.25, 77 + k
+            keep = orc().dropout_keep(seed, p, g.E + g.n, H) if drop else None
+            want_stats = k % 3 != 1
+            def ref(host, g=g, H=H, C=C, mode=mode, Q=Q, K=K, V=V, a=a, bias=bias, act=act, keep=keep, sepV=sepV, want_stats=want_stats):
+                R = attn_ref(g, True, mode, Q, K, V if sepV else K, a, slope, scale, H, C, bias, act, None, keep, p if keep is not None else 0.0)
+                out = {"out": R["out"]}
+                if want_stats:
+                    out["stats"] = R["stats"]
+                return out
+            args = [Pl(g, loops=loops), mode, Arr("Q", "in", Q), Arr("K", "in", K), Arr("V", "in", V) if sepV else None,
+                    Arr("a", "in", a) if mode == 1 else None, slope, scale]
+            if drop:
+                args += [p, seed]
+            args += [Arr("bias", "in", bias) if bias is not None else None, act, Arr("out", "out", shape=(g.n, H * C)),
+                     Arr("stats", "out", shape=(g.n, H, 2)) if want_stats else None, H, C, STREAM]
+            yield mk(export, f"{g.name}_m{mode}_H{H}_C{C}", tags, args, ref, align_status=att_align(H, C))
+    return build
+
+
+TABLE["gnnmp_attn_conv_f32"] = _attn_conv("gnnmp_attn_conv_f32", False)
+TABLE["gnnmp_attn_conv_drop_f32"] = _attn_conv("gnnmp_attn_conv_drop_f32", True)
+
+# `line` is the one argument of the attention pullbacks the header asks 16-byte alignment for (GNNMP_EINVAL otherwise)
+LINE_ALIGN = {"line": EINVAL}
+
+
+def _gat_grad(export, two, drop=False):
+    def build(ctx):
+        for k, (g, H, C, tags) in enumerate(att_shapes(ctx, True)):
+            r = rng_of(export, g.name, H, C)
+            Wx, a, dout = F(r, g.n, H * C), F(r, H, 2 * C), F(r, g.n, H * C)
+            bias = F(r, H * C) if k % 2 == 0 else None
+            act, slope = (k % 2 if two else 0), 0.2
+            p, seed = (0.25, 0xABCDEF0123 + k) if drop else (0.0, 0)
+            keep = orc().dropout_keep(seed, p, g.E + g.n, H) if drop else None
+            R = attn_ref(g, True, 0, Wx, Wx, Wx, a, slope, 1.0, H, C, bias, act, keep=keep, p=p, dout=dout)
+            want_da = k % 3 != 1
+            if two and act:                                      # dout = dL/d(o + bias): relu's switched-off entries carry 0
+                dout = np.where(R["out"] > 0, dout, 0).astype(f32)
+                R = attn_ref(g, True, 0, Wx, Wx, Wx, a, slope, 1.0, H, C, bias, act, keep=keep, p=p, dout=dout)
+            def ref(host, R=R, want_da=want_da):
+                out = {"dsd": E(R["dsd"], scale=R["gscale_t"]), "dss": E(R["dss"], scale=R["gscale_s"]),
+                       "dWx_src": E(R["dWx_src"], scale=R["gscale_s"] + R["gscale_t"])}       # Wx_dst = Wx_src: both halves land in one row
+                if want_da:
+                    out["da"] = E(R["da"], scale=R["gscale"])
+                return out
+            args = [Pl(g, loops=True), Pl(g, T=True, loops=True), Arr("Wx_src", "in", Wx), None, Arr("a", "in", a), slope] + ([p, seed] if drop else [])
+            args.append(Arr("stats", "in", R["stats"].astype(f32)))
+            if two:
+                args += [Arr("out", "in", R["out"].astype(f32)), Arr("bias", "in", bias) if bias is not None else None,
+                         Arr("oplus", "in", R["oplus"].astype(f32)), Arr("pplus", "in", R["pplus"].astype(f32))]
+            args += [Arr("dout", "in", dout), Arr("line", "scratch", shape=(g.n, H, 4)), Arr("dsd", "out", shape=(g.n, H)), Arr("dss", "out", shape=(g.n, H)),
+                     Arr("dWx_src", "out", shape=(g.n, H * C)), None, Arr("da", "out", shape=(H, 2 * C)) if want_da else None, H, C, STREAM]
+            yield mk(export, f"{g.name}_H{H}_C{C}", tags, args, ref, align_status=att_align(H, C, LINE_ALIGN))
+    return build
+
+
+TABLE["gnnmp_gat_conv_grad_f32"] = _gat_grad("gnnmp_gat_conv_grad_f32", False)
+TABLE["gnnmp_gat_conv_grad2_f32"] = _gat_grad("gnnmp_gat_conv_grad2_f32", True)
+TABLE["gnnmp_gat_conv_grad_drop_f32"] = _gat_grad("gnnmp_gat_conv_grad_drop_f32", False, drop=True)
+
+
+def _attn_grad(export, drop):
+    def build(ctx):
+        for k, (g, H, C, tags) in enumerate(att_shapes(ctx, True)):
+            mode = 1 if drop else 1 + k % 2                 # the dropped pullback exists for the GATV2 logit
+            p, seed = (0.25, 0x5EED00 + k) if drop else (0.0, 0)
+            keep = orc().dropout_keep(seed, p, g.E + g.n, H) if drop else None
+            r = rng_of(export, g.name, H, C)
+            Q, K, V, a, dout = F(r, g.n, H * C), F(r, g.n, H * C), F(r, g.n, H * C), F(r, H, C), F(r, g.n, H * C)
+            slope, scale = 0.2, 1.7
+            R = attn_ref(g, True, mode, Q, K, V if mode == 2 else K, a, slope, scale, H, C, keep=keep, p=p, dout=dout)
+            def ref(host, R=R, mode=mode):
+                out = {"dQ": E(R["dQ"], scale=R["gscale_t"]), "dK": E(R["dK"], scale=R["gscale_s"])}
+                out.update({"dV": R["dV"]} if mode == 2 else {"da": E(R["da"], scale=R["gscale"])})
+                return out
+            yield mk(export, f"{g.name}_m{mode}_H{H}_C{C}", tags,
+                     [Pl(g, loops=True), Pl(g, T=True, loops=True), mode, Arr("Q", "in", Q), Arr("K", "in", K), Arr("V", "in", V) if mode == 2 else None,
+                      Arr("a", "in", a) if mode == 1 else None, slope, scale] + ([p, seed] if drop else []) + [Arr("stats", "in", R["stats"].astype(f32)), Arr("dout", "in", dout),
+                      Arr("line", "scratch", shape=(g.n, H, 4)), Arr("dQ", "out", shape=(g.n, H * C)), Arr("dK", "out", shape=(g.n, H * C)),
+                      Arr("dV", "out", shape=(g.n, H * C)) if mode == 2 else None, Arr("dA", "scratch", shape=(g.n, H * C)) if mode == 1 else None,
+                      Arr("da", "out", shape=(H, C)) if mode == 1 else None, H, C, STREAM], ref, align_status=att_align(H, C, LINE_ALIGN))
+    return build
+
+
+TABLE["gnnmp_attn_conv_grad_f32"] = _attn_grad("gnnmp_attn_conv_grad_f32", False)
+TABLE["gnnmp_attn_conv_grad_drop_f32"] = _attn_grad("gnnmp_attn_conv_grad_drop_f32", True)
+
+
+@cases_of("gnnmp_dropout_keep_u8")
+def _(ctx):
+    for k, (n, H) in enumerate(((1, 1), (31, 3), (33, 4), (300, 7), (70001, 2))):
+        seed, p = 0xDEADBEEF12345 + k, 0.3
+        yield mk("gnnmp_dropout_keep_u8", f"n{n}_H{H}", {"align"} | ({"side"} if k == 2 else set()),
+                 [seed, p, n, H, Arr("keep", "out", shape=(n, H), dtype=np.uint8), STREAM],
+                 lambda host, seed=seed, n=n, H=H: {"keep": E(orc().dropout_keep(seed, p, n, H), "exact")})
+
+
+# ---- dense -----------------------------------------------------------------------------------------------------------------------
+def dense_guard(width):
+    return 32 * 4 * int(width)            # one full store tile of the dense kernels: 32 rows of the output
+
+
+@cases_of("gnnmp_dense_f32")
+def _(ctx):
+    shapes = [(33, 100, 0, 100, {"align", "side"}), (33, 128, 128, 128, {"align"}), (300, 100, 100, 256, {"align"}), (1, 3, 0, 5, ()), (31, 7, 6, 3, {"align"}),
+              (33, 4, 0, 4, ()), (300, 16, 16, 128, ()), (33, 260, 0, 129, ()), (31, 127, 1, 2, ()), (300, 128, 0, 64, ()), (33, 2, 0, 1, ()), (300, 6, 0, 260, ())]
+    for k, (N, K1, K2, Dout, tags) in enumerate(shapes):
+        layout, pad = k % 2, (0, 0, 4, 3)[k % 4]               # both w_layouts; ldw larger than the row on half of the shapes
+        act, has_b = k % 2, k % 3 != 0
+        r = rng_of("dense", N, K1, K2, Dout)
+        x1, x2 = F(r, N, K1), (F(r, N, K2) if K2 else None)
+        Wf = F(r, Dout, K1 + K2) * f32(0.3)
+        b = F(r, Dout) if has_b else None
+        def stored(W):
+            if layout == 0:
+                buf = F(r, W.shape[0], W.shape[1] + pad)
+                buf[:, :W.shape[1]] = W
+            else:
+                buf = F(r, W.shape[1], W.shape[0] + pad)
+                buf[:, :W.shape[0]] = W.T
+            return buf
+        W1, W2 = stored(Wf[:, :K1]), (stored(Wf[:, K1:]) if K2 else None)
+        def ref(host, x1=x1, x2=x2, Wf=Wf, b=b, act=act):
+            xin = np.concatenate([x1, x2], 1).astype(f64) if x2 is not None else x1.astype(f64)
+            pre = xin @ Wf.astype(f64).T + (0.0 if b is None else b.astype(f64))
+            mag = np.abs(xin) @ np.abs(Wf.astype(f64)).T + (0.0 if b is None else np.abs(b.astype(f64)))
+            return {"out": E(act64(act, pre), "mag", mag=mag)}
+        yield mk("gnnmp_dense_f32", f"N{N}_K{K1}+{K2}_D{Dout}_l{layout}p{pad}", tags,
+                 [Arr("x1", "in", x1), Arr("W1", "in", W1), K1, W1.shape[1], Arr("x2", "in", x2) if K2 else None, Arr("W2", "in", W2) if K2 else None, K2,
+                  W2.shape[1] if K2 else 0, layout, Arr("bias", "in", b) if has_b else None, act, Arr("out", "out", shape=(N, Dout)), N, Dout, STREAM], ref,
+                 guard=dense_guard(max(Dout, K1, K2)))
+
+
+@cases_of("gnnmp_fused_conv_f32")
+def _(ctx):
+    # the header: the feature arrays must be 16-byte aligned, anything else returns GNNMP_EUNSUPPORTED.  By default the entry point also
+    # refuses graphs whose aggregate fits the Infinity Cache (the unfused pair is faster there); knob 14 forces the kernel, as
+    # tests/test_fused_conv.py does
+    al = {n: EUNSUPPORTED for n in ("xj", "xi", "out", "agg_out")}
+    shapes = [(ctx.hub, 100, 0, 100, {"align", "side", "ws"}), (ctx.hub, 128, 0, 128, {"align"}), (ctx.hub, 64, 64, 128, {"align"}), (ctx.hub, 4, 4, 8, {"align"}), (ctx.r31, 16, 0, 32, ()),
+              (ctx.r33, 100, 100, 64, ()), (ctx.r300, 64, 64, 128, ()), (ctx.r300, 100, 100, 128, ())]
+    for k, (g, D, D1, Dout, tags) in enumerate(shapes):
+        layout, scaled, act = k % 2, k % 2 == 0, k % 2
+        aggr = SUM if scaled else (SUM, MEAN)[k % 4 // 2]
+        r = rng_of("fused_conv", g.name, D, D1, Dout)
+        xj, w = F(r, g.n, D), F(r, g.E)
+        ss = (0.5 + r.random(g.n)).astype(f32) if scaled else None
+        sd = (0.5 + r.random(g.n)).astype(f32) if scaled else None
+        xi = F(r, g.n, D1) if D1 else None
+        Wa, Wr, b = F(r, Dout, D) * f32(0.3), (F(r, Dout, D1) * f32(0.3) if D1 else None), F(r, Dout)
+        pad = (0, 0, 4, 8)[k % 4]                       # ldw larger than the row on half of the shapes, in both layouts
+        def st(W):
+            M = W if layout == 0 else W.T
+            buf = F(r, M.shape[0], M.shape[1] + pad)
+            buf[:, :M.shape[1]] = M
+            return buf
+        Wr_s, Wa_s = (st(Wr) if D1 else None), st(Wa)
+        def ref(host, g=g, aggr=aggr, xj=xj, w=w, ss=ss, sd=sd, xi=xi, Wa=Wa, Wr=Wr, b=b, act=act, scaled=scaled):
+            A = _prop_ref(ctx, g, aggr, xj, w if scaled else None, ss, sd)
+            A64 = A.value.astype(f64)
+            pre = A64 @ Wa.astype(f64).T + b.astype(f64) + (xi.astype(f64) @ Wr.astype(f64).T if xi is not None else 0.0)
+            return {"out": act64(act, pre), "agg_out": A}
+        yield mk("gnnmp_fused_conv_f32", f"{g.name}_D{D}+{D1}_o{Dout}_l{layout}p{pad}", tags,
+                 [Pl(g), aggr, Arr("xj", "in", xj), Arr("w", "in", w) if scaled else None, Arr("scale_src", "in", ss) if scaled else None, None, None,
+                  Arr("scale_dst", "in", sd) if scaled else None, D, Arr("xi", "in", xi) if D1 else None, D1, Arr("W_root", "in", Wr_s) if D1 else None,
+                  Wr_s.shape[1] if D1 else 0, Arr("W_agg", "in", Wa_s), Wa_s.shape[1], layout, Arr("bias", "in", b), act,
+                  Arr("out", "out", shape=(g.n, Dout)), Dout, Arr("agg_out", "out", shape=(g.n, D)), STREAM], ref, guard=dense_guard(max(D, Dout)), align_status=al, knobs={14: 16})
+
+
+def _grad_w_shapes():
+    return [(33, 5, 16, {"align", "side"}), (300, 128, 112, {"align"}), (300, 128, 100, ()), (1, 1, 16, ()), (31, 7, 32, {"align"}), (2500, 64, 48, ()), (33, 129, 16, ())]
+
+
+@cases_of("gnnmp_dense_grad_w_f32")
+def _(ctx):
+    from gnnmp import _lib
+    for k, (N, Dout, K, tags) in enumerate(_grad_w_shapes() + [(33, 6, 3, ()), (31, 4, 127, ())]):
+        r = rng_of("grad_w", N, Dout, K)
+        dz, x = F(r, N, Dout), F(r, N, K)
+        ws = int(_lib.load().gnnmp_dense_grad_workspace(N, Dout, K))
+        which = k % 3
+        def ref(host, dz=dz, x=x, which=which):
+            out = {}
+            if which != 2:
+                out["dW"] = dz.astype(f64).T @ x.astype(f64)
+            if which != 1:
+                out["db"] = dz.astype(f64).sum(0)
+            return out
+        yield mk("gnnmp_dense_grad_w_f32", f"N{N}_o{Dout}_K{K}_{which}", tags,
+                 [Arr("dz", "in", dz), Arr("x", "in", x), N, Dout, K, Arr("dW", "out", shape=(Dout, K)) if which != 2 else None,
+                  Arr("db", "out", shape=(Dout,)) if which != 1 else None, Arr("workspace", "scratch", shape=(max(ws, 1),)), ws, STREAM], ref, guard=dense_guard(max(Dout, K)))
+
+
+@cases_of("gnnmp_dense_grad_w2_f32")
+def _(ctx):
+    from gnnmp import _lib
+    for N, Dout, K1, tags in _grad_w_shapes():
+        K2 = (K1, 100, 4)[N % 3]
+        r = rng_of("grad_w2", N, Dout, K1)
+        dz, x1, x2 = F(r, N, Dout), F(r, N, K1), F(r, N, K2)
+        ws = int(_lib.load().gnnmp_dense_grad_w2_workspace(N, Dout, K1, K2))
+        def ref(host, dz=dz, x1=x1, x2=x2):
+            d = dz.astype(f64)
+            return {"out": np.concatenate([(d.T @ x1).reshape(-1), (d.T @ x2).reshape(-1), d.sum(0)])}
+        yield mk("gnnmp_dense_grad_w2_f32", f"N{N}_o{Dout}_K{K1}+{K2}", tags,
+                 [Arr("dz", "in", dz), Arr("x1", "in", x1), K1, Arr("x2", "in", x2), K2, N, Dout, Arr("out", "out", shape=(Dout * (K1 + K2 + 1),)),
+                  Arr("workspace", "scratch", shape=(max(ws, 1),)), ws, STREAM], ref, guard=dense_guard(max(Dout, K1, K2)),
+                 status=EUNSUPPORTED if K1 % 16 else OK)       # the header: K1 a multiple of 16, else GNNMP_EUNSUPPORTED
+
+
+# ---- temporal --------------------------------------------------------------------------------------------------------------------
+TG = ((33, 3, 5, {"align", "side"}), (1, 1, 1, ()), (31, 2, 16, {"align"}), (300, 3, 6, {"align"}), (33, 2, 128, ()), (17, 4, 100, ()))     # (N, T, out)
+
+
+def tgcn_forward64(P, Uzr, Uh, h0, N, T, D):
+    P, Uzr, Uh = P.astype(f64).reshape(N, T, 3 * D), Uzr.astype(f64), Uh.astype(f64)
+    h = np.zeros((N, D)) if h0 is None else np.broadcast_to(h0.astype(f64), (N, D)).copy()
+    y, gates = np.zeros((N, T, D)), np.zeros((N, T, 3 * D))
+    for t in range(T):
+        zr = sigmoid(P[:, t, :2 * D] + h @ Uzr.T)
+        z, r = zr[:, :D], zr[:, D:]
+        ht = np.tanh(P[:, t, 2 * D:] + (r * h) @ Uh.T)
+        h = (1 - z) * h + z * ht
+        y[:, t], gates[:, t] = h, np.concatenate([z, r, ht], 1)
+    return y, gates
+
+
+@cases_of("gnnmp_tgcn_recurrence_f32")
+def _(ctx):
+    for k, (N, T, D, tags) in enumerate(TG):
+        r = rng_of("tgcn_rec", N, T, D)
+        P, Uzr, Uh = F(r, N, T, 3 * D), F(r, 2 * D, D) * f32(0.3), F(r, D, D) * f32(0.3)
+        h0 = (F(r, N, D), F(r, D), None)[k % 3]
+        stride = (D, 0, 0)[k % 3]
+        want_g = k % 2 == 0
+        def ref(host, P=P, Uzr=Uzr, Uh=Uh, h0=h0, N=N, T=T, D=D, want_g=want_g):
+            y, gates = tgcn_forward64(P, Uzr, Uh, h0, N, T, D)
+            return {"y": y, "gates": gates} if want_g else {"y": y}
+        yield mk("gnnmp_tgcn_recurrence_f32", f"N{N}_T{T}_D{D}", tags,
+                 [Arr("P", "in", P), Arr("U_zr", "in", Uzr), Arr("U_h", "in", Uh), Arr("h0", "in", h0) if h0 is not None else None, stride,
+                  Arr("y", "out", shape=(N, T, D)), Arr("gates", "out", shape=(N, T, 3 * D)) if want_g else None, N, T, D, STREAM], ref)
+
+
+@cases_of("gnnmp_tgcn_recurrence_grad_f32")
+def _(ctx):
+    for k, (N, T, D, tags) in enumerate(TG):
+        r = rng_of("tgcn_rec_grad", N, T, D)
+        P, Uzr, Uh, dy = F(r, N, T, 3 * D), F(r, 2 * D, D) * f32(0.3), F(r, D, D) * f32(0.3), F(r, N, T, D)
+        h0 = (F(r, N, D), F(r, D), None)[k % 3]
+        stride = (D, 0, 0)[k % 3]
+        y, gates = (v.astype(f32) for v in tgcn_forward64(P, Uzr, Uh, h0, N, T, D))
+        want_S, want_h0 = k % 2 == 0, k % 3 != 2
+        def ref(host, y=y, gates=gates, Uzr=Uzr, Uh=Uh, dy=dy, h0=h0, N=N, T=T, D=D, want_S=want_S, want_h0=want_h0):
+            # backpropagation through time, the statements of the header (gnnmp_tgcn_step_grad_f32) step by step in float64
+            Y, G, Uz, Ur, U = y.astype(f64), gates.astype(f64), Uzr.astype(f64)[:D], Uzr.astype(f64)[D:], Uh.astype(f64)
+            hstart = np.zeros((N, D)) if h0 is None else np.broadcast_to(h0.astype(f64), (N, D))
+            dP, S, carry = np.zeros((N, T, 3 * D)), np.zeros((N, T, 2 * D)), np.zeros((N, D))
+            for t in range(T - 1, -1, -1):
+                hp = Y[:, t - 1] if t else hstart
+                z, rr, ht = G[:, t, :D], G[:, t, D:2 * D], G[:, t, 2 * D:]
+                dh = dy.astype(f64)[:, t] + carry
+                ah = dh * z * (1 - ht * ht)
+                drh = ah @ U
+                az = dh * (ht - hp) * z * (1 - z)
+                ar = drh * hp * rr * (1 - rr)
+                carry = dh * (1 - z) + drh * rr + az @ Uz + ar @ Ur
+                dP[:, t], S[:, t] = np.concatenate([az, ar, ah], 1), np.concatenate([hp, rr * hp], 1)
+            out = {"dP": dP}
+            if want_S:
+                out["S"] = S
+            if want_h0:
+                out["dh0"] = carry
+            return out
+        yield mk("gnnmp_tgcn_recurrence_grad_f32", f"N{N}_T{T}_D{D}", tags,
+                 [Arr("dy", "in", dy), Arr("y", "in", y), Arr("gates", "in", gates), Arr("U_zr", "in", Uzr), Arr("U_h", "in", Uh),
+                  Arr("h0", "in", h0) if h0 is not None else None, stride, Arr("dP", "out", shape=(N, T, 3 * D)),
+                  Arr("S", "out", shape=(N, T, 2 * D)) if want_S else None, Arr("dh0", "out", shape=(N, D)) if want_h0 else None, N, T, D, STREAM], ref)
+
+
+@cases_of("gnnmp_tgcn_step_f32")
+def _(ctx):
+    for k, (N, T, D, tags) in enumerate(TG):
+        phase, t = k % 2, T - 1 - (k % T)
+        r = rng_of("tgcn_step", N, T, D)
+        P, a, gates0, y0 = F(r, N, T, 3 * D), F(r, N, (1 if phase else 2) * D), r.random((N, T, 3 * D)).astype(f32), F(r, N, T, D)
+        ldh = D + 3
+        h = F(r, N, ldh) if k % 3 else None
+        def ref(host, P=P, a=a, gates0=gates0, y0=y0, h=h, phase=phase, t=t, D=D, N=N):
+            hv = np.zeros((N, D)) if h is None else h.astype(f64)[:, :D]
+            g, y = gates0.astype(f64), y0.astype(f64)
+            if phase == 0:
+                zr = sigmoid(P.astype(f64)[:, t, :2 * D] + a)
+                g[:, t, :2 * D] = zr
+                return {"gates": g, "hout": zr[:, D:] * hv}
+            ht = np.tanh(P.astype(f64)[:, t, 2 * D:] + a)
+            z = g[:, t, :D]
+            g[:, t, 2 * D:] = ht
+            hn = (1 - z) * hv + z * ht
+            y[:, t] = hn
+            return {"gates": g, "hout": hn, "y": y}
+        yield mk("gnnmp_tgcn_step_f32", f"N{N}_T{T}_D{D}_p{phase}", tags,
+                 [phase, Arr("P", "in", P), Arr("a", "in", a), Arr("h", "in", h) if h is not None else None, ldh, Arr("gates", "inout", gates0),
+                  Arr("hout", "out", shape=(N, D)), Arr("y", "inout", y0) if phase else None, N, T, t, D, STREAM], ref)
+
+
+@cases_of("gnnmp_tgcn_step_grad_f32")
+def _(ctx):
+    for k, (N, T, D, tags) in enumerate(TG):
+        phase, t = k % 2, k % T
+        r = rng_of("tgcn_step_grad", N, T, D)
+        dy, carry, gates, drh = F(r, N, T, D), F(r, N, D), r.random((N, T, 3 * D)).astype(f32) * f32(0.9), F(r, N, D)
+        ldh = D + 1
+        h = F(r, N, ldh)
+        dP0, dzr0, part0, S0, dah0 = F(r, N, T, 3 * D), F(r, N, 2 * D), F(r, N, D), F(r, N, T, 2 * D), F(r, N, D)
+        has_c, has_S = k % 3 != 0, k % 4 != 3
+        def ref(host, dy=dy, carry=carry, gates=gates, drh=drh, h=h, dP0=dP0, dzr0=dzr0, part0=part0, S0=S0, phase=phase, t=t, D=D, has_c=has_c, has_S=has_S):
+            G, hp = gates.astype(f64)[:, t], h.astype(f64)[:, :D]
+            z, rr, ht = G[:, :D], G[:, D:2 * D], G[:, 2 * D:]
+            dP, dzr, part, S = dP0.astype(f64), dzr0.astype(f64), part0.astype(f64), S0.astype(f64)
+            if phase == 0:
+                gq = dy.astype(f64)[:, t] + (carry if has_c else 0.0)
+                ah, az = gq * z * (1 - ht * ht), gq * (ht - hp) * z * (1 - z)
+                dP[:, t, :D], dP[:, t, 2 * D:], dzr[:, :D] = az, ah, az
+                return {"dP": dP, "dah": ah, "dzr": dzr, "part": gq * (1 - z)}
+            ar = drh.astype(f64) * hp * rr * (1 - rr)
+            dP[:, t, D:2 * D], dzr[:, D:] = ar, ar
+            out = {"dP": dP, "dzr": dzr, "part": part + drh.astype(f64) * rr}
+            if has_S:
+                S[:, t, :D], S[:, t, D:] = hp, rr * hp
+                out["S"] = S
+            return out
+        args = [phase, Arr("dy", "in", dy), Arr("carry", "in", carry) if has_c and phase == 0 else None, Arr("gates", "in", gates), Arr("h", "in", h), ldh,
+                Arr("drh", "in", drh) if phase else None, Arr("dP", "inout", dP0), Arr("dah", "out", shape=(N, D)) if phase == 0 else Arr("dah", "scratch", shape=(N, D)),
+                Arr("dzr", "inout", dzr0), Arr("part", "inout", part0), Arr("S", "inout", S0) if has_S and phase else None, N, T, t, D, STREAM]
+        yield mk("gnnmp_tgcn_step_grad_f32", f"N{N}_T{T}_D{D}_p{phase}", tags, args, ref)
+
+
+# ---- graph prep with caller-owned outputs ------------------------------------------------------------------------------------------
+PREP = ((1, 2), (31, 90), (33, 100), (300, 900), (40, 0))
+
+
+@cases_of("gnnmp_add_self_loops")
+def _(ctx):
+    for k, (n, E_) in enumerate(PREP):
+        ib, base = IDX[k % 4]
+        r = rng_of("asl", n, E_)
+        s1, t1 = r.integers(1, n + 1, E_), r.integers(1, n + 1, E_)
+        w = F(r, E_) if k % 2 == 0 else None
+        def ref(host, s1=s1, t1=t1, n=n, w=w, ib=ib, base=base):
+            s2, t2, w2 = orc().add_self_loops(s1, t1, n, w)
+            out = {"out_src": E(IX(s2, ib, base), "exact"), "out_dst": E(IX(t2, ib, base), "exact")}
+            if w is not None:
+                out["out_w"] = E(w2, "exact")
+            return out
+        dt = np.int64 if ib == 8 else np.int32
+        yield mk("gnnmp_add_self_loops", f"n{n}_E{E_}_i{ib}b{base}", {"align"} | ({"side"} if k == 2 else set()),
+                 [Arr("src", "in", IX(s1, ib, base)), Arr("dst", "in", IX(t1, ib, base)), ib, base, E_, n, Arr("out_src", "out", shape=(E_ + n,), dtype=dt),
+                  Arr("out_dst", "out", shape=(E_ + n,), dtype=dt), Arr("w", "in", w) if w is not None else None,
+                  Arr("out_w", "out", shape=(E_ + n,)) if w is not None else None, STREAM], ref)
+
+
+@cases_of("gnnmp_batch_coo")
+def _(ctx):
+    for k, sizes in enumerate(((1,), (5, 0, 7, 19), (33, 31, 1, 64, 2), (300, 5))):
+        ib, base = IDX[k % 4]
+        r = rng_of("batch", sizes)
+        graphs = [(r.integers(1, n + 1, 3 * n), r.integers(1, n + 1, 3 * n), n) if n else (np.zeros(0, np.int64), np.zeros(0, np.int64), 0) for n in sizes]
+        s2, t2, gi, N = orc().batch(graphs)
+        ep = np.array([0] + [len(g[0]) for g in graphs], np.int64).cumsum()
+        npt = np.array([0] + [g[2] for g in graphs], np.int64).cumsum()
+        s = np.concatenate([g[0] for g in graphs])
+        t = np.concatenate([g[1] for g in graphs])
+        dt = np.int64 if ib == 8 else np.int32
+        yield mk("gnnmp_batch_coo", f"G{len(sizes)}_N{N}_i{ib}b{base}", {"align"} | ({"side"} if k == 1 else set()),
+                 [Arr("src", "in", IX(s, ib, base)), Arr("dst", "in", IX(t, ib, base)), ib, base, Arr("edge_ptr", "in", ep), Arr("node_ptr", "in", npt), len(sizes),
+                  Arr("out_src", "out", shape=(len(s),), dtype=dt), Arr("out_dst", "out", shape=(len(s),), dtype=dt), Arr("graph_indicator", "out", shape=(N,), dtype=dt), STREAM],
+                 lambda host, s2=s2, t2=t2, gi=gi, ib=ib, base=base: {"out_src": E(IX(s2, ib, base), "exact"), "out_dst": E(IX(t2, ib, base), "exact"),
+                                                                      "graph_indicator": E(IX(gi, ib, base), "exact")})
+
+
+@cases_of("gnnmp_sort_edge_index")
+def _(ctx):
+    for k, (n, E_) in enumerate(PREP[:4] + ((500, 5000),)):
+        ib, base = IDX[k % 4]
+        r = rng_of("sort", n, E_)
+        u, v = r.integers(1, n + 1, E_), r.integers(1, n + 1, E_)
+        o = np.lexsort((v, u))
+        dt = np.int64 if ib == 8 else np.int32
+        yield mk("gnnmp_sort_edge_index", f"n{n}_E{E_}_i{ib}b{base}", {"align"} | ({"side"} if k == 2 else set()),
+                 [Arr("u", "in", IX(u, ib, base)), Arr("v", "in", IX(v, ib, base)), ib, base, E_, Arr("u_out", "out", shape=(E_,), dtype=dt),
+                  Arr("v_out", "out", shape=(E_,), dtype=dt), STREAM],
+                 lambda host, u=u, v=v, o=o, ib=ib, base=base: {"u_out": E(IX(u[o], ib, base), "exact"), "v_out": E(IX(v[o], ib, base), "exact")})
+
+
+@cases_of("gnnmp_unique_append")
+def _(ctx):
+    for k, (n, nc) in enumerate(((1, 1), (31, 50), (33, 100), (300, 900))):
+        ib, base = IDX[k % 4]
+        r = rng_of("unique", n, nc)
+        present = r.permutation(n)[: n // 3] + 1                    # the set so far, in list order
+        map0 = np.zeros(n, np.int32)
+        map0[present - 1] = np.arange(1, len(present) + 1)
+        cand = r.integers(1, n + 1, nc)
+        seen, new = set(present.tolist()), []
+        for c in cand.tolist():
+            if c not in seen:
+                seen.add(c)
+                new.append(c)
+        map1 = map0.copy()
+        map1[np.asarray(new, np.int64) - 1] = len(present) + np.arange(1, len(new) + 1)
+        dt = np.int64 if ib == 8 else np.int32
+        def ref(host, new=new, map1=map1, ib=ib, base=base):
+            assert host["n_new"] == len(new), (host["n_new"], len(new))
+            return {"map": E(map1, "exact"), "list_out": E(IX(np.asarray(new, np.int64), ib, base), "exact", prefix=len(new))}
+        yield mk("gnnmp_unique_append", f"n{n}_c{nc}_i{ib}b{base}", {"align"} | ({"side"} if k == 2 else set()),
+                 [Arr("map", "inout", map0), Arr("first", "scratch", shape=(n,), dtype=np.int32), n, Arr("cand", "in", IX(cand, ib, base)), ib, base, nc, len(present),
+                  Arr("list_out", "out", shape=(nc,), dtype=dt), HostOut("n_new"), STREAM], ref)
+
+
+@cases_of("gnnmp_induced_subgraph")
+def _(ctx):
+    for k, g in enumerate((ctx.hub, ctx.one, ctx.r31, ctx.r33, ctx.r300)):
+        ib, base = IDX[k % 4]
+        r = rng_of("induced", g.name)
+        nodes = r.permutation(g.n)[: max(1, g.n // 2)] + 1
+        mp = np.zeros(g.n, np.int32)
+        mp[nodes - 1] = np.arange(1, len(nodes) + 1)
+        so, to, eo, offs = [], [], [], [0]
+        for pos, v in enumerate(nodes.tolist()):
+            for e in np.flatnonzero(g.t == v).tolist():
+                if mp[g.s[e] - 1]:
+                    so.append(int(mp[g.s[e] - 1]))
+                    to.append(pos + 1)
+                    eo.append(e + 1)
+            offs.append(len(so))
+        tot = len(so)
+        dt = np.int64 if ib == 8 else np.int32
+        def ref(host, so=so, to=to, eo=eo, offs=offs, tot=tot, ib=ib, base=base):
+            assert host["total"] == tot, (host["total"], tot)
+            I = lambda v: E(IX(np.asarray(v, np.int64), ib, base), "exact")
+            return {"offsets": E(np.asarray(offs, np.int64), "exact"), "s_out": I(so), "t_out": I(to), "eid_out": I(eo)}
+        yield mk("gnnmp_induced_subgraph", f"{g.name}_i{ib}b{base}", ({"align", "side", "ws"} if g is ctx.hub else ()),
+                 [Pl(g), Arr("map", "in", mp), Arr("nodes", "in", IX(nodes, ib, base)), ib, base, len(nodes), Arr("offsets", "out", shape=(len(nodes) + 1,), dtype=np.int64),
+                  Arr("s_out", "out", shape=(tot,), dtype=dt), Arr("t_out", "out", shape=(tot,), dtype=dt), Arr("eid_out", "out", shape=(tot,), dtype=dt), tot,
+                  HostOut("total"), STREAM], ref)
+
+
+@cases_of("gnnmp_rand_edge_split")
+def _(ctx):
+    for k, (n, E_) in enumerate(PREP[:4]):
+        ib, base = IDX[k % 4]
+        r = rng_of("split", n, E_)
+        s1, t1 = r.integers(1, n + 1, E_), r.integers(1, n + 1, E_)
+        size1 = int(round(E_ * 0.3))
+        code = (s1 - 1 + base).astype(np.int64) * (n + 2) + (t1 - 1 + base)
+        def ref(host, code=code, size1=size1, n=n):
+            got = {}
+            def part(name):
+                def pred(v, name=name):
+                    got[name] = v.astype(np.int64)
+                    if len(got) == 4:            # the four outputs together are a permutation of the edge list (exact integers)
+                        c = np.concatenate([got["s1"] * (n + 2) + got["t1"], got["s2"] * (n + 2) + got["t2"]])
+                        if not np.array_equal(np.sort(c), np.sort(code)):
+                            return "the two parts are not a partition of the edges"
+                    return None
+                return E(pred=pred)
+            return {nm: part(nm) for nm in ("s1", "t1", "s2", "t2")}
+        dt = np.int64 if ib == 8 else np.int32
+        yield mk("gnnmp_rand_edge_split", f"n{n}_E{E_}_i{ib}b{base}", {"align"} | ({"side"} if k == 2 else set()),
+                 [Arr("s", "in", IX(s1, ib, base)), Arr("t", "in", IX(t1, ib, base)), ib, base, E_, 0, size1, 12345 + k, Arr("s1", "out", shape=(size1,), dtype=dt),
+                  Arr("t1", "out", shape=(size1,), dtype=dt), Arr("s2", "out", shape=(E_ - size1,), dtype=dt), Arr("t2", "out", shape=(E_ - size1,), dtype=dt), STREAM], ref)
+
+
+# exports the table does not cover, each with its reason (the lifecycle calls and the collective are allowed as a class; at most eight more)
+LIFECYCLE = ("gnnmp_plan_", "gnnmp_arena_", "gnnmp_chain_jobs_")
+EXCLUDED = {
+    "gnnmp_allgather_f32": "needs an RCCL communicator (tests/test_parallel_two_ranks_gpu.py runs it between two processes)",
+}
+EXCLUDED_EXTRA = {
+    "gnnmp_graphconv_chain_f32": "NOT covered by this module (host tables of device pointers, a jobs handle per batch): its scratch / out writes stay untested here",
+    "gnnmp_negative_sample": "random draws with a host-side trial loop: no deterministic reference for the written prefix (tests/test_linkpred.py: properties)",
+    "gnnmp_sample_neighbors": "random draws: parity is distributional (tests/test_graphprep.py); the written prefix has no exact reference",
+}
