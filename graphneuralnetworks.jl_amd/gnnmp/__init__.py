@@ -22,6 +22,7 @@ from .layers_temporal import TGCN, GNNRecurrence, TGCNCell, tgcn_forward  # noqa
 from .backward_temporal import tgcn_ad  # noqa: F401
 from .linkpred import (DotDecoder, WithGraph, dot_decoder, dot_decoder_ad, edge_dot_ad, edge_dot_grad,  # noqa: F401
                        negative_sample, rand_edge_split)
+from .neighbors import knn_graph, radius_graph  # noqa: F401
 from .dataset import DataLoader, GraphDataset, concat_plans  # noqa: F401
 from .sampling import (NeighborLoader, NodeSet, has_self_loops, induced_subgraph, is_bidirected, sample_neighbors,  # noqa: F401
                        sort_edge_index)

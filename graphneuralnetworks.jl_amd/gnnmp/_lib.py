@@ -48,6 +48,7 @@ SYMBOLS = (
     "gnnmp_propagate_f64", "gnnmp_gather_f64", "gnnmp_scatter_f64",
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
+    "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
@@ -182,6 +183,8 @@ def load():
         "gnnmp_negative_sample": [vp, vp, i, i, i64, i64, i64, i, i, u64, vp, vp, i64, ctypes.POINTER(i64), vp],
         "gnnmp_rand_edge_split": [vp, vp, i, i, i64, i, i64, u64, vp, vp, vp, vp, vp],
         "gnnmp_edge_dot_grad_f32": [vp, vp, vp, vp, vp, vp, vp, i64, vp],
+        "gnnmp_knn_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, i64, vp, i, i, i64, i, vp],
+        "gnnmp_radius_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, f, vp, i, i, i64, i, vp],
     }
     for name, args in sig.items():
         try:

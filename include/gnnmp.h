@@ -881,6 +881,46 @@ int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_transposed,
                             float *dxi, float *dxj, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Neighbour search (csrc/neighbors.hip): the graph constructors knn_graph(points, k; graph_indicator, self_loops, dir) and
+ * radius_graph(points, r; ...) — GNNGraphs/src/generate.jl:112-145, 196-222.  The reference runs NearestNeighbors.jl trees on the
+ * CPU; here an exact brute-force search in fp32 on the device.  points: [N][d] row-major (Julia's d x N), 4-byte aligned.
+ *
+ * Fixed semantics (the answer is unique and does not depend on tiling; reruns are bit-identical):
+ *   - d2(i, j) is accumulated over the dimensions c = 0 .. d-1 in order from 0 as acc = fmaf(x[i][c] - x[j][c], x[i][c] - x[j][c], acc);
+ *     a non-finite d2 (NaN included) ranks as +inf.
+ *   - candidates are ordered by the pair (d2, j): ties go to the lower index.
+ *   - graph_indicator (nullable; idx_bytes 4 | 8, values index_base .. index_base + n_graphs - 1; both ignored without it): the
+ *     candidates of i are the nodes with i's graph id, on the RAW coordinates (the reference rescales the points and appends a dummy
+ *     coordinate, generate.jl:125-130).  Non-decreasing indicator: the candidate range is the graph's segment (gnnmp_segment_bounds),
+ *     work sum n_g^2; otherwise the full range with the other graphs masked.  An id outside the n_graphs graphs: GNNMP_EBOUNDS.
+ *   - self_loops = 0 excludes j == i BY INDEX (a duplicated point is a neighbour at distance 0); != 0: i is a candidate like any other.
+ *
+ * The result is a PLAN, like gnnmp_plan_concat / gnnmp_plan_select hand out graphs: the reference's adjacency list -> COO conversion
+ * (convert.jl:97-117) numbers the edges centre by centre, so the edge list is destination-sorted as it is produced and the kernels
+ * write the plan's arrays themselves — row i = centre i, its slots = i's neighbours, eid[e] = e — with no sort and no copy (what
+ * gnnmp_plan_from_csc(colptr, rowval) would build).  *out is owned by the caller (gnnmp_plan_destroy), n_src = n_dst = N, no self loops
+ * added.  The edge list in any index width and base: gnnmp_plan_edge_index(plan, idx_bytes, index_base, s, t) gives dir = :in
+ * (s = neighbour, t = centre); pass the two output pointers swapped for dir = :out, for which this plan is the plan of the REVERSED
+ * edges (t, s).  rowptr / degrees: gnnmp_plan_export64; the number of edges: gnnmp_plan_info.
+ *
+ *   gnnmp_knn_graph_f32     N k edges: edge i k + r joins centre i and its r-th nearest candidate, r in rank order.  1 <= k <= 1024
+ *                           (k > 64 runs ceil(k / 64) passes over the candidates).  A graph that occurs in the indicator with fewer
+ *                           than k (k + 1 without self loops) nodes — or N below that without an indicator — is GNNMP_EBOUNDS before the
+ *                           launch (the reference's @assert all(values(cm) .>= k)).
+ *   gnnmp_radius_graph_f32  j is a neighbour of i iff d2(i, j) <= r2, r2 = r * r formed once in fp32 (r >= 0; r < 0 or NaN:
+ *                           GNNMP_EINVAL).  Centres ascend, the neighbours of a centre ascend in j.  A count pass, an exclusive scan
+ *                           (the total is read on the host: it sizes the plan) and a write pass.
+ * Both synchronise the stream, as every plan build does (+ once for an indicator's checks, twice when it is unsorted).  Arguments are
+ * checked before any HIP call.  Workspace: the segment table, the scan's scratch and int64[N + 1]; no N x N or N x tile array exists
+ * in memory.  No atomics in the search kernels (the graph sizes of an UNSORTED indicator are counted with integer adds).
+ * N < 2^31 - 1, d <= 2^20, edges < GNNMP_MAX_SLOTS.
+ * ---------------------------------------------------------------------------------------------- */
+int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, int64_t k, const void *graph_indicator,
+                        int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
+int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float r, const void *graph_indicator,
+                           int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
  * (GraphNeuralNetworks/perf/bench_gnn.jl:9-10: `B = rand(100, n)`; it asserts isequal(propagate(e_mul_xj, g, +; xj = B, e), B * A)).  The
  * seam's methods and their leaves exist for `double` too — the same plan, the same walk, the same order of operations as the `_f32` entry
