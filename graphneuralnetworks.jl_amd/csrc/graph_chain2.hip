@@ -44,12 +44,12 @@ struct gnnmp_chain_jobs {
     int64_t max_graph = 0;     // largest member graph (> 64: no jobs, the general kernel runs)
     double fill = 0.0;         // rows / (32 x tiles): MFMA work spent on real rows
     int has_empty = 0;         // some member graph has no node (its logits are the head's bias: left to the general kernel)
-    int32_t *bad = nullptr;    // [3 + 4 njobs]: [0], [1] the counters of set-aside jobs of even / odd calls (each re-armed by the other parity's
-                               // finish kernel), [3..] (job * 2 + slab) of the tiles that met a non-finite operand in the running call
+    int32_t *bad = nullptr;    // [3 + 4 njobs]: [0] the counter of set-aside jobs, [2] the arrival ticket of the finish kernel's blocks (both
+                               // zero between calls: the finish kernel re-arms them), [3..] (job * 2 + slab) of the tiles that met a
+                               // non-finite operand in the running call
     int32_t *hdr = nullptr;    // device-packed handles: [0] jobs, [1] 32-row tiles, [2] poison (the sizes contradict what the caller announced:
                                // the finish kernel then writes NaN logits), [3] largest member graph seen, [4] member graphs without a node
     float *zrows = nullptr;    // [2][N][8] the two slabs' z of every row (each word written once per call: no atomics, no memset)
-    std::atomic<unsigned> calls{0};   // launches so far: picks the parity of the set-aside counters (a handle is used on ONE stream at a time)
     void *block = nullptr;     // the ONE device allocation behind tab, bad, hdr and zrows
     size_t block_bytes = 0;
 };
@@ -76,7 +76,7 @@ struct Chain2Args {
     float *zrows;       // [2][N][nout] z = W_head[:, slab] * h2 of every row: pooled by the finish kernel
     int G, N;
     long long *trace;   // (GNNMP_CHAIN_TRACE builds: cycle stamps of block (0, 0))
-    int32_t *bad_count, *bad_reset, *bad_list;     // this call's counter of set-aside jobs, the next call's (re-armed), job * 2 + slab
+    int32_t *bad_count, *bad_ticket, *bad_list;    // the counter of set-aside jobs, the finish kernel's arrival ticket, job * 2 + slab
 };
 
 __device__ __forceinline__ float4 c2_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -179,17 +179,28 @@ __device__ __forceinline__ void c2_pool_graph(const Chain2Args &a, int g, int sl
 }
 
 // The second (and last) launch of a call: the pooling.  If the main kernel set jobs aside (non-finite operands: normally none), block 0
-// alone first redoes them with fp32 loops and then pools every graph; the other blocks leave.  The counter of set-aside jobs alternates
-// between two words from call to call: this launch reads one (nobody writes it now) and re-arms the other for the next call.
+// alone first redoes them with fp32 loops and then pools every graph; the other blocks leave.  The call leaves its own state at zero: every
+// block reads the counter of set-aside jobs, then takes a ticket, and the block that takes the last one zeroes the counter and the ticket
+// (nobody reads or writes either any more in this call).  Nothing about the counter is decided on the host, so the same launch — a
+// replayed HIP graph — may follow itself any number of times.
 __global__ void __launch_bounds__(256) graph_chain2_finish_kernel(const Chain2Args a) {
+    __shared__ int s_nbad;
+    if (threadIdx.x == 0) s_nbad = *a.bad_count;
+    __syncthreads();
+    const int nbad = s_nbad;
+    if (threadIdx.x == 0) {            // (this block's read of the counter is complete: its value went through LDS above)
+        __threadfence();
+        if (atomicAdd(a.bad_ticket, 1) == (int)gridDim.x - 1) {
+            *a.bad_count = 0;
+            *a.bad_ticket = 0;
+        }
+    }
     if (a.hdr && a.hdr[2] != 0) {
         // the device packing found member graphs its caller had excluded (more than 64 nodes / none): no job ran.  Loud, not silent: NaN
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)a.G * a.nout; i += (int64_t)gridDim.x * 256)
             a.out[i] = __builtin_nanf("");
-        if (blockIdx.x == 0 && threadIdx.x == 0) *a.bad_reset = 0;
         return;
     }
-    const int nbad = *a.bad_count;
     if (nbad == 0) {
         const int i = blockIdx.x * 256 + threadIdx.x;                // (the grid covers 2 G lanes)
         c2_pool_graph(a, i >> 1, i & 1, threadIdx.x & 63);
@@ -201,7 +212,6 @@ __global__ void __launch_bounds__(256) graph_chain2_finish_kernel(const Chain2Ar
         __syncthreads();       // (block scope: the rows written above are read below by other waves of this block)
         for (int i = threadIdx.x; i < 2 * ((a.G + 127) / 128) * 128; i += 256) c2_pool_graph(a, i >> 1, i & 1, threadIdx.x & 63);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.bad_reset = 0;
 }
 
 // ---- wave PAIRS: one 32-row tile a wave --------------------------------------------------------------------------------------------------
@@ -999,9 +1009,8 @@ int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_
     a.mean_aggr = aggr == GNNMP_MEAN;
     a.pool_mean = pool_aggr == GNNMP_MEAN;
     a.out = out;
-    const unsigned parity = const_cast<gnnmp_chain_jobs_t *>(J)->calls.fetch_add(1u, std::memory_order_relaxed) & 1u;
-    a.bad_count = J->bad + parity;
-    a.bad_reset = J->bad + (parity ^ 1u);
+    a.bad_count = J->bad;
+    a.bad_ticket = J->bad + 2;
     a.bad_list = J->bad + 3;
     a.zrows = J->zrows;
     a.N = (int)J->N;

@@ -23,6 +23,16 @@
  *     partials and arrival counters — the split rows are folded inside the row kernels by the last
  *     chunk to arrive, not by a second launch).  gnnmp_plan_create synchronises `stream` (it is graph prep, done
  *     once per graph, outside the timed path).
+ *   - stream capture (hipStreamBeginCapture / a HIP graph): a compute entry point may be recorded into a graph and replayed, with new
+ *     values in the same buffers, any number of times back to back — ONE eager call with the same plan, entry point and D must come
+ *     first (it grows the plan's scratch and opts the kernel into large LDS where it needs it; the exception above).  Not recordable:
+ *     the calls whose comment says that they synchronise (plan builds and the other graph prep: gnnmp_batch_coo,
+ *     gnnmp_sort_edge_index, gnnmp_unique_append, gnnmp_induced_subgraph, gnnmp_sample_neighbors, gnnmp_rand_edge_split,
+ *     gnnmp_negative_sample, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
+ *     thread_local): every other export of the case table of tests/abi_cases.py, and gnnmp_graphconv_chain_f32 through the Python
+ *     mirror.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
+ *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
  *     orderings): calls that take the SAME plan must be ordered on ONE stream (or by events) — two streams may run
  *     different plans, or read-only queries of one plan, concurrently, but not two compute calls on one plan.  The
@@ -252,7 +262,8 @@ int gnnmp_add_self_loops(const void *src, const void *dst, int idx_bytes, int in
  * src/dst hold the member graphs' edge indices concatenated (local numbering); edge_ptr[G+1] and
  * node_ptr[G+1] are int64 device arrays of exclusive prefix sums of num_edges / num_nodes.
  * Writes the offset indices (same width/base) and graph_indicator[N] (same width; values
- * index_base .. index_base+G-1, i.e. 1..G for Julia). */
+ * index_base .. index_base+G-1, i.e. 1..G for Julia).
+ * Synchronises the stream (graph prep: the two totals are read on the host). */
 int gnnmp_batch_coo(const void *src, const void *dst, int idx_bytes, int index_base,
                     const int64_t *edge_ptr, const int64_t *node_ptr, int64_t n_graphs,
                     void *out_src, void *out_dst, void *graph_indicator, gnnmp_stream_t stream);
@@ -297,7 +308,8 @@ int gnnmp_unique_append(int32_t *map, int32_t *first, int64_t n_nodes, const voi
  * i, eid_out = the edge's position in g.  `map` as built by gnnmp_unique_append from the same list (nodes must be valid
  * and distinct).  offsets[n_nodes + 1] (device int64) = first output edge of every listed node; *total (host) = edge
  * count; capacity as in gnnmp_sample_neighbors (capacity = 0 with NULL outputs = count-only call).  NB the reference records `findfirst` of the (source, target) pair as the
- * edge index, i.e. the FIRST parallel edge for all copies of a multi-edge; this returns each copy's own position. */
+ * edge index, i.e. the FIRST parallel edge for all copies of a multi-edge; this returns each copy's own position.
+ * Synchronises the stream (the count is read on the host). */
 int gnnmp_induced_subgraph(gnnmp_graph_t *plan, const int32_t *map, const void *nodes, int idx_bytes,
                            int index_base, int64_t n_nodes, int64_t *offsets, void *s_out, void *t_out,
                            void *eid_out, int64_t capacity, int64_t *total, gnnmp_stream_t stream);
@@ -694,8 +706,8 @@ int64_t gnnmp_graphconv_chain_scratch_floats(int64_t N, int n_layers, const int6
  * a 4 KB LDS stage the two waves share, the two 64-column halves of layer 2 go to different workgroups; each row's W_head * h2 — nout
  * floats per half — is the only intermediate written, and a second small launch pools it per member graph in node order: no
  * floating-point atomic, no memset, run-to-run identical).  The handle owns that intermediate and the list of jobs set aside for the
- * exact fp32 path (non-finite operands), so — like a plan's workspace — it serves ONE stream at a time (and one host thread at a time:
- * the chain call picks the parity of its set-aside counters from a per-handle call count).
+ * exact fp32 path (non-finite operands), so — like a plan's workspace — it serves ONE stream at a time.  The list's counter is re-armed on
+ * the device by the call's own last launch: nothing about it is chosen on the host, and a recorded call may be replayed back to back.
  * Built once per batched graph from the DEVICE seg_ptr; synchronises `stream` (graph prep).  A batch with a member graph of more than
  * 64 nodes, or without any, yields a handle without jobs: the chain then runs on the general kernel.  info[0] = jobs, [1] = member
  * graphs, [2] = rows, [3] = largest member graph, [4] = per-mille of the MFMA tiles' rows that are real rows. */

@@ -149,6 +149,24 @@ class Slab:
     def ptr(self, name):
         return ctypes.c_void_p(self.t.data_ptr() + self.arrs[name].off)
 
+    def reload(self, inputs=None):
+        """the slab as before a call, at the SAME device addresses: poison in every output, scratch array and guard band, the initial
+        data in every in / inout array.  inputs: {name: array} replaces the data of those in / inout arrays (same shape and type)"""
+        import torch
+        host = self.before.copy()
+        for name, data in (inputs or {}).items():
+            a = self.arrs[name]
+            data = np.ascontiguousarray(data)
+            assert a.role in ("in", "inout") and data.shape == a.shape and data.dtype == a.dtype, name
+            host[a.off:a.off + a.nbytes] = data.reshape(-1).view(np.uint8)
+        self.before = host
+        self.t.copy_(torch.from_numpy(host.copy()))
+
+    def outputs(self):
+        """the bytes of every out / inout array as they are on the device now"""
+        after = self.t.cpu().numpy()
+        return {a.name: after[a.off:a.off + a.nbytes].copy() for a in self.arrs.values() if a.role in ("out", "inout")}
+
     def _where(self, byte):
         best = None
         for a in self.arrs.values():
@@ -369,10 +387,8 @@ class Case:
         self.uses_plan = any(isinstance(a, Pl) for a in args)
 
 
-def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):
-    """one call with every array inside a fresh slab.  Returns (status, slab, host results)"""
-    import torch
-    slab = Slab(case.arrs, device, shifts, case.guard)
+def bind(case, slab, plans, stream=None):
+    """the ctypes arguments of one call: pointers into the slab, plan handles, the stream.  Returns (arguments, host results)"""
     host, cargs = {}, []
     for a in case.args:
         if isinstance(a, Arr):
@@ -387,16 +403,29 @@ def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):
             cargs.append(None if stream is None else ctypes.c_void_p(stream.cuda_stream))
         else:
             cargs.append(a)
-    if stream is not None:
-        torch.cuda.synchronize()       # the default stream is idle while the side stream works
+    return cargs, host
+
+
+def call(lib, case, cargs):
+    """the one library call of a case, under its tuning knobs"""
     for k, v in case.knobs.items():
         assert lib.gnnmp_tune(k, v) == OK
     try:
-        rc = getattr(lib, case.export)(*cargs)
-        torch.cuda.synchronize()
+        return getattr(lib, case.export)(*cargs)
     finally:
         for k in case.knobs:
             lib.gnnmp_tune(k, 0)
+
+
+def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):
+    """one call with every array inside a fresh slab.  Returns (status, slab, host results)"""
+    import torch
+    slab = Slab(case.arrs, device, shifts, case.guard)
+    cargs, host = bind(case, slab, plans, stream)
+    if stream is not None:
+        torch.cuda.synchronize()       # the default stream is idle while the side stream works
+    rc = call(lib, case, cargs)
+    torch.cuda.synchronize()
     return rc, slab, {k: v.value for k, v in host.items()}
 
 
@@ -419,8 +448,41 @@ IDX = ((8, 1), (4, 1), (8, 0), (4, 0))                   # (idx_bytes, index_bas
 f32, f64 = np.float32, np.float64
 
 
+_VARIANT = [0]      # the variant of the Ctx whose cases are being built (set by the TABLE wrappers below, read by rng_of)
+
+
+class Rng:
+    """the generator a case builder draws from.  Integer draws and permutations (graphs, index arrays, segment ids) always come from the
+    stream seeded by the case's key alone: every variant of a case has the same graphs, shapes, index arrays and plans.  Float draws
+    come from that stream for variant 0 (bit for bit the data the table always had); for any other variant they advance it all the same
+    (the integer draws after them stay in step) and return values from a second stream seeded by (key, variant)"""
+
+    def __init__(self, seed, variant):
+        self.base = np.random.default_rng(seed)
+        self.alt = np.random.default_rng([seed, int(variant)]) if variant else None
+
+    def integers(self, *a, **k):
+        return self.base.integers(*a, **k)
+
+    def permutation(self, *a, **k):
+        return self.base.permutation(*a, **k)
+
+    def uniform(self, *a, **k):
+        v = self.base.uniform(*a, **k)
+        return v if self.alt is None else self.alt.uniform(*a, **k)
+
+    def random(self, *a, **k):
+        v = self.base.random(*a, **k)
+        return v if self.alt is None else self.alt.random(*a, **k)
+
+    def counts(self, lo, hi, n):
+        """integers that are float DATA of the case (degrees), not indices: they differ between variants"""
+        v = self.base.integers(lo, hi, n)
+        return v if self.alt is None else self.alt.integers(lo, hi, n)
+
+
 def rng_of(*key):
-    return np.random.default_rng(zlib.crc32(repr(key).encode()))
+    return Rng(zlib.crc32(repr(key).encode()), _VARIANT[0])
 
 
 def F(rng, *shape, dtype=f32):
@@ -456,10 +518,12 @@ def act64(code, x):
 
 class Ctx:
     """the graphs every plan-taking case runs on.  thr: the plan's long-row threshold (read from the library on the GPU; the header's
-    GNNMP_MIN_LONG_ROW for the CPU dry run of the table)"""
+    GNNMP_MIN_LONG_ROW for the CPU dry run of the table).  variant: the same cases — graphs, shapes, index arrays, plans — with other
+    float inputs, hence other references (tests/test_abi_graph_capture.py replays a captured call on them)"""
 
-    def __init__(self, thr):
+    def __init__(self, thr, variant=0):
         self.thr = int(thr)
+        self.variant = int(variant)                     # salts the float inputs of every case (rng_of): 0 = the table's own data
         self.hub = hub_graph(self.thr)
         self.e0 = Graph("edgeless", [], [], 5)
         self.one = Graph("one", [1, 1], [1, 1], 1)
@@ -826,7 +890,7 @@ NS = ((1, ()), (3, {"align"}), (6, {"align"}), (31, ()), (33, ()), (128, {"align
 @cases_of("gnnmp_inv_sqrt_f32")
 def _(ctx):
     for n, tags in NS:
-        d = (1.0 + rng_of("inv_sqrt", n).integers(0, 50, n)).astype(f32)
+        d = (1.0 + rng_of("inv_sqrt", n).counts(0, 50, n)).astype(f32)
         yield mk("gnnmp_inv_sqrt_f32", f"n{n}", tags, [Arr("deg", "in", d), Arr("out", "out", shape=(n,)), n, STREAM],
                  lambda host, d=d: {"out": E(orc().inv_sqrt(d), "exact")})
 
@@ -1779,3 +1843,73 @@ EXCLUDED_EXTRA = {
     "gnnmp_negative_sample": "random draws with a host-side trial loop: no deterministic reference for the written prefix (tests/test_linkpred.py: properties)",
     "gnnmp_sample_neighbors": "random draws: parity is distributional (tests/test_graphprep.py); the written prefix has no exact reference",
 }
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# variants: TABLE[export](ctx) builds the cases of ctx.variant
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _of_variant(build):
+    def cases(ctx):
+        prev = _VARIANT[0]
+        _VARIANT[0] = getattr(ctx, "variant", 0)
+        try:
+            return list(build(ctx))          # the builders are generators: every draw happens here, under the ctx's variant
+        finally:
+            _VARIANT[0] = prev
+    return cases
+
+
+TABLE = {export: _of_variant(build) for export, build in TABLE.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the no-sync, no-alloc rule (include/gnnmp.h, Conventions): which exports of the table may be recorded into a HIP graph
+# ------------------------------------------------------------------------------------------------------------------------------------
+# An export of TABLE is CAPTURABLE — it only launches on the stream it is given — unless it is named here with the words of its own
+# comment in include/gnnmp.h (or of its paragraph in the section comment that governs it) that say it waits for the stream or allocates.
+# tests/test_abi_graph_capture.py checks the quotes against the header and captures, replays and re-feeds every other export.
+SYNCHRONISES = {
+    "gnnmp_batch_coo": "Synchronises the stream (graph prep: the two totals are read on the host)",
+    "gnnmp_sort_edge_index": "Synchronises the stream (graph prep)",
+    "gnnmp_unique_append": "Synchronises the stream",
+    "gnnmp_induced_subgraph": "Synchronises the stream (the count is read on the host)",
+    "gnnmp_rand_edge_split": "Synchronisations: 1 (the permutation's sort) + 1 when bidirected",
+}
+ALLOCATES = {}
+WAITS_OR_ALLOCATES = re.compile(r"synchronis|hipMalloc|allocat", re.I)
+
+
+def capturable():
+    return sorted(e for e in TABLE if e not in SYNCHRONISES and e not in ALLOCATES)
+
+
+def _squash(text):
+    return " ".join(text.replace("*", " ").split())
+
+
+def header_comments_of(export, path=HEADER):
+    """the comment text of the RAW header that speaks for one export, whitespace-normalised: the comments that stand directly in front of
+    its declaration, and — from the section comment (the one ruled off with dashes) that governs it — the paragraph headed by the
+    export's name, or the whole section comment if it has no paragraph per export"""
+    text = open(path).read()
+    code = re.sub(r"/\*.*?\*/", lambda c: " " * len(c.group(0)), text, flags=re.S)          # same offsets, comments blanked
+    m = re.search(r"\b%s\s*\(" % re.escape(export), code)
+    assert m, f"{export} is not declared in the header"
+    comments = [c for c in re.finditer(r"/\*.*?\*/", text, flags=re.S) if c.end() <= m.start()]
+    own, end = [], code.rfind(";", 0, m.start()) + 1          # back to the end of the previous declaration
+    for c in reversed(comments):
+        if c.start() < end or "-----" in c.group(0):
+            break
+        own.append(c.group(0)[2:-2])
+    out = [_squash(t) for t in own]
+    section = next((c.group(0)[2:-2] for c in reversed(comments) if "-----" in c.group(0)), None)
+    if section is not None:
+        heads = list(re.finditer(r"^ \*   (gnnmp_\w+)\b", section, flags=re.M))
+        mine = [k for k, h in enumerate(heads) if h.group(1) == export]
+        if mine:
+            k = mine[0]
+            stop = heads[k + 1].start() if k + 1 < len(heads) else section.find("-----", heads[k].start())
+            out.append(_squash(section[heads[k].start():stop if stop > 0 else len(section)]))
+        elif not heads:
+            out.append(_squash(section))
+    return out
