@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <stdint.h>
 #include "gnnmp.h"
@@ -16,6 +17,13 @@ int hip_fail(hipError_t e, const char *what);
     do {                                                        \
         hipError_t e__ = (expr);                                \
         if (e__ != hipSuccess) return ::gnnmp::hip_fail(e__, #expr); \
+    } while (0)
+
+// the same for a library status: returns it unless it is GNNMP_OK
+#define GNNMP_TRY(expr)                                         \
+    do {                                                        \
+        const int rc__ = (expr);                                \
+        if (rc__ != GNNMP_OK) return rc__;                      \
     } while (0)
 
 #define GNNMP_LAUNCH_CHECK(what)                                \
@@ -373,6 +381,11 @@ struct gnnmp_graph {
 };
 
 namespace gnnmp {
+// a plan under construction: destroyed on every exit that does not release() it to the caller
+struct __attribute__((visibility("hidden"))) PlanDeleter {
+    void operator()(gnnmp_graph *p) const { (void)gnnmp_plan_destroy(p); }
+};
+using PlanPtr = std::unique_ptr<gnnmp_graph, PlanDeleter>;
 // make sure plan->ws holds at least `floats` floats (hipMalloc on growth; hipFree waits for in-flight work)
 int ensure_workspace(gnnmp_graph *p, size_t floats);
 // make sure plan->arrive holds at least n zeroed counters and plan->spart at least `floats` floats.

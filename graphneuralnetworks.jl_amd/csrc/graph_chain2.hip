@@ -29,6 +29,7 @@
 // else is graph_chain.hip's.
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -764,12 +765,12 @@ extern "C" int gnnmp_chain_jobs_create(gnnmp_chain_jobs_t **out, const int64_t *
         GNNMP_HIP(hipMemcpyAsync(sp.data(), seg_ptr, sizeof(int64_t) * (size_t)(G + 1), hipMemcpyDeviceToHost, stream));
         GNNMP_HIP(hipStreamSynchronize(stream));
     }
-    gnnmp_chain_jobs *J = new gnnmp_chain_jobs();
+    std::unique_ptr<gnnmp_chain_jobs> J(new gnnmp_chain_jobs());   // (the handle dies on every exit that does not release() it)
     J->G = G;
     J->N = G > 0 ? sp[(size_t)G] - sp[0] : 0;
     for (int64_t g = 0; g < G; ++g) J->max_graph = std::max(J->max_graph, sp[(size_t)g + 1] - sp[(size_t)g]);
     if (J->max_graph > 64 || J->N >= ((int64_t)1 << 31) || G == 0) {   // no jobs: the caller's chain runs on the general kernel
-        *out = J;
+        *out = J.release();
         return GNNMP_OK;
     }
     // best fit decreasing: graphs by decreasing size (ties by id: a counting sort, sizes are 1..64), each into the fullest job that
@@ -828,10 +829,7 @@ extern "C" int gnnmp_chain_jobs_create(gnnmp_chain_jobs_t **out, const int64_t *
         const size_t off_bad = (bytes + 255) & ~(size_t)255;
         const size_t off_z = (off_bad + sizeof(int32_t) * (size_t)(3 + 4 * njobs) + 255) & ~(size_t)255;
         const size_t total = off_z + sizeof(float) * (size_t)2 * (size_t)J->N * 8;
-        if (!pool_take(&J->block, &J->block_bytes, total, stream)) {
-            delete J;
-            return fail(GNNMP_EALLOC, "chain_jobs_create: hipMalloc failed");
-        }
+        if (!pool_take(&J->block, &J->block_bytes, total, stream)) return fail(GNNMP_EALLOC, "chain_jobs_create: hipMalloc failed");
         unsigned char *base = static_cast<unsigned char *>(J->block);
         J->tab = reinterpret_cast<int32_t *>(base);
         J->bad = reinterpret_cast<int32_t *>(base + off_bad);
@@ -842,11 +840,10 @@ extern "C" int gnnmp_chain_jobs_create(gnnmp_chain_jobs_t **out, const int64_t *
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e != hipSuccess) {                 // (the block goes back, the handle does not leak)
             pool_park(J->block, J->block_bytes, stream, false);
-            delete J;
             return hip_fail(e, "chain_jobs_create: upload of the job table");
         }
     }
-    *out = J;
+    *out = J.release();
     return GNNMP_OK;
 }
 
@@ -875,13 +872,13 @@ extern "C" int gnnmp_chain_jobs_pack(gnnmp_chain_jobs_t **out, const int64_t *se
     hipStream_t stream = (hipStream_t)stream_;
     if (!out || G < 0 || n_rows < 0 || max_graph < 0 || (G > 0 && !seg_ptr)) return fail(GNNMP_EINVAL, "chain_jobs_pack: bad argument");
     *out = nullptr;
-    gnnmp_chain_jobs *J = new gnnmp_chain_jobs();
+    std::unique_ptr<gnnmp_chain_jobs> J(new gnnmp_chain_jobs());   // (the handle dies on every exit that does not release() it)
     J->G = G;
     J->N = n_rows;
     J->max_graph = max_graph;
     J->has_empty = has_empty ? 1 : 0;
     if (max_graph > 64 || has_empty || n_rows >= ((int64_t)1 << 31) || G >= ((int64_t)1 << 31) || G == 0 || n_rows == 0) {
-        *out = J;                                    // no jobs: the caller's chain runs on the general kernel
+        *out = J.release();                          // no jobs: the caller's chain runs on the general kernel
         return GNNMP_OK;
     }
     // any best fit leaves at most one job half empty: jobs <= 2 N / 64 + 1; and every job holds a graph
@@ -893,10 +890,8 @@ extern "C" int gnnmp_chain_jobs_pack(gnnmp_chain_jobs_t **out, const int64_t *se
     const size_t off_pst = (off_sorted + sizeof(int32_t) * (size_t)G + 255) & ~(size_t)255;
     const size_t off_z = (off_pst + sizeof(PackState) + 255) & ~(size_t)255;
     const size_t total = off_z + sizeof(float) * (size_t)2 * (size_t)n_rows * 8;
-    if (!pool_take(&J->block, &J->block_bytes, total, stream)) {
-        delete J;
+    if (!pool_take(&J->block, &J->block_bytes, total, stream))
         return fail(GNNMP_EALLOC, "chain_jobs_pack: hipMalloc of %zu bytes failed", total);
-    }
     unsigned char *base = static_cast<unsigned char *>(J->block);
     J->tab = reinterpret_cast<int32_t *>(base);
     J->bad = reinterpret_cast<int32_t *>(base + off_bad);
@@ -925,10 +920,9 @@ extern "C" int gnnmp_chain_jobs_pack(gnnmp_chain_jobs_t **out, const int64_t *se
     }
     if (e != hipSuccess) {
         pool_park(J->block, J->block_bytes, stream, true);
-        delete J;
         return hip_fail(e, "chain_pack_kernel");
     }
-    *out = J;
+    *out = J.release();
     return GNNMP_OK;
 }
 

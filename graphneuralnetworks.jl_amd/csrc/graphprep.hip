@@ -11,6 +11,7 @@
 
 
 #include "common.h"
+#include "scratch.h"
 #include "sort_scan.h"
 
 namespace gnnmp {
@@ -45,82 +46,22 @@ __global__ void self_loop_kernel(const void *u, const void *v, int idx_bytes, in
     if (k < E && load_index(u, k, idx_bytes, 0) == load_index(v, k, idx_bytes, 0)) *flag = 1;
 }
 
-#define PREP_HIP(expr)                                  \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-#define PREP_G(expr)                                    \
-    do {                                                \
-        rc = (expr);                                    \
-        if (rc != GNNMP_OK) goto done;                  \
-    } while (0)
-
 // sorted keys of the pairs (first, second) into keys_out (device, E entries); scratch freed before returning
 static int sorted_pair_keys(const void *first, const void *second, int idx_bytes, int base, int64_t E, uint64_t *keys_out,
                             hipStream_t stream) {
-    int rc = GNNMP_OK;
-    uint64_t *keys_in = nullptr;
-    int *flag = nullptr;
+    DevBuf<int> flag;
+    DevBuf<uint64_t> keys_in;
+    GNNMP_HIP(keys_in.alloc((size_t)std::max<int64_t>(E, 1)));
+    GNNMP_HIP(flag.alloc(1));
+    GNNMP_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), stream));
+    pack_pairs_kernel<<<nb(E), 256, 0, stream>>>(first, second, idx_bytes, base, E, keys_in.get(), flag.get());
+    GNNMP_HIP(hipGetLastError());
+    GNNMP_TRY(radix_sort_keys_u64(keys_in.get(), keys_out, (size_t)E, 0, 64, stream));
     int hflag = 0;
-    PREP_HIP(hipMalloc((void **)&keys_in, sizeof(uint64_t) * (size_t)std::max<int64_t>(E, 1)));
-    PREP_HIP(hipMalloc((void **)&flag, sizeof(int)));
-    PREP_HIP(hipMemsetAsync(flag, 0, sizeof(int), stream));
-    pack_pairs_kernel<<<nb(E), 256, 0, stream>>>(first, second, idx_bytes, base, E, keys_in, flag);
-    PREP_HIP(hipGetLastError());
-    PREP_G(radix_sort_keys_u64(keys_in, keys_out, (size_t)E, 0, 64, stream));
-    PREP_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipStreamSynchronize(stream));
-    if (hflag) rc = fail(GNNMP_EBOUNDS, "sort_edge_index: an index is negative or does not fit 32 bits");
-done:
-    if (keys_in) (void)hipFree(keys_in);
-    if (flag) (void)hipFree(flag);
-    return rc;
-}
-
-// Scratch for the per-mini-batch entry points (sample_neighbors, unique_append, induced_subgraph): hipMalloc / hipFree cost
-// ~0.1-1 ms each and a NeighborLoader batch made ~50 of them.  Freed blocks are parked in a small per-thread cache and
-// handed out again (every entry point synchronises its stream before returning, so a parked block is idle).
-// A block is only handed out on the device it was allocated on (dev = common.h's current_device at allocation; alloc and free of one
-// entry point run under the same current device).
-struct PrepBlock { void *p; size_t cap; int dev; };
-static thread_local PrepBlock g_prep_cache[8] = {};
-static hipError_t prep_alloc(void **out, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 256);
-    const int dev = current_device();
-    int best = -1;
-    for (int i = 0; i < 8; ++i)
-        if (g_prep_cache[i].p && g_prep_cache[i].dev == dev && g_prep_cache[i].cap >= bytes &&
-            (best < 0 || g_prep_cache[i].cap < g_prep_cache[best].cap))
-            best = i;
-    if (best >= 0 && g_prep_cache[best].cap <= 4 * bytes + (1 << 20)) {
-        *out = g_prep_cache[best].p;
-        g_prep_cache[best] = PrepBlock{nullptr, 0, 0};
-        return hipSuccess;
-    }
-    return hipMalloc(out, bytes);
-}
-static void prep_free(void *p, size_t bytes) {
-    if (!p) return;
-    bytes = std::max<size_t>(bytes, 256);
-    const int dev = current_device();
-    int slot = -1;
-    for (int i = 0; i < 8; ++i)
-        if (!g_prep_cache[i].p) { slot = i; break; }
-    if (slot < 0) {   // cache full: evict the smallest block
-        slot = 0;
-        for (int i = 1; i < 8; ++i)
-            if (g_prep_cache[i].cap < g_prep_cache[slot].cap) slot = i;
-        if (g_prep_cache[slot].cap >= bytes) {
-            (void)hipFree(p);
-            return;
-        }
-        (void)hipFree(g_prep_cache[slot].p);
-    }
-    g_prep_cache[slot] = PrepBlock{p, bytes, dev};
+    GNNMP_HIP(hipMemcpyAsync(&hflag, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    if (hflag) return fail(GNNMP_EBOUNDS, "sort_edge_index: an index is negative or does not fit 32 bits");
+    return GNNMP_OK;
 }
 
 // ---- neighbour sampling ---------------------------------------------------------------------------
@@ -314,17 +255,13 @@ int gnnmp_sort_edge_index(const void *u, const void *v, int idx_bytes, int index
     if (n_edges < 0) return fail(GNNMP_EINVAL, "sort_edge_index: negative size");
     if (n_edges == 0) return GNNMP_OK;
     if (!u || !v || !u_out || !v_out) return fail(GNNMP_EINVAL, "sort_edge_index: null pointer");
-    uint64_t *keys = nullptr;
-    if (hipMalloc((void **)&keys, sizeof(uint64_t) * (size_t)n_edges) != hipSuccess)
-        return fail(GNNMP_EALLOC, "sort_edge_index: hipMalloc");
-    int rc = sorted_pair_keys(u, v, idx_bytes, index_base, n_edges, keys, stream);
-    if (rc == GNNMP_OK) {
-        unpack_pairs_kernel<<<nb(n_edges), 256, 0, stream>>>(keys, idx_bytes, index_base, n_edges, u_out, v_out);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-            rc = fail(GNNMP_ELAUNCH, "sort_edge_index: unpack");
-    }
-    (void)hipFree(keys);
-    return rc;
+    DevBuf<uint64_t> keys;
+    if (keys.alloc((size_t)n_edges) != hipSuccess) return fail(GNNMP_EALLOC, "sort_edge_index: hipMalloc");
+    GNNMP_TRY(sorted_pair_keys(u, v, idx_bytes, index_base, n_edges, keys.get(), stream));
+    unpack_pairs_kernel<<<nb(n_edges), 256, 0, stream>>>(keys.get(), idx_bytes, index_base, n_edges, u_out, v_out);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return fail(GNNMP_ELAUNCH, "sort_edge_index: unpack");
+    return GNNMP_OK;
 }
 
 int gnnmp_is_bidirected(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int *result,
@@ -335,30 +272,20 @@ int gnnmp_is_bidirected(const void *s, const void *t, int idx_bytes, int index_b
     *result = 1;
     if (n_edges <= 0) return n_edges < 0 ? fail(GNNMP_EINVAL, "is_bidirected: negative size") : GNNMP_OK;
     if (!s || !t) return fail(GNNMP_EINVAL, "is_bidirected: null pointer");
-    uint64_t *a = nullptr, *b = nullptr;
-    int *flag = nullptr;
-    int rc = GNNMP_OK, h = 0;
-    if (hipMalloc((void **)&a, sizeof(uint64_t) * (size_t)n_edges) != hipSuccess ||
-        hipMalloc((void **)&b, sizeof(uint64_t) * (size_t)n_edges) != hipSuccess ||
-        hipMalloc((void **)&flag, sizeof(int)) != hipSuccess) {
-        rc = fail(GNNMP_EALLOC, "is_bidirected: hipMalloc");
-    } else {
-        rc = sorted_pair_keys(s, t, idx_bytes, index_base, n_edges, a, stream);
-        if (rc == GNNMP_OK) rc = sorted_pair_keys(t, s, idx_bytes, index_base, n_edges, b, stream);
-        if (rc == GNNMP_OK) {
-            (void)hipMemsetAsync(flag, 0, sizeof(int), stream);
-            keys_differ_kernel<<<nb(n_edges), 256, 0, stream>>>(a, b, n_edges, flag);
-            if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess)
-                rc = fail(GNNMP_ELAUNCH, "is_bidirected: compare");
-            else
-                *result = h ? 0 : 1;
-        }
-    }
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (flag) (void)hipFree(flag);
-    return rc;
+    DevBuf<int> flag;
+    DevBuf<uint64_t> b, a;
+    if (a.alloc((size_t)n_edges) != hipSuccess || b.alloc((size_t)n_edges) != hipSuccess || flag.alloc(1) != hipSuccess)
+        return fail(GNNMP_EALLOC, "is_bidirected: hipMalloc");
+    GNNMP_TRY(sorted_pair_keys(s, t, idx_bytes, index_base, n_edges, a.get(), stream));
+    GNNMP_TRY(sorted_pair_keys(t, s, idx_bytes, index_base, n_edges, b.get(), stream));
+    int h = 0;
+    if (hipMemsetAsync(flag.get(), 0, sizeof(int), stream) != hipSuccess) return fail(GNNMP_ELAUNCH, "is_bidirected: compare");
+    keys_differ_kernel<<<nb(n_edges), 256, 0, stream>>>(a.get(), b.get(), n_edges, flag.get());
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+        return fail(GNNMP_ELAUNCH, "is_bidirected: compare");
+    *result = h ? 0 : 1;
+    return GNNMP_OK;
 }
 
 int gnnmp_has_self_loops(const void *s, const void *t, int idx_bytes, int64_t n_edges, int *result,
@@ -369,18 +296,16 @@ int gnnmp_has_self_loops(const void *s, const void *t, int idx_bytes, int64_t n_
     *result = 0;
     if (n_edges <= 0) return n_edges < 0 ? fail(GNNMP_EINVAL, "has_self_loops: negative size") : GNNMP_OK;
     if (!s || !t) return fail(GNNMP_EINVAL, "has_self_loops: null pointer");
-    int *flag = nullptr;
+    DevBuf<int> flag;
+    if (flag.alloc(1) != hipSuccess) return fail(GNNMP_EALLOC, "has_self_loops: hipMalloc");
     int h = 0;
-    if (hipMalloc((void **)&flag, sizeof(int)) != hipSuccess) return fail(GNNMP_EALLOC, "has_self_loops: hipMalloc");
-    (void)hipMemsetAsync(flag, 0, sizeof(int), stream);
-    self_loop_kernel<<<nb(n_edges), 256, 0, stream>>>(s, t, idx_bytes, n_edges, flag);
-    int rc = GNNMP_OK;
-    if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    if (hipMemsetAsync(flag.get(), 0, sizeof(int), stream) != hipSuccess) return fail(GNNMP_ELAUNCH, "has_self_loops");
+    self_loop_kernel<<<nb(n_edges), 256, 0, stream>>>(s, t, idx_bytes, n_edges, flag.get());
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess)
-        rc = fail(GNNMP_ELAUNCH, "has_self_loops");
+        return fail(GNNMP_ELAUNCH, "has_self_loops");
     *result = h;
-    (void)hipFree(flag);
-    return rc;
+    return GNNMP_OK;
 }
 
 int gnnmp_sample_neighbors(gnnmp_graph_t *plan, const void *nodes, int idx_bytes, int index_base, int64_t n_nodes,
@@ -399,47 +324,37 @@ int gnnmp_sample_neighbors(gnnmp_graph_t *plan, const void *nodes, int idx_bytes
         return GNNMP_OK;
     }
     if (!nodes) return fail(GNNMP_EINVAL, "sample_neighbors: null nodes");
-    int rc = GNNMP_OK;
-    int64_t *counts = nullptr;
-    int *flag = nullptr;
-    int hflag = 0;
-    int64_t tot = 0;
     // (+ the scan's block sums behind the counts: one pooled block, no allocation or synchronisation inside the scan)
     const size_t counts_elems = (size_t)(n_nodes + 1) + exclusive_scan_workspace((size_t)(n_nodes + 1));
-    PREP_HIP(prep_alloc((void **)&counts, sizeof(int64_t) * counts_elems));
-    PREP_HIP(prep_alloc((void **)&flag, sizeof(int)));
-    PREP_HIP(hipMemsetAsync(flag, 0, sizeof(int), stream));
-    PREP_HIP(hipMemsetAsync(counts + n_nodes, 0, sizeof(int64_t), stream));
+    DevBuf<int> flag(Scratch::PrepCache);
+    DevBuf<int64_t> counts(Scratch::PrepCache);
+    GNNMP_HIP(counts.alloc(counts_elems));
+    GNNMP_HIP(flag.alloc(1));
+    GNNMP_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), stream));
+    GNNMP_HIP(hipMemsetAsync(counts.get() + n_nodes, 0, sizeof(int64_t), stream));
     sample_counts_kernel<<<nb(n_nodes), 256, 0, stream>>>(plan->rowptr, nodes, idx_bytes, index_base, n_nodes, plan->n_dst,
-                                                          K, replace, counts, flag);
-    PREP_HIP(hipGetLastError());
-    PREP_G(exclusive_scan_i64(counts, offsets, (size_t)(n_nodes + 1), stream, counts + n_nodes + 1));
-    PREP_HIP(hipMemcpyAsync(&tot, offsets + n_nodes, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipStreamSynchronize(stream));
-    if (hflag) {
-        rc = fail(GNNMP_EBOUNDS, "sample_neighbors: a seed node is outside 1..%lld", (long long)plan->n_dst);
-        goto done;
-    }
+                                                          K, replace, counts.get(), flag.get());
+    GNNMP_HIP(hipGetLastError());
+    GNNMP_TRY(exclusive_scan_i64(counts.get(), offsets, (size_t)(n_nodes + 1), stream, counts.get() + n_nodes + 1));
+    int hflag = 0;
+    int64_t tot = 0;
+    GNNMP_HIP(hipMemcpyAsync(&tot, offsets + n_nodes, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipMemcpyAsync(&hflag, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    counts.synced();   // (nothing below touches the scratch: it may be parked from here on)
+    flag.synced();
+    if (hflag) return fail(GNNMP_EBOUNDS, "sample_neighbors: a seed node is outside 1..%lld", (long long)plan->n_dst);
     *total = tot;
-    if (tot > capacity) {
-        rc = fail(GNNMP_EINVAL, "sample_neighbors: %lld edge ids do not fit the capacity %lld (offsets are valid: retry)",
-                  (long long)tot, (long long)capacity);
-        goto done;
-    }
+    if (tot > capacity)
+        return fail(GNNMP_EINVAL, "sample_neighbors: %lld edge ids do not fit the capacity %lld (offsets are valid: retry)",
+                    (long long)tot, (long long)capacity);
     if (tot > 0) {
-        if (!eids_out) {
-            rc = fail(GNNMP_EINVAL, "sample_neighbors: null eids_out");
-            goto done;
-        }
+        if (!eids_out) return fail(GNNMP_EINVAL, "sample_neighbors: null eids_out");
         sample_fill_kernel<<<nb(n_nodes), 256, 0, stream>>>(plan->rowptr, plan->eid, nodes, idx_bytes, index_base, n_nodes, K,
                                                             replace ? 1 : 0, seed, offsets, eids_out);
-        PREP_HIP(hipGetLastError());
+        GNNMP_HIP(hipGetLastError());
     }
-done:
-    prep_free(counts, sizeof(int64_t) * ((size_t)(n_nodes + 1) + exclusive_scan_workspace((size_t)(n_nodes + 1))));
-    prep_free(flag, sizeof(int));
-    return rc;
+    return GNNMP_OK;
 }
 
 int gnnmp_unique_append(int32_t *map, int32_t *first, int64_t n_nodes, const void *cand, int idx_bytes, int index_base,
@@ -453,33 +368,31 @@ int gnnmp_unique_append(int32_t *map, int32_t *first, int64_t n_nodes, const voi
     *n_new = 0;
     if (n_cand == 0) return GNNMP_OK;
     if (!map || !first || !cand || !list_out) return fail(GNNMP_EINVAL, "unique_append: null pointer");
-    int rc = GNNMP_OK;
-    int64_t *flags = nullptr, *pos = nullptr;
-    int *bad = nullptr;
+    DevBuf<int> bad(Scratch::PrepCache);
+    DevBuf<int64_t> pos(Scratch::PrepCache), flags(Scratch::PrepCache);
+    GNNMP_HIP(flags.alloc((size_t)(n_cand + 1) + exclusive_scan_workspace((size_t)(n_cand + 1))));
+    GNNMP_HIP(pos.alloc((size_t)(n_cand + 1)));
+    GNNMP_HIP(bad.alloc(1));
+    GNNMP_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int), stream));
+    unique_reset_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, first, bad.get());
+    unique_min_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, map, first);
+    unique_flag_kernel<<<nb(n_cand + 1), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, map, first, flags.get());
+    GNNMP_HIP(hipGetLastError());
+    GNNMP_TRY(exclusive_scan_i64(flags.get(), pos.get(), (size_t)(n_cand + 1), stream, flags.get() + n_cand + 1));
+    unique_write_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, flags.get(), pos.get(), set_size, map,
+                                                        list_out);
+    GNNMP_HIP(hipGetLastError());
     int hbad = 0;
     int64_t tot = 0;
-    PREP_HIP(prep_alloc((void **)&flags, sizeof(int64_t) * ((size_t)(n_cand + 1) + exclusive_scan_workspace((size_t)(n_cand + 1)))));
-    PREP_HIP(prep_alloc((void **)&pos, sizeof(int64_t) * (size_t)(n_cand + 1)));
-    PREP_HIP(prep_alloc((void **)&bad, sizeof(int)));
-    PREP_HIP(hipMemsetAsync(bad, 0, sizeof(int), stream));
-    unique_reset_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, first, bad);
-    unique_min_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, map, first);
-    unique_flag_kernel<<<nb(n_cand + 1), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, n_nodes, map, first, flags);
-    PREP_HIP(hipGetLastError());
-    PREP_G(exclusive_scan_i64(flags, pos, (size_t)(n_cand + 1), stream, flags + n_cand + 1));
-    unique_write_kernel<<<nb(n_cand), 256, 0, stream>>>(cand, idx_bytes, index_base, n_cand, flags, pos, set_size, map,
-                                                        list_out);
-    PREP_HIP(hipGetLastError());
-    PREP_HIP(hipMemcpyAsync(&tot, pos + n_cand, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipStreamSynchronize(stream));
-    if (hbad) rc = fail(GNNMP_EBOUNDS, "unique_append: a node is outside 1..%lld", (long long)n_nodes);
+    GNNMP_HIP(hipMemcpyAsync(&tot, pos.get() + n_cand, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    flags.synced();
+    pos.synced();
+    bad.synced();
     *n_new = tot;
-done:
-    prep_free(flags, sizeof(int64_t) * ((size_t)(n_cand + 1) + exclusive_scan_workspace((size_t)(n_cand + 1))));
-    prep_free(pos, sizeof(int64_t) * (size_t)(n_cand + 1));
-    prep_free(bad, sizeof(int));
-    return rc;
+    if (hbad) return fail(GNNMP_EBOUNDS, "unique_append: a node is outside 1..%lld", (long long)n_nodes);
+    return GNNMP_OK;
 }
 
 int gnnmp_induced_subgraph(gnnmp_graph_t *plan, const int32_t *map, const void *nodes, int idx_bytes, int index_base,
@@ -495,37 +408,30 @@ int gnnmp_induced_subgraph(gnnmp_graph_t *plan, const int32_t *map, const void *
     *total = 0;
     if (n_nodes == 0) return GNNMP_OK;
     if (!map || !nodes) return fail(GNNMP_EINVAL, "induced_subgraph: null pointer");
-    int rc = GNNMP_OK;
-    int64_t *counts = nullptr;
-    int64_t tot = 0;
     // (+ the scan's block sums behind the counts: one pooled block, no allocation or synchronisation inside the scan)
     const size_t counts_elems = (size_t)(n_nodes + 1) + exclusive_scan_workspace((size_t)(n_nodes + 1));
-    PREP_HIP(prep_alloc((void **)&counts, sizeof(int64_t) * counts_elems));
+    DevBuf<int64_t> counts(Scratch::PrepCache);
+    GNNMP_HIP(counts.alloc(counts_elems));
     induced_count_kernel<<<nb((n_nodes + 1) * 64), 256, 0, stream>>>(plan->rowptr, plan->col, map, nodes, idx_bytes, index_base,
-                                                              n_nodes, counts);
-    PREP_HIP(hipGetLastError());
-    PREP_G(exclusive_scan_i64(counts, offsets, (size_t)(n_nodes + 1), stream, counts + n_nodes + 1));
-    PREP_HIP(hipMemcpyAsync(&tot, offsets + n_nodes, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    PREP_HIP(hipStreamSynchronize(stream));
+                                                              n_nodes, counts.get());
+    GNNMP_HIP(hipGetLastError());
+    GNNMP_TRY(exclusive_scan_i64(counts.get(), offsets, (size_t)(n_nodes + 1), stream, counts.get() + n_nodes + 1));
+    int64_t tot = 0;
+    GNNMP_HIP(hipMemcpyAsync(&tot, offsets + n_nodes, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    counts.synced();   // (nothing below touches the scratch)
     *total = tot;
-    if (capacity == 0 && !s_out && !t_out && !eid_out) goto done;   // count-only call: offsets and *total are the result
-    if (tot > capacity) {
-        rc = fail(GNNMP_EINVAL, "induced_subgraph: %lld edges do not fit the capacity %lld (offsets are valid: retry)",
-                  (long long)tot, (long long)capacity);
-        goto done;
-    }
+    if (capacity == 0 && !s_out && !t_out && !eid_out) return GNNMP_OK;   // count-only call: offsets and *total are the result
+    if (tot > capacity)
+        return fail(GNNMP_EINVAL, "induced_subgraph: %lld edges do not fit the capacity %lld (offsets are valid: retry)",
+                    (long long)tot, (long long)capacity);
     if (tot > 0) {
-        if (!s_out || !t_out || !eid_out) {
-            rc = fail(GNNMP_EINVAL, "induced_subgraph: null output");
-            goto done;
-        }
+        if (!s_out || !t_out || !eid_out) return fail(GNNMP_EINVAL, "induced_subgraph: null output");
         induced_fill_kernel<<<nb(n_nodes * 64), 256, 0, stream>>>(plan->rowptr, plan->col, plan->eid, map, nodes, idx_bytes,
                                                              index_base, n_nodes, offsets, s_out, t_out, eid_out);
-        PREP_HIP(hipGetLastError());
+        GNNMP_HIP(hipGetLastError());
     }
-done:
-    prep_free(counts, sizeof(int64_t) * ((size_t)(n_nodes + 1) + exclusive_scan_workspace((size_t)(n_nodes + 1))));
-    return rc;
+    return GNNMP_OK;
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // that go through the generic (closure) path of propagate, the NNlib-style atomic scatter kept as the measured
 // comparator, and reduce_nodes over a sorted graph_indicator (GNNlib/src/utils.jl:12-16).
 #include "common.h"
+#include "scratch.h"
 
 namespace gnnmp {
 
@@ -600,17 +601,16 @@ int gnnmp_is_sorted(const void *idx, int idx_bytes, int64_t n, int *result_host,
     *result_host = 1;
     if (n < 2) return GNNMP_OK;
     if (!idx) return fail(GNNMP_EINVAL, "is_sorted: null pointer");
-    int *flag = nullptr;
-    GNNMP_HIP(hipMalloc((void **)&flag, sizeof(int)));
-    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), stream);
+    DevBuf<int> flag;
+    GNNMP_HIP(flag.alloc(1));
+    hipError_t e = hipMemsetAsync(flag.get(), 0, sizeof(int), stream);
     if (e == hipSuccess) {
-        unsorted_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(idx, idx_bytes, n, flag);
+        unsorted_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(idx, idx_bytes, n, flag.get());
         e = hipGetLastError();
     }
     int h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(flag);
     if (e != hipSuccess) return hip_fail(e, "is_sorted");
     *result_host = h ? 0 : 1;
     return GNNMP_OK;

@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "scratch.h"
 #include "sort_scan.h"
 
 namespace gnnmp {
@@ -286,20 +287,6 @@ __global__ void __launch_bounds__(256) edge_dot_grad_kernel(const EdgeDotGradArg
 
 using namespace gnnmp;
 
-#define LP_HIP(expr)                                    \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-#define LP_G(expr)                                      \
-    do {                                                \
-        rc = (expr);                                    \
-        if (rc != GNNMP_OK) goto done;                  \
-    } while (0)
-
 extern "C" {
 
 int gnnmp_negative_sample(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int64_t n_nodes,
@@ -328,12 +315,6 @@ int gnnmp_negative_sample(const void *s, const void *t, int idx_bytes, int index
     if (num_neg == 0 || p == 0.0 || max_trials == 0) return GNNMP_OK;
     if (!s_out || !t_out || (n_edges > 0 && (!s || !t))) return fail(GNNMP_EINVAL, "negative_sample: null pointer");
 
-    int rc = GNNMP_OK;
-    uint64_t *codes_in = nullptr, *pos = nullptr, *kept = nullptr, *prev = nullptr;
-    int64_t *counts = nullptr;
-    int *bad = nullptr;
-    int hbad = 0;
-    int64_t n_kept = 0;
     const int code_bits = bit_length(maxid - 1);
     // chunks of about 32 expected candidates: enough threads, short walks
     const double expect = p * dmax;
@@ -341,82 +322,77 @@ int gnnmp_negative_sample(const void *s, const void *t, int idx_bytes, int index
     const uint64_t chunk_len = (maxid + n_chunks - 1) / n_chunks;
     const int64_t C = (int64_t)((maxid + chunk_len - 1) / chunk_len);
     const size_t scan_ws = exclusive_scan_workspace((size_t)(C + 1));
-    LP_HIP(hipMalloc((void **)&kept, sizeof(uint64_t) * (size_t)num_neg));
-    LP_HIP(hipMalloc((void **)&counts, sizeof(int64_t) * (2 * (size_t)(C + 1) + scan_ws)));
-    LP_HIP(hipMalloc((void **)&bad, sizeof(int)));
-    LP_HIP(hipMemsetAsync(bad, 0, sizeof(int), stream));
+    // Destroyed in reverse order — codes_in, pos, kept, prev, counts, bad — when the call returns: the first hipFree waits for the
+    // decode kernel, so the outputs are complete when the call returns.
+    DevBuf<int> bad;
+    DevBuf<int64_t> counts_buf;
+    DevBuf<uint64_t> prev, kept, pos, codes_in;
+    GNNMP_HIP(kept.alloc((size_t)num_neg));
+    GNNMP_HIP(counts_buf.alloc(2 * (size_t)(C + 1) + scan_ws));
+    GNNMP_HIP(bad.alloc(1));
+    GNNMP_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int), stream));
+    int64_t *const counts = counts_buf.get();
+    int hbad = 0;
     if (n_edges > 0) {
-        LP_HIP(hipMalloc((void **)&codes_in, sizeof(uint64_t) * (size_t)n_edges));
-        LP_HIP(hipMalloc((void **)&pos, sizeof(uint64_t) * (size_t)n_edges));
-        edge_codes_kernel<<<nblk(n_edges), 256, 0, stream>>>(s, t, idx_bytes, index_base, n_edges, n_nodes, codes_in, bad);
-        LP_HIP(hipGetLastError());
+        GNNMP_HIP(codes_in.alloc((size_t)n_edges));
+        GNNMP_HIP(pos.alloc((size_t)n_edges));
+        edge_codes_kernel<<<nblk(n_edges), 256, 0, stream>>>(s, t, idx_bytes, index_base, n_edges, n_nodes, codes_in.get(), bad.get());
+        GNNMP_HIP(hipGetLastError());
         // (synchronises the stream)
-        LP_G(radix_sort_keys_u64(codes_in, pos, (size_t)n_edges, 0, std::max(code_bits, 1), stream));
-        LP_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, stream));
+        GNNMP_TRY(radix_sort_keys_u64(codes_in.get(), pos.get(), (size_t)n_edges, 0, std::max(code_bits, 1), stream));
+        GNNMP_HIP(hipMemcpyAsync(&hbad, bad.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
     }
-    {
-        NegTrialArgs a;
-        a.pos = pos;
-        a.n_pos = n_edges;
-        a.prev = nullptr;
-        a.n_prev = 0;
-        a.maxid = maxid;
-        a.chunk_len = chunk_len;
-        a.n1 = n + 1;
-        a.n_chunks = C;
-        a.p_one = p >= 1.0;
-        a.log1m_p = a.p_one ? -1.0 : std::log1p(-p);
-        a.counts = counts;
-        a.offsets = counts + (C + 1);
-        int64_t *scan_scratch = counts + 2 * (C + 1);
-        for (int trial = 0; trial < max_trials; ++trial) {
-            // this trial's stream: independent of the chunking's other trials
-            uint64_t z = seed + 0x9e3779b97f4a7c15ULL * (uint64_t)(trial + 1);
-            z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-            z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-            a.stream = z ^ (z >> 31);
-            a.out = kept + n_kept;
-            a.room = num_neg - n_kept;
-            LP_HIP(hipMemsetAsync(counts + C, 0, sizeof(int64_t), stream));
-            neg_trial_kernel<0><<<nblk(C), 256, 0, stream>>>(a);
-            LP_HIP(hipGetLastError());
-            LP_G(exclusive_scan_i64(counts, counts + (C + 1), (size_t)(C + 1), stream, scan_scratch));
-            int64_t got = 0;
-            LP_HIP(hipMemcpyAsync(&got, counts + (C + 1) + C, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-            LP_HIP(hipStreamSynchronize(stream));   // the one read of a trial
-            if (hbad) {
-                rc = fail(GNNMP_EBOUNDS, "negative_sample: an edge index is outside the %lld nodes", (long long)n_nodes);
-                goto done;
-            }
-            if (got > 0) {
-                neg_trial_kernel<1><<<nblk(C), 256, 0, stream>>>(a);
-                LP_HIP(hipGetLastError());
-            }
-            n_kept += std::min(got, a.room);
-            if (n_kept >= num_neg || trial + 1 == max_trials) break;
-            if (got > 0) {
-                // the next trial looks codes up in everything kept so far, sorted (synchronises the stream)
-                if (!prev) LP_HIP(hipMalloc((void **)&prev, sizeof(uint64_t) * (size_t)num_neg));
-                LP_G(radix_sort_keys_u64(kept, prev, (size_t)n_kept, 0, std::max(code_bits, 1), stream));
-                a.prev = prev;
-                a.n_prev = n_kept;
-            }
+    NegTrialArgs a;
+    a.pos = pos.get();
+    a.n_pos = n_edges;
+    a.prev = nullptr;
+    a.n_prev = 0;
+    a.maxid = maxid;
+    a.chunk_len = chunk_len;
+    a.n1 = n + 1;
+    a.n_chunks = C;
+    a.p_one = p >= 1.0;
+    a.log1m_p = a.p_one ? -1.0 : std::log1p(-p);
+    a.counts = counts;
+    a.offsets = counts + (C + 1);
+    int64_t *scan_scratch = counts + 2 * (C + 1);
+    int64_t n_kept = 0;
+    for (int trial = 0; trial < max_trials; ++trial) {
+        // this trial's stream: independent of the chunking's other trials
+        uint64_t z = seed + 0x9e3779b97f4a7c15ULL * (uint64_t)(trial + 1);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+        a.stream = z ^ (z >> 31);
+        a.out = kept.get() + n_kept;
+        a.room = num_neg - n_kept;
+        GNNMP_HIP(hipMemsetAsync(counts + C, 0, sizeof(int64_t), stream));
+        neg_trial_kernel<0><<<nblk(C), 256, 0, stream>>>(a);
+        GNNMP_HIP(hipGetLastError());
+        GNNMP_TRY(exclusive_scan_i64(counts, counts + (C + 1), (size_t)(C + 1), stream, scan_scratch));
+        int64_t got = 0;
+        GNNMP_HIP(hipMemcpyAsync(&got, counts + (C + 1) + C, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        GNNMP_HIP(hipStreamSynchronize(stream));   // the one read of a trial
+        if (hbad) return fail(GNNMP_EBOUNDS, "negative_sample: an edge index is outside the %lld nodes", (long long)n_nodes);
+        if (got > 0) {
+            neg_trial_kernel<1><<<nblk(C), 256, 0, stream>>>(a);
+            GNNMP_HIP(hipGetLastError());
+        }
+        n_kept += std::min(got, a.room);
+        if (n_kept >= num_neg || trial + 1 == max_trials) break;
+        if (got > 0) {
+            // the next trial looks codes up in everything kept so far, sorted (synchronises the stream)
+            if (!prev.get()) GNNMP_HIP(prev.alloc((size_t)num_neg));
+            GNNMP_TRY(radix_sort_keys_u64(kept.get(), prev.get(), (size_t)n_kept, 0, std::max(code_bits, 1), stream));
+            a.prev = prev.get();
+            a.n_prev = n_kept;
         }
     }
     if (n_kept > 0) {
-        neg_decode_kernel<<<nblk(n_kept), 256, 0, stream>>>(kept, n_kept, n, bidirected ? 1 : 0, idx_bytes, index_base, s_out, t_out);
-        LP_HIP(hipGetLastError());
+        neg_decode_kernel<<<nblk(n_kept), 256, 0, stream>>>(kept.get(), n_kept, n, bidirected ? 1 : 0, idx_bytes, index_base, s_out, t_out);
+        GNNMP_HIP(hipGetLastError());
     }
     *total = bidirected ? 2 * n_kept : n_kept;
-done:
-    // (hipFree waits for the decode kernel: the outputs are complete when the call returns)
-    if (codes_in) (void)hipFree(codes_in);
-    if (pos) (void)hipFree(pos);
-    if (kept) (void)hipFree(kept);
-    if (prev) (void)hipFree(prev);
-    if (counts) (void)hipFree(counts);
-    if (bad) (void)hipFree(bad);
-    return rc;
+    return GNNMP_OK;
 }
 
 int gnnmp_rand_edge_split(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int bidirected, int64_t size1,
@@ -430,44 +406,39 @@ int gnnmp_rand_edge_split(const void *s, const void *t, int idx_bytes, int index
     if (ne == 0) return GNNMP_OK;
     if (!s || !t || (size1 > 0 && (!s1 || !t1)) || (size1 < ne && (!s2 || !t2)))
         return fail(GNNMP_EINVAL, "rand_edge_split: null pointer");
-    int rc = GNNMP_OK;
-    int64_t *flags = nullptr, *kept = nullptr;
-    uint64_t *keys = nullptr, *sorted = nullptr;
     const int ibits = std::max(1, bit_length((uint64_t)(ne - 1)));
+    // (destroyed in reverse order — flags, kept, keys, sorted — when the call returns; the first hipFree waits for split_write_kernel)
+    DevBuf<uint64_t> sorted, keys;
+    DevBuf<int64_t> kept, flags_buf;
     if (bidirected) {
         // s .< t, compacted in edge order (transform.jl:959-960); the split draws from its first ne entries
         const size_t ws = exclusive_scan_workspace((size_t)(n_edges + 1));
-        int64_t m = 0;
-        LP_HIP(hipMalloc((void **)&flags, sizeof(int64_t) * (2 * (size_t)(n_edges + 1) + ws)));
-        LP_HIP(hipMalloc((void **)&kept, sizeof(int64_t) * (size_t)ne));
+        GNNMP_HIP(flags_buf.alloc(2 * (size_t)(n_edges + 1) + ws));
+        GNNMP_HIP(kept.alloc((size_t)ne));
+        int64_t *const flags = flags_buf.get();
         less_flag_kernel<<<nblk(n_edges + 1), 256, 0, stream>>>(s, t, idx_bytes, n_edges, flags);
-        LP_HIP(hipGetLastError());
+        GNNMP_HIP(hipGetLastError());
         int64_t *posk = flags + (n_edges + 1);
-        LP_G(exclusive_scan_i64(flags, posk, (size_t)(n_edges + 1), stream, flags + 2 * (n_edges + 1)));
-        LP_HIP(hipMemcpyAsync(&m, posk + n_edges, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-        LP_HIP(hipStreamSynchronize(stream));
-        if (m < ne) {
-            rc = fail(GNNMP_EBOUNDS, "rand_edge_split(bidirected = true): %lld edges have s < t, fewer than num_edges / 2 = %lld "
-                      "(the graph is not bidirected, or has self loops or multi-edges)", (long long)m, (long long)ne);
-            goto done;
-        }
-        less_compact_kernel<<<nblk(n_edges), 256, 0, stream>>>(flags, posk, n_edges, ne, kept);
-        LP_HIP(hipGetLastError());
+        GNNMP_TRY(exclusive_scan_i64(flags, posk, (size_t)(n_edges + 1), stream, flags + 2 * (n_edges + 1)));
+        int64_t m = 0;
+        GNNMP_HIP(hipMemcpyAsync(&m, posk + n_edges, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        GNNMP_HIP(hipStreamSynchronize(stream));
+        if (m < ne)
+            return fail(GNNMP_EBOUNDS, "rand_edge_split(bidirected = true): %lld edges have s < t, fewer than num_edges / 2 = %lld "
+                        "(the graph is not bidirected, or has self loops or multi-edges)", (long long)m, (long long)ne);
+        less_compact_kernel<<<nblk(n_edges), 256, 0, stream>>>(flags, posk, n_edges, ne, kept.get());
+        GNNMP_HIP(hipGetLastError());
     }
-    LP_HIP(hipMalloc((void **)&keys, sizeof(uint64_t) * (size_t)ne));
-    LP_HIP(hipMalloc((void **)&sorted, sizeof(uint64_t) * (size_t)ne));
-    perm_keys_kernel<<<nblk(ne), 256, 0, stream>>>(ne, ibits, seed, keys);
-    LP_HIP(hipGetLastError());
+    GNNMP_HIP(keys.alloc((size_t)ne));
+    GNNMP_HIP(sorted.alloc((size_t)ne));
+    perm_keys_kernel<<<nblk(ne), 256, 0, stream>>>(ne, ibits, seed, keys.get());
+    GNNMP_HIP(hipGetLastError());
     // randperm(ne) (synchronises the stream)
-    LP_G(radix_sort_keys_u64(keys, sorted, (size_t)ne, 0, 64, stream));
-    split_write_kernel<<<nblk(ne), 256, 0, stream>>>(sorted, ibits, kept, s, t, idx_bytes, ne, size1, bidirected ? 1 : 0, s1, t1, s2, t2);
-    LP_HIP(hipGetLastError());
-done:
-    if (flags) (void)hipFree(flags);
-    if (kept) (void)hipFree(kept);
-    if (keys) (void)hipFree(keys);
-    if (sorted) (void)hipFree(sorted);
-    return rc;
+    GNNMP_TRY(radix_sort_keys_u64(keys.get(), sorted.get(), (size_t)ne, 0, 64, stream));
+    split_write_kernel<<<nblk(ne), 256, 0, stream>>>(sorted.get(), ibits, kept.get(), s, t, idx_bytes, ne, size1, bidirected ? 1 : 0, s1, t1, s2,
+                                                     t2);
+    GNNMP_HIP(hipGetLastError());
+    return GNNMP_OK;
 }
 
 int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const float *xi, const float *xj, const float *dz, float *dxi,

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "scratch.h"
 #include "sort_scan.h"
 
 namespace gnnmp {
@@ -231,67 +232,39 @@ __global__ void seg_min_kernel(const int64_t *v, int diff, int64_t G, int64_t ne
 
 inline unsigned nblk(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
-#define NB_HIP(expr)                                    \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-#define NB_G(expr)                                      \
-    do {                                                \
-        rc = (expr);                                    \
-        if (rc != GNNMP_OK) goto done;                  \
-    } while (0)
-
-// The indicator's checks and, when it is non-decreasing, its segment boundaries (*seg_ptr: caller frees; nullptr when unsorted).
+// The indicator's checks and, when it is non-decreasing, its segment boundaries (seg: left empty when unsorted).
 // `need` > 0: every graph that occurs must hold at least `need` nodes.  Synchronises the stream (once; twice when unsorted).
 int prepare_indicator(const char *who, const void *gi, int gi_bytes, int base, int64_t N, int64_t G, int64_t need, hipStream_t stream,
-                      int64_t **seg_ptr) {
-    int rc = GNNMP_OK;
-    int64_t *sp = nullptr;
-    int *flags = nullptr;
+                      DevBuf<int64_t> &seg) {
+    DevBuf<int> flags;
+    DevBuf<int64_t> sp;
     int h[4] = {0, 0, 0, 0};
-    *seg_ptr = nullptr;
-    NB_HIP(hipMalloc((void **)&sp, sizeof(int64_t) * (size_t)(G + 1)));
-    NB_HIP(hipMalloc((void **)&flags, sizeof(int) * 4));
-    NB_HIP(hipMemsetAsync(flags, 0, sizeof(int) * 4, stream));
-    gi_check_kernel<<<nblk(N), 256, 0, stream>>>(gi, gi_bytes, base, N, G, flags);
-    NB_HIP(hipGetLastError());
-    NB_G(gnnmp_segment_bounds(gi, gi_bytes, base, N, G, sp, (gnnmp_stream_t)stream));   // (stays inside [0, G] on any input)
+    GNNMP_HIP(sp.alloc((size_t)(G + 1)));
+    GNNMP_HIP(flags.alloc(4));
+    GNNMP_HIP(hipMemsetAsync(flags.get(), 0, sizeof(int) * 4, stream));
+    gi_check_kernel<<<nblk(N), 256, 0, stream>>>(gi, gi_bytes, base, N, G, flags.get());
+    GNNMP_HIP(hipGetLastError());
+    GNNMP_TRY(gnnmp_segment_bounds(gi, gi_bytes, base, N, G, sp.get(), (gnnmp_stream_t)stream));   // (stays inside [0, G] on any input)
     if (need > 0) {
-        seg_min_kernel<<<nblk(G), 256, 0, stream>>>(sp, 1, G, need, flags);
-        NB_HIP(hipGetLastError());
+        seg_min_kernel<<<nblk(G), 256, 0, stream>>>(sp.get(), 1, G, need, flags.get());
+        GNNMP_HIP(hipGetLastError());
     }
-    NB_HIP(hipMemcpyAsync(h, flags, sizeof(int) * 4, hipMemcpyDeviceToHost, stream));
-    NB_HIP(hipStreamSynchronize(stream));
-    if (h[1]) {
-        rc = fail(GNNMP_EBOUNDS, "%s: a graph_indicator entry is outside the %lld graphs", who, (long long)G);
-        goto done;
-    }
+    GNNMP_HIP(hipMemcpyAsync(h, flags.get(), sizeof(int) * 4, hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    if (h[1]) return fail(GNNMP_EBOUNDS, "%s: a graph_indicator entry is outside the %lld graphs", who, (long long)G);
     if (h[0] && need > 0) {   // unsorted: the boundaries mean nothing, count the ids
-        NB_HIP(hipMemsetAsync(sp, 0, sizeof(int64_t) * (size_t)(G + 1), stream));
-        NB_HIP(hipMemsetAsync(flags, 0, sizeof(int) * 4, stream));
-        gi_hist_kernel<<<nblk(N), 256, 0, stream>>>(gi, gi_bytes, base, N, reinterpret_cast<unsigned long long *>(sp));
-        NB_HIP(hipGetLastError());
-        seg_min_kernel<<<nblk(G), 256, 0, stream>>>(sp, 0, G, need, flags);
-        NB_HIP(hipGetLastError());
-        NB_HIP(hipMemcpyAsync(h + 2, flags + 2, sizeof(int), hipMemcpyDeviceToHost, stream));
-        NB_HIP(hipStreamSynchronize(stream));
+        GNNMP_HIP(hipMemsetAsync(sp.get(), 0, sizeof(int64_t) * (size_t)(G + 1), stream));
+        GNNMP_HIP(hipMemsetAsync(flags.get(), 0, sizeof(int) * 4, stream));
+        gi_hist_kernel<<<nblk(N), 256, 0, stream>>>(gi, gi_bytes, base, N, reinterpret_cast<unsigned long long *>(sp.get()));
+        GNNMP_HIP(hipGetLastError());
+        seg_min_kernel<<<nblk(G), 256, 0, stream>>>(sp.get(), 0, G, need, flags.get());
+        GNNMP_HIP(hipGetLastError());
+        GNNMP_HIP(hipMemcpyAsync(h + 2, flags.get() + 2, sizeof(int), hipMemcpyDeviceToHost, stream));
+        GNNMP_HIP(hipStreamSynchronize(stream));
     }
-    if (need > 0 && h[2]) {
-        rc = fail(GNNMP_EBOUNDS, "%s: a graph of the batch has fewer than %lld nodes", who, (long long)need);
-        goto done;
-    }
-    if (!h[0]) {
-        *seg_ptr = sp;
-        sp = nullptr;
-    }
-done:
-    if (sp) (void)hipFree(sp);
-    if (flags) (void)hipFree(flags);
-    return rc;
+    if (need > 0 && h[2]) return fail(GNNMP_EBOUNDS, "%s: a graph of the batch has fewer than %lld nodes", who, (long long)need);
+    if (!h[0]) seg = std::move(sp);
+    return GNNMP_OK;
 }
 
 // rowptr[i] = i k (knn: every row holds k slots)
@@ -342,15 +315,15 @@ NbArgs make_args(const float *points, int64_t N, int64_t d, const void *gi, int 
 // the plan's arrays for n_dst = n_src = N rows and E slots (what gnnmp_plan_from_csc allocates)
 int alloc_plan_rows(gnnmp_graph_t *p, int64_t N) {
     p->n_src = p->n_dst = N;
-    GNNMP_HIP(hipMalloc((void **)&p->rowptr, sizeof(uint32_t) * (size_t)(N + 1)));
+    GNNMP_HIP(alloc_into(p->rowptr, (size_t)(N + 1)));
     return GNNMP_OK;
 }
 int alloc_plan_slots(gnnmp_graph_t *p, int64_t E) {
     const size_t epad = (size_t)std::max<int64_t>(E, 1);
     p->n_edges = p->n_total = E;
     p->long_thresh = plan_long_thresh(E);
-    GNNMP_HIP(hipMalloc((void **)&p->col, sizeof(int32_t) * epad));
-    GNNMP_HIP(hipMalloc((void **)&p->eid, sizeof(int32_t) * epad));
+    GNNMP_HIP(alloc_into(p->col, epad));
+    GNNMP_HIP(alloc_into(p->eid, epad));
     p->bytes = (int64_t)(sizeof(int32_t) * ((size_t)(p->n_dst + 1) + 2 * epad));
     return GNNMP_OK;
 }
@@ -365,88 +338,69 @@ extern "C" {
 int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, int64_t k, const void *graph_indicator,
                         int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_common("knn_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs);
-    if (rc != GNNMP_OK) return rc;
+    GNNMP_TRY(check_common("knn_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs));
     if (k < 1) return fail(GNNMP_EINVAL, "knn_graph: k = %lld < 1", (long long)k);
     if (k > NB_MAX_K) return fail(GNNMP_EINVAL, "knn_graph: k = %lld > %d", (long long)k, NB_MAX_K);
     if (N * k >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "knn_graph: N k exceeds the plan format");
     const int64_t need = k + (self_loops ? 0 : 1);
     if (N > 0 && N < need) return fail(GNNMP_EBOUNDS, "knn_graph: %lld points, fewer than %lld", (long long)N, (long long)need);
-    int64_t *seg_ptr = nullptr;
-    gnnmp_graph_t *p = new gnnmp_graph_t();
+    PlanPtr p(new gnnmp_graph_t());
+    DevBuf<int64_t> seg;
     if (graph_indicator && N > 0)
-        NB_G(prepare_indicator("knn_graph", graph_indicator, idx_bytes, index_base, N, n_graphs, need, stream, &seg_ptr));
-    NB_G(alloc_plan_rows(p, N));
-    NB_G(alloc_plan_slots(p, N * k));
+        GNNMP_TRY(prepare_indicator("knn_graph", graph_indicator, idx_bytes, index_base, N, n_graphs, need, stream, seg));
+    GNNMP_TRY(alloc_plan_rows(p.get(), N));
+    GNNMP_TRY(alloc_plan_slots(p.get(), N * k));
     knn_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(p->rowptr, N, k);
-    NB_HIP(hipGetLastError());
+    GNNMP_HIP(hipGetLastError());
     if (N > 0) {
-        NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg_ptr, self_loops, p);
+        NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg.get(), self_loops, p.get());
         a.k = (int)k;
         neighbors_kernel<NB_KNN><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
-        NB_HIP(hipGetLastError());
+        GNNMP_HIP(hipGetLastError());
     }
-    rc = plan_build_long_rows(p, stream);   // (synchronises the stream, as every plan build does)
-done:
-    if (seg_ptr) (void)hipFree(seg_ptr);
-    if (rc != GNNMP_OK) {
-        gnnmp_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    GNNMP_TRY(plan_build_long_rows(p.get(), stream));   // (synchronises the stream, as every plan build does)
+    *out = p.release();
     return GNNMP_OK;
 }
 
 int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float r, const void *graph_indicator,
                            int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_common("radius_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs);
-    if (rc != GNNMP_OK) return rc;
+    GNNMP_TRY(check_common("radius_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs));
     if (!(r >= 0.0f)) return fail(GNNMP_EINVAL, "radius_graph: r = %g (negative or NaN)", (double)r);
     const float r2 = r * r;
-    int64_t *seg_ptr = nullptr, *rowptr64 = nullptr;
-    int64_t tot = 0;
-    gnnmp_graph_t *p = new gnnmp_graph_t();
+    PlanPtr p(new gnnmp_graph_t());
+    // (rowptr64 dies when the call returns: after plan_build_long_rows' synchronisation, or its hipFree waits itself)
+    DevBuf<int64_t> rowptr64, seg;
     if (graph_indicator && N > 0)
-        NB_G(prepare_indicator("radius_graph", graph_indicator, idx_bytes, index_base, N, n_graphs, 0, stream, &seg_ptr));
-    NB_G(alloc_plan_rows(p, N));
-    NB_HIP(hipMalloc((void **)&rowptr64, sizeof(int64_t) * (size_t)(N + 1)));
-    {
-        NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg_ptr, self_loops, p);
-        a.r2 = r2;
-        NB_HIP(hipMemsetAsync(rowptr64 + N, 0, sizeof(int64_t), stream));
-        if (N > 0) {
-            a.deg = rowptr64;
-            neighbors_kernel<NB_COUNT><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
-            NB_HIP(hipGetLastError());
-        }
-        NB_G(exclusive_scan_i64(rowptr64, rowptr64, (size_t)(N + 1), stream));
-        NB_HIP(hipMemcpyAsync(&tot, rowptr64 + N, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-        NB_HIP(hipStreamSynchronize(stream));
-        if (tot >= (int64_t)GNNMP_MAX_SLOTS) {
-            rc = fail(GNNMP_EUNSUPPORTED, "radius_graph: %lld edges exceed the plan format", (long long)tot);
-            goto done;
-        }
-        NB_G(alloc_plan_slots(p, tot));
-        narrow_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(rowptr64, p->rowptr, N);
-        NB_HIP(hipGetLastError());
-        if (tot > 0) {
-            a.col = p->col;
-            a.eid = p->eid;
-            a.rowptr = rowptr64;
-            neighbors_kernel<NB_WRITE><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
-            NB_HIP(hipGetLastError());
-        }
+        GNNMP_TRY(prepare_indicator("radius_graph", graph_indicator, idx_bytes, index_base, N, n_graphs, 0, stream, seg));
+    GNNMP_TRY(alloc_plan_rows(p.get(), N));
+    GNNMP_HIP(rowptr64.alloc((size_t)(N + 1)));
+    NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg.get(), self_loops, p.get());
+    a.r2 = r2;
+    GNNMP_HIP(hipMemsetAsync(rowptr64.get() + N, 0, sizeof(int64_t), stream));
+    if (N > 0) {
+        a.deg = rowptr64.get();
+        neighbors_kernel<NB_COUNT><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
+        GNNMP_HIP(hipGetLastError());
     }
-    rc = plan_build_long_rows(p, stream);
-done:
-    if (seg_ptr) (void)hipFree(seg_ptr);
-    if (rowptr64) (void)hipFree(rowptr64);   // (after plan_build_long_rows' synchronisation, or waits itself)
-    if (rc != GNNMP_OK) {
-        gnnmp_plan_destroy(p);
-        return rc;
+    GNNMP_TRY(exclusive_scan_i64(rowptr64.get(), rowptr64.get(), (size_t)(N + 1), stream));
+    int64_t tot = 0;
+    GNNMP_HIP(hipMemcpyAsync(&tot, rowptr64.get() + N, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    if (tot >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "radius_graph: %lld edges exceed the plan format", (long long)tot);
+    GNNMP_TRY(alloc_plan_slots(p.get(), tot));
+    narrow_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(rowptr64.get(), p->rowptr, N);
+    GNNMP_HIP(hipGetLastError());
+    if (tot > 0) {
+        a.col = p->col;
+        a.eid = p->eid;
+        a.rowptr = rowptr64.get();
+        neighbors_kernel<NB_WRITE><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
+        GNNMP_HIP(hipGetLastError());
     }
-    *out = p;
+    GNNMP_TRY(plan_build_long_rows(p.get(), stream));
+    *out = p.release();
     return GNNMP_OK;
 }
 

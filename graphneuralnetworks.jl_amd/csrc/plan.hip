@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "pool.h"
+#include "scratch.h"
 #include "sort_scan.h"
 
 namespace gnnmp {
@@ -52,16 +53,7 @@ int device_cus() {
 
 int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);
 
-int ensure_workspace(gnnmp_graph *p, size_t floats) {
-    if (floats <= p->ws_floats) return GNNMP_OK;
-    if (p->ws) (void)hipFree(p->ws);  // hipFree waits for work that may still read the old buffer
-    p->ws = nullptr;
-    p->ws_floats = 0;
-    hipError_t e = hipMalloc((void **)&p->ws, sizeof(float) * floats);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(plan workspace)");
-    p->ws_floats = floats;
-    return GNNMP_OK;
-}
+int ensure_workspace(gnnmp_graph *p, size_t floats) { return grow(p->ws, p->ws_floats, floats, "hipMalloc(plan workspace)"); }
 
 bool fold_disabled_by_env() {
     static const bool off = [] {
@@ -72,31 +64,23 @@ bool fold_disabled_by_env() {
 }
 
 int ensure_arrive(gnnmp_graph *p, size_t n, size_t floats, hipStream_t stream) {
-    if (floats > p->spart_floats) {
-        if (p->spart) (void)hipFree(p->spart);   // (waits for in-flight work)
-        p->spart = nullptr;
-        p->spart_floats = 0;
-        hipError_t e = hipMalloc((void **)&p->spart, sizeof(float) * floats);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(plan slice partials)");
-        p->spart_floats = floats;
-    }
+    GNNMP_TRY(grow(p->spart, p->spart_floats, floats, "hipMalloc(plan slice partials)"));
     if (n <= p->arrive_n) return GNNMP_OK;
-    if (p->arrive) (void)hipFree(p->arrive);   // (waits for in-flight work; counters are zero between launches, nothing to carry over)
-    p->arrive = nullptr;
-    p->arrive_n = 0;
-    hipError_t e = hipMalloc((void **)&p->arrive, sizeof(uint32_t) * n);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(plan arrival counters)");
-    e = hipMemsetAsync(p->arrive, 0, sizeof(uint32_t) * n, stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(plan arrival counters)");
-    p->arrive_n = n;
+    // (counters are zero between launches, nothing to carry over)
+    GNNMP_TRY(grow(p->arrive, p->arrive_n, n, "hipMalloc(plan arrival counters)"));
+    const hipError_t e = hipMemsetAsync(p->arrive, 0, sizeof(uint32_t) * n, stream);
+    if (e != hipSuccess) {
+        p->arrive_n = 0;   // not zeroed: the next call starts over
+        return hip_fail(e, "hipMemsetAsync(plan arrival counters)");
+    }
     return GNNMP_OK;
 }
 
 int ensure_ticket(gnnmp_graph *p, hipStream_t stream) {
     if (p->ticket) return GNNMP_OK;
-    hipError_t e = hipMalloc((void **)&p->ticket, 2 * sizeof(uint32_t));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(plan ticket)");
-    e = hipMemsetAsync(p->ticket, 0, 2 * sizeof(uint32_t), stream);
+    size_t cap = 0;
+    GNNMP_TRY(grow(p->ticket, cap, 2, "hipMalloc(plan ticket)"));
+    const hipError_t e = hipMemsetAsync(p->ticket, 0, 2 * sizeof(uint32_t), stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(plan ticket)");
     return GNNMP_OK;
 }
@@ -111,27 +95,18 @@ __global__ void plan_degree_keys(const uint32_t *rowptr, int64_t n, uint32_t max
 int ensure_row_order(gnnmp_graph *p, hipStream_t stream) {
     if (p->row_order || p->n_dst == 0) return GNNMP_OK;
     const size_t n = (size_t)p->n_dst;
-    uint32_t *kin = nullptr, *kout = nullptr, *vin = nullptr;
-    int32_t *order = nullptr;
-    int rc = GNNMP_OK;
-    hipError_t e = hipSuccess;
     unsigned bits = 1;
     while (bits < 32 && ((int64_t)1 << bits) <= p->max_degree) ++bits;   // max_degree <= E' < 2^32
-    if ((e = hipMalloc((void **)&kin, 4 * n)) != hipSuccess || (e = hipMalloc((void **)&kout, 4 * n)) != hipSuccess ||
-        (e = hipMalloc((void **)&vin, 4 * n)) != hipSuccess || (e = hipMalloc((void **)&order, 4 * n)) != hipSuccess) {
-        rc = hip_fail(e, "hipMalloc(row order)");
-    } else {
-        plan_degree_keys<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(p->rowptr, p->n_dst, (uint32_t)p->max_degree, kin, vin);
-        rc = radix_sort_pairs_u32(kin, kout, vin, reinterpret_cast<uint32_t *>(order), n, 0, (int)bits, stream);   // syncs the stream
-    }
-    if (kin) (void)hipFree(kin);
-    if (kout) (void)hipFree(kout);
-    if (vin) (void)hipFree(vin);
-    if (rc != GNNMP_OK) {
-        if (order) (void)hipFree(order);
-        return rc;
-    }
-    p->row_order = order;
+    DevBuf<int32_t> order;
+    DevBuf<uint32_t> vin, kout, kin;
+    hipError_t e = hipSuccess;
+    if ((e = kin.alloc(n)) != hipSuccess || (e = kout.alloc(n)) != hipSuccess || (e = vin.alloc(n)) != hipSuccess ||
+        (e = order.alloc(n)) != hipSuccess)
+        return hip_fail(e, "hipMalloc(row order)");
+    plan_degree_keys<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(p->rowptr, p->n_dst, (uint32_t)p->max_degree, kin.get(), vin.get());
+    GNNMP_TRY(radix_sort_pairs_u32(kin.get(), kout.get(), vin.get(), reinterpret_cast<uint32_t *>(order.get()), n, 0, (int)bits,
+                                   stream));   // syncs the stream
+    p->row_order = order.release();
     p->bytes += (int64_t)(4 * n);
     return GNNMP_OK;
 }
@@ -316,94 +291,69 @@ static int plan_chunk_slots() {
 int plan_build_long_rows(gnnmp_graph *p, hipStream_t stream) {
     const int64_t n_dst = p->n_dst, Etot = p->n_total;
     const int BS = 256;
-    int *flags = nullptr;       // [0] long count; [2..3] = one unsigned long long: max degree
-    int64_t *long_tmp = nullptr;
-    int rc = GNNMP_OK;
-#define PLAN_HIP(expr)                                  \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-    {
-        // long rows: at most Etot / thresh of them
-        int cap = (int)std::min<int64_t>(Etot / std::max(1, p->long_thresh) + 1, n_dst + 1);
-        PLAN_HIP(hipMalloc((void **)&flags, sizeof(int) * 4));
-        PLAN_HIP(hipMemsetAsync(flags, 0, sizeof(int) * 4, stream));
-        PLAN_HIP(hipMalloc((void **)&long_tmp, sizeof(int64_t) * 3 * (size_t)std::max(cap, 1)));
-        if (n_dst > 0) {
-            plan_long_rows<<<nblocks(n_dst, BS), BS, 0, stream>>>(p->rowptr, n_dst, p->long_thresh, long_tmp, cap, flags,
-                                                                  reinterpret_cast<unsigned long long *>(flags + 2));
-            PLAN_HIP(hipGetLastError());
-        }
-        int meta[4] = {0, 0, 0, 0};
-        PLAN_HIP(hipMemcpyAsync(meta, flags, sizeof(int) * 4, hipMemcpyDeviceToHost, stream));
-        PLAN_HIP(hipStreamSynchronize(stream));
-        {
-            unsigned long long md;
-            memcpy(&md, meta + 2, sizeof(md));
-            p->max_degree = (int64_t)md;
-        }
-        p->n_long = std::min(meta[0], cap);
-        if (p->n_long > 0) {
-            struct Tri { int64_t row, beg, end; };
-            std::vector<Tri> h((size_t)p->n_long);
-            PLAN_HIP(hipMemcpy(h.data(), long_tmp, sizeof(Tri) * h.size(), hipMemcpyDeviceToHost));
-            // atomics filled the list in arbitrary order: make it canonical (ascending row)
-            std::sort(h.begin(), h.end(), [](const Tri &a, const Tri &b) { return a.row < b.row; });
-            std::vector<int32_t> rows, cptr, crow, clrow;
-            std::vector<uint32_t> cbeg, cend;
-            cptr.push_back(0);
-            // Chunk length (round 6): rows are split ABOVE long_thresh (that is what bounds bit-exactness and keeps a sequential row from
-            // being the kernel's tail), but the chunks of a row that is split anyway are at most plan_chunk_slots() = 128 slots long: a chunk
-            // is a latency-bound chain of len / 8 row-load batches, and the fused layer kernel's pre-pass over the split rows — nothing
-            // else runs beside it — took 110 us of a 4.8 ms GCN layer with 512-slot chunks on the products shape.
-            const int64_t clen = std::min<int64_t>(p->long_thresh, plan_chunk_slots());
-            for (const Tri &t : h) {
-                const int64_t len = t.end - t.beg;
-                const int64_t nch = (len + clen - 1) / clen;
-                const int64_t csz = (len + nch - 1) / nch;  // balanced chunks, each <= clen <= long_thresh slots
-                for (int64_t c = 0; c < nch; ++c) {
-                    crow.push_back((int32_t)t.row);
-                    clrow.push_back((int32_t)rows.size());
-                    cbeg.push_back((uint32_t)(t.beg + c * csz));
-                    cend.push_back((uint32_t)std::min(t.beg + (c + 1) * csz, t.end));
-                }
-                rows.push_back((int32_t)t.row);
-                cptr.push_back((int32_t)crow.size());
-            }
-            if (crow.size() >= (size_t)INT32_MAX) {
-                rc = fail(GNNMP_EUNSUPPORTED, "plan_create: %zu chunks of split rows exceed the int32 chunk index", crow.size());
-                goto done;
-            }
-            p->n_chunks = (int)crow.size();
-            auto upload = [&](int32_t **dst, const std::vector<int32_t> &v) -> hipError_t {
-                hipError_t e = hipMalloc((void **)dst, sizeof(int32_t) * v.size());
-                if (e != hipSuccess) return e;
-                p->bytes += (int64_t)(sizeof(int32_t) * v.size());
-                return hipMemcpy(*dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice);
-            };
-            PLAN_HIP(upload(&p->long_rows, rows));
-            PLAN_HIP(upload(&p->long_cptr, cptr));
-            PLAN_HIP(upload(&p->chunk_row, crow));
-            PLAN_HIP(upload(&p->chunk_lrow, clrow));
-            auto upload_u = [&](uint32_t **dst, const std::vector<uint32_t> &v) -> hipError_t {
-                hipError_t e = hipMalloc((void **)dst, sizeof(uint32_t) * v.size());
-                if (e != hipSuccess) return e;
-                p->bytes += (int64_t)(sizeof(uint32_t) * v.size());
-                return hipMemcpy(*dst, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice);
-            };
-            PLAN_HIP(upload_u(&p->chunk_beg, cbeg));
-            PLAN_HIP(upload_u(&p->chunk_end, cend));
-        }
+    // long rows: at most Etot / thresh of them
+    const int cap = (int)std::min<int64_t>(Etot / std::max(1, p->long_thresh) + 1, n_dst + 1);
+    DevBuf<int64_t> long_tmp;
+    DevBuf<int> flags;       // [0] long count; [2..3] = one unsigned long long: max degree
+    GNNMP_HIP(flags.alloc(4));
+    GNNMP_HIP(hipMemsetAsync(flags.get(), 0, sizeof(int) * 4, stream));
+    GNNMP_HIP(long_tmp.alloc(3 * (size_t)std::max(cap, 1)));
+    if (n_dst > 0) {
+        plan_long_rows<<<nblocks(n_dst, BS), BS, 0, stream>>>(p->rowptr, n_dst, p->long_thresh, long_tmp.get(), cap, flags.get(),
+                                                              reinterpret_cast<unsigned long long *>(flags.get() + 2));
+        GNNMP_HIP(hipGetLastError());
     }
-done:
-    if (flags) (void)hipFree(flags);
-    if (long_tmp) (void)hipFree(long_tmp);
-#undef PLAN_HIP
-    return rc;
+    int meta[4] = {0, 0, 0, 0};
+    GNNMP_HIP(hipMemcpyAsync(meta, flags.get(), sizeof(int) * 4, hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    unsigned long long md;
+    memcpy(&md, meta + 2, sizeof(md));
+    p->max_degree = (int64_t)md;
+    p->n_long = std::min(meta[0], cap);
+    if (p->n_long == 0) return GNNMP_OK;
+    struct Tri { int64_t row, beg, end; };
+    std::vector<Tri> h((size_t)p->n_long);
+    GNNMP_HIP(hipMemcpy(h.data(), long_tmp.get(), sizeof(Tri) * h.size(), hipMemcpyDeviceToHost));
+    // atomics filled the list in arbitrary order: make it canonical (ascending row)
+    std::sort(h.begin(), h.end(), [](const Tri &a, const Tri &b) { return a.row < b.row; });
+    std::vector<int32_t> rows, cptr, crow, clrow;
+    std::vector<uint32_t> cbeg, cend;
+    cptr.push_back(0);
+    // Chunk length (round 6): rows are split ABOVE long_thresh (that is what bounds bit-exactness and keeps a sequential row from
+    // being the kernel's tail), but the chunks of a row that is split anyway are at most plan_chunk_slots() = 128 slots long: a chunk
+    // is a latency-bound chain of len / 8 row-load batches, and the fused layer kernel's pre-pass over the split rows — nothing
+    // else runs beside it — took 110 us of a 4.8 ms GCN layer with 512-slot chunks on the products shape.
+    const int64_t clen = std::min<int64_t>(p->long_thresh, plan_chunk_slots());
+    for (const Tri &t : h) {
+        const int64_t len = t.end - t.beg;
+        const int64_t nch = (len + clen - 1) / clen;
+        const int64_t csz = (len + nch - 1) / nch;  // balanced chunks, each <= clen <= long_thresh slots
+        for (int64_t c = 0; c < nch; ++c) {
+            crow.push_back((int32_t)t.row);
+            clrow.push_back((int32_t)rows.size());
+            cbeg.push_back((uint32_t)(t.beg + c * csz));
+            cend.push_back((uint32_t)std::min(t.beg + (c + 1) * csz, t.end));
+        }
+        rows.push_back((int32_t)t.row);
+        cptr.push_back((int32_t)crow.size());
+    }
+    if (crow.size() >= (size_t)INT32_MAX)
+        return fail(GNNMP_EUNSUPPORTED, "plan_create: %zu chunks of split rows exceed the int32 chunk index", crow.size());
+    p->n_chunks = (int)crow.size();
+    auto upload = [&](auto *&dst, const auto &v) -> hipError_t {
+        const size_t bytes = sizeof(v[0]) * v.size();
+        const hipError_t e = alloc_into(dst, v.size());
+        if (e != hipSuccess) return e;
+        p->bytes += (int64_t)bytes;
+        return hipMemcpy(dst, v.data(), bytes, hipMemcpyHostToDevice);
+    };
+    GNNMP_HIP(upload(p->long_rows, rows));
+    GNNMP_HIP(upload(p->long_cptr, cptr));
+    GNNMP_HIP(upload(p->chunk_row, crow));
+    GNNMP_HIP(upload(p->chunk_lrow, clrow));
+    GNNMP_HIP(upload(p->chunk_beg, cbeg));
+    GNNMP_HIP(upload(p->chunk_end, cend));
+    return GNNMP_OK;
 }
 
 }  // namespace gnnmp
@@ -483,20 +433,10 @@ int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known) {
         p->col = nullptr;
         p->eid = nullptr;
     }
-    if (p->rowptr) (void)hipFree(p->rowptr);
-    if (p->col) (void)hipFree(p->col);
-    if (p->eid) (void)hipFree(p->eid);
-    if (p->long_rows) (void)hipFree(p->long_rows);
-    if (p->long_cptr) (void)hipFree(p->long_cptr);
-    if (p->chunk_row) (void)hipFree(p->chunk_row);
-    if (p->chunk_lrow) (void)hipFree(p->chunk_lrow);
-    if (p->arrive) (void)hipFree(p->arrive);
-    if (p->spart) (void)hipFree(p->spart);
-    if (p->chunk_beg) (void)hipFree(p->chunk_beg);
-    if (p->chunk_end) (void)hipFree(p->chunk_end);
-    if (p->ws) (void)hipFree(p->ws);
-    if (p->ticket) (void)hipFree(p->ticket);
-    if (p->row_order) (void)hipFree(p->row_order);
+    void *const owned[] = {p->rowptr, p->col, p->eid, p->long_rows, p->long_cptr, p->chunk_row, p->chunk_lrow, p->arrive, p->spart,
+                           p->chunk_beg, p->chunk_end, p->ws, p->ticket, p->row_order};
+    for (void *q : owned)
+        if (q) (void)dev_free(q);
     delete p;
     return GNNMP_OK;
 }
@@ -527,7 +467,7 @@ int gnnmp_plan_create(gnnmp_graph_t **out, const void *src, const void *dst, int
         return fail(GNNMP_EUNSUPPORTED, "plan_create: E' = %lld (limit 2^32 - 65536) / N = %lld (limit 2^31 - 2) exceed the plan format",
                     (long long)Etot, (long long)std::max(n_src, n_dst));
 
-    gnnmp_graph_t *p = new gnnmp_graph_t();
+    PlanPtr p(new gnnmp_graph_t());
     p->n_src = n_src;
     p->n_dst = n_dst;
     p->n_edges = n_edges;
@@ -535,72 +475,50 @@ int gnnmp_plan_create(gnnmp_graph_t **out, const void *src, const void *dst, int
     p->self_loops = add_self_loops ? 1 : 0;
     p->long_thresh = plan_long_thresh(Etot);
 
-    uint32_t *keys_in = nullptr, *keys_out = nullptr, *vals_in = nullptr;
-    int *flags = nullptr;  // [0] bad index
-    int rc = GNNMP_OK;
     const int BS = 256;
     const size_t epad = (size_t)std::max<int64_t>(Etot, 1);
-
-#define PLAN_HIP(expr)                                  \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-
-    PLAN_HIP(hipMalloc((void **)&p->rowptr, sizeof(uint32_t) * (size_t)(n_dst + 1)));
-    PLAN_HIP(hipMalloc((void **)&p->col, sizeof(int32_t) * epad));
-    PLAN_HIP(hipMalloc((void **)&p->eid, sizeof(int32_t) * epad));
-    PLAN_HIP(hipMalloc((void **)&flags, sizeof(int) * 4));
-    PLAN_HIP(hipMemsetAsync(flags, 0, sizeof(int) * 4, stream));
+    DevBuf<int> flags;                  // [0] bad index
+    DevBuf<unsigned char> sort_keys;    // keys_in | keys_out | vals_in: one allocation for the three key / value arrays of the sort
+    uint32_t *keys_out = nullptr;
+    GNNMP_HIP(alloc_into(p->rowptr, (size_t)(n_dst + 1)));
+    GNNMP_HIP(alloc_into(p->col, epad));
+    GNNMP_HIP(alloc_into(p->eid, epad));
+    GNNMP_HIP(flags.alloc(4));
+    GNNMP_HIP(hipMemsetAsync(flags.get(), 0, sizeof(int) * 4, stream));
     p->bytes = (int64_t)(sizeof(int32_t) * ((size_t)(n_dst + 1) + 2 * epad));
 
     if (Etot > 0) {
-        // one allocation for the three key / value arrays of the sort
         const size_t piece = (sizeof(uint32_t) * epad + 255) & ~(size_t)255;
-        PLAN_HIP(hipMalloc((void **)&keys_in, 3 * piece));
-        keys_out = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(keys_in) + piece);
-        vals_in = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(keys_in) + 2 * piece);
+        GNNMP_HIP(sort_keys.alloc(3 * piece));
+        uint32_t *keys_in = reinterpret_cast<uint32_t *>(sort_keys.get());
+        keys_out = reinterpret_cast<uint32_t *>(sort_keys.get() + piece);
+        uint32_t *vals_in = reinterpret_cast<uint32_t *>(sort_keys.get() + 2 * piece);
         plan_fill_keys<<<nblocks(Etot, BS), BS, 0, stream>>>(src, dst, idx_bytes, index_base,
                                                              n_edges, Etot, n_src, n_dst, keys_in,
-                                                             vals_in, flags);
-        PLAN_HIP(hipGetLastError());
+                                                             vals_in, flags.get());
+        GNNMP_HIP(hipGetLastError());
         if (validate) {
             int bad = 0;
-            PLAN_HIP(hipMemcpyAsync(&bad, flags, sizeof(int), hipMemcpyDeviceToHost, stream));
-            PLAN_HIP(hipStreamSynchronize(stream));
-            if (bad) {
-                rc = fail(GNNMP_EBOUNDS, "plan_create: edge index outside 1..N (n_src=%lld n_dst=%lld)",
-                          (long long)n_src, (long long)n_dst);
-                goto done;
-            }
+            GNNMP_HIP(hipMemcpyAsync(&bad, flags.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+            GNNMP_HIP(hipStreamSynchronize(stream));
+            if (bad)
+                return fail(GNNMP_EBOUNDS, "plan_create: edge index outside 1..N (n_src=%lld n_dst=%lld)",
+                            (long long)n_src, (long long)n_dst);
         }
         // stable LSD radix sort of (dst, edge position) on the bits that can be set
         unsigned bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < n_dst) ++bits;
-        rc = radix_sort_pairs_u32(keys_in, keys_out, vals_in, reinterpret_cast<uint32_t *>(p->eid), (size_t)Etot, 0, (int)bits,
-                                  stream);
-        if (rc != GNNMP_OK) goto done;
+        GNNMP_TRY(radix_sort_pairs_u32(keys_in, keys_out, vals_in, reinterpret_cast<uint32_t *>(p->eid), (size_t)Etot, 0, (int)bits,
+                                       stream));
         plan_col<<<nblocks(Etot, BS), BS, 0, stream>>>(src, idx_bytes, index_base, n_edges, Etot,
                                                        reinterpret_cast<uint32_t *>(p->eid), p->col);
-        PLAN_HIP(hipGetLastError());
+        GNNMP_HIP(hipGetLastError());
     }
     plan_rowptr<<<nblocks(n_dst + 1, BS), BS, 0, stream>>>(keys_out, Etot, n_dst, p->rowptr);
-    PLAN_HIP(hipGetLastError());
+    GNNMP_HIP(hipGetLastError());
 
-    rc = plan_build_long_rows(p, stream);
-
-done:
-    if (keys_in) (void)hipFree(keys_in);   // keys_out and vals_in live in the same allocation
-    if (flags) (void)hipFree(flags);
-#undef PLAN_HIP
-    if (rc != GNNMP_OK) {
-        gnnmp_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    GNNMP_TRY(plan_build_long_rows(p.get(), stream));
+    *out = p.release();
     return GNNMP_OK;
 }
 
@@ -616,57 +534,38 @@ int gnnmp_plan_from_csc(gnnmp_graph_t **out, const void *colptr, const void *row
     if (n_edges >= (int64_t)GNNMP_MAX_SLOTS || n_src >= (int64_t)INT32_MAX || n_dst >= (int64_t)INT32_MAX)
         return fail(GNNMP_EUNSUPPORTED, "plan_from_csc: E = %lld (limit 2^32 - 65536) / N = %lld (limit 2^31 - 2) exceed the plan format",
                     (long long)n_edges, (long long)std::max(n_src, n_dst));
-    gnnmp_graph_t *p = new gnnmp_graph_t();
+    PlanPtr p(new gnnmp_graph_t());
     p->n_src = n_src;
     p->n_dst = n_dst;
     p->n_edges = n_edges;
     p->n_total = n_edges;
     p->long_thresh = plan_long_thresh(n_edges);
-    int *flags = nullptr;
-    int rc = GNNMP_OK;
     const int BS = 256;
     const size_t epad = (size_t)std::max<int64_t>(n_edges, 1);
-#define PLAN_HIP(expr)                                  \
-    do {                                                \
-        hipError_t e__ = (expr);                        \
-        if (e__ != hipSuccess) {                        \
-            rc = hip_fail(e__, #expr);                  \
-            goto done;                                  \
-        }                                               \
-    } while (0)
-    PLAN_HIP(hipMalloc((void **)&p->rowptr, sizeof(uint32_t) * (size_t)(n_dst + 1)));
-    PLAN_HIP(hipMalloc((void **)&p->col, sizeof(int32_t) * epad));
-    PLAN_HIP(hipMalloc((void **)&p->eid, sizeof(int32_t) * epad));
-    PLAN_HIP(hipMalloc((void **)&flags, sizeof(int) * 4));
-    PLAN_HIP(hipMemsetAsync(flags, 0, sizeof(int) * 4, stream));
+    DevBuf<int> flags;
+    GNNMP_HIP(alloc_into(p->rowptr, (size_t)(n_dst + 1)));
+    GNNMP_HIP(alloc_into(p->col, epad));
+    GNNMP_HIP(alloc_into(p->eid, epad));
+    GNNMP_HIP(flags.alloc(4));
+    GNNMP_HIP(hipMemsetAsync(flags.get(), 0, sizeof(int) * 4, stream));
     p->bytes = (int64_t)(sizeof(int32_t) * ((size_t)(n_dst + 1) + 2 * epad));
-    csc_rowptr_kernel<<<nblocks(n_dst + 1, BS), BS, 0, stream>>>(colptr, idx_bytes, index_base, n_dst, n_edges, p->rowptr, flags);
-    PLAN_HIP(hipGetLastError());
+    csc_rowptr_kernel<<<nblocks(n_dst + 1, BS), BS, 0, stream>>>(colptr, idx_bytes, index_base, n_dst, n_edges, p->rowptr, flags.get());
+    GNNMP_HIP(hipGetLastError());
     if (n_edges > 0) {
-        csc_col_kernel<<<nblocks(n_edges, BS), BS, 0, stream>>>(rowval, idx_bytes, index_base, n_edges, n_src, p->col, p->eid, flags);
-        PLAN_HIP(hipGetLastError());
+        csc_col_kernel<<<nblocks(n_edges, BS), BS, 0, stream>>>(rowval, idx_bytes, index_base, n_edges, n_src, p->col, p->eid, flags.get());
+        GNNMP_HIP(hipGetLastError());
     }
     (void)validate;
-    {   // ALWAYS checked: the build synchronises below anyway (plan_build_long_rows), so skipping the read-back would save nothing, and a
-        // column pointer sanitised entry by entry can leave a row with beg > end that no kernel would ever write
-        int bad = 0;
-        PLAN_HIP(hipMemcpyAsync(&bad, flags, sizeof(int), hipMemcpyDeviceToHost, stream));
-        PLAN_HIP(hipStreamSynchronize(stream));
-        if (bad) {
-            rc = fail(GNNMP_EBOUNDS, "plan_from_csc: colptr is not a monotone 0..E column pointer, or a row index lies outside 1..n_src "
-                      "(n_src=%lld n_dst=%lld E=%lld)", (long long)n_src, (long long)n_dst, (long long)n_edges);
-            goto done;
-        }
-    }
-    rc = plan_build_long_rows(p, stream);
-done:
-    if (flags) (void)hipFree(flags);
-#undef PLAN_HIP
-    if (rc != GNNMP_OK) {
-        gnnmp_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    // ALWAYS checked: the build synchronises below anyway (plan_build_long_rows), so skipping the read-back would save nothing, and a
+    // column pointer sanitised entry by entry can leave a row with beg > end that no kernel would ever write
+    int bad = 0;
+    GNNMP_HIP(hipMemcpyAsync(&bad, flags.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    if (bad)
+        return fail(GNNMP_EBOUNDS, "plan_from_csc: colptr is not a monotone 0..E column pointer, or a row index lies outside 1..n_src "
+                    "(n_src=%lld n_dst=%lld E=%lld)", (long long)n_src, (long long)n_dst, (long long)n_edges);
+    GNNMP_TRY(plan_build_long_rows(p.get(), stream));
+    *out = p.release();
     return GNNMP_OK;
 }
 

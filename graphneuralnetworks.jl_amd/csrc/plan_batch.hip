@@ -222,11 +222,9 @@ static int batch_plan_alloc(gnnmp_graph_t **out, BatchTab *tab, int64_t k, int64
     const size_t o_desc = o_slotoff + up256(sizeof(uint32_t) * (size_t)(k + 1));
     const size_t o_status = o_desc + up256(sizeof(MemberDesc) * (size_t)std::max<int64_t>(k, 1));
     const size_t total = o_status + 256;
-    gnnmp_graph_t *p = new gnnmp_graph_t();
-    if (!pool_take(&p->block, &p->block_bytes, total, stream)) {
-        delete p;
+    PlanPtr p(new gnnmp_graph_t());
+    if (!pool_take(&p->block, &p->block_bytes, total, stream))
         return fail(GNNMP_EALLOC, "batch plan: hipMalloc of %zu bytes failed", total);
-    }
     unsigned char *b = static_cast<unsigned char *>(p->block);
     p->rowptr = reinterpret_cast<uint32_t *>(b + o_rowptr);
     p->col = reinterpret_cast<int32_t *>(b + o_col);
@@ -242,7 +240,7 @@ static int batch_plan_alloc(gnnmp_graph_t **out, BatchTab *tab, int64_t k, int64
     p->self_loops = self_loops;
     p->long_thresh = plan_long_thresh(n_slots);
     p->bytes = (int64_t)total;
-    *out = p;
+    *out = p.release();
     return GNNMP_OK;
 }
 

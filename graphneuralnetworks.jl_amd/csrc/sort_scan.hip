@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scratch.h"
 #include "sort_scan.h"
 
 namespace gnnmp {
@@ -271,12 +272,11 @@ static int exclusive_scan_impl(const T *in, T *out, size_t n, hipStream_t stream
         if (e0 != hipSuccess) return hip_fail(e0, "exclusive_scan");
         return GNNMP_OK;
     }
-    T *sums = nullptr;
-    GNNMP_HIP(hipMalloc((void **)&sums, sizeof(T) * scan_blocks(n)));
-    exclusive_scan_enqueue<T>(in, out, n, sums, stream);
+    DevBuf<T> sums;
+    GNNMP_HIP(sums.alloc(scan_blocks(n)));
+    exclusive_scan_enqueue<T>(in, out, n, sums.get(), stream);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);     // the block sums are freed below
-    (void)hipFree(sums);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);     // the block sums die with this call
     if (e != hipSuccess) return hip_fail(e, "exclusive_scan");
     return GNNMP_OK;
 }
@@ -313,46 +313,35 @@ static int radix_sort_impl(const K *keys_in, K *keys_out, const uint32_t *vals_i
     const int passes = std::max(1, (end_bit - begin_bit + 7) / 8);
     const size_t n_tiles = (n + RS_WT - 1) / RS_WT;
     const size_t m = 256 * n_tiles;
-    K *ktmp = nullptr;
-    uint32_t *vtmp = nullptr, *counts = nullptr, *sums = nullptr;
-    unsigned long long *dvary = nullptr, hvary = 0;
-    int rc = GNNMP_OK;
     // ONE allocation for every temporary (hipMalloc / hipFree cost 0.1 - 0.5 ms each at these sizes: five pairs of them were a
     // third of the products plan build): [ktmp | vtmp | counts | sums | dvary], each piece 256-byte aligned
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_k = up(sizeof(K) * n), b_v = PAIRS ? up(sizeof(uint32_t) * n) : 0, b_c = up(sizeof(uint32_t) * m),
                  b_s = up(sizeof(uint32_t) * scan_blocks(m));
-    unsigned char *arena = nullptr;
-    hipError_t e = hipMalloc((void **)&arena, b_k + b_v + b_c + b_s + 256);
-    if (e != hipSuccess) {
-        rc = hip_fail(e, "hipMalloc(radix sort temporaries)");
-    } else {
-        ktmp = reinterpret_cast<K *>(arena);
-        vtmp = PAIRS ? reinterpret_cast<uint32_t *>(arena + b_k) : nullptr;
-        counts = reinterpret_cast<uint32_t *>(arena + b_k + b_v);
-        sums = reinterpret_cast<uint32_t *>(arena + b_k + b_v + b_c);
-        dvary = reinterpret_cast<unsigned long long *>(arena + b_k + b_v + b_c + b_s);
-    }
+    DevBuf<unsigned char> arena;
+    hipError_t e = arena.alloc(b_k + b_v + b_c + b_s + 256);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(radix sort temporaries)");
+    K *ktmp = reinterpret_cast<K *>(arena.get());
+    uint32_t *vtmp = PAIRS ? reinterpret_cast<uint32_t *>(arena.get() + b_k) : nullptr;
+    uint32_t *counts = reinterpret_cast<uint32_t *>(arena.get() + b_k + b_v);
+    uint32_t *sums = reinterpret_cast<uint32_t *>(arena.get() + b_k + b_v + b_c);
+    unsigned long long *dvary = reinterpret_cast<unsigned long long *>(arena.get() + b_k + b_v + b_c + b_s), hvary = 0;
     const unsigned blocks = (unsigned)((n_tiles + RS_WPB - 1) / RS_WPB);
     const size_t scatter_lds = (size_t)RS_WT * RS_WPB * (sizeof(K) + (PAIRS ? sizeof(uint32_t) : 0)) + (256 * RS_WPB + 256) * sizeof(uint32_t);
-    {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&rs_scatter<K, PAIRS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)scatter_lds);
-        if (ea != hipSuccess && rc == GNNMP_OK) rc = hip_fail(ea, "hipFuncSetAttribute(rs_scatter)");
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rs_scatter<K, PAIRS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)scatter_lds);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(rs_scatter)");
+    e = hipMemsetAsync(dvary, 0, sizeof(unsigned long long), stream);
+    if (e == hipSuccess) {
+        const unsigned vb = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)device_cus() * 8);
+        rs_varying_bits<K><<<vb, 256, 0, stream>>>(keys_in, n, dvary);
+        e = hipMemcpyAsync(&hvary, dvary, sizeof(hvary), hipMemcpyDeviceToHost, stream);
     }
-    if (rc == GNNMP_OK) {
-        e = hipMemsetAsync(dvary, 0, sizeof(unsigned long long), stream);
-        if (e == hipSuccess) {
-            const unsigned vb = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)device_cus() * 8);
-            rs_varying_bits<K><<<vb, 256, 0, stream>>>(keys_in, n, dvary);
-            e = hipMemcpyAsync(&hvary, dvary, sizeof(hvary), hipMemcpyDeviceToHost, stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) rc = hip_fail(e, "radix sort: varying bits");
-    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "radix sort: varying bits");
     const K *ksrc = keys_in;
     const uint32_t *vsrc = vals_in;
-    for (int p = 0; p < passes && rc == GNNMP_OK; ++p) {
+    for (int p = 0; p < passes; ++p) {
         const int shift = begin_bit + 8 * p;
         if (((hvary >> shift) & 255ull) == 0) continue;    // every key has the same digit here: nothing moves
         rs_hist<K><<<blocks, 64 * RS_WPB, 0, stream>>>(ksrc, n, shift, counts, n_tiles);
@@ -362,21 +351,18 @@ static int radix_sort_impl(const K *keys_in, K *keys_out, const uint32_t *vals_i
         uint32_t *vdst = (ksrc == keys_out) ? vtmp : vals_out;
         rs_scatter<K, PAIRS><<<blocks, 64 * RS_WPB, scatter_lds, stream>>>(ksrc, vsrc, n, shift, counts, n_tiles, kdst, vdst);
         e = hipGetLastError();
-        if (e != hipSuccess) rc = hip_fail(e, "radix sort pass");
+        if (e != hipSuccess) return hip_fail(e, "radix sort pass");
         ksrc = kdst;
         vsrc = vdst;
     }
-    if (rc == GNNMP_OK && ksrc != keys_out) {              // every pass was trivial, or the last one landed in the temporary
+    if (ksrc != keys_out) {              // every pass was trivial, or the last one landed in the temporary
         e = hipMemcpyAsync(keys_out, ksrc, sizeof(K) * n, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess && PAIRS) e = hipMemcpyAsync(vals_out, vsrc, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) rc = hip_fail(e, "radix sort copy-out");
+        if (e != hipSuccess) return hip_fail(e, "radix sort copy-out");
     }
-    if (rc == GNNMP_OK) {
-        e = hipStreamSynchronize(stream);                    // temporaries are freed below
-        if (e != hipSuccess) rc = hip_fail(e, "radix sort");
-    }
-    if (arena) (void)hipFree(arena);
-    return rc;
+    e = hipStreamSynchronize(stream);                    // the temporaries die with this call
+    if (e != hipSuccess) return hip_fail(e, "radix sort");
+    return GNNMP_OK;
 }
 
 int radix_sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, size_t n,
