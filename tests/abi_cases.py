@@ -1587,6 +1587,25 @@ def tgcn_forward64(P, Uzr, Uh, h0, N, T, D):
     return y, gates
 
 
+def tgcn_backward64(dy, y, gates, Uzr, Uh, h0, N, T, D):
+    """backpropagation through time, the statements of the header (gnnmp_tgcn_step_grad_f32) step by step in float64, from the saved
+    y and gates as given.  Returns (dP [N, T, 3D], S [N, T, 2D], dh0 [N, D])"""
+    Y, G, Uz, Ur, U = y.astype(f64), gates.astype(f64), Uzr.astype(f64)[:D], Uzr.astype(f64)[D:], Uh.astype(f64)
+    hstart = np.zeros((N, D)) if h0 is None else np.broadcast_to(h0.astype(f64), (N, D))
+    dP, S, carry = np.zeros((N, T, 3 * D)), np.zeros((N, T, 2 * D)), np.zeros((N, D))
+    for t in range(T - 1, -1, -1):
+        hp = Y[:, t - 1] if t else hstart
+        z, rr, ht = G[:, t, :D], G[:, t, D:2 * D], G[:, t, 2 * D:]
+        dh = dy.astype(f64)[:, t] + carry
+        ah = dh * z * (1 - ht * ht)
+        drh = ah @ U
+        az = dh * (ht - hp) * z * (1 - z)
+        ar = drh * hp * rr * (1 - rr)
+        carry = dh * (1 - z) + drh * rr + az @ Uz + ar @ Ur
+        dP[:, t], S[:, t] = np.concatenate([az, ar, ah], 1), np.concatenate([hp, rr * hp], 1)
+    return dP, S, carry
+
+
 @cases_of("gnnmp_tgcn_recurrence_f32")
 def _(ctx):
     for k, (N, T, D, tags) in enumerate(TG):
@@ -1613,20 +1632,7 @@ def _(ctx):
         y, gates = (v.astype(f32) for v in tgcn_forward64(P, Uzr, Uh, h0, N, T, D))
         want_S, want_h0 = k % 2 == 0, k % 3 != 2
         def ref(host, y=y, gates=gates, Uzr=Uzr, Uh=Uh, dy=dy, h0=h0, N=N, T=T, D=D, want_S=want_S, want_h0=want_h0):
-            # backpropagation through time, the statements of the header (gnnmp_tgcn_step_grad_f32) step by step in float64
-            Y, G, Uz, Ur, U = y.astype(f64), gates.astype(f64), Uzr.astype(f64)[:D], Uzr.astype(f64)[D:], Uh.astype(f64)
-            hstart = np.zeros((N, D)) if h0 is None else np.broadcast_to(h0.astype(f64), (N, D))
-            dP, S, carry = np.zeros((N, T, 3 * D)), np.zeros((N, T, 2 * D)), np.zeros((N, D))
-            for t in range(T - 1, -1, -1):
-                hp = Y[:, t - 1] if t else hstart
-                z, rr, ht = G[:, t, :D], G[:, t, D:2 * D], G[:, t, 2 * D:]
-                dh = dy.astype(f64)[:, t] + carry
-                ah = dh * z * (1 - ht * ht)
-                drh = ah @ U
-                az = dh * (ht - hp) * z * (1 - z)
-                ar = drh * hp * rr * (1 - rr)
-                carry = dh * (1 - z) + drh * rr + az @ Uz + ar @ Ur
-                dP[:, t], S[:, t] = np.concatenate([az, ar, ah], 1), np.concatenate([hp, rr * hp], 1)
+            dP, S, carry = tgcn_backward64(dy, y, gates, Uzr, Uh, h0, N, T, D)
             out = {"dP": dP}
             if want_S:
                 out["S"] = S

@@ -229,6 +229,11 @@ CASES = {
     "out128": dict(n=50, m=200, cin=3, cout=128, T=3),
     "out_beyond_envelope": dict(n=20, m=60, cin=3, cout=136, T=2),
     "T1": dict(n=25, m=80, cin=4, cout=9, T=1),
+    # backward_temporal.py's slicing (_diag_blocks, the dU blocks, stacked_params) at NT = 3, 5, 6 and the ragged NT = 8
+    "out40": dict(n=40, m=160, cin=3, cout=40, T=3),
+    "out72": dict(n=40, m=160, cin=3, cout=72, T=3),
+    "out90": dict(n=40, m=160, cin=3, cout=90, T=3),
+    "out120": dict(n=40, m=160, cin=3, cout=120, T=3),
 }
 
 
