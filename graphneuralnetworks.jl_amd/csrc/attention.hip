@@ -8,7 +8,7 @@
 // resident) and the 4*H*C-byte source row.  Per destination row the three reference steps run in the reference's order:
 // max over the row, sum of exp(l - max) in edge order, then alpha = num / den (true division), beta = alpha * Wx_j
 // (rounded), accumulated in edge order.
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
@@ -45,9 +45,8 @@ __global__ void __launch_bounds__(256) gat_node_scores_kernel(const float *Wx, c
 
 // ---- fused edge softmax + weighted aggregate -----------------------------------------------------
 struct GatArgs {
-    const uint32_t *rowptr;
-    const int32_t *col;
-    const int32_t *eid;
+    PlanRows rows;       // n_chunks = 0 here: split rows are not chunked but go whole to gat_long_rows_kernel
+    RowGeom geom;
     const float *Wx;     // [n_src][D], D = H*C
     const float *sdst;   // [n_dst][H]
     const float *ssrc;   // [n_src][H]
@@ -55,15 +54,8 @@ struct GatArgs {
     float *alpha_out;    // [E'][H] or null
     const float *bias;   // [D] or null  (σ.(x .+ bias), conv.jl:147, concat case)
     int act;
-    const int32_t *long_rows;
-    int n_long;
     int H, C, D;
-    int n_rows;
-    int log2g;
     float slope;
-    int long_thresh;
-    int cpx;
-    int waves;
 };
 
 // pass 1: running max of the row's logits (per lane: the lane's head)
@@ -73,7 +65,7 @@ __device__ __forceinline__ float gat_pass_max(const GatArgs &a, uint32_t beg, ui
     float mx = -__builtin_inff();
     for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float s[U];
@@ -96,7 +88,7 @@ __device__ __forceinline__ float gat_pass_den(const GatArgs &a, uint32_t beg, ui
     float den = 0.0f;
     for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float s[U];
@@ -122,8 +114,8 @@ __device__ __forceinline__ void gat_pass_acc(const GatArgs &a, uint32_t beg, uin
         const uint32_t p = base + lig;
         int c = 0, e = 0;                      // e: original edge position, an unsigned 32-bit value carried in an int
         if (p < end) {
-            c = a.col[p];
-            if (a.alpha_out) e = a.eid[p];
+            c = a.rows.col[p];
+            if (a.alpha_out) e = a.rows.eid[p];
         }
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
@@ -178,21 +170,21 @@ template <int VEC, int U>
 __global__ void __launch_bounds__(256) gat_rows_kernel(const GatArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
+    const int grp = lane >> a.geom.log2g;
     const int gbase = lane - lig;
-    const int rpw = 64 >> a.log2g;
-    const int chunk = a.cpx ? xcd_remap(blockIdx.x, a.cpx, 1) : (int)blockIdx.x;
-    const int64_t row64 = ((int64_t)chunk * a.waves + wave) * rpw + grp;
-    if (row64 >= a.n_rows) return;
+    const int rpw = 64 >> a.geom.log2g;
+    const int chunk = a.geom.cpx ? xcd_remap(blockIdx.x, a.geom.cpx, 1) : (int)blockIdx.x;
+    const int64_t row64 = ((int64_t)chunk * a.geom.waves + wave) * rpw + grp;
+    if (row64 >= a.rows.n_rows) return;
     const int row = (int)row64;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
     const int h = active ? f0 / a.C : 0;
-    const uint32_t beg = a.rowptr[row];
-    const uint32_t end = a.rowptr[row + 1];
-    if (end - beg > a.long_thresh) return;
+    const uint32_t beg = a.rows.rowptr[row];
+    const uint32_t end = a.rows.rowptr[row + 1];
+    if (end - beg > a.rows.long_thresh) return;
     const float sd = a.sdst[(int64_t)row * a.H + h];
     const float mx = gat_pass_max<U>(a, beg, end, lig, gbase, G, h, sd);
     const float den = gat_pass_den<U>(a, beg, end, lig, gbase, G, h, sd, mx);
@@ -208,17 +200,17 @@ template <int VEC, int U>
 __global__ void __launch_bounds__(1024) gat_long_rows_kernel(const GatArgs a) {
     extern __shared__ float lds[];  // [NG][G*VEC]
     const int lane = threadIdx.x & 63;
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = lane & (G - 1);
     const int gbase = lane - lig;
-    const int q = threadIdx.x >> a.log2g;
-    const int NG = 1024 >> a.log2g;
-    const int row = a.long_rows[blockIdx.x];
+    const int q = threadIdx.x >> a.geom.log2g;
+    const int NG = 1024 >> a.geom.log2g;
+    const int row = a.rows.long_rows[blockIdx.x];
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
     const int h = active ? f0 / a.C : 0;
-    const uint32_t beg = a.rowptr[row];
-    const uint32_t end = a.rowptr[row + 1];
+    const uint32_t beg = a.rows.rowptr[row];
+    const uint32_t end = a.rows.rowptr[row + 1];
     const uint32_t len = end - beg;
     const uint32_t part = (len + NG - 1) / NG;
     const uint32_t pb = (uint32_t)min((uint64_t)beg + (uint64_t)q * part, (uint64_t)end);
@@ -259,29 +251,20 @@ __global__ void __launch_bounds__(1024) gat_long_rows_kernel(const GatArgs a) {
 
 template <int VEC>
 static int launch_gat(GatArgs a, hipStream_t stream) {
-    const int G = 1 << a.log2g;
-    const int rpw = 64 / G;
+    const int G = 1 << a.geom.log2g;
     int waves = knob(KNOB_BLOCK_WAVES);
     if (waves < 1 || waves > 4) waves = 1;   // auto (see gat_fused.hip)
-    a.waves = waves;
-    const int rows_per_block = rpw * waves;
-    const int64_t chunks = ((int64_t)a.n_rows + rows_per_block - 1) / rows_per_block;
+    a.geom.waves = waves;
     const int lanes_needed = (a.D + VEC - 1) / VEC;
     const int tiles = (lanes_needed + G - 1) / G;
-    if (chunks > 0) {
-        int64_t gx = chunks;
-        a.cpx = 0;
-        if (use_xcd_remap(a.n_rows, a.D, chunks)) {
-            a.cpx = (int)((chunks + 7) / 8);
-            gx = (int64_t)a.cpx * 8;
-        }
-        dim3 grid((unsigned)gx, (unsigned)tiles);
+    const dim3 grid = row_grid(a.rows, a.geom, tiles, use_xcd_remap(a.rows.n_rows, a.D, row_blocks(a.rows, a.geom)));   // (nbc = 0)
+    if (grid.x > 0) {
         gat_rows_kernel<VEC, 4><<<grid, 64 * waves, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("gat_rows_kernel");
     }
-    if (a.n_long > 0) {
-        dim3 grid((unsigned)a.n_long, (unsigned)tiles);
-        gat_long_rows_kernel<VEC, 4><<<grid, 1024, sizeof(float) * 1024 * VEC, stream>>>(a);
+    if (a.rows.n_long > 0) {
+        dim3 lg((unsigned)a.rows.n_long, (unsigned)tiles);
+        gat_long_rows_kernel<VEC, 4><<<lg, 1024, sizeof(float) * 1024 * VEC, stream>>>(a);
         GNNMP_LAUNCH_CHECK("gat_long_rows_kernel");
     }
     return GNNMP_OK;
@@ -339,9 +322,8 @@ int gnnmp_gat_aggregate_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
     if (!out || !score_dst || (plan->n_total > 0 && (!Wx_src || !score_src)))
         return fail(GNNMP_EINVAL, "gat_aggregate: null pointer");
     GatArgs a;
-    a.rowptr = plan->rowptr;
-    a.col = plan->col;
-    a.eid = plan->eid;
+    a.rows = plan_rows(plan);
+    a.rows.n_chunks = 0;
     a.Wx = Wx_src;
     a.sdst = score_dst;
     a.ssrc = score_src;
@@ -349,20 +331,14 @@ int gnnmp_gat_aggregate_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
     a.alpha_out = alpha_out;
     a.bias = bias;
     a.act = act;
-    a.long_rows = plan->long_rows;
-    a.n_long = plan->n_long;
     a.H = (int)H;
     a.C = (int)C;
     a.D = (int)(H * C);
-    a.n_rows = (int)plan->n_dst;
     a.slope = negative_slope;
-    a.long_thresh = plan->long_thresh;
-    a.cpx = 0;
-    a.waves = 4;
     // the lane's VEC features must lie inside one head
     int vec = pick_vec(a.D, Wx_src, out);
     while (vec > 1 && (C % vec) != 0) vec >>= 1;
-    a.log2g = pick_log2g((a.D + vec - 1) / vec);
+    a.geom = RowGeom{pick_log2g((a.D + vec - 1) / vec), 4, 0, 0};
     switch (vec) {
         case 4: return launch_gat<4>(a, stream);
         case 2: return launch_gat<2>(a, stream);

@@ -14,17 +14,13 @@
 // Long rows are chunked into virtual rows; partials are folded in chunk order.  No atomics.
 #include <algorithm>
 
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
 struct AttnBwdArgs {
-    const uint32_t *rowptr;
-    const int32_t *col;
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    const int32_t *long_rows, *long_cptr;
-    int n_chunks, n_long, n_rows, long_thresh;
+    PlanRows rows;        // of the plan the running pass walks (rows.eid: DROP's slot -> original edge position)
+    RowGeom geom;
     const float *Q, *K, *V;   // [n_dst][D], [n_src][D], [n_src][D]
     const float *a;           // GATV2: [H][C]
     const float *dout;        // Δ [n_dst][D]
@@ -34,39 +30,12 @@ struct AttnBwdArgs {
     float *dA;                // GATV2: per-destination Σ_j dl_ij lrelu(z_c)  [n_dst][D]
     float *dK, *dV;           // [n_src][D]  (GATV2: dK holds dK + dV, dV unused)
     float *partial;
-    int H, C, D, log2g, lph, waves;
+    int H, C, D, lph;
     float slope, scale;
-    const int32_t *eid;       // DROP: slot -> original edge position of the plan the running pass walks
     DropArgs drop;
 };
 
 __device__ __forceinline__ float lrelu_a(float x, float slope) { return x > 0.0f ? x : x * slope; }
-
-__device__ __forceinline__ bool attn_virtual_row(const AttnBwdArgs &a, int &v, bool &is_chunk, int &row, uint32_t &beg, uint32_t &end,
-                                                 int &lig, int &gbase, int &G) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    G = 1 << a.log2g;
-    lig = lane & (G - 1);
-    gbase = lane - lig;
-    const int grp = lane >> a.log2g;
-    const int rpw = 64 >> a.log2g;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return false;
-    v = (int)v64;
-    is_chunk = v < a.n_chunks;
-    if (is_chunk) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return false;
-    }
-    return true;
-}
 
 // number of VEC-wide accumulators pass 1 keeps per lane: Σαgf and Σαf for f = s_c (+ f = lrelu(z_c) for da) | f = K_jc
 template <int MODE>
@@ -103,10 +72,11 @@ __device__ __forceinline__ void attn_dst_finalize(const AttnBwdArgs &a, int row,
 template <int VEC, int U, int LPH, int MODE, bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_dst_kernel(const AttnBwdArgs a) {
     constexpr int NA = Acc1<MODE>::N;
-    int v, row, lig, gbase, G;
-    uint32_t beg, end;
-    bool is_chunk;
-    if (!attn_virtual_row(a, v, is_chunk, row, beg, end, lig, gbase, G)) return;
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     const int fc = active ? f0 : 0;
@@ -133,10 +103,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dst_kernel(const AttnBwdArgs a) 
     for (int k = 0; k < NA; ++k)
 #pragma unroll
         for (int q = 0; q < VEC; ++q) acc[k][q] = 0.0f;
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.eid[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
+        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float kv[U][VEC];                                   // K_j
@@ -212,14 +182,14 @@ __global__ void __launch_bounds__(256) attn_bwd_dst_kernel(const AttnBwdArgs a) 
 template <int VEC, int MODE>
 __global__ void __launch_bounds__(256) attn_bwd_dst_combine_kernel(const AttnBwdArgs a) {
     constexpr int NA = Acc1<MODE>::N;
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = threadIdx.x & (G - 1);
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.log2g;
-    if (r >= a.n_long) return;
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.geom.log2g;
+    if (r >= a.rows.n_long) return;
     const int f0 = lig * VEC;
     if (f0 >= a.D) return;
     const int h = f0 / a.C;
-    const int row = a.long_rows[r];
+    const int row = a.rows.long_rows[r];
     const int LN = a.D / VEC;
     const int64_t S = (int64_t)NA * a.D + LN;
     float S1 = 0.0f, acc[NA][VEC];
@@ -227,7 +197,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dst_combine_kernel(const AttnBwd
     for (int k = 0; k < NA; ++k)
 #pragma unroll
         for (int q = 0; q < VEC; ++q) acc[k][q] = 0.0f;
-    for (int c = a.long_cptr[r]; c < a.long_cptr[r + 1]; ++c) {
+    for (int c = a.rows.long_cptr[r]; c < a.rows.long_cptr[r + 1]; ++c) {
         const float *pc = a.partial + (int64_t)c * S;
         float t[NA][VEC];
 #pragma unroll
@@ -265,10 +235,11 @@ __device__ __forceinline__ void attn_src_store(const AttnBwdArgs &a, int row, in
 
 template <int VEC, int U, int LPH, int MODE, bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_src_kernel(const AttnBwdArgs a) {
-    int v, row, lig, gbase, G;
-    uint32_t beg, end;
-    bool is_chunk;
-    if (!attn_virtual_row(a, v, is_chunk, row, beg, end, lig, gbase, G)) return;
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     const int fc = active ? f0 : 0;
@@ -290,10 +261,10 @@ __global__ void __launch_bounds__(256) attn_bwd_src_kernel(const AttnBwdArgs a) 
     float dk[VEC], dv[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) dk[q] = dv[q] = 0.0f;
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.eid[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
+        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float dd[U][VEC], qq[U][VEC];
@@ -363,17 +334,17 @@ __global__ void __launch_bounds__(256) attn_bwd_src_kernel(const AttnBwdArgs a) 
 
 template <int VEC, int MODE>
 __global__ void __launch_bounds__(256) attn_bwd_src_combine_kernel(const AttnBwdArgs a) {
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = threadIdx.x & (G - 1);
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.log2g;
-    if (r >= a.n_long) return;
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.geom.log2g;
+    if (r >= a.rows.n_long) return;
     const int f0 = lig * VEC;
     if (f0 >= a.D) return;
-    const int row = a.long_rows[r];
+    const int row = a.rows.long_rows[r];
     float dk[VEC], dv[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) dk[q] = dv[q] = 0.0f;
-    for (int c = a.long_cptr[r]; c < a.long_cptr[r + 1]; ++c) {
+    for (int c = a.rows.long_cptr[r]; c < a.rows.long_cptr[r + 1]; ++c) {
         const float *pc = a.partial + (int64_t)c * 2 * a.D;
         float t1[VEC], t2[VEC];
         Vec<VEC>::load(pc + f0, t1);
@@ -418,52 +389,32 @@ __global__ void __launch_bounds__(256) attn_colsum_fold_kernel(const float *part
     if (threadIdx.x == 0) out[d] = red[0];
 }
 
-static void fill_plan(AttnBwdArgs &g, const gnnmp_graph *p) {
-    g.rowptr = p->rowptr;
-    g.col = p->col;
-    g.chunk_row = p->chunk_row;
-    g.chunk_beg = p->chunk_beg;
-    g.chunk_end = p->chunk_end;
-    g.long_rows = p->long_rows;
-    g.long_cptr = p->long_cptr;
-    g.n_chunks = p->n_chunks;
-    g.n_long = p->n_long;
-    g.n_rows = (int)p->n_dst;
-    g.long_thresh = p->long_thresh;
-    g.partial = p->ws;
-}
-
 template <int VEC, int LPH, int MODE, bool DROP>
 static int launch_attn_bwd(AttnBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *da, hipStream_t stream) {
-    const int G = 1 << g.log2g;
-    const int rpw = 64 / G;
-    g.waves = 1;
-    fill_plan(g, plan);
-    g.eid = plan->eid;
+    g.rows = plan_rows(plan);
+    g.partial = plan->ws;
     {
-        const int64_t nvirt = (int64_t)g.n_rows + g.n_chunks;
-        const int64_t blocks = (nvirt + rpw - 1) / rpw;
+        const unsigned blocks = row_grid(g.rows, g.geom, 1).x;
         if (blocks > 0) {
-            attn_bwd_dst_kernel<VEC, 4, LPH, MODE, DROP><<<(unsigned)blocks, 64, 0, stream>>>(g);
+            attn_bwd_dst_kernel<VEC, 4, LPH, MODE, DROP><<<blocks, 64, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("attn_bwd_dst_kernel");
         }
-        if (g.n_long > 0) {
-            const int64_t threads = (int64_t)g.n_long << g.log2g;
+        if (g.rows.n_long > 0) {
+            const int64_t threads = (int64_t)g.rows.n_long << g.geom.log2g;
             attn_bwd_dst_combine_kernel<VEC, MODE><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("attn_bwd_dst_combine_kernel");
         }
     }
-    fill_plan(g, plan_t);
-    g.eid = plan_t->eid;
+    g.rows = plan_rows(plan_t);
+    g.partial = plan_t->ws;
     {
-        const int64_t nvirt = (int64_t)g.n_rows + g.n_chunks;
-        const int64_t blocks = (nvirt + rpw - 1) / rpw;
+        const unsigned blocks = row_grid(g.rows, g.geom, 1).x;
         if (blocks > 0) {
-            attn_bwd_src_kernel<VEC, 4, LPH, MODE, DROP><<<(unsigned)blocks, 64, 0, stream>>>(g);
+            attn_bwd_src_kernel<VEC, 4, LPH, MODE, DROP><<<blocks, 64, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("attn_bwd_src_kernel");
         }
-        if (g.n_long > 0) {
-            const int64_t threads = (int64_t)g.n_long << g.log2g;
+        if (g.rows.n_long > 0) {
+            const int64_t threads = (int64_t)g.rows.n_long << g.geom.log2g;
             attn_bwd_src_combine_kernel<VEC, MODE><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("attn_bwd_src_combine_kernel");
         }
@@ -556,12 +507,10 @@ static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, int m
     g.H = (int)H;
     g.C = (int)C;
     g.D = D;
-    g.log2g = log2g;
+    g.geom = RowGeom{log2g, 1, 0, 0};
     g.lph = lph_code(lph, log2g);
-    g.waves = 1;
     g.slope = negative_slope;
     g.scale = scale;
-    g.eid = nullptr;
     g.drop = make_drop(drop_p, drop_seed);
     if (drop_p > 0.0f) {       // (the dropout variants walk the head butterfly with the run-time lane count: one instantiation per width)
         if (vec == 4) return launch_attn_bwd<4, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, da, stream);

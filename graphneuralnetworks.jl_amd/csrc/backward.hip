@@ -16,7 +16,7 @@
 //     of two gathered rows (SDDMM): edge_dot_kernel;
 //   - the max / min adjoint, which compares the forward input with the forward output per feature: maxmin_grad_kernel
 //     on the transposed plan.
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
@@ -48,15 +48,11 @@ __global__ void __launch_bounds__(256) edge_dot_kernel(const float *a, const flo
 // chunk for split rows) and stays in registers, only b[col_p] is gathered per edge — half the traffic of the COO-order
 // kernel above (measured 12.0 -> 6.6 ms, LABNOTES.md §7).  Results are written back in ORIGINAL edge order through eid.
 struct EdgeDotRowsArgs {
-    const uint32_t *rowptr;
-    const int32_t *col, *eid;
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
+    PlanRows rows;
+    RowGeom geom;
     const float *a, *b;
     float *out;
-    int n_chunks, long_thresh;
-    uint32_t n_edges;
-    int D, n_rows, log2g, waves;
+    int D;
 };
 // U dot products' partial sums, one set per lane of a G-lane group -> lane l of the group gets the TOTAL of product (l mod U): a
 // transposing butterfly.  At step s a lane keeps the products whose index has bit s equal to ITS bit s and hands the others to lane ^ 2^s:
@@ -88,26 +84,12 @@ __global__ void __launch_bounds__(256) edge_dot_rows_kernel(const EdgeDotRowsArg
     constexpr int G = 1 << LOG2G;
     constexpr int U = G < 8 ? G : 8;               // products per batch: loads in flight per lane, and the transposed reduction's width
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> LOG2G;
-    const int gbase = lane - lig;
-    constexpr int rpw = 64 >> LOG2G;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
-    int row;
-    uint32_t beg, end;
-    if (v < a.n_chunks) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return;   // its chunks are separate virtual rows (outputs are per edge: no combine)
-    }
+    RowGeom geom = a.geom;
+    geom.log2g = LOG2G;                            // compile-time here: the decode's shifts and masks fold
+    VRow vr;
+    if (!decode_vrow(a.rows, geom, blockIdx.x, vr)) return;   // (split rows: outputs are per edge, so their chunks need no combine)
+    const int row = vr.row, lig = vr.lig, gbase = vr.gbase;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = lig * VEC;                      // one feature tile: G * VEC >= D (checked by the launcher)
     const bool active = f0 < a.D;
     float av[VEC];
@@ -119,8 +101,8 @@ __global__ void __launch_bounds__(256) edge_dot_rows_kernel(const EdgeDotRowsArg
         int c = 0;
         uint32_t e = 0;
         if (p < end) {
-            c = a.col[p];
-            e = (uint32_t)a.eid[p];
+            c = a.rows.col[p];
+            e = (uint32_t)a.rows.eid[p];
         }
         const int n = (int)min((uint32_t)G, end - base);
         float mine = 0.0f;                         // lane lig keeps the result of slot base + lig
@@ -146,59 +128,38 @@ __global__ void __launch_bounds__(256) edge_dot_rows_kernel(const EdgeDotRowsArg
             const float r = reduce_transposed<U, G>(d, lane);      // the total of product j + (lig mod U)
             if ((lig & ~(U - 1)) == j) mine = r;
         }
-        if (p < end && e < a.n_edges) a.out[e] = mine;   // plan-added self loops carry no weight: no output slot
+        if (p < end && e < a.rows.n_edges) a.out[e] = mine;   // plan-added self loops carry no weight: no output slot
     }
 }
 
 struct MaxMinGradArgs {
-    const uint32_t *rowptr;  // transposed plan: row j = source node, slots = the edges j -> i in original order
-    const int32_t *col;     // destination i of each slot
+    PlanRows rows;          // transposed plan: row j = source node, slots = the edges j -> i in original order, rows.col = destination i
+    RowGeom geom;
     const float *x;         // [n_src][D] forward input
     const float *y;         // [n_dst][D] forward output (max / min over incoming messages)
     const float *dy;        // [n_dst][D]
     float *dx;              // [n_src][D]
     float *partial;         // [n_chunks][D] (rows of the transposed plan longer than its threshold are split)
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    int n_chunks, long_thresh;
-    int D, n_rows, log2g, waves;
+    int D;
 };
 
 // Δx_j[d] = Σ_{slots p of row j} (x_j[d] == y_{col_p}[d]) ? Δ_{col_p}[d] : 0     (ties: every maximiser gets Δ, like NNlib)
 template <int VEC, int U>
 __global__ void __launch_bounds__(256) maxmin_grad_kernel(const MaxMinGradArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int gbase = lane - lig;
-    const int rpw = 64 >> a.log2g;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
-    const bool is_chunk = v < a.n_chunks;
-    int row;
-    uint32_t beg, end;
-    if (is_chunk) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return;   // split row: chunks are virtual rows, folded by csr_combine_kernel
-    }
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;   // (split rows: folded by csr_combine_kernel)
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
     float xv[VEC], acc[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) { xv[q] = 0.0f; acc[q] = 0.0f; }
     if (active) Vec<VEC>::load(a.x + (int64_t)row * a.D + f0, xv);
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float yv[U][VEC], dv[U][VEC];
@@ -266,28 +227,17 @@ int gnnmp_edge_dot_plan_f32(gnnmp_graph_t *plan, const float *a_dst, const float
     const int lanes = (int)((D + vec - 1) / vec);
     if (lanes > 64) return fail(GNNMP_EUNSUPPORTED, "edge_dot_plan: D = %lld needs more than one wave per row; use gnnmp_edge_dot_f32", (long long)D);
     EdgeDotRowsArgs a;
-    a.rowptr = plan->rowptr;
-    a.col = plan->col;
-    a.eid = plan->eid;
-    a.chunk_row = plan->chunk_row;
-    a.chunk_beg = plan->chunk_beg;
-    a.chunk_end = plan->chunk_end;
+    a.rows = plan_rows(plan);
     a.a = a_dst;
     a.b = b_src;
     a.out = out;
-    a.n_chunks = plan->n_chunks;
-    a.long_thresh = plan->long_thresh;
-    a.n_edges = (uint32_t)plan->n_edges;
     a.D = (int)D;
-    a.n_rows = (int)plan->n_dst;
-    a.log2g = 0;
-    while ((1 << a.log2g) < lanes) ++a.log2g;
-    a.waves = 4;
-    const int rows_per_block = (64 >> a.log2g) * a.waves;
-    const unsigned nb = (unsigned)(((int64_t)a.n_rows + a.n_chunks + rows_per_block - 1) / rows_per_block);
+    a.geom = RowGeom{0, 4, 0, 0};
+    while ((1 << a.geom.log2g) < lanes) ++a.geom.log2g;
+    const unsigned nb = (unsigned)row_blocks(a.rows, a.geom);
 #define EDR(V, LG) edge_dot_rows_kernel<V, LG><<<nb, 256, 0, stream>>>(a)
 #define EDR_LG(V)                                                                                                       \
-    switch (a.log2g) {                                                                                                  \
+    switch (a.geom.log2g) {                                                                                                \
         case 0: EDR(V, 0); break; case 1: EDR(V, 1); break; case 2: EDR(V, 2); break; case 3: EDR(V, 3); break;          \
         case 4: EDR(V, 4); break; case 5: EDR(V, 5); break; default: EDR(V, 6); break;                                   \
     }
@@ -314,30 +264,20 @@ int gnnmp_propagate_maxmin_grad_f32(gnnmp_graph_t *plan_t, const float *x, const
     }
     MaxMinGradArgs a;
     a.partial = plan_t->ws;
-    a.chunk_row = plan_t->chunk_row;
-    a.chunk_beg = plan_t->chunk_beg;
-    a.chunk_end = plan_t->chunk_end;
-    a.n_chunks = plan_t->n_chunks;
-    a.long_thresh = plan_t->long_thresh;
-    a.rowptr = plan_t->rowptr;
-    a.col = plan_t->col;
+    a.rows = plan_rows(plan_t);
     a.x = x;
     a.y = y;
     a.dy = dy;
     a.dx = dx;
     a.D = (int)D;
-    a.n_rows = (int)plan_t->n_dst;
     uintptr_t m = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy);
     int vec = pick_vec(D, x, dx);
     if (vec == 4 && (m & 15)) vec = 1;
     if (vec == 2 && (m & 7)) vec = 1;
-    a.log2g = pick_log2g((D + vec - 1) / vec);
-    a.waves = 4;
-    const int G = 1 << a.log2g;
-    const int rows_per_block = (64 / G) * a.waves;
+    a.geom = RowGeom{pick_log2g((D + vec - 1) / vec), 4, 0, 0};
+    const int G = 1 << a.geom.log2g;
     const int lanes_needed = (int)((D + vec - 1) / vec);
-    dim3 grid((unsigned)(((int64_t)a.n_rows + a.n_chunks + rows_per_block - 1) / rows_per_block),
-              (unsigned)((lanes_needed + G - 1) / G));
+    const dim3 grid = row_grid(a.rows, a.geom, (lanes_needed + G - 1) / G);
     switch (vec) {
         case 4: maxmin_grad_kernel<4, 4><<<grid, 256, 0, stream>>>(a); break;
         case 2: maxmin_grad_kernel<2, 4><<<grid, 256, 0, stream>>>(a); break;

@@ -343,8 +343,9 @@ struct gnnmp_graph {
     int32_t *col = nullptr;     // [n_total] 0-based source of each slot (n_src < 2^31)
     int32_t *eid = nullptr;     // [n_total] 0-based original edge position of each slot, to be read as UNSIGNED 32 bits
     // rows longer than long_thresh (sorted ascending) are cut into n_chunks balanced chunks of at most
-    // long_thresh slots; the row kernels process chunks like ordinary (virtual) rows into a partial buffer and a
-    // small combine kernel folds the partials of each long row in chunk order.
+    // long_thresh slots; the row kernels process chunks like ordinary (virtual) rows into a partial buffer (rowwalk.h), and the
+    // partials of each long row are folded in chunk order: inside the row kernel by the last chunk to arrive where the kernel has a
+    // FOLD instance (csr_reduce.h: long_geom; chunk_lrow / arrive / spart below), by a small combine kernel otherwise.
     int32_t *long_rows = nullptr;   // [n_long]
     int32_t *long_cptr = nullptr;   // [n_long + 1] chunk range of each long row
     int32_t *chunk_row = nullptr;   // [n_chunks]

@@ -3,15 +3,13 @@
 // 16-byte row loads in flight per lane group and folds them in ORIGINAL edge order (GNNlib/src/msgpass.jl:71-79,145-149;
 // NNlib's CPU scatter loop order).  See propagate.hip's header for the mapping.
 #pragma once
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
 struct ReduceArgs {
-    const uint32_t *rowptr;
-    const int32_t *row_order; // [n_rows] rows by decreasing length, or null (common.h: gnnmp_graph::row_order)
-    const int32_t *idx;      // per slot: source row of x to read (plan->col, or plan->eid for scatter)
-    const int32_t *eid;      // per slot: original edge position (weights lookup); unused unless w
+    PlanRows rows;           // rows.col: per slot, the source row of x to read (plan->col, or plan->eid for scatter); rows.eid: weights lookup
+    RowGeom geom;
     const float *x;          // [n_src][D]
     const float *w;          // [n_edges] original order, nullable
     const float *emat;       // [n_edges][D] original order: per-edge, per-feature factor (e_mul_xj with a matrix e)
@@ -34,25 +32,12 @@ struct ReduceArgs {
                              //   Δx = Δz W_root + Aᵀ(Δz W_agg) (conv.jl:102-108), added where the row is finished instead of in a pass of its own
     const float *mask_y;     // [n_dst][D] or null: out = mask_y[row] > 0 ? out : 0 — relu' of the layer below (its stored output), ditto
     float *partial;          // [n_chunks][D]
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    const int32_t *long_rows, *long_cptr;
-    int n_chunks;
-    int n_long;
     int D;
-    int n_rows;
     int n_src;               // rows of x (XCD-remap heuristic)
-    uint32_t n_edges;        // weights exist for eid < n_edges; others are 1 (edge positions are unsigned 32-bit)
-    int log2g;
     int mean;
-    int long_thresh;
-    int cpx;                 // logical blocks per XCD (grid.x = nbc + 8*cpx) ; 0 = no remap
-    int nbc;                 // leading blocks (chunk virtual rows) that are not remapped
-    int waves;               // waves per block
     int compact_long;        // csr_combine_kernel writes long row r to out[r] (a compact [n_long][D] buffer), not out[row]
-    // fold-in-kernel (FOLD instances of csr_rows_kernel, see long_geom below): chunk v belongs to long row chunk_lrow[v]; arrival
+    // fold-in-kernel (FOLD instances of csr_rows_kernel, see long_geom below): chunk v belongs to long row rows.chunk_lrow[v]; arrival
     // counters per slice of the row's chunks and per row — the LAST one to arrive folds, and resets the counter for the next launch
-    const int32_t *chunk_lrow;
     uint32_t *arrive;        // [n_long][tiles][256 / G + 1]: per slice, then the row's own
     float *spart;            // [n_long][256 / G][D] slice partials
 };
@@ -118,22 +103,19 @@ __device__ __forceinline__ void reduce_range(const ReduceArgs &a, uint32_t beg, 
         Vec<VEC>::load(a.gate_i + (int64_t)row * 2 * a.D + a.D + f0, sub2);              // dense_s's share of x_i
     }
     const int64_t ldx = GATED ? 2 * (int64_t)a.D : (int64_t)a.D;
-    // Slots are UNSIGNED 32-bit (a plan holds fewer than 2^32 - 65536 of them): the walk costs what it cost with int32 slots.
-    // (A 64-bit rowptr was tried first: 64-bit loop counters cost the VALU-sensitive attention kernel 7 % on the products shape,
-    // and with per-row base pointers instead the row kernels went from 78 to 90 VGPRs — 6 -> 5 waves per SIMD, arxiv shape +4 %.)
-    for (uint32_t base = beg; base < end; base += G) {
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h: PlanRows)
         const uint32_t p = base + lig;
         uint32_t c = 0, ev = 0;     // row ids: sources (< 2^31) or, for _scatter, edge positions (< 2^32)
         float wv = 1.0f, sv = 1.0f;
         if (p < end) {
-            c = (uint32_t)a.idx[p];
-            if (EMAT) ev = (uint32_t)a.eid[p];
+            c = (uint32_t)a.rows.col[p];
+            if (EMAT) ev = (uint32_t)a.rows.eid[p];
             if (SCALED) {
                 if (a.w_slot) {
                     wv = a.w_slot[p];
                 } else if (a.w) {
-                    const uint32_t e = (uint32_t)a.eid[p];
-                    if (e < a.n_edges) wv = a.w[e];
+                    const uint32_t e = (uint32_t)a.rows.eid[p];
+                    if (e < a.rows.n_edges) wv = a.w[e];
                 }
                 if (a.ss_slot)
                     sv = a.ss_slot[p];
@@ -168,14 +150,14 @@ __device__ __forceinline__ void reduce_range(const ReduceArgs &a, uint32_t beg, 
                     // plan added carry no features and weigh 1
                     const uint32_t ej = ejs[EMAT ? u : 0];
                     if (GATED == 2) {   // the edge's share of both pre-activations (additive: absent = 0)
-                        if (active && (j + u < n) && ej < a.n_edges) {
+                        if (active && (j + u < n) && ej < a.rows.n_edges) {
                             Vec<VEC>::load(a.emat + (int64_t)ej * 2 * a.D + f0, em[EMAT ? u : 0]);
                             Vec<VEC>::load(a.emat + (int64_t)ej * 2 * a.D + a.D + f0, em2[(EMAT && GATED == 2) ? u : 0]);
                         } else {
 #pragma unroll
                             for (int q = 0; q < VEC; ++q) em[EMAT ? u : 0][q] = em2[(EMAT && GATED == 2) ? u : 0][q] = 0.0f;
                         }
-                    } else if (active && (j + u < n) && ej < a.n_edges) {
+                    } else if (active && (j + u < n) && ej < a.rows.n_edges) {
                         Vec<VEC>::load(a.emat + (int64_t)ej * a.D + f0, em[EMAT ? u : 0]);
                     } else {
 #pragma unroll

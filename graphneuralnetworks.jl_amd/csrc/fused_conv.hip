@@ -29,7 +29,7 @@ namespace gnnmp {
 
 struct FusedArgs {
     ReduceArgs r;             // the aggregation: rowptr / idx / x / scalings / D / n_rows / long_thresh / log2g (out unused)
-    const float *agg_long;    // [n_long][D] finalised aggregates of the split rows (r.long_rows sorted ascending)
+    const float *agg_long;    // [n_long][D] finalised aggregates of the split rows (r.rows.long_rows sorted ascending)
     float *agg_out;           // optional [n_rows][D]: also write the aggregate (parity tests of the pre-GEMM value)
     const float *xi;          // optional root features [n_rows][D1] (first segment of the contraction)
     int D1;
@@ -90,14 +90,14 @@ __device__ __forceinline__ void gather_rows8(const ReduceArgs &r, const float *_
             for (int q = 0; q < 4; ++q) acc[k][q] = op_identity<OP>();
         if (rr >= ROWS) return;
         const int row = row0 + rr;
-        if (row >= r.n_rows) {                           // past the last row: a zero row (never stored)
+        if (row >= r.rows.n_rows) {                           // past the last row: a zero row (never stored)
 #pragma unroll
             for (int k = 0; k < NT; ++k)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc[k][q] = 0.0f;
             is_long = true;                              // (= "finished as it stands")
-        } else if (re - rb > (uint32_t)r.long_thresh) {  // split row: reduced beforehand by the chunk pass, copied in
-            const float *src = agg_long + (int64_t)long_slot(r.long_rows, r.n_long, row) * D;
+        } else if (re - rb > (uint32_t)r.rows.long_thresh) {  // split row: reduced beforehand by the chunk pass, copied in
+            const float *src = agg_long + (int64_t)long_slot(r.rows.long_rows, r.rows.n_long, row) * D;
 #pragma unroll
             for (int k = 0; k < NT; ++k)
                 if (pact[k]) Vec<4>::load(src + 4 * gl + 32 * k, acc[k]);
@@ -113,14 +113,14 @@ __device__ __forceinline__ void gather_rows8(const ReduceArgs &r, const float *_
         const uint32_t left = pend - p;
         const int nb = (int)min(left, (uint32_t)GL);
         const bool have = (uint32_t)gl < left;
-        const uint32_t cidx = have ? (uint32_t)r.idx[p + gl] : 0u;
+        const uint32_t cidx = have ? (uint32_t)r.rows.col[p + gl] : 0u;
         float wv = 1.0f, sv = 1.0f;
         if (SCALED && have) {
             if (r.w_slot) {
                 wv = r.w_slot[p + gl];
             } else if (r.w) {
-                const uint32_t e = (uint32_t)r.eid[p + gl];
-                if (e < r.n_edges) wv = r.w[e];
+                const uint32_t e = (uint32_t)r.rows.eid[p + gl];
+                if (e < r.rows.n_edges) wv = r.w[e];
             }
             if (r.ss_slot) sv = r.ss_slot[p + gl];
             else if (r.ss) sv = r.ss[cidx];
@@ -173,7 +173,7 @@ __device__ __forceinline__ void gather_rows8(const ReduceArgs &r, const float *_
 #pragma unroll
             for (int k = 0; k < NT; ++k)
                 if (pact[k]) {
-                    if (agg_out && row < r.n_rows) Vec<4>::store(agg_out + (int64_t)row * D + 4 * gl + 32 * k, acc[k]);
+                    if (agg_out && row < r.rows.n_rows) Vec<4>::store(agg_out + (int64_t)row * D + 4 * gl + 32 * k, acc[k]);
                     *reinterpret_cast<float4 *>(tile + cur * stride + 4 * gl + 32 * k) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
                 }
         }
@@ -221,13 +221,13 @@ __global__ void __launch_bounds__(1024) fused_conv_kernel(const FusedArgs a) {
     const int lane = tid & 63, wave = tid >> 6;
     float *tile = tiles + (size_t)wave * 16 * a.stride;
     // gather-phase lane roles (csr_rows_kernel's): group of G lanes per row, lane lig owns features f0 .. f0 + 3
-    const int G = 1 << r.log2g;
-    const int lig = lane & (G - 1), grp = lane >> r.log2g, gbase = lane - lig, rpw = 64 >> r.log2g;
+    const int G = 1 << r.geom.log2g;
+    const int lig = lane & (G - 1), grp = lane >> r.geom.log2g, gbase = lane - lig, rpw = 64 >> r.geom.log2g;
     const int f0 = lig * VEC;
     const bool active = f0 < D;
     // MFMA-phase lane roles: node n of the tile, k-slot q
     const int n = lane & 15, q = lane >> 4;
-    const int ntiles = (r.n_rows + 15) >> 4;
+    const int ntiles = (r.rows.n_rows + 15) >> 4;
     const bool has_bias = a.bias != nullptr;
 
     // Tile hand-out: the first 7/8 of the tiles are dealt statically (wave w takes w, w + W, w + 2 W, ...: no traffic), the last
@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(1024) fused_conv_kernel(const FusedArgs a) {
         const int row0 = t * 16;
         // the tile's 17 row pointers in one coalesced load (lane l holds rowptr[row0 + l]); each row then takes its bounds from
         // two lanes instead of starting with a dependent load of its own (not with a row order: those rows are not adjacent)
-        const uint32_t rp = (!r.row_order && lane <= 16) ? r.rowptr[min(row0 + lane, r.n_rows)] : 0u;
+        const uint32_t rp = (!r.rows.row_order && lane <= 16) ? r.rows.rowptr[min(row0 + lane, r.rows.n_rows)] : 0u;
         // ---- 1. the 16 rows of the tile, rpw at a time ----
         for (int rr0 = 0; rr0 < 16; rr0 += rpw) {
             const int rr = rr0 + grp;
@@ -259,14 +259,14 @@ __global__ void __launch_bounds__(1024) fused_conv_kernel(const FusedArgs a) {
             const uint32_t rb = (uint32_t)__shfl((int)rp, min(rr, 16), 64), re = (uint32_t)__shfl((int)rp, min(rr + 1, 16), 64);
             if (rr >= 16) continue;
             int row = row0 + rr;
-            if (r.row_order && row < r.n_rows) row = r.row_order[row];
+            if (r.rows.row_order && row < r.rows.n_rows) row = r.rows.row_order[row];
             float acc[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] = op_identity<OP>();
-            if (row < r.n_rows) {
-                const uint32_t beg = r.row_order ? r.rowptr[row] : rb, end = r.row_order ? r.rowptr[row + 1] : re;
-                if (end - beg > r.long_thresh) {
-                    if (active) Vec<VEC>::load(a.agg_long + (int64_t)long_slot(r.long_rows, r.n_long, row) * D + f0, acc);
+            if (row < r.rows.n_rows) {
+                const uint32_t beg = r.rows.row_order ? r.rows.rowptr[row] : rb, end = r.rows.row_order ? r.rows.rowptr[row + 1] : re;
+                if (end - beg > r.rows.long_thresh) {
+                    if (active) Vec<VEC>::load(a.agg_long + (int64_t)long_slot(r.rows.long_rows, r.rows.n_long, row) * D + f0, acc);
                 } else {
                     reduce_range<VEC, OP, SCALED, U>(r, beg, end, lig, gbase, G, f0, active, acc, row);
                     finalize_row<VEC, OP>(r, row, end - beg, acc);
@@ -285,9 +285,9 @@ __global__ void __launch_bounds__(1024) fused_conv_kernel(const FusedArgs a) {
         f32x4 acc2[NCB];
 #pragma unroll
         for (int c = 0; c < NCB; ++c) acc2[c] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const bool row_ok = row0 + n < r.n_rows;
-        int row = min(row0 + n, r.n_rows - 1);
-        if (r.row_order) row = r.row_order[row];
+        const bool row_ok = row0 + n < r.rows.n_rows;
+        int row = min(row0 + n, r.rows.n_rows - 1);
+        if (r.rows.row_order) row = r.rows.row_order[row];
         if (a.xi) {
             const float *xr = a.xi + (int64_t)row * a.D1;
             t16_segment_rt<NCB>(acc2, img, 0, a.D1 >> 2, n, q, [&](int kcol) { return *reinterpret_cast<const float4 *>(xr + kcol); });
@@ -322,7 +322,7 @@ static int launch_fused(FusedArgs &a, size_t img_bytes, hipStream_t stream) {
     if (kw >= 1 && kw <= waves) waves = kw;
     a.waves = waves;
     GNNMP_LDS_OPTIN("fused_conv_kernel", &fused_conv_kernel<NCB, KQA, OP, SCALED>);
-    const int ntiles = (a.r.n_rows + 15) / 16;
+    const int ntiles = (a.r.rows.n_rows + 15) / 16;
     const int gx = std::min(device_cus(), (ntiles + waves - 1) / waves);
     // the ticket starts every launch at zero: an 8-byte memset node on the same stream (a kernel that re-armed it itself would
     // leave it dirty after a failed launch and the next one would silently skip tiles)
@@ -461,7 +461,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
     const int lane = tid & 63, wave = tid >> 6;
     float *tile = tiles + wave * FC2_ROWS * K1;
     const int n = lane & 31, h = lane >> 5;
-    const int ntiles = (r.n_rows + FC2_ROWS - 1) / FC2_ROWS;
+    const int ntiles = (r.rows.n_rows + FC2_ROWS - 1) / FC2_ROWS;
 
     const int total_waves = (int)gridDim.x * FC2_WAVES;
     const int wave_global = (int)blockIdx.x * FC2_WAVES + wave;
@@ -479,7 +479,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
         }
         if (t >= ntiles) break;
         const int row0 = t * FC2_ROWS;
-        const uint32_t rp = lane <= FC2_ROWS ? r.rowptr[min(row0 + lane, r.n_rows)] : 0u;
+        const uint32_t rp = lane <= FC2_ROWS ? r.rows.rowptr[min(row0 + lane, r.rows.n_rows)] : 0u;
         // ---- 1. the 32 rows of the tile: eight lane groups of 8 lanes, each pulling the tile's next row when done (gather_rows8) ----
         if (!(a.dbg & 2)) gather_rows8<K1, FC2_ROWS, OP, SCALED>(r, a.agg_long, a.agg_out, row0, rp, tile, K1, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -487,7 +487,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
         // ---- 2. [x_i | m_i] * W^T, 128 columns at a time ----
-        const int rowc = min(row0 + n, r.n_rows - 1);
+        const int rowc = min(row0 + n, r.rows.n_rows - 1);
         const float *xr = a.xi + (int64_t)rowc * K0;
         const float *tr = tile + n * K1;
         // piece p of k-block kb (p = 0, 1: positions 16 kb + 4 h + 8 p .. + 3 of the concatenated row): from x_i or from the tile
@@ -499,7 +499,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
             const int c = min(max(16 * kb + 4 * h + 8 * p - K0, 0), K1 - 4);
             return *reinterpret_cast<const float4 *>(tr + c);
         };
-        const bool full_tile = row0 + FC2_ROWS <= r.n_rows;
+        const bool full_tile = row0 + FC2_ROWS <= r.rows.n_rows;
 #pragma unroll 1
         for (int half = 0; half < ((a.dbg & 1) ? 0 : a.NH); ++half) {
             f32x16 acc2[4];
@@ -558,7 +558,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
             }
             const int col0 = 128 * half;
             if (split_any_nan<4>(acc2)) {
-                fused_cat_exact(a.w, a.xi, tile, K0, K1, col0, row0, r.n_rows, a.bias, a.act, a.out, a.Dout, lane);
+                fused_cat_exact(a.w, a.xi, tile, K0, K1, col0, row0, r.rows.n_rows, a.bias, a.act, a.out, a.Dout, lane);
                 continue;
             }
 #pragma unroll
@@ -571,7 +571,7 @@ __global__ void __launch_bounds__(64 * NW) fused_cat_kernel(const FusedCatArgs a
                     const int nu = 8 * (q >> 2) + (q & 3);                         // wave-uniform part of the node number
                     float v = acc2[cb][q] + bv;
                     if (a.act == GNNMP_ACT_RELU) v = fmaxf(v, 0.0f);      // (finite here: NaN tiles took the exact path)
-                    if ((full_tile || row0 + nu + 4 * h < r.n_rows) && !(a.dbg & 4)) op[(int64_t)nu * a.Dout] = v;
+                    if ((full_tile || row0 + nu + 4 * h < r.rows.n_rows) && !(a.dbg & 4)) op[(int64_t)nu * a.Dout] = v;
                 }
             }
         }
@@ -591,7 +591,7 @@ static int launch_fused_cat_v(FusedCatArgs &a, u32x4 *wimg, hipStream_t stream) 
     GNNMP_LAUNCH_CHECK("fused_cat_wimg_kernel");
     a.wimg = wimg;
     GNNMP_LDS_OPTIN("fused_cat_kernel", &fused_cat_kernel<K0, K1, OP, SCALED, NW, RD, U>);
-    const int ntiles = (a.r.n_rows + FC2_ROWS - 1) / FC2_ROWS;
+    const int ntiles = (a.r.rows.n_rows + FC2_ROWS - 1) / FC2_ROWS;
     const int gx = std::min(device_cus(), (ntiles + FC2_WAVES - 1) / FC2_WAVES);
     GNNMP_HIP(hipMemsetAsync(a.ticket, 0, 2 * sizeof(uint32_t), stream));
     fused_cat_kernel<K0, K1, OP, SCALED, NW, RD, U><<<gx, 64 * FC2_WAVES, lds, stream>>>(a);
@@ -667,11 +667,10 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
         }
         FusedCatArgs a = {};
         ReduceArgs &r = a.r;
-        r.rowptr = p->rowptr; r.idx = p->col; r.eid = p->eid; r.x = xj; r.w = w; r.ss = scale_src; r.w_slot = w_slot; r.ss_slot = ss_slot;
-        r.sd = scale_dst; r.long_rows = p->long_rows; r.n_long = p->n_long; r.D = (int)D; r.n_rows = (int)p->n_dst; r.n_src = (int)p->n_src;
-        r.n_edges = (uint32_t)p->n_edges; r.mean = (aggr == GNNMP_MEAN); r.long_thresh = p->long_thresh;
-        r.log2g = pick_log2g((D + 3) / 4);
-        if (r.log2g != 5) return fail(GNNMP_EUNSUPPORTED, "fused_conv: lane-group width forced by a knob");
+        r.rows = plan_rows(p); r.x = xj; r.w = w; r.ss = scale_src; r.w_slot = w_slot; r.ss_slot = ss_slot;
+        r.sd = scale_dst; r.D = (int)D; r.n_src = (int)p->n_src; r.mean = (aggr == GNNMP_MEAN);
+        r.geom.log2g = pick_log2g((D + 3) / 4);
+        if (r.geom.log2g != 5) return fail(GNNMP_EUNSUPPORTED, "fused_conv: lane-group width forced by a knob");
         a.agg_long = agg_long; a.agg_out = agg_out; a.xi = xi;
         a.w.W[0] = W_root; a.w.W[1] = W_agg; a.w.K[0] = (int)D1; a.w.K[1] = (int)D;
         a.w.sj[0] = ldw_root; a.w.sk[0] = 1; a.w.sj[1] = ldw_agg; a.w.sk[1] = 1;
@@ -709,29 +708,22 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
     }
     FusedArgs a = {};
     ReduceArgs &r = a.r;
-    r.rowptr = p->rowptr;
-    r.idx = p->col;
-    r.eid = p->eid;
+    r.rows = plan_rows(p);
     r.x = xj;
     r.w = w;
     r.ss = scale_src;
     r.w_slot = w_slot;
     r.ss_slot = ss_slot;
     r.sd = scale_dst;
-    r.long_rows = p->long_rows;
-    r.n_long = p->n_long;
     r.D = (int)D;
-    r.n_rows = (int)p->n_dst;
     r.n_src = (int)p->n_src;
-    r.n_edges = (uint32_t)p->n_edges;
     r.mean = (aggr == GNNMP_MEAN);
-    r.long_thresh = p->long_thresh;
-    r.log2g = pick_log2g((D + 3) / 4);
+    r.geom.log2g = pick_log2g((D + 3) / 4);
     // >= 2 rows per wave: the rows of a wave should be equally long (only when output rows are whole 128-byte lines, see
     // run_reduce in propagate.hip: measured 4.98 -> 6.02 ms with 400-byte rows)
-    if (use_row_order(p->n_src, D) && r.log2g <= 5 && (Dout & 31) == 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0) {
+    if (use_row_order(p->n_src, D) && r.geom.log2g <= 5 && (Dout & 31) == 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0) {
         if (int rc = ensure_row_order(p, stream)) return rc;
-        r.row_order = p->row_order;
+        r.rows.row_order = p->row_order;
     }
     a.agg_long = agg_long;
     a.agg_out = agg_out;

@@ -17,17 +17,12 @@
 // Long rows are chunked into virtual rows exactly like the forward kernels; partials are folded in chunk order.
 #include <algorithm>
 
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
 struct GatBwdArgs {
-    const uint32_t *rowptr;
-    const int32_t *col;
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    const int32_t *long_rows, *long_cptr;
-    int n_chunks, n_long, n_rows, long_thresh;
+    PlanRows rows;        // of the plan the running pass walks (rows.eid: DROP's slot -> original edge position)
     const float *Wx_src;  // [n_src][D]
     const float *Wx_dst;  // [n_dst][D]
     const float *a;       // [H][2C]
@@ -39,9 +34,9 @@ struct GatBwdArgs {
     float *dWx;           // [n_src][D]
     float *partial;
     int fold_dst;         // add a_d * dsd_j into dWx_j (non-bipartite: Wx_dst is Wx_src)
-    int H, C, D, log2g, lph, waves;
+    int H, C, D, lph;
+    RowGeom geom;
     float slope;
-    const int32_t *eid;   // DROP: plan slot -> original edge position (of the plan the running pass walks)
     DropArgs drop;
     // gnnmp_gat_conv_grad2_f32: what the training forward saved (gnnmp_gat_conv_train_f32) — the destination side then needs no edge pass
     const float *outk;    // [n_dst][D] the forward's output act(o + bias) with act in {identity, relu}
@@ -52,39 +47,13 @@ struct GatBwdArgs {
 
 __device__ __forceinline__ float lrelu_b(float x, float slope) { return x > 0.0f ? x : x * slope; }
 
-// decode the virtual row of this lane group; false = nothing to do
-__device__ __forceinline__ bool virtual_row(const GatBwdArgs &a, int &v, bool &is_chunk, int &row, uint32_t &beg, uint32_t &end,
-                                            int &lig, int &gbase, int &G) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    G = 1 << a.log2g;
-    lig = lane & (G - 1);
-    gbase = lane - lig;
-    const int grp = lane >> a.log2g;
-    const int rpw = 64 >> a.log2g;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return false;
-    v = (int)v64;
-    is_chunk = v < a.n_chunks;
-    if (is_chunk) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return false;
-    }
-    return true;
-}
-
 template <int VEC, int U, int LPH, bool DROP>
 __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
-    int v, row, lig, gbase, G;
-    uint32_t beg, end;
-    bool is_chunk;
-    if (!virtual_row(a, v, is_chunk, row, beg, end, lig, gbase, G)) return;
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     const int fc = active ? f0 : 0;   // idle lanes (D/VEC not a power of two) shadow lane 0 with zero coefficients
@@ -113,10 +82,10 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
     // branch-free body: the U loads, the 2U dot products, their butterflies and the U exponentials are independent
     // chains the scheduler interleaves; slots past the end of the row re-read the last edge and get α = 0
     float S1 = 0.0f, S2 = 0.0f, S3 = 0.0f;
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.eid[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
+        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float w[U][VEC];
@@ -187,12 +156,12 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
 template <int VEC, int LPH>
 __global__ void __launch_bounds__(256) gat_bwd_node_kernel(const GatBwdArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int rpw = 64 >> a.log2g;
+    const int grp = lane >> a.geom.log2g;
+    const int rpw = 64 >> a.geom.log2g;
     const int64_t r64 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * rpw + grp;
-    if (r64 >= a.n_rows) return;
+    if (r64 >= a.rows.n_rows) return;
     const int row = (int)r64;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
@@ -219,7 +188,7 @@ __global__ void __launch_bounds__(256) gat_bwd_node_kernel(const GatBwdArgs a) {
     if (!active || (f0 % a.C) != 0) return;
     const float m = a.stats[((int64_t)row * a.H + h) * 2];
     const float den = a.stats[((int64_t)row * a.H + h) * 2 + 1];
-    const bool any = a.rowptr[row + 1] > a.rowptr[row];
+    const bool any = a.rows.rowptr[row + 1] > a.rows.rowptr[row];
     float *ln = a.line + ((int64_t)row * a.H + h) * 4;
     ln[0] = sd;
     ln[1] = m;
@@ -230,10 +199,10 @@ __global__ void __launch_bounds__(256) gat_bwd_node_kernel(const GatBwdArgs a) {
 
 __global__ void __launch_bounds__(256) gat_bwd_dst_combine_kernel(const GatBwdArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)a.n_long * a.H) return;
+    if (i >= (int64_t)a.rows.n_long * a.H) return;
     const int r = (int)(i / a.H), h = (int)(i - (int64_t)r * a.H);
-    const int row = a.long_rows[r];
-    const int c0 = a.long_cptr[r], c1 = a.long_cptr[r + 1];
+    const int row = a.rows.long_rows[r];
+    const int c0 = a.rows.long_cptr[r], c1 = a.rows.long_cptr[r + 1];
     float S1 = 0.0f, S2 = 0.0f, S3 = 0.0f;
     for (int c = c0; c < c1; ++c) {
         const float *pc = a.partial + ((int64_t)c * a.H + h) * 4;
@@ -265,10 +234,11 @@ __device__ __forceinline__ void gat_bwd_src_store(const GatBwdArgs &a, int row, 
 
 template <int VEC, int U, int LPH, bool DROP>
 __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
-    int v, row, lig, gbase, G;
-    uint32_t beg, end;
-    bool is_chunk;
-    if (!virtual_row(a, v, is_chunk, row, beg, end, lig, gbase, G)) return;
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     const int fc = active ? f0 : 0;
@@ -293,10 +263,10 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
     float acc[VEC], dss = 0.0f;
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.eid[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
+        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float dv[U][VEC];
@@ -348,15 +318,15 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
 
 template <int VEC>
 __global__ void __launch_bounds__(256) gat_bwd_src_combine_kernel(const GatBwdArgs a) {
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = threadIdx.x & (G - 1);
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.log2g;
-    if (r >= a.n_long) return;
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.geom.log2g;
+    if (r >= a.rows.n_long) return;
     const int f0 = lig * VEC;
     if (f0 >= a.D) return;
     const int h = f0 / a.C;
-    const int row = a.long_rows[r];
-    const int c0 = a.long_cptr[r], c1 = a.long_cptr[r + 1];
+    const int row = a.rows.long_rows[r];
+    const int c0 = a.rows.long_cptr[r], c1 = a.rows.long_cptr[r + 1];
     const int LN = a.D / VEC;
     const int64_t S = a.D + LN;
     constexpr int CB = 8;
@@ -446,72 +416,54 @@ __global__ void __launch_bounds__(256) gat_wcolsum_fold_kernel(const float *part
     }
 }
 
-static void fill_plan(GatBwdArgs &g, const gnnmp_graph *p) {
-    g.rowptr = p->rowptr;
-    g.col = p->col;
-    g.chunk_row = p->chunk_row;
-    g.chunk_beg = p->chunk_beg;
-    g.chunk_end = p->chunk_end;
-    g.long_rows = p->long_rows;
-    g.long_cptr = p->long_cptr;
-    g.n_chunks = p->n_chunks;
-    g.n_long = p->n_long;
-    g.n_rows = (int)p->n_dst;
-    g.long_thresh = p->long_thresh;
-    g.partial = p->ws;
-}
-
 template <int VEC, int LPH, bool DROP>
 static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *dWx_dst, float *da,
                           hipStream_t stream) {
-    const int G = 1 << g.log2g;
-    const int rpw = 64 / G;
+    const int rpw = 64 >> g.geom.log2g;
     int waves = knob(KNOB_BLOCK_WAVES);
     if (waves < 1 || waves > 4) waves = 1;
-    g.waves = waves;
+    g.geom.waves = waves;
     const int unroll = knob(KNOB_UNROLL);
     // ---- pass 1: destinations (forward plan)
-    fill_plan(g, plan);
-    g.eid = plan->eid;
+    g.rows = plan_rows(plan);
+    g.partial = plan->ws;
     if (g.oplus) {        // the training forward saved o+ / P: a node kernel, no edge pass
-        const int64_t blocks = ((int64_t)g.n_rows + (int64_t)rpw * 4 - 1) / ((int64_t)rpw * 4);
+        const int64_t blocks = ((int64_t)g.rows.n_rows + (int64_t)rpw * 4 - 1) / ((int64_t)rpw * 4);
         if (blocks > 0) {
             gat_bwd_node_kernel<VEC, LPH><<<(unsigned)blocks, 256, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_node_kernel");
         }
     } else {
-        const int64_t nvirt = (int64_t)g.n_rows + g.n_chunks;
-        const int64_t blocks = (nvirt + (int64_t)rpw * waves - 1) / ((int64_t)rpw * waves);
+        const unsigned blocks = row_grid(g.rows, g.geom, 1).x;
         if (blocks > 0) {
             if (unroll == 4)
-                gat_bwd_dst_kernel<VEC, 4, LPH, DROP><<<(unsigned)blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_dst_kernel<VEC, 4, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
             else
-                gat_bwd_dst_kernel<VEC, 8, LPH, DROP><<<(unsigned)blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_dst_kernel<VEC, 8, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_dst_kernel");
         }
-        if (g.n_long > 0) {
-            const int64_t threads = (int64_t)g.n_long * g.H;
+        if (g.rows.n_long > 0) {
+            const int64_t threads = (int64_t)g.rows.n_long * g.H;
             gat_bwd_dst_combine_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_dst_combine_kernel");
         }
     }
     // ---- pass 2: sources (transposed plan)
-    fill_plan(g, plan_t);
-    g.eid = plan_t->eid;
+    g.rows = plan_rows(plan_t);
+    g.partial = plan_t->ws;
     {
-        const int64_t nvirt = (int64_t)g.n_rows + g.n_chunks;
-        const int64_t blocks = (nvirt + (int64_t)rpw * waves - 1) / ((int64_t)rpw * waves);
+        const unsigned blocks = row_grid(g.rows, g.geom, 1).x;
         if (blocks > 0) {
             // 20 bytes of operands per lane and edge here (Δ slice + the statistics line): 4 in flight keeps 6 waves/SIMD
             // (7.0 ms on the products shape against 8.4 ms with 8 in flight at 4 waves/SIMD)
             if (unroll == 8)
-                gat_bwd_src_kernel<VEC, 8, LPH, DROP><<<(unsigned)blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_src_kernel<VEC, 8, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
             else
-                gat_bwd_src_kernel<VEC, 4, LPH, DROP><<<(unsigned)blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_src_kernel<VEC, 4, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_src_kernel");
         }
-        if (g.n_long > 0) {
-            const int64_t threads = (int64_t)g.n_long << g.log2g;
+        if (g.rows.n_long > 0) {
+            const int64_t threads = (int64_t)g.rows.n_long << g.geom.log2g;
             gat_bwd_src_combine_kernel<VEC><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_src_combine_kernel");
         }
@@ -603,12 +555,10 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const 
     g.H = (int)H;
     g.C = (int)C;
     g.D = D;
-    g.log2g = 0;
-    while ((1 << g.log2g) < lanes) ++g.log2g;
-    g.lph = lph_code(lph, g.log2g);   // odd head widths sum their lanes one by one (common.h group_sum<0>)
-    g.waves = 1;
+    g.geom = RowGeom{0, 1, 0, 0};
+    while ((1 << g.geom.log2g) < lanes) ++g.geom.log2g;
+    g.lph = lph_code(lph, g.geom.log2g);   // odd head widths sum their lanes one by one (common.h group_sum<0>)
     g.slope = negative_slope;
-    g.eid = nullptr;
     g.drop = make_drop(drop_p, drop_seed);
     g.outk = outk;
     g.bias = bias;

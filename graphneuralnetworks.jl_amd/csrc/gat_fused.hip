@@ -24,47 +24,34 @@
 //
 // Long rows: same chunking as propagate.hip — a chunk is a virtual row that emits (acc, m, den) partials; the combine
 // kernel merges them with the usual log-sum-exp rescale.
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
 struct GatFusedArgs {
-    const uint32_t *rowptr;
-    const int32_t *row_order;   // [n_rows] rows by decreasing length, or null: virtual row v -> destination (see common.h)
-    const int32_t *col;
+    PlanRows rows;        // rows.eid: plan slot -> original edge position (escore lookup, dropout)
+    RowGeom geom;
     const float *Wx_src;  // K [n_src][D]
     const float *Wx_val;  // V [n_src][D] (== Wx_src unless MODE = DOT)
     const float *Wx_dst;  // Q [n_dst][D]
     const float *a;       // GAT [H][2C], GATV2 [H][C], else unused
     const float *escore;  // GAT with edge features: [n_edges][H] = a_e . We_k, original edge order; else null
-    const int32_t *eid;   // plan slot -> original edge position (escore lookup)
     const float *bias;    // [D] or null
     float *out;           // [n_dst][D]
     float *partial;       // [n_chunks][D + 2*D/VEC]
     float *stats;         // [n_dst][H][2] = (running max m, denominator) of every destination, or null (saved for the adjoint)
     float *oplus;         // ATTN_GAT_PLUS: [n_dst][D]  o+_i = sum over the neighbours with a POSITIVE pre-activation logit of α_ij Wx_j
     float *pplus;         // ATTN_GAT_PLUS: [n_dst][H]  P_i = sum of those α_ij            (gat_backward.hip: the pullback's dsd_i from them)
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    const int32_t *long_rows, *long_cptr;
-    int n_chunks, n_long;
     int H, C, D;
-    int n_rows;
     int n_src;
-    int log2g;
     int off24;            // 1: row offsets fit the 24-bit multiply (see gat_online_range)
     int lph;              // lanes per head = C / VEC (power of two; the whole group when H = 1)
     int act;
     float slope;
     float scale;          // DOT: divisor (sqrt(out)); COS: multiplier (β)
-    int long_thresh;
-    int cpx;
-    int nbc;              // leading blocks (chunk virtual rows) that are not remapped
-    int waves;
     DropArgs drop;        // ATTN_GAT_DROP / ATTN_GATV2_DROP only
-    // fold-in-kernel (FOLD instances of gat_fused_rows_kernel; csr_reduce.h's scheme): chunk v belongs to long row chunk_lrow[v];
+    // fold-in-kernel (FOLD instances of gat_fused_rows_kernel; csr_reduce.h's scheme): chunk v belongs to long row rows.chunk_lrow[v];
     // arrive[r] counts the chunks of long row r whose partial is stored — the last one to arrive merges the row (gat_fold_row)
-    const int32_t *chunk_lrow;
     uint32_t *arrive;     // [n_long][256 / G + 1]
     float *spart;         // [n_long][256 / G][partial row]
 };
@@ -214,12 +201,12 @@ template <int VEC, int U, int LPH, int MODE, bool OFF24>
 __device__ __forceinline__ void gat_online_range(const GatFusedArgs &a, uint32_t beg, uint32_t end, int lig,
                                                  int gbase, int G, int fc, const LaneRow<VEC> &r,
                                                  float &m, float &den, float acc[VEC], float &den2, float acc2[VEC]) {
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (see csr_reduce.h: reduce_range)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.col[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
         // edge features (gat_conv with dense_e): the edge's share of the logit, a_e . We_k, precomputed per edge and head,
         // is fetched by original edge position (uniform branch: absent for the headline layer)
-        const int ev = (needs_eid(MODE) && p < end) ? a.eid[p] : 0;
+        const int ev = (needs_eid(MODE) && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         int j = 0;
         for (; j + U <= n; j += U) gat_batch<VEC, U, LPH, MODE, OFF24>(a, c, ev, gbase, j, n, fc, r, m, den, acc, den2, acc2);
@@ -385,33 +372,13 @@ __device__ __forceinline__ bool gat_chunk_arrive(uint32_t *counter, int n, int l
 
 template <int VEC, int U, int LPH, int MODE, bool FOLD = false>
 __global__ void __launch_bounds__(256) gat_fused_rows_kernel(const GatFusedArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int gbase = lane - lig;
-    const int rpw = 64 >> a.log2g;
-    const int chunk = a.cpx ? xcd_remap_after(blockIdx.x, a.nbc, a.cpx) : (int)blockIdx.x;
-    const int64_t v64 = ((int64_t)chunk * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
+    VRow vr;
+    if (!decode_vrow<VROW_REMAP | VROW_ORDER>(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
-    const bool is_chunk = v < a.n_chunks;
-    int row;
-    uint32_t beg, end;
-    if (is_chunk) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        if (a.row_order) row = a.row_order[row];
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return;
-    }
     // this lane's slice of the attention vector and of Q_i; idle lanes (D/VEC not a power of two) shadow lane 0 with zero
     // coefficients so that no load below needs a predicate
     const int fc = active ? f0 : 0;
@@ -480,9 +447,9 @@ __global__ void __launch_bounds__(256) gat_fused_rows_kernel(const GatFusedArgs 
             }
         }
         if (FOLD) {
-            const int lr = a.chunk_lrow[v];
-            const int NG = 256 >> a.log2g;
-            const int c0 = a.long_cptr[lr], c1 = a.long_cptr[lr + 1];
+            const int lr = a.rows.chunk_lrow[v];
+            const int NG = 256 >> a.geom.log2g;
+            const int c0 = a.rows.long_cptr[lr], c1 = a.rows.long_cptr[lr + 1];
             const int per = (c1 - c0 + NG - 1) / NG, ns = (c1 - c0 + per - 1) / per;
             const int k = (v - c0) / per;
             const int s0 = c0 + k * per, s1 = min(c1, s0 + per);
@@ -522,16 +489,16 @@ template <int VEC, bool PLUS>
 __global__ void __launch_bounds__(256) gat_fused_combine_kernel(const GatFusedArgs a) {
     constexpr int RS = PLUS ? 2 * VEC + 3 : VEC + 2;        // floats a thread parks in LDS: acc, M, den (, acc2, den2)
     __shared__ float red[256 * RS];
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = threadIdx.x & (G - 1);
-    const int grp = threadIdx.x >> a.log2g;
-    const int NG = 256 >> a.log2g;
+    const int grp = threadIdx.x >> a.geom.log2g;
+    const int NG = 256 >> a.geom.log2g;
     const int r = blockIdx.x;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     const int fc = active ? f0 : 0;
-    const int row = a.long_rows[r];
-    const int c0 = a.long_cptr[r], c1 = a.long_cptr[r + 1];
+    const int row = a.rows.long_rows[r];
+    const int c0 = a.rows.long_cptr[r], c1 = a.rows.long_cptr[r + 1];
     const int per = (c1 - c0 + NG - 1) / NG;
     const int s0 = min(c1, c0 + grp * per), s1 = min(c1, s0 + per);
     const int LN = a.D / VEC;
@@ -592,7 +559,7 @@ __global__ void __launch_bounds__(256) gat_fused_combine_kernel(const GatFusedAr
     float Mt = M;
     for (int k = 1; k < NG; ++k) {
         if (c0 + k * per >= c1) break;
-        Mt = fmaxf(Mt, red[((k << a.log2g) + lig) * RS + VEC]);
+        Mt = fmaxf(Mt, red[((k << a.geom.log2g) + lig) * RS + VEC]);
     }
     {
         const float sc = expf(M - Mt);
@@ -603,7 +570,7 @@ __global__ void __launch_bounds__(256) gat_fused_combine_kernel(const GatFusedAr
     }
     for (int k = 1; k < NG; ++k) {
         if (c0 + k * per >= c1) break;
-        const float *o = red + ((k << a.log2g) + lig) * RS;
+        const float *o = red + ((k << a.geom.log2g) + lig) * RS;
         const float sc = expf(o[VEC] - Mt);
         den = fmaf(o[VEC + 1], sc, den);
 #pragma unroll
@@ -641,24 +608,12 @@ static void launch_rows_lph(const GatFusedArgs &a, dim3 grid, int blk, hipStream
 
 template <int VEC, int MODE>
 static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
-    const int G = 1 << a.log2g;
-    const int rpw = 64 / G;
     int waves = knob(KNOB_BLOCK_WAVES);
     if (waves < 1 || waves > 4) waves = 1;   // auto: single-wave blocks (measured 5.21 vs 5.41 ms on products: finer
                                               // grained retirement for a kernel whose rows differ 100x in length)
-    a.waves = waves;
-    const int rows_per_block = rpw * waves;
-    const int64_t nvirt = (int64_t)a.n_rows + a.n_chunks;
-    const int64_t chunks = (nvirt + rows_per_block - 1) / rows_per_block;
-    if (chunks > 0) {
-        int64_t gx = chunks;
-        a.cpx = 0;
-        if (use_xcd_remap(a.n_src, a.D, chunks)) {
-            a.nbc = (int)std::min<int64_t>(chunks, (a.n_chunks + rows_per_block - 1) / rows_per_block);
-            a.cpx = (int)((chunks - a.nbc + 7) / 8);
-            gx = (int64_t)a.nbc + (int64_t)a.cpx * 8;
-        }
-        dim3 grid((unsigned)gx, 1);
+    a.geom.waves = waves;
+    const dim3 grid = row_grid(a.rows, a.geom, 1, use_xcd_remap(a.n_src, a.D, row_blocks(a.rows, a.geom)));
+    if (grid.x > 0) {
         const int U = knob(KNOB_UNROLL);
         const int blk = 64 * waves;
         if (MODE == GNNMP_ATTN_DOT) {
@@ -667,7 +622,7 @@ static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
             gat_fused_rows_kernel<VEC, 4, 0, MODE><<<grid, blk, 0, stream>>>(a);
         } else if (is_gat(MODE) && U == 2) {
             gat_fused_rows_kernel<VEC, 2, 0, MODE><<<grid, blk, 0, stream>>>(a);
-        } else if (MODE == GNNMP_ATTN_GAT && a.arrive && a.n_long > 0) {
+        } else if (MODE == GNNMP_ATTN_GAT && a.arrive && a.rows.n_long > 0) {
             // GATConv's forward merges its split rows inside the row kernel: no second launch.  (Not the training forward: with the o+ / P
             // accumulators the merge code took the kernel from 86 to 101 registers — 5 -> 4 waves a SIMD.)
             launch_rows_lph<VEC, 8, MODE, MODE == GNNMP_ATTN_GAT>(a, grid, blk, stream);
@@ -678,11 +633,11 @@ static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
         }
         GNNMP_LAUNCH_CHECK("gat_fused_rows_kernel");
     }
-    if (a.n_long > 0) {
+    if (a.rows.n_long > 0) {
         if (MODE == ATTN_GAT_PLUS)
-            gat_fused_combine_kernel<VEC, true><<<(unsigned)a.n_long, 256, 0, stream>>>(a);
+            gat_fused_combine_kernel<VEC, true><<<(unsigned)a.rows.n_long, 256, 0, stream>>>(a);
         else
-            gat_fused_combine_kernel<VEC, false><<<(unsigned)a.n_long, 256, 0, stream>>>(a);
+            gat_fused_combine_kernel<VEC, false><<<(unsigned)a.rows.n_long, 256, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("gat_fused_combine_kernel");
     }
     return GNNMP_OK;
@@ -756,47 +711,31 @@ static int attn_conv_impl(gnnmp_graph_t *plan, int mode, const float *Q, const f
     GatFusedArgs g;
     g.oplus = oplus;
     g.pplus = pplus;
-    g.rowptr = plan->rowptr;
-    g.row_order = nullptr;
+    g.rows = plan_rows(plan);
     if (use_row_order(plan->n_src, D) && lanes <= 32) {   // two or more rows per wave: pair rows of equal length
         if (int rc = ensure_row_order(plan, stream)) return rc;
-        g.row_order = plan->row_order;
+        g.rows.row_order = plan->row_order;
     }
-    g.col = plan->col;
     g.Wx_src = K;
     g.Wx_val = V;
     g.Wx_dst = Q;
     g.a = a;
     g.escore = escore;
-    g.eid = plan->eid;
     g.bias = bias;
     g.out = out;
     g.partial = plan->ws;
     g.stats = stats;
-    g.chunk_row = plan->chunk_row;
-    g.chunk_beg = plan->chunk_beg;
-    g.chunk_end = plan->chunk_end;
-    g.long_rows = plan->long_rows;
-    g.long_cptr = plan->long_cptr;
-    g.n_chunks = plan->n_chunks;
-    g.n_long = plan->n_long;
     g.H = (int)H;
     g.C = (int)C;
     g.D = D;
-    g.n_rows = (int)plan->n_dst;
     g.n_src = (int)plan->n_src;
-    g.log2g = log2g;
+    g.geom = RowGeom{log2g, 4, 0, 0};
     g.lph = lph_code(lph, log2g);   // odd head widths (C = 7 classes, ...) sum their lanes one by one
     g.act = act;
     g.slope = negative_slope;
     g.scale = scale;
-    g.long_thresh = plan->long_thresh;
-    g.cpx = 0;
-    g.nbc = 0;
-    g.waves = 4;
     g.off24 = plan->n_src < (1 << 24) && D < (1 << 24) && (int64_t)plan->n_src * D < (1ll << 32);
     g.drop = make_drop(drop_p, drop_seed);
-    g.chunk_lrow = plan->chunk_lrow;
     g.arrive = nullptr;
     g.spart = nullptr;
     if (plan->n_long > 0 && use_fold() && (mode == GNNMP_ATTN_GAT && !escore && drop_p == 0.0f && !plus)) {   // (plain GAT only)

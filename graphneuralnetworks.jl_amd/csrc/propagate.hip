@@ -19,39 +19,30 @@
 
 namespace gnnmp {
 
-// virtual rows: [0, n_chunks) are chunks of long rows (raw partials), [n_chunks, n_chunks + n_rows) ordinary rows.
+// one lane group per virtual row (rowwalk.h): a chunk of a long row leaves a raw partial, an ordinary row is finished here.
 // FOLD: no second kernel for the split rows — the last chunk of a long row to arrive folds the row's partials itself, in the order of
 // csr_combine_kernel (csr_reduce.h: chunk_arrive, fold_long_row).  One launch and one launch seam less per call: 5.6 us + the seam of a
 // 107 us arxiv-shaped propagate.
 template <int VEC, int OP, bool SCALED, int U, bool EMAT = false, bool EXPSUB = false, int GATED = 0, bool FOLD = false>
 __global__ void __launch_bounds__(256) csr_rows_kernel(const ReduceArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int gbase = lane - lig;
-    const int rpw = 64 >> a.log2g;
-    const int chunk = a.cpx ? xcd_remap_after(blockIdx.x, a.nbc, a.cpx) : (int)blockIdx.x;
-    const int64_t v64 = ((int64_t)chunk * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
+    VRow vr;   // (only the EXPSUB / GATED instances read a chunk's row)
+    if (!decode_vrow<VROW_REMAP | VROW_ORDER | ((EXPSUB || GATED) ? 0 : VROW_NO_CHUNK_ROW)>(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, lig = vr.lig, gbase = vr.gbase, G = vr.G;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
     float acc[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = op_identity<OP>();
-    if (v < a.n_chunks) {
-        reduce_range<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED>(a, a.chunk_beg[v], a.chunk_end[v], lig, gbase, G, f0, active, acc,
-                                                              (EXPSUB || GATED) ? a.chunk_row[v] : 0);
+    if (vr.is_chunk) {
+        reduce_range<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED>(a, vr.beg, vr.end, lig, gbase, G, f0, active, acc, vr.row);
         if (active) {
             if (FOLD) coh_store<VEC>(a.partial + (int64_t)v * a.D + f0, acc);      // read by another workgroup of this launch
             else Vec<VEC>::store(a.partial + (int64_t)v * a.D + f0, acc);
         }
         if (FOLD) {
-            const int r = a.chunk_lrow[v];
-            const LongGeom lg = long_geom(a.long_cptr, r, a.log2g);
-            const int NG = 256 >> a.log2g;
+            const int r = a.rows.chunk_lrow[v];
+            const LongGeom lg = long_geom(a.rows.long_cptr, r, a.geom.log2g);
+            const int NG = 256 >> a.geom.log2g;
             const int k = (v - lg.c0) / lg.per;
             const int s0 = lg.c0 + k * lg.per, s1 = min(lg.c1, s0 + lg.per);
             uint32_t *cnt = a.arrive + ((int64_t)r * gridDim.y + blockIdx.y) * (NG + 1);
@@ -61,48 +52,25 @@ __global__ void __launch_bounds__(256) csr_rows_kernel(const ReduceArgs a) {
             if (active) coh_store<VEC>(sp + (int64_t)k * a.D + f0, acc);
             if (!chunk_arrive(cnt + NG, lg.ns, lig, gbase)) return;
             fold_rows<VEC, OP>(sp, a.D, lg.ns, f0, active, acc, false);
-            const int lrow = a.long_rows[r];
-            finalize_store<VEC, OP>(a, lrow, a.rowptr[lrow + 1] - a.rowptr[lrow], f0, active, acc, a.compact_long ? r : -1);
+            const int lrow = a.rows.long_rows[r];
+            finalize_store<VEC, OP>(a, lrow, a.rows.rowptr[lrow + 1] - a.rows.rowptr[lrow], f0, active, acc, a.compact_long ? r : -1);
         }
         return;
     }
-    int row = v - a.n_chunks;
-    if (a.row_order) row = a.row_order[row];
-    const uint32_t beg = a.rowptr[row];
-    const uint32_t end = a.rowptr[row + 1];
-    if (end - beg > (uint32_t)a.long_thresh) return;  // split row: its chunks are virtual rows, folded by csr_combine_kernel
-    reduce_range<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED>(a, beg, end, lig, gbase, G, f0, active, acc, row);
-    finalize_store<VEC, OP>(a, row, end - beg, f0, active, acc);
+    reduce_range<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED>(a, vr.beg, vr.end, lig, gbase, G, f0, active, acc, vr.row);
+    finalize_store<VEC, OP>(a, vr.row, vr.end - vr.beg, f0, active, acc);
 }
 
 // softmax_edge_neighbors, last step (GNNlib/src/utils.jl:96): alpha[k] = exp(e[k] - max_[t_k]) / den[t_k] for every edge of
 // the (virtual) row, written back in ORIGINAL edge order.  idx = the plan's eid (rows of e / alpha).
 template <int VEC, int U>
 __global__ void __launch_bounds__(256) softmax_write_kernel(const ReduceArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int gbase = lane - lig;
-    const int rpw = 64 >> a.log2g;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
-    int row;
-    uint32_t beg, end;
-    if (v < a.n_chunks) {
-        row = a.chunk_row[v];
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return;
-    }
     float mx[VEC], den[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) mx[q] = den[q] = 1.0f;
@@ -115,9 +83,9 @@ __global__ void __launch_bounds__(256) softmax_write_kernel(const ReduceArgs a) 
         for (int q = 0; q < VEC; ++q) den[q] = den[q] + a.den_add;
     }
     float *outp = a.out;
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (csr_reduce.h)
+    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
-        const int c = p < end ? a.idx[p] : 0;
+        const int c = p < end ? a.rows.col[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float x[U][VEC];
@@ -145,15 +113,15 @@ __global__ void __launch_bounds__(256) softmax_write_kernel(const ReduceArgs a) 
 template <int VEC, int OP>
 __global__ void __launch_bounds__(256) csr_combine_kernel(const ReduceArgs a) {
     __shared__ float red[256 * VEC];
-    const int G = 1 << a.log2g;
+    const int G = 1 << a.geom.log2g;
     const int lig = threadIdx.x & (G - 1);
-    const int grp = threadIdx.x >> a.log2g;
-    const int NG = 256 >> a.log2g;
+    const int grp = threadIdx.x >> a.geom.log2g;
+    const int NG = 256 >> a.geom.log2g;
     const int r = blockIdx.x;
     const int f0 = ((int)blockIdx.y * G + lig) * VEC;
     const bool active = f0 < a.D;
-    const int row = a.long_rows[r];
-    const int c0 = a.long_cptr[r], c1 = a.long_cptr[r + 1];
+    const int row = a.rows.long_rows[r];
+    const int c0 = a.rows.long_cptr[r], c1 = a.rows.long_cptr[r + 1];
     const int per = (c1 - c0 + NG - 1) / NG;
     const int s0 = min(c1, c0 + grp * per), s1 = min(c1, s0 + per);
     float acc[VEC];
@@ -181,9 +149,9 @@ __global__ void __launch_bounds__(256) csr_combine_kernel(const ReduceArgs a) {
     for (int k = 1; k < NG; ++k) {
         if (c0 + k * per >= c1) break;               // empty slices hold the identity: nothing to fold
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) acc[q] = op_apply<OP>(acc[q], red[((k << a.log2g) + lig) * VEC + q]);
+        for (int q = 0; q < VEC; ++q) acc[q] = op_apply<OP>(acc[q], red[((k << a.geom.log2g) + lig) * VEC + q]);
     }
-    finalize_store<VEC, OP>(a, row, a.rowptr[row + 1] - a.rowptr[row], f0, active, acc, a.compact_long ? r : -1);
+    finalize_store<VEC, OP>(a, row, a.rows.rowptr[row + 1] - a.rows.rowptr[row], f0, active, acc, a.compact_long ? r : -1);
 }
 
 // nn_conv's propagate (GNNlib/src/layers/conv.jl:260-273): the message of edge k is W_k x_j with W_k = reshape(nn(e_k), out, in)
@@ -194,29 +162,13 @@ __global__ void __launch_bounds__(256) csr_combine_kernel(const ReduceArgs a) {
 // csr_combine_kernel like every other row kernel.
 template <int OP>
 __global__ void __launch_bounds__(256) nn_rows_kernel(const ReduceArgs a, const float *__restrict__ we, int Din) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1);
-    const int grp = lane >> a.log2g;
-    const int rpw = 64 >> a.log2g;
-    const int64_t v64 = ((int64_t)blockIdx.x * a.waves + wave) * rpw + grp;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
-    const int o = (int)blockIdx.y * G + lig;
+    VRow vr;
+    if (!decode_vrow<VROW_NO_CHUNK_ROW>(a.rows, a.geom, blockIdx.x, vr)) return;
+    const int v = vr.v, row = vr.row;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
+    const int o = (int)blockIdx.y * vr.G + vr.lig;
     const bool active = o < a.D;
-    int row = 0;
-    uint32_t beg, end;
-    const bool is_chunk = v < a.n_chunks;
-    if (is_chunk) {
-        beg = a.chunk_beg[v];
-        end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks;
-        beg = a.rowptr[row];
-        end = a.rowptr[row + 1];
-        if (end - beg > a.long_thresh) return;
-    }
     float acc = op_identity<OP>();
     const int oc = active ? o : 0;
     // EB edges at a time: their EB x 2 in-channel loads are independent (a row walks its edges alone — with one edge in flight
@@ -229,10 +181,10 @@ __global__ void __launch_bounds__(256) nn_rows_kernel(const ReduceArgs a, const 
 #pragma unroll
         for (int u = 0; u < EB; ++u) {
             const uint32_t p = min(p0 + u, end - 1);
-            const int cj = a.idx[p];
-            const uint32_t ej = (uint32_t)a.eid[p];
-            ok[u] = p0 + u < end && ej < a.n_edges;          // a self loop the plan added: no edge features, no message
-            wk[u] = we + (int64_t)(a.n_edges ? min(ej, a.n_edges - 1) : 0u) * a.D * Din + oc;
+            const int cj = a.rows.col[p];
+            const uint32_t ej = (uint32_t)a.rows.eid[p];
+            ok[u] = p0 + u < end && ej < a.rows.n_edges;          // a self loop the plan added: no edge features, no message
+            wk[u] = we + (int64_t)(a.rows.n_edges ? min(ej, a.rows.n_edges - 1) : 0u) * a.D * Din + oc;
             xr[u] = a.x + (int64_t)cj * Din;
         }
         float m[EB];
@@ -273,28 +225,17 @@ __global__ void __launch_bounds__(256) nn_rows_kernel(const ReduceArgs a, const 
 template <int VEC, int OP, bool SCALED, int U, bool EMAT = false, bool EXPSUB = false, int GATED = 0>
 static int launch_reduce(const ReduceArgs &a0, hipStream_t stream) {
     ReduceArgs a = a0;
-    const int G = 1 << a.log2g;
-    const int rpw = 64 / G;
+    const int G = 1 << a.geom.log2g;
     int waves = knob(KNOB_BLOCK_WAVES);
     if (waves < 1 || waves > 4) waves = 4;
-    a.waves = waves;
-    const int rows_per_block = rpw * waves;
-    const int64_t nvirt = (int64_t)a.n_rows + a.n_chunks;
-    const int64_t chunks = (nvirt + rows_per_block - 1) / rows_per_block;
+    a.geom.waves = waves;
     const int lanes_needed = (a.D + VEC - 1) / VEC;
     const int tiles = (lanes_needed + G - 1) / G;
-    if (chunks > 0) {
-        int64_t gx = chunks;
-        a.cpx = 0;
-        if (use_xcd_remap(a.n_src, a.D, chunks)) {
-            a.nbc = (int)std::min<int64_t>(chunks, (a.n_chunks + rows_per_block - 1) / rows_per_block);
-            a.cpx = (int)((chunks - a.nbc + 7) / 8);
-            gx = (int64_t)a.nbc + (int64_t)a.cpx * 8;
-        }
-        dim3 grid((unsigned)gx, (unsigned)tiles);
+    const dim3 grid = row_grid(a.rows, a.geom, tiles, use_xcd_remap(a.n_src, a.D, row_blocks(a.rows, a.geom)));
+    if (grid.x > 0) {
         // the plain propagate / scatter instances fold their split rows themselves (a.arrive set by run_reduce when it may)
         constexpr bool CAN_FOLD = !EMAT && !EXPSUB && GATED == 0 && U == 8;
-        if (CAN_FOLD && a.arrive && a.n_long > 0) {
+        if (CAN_FOLD && a.arrive && a.rows.n_long > 0) {
             csr_rows_kernel<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED, CAN_FOLD><<<grid, 64 * waves, 0, stream>>>(a);
             GNNMP_LAUNCH_CHECK("csr_rows_kernel<FOLD>");
             return GNNMP_OK;
@@ -302,9 +243,9 @@ static int launch_reduce(const ReduceArgs &a0, hipStream_t stream) {
         csr_rows_kernel<VEC, OP, SCALED, U, EMAT, EXPSUB, GATED><<<grid, 64 * waves, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("csr_rows_kernel");
     }
-    if (a.n_long > 0) {
-        dim3 grid((unsigned)a.n_long, (unsigned)tiles);
-        csr_combine_kernel<VEC, OP><<<grid, 256, 0, stream>>>(a);
+    if (a.rows.n_long > 0) {
+        dim3 cg((unsigned)a.rows.n_long, (unsigned)tiles);
+        csr_combine_kernel<VEC, OP><<<cg, 256, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("csr_combine_kernel");
     }
     return GNNMP_OK;
@@ -366,10 +307,9 @@ int run_reduce(gnnmp_graph_t *p, const int32_t *idx, int aggr, const float *x, c
     }
     ReduceArgs a;
     a.compact_long = long_only;
-    a.rowptr = p->rowptr;
-    a.row_order = nullptr;
-    a.idx = idx;
-    a.eid = p->eid;
+    a.rows = plan_rows(p);
+    a.rows.col = idx;
+    if (long_only) a.rows.n_rows = 0;
     a.x = x;
     a.w = w;
     a.emat = emat;
@@ -389,42 +329,29 @@ int run_reduce(gnnmp_graph_t *p, const int32_t *idx, int aggr, const float *x, c
     a.addend = addend;
     a.mask_y = mask_y;
     a.partial = p->ws;
-    a.chunk_row = p->chunk_row;
-    a.chunk_beg = p->chunk_beg;
-    a.chunk_end = p->chunk_end;
-    a.long_rows = p->long_rows;
-    a.long_cptr = p->long_cptr;
-    a.n_chunks = p->n_chunks;
-    a.n_long = p->n_long;
     a.D = (int)D;
-    a.n_rows = long_only ? 0 : (int)p->n_dst;
     a.n_src = (int)p->n_src;
-    a.n_edges = (uint32_t)p->n_edges;
     a.mean = (aggr == GNNMP_MEAN);
-    a.long_thresh = p->long_thresh;
-    a.cpx = 0;
-    a.nbc = 0;
-    a.waves = 4;
-    a.chunk_lrow = p->chunk_lrow;
+    a.geom = RowGeom{0, 4, 0, 0};
     a.arrive = nullptr;
     int vec = pick_vec(D, x, out);
     if (addend && (reinterpret_cast<uintptr_t>(addend) & (4 * vec - 1)) != 0) vec = 1;
     if (mask_y && (reinterpret_cast<uintptr_t>(mask_y) & (4 * vec - 1)) != 0) vec = 1;
     if (emat && (reinterpret_cast<uintptr_t>(emat) & (4 * vec - 1)) != 0) vec = 1;
     if (gate_i && (reinterpret_cast<uintptr_t>(gate_i) & (4 * vec - 1)) != 0) vec = 1;
-    a.log2g = pick_log2g((D + vec - 1) / vec);
+    a.geom.log2g = pick_log2g((D + vec - 1) / vec);
     // >= 2 rows per wave: pair rows of equal length — but only when an output row is whole 128-byte lines: out of index order,
     // rows of 400 bytes (D = 100) leave every line half written by one wave and finished by another, measured 4.75 -> 5.11 ms
-    if (!long_only && use_row_order(p->n_src, D) && a.log2g <= 5 && idx == p->col && (D & 31) == 0 &&
+    if (!long_only && use_row_order(p->n_src, D) && a.geom.log2g <= 5 && idx == p->col && (D & 31) == 0 &&
         (reinterpret_cast<uintptr_t>(out) & 127) == 0) {
         if (int rc = ensure_row_order(p, stream)) return rc;
-        a.row_order = p->row_order;
+        a.rows.row_order = p->row_order;
     }
     const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
     const bool scaled = w || ss || w_slot || ss_slot;
     a.spart = nullptr;
     if (p->n_long > 0 && use_fold()) {      // split rows folded inside the row kernel: arrival counters per (long row, feature tile, slice)
-        const int G = 1 << a.log2g, NG = 256 >> a.log2g;
+        const int G = 1 << a.geom.log2g, NG = 256 >> a.geom.log2g;
         const size_t tiles = (size_t)(((D + vec - 1) / vec + G - 1) / G);
         if (int rc = ensure_arrive(p, (size_t)p->n_long * tiles * (size_t)(NG + 1), (size_t)p->n_long * (size_t)NG * (size_t)D, stream)) return rc;
         a.arrive = p->arrive;
@@ -455,32 +382,23 @@ int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float
     if (int rc = run_reduce(p, p->eid, GNNMP_SUM, e, nullptr, nullptr, nullptr, nullptr, nullptr, den, D, stream, nullptr, mx))
         return rc;
     ReduceArgs a = {};
-    a.rowptr = p->rowptr;
-    a.idx = p->eid;
+    a.rows = plan_rows(p);
+    a.rows.col = p->eid;      // rows of e / alpha: by original edge position
     a.x = e;
     a.out = alpha;
     a.rowsub = mx;
     a.rowden = den;
     a.den_add = den_add;
-    a.chunk_row = p->chunk_row;
-    a.chunk_beg = p->chunk_beg;
-    a.chunk_end = p->chunk_end;
-    a.n_chunks = p->n_chunks;
     a.D = (int)D;
-    a.n_rows = (int)p->n_dst;
-    a.long_thresh = p->long_thresh;
-    a.waves = 4;
     int vec = pick_vec(D, e, alpha);
-    a.log2g = pick_log2g((D + vec - 1) / vec);
-    const int G = 1 << a.log2g;
+    a.geom = RowGeom{pick_log2g((D + vec - 1) / vec), 4, 0, 0};
+    const int G = 1 << a.geom.log2g;
     const int tiles = (int)(((D + vec - 1) / vec + G - 1) / G);
-    const int64_t nvirt = (int64_t)a.n_rows + a.n_chunks;
-    const int64_t rows_per_block = (int64_t)(64 / G) * a.waves;
-    dim3 grid((unsigned)((nvirt + rows_per_block - 1) / rows_per_block), (unsigned)tiles);
+    const dim3 grid = row_grid(a.rows, a.geom, tiles);
     switch (vec) {
-        case 4: softmax_write_kernel<4, 8><<<grid, 64 * a.waves, 0, stream>>>(a); break;
-        case 2: softmax_write_kernel<2, 8><<<grid, 64 * a.waves, 0, stream>>>(a); break;
-        default: softmax_write_kernel<1, 8><<<grid, 64 * a.waves, 0, stream>>>(a); break;
+        case 4: softmax_write_kernel<4, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
+        case 2: softmax_write_kernel<2, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
+        default: softmax_write_kernel<1, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
     }
     GNNMP_LAUNCH_CHECK("softmax_write_kernel");
     return GNNMP_OK;
@@ -490,18 +408,15 @@ int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float
 int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int aggr, hipStream_t stream) {
     if (p->n_long == 0) return GNNMP_OK;
     ReduceArgs a = {};
-    a.rowptr = p->rowptr;
+    a.rows = plan_rows(p);
     a.out = out;
     a.partial = p->ws;
-    a.long_rows = p->long_rows;
-    a.long_cptr = p->long_cptr;
-    a.n_long = p->n_long;
     a.D = (int)D;
     const int vec = pick_vec(D, p->ws, out);
-    a.log2g = pick_log2g((D + vec - 1) / vec);
-    const int G = 1 << a.log2g;
+    a.geom.log2g = pick_log2g((D + vec - 1) / vec);
+    const int G = 1 << a.geom.log2g;
     const int tiles = (int)(((D + vec - 1) / vec + G - 1) / G);
-    dim3 grid((unsigned)a.n_long, (unsigned)tiles);
+    dim3 grid((unsigned)a.rows.n_long, (unsigned)tiles);
     if (aggr == GNNMP_MAX) {
         switch (vec) {
             case 4: csr_combine_kernel<4, OP_MAX><<<grid, 256, 0, stream>>>(a); break;
@@ -649,41 +564,26 @@ int gnnmp_propagate_nn_f32(gnnmp_graph_t *p, int aggr, const float *xj, const fl
         if (int rc = ensure_workspace(p, (size_t)p->n_chunks * (size_t)Dout)) return rc;
     }
     ReduceArgs a = {};
-    a.rowptr = p->rowptr;
-    a.idx = p->col;
-    a.eid = p->eid;
+    a.rows = plan_rows(p);
     a.x = xj;
     a.out = out;
     a.partial = p->ws;
-    a.chunk_row = p->chunk_row;
-    a.chunk_beg = p->chunk_beg;
-    a.chunk_end = p->chunk_end;
-    a.long_rows = p->long_rows;
-    a.long_cptr = p->long_cptr;
-    a.n_chunks = p->n_chunks;
-    a.n_long = p->n_long;
     a.D = (int)Dout;
-    a.n_rows = (int)p->n_dst;
     a.n_src = (int)p->n_src;
-    a.n_edges = (uint32_t)p->n_edges;
     a.mean = (aggr == GNNMP_MEAN);
-    a.long_thresh = p->long_thresh;
-    a.waves = 4;
-    a.log2g = pick_log2g(Dout);
-    const int G = 1 << a.log2g;
+    a.geom = RowGeom{pick_log2g(Dout), 4, 0, 0};
+    const int G = 1 << a.geom.log2g;
     const int tiles = (int)((Dout + G - 1) / G);
-    const int64_t nvirt = (int64_t)a.n_rows + a.n_chunks;
-    const int64_t rows_per_block = (int64_t)(64 / G) * a.waves;
-    dim3 grid((unsigned)((nvirt + rows_per_block - 1) / rows_per_block), (unsigned)tiles);
+    const dim3 grid = row_grid(a.rows, a.geom, tiles);
     const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
     switch (op) {
-        case OP_SUM: nn_rows_kernel<OP_SUM><<<grid, 64 * a.waves, 0, stream>>>(a, we, (int)Din); break;
-        case OP_MAX: nn_rows_kernel<OP_MAX><<<grid, 64 * a.waves, 0, stream>>>(a, we, (int)Din); break;
-        default: nn_rows_kernel<OP_MIN><<<grid, 64 * a.waves, 0, stream>>>(a, we, (int)Din); break;
+        case OP_SUM: nn_rows_kernel<OP_SUM><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
+        case OP_MAX: nn_rows_kernel<OP_MAX><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
+        default: nn_rows_kernel<OP_MIN><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
     }
     GNNMP_LAUNCH_CHECK("nn_rows_kernel");
-    if (a.n_long > 0) {
-        dim3 cg((unsigned)a.n_long, (unsigned)tiles);
+    if (a.rows.n_long > 0) {
+        dim3 cg((unsigned)a.rows.n_long, (unsigned)tiles);
         switch (op) {
             case OP_SUM: csr_combine_kernel<1, OP_SUM><<<cg, 256, 0, stream>>>(a); break;
             case OP_MAX: csr_combine_kernel<1, OP_MAX><<<cg, 256, 0, stream>>>(a); break;

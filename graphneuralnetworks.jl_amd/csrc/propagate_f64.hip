@@ -10,7 +10,7 @@
 // folded in chunk order by a second small kernel (the two-kernel scheme of rounds 1-4: deterministic, no cross-workgroup hand-off inside
 // a launch).  Bound: HBM / the fabric's line-request rate like the fp32 kernels — a row of D doubles is 8 D bytes; no effort was spent
 // on tuning beyond the shared structure (the fp32 kernels are the measured product path; this one is about not falling back).
-#include "common.h"
+#include "rowwalk.h"
 
 namespace gnnmp {
 
@@ -39,40 +39,25 @@ __device__ __forceinline__ double op_apply64(double a, double b) {
 }
 
 struct R64Args {
-    const uint32_t *rowptr;
-    const int32_t *idx;       // per slot: row of x to read (plan->col, or plan->eid for _scatter)
-    const int32_t *eid;       // per slot: original edge position (weights)
+    PlanRows rows;            // rows.col: per slot, the row of x to read (plan->col, or plan->eid for _scatter); rows.eid: weights
+    RowGeom geom;
     const double *x;          // [n_src][D]
     const double *w;          // [n_edges] original edge order, nullable; plan-added self loops weigh 1
     const double *ss, *sd;    // [n_src] / [n_dst] nullable: the GCN-style source / destination factors
     double *out;              // [n_dst][D]
     double *partial;          // [n_chunks][D]
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    const int32_t *long_rows, *long_cptr;
-    int n_chunks, n_long, D, n_rows, log2g, mean, long_thresh;
-    uint32_t n_edges;
+    int D, mean;
 };
 
 // PAIR: D is even and x is 16-byte aligned — a lane's two doubles are ONE 16-byte load (otherwise two 8-byte loads)
 template <int OP, bool SCALED, bool PAIR>
 __global__ void __launch_bounds__(256) csr_rows_f64_kernel(const R64Args a) {
     constexpr int U = 8;
-    const int lane = threadIdx.x & 63;
-    const int G = 1 << a.log2g;
-    const int lig = lane & (G - 1), gbase = lane - lig;
-    const int64_t v64 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> a.log2g;
-    if (v64 >= (int64_t)a.n_rows + a.n_chunks) return;
-    const int v = (int)v64;
-    int row;
-    uint32_t beg, end;
-    const bool is_chunk = v < a.n_chunks;
-    if (is_chunk) {
-        row = a.chunk_row[v]; beg = a.chunk_beg[v]; end = a.chunk_end[v];
-    } else {
-        row = v - a.n_chunks; beg = a.rowptr[row]; end = a.rowptr[row + 1];
-        if (end - beg > (uint32_t)a.long_thresh) return;      // split row: its chunks are virtual rows, folded by csr_combine_f64_kernel
-    }
+    VRow vr;
+    if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;      // (split rows: folded by csr_combine_f64_kernel)
+    const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
+    const bool is_chunk = vr.is_chunk;
+    const uint32_t beg = vr.beg, end = vr.end;
     const int D = a.D;
     for (int ft = 0; ft < D; ft += 2 * G) {                    // feature tiles of 2 G columns (one pass over the row per tile)
         // EVERY lane of the group walks the edges (it supplies source ids to the others); only its loads and sums depend on its columns
@@ -84,11 +69,11 @@ __global__ void __launch_bounds__(256) csr_rows_f64_kernel(const R64Args a) {
             uint32_t c = 0;
             double wv = 1.0, sv = 1.0;
             if (p < end) {
-                c = (uint32_t)a.idx[p];
+                c = (uint32_t)a.rows.col[p];
                 if (SCALED) {
                     if (a.w) {
-                        const uint32_t e = (uint32_t)a.eid[p];
-                        if (e < a.n_edges) wv = a.w[e];
+                        const uint32_t e = (uint32_t)a.rows.eid[p];
+                        if (e < a.rows.n_edges) wv = a.w[e];
                     }
                     if (a.ss) sv = a.ss[c];
                 }
@@ -154,12 +139,12 @@ __global__ void __launch_bounds__(256) csr_rows_f64_kernel(const R64Args a) {
 template <int OP>
 __global__ void __launch_bounds__(256) csr_combine_f64_kernel(const R64Args a) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)a.n_long * a.D) return;
+    if (t >= (int64_t)a.rows.n_long * a.D) return;
     const int r = (int)(t / a.D), f = (int)(t - (int64_t)r * a.D);
-    const int row = a.long_rows[r];
+    const int row = a.rows.long_rows[r];
     double acc = op_identity64<OP>();
-    for (int c = a.long_cptr[r]; c < a.long_cptr[r + 1]; ++c) acc = op_apply64<OP>(acc, a.partial[(int64_t)c * a.D + f]);
-    const uint32_t len = a.rowptr[row + 1] - a.rowptr[row];
+    for (int c = a.rows.long_cptr[r]; c < a.rows.long_cptr[r + 1]; ++c) acc = op_apply64<OP>(acc, a.partial[(int64_t)c * a.D + f]);
+    const uint32_t len = a.rows.rowptr[row + 1] - a.rows.rowptr[row];
     if (OP == OP_SUM && a.mean) acc = 0.0 + acc / (double)len;
     if (a.sd) acc = acc * a.sd[row];
     a.out[(int64_t)row * a.D + f] = acc;
@@ -175,16 +160,14 @@ __global__ void __launch_bounds__(256) gather_f64_kernel(const double *x, const 
 
 template <int OP, bool SCALED>
 static int launch_rows64(const R64Args &a, hipStream_t stream) {
-    const int64_t groups = (int64_t)a.n_rows + a.n_chunks;
-    const int64_t threads = groups << a.log2g;
-    const unsigned nb = (unsigned)((threads + 255) / 256);
+    const unsigned nb = (unsigned)row_blocks(a.rows, a.geom);
     if ((a.D & 1) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0)
         csr_rows_f64_kernel<OP, SCALED, true><<<nb, 256, 0, stream>>>(a);
     else
         csr_rows_f64_kernel<OP, SCALED, false><<<nb, 256, 0, stream>>>(a);
     GNNMP_LAUNCH_CHECK("csr_rows_f64_kernel");
-    if (a.n_long > 0) {
-        const int64_t tc = (int64_t)a.n_long * a.D;
+    if (a.rows.n_long > 0) {
+        const int64_t tc = (int64_t)a.rows.n_long * a.D;
         csr_combine_f64_kernel<OP><<<(unsigned)((tc + 255) / 256), 256, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("csr_combine_f64_kernel");
     }
@@ -196,13 +179,12 @@ static int run_reduce64(gnnmp_graph_t *p, const int32_t *idx, int aggr, const do
     if (p->n_dst == 0 || D == 0) return GNNMP_OK;
     if (D > (int64_t)INT32_MAX / 4) return fail(GNNMP_EUNSUPPORTED, "propagate_f64: D too large");
     R64Args a = {};
-    a.rowptr = p->rowptr; a.idx = idx; a.eid = p->eid; a.x = x; a.w = w; a.ss = ss; a.sd = sd; a.out = out;
-    a.chunk_row = p->chunk_row; a.chunk_beg = p->chunk_beg; a.chunk_end = p->chunk_end; a.long_rows = p->long_rows; a.long_cptr = p->long_cptr;
-    a.n_chunks = p->n_chunks; a.n_long = p->n_long; a.D = (int)D; a.n_rows = (int)p->n_dst; a.n_edges = (uint32_t)p->n_edges;
-    a.mean = (aggr == GNNMP_MEAN); a.long_thresh = p->long_thresh;
+    a.rows = plan_rows(p);
+    a.rows.col = idx;
+    a.x = x; a.w = w; a.ss = ss; a.sd = sd; a.out = out; a.D = (int)D; a.mean = (aggr == GNNMP_MEAN);
     int l = 0;
     while ((2 << l) < D && l < 6) ++l;            // 2 G >= D up to a whole wave
-    a.log2g = l;
+    a.geom = RowGeom{l, 4, 0, 0};
     if (p->n_chunks > 0) {
         if (int rc = ensure_workspace(p, 2 * (size_t)p->n_chunks * (size_t)D + 2)) return rc;      // (doubles in the float workspace: hipMalloc is 256-byte aligned)
         a.partial = reinterpret_cast<double *>(p->ws);

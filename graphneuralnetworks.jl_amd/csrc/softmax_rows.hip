@@ -22,20 +22,16 @@
 namespace gnnmp {
 
 struct SmxArgs {
-    const uint32_t *rowptr;
-    const int32_t *eid;
+    PlanRows rows;    // the rows by rowptr (softmax_rows_lds_kernel), the plan's split rows by chunk (softmax_chunk_kernel)
+    RowGeom geom;     // log2g and waves only: a WAVE owns rows / a chunk here, the virtual-row decode of rowwalk.h does not apply
     const float *e;
     float *alpha;
-    int D, n_rows, log2g, long_thresh;
+    int D;
     int cap;          // slots per batch (cap << log2g = 512: 8 items per lane)
-    int waves;        // waves per block
     int rw;           // destinations per wave (<= 64)
     int wave_bytes;   // LDS per wave
     float den_add;
     // the plan's split rows (softmax_chunk_kernel)
-    const int32_t *chunk_row;
-    const uint32_t *chunk_beg, *chunk_end;
-    int n_chunks;
     float *partial;       // [n_chunks][D]
     const float *mx;      // [n_rows][D] (split rows only)
     const float *den;     // [n_rows][D] (split rows only)
@@ -85,7 +81,7 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int IT = SMX_IT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g, Dp = G * VEC, RB = 64 >> a.log2g;
+    const int G = 1 << a.geom.log2g, Dp = G * VEC, RB = 64 >> a.geom.log2g;
     unsigned char *base = smem + (size_t)wave * a.wave_bytes;
     float *vals = reinterpret_cast<float *>(base);           // [cap][Dp]
     float *rmx = vals + (size_t)a.cap * Dp;                   // [RB][Dp]
@@ -93,13 +89,13 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
     uint32_t *wrp = reinterpret_cast<uint32_t *>(rden + RB * Dp);   // [rw + 1] the wave's row pointers (68 reserved)
     int *seid = reinterpret_cast<int *>(wrp + 68);            // [cap] original edge position of a slot (unsigned 32-bit)
     unsigned char *srow = reinterpret_cast<unsigned char *>(seid + a.cap);   // [cap] batch-relative row of a slot
-    const int64_t r0l = ((int64_t)blockIdx.x * a.waves + wave) * a.rw;
-    if (r0l >= a.n_rows) return;
-    const int r0 = (int)r0l, nr = min(a.rw, a.n_rows - r0);
-    wrp[lane] = a.rowptr[r0 + min(lane, nr)];
-    if (lane == 0) wrp[64] = a.rowptr[r0 + min(64, nr)];
+    const int64_t r0l = ((int64_t)blockIdx.x * a.geom.waves + wave) * a.rw;
+    if (r0l >= a.rows.n_rows) return;
+    const int r0 = (int)r0l, nr = min(a.rw, a.rows.n_rows - r0);
+    wrp[lane] = a.rows.rowptr[r0 + min(lane, nr)];
+    if (lane == 0) wrp[64] = a.rows.rowptr[r0 + min(64, nr)];
     smx_wave_sync();
-    const int lig = lane & (G - 1), grp = lane >> a.log2g;
+    const int lig = lane & (G - 1), grp = lane >> a.geom.log2g;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
 
@@ -110,26 +106,26 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
             const uint32_t sb = wrp[r];
             const int ci = min(r + lane + 1, nr);
             const uint32_t hi = wrp[ci];
-            const bool ok = lane < RB && r + lane + 1 <= nr && hi - sb <= (uint32_t)a.cap && hi - wrp[ci - 1] <= (uint32_t)a.long_thresh;
+            const bool ok = lane < RB && r + lane + 1 <= nr && hi - sb <= (uint32_t)a.cap && hi - wrp[ci - 1] <= (uint32_t)a.rows.long_thresh;
             const unsigned long long m = __ballot(ok);
             const int nb = (~m == 0ull) ? 64 : __builtin_ctzll(~m);
             if (nb > 0) return SmxBatch{r, nb, sb, (int)(wrp[r + nb] - sb)};
             const uint32_t len0 = wrp[r + 1] - sb;
-            if (len0 <= (uint32_t)a.long_thresh) return SmxBatch{r, 1, sb, (int)len0};
+            if (len0 <= (uint32_t)a.rows.long_thresh) return SmxBatch{r, 1, sb, (int)len0};
             ++r;
         }
         return SmxBatch{nr, 0, 0, 0};
     };
     auto load_eids = [&](uint32_t sb, int ns, int (&c)[IT]) {
-        const int nitems = min(ns, a.cap) << a.log2g;
+        const int nitems = min(ns, a.cap) << a.geom.log2g;
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
             const int i = k * 64 + lane;
-            c[k] = i < nitems ? a.eid[sb + (i >> a.log2g)] : 0;
+            c[k] = i < nitems ? a.rows.eid[sb + (i >> a.geom.log2g)] : 0;
         }
     };
     auto load_rows = [&](int ns, const int (&c)[IT], float (&v)[IT][VEC]) {
-        const int nitems = min(ns, a.cap) << a.log2g;
+        const int nitems = min(ns, a.cap) << a.geom.log2g;
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
             const int i = k * 64 + lane;
@@ -138,13 +134,13 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
     };
     // registers -> LDS (rows and edge positions of one batch)
     auto stash = [&](int ns, const int (&c)[IT], const float (&v)[IT][VEC]) {
-        const int nitems = ns << a.log2g;
+        const int nitems = ns << a.geom.log2g;
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
             const int i = k * 64 + lane;
             if (i < nitems) {
-                if (active) Vec<VEC>::store(vals + (size_t)(i >> a.log2g) * Dp + f0, v[k]);
-                if (lig == 0) seid[i >> a.log2g] = c[k];
+                if (active) Vec<VEC>::store(vals + (size_t)(i >> a.geom.log2g) * Dp + f0, v[k]);
+                if (lig == 0) seid[i >> a.geom.log2g] = c[k];
             }
         }
     };
@@ -153,7 +149,7 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
 #pragma unroll 2
         for (int i = lane; i < nitems; i += 64) {
             if (active) {
-                const int s = i >> a.log2g;
+                const int s = i >> a.geom.log2g;
                 const int j = srow[s];
                 float v[VEC], mq[VEC];
                 Vec<VEC>::load(vals + (size_t)s * Dp + f0, v);
@@ -169,7 +165,7 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
 #pragma unroll 4
         for (int i = lane; i < nitems; i += 64) {
             if (active) {
-                const int s = i >> a.log2g;
+                const int s = i >> a.geom.log2g;
                 const int j = srow[s];
                 const int c = seid[s];
                 float v[VEC], dq[VEC];
@@ -224,7 +220,7 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
         if (!big) {
             const int st = rowlane ? (int)(wrp[r + grp] - sb) : 0;
             const int len = rowlane ? (int)(wrp[r + grp + 1] - wrp[r + grp]) : 0;
-            const int nitems = ns << a.log2g;
+            const int nitems = ns << a.geom.log2g;
             // B: max_ of every row of the batch
             float acc[VEC];
 #pragma unroll
@@ -274,7 +270,7 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
             for (int q = 0; q < VEC; ++q) acc[q] = op_identity<OP_SUM>();
             for (int off = 0; off < total; off += a.cap) {
                 const int n = gather(off);
-                phase_exp(n << a.log2g);
+                phase_exp(n << a.geom.log2g);
                 smx_wave_sync();
                 smx_fold<VEC, OP_SUM>(vals, Dp, f0, 0, rowlane ? n : 0, acc);
                 smx_wave_sync();
@@ -287,9 +283,9 @@ __global__ void __launch_bounds__(256) softmax_rows_lds_kernel(const SmxArgs a) 
             smx_wave_sync();
             for (int off = 0; off < total; off += a.cap) {
                 const int n = gather(off);
-                phase_exp(n << a.log2g);
+                phase_exp(n << a.geom.log2g);
                 smx_wave_sync();
-                phase_write(n << a.log2g);
+                phase_write(n << a.geom.log2g);
                 smx_wave_sync();
             }
         }
@@ -311,12 +307,12 @@ __global__ void __launch_bounds__(256) softmax_chunk_kernel(const SmxArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int IT = SMX_IT;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int G = 1 << a.log2g, Dp = G * VEC;
-    const int v = (int)blockIdx.x * a.waves + wave;
-    if (v >= a.n_chunks) return;
-    const int row = a.chunk_row[v];
-    const uint32_t beg = a.chunk_beg[v], end = a.chunk_end[v];
-    const int lig = lane & (G - 1), grp = lane >> a.log2g;
+    const int G = 1 << a.geom.log2g, Dp = G * VEC;
+    const int v = (int)blockIdx.x * a.geom.waves + wave;
+    if (v >= a.rows.n_chunks) return;
+    const int row = a.rows.chunk_row[v];
+    const uint32_t beg = a.rows.chunk_beg[v], end = a.rows.chunk_end[v];
+    const int lig = lane & (G - 1), grp = lane >> a.geom.log2g;
     const int f0 = lig * VEC;
     const bool active = f0 < a.D;
     float *vals = reinterpret_cast<float *>(smem + (MODE == 1 ? (size_t)wave * a.wave_bytes : 0));
@@ -337,13 +333,13 @@ __global__ void __launch_bounds__(256) softmax_chunk_kernel(const SmxArgs a) {
     }
     for (uint32_t off = beg; off < end; off += a.cap) {
         const int n = (int)min((uint32_t)a.cap, end - off);
-        const int nitems = n << a.log2g;
+        const int nitems = n << a.geom.log2g;
         int c[IT];
         float x[IT][VEC];
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
             const int i = k * 64 + lane;
-            c[k] = i < nitems ? a.eid[off + (i >> a.log2g)] : 0;
+            c[k] = i < nitems ? a.rows.eid[off + (i >> a.geom.log2g)] : 0;
         }
 #pragma unroll
         for (int k = 0; k < IT; ++k) {
@@ -361,7 +357,7 @@ __global__ void __launch_bounds__(256) softmax_chunk_kernel(const SmxArgs a) {
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) x[k][q] = expf(x[k][q] - rm[q]);
                     if (MODE == 1) {
-                        Vec<VEC>::store(vals + (size_t)(i >> a.log2g) * Dp + f0, x[k]);
+                        Vec<VEC>::store(vals + (size_t)(i >> a.geom.log2g) * Dp + f0, x[k]);
                     } else {
 #pragma unroll
                         for (int q = 0; q < VEC; ++q) x[k][q] = x[k][q] / rd[q];
@@ -389,22 +385,21 @@ __global__ void __launch_bounds__(256) softmax_chunk_kernel(const SmxArgs a) {
 template <int VEC, int MODE>
 static int launch_chunks(const SmxArgs &a0, hipStream_t stream) {
     SmxArgs a = a0;
-    a.waves = 4;
-    a.wave_bytes = a.cap * (1 << a.log2g) * VEC * 4;
-    const size_t lds = MODE == 1 ? (size_t)a.waves * a.wave_bytes : 0;
-    const unsigned blocks = (unsigned)((a.n_chunks + a.waves - 1) / a.waves);
-    softmax_chunk_kernel<VEC, MODE><<<blocks, 64 * a.waves, lds, stream>>>(a);
+    a.wave_bytes = a.cap * (1 << a.geom.log2g) * VEC * 4;
+    const size_t lds = MODE == 1 ? (size_t)a.geom.waves * a.wave_bytes : 0;
+    const unsigned blocks = (unsigned)((a.rows.n_chunks + a.geom.waves - 1) / a.geom.waves);
+    softmax_chunk_kernel<VEC, MODE><<<blocks, 64 * a.geom.waves, lds, stream>>>(a);
     GNNMP_LAUNCH_CHECK("softmax_chunk_kernel");
     return GNNMP_OK;
 }
 
 template <int VEC>
 static int launch_smx(const SmxArgs &a, hipStream_t stream) {
-    const size_t lds = (size_t)a.waves * a.wave_bytes;
+    const size_t lds = (size_t)a.geom.waves * a.wave_bytes;
     GNNMP_LDS_OPTIN("softmax_rows_lds_kernel", &softmax_rows_lds_kernel<VEC>);
-    const int64_t wave_rows = ((int64_t)a.n_rows + a.rw - 1) / a.rw;
-    const int64_t blocks = (wave_rows + a.waves - 1) / a.waves;
-    softmax_rows_lds_kernel<VEC><<<(unsigned)blocks, 64 * a.waves, lds, stream>>>(a);
+    const int64_t wave_rows = ((int64_t)a.rows.n_rows + a.rw - 1) / a.rw;
+    const int64_t blocks = (wave_rows + a.geom.waves - 1) / a.geom.waves;
+    softmax_rows_lds_kernel<VEC><<<(unsigned)blocks, 64 * a.geom.waves, lds, stream>>>(a);
     GNNMP_LAUNCH_CHECK("softmax_rows_lds_kernel");
     return GNNMP_OK;
 }
@@ -422,26 +417,22 @@ int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, 
     const int vec = pick_vec(D, e, alpha);
     const int lanes = (int)((D + vec - 1) / vec);
     if (lanes > 64) return 1;
-    a.log2g = 0;
-    while ((1 << a.log2g) < lanes) ++a.log2g;   // not pick_log2g: the batch layout needs every lane of a row in ONE group
-    const int G = 1 << a.log2g, Dp = G * vec, RB = 64 / G;
+    a.geom.waves = 4;
+    while ((1 << a.geom.log2g) < lanes) ++a.geom.log2g;   // not pick_log2g: the batch layout needs every lane of a row in ONE group
+    const int G = 1 << a.geom.log2g, Dp = G * vec, RB = 64 / G;
     a.cap = SMX_IT * 64 / G;
     if (a.cap < 64) return 1;                   // more than 8 lanes per row (H > 32): whole lines per row, the row walk of
                                                 // propagate.hip is the tool (H = 64: 14.0 ms here, 13.2 ms there; H = 32: 6.6 / 8.5)
-    a.rowptr = p->rowptr;
-    a.eid = p->eid;
+    a.rows = plan_rows(p);
     a.e = e;
     a.alpha = alpha;
     a.D = (int)D;
-    a.n_rows = (int)p->n_dst;
-    a.long_thresh = p->long_thresh;
     a.den_add = den_add;
     const size_t bytes = ((size_t)a.cap * Dp + 2 * (size_t)RB * Dp + 68 + (size_t)a.cap) * 4 + (size_t)a.cap;
     a.wave_bytes = (int)((bytes + 15) & ~(size_t)15);
-    a.waves = 4;
     // destinations per wave: 64, fewer on small inputs so that every CU has waves to run
     a.rw = 64;
-    while (a.rw > 8 && ((int64_t)a.n_rows + a.rw - 1) / a.rw < 16 * (int64_t)device_cus()) a.rw >>= 1;
+    while (a.rw > 8 && ((int64_t)a.rows.n_rows + a.rw - 1) / a.rw < 16 * (int64_t)device_cus()) a.rw >>= 1;
     int rc;
     switch (vec) {
         case 4: rc = launch_smx<4>(a, stream); break;
@@ -449,10 +440,6 @@ int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, 
         default: rc = launch_smx<1>(a, stream); break;
     }
     if (rc != GNNMP_OK || p->n_chunks == 0) return rc;
-    a.chunk_row = p->chunk_row;
-    a.chunk_beg = p->chunk_beg;
-    a.chunk_end = p->chunk_end;
-    a.n_chunks = p->n_chunks;
     a.partial = partial;
     a.mx = mx;
     a.den = den;

@@ -279,7 +279,7 @@ def set_probe(p):
 
 KNOB_TGCN = 20                            # csrc/common.h: 0 = auto, < 0 = TGCN's per-step path
 KNOB_EDGE_DOT_GRAD = 21                   # csrc/common.h: 0 = auto, < 0 = the edge-dot adjoint as two propagates (gnnmp/linkpred.py)
-KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.cpp g_knobs)
+KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.hip g_knobs)
 _knobs = {}
 
 

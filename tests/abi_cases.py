@@ -532,8 +532,9 @@ class Ctx:
         self.r300 = random_graph("n300", 300, 900, 3)
         self.cache = {}                                 # graphs a builder makes for itself (plans are keyed on the Graph object)
 
-    def graph_shapes(self, Ds=DS, small=(3, 128), align=(3, 6, 128), ws=(4,)):
-        """(graph, D, tags): every width on the hub graph, two widths on the others"""
+    def graph_shapes(self, Ds=DS, small=(3, 128), align=(3, 6, 128), ws=(4,), rows300=(1, 260)):
+        """(graph, D, tags): every width on the hub graph, two widths on the others; the 300-row graph also at the narrowest width (64 rows to
+        a wave: only there does a launch have a second block of rows and a last block that is not full) and at one of several feature tiles"""
         first = True
         for D in Ds:
             tags = set()
@@ -549,6 +550,9 @@ class Ctx:
             for D in small:
                 if D in Ds:
                     yield g, D, set()
+        for D in rows300:
+            if D in Ds and D not in small:
+                yield self.r300, D, set()
 
     def short_rows(self, g, loops=False):
         return (g.indeg() + (1 if loops else 0)) <= self.thr
@@ -823,7 +827,8 @@ def _(ctx):
 @cases_of("gnnmp_propagate_nn_f32")
 def _(ctx):
     shapes = [(ctx.hub, 3, 5, {"align", "side", "ws"}), (ctx.hub, 4, 4, {"align"}), (ctx.hub, 7, 2, ()), (ctx.hub, 1, 1, ()), (ctx.hub, 6, 33, {"align"}),
-              (ctx.e0, 3, 4, ()), (ctx.one, 4, 3, ()), (ctx.r31, 2, 6, ()), (ctx.r33, 5, 3, ()), (ctx.r300, 4, 8, ())]
+              (ctx.e0, 3, 4, ()), (ctx.one, 4, 3, ()), (ctx.r31, 2, 6, ()), (ctx.r33, 5, 3, ()), (ctx.r300, 4, 8, ()),
+              (ctx.r300, 3, 1, ()), (ctx.r300, 2, 70, ())]         # 64 rows to a wave; two feature tiles (a lane per output feature)
     for k, (g, Din, Dout, tags) in enumerate(shapes):
         aggr = (SUM, MEAN, MAX)[k % 3]
         r = rng_of("nn", g.name, Din, Dout)
@@ -1137,7 +1142,7 @@ def _(ctx):
 # ---- softmax and attention -------------------------------------------------------------------------------------------------------
 @cases_of("gnnmp_edge_softmax_f32")
 def _(ctx):
-    for g, H, tags in ctx.graph_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129), small=(3, 4), ws=(3,)):
+    for g, H, tags in list(ctx.graph_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129), small=(3, 4), ws=(3,))) + [(ctx.r300, 260, set())]:   # (two feature tiles)
         lg = F(rng_of("edge_softmax", g.name, H), g.E, H) * f32(3)
         yield mk("gnnmp_edge_softmax_f32", f"{g.name}_H{H}", tags, [Pl(g), Arr("logits", "in", lg), Arr("alpha", "out", shape=(g.E, H)), H, STREAM],
                  lambda host, g=g, lg=lg: {"alpha": orc().softmax_edge_neighbors(g.t, g.n_dst, lg)})
@@ -1275,7 +1280,7 @@ def att_shapes(ctx, loops):
     for k, (H, C) in enumerate(ATT_HC):
         yield ctx.hub, H, C, ({"align"} if k < 4 else set()) | ({"side", "ws"} if k == 0 else set())
     for g in (ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300):
-        for H, C in ((3, 7), (2, 8)):
+        for H, C in ((3, 7), (2, 8)) + (((1, 1),) if g is ctx.r300 else ()):     # (1, 1): 64 rows to a wave, more than one block of them
             yield g, H, C, set()
 
 
