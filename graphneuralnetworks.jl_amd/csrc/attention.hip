@@ -9,10 +9,10 @@
 // max over the row, sum of exp(l - max) in edge order, then alpha = num / den (true division), beta = alpha * Wx_j
 // (rounded), accumulated in edge order.
 #include "rowwalk.h"
+#include "launch.h"
 
 namespace gnnmp {
 
-int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, hipStream_t stream);  // propagate.hip
 
 __device__ __forceinline__ float leaky_relu(float x, float slope) {
     return x > 0.0f ? x : x * slope;  // NNlib.leakyrelu
@@ -339,11 +339,7 @@ int gnnmp_gat_aggregate_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
     int vec = pick_vec(a.D, Wx_src, out);
     while (vec > 1 && (C % vec) != 0) vec >>= 1;
     a.geom = RowGeom{pick_log2g((a.D + vec - 1) / vec), 4, 0, 0};
-    switch (vec) {
-        case 4: return launch_gat<4>(a, stream);
-        case 2: return launch_gat<2>(a, stream);
-        default: return launch_gat<1>(a, stream);
-    }
+    return with_vec(vec, [&](auto V) { return launch_gat<decltype(V)::value>(a, stream); });
 }
 
 int gnnmp_bias_act_f32(const float *x, const float *bias, int act, float *out, int64_t N, int64_t D,

@@ -452,80 +452,109 @@ static int dispatch_attn_bwd(const AttnBwdArgs &g, int vec, int lph, gnnmp_graph
 
 using namespace gnnmp;
 
-static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, int mode, const float *Q, const float *K,
-                               const float *V, const float *a, float negative_slope, float scale, float drop_p, uint64_t drop_seed,
-                               const float *stats, const float *dout, float *line, float *dQ, float *dK, float *dV,
-                               float *dA, float *da, int64_t H, int64_t C, gnnmp_stream_t stream_) {
+// one call of the GATv2 / dot-product attention pullback: what the two exports below ask of attn_conv_grad_impl, by name
+struct AttnGradCall {
+    int mode = GNNMP_ATTN_GATV2;
+    const float *Q = nullptr, *K = nullptr, *V = nullptr, *a = nullptr;   // V null: K
+    float negative_slope = 0.0f, scale = 1.0f;
+    float drop_p = 0.0f;
+    uint64_t drop_seed = 0;
+    const float *stats = nullptr, *dout = nullptr;
+    float *line = nullptr, *dQ = nullptr, *dK = nullptr, *dV = nullptr, *dA = nullptr, *da = nullptr;
+    int64_t H = 0, C = 0;
+};
+
+static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, AttnGradCall c, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!(drop_p >= 0.0f && drop_p < 1.0f)) return fail(GNNMP_EINVAL, "attn_conv_grad: dropout probability %g outside [0, 1)", (double)drop_p);
-    if (drop_p > 0.0f && mode != GNNMP_ATTN_GATV2)
+    if (!(c.drop_p >= 0.0f && c.drop_p < 1.0f)) return fail(GNNMP_EINVAL, "attn_conv_grad: dropout probability %g outside [0, 1)", (double)c.drop_p);
+    if (c.drop_p > 0.0f && c.mode != GNNMP_ATTN_GATV2)
         return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: attention dropout only on the GATv2 logit here (GAT: gnnmp_gat_conv_grad_drop_f32)");
     if (!plan || !plan_t) return fail(GNNMP_EINVAL, "attn_conv_grad: null plan");
-    if (mode != GNNMP_ATTN_GATV2 && mode != GNNMP_ATTN_DOT)
-        return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: mode %d (GAT has gnnmp_gat_conv_grad_f32; the cosine logit has no pullback yet)", mode);
-    if (H <= 0 || C <= 0 || H * C > (1 << 20)) return fail(GNNMP_EINVAL, "attn_conv_grad: bad H/C");
+    if (c.mode != GNNMP_ATTN_GATV2 && c.mode != GNNMP_ATTN_DOT)
+        return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: mode %d (GAT has gnnmp_gat_conv_grad_f32; the cosine logit has no pullback yet)", c.mode);
+    if (c.H <= 0 || c.C <= 0 || c.H * c.C > (1 << 20)) return fail(GNNMP_EINVAL, "attn_conv_grad: bad H/C");
     if (plan_t->n_dst != plan->n_src || plan_t->n_src != plan->n_dst || plan_t->n_total != plan->n_total)
         return fail(GNNMP_EINVAL, "attn_conv_grad: plan_t is not the transpose of plan");
     if (plan->n_dst == 0 && plan->n_src == 0) return GNNMP_OK;
-    if (!V) V = K;
-    if (mode == GNNMP_ATTN_GATV2 && V != K) return fail(GNNMP_EINVAL, "attn_conv_grad: GATV2 has V = K");
-    if (!Q || !K || !stats || !dout || !line || !dQ || !dK || (mode == GNNMP_ATTN_DOT && !dV) ||
-        (mode == GNNMP_ATTN_GATV2 && (!a || !dA)))
+    if (!c.V) c.V = c.K;
+    if (c.mode == GNNMP_ATTN_GATV2 && c.V != c.K) return fail(GNNMP_EINVAL, "attn_conv_grad: GATV2 has V = K");
+    if (!c.Q || !c.K || !c.stats || !c.dout || !c.line || !c.dQ || !c.dK || (c.mode == GNNMP_ATTN_DOT && !c.dV) ||
+        (c.mode == GNNMP_ATTN_GATV2 && (!c.a || !c.dA)))
         return fail(GNNMP_EINVAL, "attn_conv_grad: null pointer");
-    if ((reinterpret_cast<uintptr_t>(line) & 15) != 0) return fail(GNNMP_EINVAL, "attn_conv_grad: line must be 16-byte aligned");
-    const int D = (int)(H * C);
-    int vec = pick_vec(D, K, dK);
-    const uintptr_t all = reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(dout) |
-                          reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dV) | reinterpret_cast<uintptr_t>(dA);
-    if ((all & (4 * vec - 1)) != 0) vec = 1;
-    while (vec > 1 && (C % vec) != 0) vec >>= 1;
-    int lph = (int)(C / vec);
+    if ((reinterpret_cast<uintptr_t>(c.line) & 15) != 0) return fail(GNNMP_EINVAL, "attn_conv_grad: line must be 16-byte aligned");
+    const int D = (int)(c.H * c.C);
+    int vec = narrow_vec(pick_vec(D, c.K, c.dK), c.Q, c.V, c.dout, c.dQ, c.dV, c.dA);
+    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
+    int lph = (int)(c.C / vec);
     const int lanes = D / vec;
     int log2g = 0;
     while ((1 << log2g) < lanes) ++log2g;
-    if (H == 1 && lanes <= 64) lph = 1 << log2g;
+    if (c.H == 1 && lanes <= 64) lph = 1 << log2g;
     if (lanes > 64)
-        return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(H * C));
-    const int NA = mode == GNNMP_ATTN_GATV2 ? 4 : 2;
+        return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(c.H * c.C));
+    const int NA = c.mode == GNNMP_ATTN_GATV2 ? 4 : 2;
     const int64_t R = std::max<int64_t>(256, (plan->n_dst + 2047) / 2048);
     const size_t colsum_need = (size_t)((plan->n_dst + R - 1) / R) * (size_t)D;
     if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * ((size_t)NA * D + lanes), colsum_need))) return rc;
     if (plan_t->n_chunks > 0)
         if (int rc = ensure_workspace(plan_t, (size_t)plan_t->n_chunks * 2 * (size_t)D)) return rc;
     AttnBwdArgs g;
-    g.Q = Q;
-    g.K = K;
-    g.V = V;
-    g.a = a;
-    g.dout = dout;
-    g.stats = stats;
-    g.line = line;
-    g.dQ = dQ;
-    g.dA = dA;
-    g.dK = dK;
-    g.dV = dV;
-    g.H = (int)H;
-    g.C = (int)C;
+    g.Q = c.Q;
+    g.K = c.K;
+    g.V = c.V;
+    g.a = c.a;
+    g.dout = c.dout;
+    g.stats = c.stats;
+    g.line = c.line;
+    g.dQ = c.dQ;
+    g.dA = c.dA;
+    g.dK = c.dK;
+    g.dV = c.dV;
+    g.H = (int)c.H;
+    g.C = (int)c.C;
     g.D = D;
     g.geom = RowGeom{log2g, 1, 0, 0};
     g.lph = lph_code(lph, log2g);
-    g.slope = negative_slope;
-    g.scale = scale;
-    g.drop = make_drop(drop_p, drop_seed);
-    if (drop_p > 0.0f) {       // (the dropout variants walk the head butterfly with the run-time lane count: one instantiation per width)
-        if (vec == 4) return launch_attn_bwd<4, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, da, stream);
-        if (vec == 2) return launch_attn_bwd<2, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, da, stream);
-        return launch_attn_bwd<1, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, da, stream);
+    g.slope = c.negative_slope;
+    g.scale = c.scale;
+    g.drop = make_drop(c.drop_p, c.drop_seed);
+    if (c.drop_p > 0.0f) {       // (the dropout variants walk the head butterfly with the run-time lane count: one instantiation per width)
+        return with_vec(vec, [&](auto W) { return launch_attn_bwd<decltype(W)::value, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, c.da, stream); });
     }
-    if (mode == GNNMP_ATTN_GATV2) return dispatch_attn_bwd<GNNMP_ATTN_GATV2>(g, vec, lph, plan, plan_t, da, stream);
-    return dispatch_attn_bwd<GNNMP_ATTN_DOT>(g, vec, lph, plan, plan_t, da, stream);
+    if (c.mode == GNNMP_ATTN_GATV2) return dispatch_attn_bwd<GNNMP_ATTN_GATV2>(g, vec, lph, plan, plan_t, c.da, stream);
+    return dispatch_attn_bwd<GNNMP_ATTN_DOT>(g, vec, lph, plan, plan_t, c.da, stream);
+}
+
+// what the two exports share (their arguments in the exports' order)
+static AttnGradCall attn_grad_call(int mode, const float *Q, const float *K, const float *V, const float *a, float negative_slope,
+                                   float scale, const float *stats, const float *dout, float *line, float *dQ, float *dK, float *dV,
+                                   float *dA, float *da, int64_t H, int64_t C) {
+    AttnGradCall c;
+    c.mode = mode;
+    c.Q = Q;
+    c.K = K;
+    c.V = V;
+    c.a = a;
+    c.negative_slope = negative_slope;
+    c.scale = scale;
+    c.stats = stats;
+    c.dout = dout;
+    c.line = line;
+    c.dQ = dQ;
+    c.dK = dK;
+    c.dV = dV;
+    c.dA = dA;
+    c.da = da;
+    c.H = H;
+    c.C = C;
+    return c;
 }
 
 extern "C" int gnnmp_attn_conv_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, int mode, const float *Q, const float *K,
                                         const float *V, const float *a, float negative_slope, float scale,
                                         const float *stats, const float *dout, float *line, float *dQ, float *dK, float *dV,
                                         float *dA, float *da, int64_t H, int64_t C, gnnmp_stream_t stream) {
-    return attn_conv_grad_impl(plan, plan_t, mode, Q, K, V, a, negative_slope, scale, 0.0f, 0, stats, dout, line, dQ, dK, dV, dA, da, H, C,
+    return attn_conv_grad_impl(plan, plan_t, attn_grad_call(mode, Q, K, V, a, negative_slope, scale, stats, dout, line, dQ, dK, dV, dA, da, H, C),
                                stream);
 }
 extern "C" int gnnmp_attn_conv_grad_drop_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, int mode, const float *Q, const float *K,
@@ -533,6 +562,8 @@ extern "C" int gnnmp_attn_conv_grad_drop_f32(gnnmp_graph_t *plan, gnnmp_graph_t 
                                              uint64_t seed, const float *stats, const float *dout, float *line, float *dQ,
                                              float *dK, float *dV, float *dA, float *da, int64_t H, int64_t C,
                                              gnnmp_stream_t stream) {
-    return attn_conv_grad_impl(plan, plan_t, mode, Q, K, V, a, negative_slope, scale, p, seed, stats, dout, line, dQ, dK, dV, dA, da, H,
-                               C, stream);
+    AttnGradCall c = attn_grad_call(mode, Q, K, V, a, negative_slope, scale, stats, dout, line, dQ, dK, dV, dA, da, H, C);
+    c.drop_p = p;
+    c.drop_seed = seed;
+    return attn_conv_grad_impl(plan, plan_t, c, stream);
 }

@@ -17,6 +17,7 @@
 //   - the max / min adjoint, which compares the forward input with the forward output per feature: maxmin_grad_kernel
 //     on the transposed plan.
 #include "rowwalk.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -186,8 +187,6 @@ __global__ void __launch_bounds__(256) maxmin_grad_kernel(const MaxMinGradArgs a
     if (active) Vec<VEC>::store((is_chunk ? a.partial + (int64_t)v * a.D : a.dx + (int64_t)row * a.D) + f0, acc);
 }
 
-int run_combine_sum(gnnmp_graph_t *p, float *out, int64_t D, hipStream_t stream);  // propagate.hip
-
 }  // namespace gnnmp
 
 using namespace gnnmp;
@@ -207,11 +206,9 @@ int gnnmp_edge_dot_f32(const float *a_dst, const float *b_src, const void *src, 
     const int log2g = pick_log2g((D + vec - 1) / vec);
     const int64_t threads = n_edges << log2g;
     const unsigned nb = (unsigned)((threads + 255) / 256);
-    switch (vec) {
-        case 4: edge_dot_kernel<4><<<nb, 256, 0, stream>>>(a_dst, b_src, src, dst, idx_bytes, index_base, n_edges, (int)D, log2g, out); break;
-        case 2: edge_dot_kernel<2><<<nb, 256, 0, stream>>>(a_dst, b_src, src, dst, idx_bytes, index_base, n_edges, (int)D, log2g, out); break;
-        default: edge_dot_kernel<1><<<nb, 256, 0, stream>>>(a_dst, b_src, src, dst, idx_bytes, index_base, n_edges, (int)D, log2g, out); break;
-    }
+    with_vec(vec, [&](auto V) {
+        edge_dot_kernel<decltype(V)::value><<<nb, 256, 0, stream>>>(a_dst, b_src, src, dst, idx_bytes, index_base, n_edges, (int)D, log2g, out);
+    });
     GNNMP_LAUNCH_CHECK("edge_dot_kernel");
     return GNNMP_OK;
 }
@@ -235,19 +232,9 @@ int gnnmp_edge_dot_plan_f32(gnnmp_graph_t *plan, const float *a_dst, const float
     a.geom = RowGeom{0, 4, 0, 0};
     while ((1 << a.geom.log2g) < lanes) ++a.geom.log2g;
     const unsigned nb = (unsigned)row_blocks(a.rows, a.geom);
-#define EDR(V, LG) edge_dot_rows_kernel<V, LG><<<nb, 256, 0, stream>>>(a)
-#define EDR_LG(V)                                                                                                       \
-    switch (a.geom.log2g) {                                                                                                \
-        case 0: EDR(V, 0); break; case 1: EDR(V, 1); break; case 2: EDR(V, 2); break; case 3: EDR(V, 3); break;          \
-        case 4: EDR(V, 4); break; case 5: EDR(V, 5); break; default: EDR(V, 6); break;                                   \
-    }
-    switch (vec) {
-        case 4: EDR_LG(4); break;
-        case 2: EDR_LG(2); break;
-        default: EDR_LG(1); break;
-    }
-#undef EDR_LG
-#undef EDR
+    with_vec(vec, [&](auto V) {
+        with_log2g(a.geom.log2g, [&](auto LG) { edge_dot_rows_kernel<decltype(V)::value, decltype(LG)::value><<<nb, 256, 0, stream>>>(a); });
+    });
     GNNMP_LAUNCH_CHECK("edge_dot_rows_kernel");
     return GNNMP_OK;
 }
@@ -270,21 +257,12 @@ int gnnmp_propagate_maxmin_grad_f32(gnnmp_graph_t *plan_t, const float *x, const
     a.dy = dy;
     a.dx = dx;
     a.D = (int)D;
-    uintptr_t m = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy);
-    int vec = pick_vec(D, x, dx);
-    if (vec == 4 && (m & 15)) vec = 1;
-    if (vec == 2 && (m & 7)) vec = 1;
+    const int vec = narrow_vec(pick_vec(D, x, dx), y, dy);
     a.geom = RowGeom{pick_log2g((D + vec - 1) / vec), 4, 0, 0};
-    const int G = 1 << a.geom.log2g;
-    const int lanes_needed = (int)((D + vec - 1) / vec);
-    const dim3 grid = row_grid(a.rows, a.geom, (lanes_needed + G - 1) / G);
-    switch (vec) {
-        case 4: maxmin_grad_kernel<4, 4><<<grid, 256, 0, stream>>>(a); break;
-        case 2: maxmin_grad_kernel<2, 4><<<grid, 256, 0, stream>>>(a); break;
-        default: maxmin_grad_kernel<1, 4><<<grid, 256, 0, stream>>>(a); break;
-    }
+    const dim3 grid = row_grid(a.rows, a.geom, feature_tiles(D, vec, a.geom.log2g));
+    with_vec(vec, [&](auto V) { maxmin_grad_kernel<decltype(V)::value, 4><<<grid, 256, 0, stream>>>(a); });
     GNNMP_LAUNCH_CHECK("maxmin_grad_kernel");
-    return run_combine_sum(plan_t, dx, D, stream);
+    return run_combine(plan_t, dx, D, GNNMP_SUM, stream);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <memory>
 #include <mutex>
 #include <stdint.h>
+#include <type_traits>
 #include "gnnmp.h"
 
 namespace gnnmp {
@@ -457,5 +458,50 @@ inline int pick_log2g(int64_t lanes_needed) {
     int l = 0;
     while ((1 << l) < lanes_needed && l < 6) ++l;
     return l;
+}
+// feature tiles (grid.y) of a row walk: groups of 1 << log2g lanes, vec features a lane, to cover D features
+inline int feature_tiles(int64_t D, int vec, int log2g) {
+    const int64_t G = (int64_t)1 << log2g;
+    return (int)(((D + vec - 1) / vec + G - 1) / G);
+}
+// pick_vec looks at two pointers; every further array a kernel touches with Vec<vec> accesses goes through here: vec if each
+// pointer is aligned to 4 * vec bytes (a null one is), 1 otherwise
+template <class... P>
+inline int narrow_vec(int vec, const P *...ptr) {
+    uintptr_t m = 0;
+    ((m |= reinterpret_cast<uintptr_t>(ptr)), ...);
+    return (m & (uintptr_t)(4 * vec - 1)) != 0 ? 1 : vec;
+}
+// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the V that equals the value, for switches whose
+// arms differ in nothing else.  Inside f: `constexpr int VEC = decltype(V)::value;`.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class F>
+inline auto with_vec(int vec, F &&f) {   // 4 | 2 | anything else: 1
+    switch (vec) {
+        case 4: return f(int_c<4>{});
+        case 2: return f(int_c<2>{});
+        default: return f(int_c<1>{});
+    }
+}
+template <class F>
+inline auto with_op(int op, F &&f) {   // OP_SUM | OP_MAX | anything else: OP_MIN
+    switch (op) {
+        case OP_SUM: return f(int_c<OP_SUM>{});
+        case OP_MAX: return f(int_c<OP_MAX>{});
+        default: return f(int_c<OP_MIN>{});
+    }
+}
+template <class F>
+inline auto with_log2g(int log2g, F &&f) {   // 0 .. 5 | anything else: 6 (a whole wave)
+    switch (log2g) {
+        case 0: return f(int_c<0>{});
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 3: return f(int_c<3>{});
+        case 4: return f(int_c<4>{});
+        case 5: return f(int_c<5>{});
+        default: return f(int_c<6>{});
+    }
 }
 }  // namespace gnnmp

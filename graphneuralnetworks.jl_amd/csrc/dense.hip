@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -531,30 +532,22 @@ __global__ void __launch_bounds__(256) dense_narrow_kernel(const float *__restri
 }
 
 // Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes.
-static int dense_narrow_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2,
-                            int64_t D2, int64_t ldw2, int w_layout, const float *bias, int act, float *out, int64_t N,
-                            int64_t Dout, hipStream_t stream) {
-    if (Dout > 8 || (D1 & 3) || (D2 & 3) || D1 > 4096 || D2 > 4096) return 1;
-    if ((reinterpret_cast<uintptr_t>(x1) & 15) || (D2 > 0 && (reinterpret_cast<uintptr_t>(x2) & 15))) return 1;
-    const int64_t sj1 = w_layout == 0 ? ldw1 : 1, sk1 = w_layout == 0 ? 1 : ldw1;
-    const int64_t sj2 = w_layout == 0 ? ldw2 : 1, sk2 = w_layout == 0 ? 1 : ldw2;
-    const unsigned nb = (unsigned)((N * 8 + 255) / 256);
-    if (Dout <= 2)
-        dense_narrow_kernel<2><<<nb, 256, 0, stream>>>(x1, W1, (int)D1, sj1, sk1, x2, W2, (int)D2, sj2, sk2, bias, act, out, N, (int)Dout);
-    else if (Dout <= 4)
-        dense_narrow_kernel<4><<<nb, 256, 0, stream>>>(x1, W1, (int)D1, sj1, sk1, x2, W2, (int)D2, sj2, sk2, bias, act, out, N, (int)Dout);
+static int dense_narrow_try(const DenseCall &c, hipStream_t stream) {
+    if (c.Dout > 8 || (c.D1 & 3) || (c.D2 & 3) || c.D1 > 4096 || c.D2 > 4096) return 1;
+    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (c.D2 > 0 && (reinterpret_cast<uintptr_t>(c.x2) & 15))) return 1;
+    const int64_t sj1 = c.w_layout == 0 ? c.ldw1 : 1, sk1 = c.w_layout == 0 ? 1 : c.ldw1;
+    const int64_t sj2 = c.w_layout == 0 ? c.ldw2 : 1, sk2 = c.w_layout == 0 ? 1 : c.ldw2;
+    const unsigned nb = (unsigned)((c.N * 8 + 255) / 256);
+    if (c.Dout <= 2)
+        dense_narrow_kernel<2><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
+    else if (c.Dout <= 4)
+        dense_narrow_kernel<4><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
     else
-        dense_narrow_kernel<8><<<nb, 256, 0, stream>>>(x1, W1, (int)D1, sj1, sk1, x2, W2, (int)D2, sj2, sk2, bias, act, out, N, (int)Dout);
+        dense_narrow_kernel<8><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
     GNNMP_LAUNCH_CHECK("dense_narrow_kernel");
     return GNNMP_OK;
 }
 
-int dense_split_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2,
-                    int64_t ldw2, int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout,
-                    hipStream_t stream);   // dense_split.hip
-int dense_t16_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2,
-                  int64_t ldw2, int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout,
-                  hipStream_t stream);   // dense_t16.hip
 }  // namespace gnnmp
 
 using namespace gnnmp;
@@ -570,19 +563,28 @@ extern "C" int gnnmp_dense_f32(const float *x1, const float *W1, int64_t D1, int
     if (act != GNNMP_ACT_IDENTITY && act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "dense: bad act %d", act);
     if (N == 0) return GNNMP_OK;
     if (!x1 || !W1 || !out || (D2 > 0 && (!x2 || !W2))) return fail(GNNMP_EINVAL, "dense: null pointer");
+    DenseCall c;
+    c.x1 = x1; c.W1 = W1; c.D1 = D1; c.ldw1 = ldw1;
+    c.x2 = x2; c.W2 = W2; c.D2 = D2; c.ldw2 = ldw2;
+    c.w_layout = w_layout;
+    c.bias = bias;
+    c.act = act;
+    c.out = out;
+    c.N = N;
+    c.Dout = Dout;
     {
         // round 3: the split-bf16 core (three exact bf16 planes per operand, six bf16 MFMAs per product: fp32-class accuracy at
         // 2.7x the fp32-MFMA rate) for every shape whose W image fits LDS
-        const int rc = dense_split_try(x1, W1, D1, ldw1, x2, W2, D2, ldw2, w_layout, bias, act, out, N, Dout, stream);
+        const int rc = dense_split_try(c, stream);
         if (rc != 1) return rc;
     }
     {
         // the shapes of the hot path (K a multiple of 4, <= 128 per segment): operands straight from HBM, 16x16x4 MFMAs
-        const int rc = dense_t16_try(x1, W1, D1, ldw1, x2, W2, D2, ldw2, w_layout, bias, act, out, N, Dout, stream);
+        const int rc = dense_t16_try(c, stream);
         if (rc != 1) return rc;
     }
     if (knob(KNOB_DENSE_GENERIC) == 0) {
-        const int rc = dense_narrow_try(x1, W1, D1, ldw1, x2, W2, D2, ldw2, w_layout, bias, act, out, N, Dout, stream);
+        const int rc = dense_narrow_try(c, stream);
         if (rc != 1) return rc;
     }
     DenseArgs a;

@@ -12,6 +12,7 @@
 // <= ~158 KB — DP = 128 up to K1 + K2 = 208 (SAGEConv 100 + 100), 64 up to 416, 32 up to 832; beyond that dense.hip's kernels.
 #include <algorithm>
 
+#include "launch.h"
 #include "msplit.h"
 
 namespace gnnmp {
@@ -286,55 +287,50 @@ static int launch_split(const SplitArgs &a, hipStream_t stream) {
     return staged ? launch_split_var<NCB, K0C, K1C, 4096>(a, stream) : launch_split_var<NCB, K0C, K1C, 0>(a, stream);
 }
 
-int dense_wreg_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2, int64_t ldw2,
-                   int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout, hipStream_t stream);   // dense_wreg.hip
-
 // Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (the caller falls back to the fp32-MFMA kernels).
-int dense_split_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2,
-                    int64_t ldw2, int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout,
-                    hipStream_t stream) {
+int dense_split_try(const DenseCall &c, hipStream_t stream) {
     if (knob(KNOB_DENSE_GENERIC) != 0 || knob(KNOB_DENSE_SPLIT) < 0) return 1;
-    const bool two = D2 > 0;
-    if ((D1 & 3) || (D2 & 3) || (Dout & 3) || Dout < 4 || N < 32) return 1;
+    const bool two = c.D2 > 0;
+    if ((c.D1 & 3) || (c.D2 & 3) || (c.Dout & 3) || c.Dout < 4 || c.N < 32) return 1;
     {
         // 256 outputs (SAGEConv(100 => 256)): W in registers, x through LDS once (dense_wreg.hip)
-        const int rc = dense_wreg_try(x1, W1, D1, ldw1, x2, W2, D2, ldw2, w_layout, bias, act, out, N, Dout, stream);
+        const int rc = dense_wreg_try(c, stream);
         if (rc != 1) return rc;
     }
     // column blocks are 32 wide: a Dout that pads by more than a tenth (100 -> 128) costs more MFMA work and a select per stored piece
     // than the fp32 16x16x4 kernel's 16-wide blocks (measured 2.4 M x 100 => 100: 625 us here, 549 us there)
-    if (((Dout + 31) & ~(int64_t)31) * 10 > Dout * 11) return 1;
-    if ((reinterpret_cast<uintptr_t>(x1) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return 1;
-    if (two && (reinterpret_cast<uintptr_t>(x2) & 15)) return 1;
-    const int kcat = (int)(D1 + D2), nkb = split_nkb(kcat);
+    if (((c.Dout + 31) & ~(int64_t)31) * 10 > c.Dout * 11) return 1;
+    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 15)) return 1;
+    if (two && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
+    const int kcat = (int)(c.D1 + c.D2), nkb = split_nkb(kcat);
     SplitArgs a;
-    a.x[0] = x1; a.x[1] = x2;
-    a.w.W[0] = W1; a.w.W[1] = two ? W2 : W1;
-    a.w.K[0] = (int)D1; a.w.K[1] = (int)D2;
-    a.w.sj[0] = w_layout == 0 ? ldw1 : 1; a.w.sk[0] = w_layout == 0 ? 1 : ldw1;
-    a.w.sj[1] = w_layout == 0 ? ldw2 : 1; a.w.sk[1] = w_layout == 0 ? 1 : ldw2;
-    a.bias = bias;
-    a.act = act;
-    a.out = out;
-    a.N = N;
-    a.Dout = (int)Dout;
+    a.x[0] = c.x1; a.x[1] = c.x2;
+    a.w.W[0] = c.W1; a.w.W[1] = two ? c.W2 : c.W1;
+    a.w.K[0] = (int)c.D1; a.w.K[1] = (int)c.D2;
+    a.w.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.w.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
+    a.w.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.w.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
+    a.bias = c.bias;
+    a.act = c.act;
+    a.out = c.out;
+    a.N = c.N;
+    a.Dout = (int)c.Dout;
     a.waves = 12;
     a.nkb = nkb;
     // the widest column tile whose image fits: fewer passes over x.  K known at compile time for the shapes of the configs.
     const size_t budget = 160 * 1024 - 1024;
-    if (Dout > 64 && split_img_bytes(kcat, 128) <= budget) {
+    if (c.Dout > 64 && split_img_bytes(kcat, 128) <= budget) {
         if (two) {
-            if (D1 == 16 && D2 == 16) return launch_split<4, 16, 16>(a, stream);     // GraphConv 16 + 16 => 128
-            if (D1 == 100 && D2 == 100) return launch_split<4, 100, 100>(a, stream);   // SAGEConv 100 + 100 => 256 (two column tiles)
+            if (c.D1 == 16 && c.D2 == 16) return launch_split<4, 16, 16>(a, stream);     // GraphConv 16 + 16 => 128
+            if (c.D1 == 100 && c.D2 == 100) return launch_split<4, 100, 100>(a, stream);   // SAGEConv 100 + 100 => 256 (two column tiles)
             return launch_split<4, 0, 1>(a, stream);
         }
-        if (D1 == 100) return launch_split<4, 100, 0>(a, stream);        // 100 => 100 | 128 (GCNConv, GATConv dense_x: products)
-        if (D1 == 128) return launch_split<4, 128, 0>(a, stream);        // 128 => 128 (arxiv)
+        if (c.D1 == 100) return launch_split<4, 100, 0>(a, stream);        // 100 => 100 | 128 (GCNConv, GATConv dense_x: products)
+        if (c.D1 == 128) return launch_split<4, 128, 0>(a, stream);        // 128 => 128 (arxiv)
         return launch_split<4, 0, 0>(a, stream);
     }
     if (split_img_bytes(kcat, 64) <= budget) {
         if (two) {
-            if (D1 == 128 && D2 == 128) return launch_split<2, 128, 128>(a, stream);   // GraphConv 128 + 128 => 128 (two column tiles)
+            if (c.D1 == 128 && c.D2 == 128) return launch_split<2, 128, 128>(a, stream);   // GraphConv 128 + 128 => 128 (two column tiles)
             return launch_split<2, 0, 1>(a, stream);
         }
         return launch_split<2, 0, 0>(a, stream);

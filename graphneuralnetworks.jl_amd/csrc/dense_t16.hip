@@ -12,6 +12,7 @@
 // (1 380 W of the 1 400 W socket limit), 89-126 TF by shape (profiles/README.md, round 2).
 #include <algorithm>
 
+#include "launch.h"
 #include "mfma16.h"
 
 namespace gnnmp {
@@ -148,30 +149,28 @@ static int launch_t16(const T16Args &a0, hipStream_t stream) {
 }
 
 // Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (the caller falls back to dense.hip's kernels).
-int dense_t16_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2,
-                  int64_t ldw2, int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout,
-                  hipStream_t stream) {
+int dense_t16_try(const DenseCall &c, hipStream_t stream) {
     if (knob(KNOB_DENSE_GENERIC) != 0) return 1;
-    const int nseg = D2 > 0 ? 2 : 1;
-    if ((D1 & 3) || (D2 & 3) || D1 > 128 || D2 > 128 || (Dout & 3) || Dout < 4) return 1;
-    if ((reinterpret_cast<uintptr_t>(x1) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return 1;
-    if (nseg > 1 && (reinterpret_cast<uintptr_t>(x2) & 15)) return 1;
-    if (N < 16) return 1;
+    const int nseg = c.D2 > 0 ? 2 : 1;
+    if ((c.D1 & 3) || (c.D2 & 3) || c.D1 > 128 || c.D2 > 128 || (c.Dout & 3) || c.Dout < 4) return 1;
+    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 15)) return 1;
+    if (nseg > 1 && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
+    if (c.N < 16) return 1;
     T16Args a;
-    a.x[0] = x1; a.W[0] = W1; a.K[0] = (int)D1;
-    a.x[1] = x2; a.W[1] = W2; a.K[1] = (int)D2;
-    a.sj[0] = w_layout == 0 ? ldw1 : 1; a.sk[0] = w_layout == 0 ? 1 : ldw1;
-    a.sj[1] = w_layout == 0 ? ldw2 : 1; a.sk[1] = w_layout == 0 ? 1 : ldw2;
+    a.x[0] = c.x1; a.W[0] = c.W1; a.K[0] = (int)c.D1;
+    a.x[1] = c.x2; a.W[1] = c.W2; a.K[1] = (int)c.D2;
+    a.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
+    a.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
     a.nseg = nseg;
-    a.bias = bias;
-    a.act = act;
-    a.out = out;
-    a.N = N;
-    a.Dout = (int)Dout;
+    a.bias = c.bias;
+    a.act = c.act;
+    a.out = c.out;
+    a.N = c.N;
+    a.Dout = (int)c.Dout;
     a.waves = 16;
     // column blocks of 16 per column tile: as few padded columns as the shape allows (100 -> 7 x 16 = 112, not 128)
-    const int cb = (int)((Dout + 15) / 16);
-    const int kq1 = (int)D1 / 4, kq2 = (int)D2 / 4;
+    const int cb = (int)((c.Dout + 15) / 16);
+    const int kq1 = (int)c.D1 / 4, kq2 = (int)c.D2 / 4;
     if (cb > 8 || cb == 8) {
         // 128-column tiles (grid.y of them): the shapes of the configs first, K known at compile time
         if (kq1 == 25 && kq2 == 0) return launch_t16<8, 7, 25, 0>(a, stream);     // GATConv dense_x 100 => 128

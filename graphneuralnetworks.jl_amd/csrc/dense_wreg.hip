@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "launch.h"
 #include "msplit.h"
 
 namespace gnnmp {
@@ -208,24 +209,23 @@ static int launch_wreg(const WregArgs &a, hipStream_t stream) {
 }
 
 // Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (dense_split_try goes on with its own kernels).
-int dense_wreg_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, const float *x2, const float *W2, int64_t D2, int64_t ldw2,
-                   int w_layout, const float *bias, int act, float *out, int64_t N, int64_t Dout, hipStream_t stream) {
+int dense_wreg_try(const DenseCall &c, hipStream_t stream) {
     if (knob(KNOB_VARIANT) & 64) return 1;                    // knob 19 bit 6: never (A/B runs)
-    if (Dout != WR_DP || N < ((knob(KNOB_VARIANT) & 512) ? 4096 : 32768) || N > (int64_t)INT32_MAX - 64) return 1;      // (knob 19 bit 9: tests)      // (row numbers of a tile are 32-bit)
-    const bool two = D2 > 0;
-    if ((reinterpret_cast<uintptr_t>(x1) & 15) || (reinterpret_cast<uintptr_t>(out) & 127)) return 1;
-    if (two && (reinterpret_cast<uintptr_t>(x2) & 15)) return 1;
+    if (c.Dout != WR_DP || c.N < ((knob(KNOB_VARIANT) & 512) ? 4096 : 32768) || c.N > (int64_t)INT32_MAX - 64) return 1;      // (knob 19 bit 9: tests)      // (row numbers of a tile are 32-bit)
+    const bool two = c.D2 > 0;
+    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 127)) return 1;
+    if (two && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
     WregArgs a;
-    a.x[0] = x1; a.x[1] = x2;
-    a.w.W[0] = W1; a.w.W[1] = two ? W2 : W1;
-    a.w.K[0] = (int)D1; a.w.K[1] = (int)D2;
-    a.w.sj[0] = w_layout == 0 ? ldw1 : 1; a.w.sk[0] = w_layout == 0 ? 1 : ldw1;
-    a.w.sj[1] = w_layout == 0 ? ldw2 : 1; a.w.sk[1] = w_layout == 0 ? 1 : ldw2;
-    a.bias = bias;
-    a.act = act;
-    a.out = out;
-    a.N = N;
-    a.Dout = (int)Dout;
+    a.x[0] = c.x1; a.x[1] = c.x2;
+    a.w.W[0] = c.W1; a.w.W[1] = two ? c.W2 : c.W1;
+    a.w.K[0] = (int)c.D1; a.w.K[1] = (int)c.D2;
+    a.w.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.w.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
+    a.w.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.w.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
+    a.bias = c.bias;
+    a.act = c.act;
+    a.out = c.out;
+    a.N = c.N;
+    a.Dout = (int)c.Dout;
     // Instantiated for the layer widths of the reference's examples and benchmarks (64, 100, 128 per segment; one segment up to 256): the
     // W planes of a wave's 32 columns take 12 VGPRs per 16 positions of the concatenated K — 96 (K = 128) to 192 (K = 256) of the 256 a
     // wave has at two waves a SIMD.  K = 228 and 256 (100 + 128, 128 + 128, 256) were compiled too and spill 22-34 registers: left to
@@ -233,7 +233,7 @@ int dense_wreg_try(const float *x1, const float *W1, int64_t D1, int64_t ldw1, c
     // microseconds, this kernel / dense_split): 100+100 1439 / 1578, 64+64 1006 / 1200, 64+100 1326 / 1626, 128+64 1514 / 1701, 200 1572 /
     // 1670 — and one segment of K <= 128 the other way round (64: 699 / 679, 100: 922 / 871, 128: 988 / 969: not instantiated); at
     // N = 5 000 the eight-wave blocks are too few (31 / 18): from 32 768 rows on.  Bit-identical to dense_split on every shape.
-#define GNNMP_WREG_CASE(K0, K1) if (D1 == K0 && D2 == K1) return launch_wreg<K0, K1>(a, stream)
+#define GNNMP_WREG_CASE(K0, K1) if (c.D1 == K0 && c.D2 == K1) return launch_wreg<K0, K1>(a, stream)
     GNNMP_WREG_CASE(100, 100);      // SAGEConv(100 => 256), GraphConv(100 => 256): BASELINE config 4
     GNNMP_WREG_CASE(64, 64);
     GNNMP_WREG_CASE(64, 100);

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "csr_reduce.h"
+#include "launch.h"
 #include "mfma16.h"
 #include "msplit.h"
 
@@ -616,14 +617,28 @@ static int dispatch_fused_cat(FusedCatArgs &a, int op, bool scaled, u32x4 *wimg,
     }
 }
 
-int run_reduce(gnnmp_graph_t *p, const int32_t *idx, int aggr, const float *x, const float *w, const float *ss,
-               const float *w_slot, const float *ss_slot, const float *sd, float *out, int64_t D, hipStream_t stream,
-               const float *emat, const float *rowsub, const float *gate_i, int gated, int act, int long_only, const float *bias,
-               int bias_relu, const float *addend, const float *mask_y);   // propagate.hip
-
 }  // namespace gnnmp
 
 using namespace gnnmp;
+
+// the split rows of a fused layer, ahead of the fused kernel: chunk partials + combine into the compact buffer agg_long
+static int reduce_long_rows(gnnmp_graph_t *p, int aggr, const float *xj, const float *w, const float *scale_src, const float *w_slot,
+                            const float *ss_slot, const float *scale_dst, float *agg_long, int64_t D, hipStream_t stream) {
+    if (p->n_long == 0) return GNNMP_OK;
+    ReduceCall c;
+    c.idx = p->col;
+    c.aggr = aggr;
+    c.x = xj;
+    c.w = w;
+    c.ss = scale_src;
+    c.w_slot = w_slot;
+    c.ss_slot = ss_slot;
+    c.sd = scale_dst;
+    c.out = agg_long;
+    c.D = D;
+    c.long_only = 1;
+    return run_reduce(p, c, stream);
+}
 
 extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj, const float *w, const float *scale_src,
                                     const float *w_slot, const float *ss_slot, const float *scale_dst, int64_t D,
@@ -660,11 +675,7 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
         if (int rc = ensure_workspace(p, wimg_at + wimg_floats + 4)) return rc;
         if (int rc = ensure_ticket(p, stream)) return rc;
         float *agg_long = p->ws + ((pc + 3) & ~(size_t)3);
-        if (p->n_long > 0) {
-            if (int rc = run_reduce(p, p->col, aggr, xj, w, scale_src, w_slot, ss_slot, scale_dst, agg_long, D, stream, nullptr,
-                                    nullptr, nullptr, 1, 0, 1, nullptr, 0, nullptr, nullptr))
-                return rc;
-        }
+        if (int rc = reduce_long_rows(p, aggr, xj, w, scale_src, w_slot, ss_slot, scale_dst, agg_long, D, stream)) return rc;
         FusedCatArgs a = {};
         ReduceArgs &r = a.r;
         r.rows = plan_rows(p); r.x = xj; r.w = w; r.ss = scale_src; r.w_slot = w_slot; r.ss_slot = ss_slot;
@@ -701,11 +712,7 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
     if (int rc = ensure_workspace(p, pc + pl + 4)) return rc;
     if (int rc = ensure_ticket(p, stream)) return rc;
     float *agg_long = p->ws + ((pc + 3) & ~(size_t)3);
-    if (p->n_long > 0) {
-        if (int rc = run_reduce(p, p->col, aggr, xj, w, scale_src, w_slot, ss_slot, scale_dst, agg_long, D, stream, nullptr,
-                                nullptr, nullptr, 1, 0, 1, nullptr, 0, nullptr, nullptr))
-            return rc;
-    }
+    if (int rc = reduce_long_rows(p, aggr, xj, w, scale_src, w_slot, ss_slot, scale_dst, agg_long, D, stream)) return rc;
     FusedArgs a = {};
     ReduceArgs &r = a.r;
     r.rows = plan_rows(p);

@@ -497,106 +497,135 @@ static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, 
 
 using namespace gnnmp;
 
-static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const float *Wx_src,
-                              const float *Wx_dst, const float *a, float negative_slope, float drop_p, uint64_t drop_seed,
-                              const float *stats, const float *dout, float *line, float *dsd, float *dss, float *dWx_src,
-                              float *dWx_dst, float *da, int64_t H, int64_t C, gnnmp_stream_t stream_, const float *outk = nullptr,
-                              const float *bias = nullptr, const float *oplus = nullptr, const float *pplus = nullptr) {
+// one call of GATConv's pullback: what the three exports below ask of gat_conv_grad_impl, by name
+struct GatGradCall {
+    const float *Wx_src = nullptr, *Wx_dst = nullptr, *a = nullptr;
+    float negative_slope = 0.0f;
+    float drop_p = 0.0f;
+    uint64_t drop_seed = 0;
+    const float *stats = nullptr, *dout = nullptr;
+    float *line = nullptr, *dsd = nullptr, *dss = nullptr, *dWx_src = nullptr, *dWx_dst = nullptr, *da = nullptr;
+    int64_t H = 0, C = 0;
+    // grad2 (after gnnmp_gat_conv_train_f32): the forward's out, its bias, o+ and P
+    const float *outk = nullptr, *bias = nullptr, *oplus = nullptr, *pplus = nullptr;
+};
+
+static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGradCall c, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (oplus && (!outk || !pplus || drop_p > 0.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad2: needs out, oplus and pplus of gnnmp_gat_conv_train_f32");
-    if (!(drop_p >= 0.0f && drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad: dropout probability %g outside [0, 1)", (double)drop_p);
+    if (c.oplus && (!c.outk || !c.pplus || c.drop_p > 0.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad2: needs out, oplus and pplus of gnnmp_gat_conv_train_f32");
+    if (!(c.drop_p >= 0.0f && c.drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad: dropout probability %g outside [0, 1)", (double)c.drop_p);
     if (!plan || !plan_t) return fail(GNNMP_EINVAL, "gat_conv_grad: null plan");
-    if (H <= 0 || C <= 0 || H * C > (1 << 20)) return fail(GNNMP_EINVAL, "gat_conv_grad: bad H/C");
+    if (c.H <= 0 || c.C <= 0 || c.H * c.C > (1 << 20)) return fail(GNNMP_EINVAL, "gat_conv_grad: bad H/C");
     if (plan_t->n_dst != plan->n_src || plan_t->n_src != plan->n_dst || plan_t->n_total != plan->n_total)
         return fail(GNNMP_EINVAL, "gat_conv_grad: plan_t is not the transpose of plan (%lld x %lld, %lld edges vs %lld x %lld, %lld)",
                     (long long)plan_t->n_dst, (long long)plan_t->n_src, (long long)plan_t->n_total,
                     (long long)plan->n_dst, (long long)plan->n_src, (long long)plan->n_total);
-    const bool same = !Wx_dst || Wx_dst == Wx_src;
-    if (same) Wx_dst = Wx_src;
+    const bool same = !c.Wx_dst || c.Wx_dst == c.Wx_src;
+    if (same) c.Wx_dst = c.Wx_src;
     if (same && plan->n_src != plan->n_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: bipartite plan needs Wx_dst");
-    if (!same && !dWx_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: separate Wx_dst needs dWx_dst");
-    if (same && dWx_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: dWx_dst given but Wx_dst is Wx_src (the target term is folded into dWx_src)");
+    if (!same && !c.dWx_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: separate Wx_dst needs dWx_dst");
+    if (same && c.dWx_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: dWx_dst given but Wx_dst is Wx_src (the target term is folded into dWx_src)");
     if (plan->n_dst == 0 && plan->n_src == 0) return GNNMP_OK;
-    if (!Wx_src || !a || !stats || !dout || !line || !dsd || !dss || !dWx_src)
+    if (!c.Wx_src || !c.a || !c.stats || !c.dout || !c.line || !c.dsd || !c.dss || !c.dWx_src)
         return fail(GNNMP_EINVAL, "gat_conv_grad: null pointer");
-    const int D = (int)(H * C);
-    int vec = pick_vec(D, Wx_src, dWx_src);
+    const int D = (int)(c.H * c.C);
     // every array read or written with Vec<VEC> enters the decision (grad2's out / oplus included: an under-aligned one narrows the
     // lanes like any other array, the header promises alignment for `line` only); dWx_dst is written by a scalar kernel
-    if (((reinterpret_cast<uintptr_t>(Wx_dst) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(outk) |
-          reinterpret_cast<uintptr_t>(oplus)) & (4 * vec - 1)) != 0) vec = 1;
-    if ((reinterpret_cast<uintptr_t>(line) & 15) != 0) return fail(GNNMP_EINVAL, "gat_conv_grad: line must be 16-byte aligned");
-    while (vec > 1 && (C % vec) != 0) vec >>= 1;
-    int lph = (int)(C / vec);
+    int vec = narrow_vec(pick_vec(D, c.Wx_src, c.dWx_src), c.Wx_dst, c.dout, c.outk, c.oplus);
+    if ((reinterpret_cast<uintptr_t>(c.line) & 15) != 0) return fail(GNNMP_EINVAL, "gat_conv_grad: line must be 16-byte aligned");
+    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
+    int lph = (int)(c.C / vec);
     const int lanes = D / vec;
-    if (H == 1 && lanes <= 64) {   // a single head may spill over idle lanes: they carry zeros
+    if (c.H == 1 && lanes <= 64) {   // a single head may spill over idle lanes: they carry zeros
         lph = 1;
         while (lph < lanes) lph <<= 1;
     }
     if (lanes > 64)
-        return fail(GNNMP_EUNSUPPORTED, "gat_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(H * C));
+        return fail(GNNMP_EUNSUPPORTED, "gat_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(c.H * c.C));
     // workspaces: chunk partials of each pass in that plan's workspace; the da partials reuse the forward plan's
     const int64_t Rd = std::max<int64_t>(256, (plan->n_dst + 2047) / 2048), Rs = std::max<int64_t>(256, (plan->n_src + 2047) / 2048);
     const size_t colsum_need = (size_t)std::max((plan->n_dst + Rd - 1) / Rd, (plan->n_src + Rs - 1) / Rs) * (size_t)D;
-    if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * (size_t)H * 4, da ? colsum_need : (size_t)0))) return rc;
+    if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * (size_t)c.H * 4, c.da ? colsum_need : (size_t)0))) return rc;
     if (plan_t->n_chunks > 0)
         if (int rc = ensure_workspace(plan_t, (size_t)plan_t->n_chunks * (size_t)(D + lanes))) return rc;
     GatBwdArgs g;
-    g.Wx_src = Wx_src;
-    g.Wx_dst = Wx_dst;
-    g.a = a;
-    g.dout = dout;
-    g.stats = stats;
-    g.line = line;
-    g.dsd = dsd;
-    g.dss = dss;
-    g.dWx = dWx_src;
+    g.Wx_src = c.Wx_src;
+    g.Wx_dst = c.Wx_dst;
+    g.a = c.a;
+    g.dout = c.dout;
+    g.stats = c.stats;
+    g.line = c.line;
+    g.dsd = c.dsd;
+    g.dss = c.dss;
+    g.dWx = c.dWx_src;
     g.fold_dst = same ? 1 : 0;
-    g.H = (int)H;
-    g.C = (int)C;
+    g.H = (int)c.H;
+    g.C = (int)c.C;
     g.D = D;
     g.geom = RowGeom{0, 1, 0, 0};
     while ((1 << g.geom.log2g) < lanes) ++g.geom.log2g;
     g.lph = lph_code(lph, g.geom.log2g);   // odd head widths sum their lanes one by one (common.h group_sum<0>)
-    g.slope = negative_slope;
-    g.drop = make_drop(drop_p, drop_seed);
-    g.outk = outk;
-    g.bias = bias;
-    g.oplus = oplus;
-    g.pplus = pplus;
-    if (drop_p > 0.0f) {   // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
-        if (vec == 4) return launch_gat_bwd<4, 0, true>(g, plan, plan_t, dWx_dst, da, stream);
-        if (vec == 2) return launch_gat_bwd<2, 0, true>(g, plan, plan_t, dWx_dst, da, stream);
-        return launch_gat_bwd<1, 0, true>(g, plan, plan_t, dWx_dst, da, stream);
+    g.slope = c.negative_slope;
+    g.drop = make_drop(c.drop_p, c.drop_seed);
+    g.outk = c.outk;
+    g.bias = c.bias;
+    g.oplus = c.oplus;
+    g.pplus = c.pplus;
+    if (c.drop_p > 0.0f) {   // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
+        return with_vec(vec, [&](auto V) { return launch_gat_bwd<decltype(V)::value, 0, true>(g, plan, plan_t, c.dWx_dst, c.da, stream); });
     }
     if (vec == 4) {   // the usual case (C a multiple of 4): compile-time lane count per head -> DPP butterflies
         switch (lph) {
-            case 1: return launch_gat_bwd<4, 1, false>(g, plan, plan_t, dWx_dst, da, stream);
-            case 2: return launch_gat_bwd<4, 2, false>(g, plan, plan_t, dWx_dst, da, stream);
-            case 4: return launch_gat_bwd<4, 4, false>(g, plan, plan_t, dWx_dst, da, stream);
-            case 8: return launch_gat_bwd<4, 8, false>(g, plan, plan_t, dWx_dst, da, stream);
-            case 16: return launch_gat_bwd<4, 16, false>(g, plan, plan_t, dWx_dst, da, stream);
-            default: return launch_gat_bwd<4, 0, false>(g, plan, plan_t, dWx_dst, da, stream);
+            case 1: return launch_gat_bwd<4, 1, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+            case 2: return launch_gat_bwd<4, 2, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+            case 4: return launch_gat_bwd<4, 4, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+            case 8: return launch_gat_bwd<4, 8, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+            case 16: return launch_gat_bwd<4, 16, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+            default: return launch_gat_bwd<4, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
         }
     }
-    if (vec == 2) return launch_gat_bwd<2, 0, false>(g, plan, plan_t, dWx_dst, da, stream);
-    return launch_gat_bwd<1, 0, false>(g, plan, plan_t, dWx_dst, da, stream);
+    if (vec == 2) return launch_gat_bwd<2, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+    return launch_gat_bwd<1, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+}
+
+// what the three exports share (their arguments in the exports' order)
+static GatGradCall gat_grad_call(const float *Wx_src, const float *Wx_dst, const float *a, float negative_slope, const float *stats,
+                                 const float *dout, float *line, float *dsd, float *dss, float *dWx_src, float *dWx_dst, float *da,
+                                 int64_t H, int64_t C) {
+    GatGradCall c;
+    c.Wx_src = Wx_src;
+    c.Wx_dst = Wx_dst;
+    c.a = a;
+    c.negative_slope = negative_slope;
+    c.stats = stats;
+    c.dout = dout;
+    c.line = line;
+    c.dsd = dsd;
+    c.dss = dss;
+    c.dWx_src = dWx_src;
+    c.dWx_dst = dWx_dst;
+    c.da = da;
+    c.H = H;
+    c.C = C;
+    return c;
 }
 
 extern "C" int gnnmp_gat_conv_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const float *Wx_src,
                                        const float *Wx_dst, const float *a, float negative_slope, const float *stats,
                                        const float *dout, float *line, float *dsd, float *dss, float *dWx_src,
                                        float *dWx_dst, float *da, int64_t H, int64_t C, gnnmp_stream_t stream) {
-    return gat_conv_grad_impl(plan, plan_t, Wx_src, Wx_dst, a, negative_slope, 0.0f, 0, stats, dout, line, dsd, dss, dWx_src, dWx_dst,
-                              da, H, C, stream);
+    return gat_conv_grad_impl(plan, plan_t, gat_grad_call(Wx_src, Wx_dst, a, negative_slope, stats, dout, line, dsd, dss, dWx_src, dWx_dst, da, H, C),
+                              stream);
 }
 extern "C" int gnnmp_gat_conv_grad_drop_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const float *Wx_src,
                                             const float *Wx_dst, const float *a, float negative_slope, float p, uint64_t seed,
                                             const float *stats, const float *dout, float *line, float *dsd, float *dss,
                                             float *dWx_src, float *dWx_dst, float *da, int64_t H, int64_t C,
                                             gnnmp_stream_t stream) {
-    return gat_conv_grad_impl(plan, plan_t, Wx_src, Wx_dst, a, negative_slope, p, seed, stats, dout, line, dsd, dss, dWx_src, dWx_dst,
-                              da, H, C, stream);
+    GatGradCall c = gat_grad_call(Wx_src, Wx_dst, a, negative_slope, stats, dout, line, dsd, dss, dWx_src, dWx_dst, da, H, C);
+    c.drop_p = p;
+    c.drop_seed = seed;
+    return gat_conv_grad_impl(plan, plan_t, c, stream);
 }
 
 /* The pullback after gnnmp_gat_conv_train_f32 (see gnnmp.h): the destination side is a node kernel on (Δ, out, o+, P), one edge pass
@@ -606,6 +635,10 @@ extern "C" int gnnmp_gat_conv_grad2_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan
                                         const float *oplus, const float *pplus, const float *dout, float *line, float *dsd, float *dss,
                                         float *dWx_src, float *dWx_dst, float *da, int64_t H, int64_t C, gnnmp_stream_t stream) {
     if (!out || !oplus || !pplus) return fail(GNNMP_EINVAL, "gat_conv_grad2: null out / oplus / pplus");
-    return gat_conv_grad_impl(plan, plan_t, Wx_src, Wx_dst, a, negative_slope, 0.0f, 0, stats, dout, line, dsd, dss, dWx_src, dWx_dst,
-                              da, H, C, stream, out, bias, oplus, pplus);
+    GatGradCall c = gat_grad_call(Wx_src, Wx_dst, a, negative_slope, stats, dout, line, dsd, dss, dWx_src, dWx_dst, da, H, C);
+    c.outk = out;
+    c.bias = bias;
+    c.oplus = oplus;
+    c.pplus = pplus;
+    return gat_conv_grad_impl(plan, plan_t, c, stream);
 }

@@ -645,100 +645,109 @@ static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
 
 template <int MODE>
 static int launch_mode(const GatFusedArgs &g, int vec, hipStream_t stream) {
-    switch (vec) {
-        case 4: return launch_gat_fused<4, MODE>(g, stream);
-        case 2: return launch_gat_fused<2, MODE>(g, stream);
-        default: return launch_gat_fused<1, MODE>(g, stream);
-    }
+    return with_vec(vec, [&](auto V) { return launch_gat_fused<decltype(V)::value, MODE>(g, stream); });
 }
 
 }  // namespace gnnmp
 
 using namespace gnnmp;
 
-static int attn_conv_impl(gnnmp_graph_t *plan, int mode, const float *Q, const float *K, const float *V, const float *a,
-                          float negative_slope, float scale, const float *bias, int act, float *out, float *stats,
-                          int64_t H, int64_t C, gnnmp_stream_t stream_, const float *escore = nullptr, float drop_p = 0.0f,
-                          uint64_t drop_seed = 0, float *oplus = nullptr, float *pplus = nullptr) {
+// one call of the one-pass attention layer: what the exports below ask of attn_conv_impl, by name
+struct AttnCall {
+    int mode = GNNMP_ATTN_GAT;
+    const float *Q = nullptr, *K = nullptr, *V = nullptr;   // Q null: K; V null: K
+    const float *a = nullptr;
+    float negative_slope = 0.0f, scale = 1.0f;
+    const float *bias = nullptr;
+    int act = GNNMP_ACT_IDENTITY;
+    float *out = nullptr;
+    float *stats = nullptr;
+    int64_t H = 0, C = 0;
+    const float *escore = nullptr;
+    float drop_p = 0.0f;
+    uint64_t drop_seed = 0;
+    float *oplus = nullptr, *pplus = nullptr;               // the training forward's extra outputs
+};
+
+static int attn_conv_impl(gnnmp_graph_t *plan, AttnCall c, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    const bool plus = oplus != nullptr;
-    if (plus && (mode != GNNMP_ATTN_GAT || !stats || !pplus || escore || drop_p > 0.0f))
+    const bool plus = c.oplus != nullptr;
+    if (plus && (c.mode != GNNMP_ATTN_GAT || !c.stats || !c.pplus || c.escore || c.drop_p > 0.0f))
         return fail(GNNMP_EINVAL, "gat_conv_train: needs stats, oplus and pplus; plain GAT logits only");
     if (!plan) return fail(GNNMP_EINVAL, "attn_conv: null plan");
-    if (!(drop_p >= 0.0f && drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv: dropout probability %g outside [0, 1)", (double)drop_p);
-    if (drop_p > 0.0f && ((mode != GNNMP_ATTN_GAT && mode != GNNMP_ATTN_GATV2) || escore))
+    if (!(c.drop_p >= 0.0f && c.drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv: dropout probability %g outside [0, 1)", (double)c.drop_p);
+    if (c.drop_p > 0.0f && ((c.mode != GNNMP_ATTN_GAT && c.mode != GNNMP_ATTN_GATV2) || c.escore))
         return fail(GNNMP_EUNSUPPORTED, "attention dropout: only on the GAT / GATv2 logits without edge features");
-    if (escore && plan->self_loops)
+    if (c.escore && plan->self_loops)
         return fail(GNNMP_EINVAL, "gat_conv: edge features and add_self_loops cannot be combined (GNNlib/src/layers/conv.jl:120)");
-    if (mode < GNNMP_ATTN_GAT || mode > GNNMP_ATTN_COS) return fail(GNNMP_EINVAL, "attn_conv: bad mode %d", mode);
-    if (H <= 0 || C <= 0 || H * C > (1 << 20)) return fail(GNNMP_EINVAL, "attn_conv: bad H/C");
-    if (mode == GNNMP_ATTN_COS && H != 1) return fail(GNNMP_EINVAL, "attn_conv: the cosine logit is single-head");
-    if (act != GNNMP_ACT_IDENTITY && act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "attn_conv: bad act %d", act);
+    if (c.mode < GNNMP_ATTN_GAT || c.mode > GNNMP_ATTN_COS) return fail(GNNMP_EINVAL, "attn_conv: bad mode %d", c.mode);
+    if (c.H <= 0 || c.C <= 0 || c.H * c.C > (1 << 20)) return fail(GNNMP_EINVAL, "attn_conv: bad H/C");
+    if (c.mode == GNNMP_ATTN_COS && c.H != 1) return fail(GNNMP_EINVAL, "attn_conv: the cosine logit is single-head");
+    if (c.act != GNNMP_ACT_IDENTITY && c.act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "attn_conv: bad act %d", c.act);
     if (plan->n_dst == 0) return GNNMP_OK;
-    if (!Q) Q = K;
-    if (!V) V = K;
-    if (mode != GNNMP_ATTN_DOT && V != K) return fail(GNNMP_EINVAL, "attn_conv: a separate value array needs mode DOT");
-    const bool needs_a = mode == GNNMP_ATTN_GAT || mode == GNNMP_ATTN_GATV2;
-    if (!out || (needs_a && !a) || !Q || (plan->n_total > 0 && !K)) return fail(GNNMP_EINVAL, "attn_conv: null pointer");
-    if (Q == K && plan->n_src != plan->n_dst) return fail(GNNMP_EINVAL, "attn_conv: bipartite plan needs a separate Q");
-    const int D = (int)(H * C);
-    int vec = pick_vec(D, K, out);
-    // every array the kernel touches with Vec<VEC> loads / stores enters the decision: K and out above, Q, V and the training forward's
-    // oplus here (bias, stats, pplus and escore are scalar accesses and need none)
-    if (((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(oplus)) & (4 * vec - 1)) != 0) vec = 1;
-    while (vec > 1 && (C % vec) != 0) vec >>= 1;
-    int lph = (int)(C / vec);
+    if (!c.Q) c.Q = c.K;
+    if (!c.V) c.V = c.K;
+    if (c.mode != GNNMP_ATTN_DOT && c.V != c.K) return fail(GNNMP_EINVAL, "attn_conv: a separate value array needs mode DOT");
+    const bool needs_a = c.mode == GNNMP_ATTN_GAT || c.mode == GNNMP_ATTN_GATV2;
+    if (!c.out || (needs_a && !c.a) || !c.Q || (plan->n_total > 0 && !c.K)) return fail(GNNMP_EINVAL, "attn_conv: null pointer");
+    if (c.Q == c.K && plan->n_src != plan->n_dst) return fail(GNNMP_EINVAL, "attn_conv: bipartite plan needs a separate Q");
+    const int D = (int)(c.H * c.C);
+    // every array the kernel touches with Vec<VEC> loads / stores enters the decision: K and out, Q, V and the training forward's
+    // oplus (bias, stats, pplus and escore are scalar accesses and need none)
+    int vec = narrow_vec(pick_vec(D, c.K, c.out), c.Q, c.V, c.oplus);
+    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
+    int lph = (int)(c.C / vec);
     const int lanes = D / vec;
     int log2g = 0;
     while ((1 << log2g) < lanes) ++log2g;   // one feature tile: the head butterfly needs the whole row in one group
-    if (H == 1 && lanes <= 64) lph = 1 << log2g;   // a single head may spill over idle lanes: they carry zeros
+    if (c.H == 1 && lanes <= 64) lph = 1 << log2g;   // a single head may spill over idle lanes: they carry zeros
     if (lanes > 64) {
-        if (mode != GNNMP_ATTN_GAT || stats || escore || drop_p > 0.0f || plus)
+        if (c.mode != GNNMP_ATTN_GAT || c.stats || c.escore || c.drop_p > 0.0f || plus)
             return fail(GNNMP_EUNSUPPORTED,
                         "attn_conv: the one-pass kernel needs a feature row that fits one wave (H*C = %lld lanes %d > 64)",
-                        (long long)(H * C), lanes);
+                        (long long)(c.H * c.C), lanes);
         // GAT rows wider than a wave: three-pass kernels on node scores
-        const size_t need = (size_t)(plan->n_dst + plan->n_src) * (size_t)H;
+        const size_t need = (size_t)(plan->n_dst + plan->n_src) * (size_t)c.H;
         if (int rc = ensure_workspace(plan, need)) return rc;
-        float *sdst = plan->ws, *ssrc = plan->ws + (size_t)plan->n_dst * (size_t)H;
-        if (int rc = gnnmp_gat_node_scores_f32(Q, a, sdst, nullptr, plan->n_dst, H, C, stream_)) return rc;
-        if (int rc = gnnmp_gat_node_scores_f32(K, a, nullptr, ssrc, plan->n_src, H, C, stream_)) return rc;
-        return gnnmp_gat_aggregate_f32(plan, K, sdst, ssrc, negative_slope, bias, act, out, nullptr, H, C, stream_);
+        float *sdst = plan->ws, *ssrc = plan->ws + (size_t)plan->n_dst * (size_t)c.H;
+        if (int rc = gnnmp_gat_node_scores_f32(c.Q, c.a, sdst, nullptr, plan->n_dst, c.H, c.C, stream_)) return rc;
+        if (int rc = gnnmp_gat_node_scores_f32(c.K, c.a, nullptr, ssrc, plan->n_src, c.H, c.C, stream_)) return rc;
+        return gnnmp_gat_aggregate_f32(plan, c.K, sdst, ssrc, c.negative_slope, c.bias, c.act, c.out, nullptr, c.H, c.C, stream_);
     }
     if (plan->n_chunks > 0) {
         if (int rc = ensure_workspace(plan, (size_t)plan->n_chunks * (size_t)(plus ? 2 * D + 3 * lanes : D + 2 * lanes))) return rc;
     }
     GatFusedArgs g;
-    g.oplus = oplus;
-    g.pplus = pplus;
+    g.oplus = c.oplus;
+    g.pplus = c.pplus;
     g.rows = plan_rows(plan);
     if (use_row_order(plan->n_src, D) && lanes <= 32) {   // two or more rows per wave: pair rows of equal length
         if (int rc = ensure_row_order(plan, stream)) return rc;
         g.rows.row_order = plan->row_order;
     }
-    g.Wx_src = K;
-    g.Wx_val = V;
-    g.Wx_dst = Q;
-    g.a = a;
-    g.escore = escore;
-    g.bias = bias;
-    g.out = out;
+    g.Wx_src = c.K;
+    g.Wx_val = c.V;
+    g.Wx_dst = c.Q;
+    g.a = c.a;
+    g.escore = c.escore;
+    g.bias = c.bias;
+    g.out = c.out;
     g.partial = plan->ws;
-    g.stats = stats;
-    g.H = (int)H;
-    g.C = (int)C;
+    g.stats = c.stats;
+    g.H = (int)c.H;
+    g.C = (int)c.C;
     g.D = D;
     g.n_src = (int)plan->n_src;
     g.geom = RowGeom{log2g, 4, 0, 0};
     g.lph = lph_code(lph, log2g);   // odd head widths (C = 7 classes, ...) sum their lanes one by one
-    g.act = act;
-    g.slope = negative_slope;
-    g.scale = scale;
+    g.act = c.act;
+    g.slope = c.negative_slope;
+    g.scale = c.scale;
     g.off24 = plan->n_src < (1 << 24) && D < (1 << 24) && (int64_t)plan->n_src * D < (1ll << 32);
-    g.drop = make_drop(drop_p, drop_seed);
+    g.drop = make_drop(c.drop_p, c.drop_seed);
     g.arrive = nullptr;
     g.spart = nullptr;
-    if (plan->n_long > 0 && use_fold() && (mode == GNNMP_ATTN_GAT && !escore && drop_p == 0.0f && !plus)) {   // (plain GAT only)
+    if (plan->n_long > 0 && use_fold() && (c.mode == GNNMP_ATTN_GAT && !c.escore && c.drop_p == 0.0f && !plus)) {   // (plain GAT only)
         const size_t NG = (size_t)(256 >> log2g);
         if (int rc = ensure_arrive(plan, (size_t)plan->n_long * (NG + 1),
                                    (size_t)plan->n_long * NG * (size_t)(plus ? 2 * D + 3 * lanes : D + 2 * lanes), stream))
@@ -746,10 +755,10 @@ static int attn_conv_impl(gnnmp_graph_t *plan, int mode, const float *Q, const f
         g.arrive = plan->arrive;
         g.spart = plan->spart;
     }
-    if (drop_p > 0.0f)
-        return mode == GNNMP_ATTN_GATV2 ? launch_mode<ATTN_GATV2_DROP>(g, vec, stream) : launch_mode<ATTN_GAT_DROP>(g, vec, stream);
+    if (c.drop_p > 0.0f)
+        return c.mode == GNNMP_ATTN_GATV2 ? launch_mode<ATTN_GATV2_DROP>(g, vec, stream) : launch_mode<ATTN_GAT_DROP>(g, vec, stream);
     if (plus) return launch_mode<ATTN_GAT_PLUS>(g, vec, stream);
-    switch (mode) {
+    switch (c.mode) {
         case GNNMP_ATTN_GATV2: return launch_mode<GNNMP_ATTN_GATV2>(g, vec, stream);
         case GNNMP_ATTN_DOT: return launch_mode<GNNMP_ATTN_DOT>(g, vec, stream);
         case GNNMP_ATTN_COS: return launch_mode<GNNMP_ATTN_COS>(g, vec, stream);
@@ -757,46 +766,78 @@ static int attn_conv_impl(gnnmp_graph_t *plan, int mode, const float *Q, const f
     }
 }
 
+// GATConv's exports: plain GAT logits on one projection (K = V = Wx_src, Q = Wx_dst)
+static AttnCall gat_call(const float *Wx_src, const float *Wx_dst, const float *a, float negative_slope, const float *bias, int act,
+                         float *out, float *stats, int64_t H, int64_t C) {
+    AttnCall c;
+    c.K = Wx_src;
+    c.Q = Wx_dst;
+    c.a = a;
+    c.negative_slope = negative_slope;
+    c.bias = bias;
+    c.act = act;
+    c.out = out;
+    c.stats = stats;
+    c.H = H;
+    c.C = C;
+    return c;
+}
+// the general form: any logit, separate Q / K / V
+static AttnCall attn_call(int mode, const float *Q, const float *K, const float *V, const float *a, float negative_slope, float scale,
+                          const float *bias, int act, float *out, float *stats, int64_t H, int64_t C) {
+    AttnCall c = gat_call(K, Q, a, negative_slope, bias, act, out, stats, H, C);
+    c.mode = mode;
+    c.V = V;
+    c.scale = scale;
+    return c;
+}
+
 extern "C" int gnnmp_gat_conv_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                   float negative_slope, const float *bias, int act, float *out, int64_t H, int64_t C,
                                   gnnmp_stream_t stream) {
-    return attn_conv_impl(plan, GNNMP_ATTN_GAT, Wx_dst, Wx_src, nullptr, a, negative_slope, 1.0f, bias, act, out, nullptr,
-                          H, C, stream);
+    return attn_conv_impl(plan, gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, nullptr, H, C), stream);
 }
 extern "C" int gnnmp_gat_conv_stats_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                         float negative_slope, const float *bias, int act, float *out, float *stats,
                                         int64_t H, int64_t C, gnnmp_stream_t stream) {
     if (!stats) return fail(GNNMP_EINVAL, "gat_conv_stats: null stats");
-    return attn_conv_impl(plan, GNNMP_ATTN_GAT, Wx_dst, Wx_src, nullptr, a, negative_slope, 1.0f, bias, act, out, stats, H,
-                          C, stream);
+    return attn_conv_impl(plan, gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, stats, H, C), stream);
 }
 /* the training forward: out, (m, den), and what lets the pullback skip its destination-side edge pass (see ATTN_GAT_PLUS above) */
 extern "C" int gnnmp_gat_conv_train_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                         float negative_slope, const float *bias, int act, float *out, float *stats, float *oplus,
                                         float *pplus, int64_t H, int64_t C, gnnmp_stream_t stream) {
     if (!stats || !oplus || !pplus) return fail(GNNMP_EINVAL, "gat_conv_train: null stats / oplus / pplus");
-    return attn_conv_impl(plan, GNNMP_ATTN_GAT, Wx_dst, Wx_src, nullptr, a, negative_slope, 1.0f, bias, act, out, stats, H, C, stream,
-                          nullptr, 0.0f, 0, oplus, pplus);
+    AttnCall c = gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, stats, H, C);
+    c.oplus = oplus;
+    c.pplus = pplus;
+    return attn_conv_impl(plan, c, stream);
 }
 extern "C" int gnnmp_gat_conv_edge_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                        const float *edge_score, float negative_slope, const float *bias, int act,
                                        float *out, int64_t H, int64_t C, gnnmp_stream_t stream) {
     if (!edge_score && plan && plan->n_edges > 0) return fail(GNNMP_EINVAL, "gat_conv_edge: null edge_score");
-    return attn_conv_impl(plan, GNNMP_ATTN_GAT, Wx_dst, Wx_src, nullptr, a, negative_slope, 1.0f, bias, act, out, nullptr,
-                          H, C, stream, edge_score);
+    AttnCall c = gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, nullptr, H, C);
+    c.escore = edge_score;
+    return attn_conv_impl(plan, c, stream);
 }
 extern "C" int gnnmp_gat_conv_drop_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                        float negative_slope, float p, uint64_t seed, const float *bias, int act, float *out,
                                        float *stats, int64_t H, int64_t C, gnnmp_stream_t stream) {
-    return attn_conv_impl(plan, GNNMP_ATTN_GAT, Wx_dst, Wx_src, nullptr, a, negative_slope, 1.0f, bias, act, out, stats, H, C,
-                          stream, nullptr, p, seed);
+    AttnCall c = gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, stats, H, C);
+    c.drop_p = p;
+    c.drop_seed = seed;
+    return attn_conv_impl(plan, c, stream);
 }
 
 extern "C" int gnnmp_attn_conv_drop_f32(gnnmp_graph_t *plan, int mode, const float *Q, const float *K, const float *V,
                                         const float *a, float negative_slope, float scale, float p, uint64_t seed,
                                         const float *bias, int act, float *out, float *stats, int64_t H, int64_t C,
                                         gnnmp_stream_t stream) {
-    return attn_conv_impl(plan, mode, Q, K, V, a, negative_slope, scale, bias, act, out, stats, H, C, stream, nullptr, p, seed);
+    AttnCall c = attn_call(mode, Q, K, V, a, negative_slope, scale, bias, act, out, stats, H, C);
+    c.drop_p = p;
+    c.drop_seed = seed;
+    return attn_conv_impl(plan, c, stream);
 }
 
 __global__ void __launch_bounds__(256) dropout_keep_kernel(DropArgs d, int64_t n, int H, uint8_t *keep) {
@@ -818,5 +859,5 @@ extern "C" int gnnmp_dropout_keep_u8(uint64_t seed, float p, int64_t n_edges, in
 extern "C" int gnnmp_attn_conv_f32(gnnmp_graph_t *plan, int mode, const float *Q, const float *K, const float *V,
                                    const float *a, float negative_slope, float scale, const float *bias, int act,
                                    float *out, float *stats, int64_t H, int64_t C, gnnmp_stream_t stream) {
-    return attn_conv_impl(plan, mode, Q, K, V, a, negative_slope, scale, bias, act, out, stats, H, C, stream);
+    return attn_conv_impl(plan, attn_call(mode, Q, K, V, a, negative_slope, scale, bias, act, out, stats, H, C), stream);
 }

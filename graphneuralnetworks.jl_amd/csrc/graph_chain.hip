@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "msplit.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -452,13 +453,6 @@ extern "C" int64_t gnnmp_graphconv_chain_scratch_floats(int64_t N, int n_layers,
         d = std::max(d, dims[l + 1]);
     }
     return N * (d0 + d1 + nout) + 16;
-}
-
-namespace gnnmp {
-int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_t *seg_ptr, int64_t G, const float *x, int n_layers,
-                     const int64_t *dims, const float *const *W_root, const float *const *W_agg, const float *const *bias,
-                     const int *act, int w_layout, int aggr, int pool_aggr, const float *W_head, const float *b_head, int64_t nout,
-                     float *out, hipStream_t stream);   // graph_chain2.hip
 }
 
 extern "C" int gnnmp_graphconv_chain_f32(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *jobs, const int64_t *seg_ptr, int64_t G, const float *x, int n_layers,

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "chain_pack.h"
+#include "launch.h"
 #include "msplit.h"
 #include "pool.h"
 

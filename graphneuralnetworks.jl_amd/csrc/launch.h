@@ -1,0 +1,78 @@
+// launch.h — every host function that is called across translation units, declared ONCE, and the request structs those
+// functions take.  The defining .hip and every caller include this header; a prototype is never copied into a .hip.
+// (What common.h declares — fail, knob, the ensure_* plan helpers — stays there: those are the library's plumbing.)
+#pragma once
+#include "common.h"
+
+namespace gnnmp {
+
+// ---- the row reduction (propagate.hip) --------------------------------------------------------------------------------------
+// One call of csr_rows_kernel (+ its combine).  Fields are named after what they become in ReduceArgs (csr_reduce.h), where
+// each one is documented; a call site sets only what it means.  A new optional input is a field here, a field in ReduceArgs
+// and one line in run_reduce.
+struct ReduceCall {
+    const int32_t *idx = nullptr;   // per slot, the row of x to read: plan->col (propagate) or plan->eid (scatter)
+    int aggr = GNNMP_SUM;
+    const float *x = nullptr;
+    const float *w = nullptr;
+    const float *ss = nullptr;
+    const float *w_slot = nullptr;
+    const float *ss_slot = nullptr;
+    const float *sd = nullptr;
+    float *out = nullptr;
+    int64_t D = 0;
+    const float *emat = nullptr;
+    const float *rowsub = nullptr;
+    const float *gate_i = nullptr;
+    int gated = 1;                  // the form gate_i selects (1 | 2); ignored without gate_i
+    int act = 0;
+    // reduce ONLY the split rows (their chunk virtual rows + the combine) and write row long_rows[r], finalised, to out[r] — a
+    // compact [n_long][D] buffer the fused kernel reads instead of walking those rows (the caller sized the workspace and
+    // passes out inside it)
+    int long_only = 0;
+    const float *bias = nullptr;
+    int bias_relu = 0;
+    const float *addend = nullptr;
+    const float *mask_y = nullptr;
+};
+// shared by propagate (idx = col) and scatter (idx = eid)
+int run_reduce(gnnmp_graph_t *p, const ReduceCall &c, hipStream_t stream);
+// softmax over the rows of a plan, in the reference's three steps or the one-pass kernel of softmax_rows.hip
+int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, hipStream_t stream);
+// fold plan->ws ([n_chunks][D] partials written by another kernel in the same virtual-row layout) into out's long rows;
+// aggr: GNNMP_MAX, anything else sums
+int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int aggr, hipStream_t stream);
+
+// ---- softmax_rows.hip ---------------------------------------------------------------------------------------------------------
+// GNNMP_OK if it ran, 1 if the shape is not one it takes (the caller runs the three-step kernels)
+int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, float *partial, float *mx, float *den,
+                     hipStream_t stream);
+
+// ---- the dense family (dense.hip -> dense_split.hip -> dense_wreg.hip, dense_t16.hip) ---------------------------------
+// gnnmp_dense_f32's arguments (gnnmp.h), validated, as its kernels' host paths pass them on.  Every *_try returns GNNMP_OK if
+// it launched, 1 if the shape is not one its kernel takes, or an error status.
+struct DenseCall {
+    const float *x1, *W1;
+    int64_t D1, ldw1;
+    const float *x2, *W2;
+    int64_t D2, ldw2;
+    int w_layout;
+    const float *bias;
+    int act;
+    float *out;
+    int64_t N, Dout;
+};
+int dense_split_try(const DenseCall &c, hipStream_t stream);
+int dense_wreg_try(const DenseCall &c, hipStream_t stream);
+int dense_t16_try(const DenseCall &c, hipStream_t stream);
+
+// ---- graph_chain2.hip -----------------------------------------------------------------------------------------------------------
+int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_t *seg_ptr, int64_t G, const float *x, int n_layers,
+                     const int64_t *dims, const float *const *W_root, const float *const *W_agg, const float *const *bias,
+                     const int *act, int w_layout, int aggr, int pool_aggr, const float *W_head, const float *b_head, int64_t nout,
+                     float *out, hipStream_t stream);
+
+// ---- plan.hip -------------------------------------------------------------------------------------------------------------------
+int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);
+
+}  // namespace gnnmp

@@ -391,11 +391,7 @@ int gnnmp_gather_f32(const float *x, const void *idx, int idx_bytes, int index_b
     const int log2g = pick_log2g((D + vec - 1) / vec);
     const int64_t threads = K << log2g;
     const unsigned nb = (unsigned)((threads + 255) / 256);
-    switch (vec) {
-        case 4: gather_kernel<4><<<nb, 256, 0, stream>>>(x, idx, idx_bytes, index_base, K, out, (int)D, log2g); break;
-        case 2: gather_kernel<2><<<nb, 256, 0, stream>>>(x, idx, idx_bytes, index_base, K, out, (int)D, log2g); break;
-        default: gather_kernel<1><<<nb, 256, 0, stream>>>(x, idx, idx_bytes, index_base, K, out, (int)D, log2g); break;
-    }
+    with_vec(vec, [&](auto V) { gather_kernel<decltype(V)::value><<<nb, 256, 0, stream>>>(x, idx, idx_bytes, index_base, K, out, (int)D, log2g); });
     GNNMP_LAUNCH_CHECK("gather_kernel");
     return GNNMP_OK;
 }
@@ -408,17 +404,14 @@ int gnnmp_edge_sub_f32(const float *xi, const float *xj, const void *s, const vo
     if (K < 0 || D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "edge_sub: bad size");
     if (K == 0 || D == 0) return GNNMP_OK;
     if (!xi || !xj || !s || !t || !out) return fail(GNNMP_EINVAL, "edge_sub: null pointer");
-    int vec = pick_vec(D, xi, out);
-    if ((reinterpret_cast<uintptr_t>(xj) & (4 * vec - 1)) != 0) vec = 1;
+    const int vec = narrow_vec(pick_vec(D, xi, out), xj);
     const int log2g = pick_log2g((D + vec - 1) / vec);
     const int64_t threads = K << log2g;
     const unsigned nb = (unsigned)((threads + 255) / 256);
     const int sw = xj_minus_xi ? 1 : 0;
-    switch (vec) {
-        case 4: edge_sub_kernel<4><<<nb, 256, 0, stream>>>(xi, xj, s, t, idx_bytes, index_base, K, sw, out, (int)D, log2g); break;
-        case 2: edge_sub_kernel<2><<<nb, 256, 0, stream>>>(xi, xj, s, t, idx_bytes, index_base, K, sw, out, (int)D, log2g); break;
-        default: edge_sub_kernel<1><<<nb, 256, 0, stream>>>(xi, xj, s, t, idx_bytes, index_base, K, sw, out, (int)D, log2g); break;
-    }
+    with_vec(vec, [&](auto V) {
+        edge_sub_kernel<decltype(V)::value><<<nb, 256, 0, stream>>>(xi, xj, s, t, idx_bytes, index_base, K, sw, out, (int)D, log2g);
+    });
     GNNMP_LAUNCH_CHECK("edge_sub_kernel");
     return GNNMP_OK;
 }
@@ -631,21 +624,13 @@ int gnnmp_segment_pool_f32(int aggr, const float *x, const void *seg_ids, int id
     const int64_t threads = G << log2g;
     const unsigned nb = (unsigned)((threads + 255) / 256);
     const int mean = aggr == GNNMP_MEAN;
-#define POOL_LAUNCH(V, O) \
-    segment_pool_kernel<V, O><<<nb, 256, 0, stream>>>(x, seg_ids, idx_bytes, index_base, out, (int)D, N, G, log2g, mean)
-#define POOL_OP(V)                                             \
-    do {                                                       \
-        if (aggr == GNNMP_MAX) POOL_LAUNCH(V, OP_MAX);         \
-        else if (aggr == GNNMP_MIN) POOL_LAUNCH(V, OP_MIN);    \
-        else POOL_LAUNCH(V, OP_SUM);                           \
-    } while (0)
-    switch (vec) {
-        case 4: POOL_OP(4); break;
-        case 2: POOL_OP(2); break;
-        default: POOL_OP(1); break;
-    }
-#undef POOL_OP
-#undef POOL_LAUNCH
+    const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
+    with_vec(vec, [&](auto V) {
+        with_op(op, [&](auto O) {
+            segment_pool_kernel<decltype(V)::value, decltype(O)::value>
+                <<<nb, 256, 0, stream>>>(x, seg_ids, idx_bytes, index_base, out, (int)D, N, G, log2g, mean);
+        });
+    });
     GNNMP_LAUNCH_CHECK("segment_pool_kernel");
     return GNNMP_OK;
 }
@@ -674,20 +659,12 @@ int gnnmp_segment_pool_ptr_f32(int aggr, const float *x, const int64_t *seg_ptr,
     const int64_t threads = G << log2g;
     const unsigned nb = (unsigned)((threads + 255) / 256);
     const int mean = aggr == GNNMP_MEAN;
-#define POOLP_LAUNCH(V, O) segment_pool_ptr_kernel<V, O><<<nb, 256, 0, stream>>>(x, seg_ptr, out, (int)D, G, log2g, mean)
-#define POOLP_OP(V)                                             \
-    do {                                                        \
-        if (aggr == GNNMP_MAX) POOLP_LAUNCH(V, OP_MAX);         \
-        else if (aggr == GNNMP_MIN) POOLP_LAUNCH(V, OP_MIN);    \
-        else POOLP_LAUNCH(V, OP_SUM);                           \
-    } while (0)
-    switch (vec) {
-        case 4: POOLP_OP(4); break;
-        case 2: POOLP_OP(2); break;
-        default: POOLP_OP(1); break;
-    }
-#undef POOLP_OP
-#undef POOLP_LAUNCH
+    const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
+    with_vec(vec, [&](auto V) {
+        with_op(op, [&](auto O) {
+            segment_pool_ptr_kernel<decltype(V)::value, decltype(O)::value><<<nb, 256, 0, stream>>>(x, seg_ptr, out, (int)D, G, log2g, mean);
+        });
+    });
     GNNMP_LAUNCH_CHECK("segment_pool_ptr_kernel");
     return GNNMP_OK;
 }

@@ -480,21 +480,15 @@ int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const fl
     const int64_t rows = alias ? plan->n_dst : 2 * plan->n_dst;
     const int64_t rows_per_block = (int64_t)(64 >> log2g) * a.waves;
     const unsigned nb = (unsigned)((rows + rows_per_block - 1) / rows_per_block);
-#define EDG(V, LG, NT) edge_dot_grad_kernel<V, LG, NT><<<nb, 256, 0, stream>>>(a)
-#define EDG_V(V)                                                                                                        \
-    if (nt == 4) EDG(V, 6, 4);                                                                                          \
-    else if (nt == 2) EDG(V, 6, 2);                                                                                     \
-    else switch (log2g) {                                                                                               \
-        case 0: EDG(V, 0, 1); break; case 1: EDG(V, 1, 1); break; case 2: EDG(V, 2, 1); break; case 3: EDG(V, 3, 1); break; \
-        case 4: EDG(V, 4, 1); break; case 5: EDG(V, 5, 1); break; default: EDG(V, 6, 1); break;                         \
-    }
-    switch (vec) {
-        case 4: EDG_V(4); break;
-        case 2: EDG_V(2); break;
-        default: EDG_V(1); break;
-    }
-#undef EDG_V
-#undef EDG
+    with_vec(vec, [&](auto V) {
+        constexpr int VEC = decltype(V)::value;
+        if (nt == 4)
+            edge_dot_grad_kernel<VEC, 6, 4><<<nb, 256, 0, stream>>>(a);
+        else if (nt == 2)
+            edge_dot_grad_kernel<VEC, 6, 2><<<nb, 256, 0, stream>>>(a);
+        else
+            with_log2g(log2g, [&](auto LG) { edge_dot_grad_kernel<VEC, decltype(LG)::value, 1><<<nb, 256, 0, stream>>>(a); });
+    });
     GNNMP_LAUNCH_CHECK("edge_dot_grad_kernel");
     return GNNMP_OK;
 }

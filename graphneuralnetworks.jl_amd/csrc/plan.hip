@@ -11,6 +11,7 @@
 
 
 #include "common.h"
+#include "launch.h"
 #include "pool.h"
 #include "scratch.h"
 #include "sort_scan.h"
@@ -50,8 +51,6 @@ int device_cus() {
     }
     return cus;
 }
-
-int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);
 
 int ensure_workspace(gnnmp_graph *p, size_t floats) { return grow(p->ws, p->ws_floats, floats, "hipMalloc(plan workspace)"); }
 

@@ -14,11 +14,10 @@
 #include <vector>
 
 #include "common.h"
+#include "launch.h"
 #include "pool.h"
 
 namespace gnnmp {
-
-int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);   // plan.hip
 
 // where a member's piece of its source plan lives
 struct MemberDesc {

@@ -16,6 +16,7 @@
 //     partials in chunk order.  The dominant kernel therefore touches every edge exactly once and has no tail.
 //   - block -> row-chunk mapping is XCD-aware (contiguous destination ranges per XCD / L2).
 #include "csr_reduce.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -225,12 +226,10 @@ __global__ void __launch_bounds__(256) nn_rows_kernel(const ReduceArgs a, const 
 template <int VEC, int OP, bool SCALED, int U, bool EMAT = false, bool EXPSUB = false, int GATED = 0>
 static int launch_reduce(const ReduceArgs &a0, hipStream_t stream) {
     ReduceArgs a = a0;
-    const int G = 1 << a.geom.log2g;
     int waves = knob(KNOB_BLOCK_WAVES);
     if (waves < 1 || waves > 4) waves = 4;
     a.geom.waves = waves;
-    const int lanes_needed = (a.D + VEC - 1) / VEC;
-    const int tiles = (lanes_needed + G - 1) / G;
+    const int tiles = feature_tiles(a.D, VEC, a.geom.log2g);
     const dim3 grid = row_grid(a.rows, a.geom, tiles, use_xcd_remap(a.n_src, a.D, row_blocks(a.rows, a.geom)));
     if (grid.x > 0) {
         // the plain propagate / scatter instances fold their split rows themselves (a.arrive set by run_reduce when it may)
@@ -291,15 +290,9 @@ static int dispatch_op(const ReduceArgs &a, int op, bool scaled, hipStream_t s) 
     }
 }
 
-// shared by propagate (idx = col) and scatter (idx = eid)
-int run_reduce(gnnmp_graph_t *p, const int32_t *idx, int aggr, const float *x, const float *w,
-               const float *ss, const float *w_slot, const float *ss_slot, const float *sd, float *out,
-               int64_t D, hipStream_t stream, const float *emat = nullptr, const float *rowsub = nullptr,
-               const float *gate_i = nullptr, int gated = 1, int act = 0, int long_only = 0, const float *bias = nullptr,
-               int bias_relu = 0, const float *addend = nullptr, const float *mask_y = nullptr) {
-    // long_only: reduce ONLY the split rows (their chunk virtual rows + the combine) and write row long_rows[r], finalised, to
-    // out[r] — a compact [n_long][D] buffer the fused kernel reads instead of walking those rows (the caller sized the
-    // workspace and passes out inside it)
+int run_reduce(gnnmp_graph_t *p, const ReduceCall &c, hipStream_t stream) {
+    const int64_t D = c.D;
+    const int long_only = c.long_only;
     if (p->n_dst == 0 || D == 0) return GNNMP_OK;
     if (long_only && p->n_long == 0) return GNNMP_OK;
     if (p->n_chunks > 0 && !long_only) {
@@ -308,68 +301,57 @@ int run_reduce(gnnmp_graph_t *p, const int32_t *idx, int aggr, const float *x, c
     ReduceArgs a;
     a.compact_long = long_only;
     a.rows = plan_rows(p);
-    a.rows.col = idx;
+    a.rows.col = c.idx;
     if (long_only) a.rows.n_rows = 0;
-    a.x = x;
-    a.w = w;
-    a.emat = emat;
-    a.rowsub = rowsub;
+    a.x = c.x;
+    a.w = c.w;
+    a.emat = c.emat;
+    a.rowsub = c.rowsub;
     a.rowden = nullptr;
     a.den_add = 0.0f;
-    a.gate_i = gate_i;
-    a.gated = gate_i ? gated : 0;
-    a.act = act;
-    a.ss = ss;
-    a.w_slot = w_slot;
-    a.ss_slot = ss_slot;
-    a.sd = sd;
-    a.out = out;
-    a.bias = bias;
-    a.bias_relu = bias_relu;
-    a.addend = addend;
-    a.mask_y = mask_y;
+    a.gate_i = c.gate_i;
+    a.gated = c.gate_i ? c.gated : 0;
+    a.act = c.act;
+    a.ss = c.ss;
+    a.w_slot = c.w_slot;
+    a.ss_slot = c.ss_slot;
+    a.sd = c.sd;
+    a.out = c.out;
+    a.bias = c.bias;
+    a.bias_relu = c.bias_relu;
+    a.addend = c.addend;
+    a.mask_y = c.mask_y;
     a.partial = p->ws;
     a.D = (int)D;
     a.n_src = (int)p->n_src;
-    a.mean = (aggr == GNNMP_MEAN);
+    a.mean = (c.aggr == GNNMP_MEAN);
     a.geom = RowGeom{0, 4, 0, 0};
     a.arrive = nullptr;
-    int vec = pick_vec(D, x, out);
-    if (addend && (reinterpret_cast<uintptr_t>(addend) & (4 * vec - 1)) != 0) vec = 1;
-    if (mask_y && (reinterpret_cast<uintptr_t>(mask_y) & (4 * vec - 1)) != 0) vec = 1;
-    if (emat && (reinterpret_cast<uintptr_t>(emat) & (4 * vec - 1)) != 0) vec = 1;
-    if (gate_i && (reinterpret_cast<uintptr_t>(gate_i) & (4 * vec - 1)) != 0) vec = 1;
+    const int vec = narrow_vec(pick_vec(D, c.x, c.out), c.addend, c.mask_y, c.emat, c.gate_i);
     a.geom.log2g = pick_log2g((D + vec - 1) / vec);
     // >= 2 rows per wave: pair rows of equal length — but only when an output row is whole 128-byte lines: out of index order,
     // rows of 400 bytes (D = 100) leave every line half written by one wave and finished by another, measured 4.75 -> 5.11 ms
-    if (!long_only && use_row_order(p->n_src, D) && a.geom.log2g <= 5 && idx == p->col && (D & 31) == 0 &&
-        (reinterpret_cast<uintptr_t>(out) & 127) == 0) {
+    if (!long_only && use_row_order(p->n_src, D) && a.geom.log2g <= 5 && c.idx == p->col && (D & 31) == 0 &&
+        (reinterpret_cast<uintptr_t>(c.out) & 127) == 0) {
         if (int rc = ensure_row_order(p, stream)) return rc;
         a.rows.row_order = p->row_order;
     }
-    const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
-    const bool scaled = w || ss || w_slot || ss_slot;
+    const int op = (c.aggr == GNNMP_MAX) ? OP_MAX : (c.aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
+    const bool scaled = c.w || c.ss || c.w_slot || c.ss_slot;
     a.spart = nullptr;
     if (p->n_long > 0 && use_fold()) {      // split rows folded inside the row kernel: arrival counters per (long row, feature tile, slice)
-        const int G = 1 << a.geom.log2g, NG = 256 >> a.geom.log2g;
-        const size_t tiles = (size_t)(((D + vec - 1) / vec + G - 1) / G);
+        const int NG = 256 >> a.geom.log2g;
+        const size_t tiles = (size_t)feature_tiles(D, vec, a.geom.log2g);
         if (int rc = ensure_arrive(p, (size_t)p->n_long * tiles * (size_t)(NG + 1), (size_t)p->n_long * (size_t)NG * (size_t)D, stream)) return rc;
         a.arrive = p->arrive;
         a.spart = p->spart;
     }
-    switch (vec) {
-        case 4: return dispatch_op<4>(a, op, scaled, stream);
-        case 2: return dispatch_op<2>(a, op, scaled, stream);
-        default: return dispatch_op<1>(a, op, scaled, stream);
-    }
+    return with_vec(vec, [&](auto V) { return dispatch_op<decltype(V)::value>(a, op, scaled, stream); });
 }
 
 // softmax over the rows of a plan in the reference's three steps (utils.jl:84-97 / :49-72): max_ = scatter(max, e, t),
 // den = scatter(+, exp.(e .- max_[t]), t) (edge order), alpha = num ./ den.  Every step is the balanced row-group walk
 // (chunked long rows), so a 17 000-edge hub costs what 17 000 edges cost, not a serial tail.
-int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, float *partial, float *mx, float *den,
-                     hipStream_t stream);  // softmax_rows.hip
-
 int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, hipStream_t stream) {
     if (p->n_dst == 0 || p->n_total == 0 || D == 0) return GNNMP_OK;
     const size_t nd = (size_t)p->n_dst * (size_t)D, pc = (size_t)p->n_chunks * (size_t)D;
@@ -378,9 +360,17 @@ int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float
     // narrow rows: one pass over the rows the plan does not split, a wave per chunk on those it does (softmax_rows.hip)
     const int rc1 = softmax_rows_try(p, e, alpha, D, den_add, p->ws, mx, den, stream);
     if (rc1 != 1) return rc1;
-    if (int rc = run_reduce(p, p->eid, GNNMP_MAX, e, nullptr, nullptr, nullptr, nullptr, nullptr, mx, D, stream)) return rc;
-    if (int rc = run_reduce(p, p->eid, GNNMP_SUM, e, nullptr, nullptr, nullptr, nullptr, nullptr, den, D, stream, nullptr, mx))
-        return rc;
+    ReduceCall c;
+    c.idx = p->eid;
+    c.x = e;
+    c.D = D;
+    c.aggr = GNNMP_MAX;
+    c.out = mx;
+    if (int rc = run_reduce(p, c, stream)) return rc;
+    c.aggr = GNNMP_SUM;
+    c.rowsub = mx;
+    c.out = den;
+    if (int rc = run_reduce(p, c, stream)) return rc;
     ReduceArgs a = {};
     a.rows = plan_rows(p);
     a.rows.col = p->eid;      // rows of e / alpha: by original edge position
@@ -390,21 +380,14 @@ int run_softmax(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float
     a.rowden = den;
     a.den_add = den_add;
     a.D = (int)D;
-    int vec = pick_vec(D, e, alpha);
+    const int vec = pick_vec(D, e, alpha);
     a.geom = RowGeom{pick_log2g((D + vec - 1) / vec), 4, 0, 0};
-    const int G = 1 << a.geom.log2g;
-    const int tiles = (int)(((D + vec - 1) / vec + G - 1) / G);
-    const dim3 grid = row_grid(a.rows, a.geom, tiles);
-    switch (vec) {
-        case 4: softmax_write_kernel<4, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
-        case 2: softmax_write_kernel<2, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
-        default: softmax_write_kernel<1, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); break;
-    }
+    const dim3 grid = row_grid(a.rows, a.geom, feature_tiles(D, vec, a.geom.log2g));
+    with_vec(vec, [&](auto V) { softmax_write_kernel<decltype(V)::value, 8><<<grid, 64 * a.geom.waves, 0, stream>>>(a); });
     GNNMP_LAUNCH_CHECK("softmax_write_kernel");
     return GNNMP_OK;
 }
 
-// fold plan->ws ([n_chunks][D] partial sums written by another kernel in the same virtual-row layout) into out's long rows
 int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int aggr, hipStream_t stream) {
     if (p->n_long == 0) return GNNMP_OK;
     ReduceArgs a = {};
@@ -414,26 +397,17 @@ int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int aggr, hipStream_t s
     a.D = (int)D;
     const int vec = pick_vec(D, p->ws, out);
     a.geom.log2g = pick_log2g((D + vec - 1) / vec);
-    const int G = 1 << a.geom.log2g;
-    const int tiles = (int)(((D + vec - 1) / vec + G - 1) / G);
-    dim3 grid((unsigned)a.rows.n_long, (unsigned)tiles);
-    if (aggr == GNNMP_MAX) {
-        switch (vec) {
-            case 4: csr_combine_kernel<4, OP_MAX><<<grid, 256, 0, stream>>>(a); break;
-            case 2: csr_combine_kernel<2, OP_MAX><<<grid, 256, 0, stream>>>(a); break;
-            default: csr_combine_kernel<1, OP_MAX><<<grid, 256, 0, stream>>>(a); break;
-        }
-    } else {
-        switch (vec) {
-            case 4: csr_combine_kernel<4, OP_SUM><<<grid, 256, 0, stream>>>(a); break;
-            case 2: csr_combine_kernel<2, OP_SUM><<<grid, 256, 0, stream>>>(a); break;
-            default: csr_combine_kernel<1, OP_SUM><<<grid, 256, 0, stream>>>(a); break;
-        }
-    }
+    dim3 grid((unsigned)a.rows.n_long, (unsigned)feature_tiles(D, vec, a.geom.log2g));
+    with_vec(vec, [&](auto V) {
+        constexpr int VEC = decltype(V)::value;
+        if (aggr == GNNMP_MAX)
+            csr_combine_kernel<VEC, OP_MAX><<<grid, 256, 0, stream>>>(a);
+        else
+            csr_combine_kernel<VEC, OP_SUM><<<grid, 256, 0, stream>>>(a);
+    });
     GNNMP_LAUNCH_CHECK("csr_combine_kernel");
     return GNNMP_OK;
 }
-int run_combine_sum(gnnmp_graph_t *p, float *out, int64_t D, hipStream_t stream) { return run_combine(p, out, D, GNNMP_SUM, stream); }
 
 // ---- degree / norm ------------------------------------------------------------------------------
 __global__ void degree_count_kernel(const uint32_t *rowptr, int64_t n, float *deg) {
@@ -496,9 +470,25 @@ __global__ void inv_sqrt_kernel(const float *deg, float *out, int64_t n) {
 
 using namespace gnnmp;
 
-static int check_aggr(int aggr, const char *who) {
+// What the propagate / scatter exports check first, in this order: the plan, aggr, D in [0, max_D], and the two arrays every one
+// of them needs — `in` where the plan has slots, and `out` (`io` names them in the message).  What only one export checks stays there.
+static int check_rows_call(const char *who, const gnnmp_graph_t *plan, int aggr, int64_t D, int64_t max_D, const float *in,
+                           const float *out, const char *io = "xj/out") {
+    if (!plan) return fail(GNNMP_EINVAL, "%s: null plan", who);
     if (aggr < GNNMP_SUM || aggr > GNNMP_MIN) return fail(GNNMP_EINVAL, "%s: bad aggr %d", who, aggr);
+    if (D < 0 || D > max_D) return fail(GNNMP_EINVAL, "%s: bad D %lld", who, (long long)D);
+    if (plan->n_dst > 0 && D > 0 && (!out || (!in && plan->n_total > 0))) return fail(GNNMP_EINVAL, "%s: null %s", who, io);
     return GNNMP_OK;
+}
+// a propagate over the plan's sources: what every export below starts its ReduceCall from
+static ReduceCall propagate_call(const gnnmp_graph_t *plan, int aggr, const float *xj, float *out, int64_t D) {
+    ReduceCall c;
+    c.idx = plan->col;
+    c.aggr = aggr;
+    c.x = xj;
+    c.out = out;
+    c.D = D;
+    return c;
 }
 
 extern "C" {
@@ -506,57 +496,53 @@ extern "C" {
 int gnnmp_propagate_f32(gnnmp_graph_t *plan, int msg, int aggr, const float *xj, const float *w,
                         const float *scale_src, const float *scale_dst, float *out, int64_t D,
                         gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate: null plan");
-    if (int rc = check_aggr(aggr, "propagate")) return rc;
+    if (int rc = check_rows_call("propagate", plan, aggr, D, 1 << 20, xj, out)) return rc;
     if (msg != GNNMP_COPY_XJ && msg != GNNMP_W_MUL_XJ) return fail(GNNMP_EINVAL, "propagate: bad msg %d", msg);
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "propagate: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!xj && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate: null xj/out");
     if (msg == GNNMP_W_MUL_XJ && !w && plan->n_edges > 0)
         return fail(GNNMP_EINVAL, "propagate: W_MUL_XJ needs w");
-    if (msg == GNNMP_COPY_XJ) w = nullptr;
-    return run_reduce(plan, plan->col, aggr, xj, w, scale_src, nullptr, nullptr, scale_dst, out, D,
-                      (hipStream_t)stream);
+    ReduceCall c = propagate_call(plan, aggr, xj, out, D);
+    if (msg == GNNMP_W_MUL_XJ) c.w = w;
+    c.ss = scale_src;
+    c.sd = scale_dst;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_propagate_emul_f32(gnnmp_graph_t *plan, int aggr, const float *xj, const float *e, float *out, int64_t D,
                              gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_emul: null plan");
-    if (int rc = check_aggr(aggr, "propagate_emul")) return rc;
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "propagate_emul: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!xj && plan->n_total > 0) || (!e && plan->n_edges > 0)))
-        return fail(GNNMP_EINVAL, "propagate_emul: null xj/e/out");
-    if (!e) return run_reduce(plan, plan->col, aggr, xj, nullptr, nullptr, nullptr, nullptr, nullptr, out, D, (hipStream_t)stream);
-    return run_reduce(plan, plan->col, aggr, xj, nullptr, nullptr, nullptr, nullptr, nullptr, out, D, (hipStream_t)stream, e);
+    if (int rc = check_rows_call("propagate_emul", plan, aggr, D, 1 << 20, xj, out, "xj/e/out")) return rc;
+    if (plan->n_dst > 0 && D > 0 && !e && plan->n_edges > 0) return fail(GNNMP_EINVAL, "propagate_emul: null xj/e/out");
+    ReduceCall c = propagate_call(plan, aggr, xj, out, D);
+    c.emat = e;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_propagate_gated_f32(gnnmp_graph_t *plan, int aggr, const float *gate_i, const float *bv_j, float *out, int64_t D,
                               gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_gated: null plan");
-    if (int rc = check_aggr(aggr, "propagate_gated")) return rc;
-    if (D < 0 || D > (1 << 19)) return fail(GNNMP_EINVAL, "propagate_gated: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || !gate_i || (!bv_j && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate_gated: null pointer");
-    return run_reduce(plan, plan->col, aggr, bv_j, nullptr, nullptr, nullptr, nullptr, nullptr, out, D, (hipStream_t)stream,
-                      nullptr, nullptr, gate_i);
+    if (int rc = check_rows_call("propagate_gated", plan, aggr, D, 1 << 19, bv_j, out, "pointer")) return rc;
+    if (plan->n_dst > 0 && D > 0 && !gate_i) return fail(GNNMP_EINVAL, "propagate_gated: null pointer");
+    ReduceCall c = propagate_call(plan, aggr, bv_j, out, D);
+    c.gate_i = gate_i;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_propagate_cg_f32(gnnmp_graph_t *plan, const float *fs_i, const float *fs_j, const float *fs_e, int act, float *out,
                            int64_t D, gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_cg: null plan");
+    if (int rc = check_rows_call("propagate_cg", plan, GNNMP_SUM, D, 1 << 19, fs_j, out, "pointer")) return rc;
     if (act < GNNMP_ACT_IDENTITY || act > GNNMP_ACT_TANH) return fail(GNNMP_EINVAL, "propagate_cg: bad act %d", act);
-    if (D < 0 || D > (1 << 19)) return fail(GNNMP_EINVAL, "propagate_cg: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || !fs_i || (!fs_j && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate_cg: null pointer");
-    return run_reduce(plan, plan->col, GNNMP_SUM, fs_j, nullptr, nullptr, nullptr, nullptr, nullptr, out, D, (hipStream_t)stream,
-                      fs_e, nullptr, fs_i, 2, act);
+    if (plan->n_dst > 0 && D > 0 && !fs_i) return fail(GNNMP_EINVAL, "propagate_cg: null pointer");
+    ReduceCall c = propagate_call(plan, GNNMP_SUM, fs_j, out, D);
+    c.emat = fs_e;
+    c.gate_i = fs_i;
+    c.gated = 2;
+    c.act = act;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_propagate_nn_f32(gnnmp_graph_t *p, int aggr, const float *xj, const float *we, float *out, int64_t Din, int64_t Dout,
                            gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!p) return fail(GNNMP_EINVAL, "propagate_nn: null plan");
-    if (int rc = check_aggr(aggr, "propagate_nn")) return rc;
+    if (aggr < GNNMP_SUM || aggr > GNNMP_MIN) return fail(GNNMP_EINVAL, "propagate_nn: bad aggr %d", aggr);
     if (Din <= 0 || Dout <= 0 || Din > (1 << 16) || Dout > (1 << 16)) return fail(GNNMP_EINVAL, "propagate_nn: bad size");
     if (p->n_dst == 0) return GNNMP_OK;
     if (!out || ((!xj || !we) && p->n_total > 0)) return fail(GNNMP_EINVAL, "propagate_nn: null pointer");
@@ -572,23 +558,14 @@ int gnnmp_propagate_nn_f32(gnnmp_graph_t *p, int aggr, const float *xj, const fl
     a.n_src = (int)p->n_src;
     a.mean = (aggr == GNNMP_MEAN);
     a.geom = RowGeom{pick_log2g(Dout), 4, 0, 0};
-    const int G = 1 << a.geom.log2g;
-    const int tiles = (int)((Dout + G - 1) / G);
+    const int tiles = feature_tiles(Dout, 1, a.geom.log2g);
     const dim3 grid = row_grid(a.rows, a.geom, tiles);
     const int op = (aggr == GNNMP_MAX) ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
-    switch (op) {
-        case OP_SUM: nn_rows_kernel<OP_SUM><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
-        case OP_MAX: nn_rows_kernel<OP_MAX><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
-        default: nn_rows_kernel<OP_MIN><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); break;
-    }
+    with_op(op, [&](auto O) { nn_rows_kernel<decltype(O)::value><<<grid, 64 * a.geom.waves, 0, stream>>>(a, we, (int)Din); });
     GNNMP_LAUNCH_CHECK("nn_rows_kernel");
     if (a.rows.n_long > 0) {
         dim3 cg((unsigned)a.rows.n_long, (unsigned)tiles);
-        switch (op) {
-            case OP_SUM: csr_combine_kernel<1, OP_SUM><<<cg, 256, 0, stream>>>(a); break;
-            case OP_MAX: csr_combine_kernel<1, OP_MAX><<<cg, 256, 0, stream>>>(a); break;
-            default: csr_combine_kernel<1, OP_MIN><<<cg, 256, 0, stream>>>(a); break;
-        }
+        with_op(op, [&](auto O) { csr_combine_kernel<1, decltype(O)::value><<<cg, 256, 0, stream>>>(a); });
         GNNMP_LAUNCH_CHECK("csr_combine_kernel");
     }
     return GNNMP_OK;
@@ -597,49 +574,47 @@ int gnnmp_propagate_nn_f32(gnnmp_graph_t *p, int aggr, const float *xj, const fl
 int gnnmp_propagate_slots_f32(gnnmp_graph_t *plan, int aggr, const float *xj, const float *w_slot,
                               const float *ss_slot, const float *scale_dst, float *out, int64_t D,
                               gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_slots: null plan");
-    if (int rc = check_aggr(aggr, "propagate_slots")) return rc;
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "propagate_slots: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!xj && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate_slots: null xj/out");
-    return run_reduce(plan, plan->col, aggr, xj, nullptr, nullptr, w_slot, ss_slot, scale_dst, out, D,
-                      (hipStream_t)stream);
+    if (int rc = check_rows_call("propagate_slots", plan, aggr, D, 1 << 20, xj, out)) return rc;
+    ReduceCall c = propagate_call(plan, aggr, xj, out, D);
+    c.w_slot = w_slot;
+    c.ss_slot = ss_slot;
+    c.sd = scale_dst;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_propagate_slots_act_f32(gnnmp_graph_t *plan, int aggr, const float *xj, const float *w_slot, const float *ss_slot,
                                   const float *scale_dst, const float *bias, int act, float *out, int64_t D,
                                   gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_slots_act: null plan");
-    if (int rc = check_aggr(aggr, "propagate_slots_act")) return rc;
+    if (int rc = check_rows_call("propagate_slots_act", plan, aggr, D, 1 << 20, xj, out)) return rc;
     if (act != GNNMP_ACT_IDENTITY && act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "propagate_slots_act: bad act %d", act);
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "propagate_slots_act: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!xj && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate_slots_act: null xj/out");
-    return run_reduce(plan, plan->col, aggr, xj, nullptr, nullptr, w_slot, ss_slot, scale_dst, out, D, (hipStream_t)stream, nullptr,
-                      nullptr, nullptr, 1, 0, 0, bias, act == GNNMP_ACT_RELU ? 1 : 0);
+    ReduceCall c = propagate_call(plan, aggr, xj, out, D);
+    c.w_slot = w_slot;
+    c.ss_slot = ss_slot;
+    c.sd = scale_dst;
+    c.bias = bias;
+    c.bias_relu = act == GNNMP_ACT_RELU ? 1 : 0;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 /* out = act'( addend + aggregate ): the tail of graph_conv's / sage_conv's pullback w.r.t. x in the row kernel's epilogue (gnnmp.h) */
 int gnnmp_propagate_add_mask_f32(gnnmp_graph_t *plan, int aggr, const float *xj, const float *scale_dst, const float *addend,
                                  const float *mask_y, float *out, int64_t D, gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "propagate_add_mask: null plan");
-    if (aggr != GNNMP_SUM && aggr != GNNMP_MEAN) return fail(GNNMP_EINVAL, "propagate_add_mask: aggr must be + or mean (got %d)", aggr);
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "propagate_add_mask: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!xj && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "propagate_add_mask: null xj/out");
-    return run_reduce(plan, plan->col, aggr, xj, nullptr, nullptr, nullptr, nullptr, scale_dst, out, D, (hipStream_t)stream, nullptr,
-                      nullptr, nullptr, 1, 0, 0, nullptr, 0, addend, mask_y);
+    const bool sum_or_mean = aggr == GNNMP_SUM || aggr == GNNMP_MEAN;   // (its own message for aggr, below)
+    if (int rc = check_rows_call("propagate_add_mask", plan, sum_or_mean ? aggr : GNNMP_SUM, D, 1 << 20, xj, out)) return rc;
+    if (!sum_or_mean) return fail(GNNMP_EINVAL, "propagate_add_mask: aggr must be + or mean (got %d)", aggr);
+    ReduceCall c = propagate_call(plan, aggr, xj, out, D);
+    c.sd = scale_dst;
+    c.addend = addend;
+    c.mask_y = mask_y;
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_scatter_f32(gnnmp_graph_t *plan, int aggr, const float *m, float *out, int64_t D,
                       gnnmp_stream_t stream) {
-    if (!plan) return fail(GNNMP_EINVAL, "scatter: null plan");
-    if (int rc = check_aggr(aggr, "scatter")) return rc;
-    if (D < 0 || D > (1 << 20)) return fail(GNNMP_EINVAL, "scatter: bad D %lld", (long long)D);
-    if (plan->n_dst > 0 && D > 0 && (!out || (!m && plan->n_total > 0)))
-        return fail(GNNMP_EINVAL, "scatter: null m/out");
-    return run_reduce(plan, plan->eid, aggr, m, nullptr, nullptr, nullptr, nullptr, nullptr, out, D,
-                      (hipStream_t)stream);
+    if (int rc = check_rows_call("scatter", plan, aggr, D, 1 << 20, m, out, "m/out")) return rc;
+    ReduceCall c = propagate_call(plan, aggr, m, out, D);
+    c.idx = plan->eid;      // rows of m: by original edge position
+    return run_reduce(plan, c, (hipStream_t)stream);
 }
 
 int gnnmp_degree_f32(gnnmp_graph_t *plan, const float *w, float *deg, gnnmp_stream_t stream_) {

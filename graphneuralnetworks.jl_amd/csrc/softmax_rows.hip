@@ -18,6 +18,7 @@
 // go chunk by chunk through softmax_chunk_kernel — a wave per chunk, edge-parallel loads — with the same partials and the
 // same combine kernels as the three-step path.
 #include "csr_reduce.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -404,7 +405,6 @@ static int launch_smx(const SmxArgs &a, hipStream_t stream) {
     return GNNMP_OK;
 }
 
-int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int op, hipStream_t stream);   // propagate.hip
 
 // softmax over the rows of a plan for narrow rows.  Returns GNNMP_OK if it ran, 1 if the row width is not one these kernels
 // take (the caller runs the three-step kernels instead).  partial: [n_chunks][D]; mx, den: [n_dst][D] (touched on split rows
@@ -433,30 +433,19 @@ int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, 
     // destinations per wave: 64, fewer on small inputs so that every CU has waves to run
     a.rw = 64;
     while (a.rw > 8 && ((int64_t)a.rows.n_rows + a.rw - 1) / a.rw < 16 * (int64_t)device_cus()) a.rw >>= 1;
-    int rc;
-    switch (vec) {
-        case 4: rc = launch_smx<4>(a, stream); break;
-        case 2: rc = launch_smx<2>(a, stream); break;
-        default: rc = launch_smx<1>(a, stream); break;
-    }
+    int rc = with_vec(vec, [&](auto V) { return launch_smx<decltype(V)::value>(a, stream); });
     if (rc != GNNMP_OK || p->n_chunks == 0) return rc;
     a.partial = partial;
     a.mx = mx;
     a.den = den;
-#define SMX_CHUNKS(MODE)                                                     \
-    switch (vec) {                                                           \
-        case 4: rc = launch_chunks<4, MODE>(a, stream); break;               \
-        case 2: rc = launch_chunks<2, MODE>(a, stream); break;               \
-        default: rc = launch_chunks<1, MODE>(a, stream); break;              \
-    }                                                                        \
-    if (rc != GNNMP_OK) return rc;
-    SMX_CHUNKS(0)
+    auto chunks = [&](auto MODE) {
+        return with_vec(vec, [&](auto V) { return launch_chunks<decltype(V)::value, decltype(MODE)::value>(a, stream); });
+    };
+    if ((rc = chunks(int_c<0>{})) != GNNMP_OK) return rc;
     if ((rc = run_combine(p, mx, D, GNNMP_MAX, stream)) != GNNMP_OK) return rc;
-    SMX_CHUNKS(1)
+    if ((rc = chunks(int_c<1>{})) != GNNMP_OK) return rc;
     if ((rc = run_combine(p, den, D, GNNMP_SUM, stream)) != GNNMP_OK) return rc;
-    SMX_CHUNKS(2)
-#undef SMX_CHUNKS
-    return GNNMP_OK;
+    return chunks(int_c<2>{});
 }
 
 }  // namespace gnnmp
