@@ -108,7 +108,10 @@ enum Knob {
                                // (dense launches + the step pointwise kernels, every out) — read by the host layer (gnnmp/layers_temporal.py)
     KNOB_EDGE_DOT_GRAD = 21,   // adjoint of the per-edge dot product (linkpred.hip): 0 = auto (the fused kernel for D <= 256), < 0 = two
                                // w_mul_xj propagates (plan and transposed plan) plus an add — read by the host (gnnmp/linkpred.py)
-    KNOB_COUNT = 22
+    KNOB_HETERO = 22,          // heterograph aggregation (hetero.hip): 0 = auto (one hetero_rows_kernel launch per layer, and HeteroGraphConv's
+                               // transform-first path), < 0 = the composition — propagate per relation, then the same kernel over identity
+                               // relations as the combiner: the A/B baseline — read by the host (gnnmp/hetero.py)
+    KNOB_COUNT = 23
 };
 int knob(int k);
 int device_cus();   // compute units of the current device, queried once (hipDeviceGetAttribute costs microseconds per call)

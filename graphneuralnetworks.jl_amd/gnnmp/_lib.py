@@ -49,9 +49,24 @@ SYMBOLS = (
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
+    "gnnmp_hetero_propagate_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
+
+
+HETERO_MAX_REL = 16                       # include/gnnmp.h: GNNMP_HETERO_MAX_REL
+
+
+class HeteroRel(ctypes.Structure):
+    """gnnmp_hetero_rel_t: one relation of a destination type (plan = NULL: an identity relation)"""
+    _fields_ = [("plan", ctypes.c_void_p), ("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("aggr", ctypes.c_int)]
+
+
+class HeteroDst(ctypes.Structure):
+    """gnnmp_hetero_dst_t: one destination type of a gnnmp_hetero_propagate_f32 call"""
+    _fields_ = [("out", ctypes.c_void_p), ("n_dst", ctypes.c_int64), ("combine", ctypes.c_int), ("n_rel", ctypes.c_int),
+                ("rels", ctypes.POINTER(HeteroRel))]
 
 
 class GnnmpError(RuntimeError):
@@ -185,6 +200,7 @@ def load():
         "gnnmp_edge_dot_grad_f32": [vp, vp, vp, vp, vp, vp, vp, i64, vp],
         "gnnmp_knn_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, i64, vp, i, i, i64, i, vp],
         "gnnmp_radius_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, f, vp, i, i, i64, i, vp],
+        "gnnmp_hetero_propagate_f32": [ctypes.POINTER(HeteroDst), i, i64, vp],
     }
     for name, args in sig.items():
         try:
@@ -279,6 +295,7 @@ def set_probe(p):
 
 KNOB_TGCN = 20                            # csrc/common.h: 0 = auto, < 0 = TGCN's per-step path
 KNOB_EDGE_DOT_GRAD = 21                   # csrc/common.h: 0 = auto, < 0 = the edge-dot adjoint as two propagates (gnnmp/linkpred.py)
+KNOB_HETERO = 22                          # csrc/common.h: 0 = auto, < 0 = heterograph aggregation composed from propagate (gnnmp/hetero.py)
 KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.hip g_knobs)
 _knobs = {}
 

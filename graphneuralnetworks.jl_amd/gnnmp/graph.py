@@ -322,6 +322,8 @@ class GNNGraph:
 def check_num_nodes(g: GNNGraph, x):
     if x is None:
         return True
+    if getattr(g, "is_hetero", False):     # GNNGraphs/src/gnnheterograph/utils.jl:1-12: (x_src, x_dst) against the relation's two node types
+        return g._check_num_nodes(x)
     if isinstance(x, dict):
         for v in x.values():
             check_num_nodes(g, v)
@@ -338,6 +340,8 @@ def check_num_nodes(g: GNNGraph, x):
 def check_num_edges(g: GNNGraph, e):
     if e is None:
         return True
+    if getattr(g, "is_hetero", False):     # gnnheterograph/utils.jl:14-18
+        return g._check_num_edges(e)
     if isinstance(e, dict):
         for v in e.values():
             check_num_edges(g, v)
@@ -354,12 +358,17 @@ def check_num_edges(g: GNNGraph, e):
 # ---------------------------------------------------------------------------------------------------------
 # queries
 # ---------------------------------------------------------------------------------------------------------
-def edge_index(g: GNNGraph):
-    """(s, t) — zero-copy for COO graphs (GNNGraphs/src/query.jl:12)"""
+def edge_index(g: GNNGraph, edge_t=None):
+    """(s, t) — zero-copy for COO graphs (GNNGraphs/src/query.jl:12); edge_index(g, edge_t) on a heterograph
+    (gnnheterograph/query.jl:9-10: without a type it raises on more than one relation, as `only` does)"""
+    if getattr(g, "is_hetero", False):
+        return g.edge_index(edge_t)
     return g.s, g.t
 
 
-def get_edge_weight(g: GNNGraph):
+def get_edge_weight(g: GNNGraph, edge_t=None):
+    if getattr(g, "is_hetero", False):
+        return g.get_edge_weight(edge_t)
     return g.w
 
 
@@ -392,10 +401,13 @@ def graph_indicator(g: GNNGraph, edges: bool = False):
 def degree(g: GNNGraph, T=None, dir: str = "out", edge_weight=True):
     """degree(g, T = nothing; dir = :out, edge_weight = true) — GNNGraphs/src/query.jl:314-331,355-369: same defaults.
 
+    degree(g, edge_t; dir) on a heterograph (gnnheterograph/query.jl:57-68): pass the edge type where T stands.
     edge_weight: True (use the graph's weights if any), False/None (count edges) or a weight vector.
     T: None follows the reference's typing (query.jl:336-345): the weights' element type (Float32) when weights are used,
     the index element type (Int64 / Int32) when edges are counted.  The count itself runs in Float32 on the device (the
     element type gcn_conv asks for, conv.jl:43,53-55) and is exact below 2^24 edges per node."""
+    if getattr(g, "is_hetero", False):
+        return g.degree(T, dir=dir)
     assert dir in ("in", "out", "both")
     if isinstance(edge_weight, torch.Tensor) or isinstance(edge_weight, (list, tuple)):
         w = _as_f32(edge_weight, g.device)

@@ -29,8 +29,8 @@
  *     the calls whose comment says that they synchronise (plan builds and the other graph prep: gnnmp_batch_coo,
  *     gnnmp_sort_edge_index, gnnmp_unique_append, gnnmp_induced_subgraph, gnnmp_sample_neighbors, gnnmp_rand_edge_split,
  *     gnnmp_negative_sample, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
- *     thread_local): every other export of the case table of tests/abi_cases.py, and gnnmp_graphconv_chain_f32 through the Python
- *     mirror.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
+ *     mirror, and gnnmp_hetero_propagate_f32 (tests/test_hetero.py).  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -931,6 +931,43 @@ int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int
                         int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
 int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float r, const void *graph_indicator,
                            int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Heterogeneous graphs: the aggregation of one layer over typed relations in ONE launch (csrc/hetero.hip).  HeteroGraphConv
+ * (GraphNeuralNetworks/src/layers/heteroconv.jl:57-86) applies one layer per relation (src_type, rel, dst_type) and folds the outputs per
+ * destination type, foldl(aggr, outs).  For every destination type d of the call and every row i < n_dst:
+ *     out_d[i][:] = foldl(combine_d, m_1[i], ..., m_R[i]),     m_r = what gnnmp_propagate_f32(plan_r, msg, aggr_r, x_r, w_r) returns
+ * (msg = W_MUL_XJ where w_r is given, else COPY_XJ; no scale vectors), relations in table order, the m_r never written: a lane group
+ * walks row i in each relation in turn, in ORIGINAL edge order, and keeps the running value in registers.  An empty row contributes the
+ * operator's identity (0 / 0 / -Inf / +Inf), MEAN divides by the row's count, exactly as gnnmp_propagate_f32 does.
+ *   gnnmp_hetero_rel_t  plan: the relation's plan (n_dst = the destination type's), x [n_src][D], w [n_edges] in original edge order or
+ *                       NULL, aggr: its own gnnmp_aggr.  plan = NULL is an IDENTITY relation: it contributes row i of x [n_dst][D] as
+ *                       it is (w is ignored; aggr must still be a gnnmp_aggr) — a layer's root term, or finished layer outputs to be combined.
+ *   gnnmp_hetero_dst_t  out [n_dst][D], combine: GNNMP_SUM | GNNMP_MAX | GNNMP_MIN (Base.max / Base.min as everywhere), n_rel >= 1 records.
+ * `dsts` and every `rels` are HOST arrays (the grouped-call form of gnnmp_graphconv_chain_f32's host tables of device pointers); out, x and
+ * w are device pointers.  The tables travel by value in the kernel arguments: the call neither allocates nor synchronises, uses no
+ * plan-owned scratch (plans are only read: two streams may share one), and may be recorded into a HIP graph without an eager call first.
+ * Refused before any HIP call: GNNMP_EINVAL for a NULL or empty table, D outside 1 .. 2^20, a NULL out / x that would be dereferenced,
+ * a bad combine / aggr, a plan whose n_dst is not the record's; GNNMP_EUNSUPPORTED for more than GNNMP_HETERO_MAX_REL relations in one
+ * call (all destination types together).  Rows of at most the plan's long-row threshold are bit-identical to the per-relation calls
+ * folded in order; a longer row is walked whole, in edge order (bit-identical to the sequential loop, slow for hubs — a caller with
+ * split rows composes gnnmp_propagate_f32 per relation and combines with identity relations).
+ * ---------------------------------------------------------------------------------------------- */
+#define GNNMP_HETERO_MAX_REL 16
+typedef struct {
+    const gnnmp_graph_t *plan;
+    const float *x;
+    const float *w;
+    int aggr;
+} gnnmp_hetero_rel_t;
+typedef struct {
+    float *out;
+    int64_t n_dst;
+    int combine;
+    int n_rel;
+    const gnnmp_hetero_rel_t *rels;
+} gnnmp_hetero_dst_t;
+int gnnmp_hetero_propagate_f32(const gnnmp_hetero_dst_t *dsts, int n_dsts, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
