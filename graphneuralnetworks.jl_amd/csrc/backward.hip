@@ -18,6 +18,7 @@
 //     on the transposed plan.
 #include "rowwalk.h"
 #include "launch.h"
+#include "maxmin_grad.h"
 
 namespace gnnmp {
 
@@ -158,32 +159,7 @@ __global__ void __launch_bounds__(256) maxmin_grad_kernel(const MaxMinGradArgs a
 #pragma unroll
     for (int q = 0; q < VEC; ++q) { xv[q] = 0.0f; acc[q] = 0.0f; }
     if (active) Vec<VEC>::load(a.x + (int64_t)row * a.D + f0, xv);
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
-        const uint32_t p = base + lig;
-        const int c = p < end ? a.rows.col[p] : 0;
-        const int n = (int)min((uint32_t)G, end - base);
-        for (int j = 0; j < n; j += U) {
-            float yv[U][VEC], dv[U][VEC];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int cj = __shfl(c, gbase + min(j + u, n - 1), 64);
-                if (active) {   // clamped, unconditional within the lane's activity: no per-element branch + wait
-                    Vec<VEC>::load(a.y + (int64_t)cj * a.D + f0, yv[u]);
-                    Vec<VEC>::load(a.dy + (int64_t)cj * a.D + f0, dv[u]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) { yv[u][q] = 0.0f; dv[u][q] = 0.0f; }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (j + u < n) {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) acc[q] = acc[q] + (xv[q] == yv[u][q] ? dv[u][q] : 0.0f);
-                }
-            }
-        }
-    }
+    maxmin_grad_range<VEC, U>(a.rows.col, a.y, a.dy, a.D, beg, end, lig, gbase, G, f0, active, xv, acc);
     if (active) Vec<VEC>::store((is_chunk ? a.partial + (int64_t)v * a.D : a.dx + (int64_t)row * a.D) + f0, acc);
 }
 

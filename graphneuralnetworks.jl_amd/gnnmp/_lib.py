@@ -49,7 +49,7 @@ SYMBOLS = (
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
-    "gnnmp_hetero_propagate_f32",
+    "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
@@ -67,6 +67,18 @@ class HeteroDst(ctypes.Structure):
     """gnnmp_hetero_dst_t: one destination type of a gnnmp_hetero_propagate_f32 call"""
     _fields_ = [("out", ctypes.c_void_p), ("n_dst", ctypes.c_int64), ("combine", ctypes.c_int), ("n_rel", ctypes.c_int),
                 ("rels", ctypes.POINTER(HeteroRel))]
+
+
+class HeteroRelGrad(ctypes.Structure):
+    """gnnmp_hetero_rel_grad_t: one relation that leaves a source type (plan_t = NULL: an identity / masked identity term)"""
+    _fields_ = [("plan_t", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("w", ctypes.c_void_p), ("sd", ctypes.c_void_p),
+                ("y", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+class HeteroSrc(ctypes.Structure):
+    """gnnmp_hetero_src_t: one source type of a gnnmp_hetero_propagate_grad_f32 call"""
+    _fields_ = [("dx", ctypes.c_void_p), ("x", ctypes.c_void_p), ("n_src", ctypes.c_int64), ("n_rel", ctypes.c_int),
+                ("rels", ctypes.POINTER(HeteroRelGrad))]
 
 
 class GnnmpError(RuntimeError):
@@ -201,6 +213,7 @@ def load():
         "gnnmp_knn_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, i64, vp, i, i, i64, i, vp],
         "gnnmp_radius_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, f, vp, i, i, i64, i, vp],
         "gnnmp_hetero_propagate_f32": [ctypes.POINTER(HeteroDst), i, i64, vp],
+        "gnnmp_hetero_propagate_grad_f32": [ctypes.POINTER(HeteroSrc), i, i64, vp],
     }
     for name, args in sig.items():
         try:

@@ -30,7 +30,8 @@
  *     gnnmp_sort_edge_index, gnnmp_unique_append, gnnmp_induced_subgraph, gnnmp_sample_neighbors, gnnmp_rand_edge_split,
  *     gnnmp_negative_sample, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
- *     mirror, and gnnmp_hetero_propagate_f32 (tests/test_hetero.py).  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
+ *     two without the eager call, they use no plan scratch.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -968,6 +969,54 @@ typedef struct {
     const gnnmp_hetero_rel_t *rels;
 } gnnmp_hetero_dst_t;
 int gnnmp_hetero_propagate_f32(const gnnmp_hetero_dst_t *dsts, int n_dsts, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The adjoint of the heterograph aggregation w.r.t. the node features, in ONE launch over all source types (csrc/hetero_backward.hip):
+ * the forward's shape, mirrored.  For every source type S of the call and every row j < n_src:
+ *     dx_S[j][:] = c_1[j] + ... + c_R[j]        (table order; the first term is copied, not added to zero)
+ * a lane group owns row j, walks it in each outgoing relation's TRANSPOSED plan (a plan built from (t, s): rows = source nodes, col =
+ * destination, slots in ORIGINAL edge order) and keeps the running sum in registers: no per-relation [n_src][D] matrix is written.
+ * Each record takes one of four modes:
+ *   linear           plan_t given, y NULL — the adjoint of + / mean, with or without edge weights:
+ *                    c[j] = sum over the slots p of row j, in edge order, of w[eid_p] * (dy[col_p] * sd[col_p]), every product rounded, sd
+ *                    first (the order of gnnmp_propagate_f32 with scale_src = sd); an absent w or sd is 1.0f.  mean: sd = 1 / count.
+ *   winners          plan_t and y given — the adjoint of max / min over copy_xj (NNlib: every tie receives the gradient):
+ *                    c[j][f] = sum over the slots p of row j of (x_S[j][f] == y[col_p][f] ? dy[col_p][f] : 0).  w or sd: GNNMP_EINVAL.
+ *   identity         plan_t NULL, y and out NULL — c[j] = dy[j] (dy is [n_src][D]): a layer's root term, a type that is its own source.
+ *   masked identity  plan_t NULL, y and out given ([n_src][D] each) — c[j][f] = (y[j][f] == out[j][f]) ? dy[j][f] : 0: the pullback of ONE
+ *                    term y of out = foldl(max | min, terms).  EVERY term that ties with the result receives the gradient.  That tie rule is
+ *                    this project's own, chosen to agree with the winners mode; how the reference's AD splits a tie of a fold of `max` is
+ *                    not pinned anywhere here (ties have measure zero for real-valued features).
+ *   gnnmp_hetero_rel_grad_t  plan_t, dy [n_dst][D] (identity: [n_src][D]), w [n_edges] original edge order or NULL, sd [n_dst] a factor per
+ *                            GATHERED row or NULL, y [n_dst][D] the relation's forward aggregate (identity: the term that entered the
+ *                            fold) or NULL, out [n_src][D] the fold's result (identity relations only) or NULL.
+ *   gnnmp_hetero_src_t       dx [n_src][D] (written in full), x [n_src][D] the forward input (read by winners records only; may be NULL
+ *                            without one), n_rel >= 1 records.
+ * `srcs` and every `rels` are HOST arrays; dx, x, dy, w, sd, y and out are device pointers.  As gnnmp_hetero_propagate_f32: the tables
+ * travel by value in the kernel arguments, the call neither allocates nor synchronises, uses no plan-owned scratch (plans are only read)
+ * and may be recorded into a HIP graph without an eager call first; a call whose n_src are all 0 launches nothing.  Refused before any
+ * HIP call: GNNMP_EINVAL for a NULL or empty table, D outside 1 .. 2^20, a NULL dx / x / dy that would be dereferenced, y together with w
+ * or sd, out without y (or with a plan), an identity record with y but no out, a plan whose height is not n_src; GNNMP_EUNSUPPORTED for
+ * more than GNNMP_HETERO_MAX_REL records in one call (all source types together).  A row longer than the plan's long-row threshold is
+ * walked whole, in edge order (slow for hubs — a caller with split rows composes gnnmp_propagate_f32 on the transposed plan /
+ * gnnmp_propagate_maxmin_grad_f32 per relation and sums with the forward export's identity relations).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const gnnmp_graph_t *plan_t;
+    const float *dy;
+    const float *w;
+    const float *sd;
+    const float *y;
+    const float *out;
+} gnnmp_hetero_rel_grad_t;
+typedef struct {
+    float *dx;
+    const float *x;
+    int64_t n_src;
+    int n_rel;
+    const gnnmp_hetero_rel_grad_t *rels;
+} gnnmp_hetero_src_t;
+int gnnmp_hetero_propagate_grad_f32(const gnnmp_hetero_src_t *srcs, int n_srcs, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64

@@ -4,6 +4,9 @@ process, A, B, A, B.  Two layers of measurement per shape:
     aggregate   gnnmp.hetero_propagate(copy_xj, +) over the relations: the kernel against the composition
     layer       HeteroGraphConv of GraphConv(D => Dout, no activation): the transform-first fused path against the general path —
                 this is the `Dout <= Din` gate of gnnmp/hetero.py, measured at Dout = D and Dout = D / 2
+    backward    gnnmp.hetero_propagate_grad over the same relations, + and mean: ONE hetero_grad_rows_kernel launch for all source
+                types (csrc/hetero_backward.hip) against the composition — a transposed propagate per relation, then the identity-relation
+                sum (`--only backward` / `--only forward` run one half)
 Shapes:
     few_large    2 node types, 3 relations of 2 M edges into 200 k rows each (users - items)
     many_small   1 destination type of 20 k rows with 12 incoming relations of 40 k edges, next to one of 2 M edges
@@ -86,6 +89,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--D", type=int, default=128)
+    ap.add_argument("--only", choices=("forward", "backward"), default=None)
     args = ap.parse_args()
     D = args.D
     out = {"tool": "bench_hetero", "D": D, "reps": args.reps, "device": torch.cuda.get_device_name(0), "shapes": {}}
@@ -101,20 +105,34 @@ def main():
         comp_bytes = kernel_bytes + sum(2 * 4 * D * r * g.num_nodes[t] for t, r in rows.items())
         rec = {"edges": E, "relations": len(g.etypes), "split_rows": int(sum(g.plan(et).n_long for et in g.etypes)),
                "kernel_algorithmic_MB": kernel_bytes / 1e6, "composition_algorithmic_MB": comp_bytes / 1e6}
-        run = lambda: gnnmp.hetero_propagate(g, x)      # noqa: E731
-        f, c = ab(run, run, args.reps, args.warmup)
-        rec["aggregate_ms"] = {"auto": f, "composition": c}
-        if rec["split_rows"]:
-            # the one-launch kernel walking the split rows whole (what the auto path avoids): called below the Python gate
-            outs = {t: torch.empty((g.num_nodes[t], D), device="cuda") for t in rows}
-            recs = [(outs[t], g.num_nodes[t], L.SUM, [(g.plan(et), x[et[0]], None, L.SUM) for et in g.etypes if et[2] == t]) for t in rows]
-            rec["aggregate_ms"]["kernel_forced"] = timed(lambda: hetero._hetero_call(recs, D), args.reps, args.warmup)
-        rec["aggregate_GBps"] = {"auto": kernel_bytes / f / 1e6, "composition": comp_bytes / c / 1e6}
-        for Dout in (D, D // 2):
-            model = gnnmp.HeteroGraphConv({et: gnnmp.GraphConv((D, Dout), seed=k) for k, et in enumerate(g.etypes)})
-            run = lambda: model(g, x)                   # noqa: E731
+        if args.only != "backward":
+            run = lambda: gnnmp.hetero_propagate(g, x)      # noqa: E731
             f, c = ab(run, run, args.reps, args.warmup)
-            rec[f"layer_Dout{Dout}_ms"] = {"auto": f, "general": c}
+            rec["aggregate_ms"] = {"auto": f, "composition": c}
+            if rec["split_rows"]:
+                # the one-launch kernel walking the split rows whole (what the auto path avoids): called below the Python gate
+                outs = {t: torch.empty((g.num_nodes[t], D), device="cuda") for t in rows}
+                recs = [(outs[t], g.num_nodes[t], L.SUM, [(g.plan(et), x[et[0]], None, L.SUM) for et in g.etypes if et[2] == t]) for t in rows]
+                rec["aggregate_ms"]["kernel_forced"] = timed(lambda: hetero._hetero_call(recs, D), args.reps, args.warmup)
+            rec["aggregate_GBps"] = {"auto": kernel_bytes / f / 1e6, "composition": comp_bytes / c / 1e6}
+            for Dout in (D, D // 2):
+                model = gnnmp.HeteroGraphConv({et: gnnmp.GraphConv((D, Dout), seed=k) for k, et in enumerate(g.etypes)})
+                run = lambda: model(g, x)                   # noqa: E731
+                f, c = ab(run, run, args.reps, args.warmup)
+                rec[f"layer_Dout{Dout}_ms"] = {"auto": f, "general": c}
+        if args.only != "forward":
+            # the adjoint w.r.t. x: Δ arrives at every destination type; a source row is finished over all its outgoing relations
+            dy = {t: torch.rand((g.num_nodes[t], D), generator=gen).cuda() for t in rows}
+            rec["split_rows_transposed"] = int(sum(g.plan(et, transposed=True).n_long for et in g.etypes))
+            outgoing = {}
+            for et in g.etypes:
+                outgoing[et[0]] = outgoing.get(et[0], 0) + 1
+            grad_bytes = (4 * D + 4) * E + sum(4 * D * g.num_nodes[s] for s in outgoing)
+            for aggr in ("+", "mean"):
+                run = lambda: gnnmp.hetero_propagate_grad(g, dy, aggr=aggr)      # noqa: E731
+                f, c = ab(run, run, args.reps, args.warmup)
+                rec[f"backward_{'sum' if aggr == '+' else aggr}_ms"] = {"auto": f, "composition": c}
+            rec["backward_algorithmic_MB"] = grad_bytes / 1e6
         out["shapes"][name] = rec
     print(json.dumps(out))
 
