@@ -1,6 +1,7 @@
 // sort_scan.hip — the two primitives graph preparation needs, hand-written for gfx950 (round 1 called rocPRIM for them):
 //   * a STABLE least-significant-digit radix sort (8-bit digits) of 32-bit keys with 32-bit payloads — the destination sort
-//     behind the plan (dst, edge position) and the row order — and of bare 64-bit keys (sort_edge_index's packed (s, t) pairs);
+//     behind the plan (dst, edge position) and the row order — of bare 64-bit keys (sort_edge_index's packed (s, t) pairs) and of
+//     64-bit keys with 32-bit payloads (coalesce.hip: packed pairs and the edge positions they came from);
 //   * an exclusive prefix sum of 32- or 64-bit integers (the digit-count tables of the sort, rowptr-like offset arrays).
 // Off the timed path (a plan is built once per graph), but part of the drop-in all the same.
 //
@@ -371,6 +372,10 @@ int radix_sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const uint
 }
 int radix_sort_keys_u64(const uint64_t *keys_in, uint64_t *keys_out, size_t n, int begin_bit, int end_bit, hipStream_t stream) {
     return radix_sort_impl<uint64_t, false>(keys_in, keys_out, nullptr, nullptr, n, begin_bit, end_bit, stream);
+}
+int radix_sort_pairs_u64(const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, size_t n,
+                         int begin_bit, int end_bit, hipStream_t stream) {
+    return radix_sort_impl<uint64_t, true>(keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, stream);
 }
 
 }  // namespace gnnmp

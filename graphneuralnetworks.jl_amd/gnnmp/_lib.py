@@ -50,6 +50,7 @@ SYMBOLS = (
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
+    "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
 )
@@ -79,6 +80,25 @@ class HeteroSrc(ctypes.Structure):
     """gnnmp_hetero_src_t: one source type of a gnnmp_hetero_propagate_grad_f32 call"""
     _fields_ = [("dx", ctypes.c_void_p), ("x", ctypes.c_void_p), ("n_src", ctypes.c_int64), ("n_rel", ctypes.c_int),
                 ("rels", ctypes.POINTER(HeteroRelGrad))]
+
+
+COALESCE_DIRECTED, COALESCE_MIRRORED, COALESCE_UNDIRECTED = 0, 1, 2      # include/gnnmp.h: gnnmp_coalesce_mode
+COMPACT_SELF_LOOPS, COMPACT_LIST, COMPACT_RANDOM = 0, 1, 2               # include/gnnmp.h: gnnmp_compact_rule
+
+
+class CoalesceJob(ctypes.Structure):
+    """gnnmp_coalesce_t: one gnnmp_coalesce_edges call (a host record of device pointers)"""
+    _fields_ = [("s", ctypes.c_void_p), ("t", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("index_base", ctypes.c_int),
+                ("n_edges", ctypes.c_int64), ("n_nodes", ctypes.c_int64), ("mode", ctypes.c_int), ("s_out", ctypes.c_void_p),
+                ("t_out", ctypes.c_void_p), ("colptr", ctypes.c_void_p), ("rowval", ctypes.c_void_p)]
+
+
+class CompactJob(ctypes.Structure):
+    """gnnmp_compact_t: one gnnmp_compact_edges call"""
+    _fields_ = [("s", ctypes.c_void_p), ("t", ctypes.c_void_p), ("w", ctypes.c_void_p), ("idx_bytes", ctypes.c_int),
+                ("index_base", ctypes.c_int), ("n_edges", ctypes.c_int64), ("rule", ctypes.c_int), ("remove", ctypes.c_void_p),
+                ("n_remove", ctypes.c_int64), ("p", ctypes.c_float), ("seed", ctypes.c_uint64), ("s_out", ctypes.c_void_p),
+                ("t_out", ctypes.c_void_p), ("w_out", ctypes.c_void_p), ("eid_out", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -214,6 +234,10 @@ def load():
         "gnnmp_radius_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, f, vp, i, i, i64, i, vp],
         "gnnmp_hetero_propagate_f32": [ctypes.POINTER(HeteroDst), i, i64, vp],
         "gnnmp_hetero_propagate_grad_f32": [ctypes.POINTER(HeteroSrc), i, i64, vp],
+        "gnnmp_coalesce_edges": [ctypes.POINTER(CoalesceJob), ctypes.POINTER(i64), vp],
+        "gnnmp_compact_edges": [ctypes.POINTER(CompactJob), ctypes.POINTER(i64), vp],
+        "gnnmp_has_multi_edges": [vp, vp, i, i, i64, ctypes.POINTER(i), vp],
+        "gnnmp_has_isolated_nodes": [vp, ctypes.POINTER(i), vp],
     }
     for name, args in sig.items():
         try:

@@ -28,7 +28,7 @@
  *     first (it grows the plan's scratch and opts the kernel into large LDS where it needs it; the exception above).  Not recordable:
  *     the calls whose comment says that they synchronise (plan builds and the other graph prep: gnnmp_batch_coo,
  *     gnnmp_sort_edge_index, gnnmp_unique_append, gnnmp_induced_subgraph, gnnmp_sample_neighbors, gnnmp_rand_edge_split,
- *     gnnmp_negative_sample, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
+ *     gnnmp_negative_sample, gnnmp_coalesce_edges, gnnmp_compact_edges, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
  *     two without the eager call, they use no plan scratch.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
@@ -315,8 +315,92 @@ int gnnmp_induced_subgraph(gnnmp_graph_t *plan, const int32_t *map, const void *
                            int index_base, int64_t n_nodes, int64_t *offsets, void *s_out, void *t_out,
                            void *eid_out, int64_t capacity, int64_t *total, gnnmp_stream_t stream);
 
+/* Edge coalescing (csrc/coalesce.hip) — the sort, mask and index map of remove_multi_edges(g; aggr), to_bidirected and to_unidirected
+ * (GNNGraphs/src/transform.jl:157-185, 495-529), which the reference runs on the CPU.  Coalescing parallel edges is a bipartite plan
+ * from the input edges to the output edges, and aggregating edge data over it is propagate(copy_xj, aggr): this call writes the output
+ * edge list and that plan's CSC arrays, gnnmp_plan_from_csc(colptr, rowval, n_src = n_edges, n_dst = *total) makes the plan without
+ * another sort, and gnnmp_propagate_f32(plan, GNNMP_COPY_XJ, aggr, edata) reduces [n_edges][D] edge data to [*total][D].
+ *   mode  GNNMP_COALESCE_DIRECTED    key (s, t) over the n_edges input edges                                        E' = n_edges
+ *         GNNMP_COALESCE_MIRRORED    the VIRTUAL list [s; t], [t; s] of to_bidirected (position p >= n_edges is edge p - n_edges
+ *                                    reversed); the concatenation and the doubled edge data `[e e]` are never materialised   E' = 2 n_edges
+ *         GNNMP_COALESCE_UNDIRECTED  key (min(s, t), max(s, t)), to_unidirected's encoding; the output edge is (lo, hi) itself.  The
+ *                                    reference decodes its triangular index with a Float64 sqrt (utils.jl:244), which is exact only
+ *                                    for small n; here nothing is encoded, so nothing is decoded.                     E' = n_edges
+ * The virtual positions 0 .. E' - 1 are sorted STABLY by key (the reference's sortperm is stable); a key larger than its predecessor
+ * starts an output edge.  The output is the distinct edges in ascending key order — lexicographic (s, t), the order of the reference's
+ * (s - 1) n + t — and it is sorted whether or not any duplicate existed.  Written through the job (all device memory):
+ *   s_out, t_out [0 .. *total)   the output edges, in the width and base of the inputs        (capacity E' each)
+ *   colptr [0 .. *total]          the first sorted slot of every output edge, in index_base, ending at E' + index_base   (capacity E' + 1)
+ *   rowval [0 .. E')              for every sorted slot, the row (in index_base) of the ORIGINAL edge data it came from: a virtual
+ *                                 position p >= n_edges is folded to p - n_edges, so the mirrored copy reads the same row
+ * and nothing else: no byte outside those ranges of any output.  *total is HOST memory.  Integer work only, no atomics on data:
+ * bit-exact against the reference's algorithm.  Refused before any HIP call: GNNMP_EINVAL for a NULL job or total, idx_bytes not 4 | 8,
+ * index_base not 0 | 1, an unknown mode, a negative size, a NULL pointer with n_edges > 0; GNNMP_EBOUNDS for n_nodes > 2^32 (indices
+ * must fit 32 bits, as for gnnmp_sort_edge_index) or E' >= 2^32 (the pair sort's value width).  An index outside 0 .. n_nodes - 1 found
+ * on the device is GNNMP_EBOUNDS too, with no output written.  n_edges = 0 returns GNNMP_OK with *total = 0 and touches nothing. */
+typedef enum { GNNMP_COALESCE_DIRECTED = 0, GNNMP_COALESCE_MIRRORED = 1, GNNMP_COALESCE_UNDIRECTED = 2 } gnnmp_coalesce_mode;
+typedef struct {
+    const void *s;
+    const void *t;
+    int idx_bytes;
+    int index_base;
+    int64_t n_edges;
+    int64_t n_nodes;
+    int mode;
+    void *s_out;
+    void *t_out;
+    void *colptr;
+    void *rowval;
+} gnnmp_coalesce_t;
+/* Synchronises the stream (graph prep). */
+int gnnmp_coalesce_edges(const gnnmp_coalesce_t *job, int64_t *total, gnnmp_stream_t stream);
+
+/* Stable stream compaction of an edge list: the edges that satisfy the rule, in their original order.
+ *   rule  GNNMP_COMPACT_SELF_LOOPS  keep s != t                          remove_self_loops(g)          transform.jl:49-64
+ *         GNNMP_COMPACT_LIST        keep the positions that are NOT in `remove` (n_remove device entries in idx_bytes / index_base;
+ *                                   a repeated position is harmless, one outside the edge list is GNNMP_EBOUNDS with no output
+ *                                   written)                              remove_edges(g, idx)          transform.jl:121-139
+ *         GNNMP_COMPACT_RANDOM      keep position e with probability 1 - p: kept when the 32 bits of gnnmp_dropout_keep_u8's hash of
+ *                                   (seed, e, h = 0) are >= floor(p 2^32) (p = 1 keeps nothing) — a pure function of (seed, e), so
+ *                                   the same seed gives the same graph whatever the launch shape; not Julia's RNG stream
+ *                                                                         remove_edges(g, p)            transform.jl:142-146
+ * Writes s_out, t_out, w_out (w and w_out both NULL, or both given: the kept weights) and eid_out — the kept positions, in index width
+ * and base: edge features are then taken with gnnmp_gather_f32(edata, eid_out, ...) — entries [0 .. *total) of each, capacity n_edges;
+ * nothing else is written.  *total is HOST memory.  Refused before any HIP call: GNNMP_EINVAL for a NULL job or total, bad idx_bytes /
+ * index_base / rule, a negative size, p outside [0, 1], w without w_out or the reverse, a NULL pointer that would be dereferenced;
+ * GNNMP_EBOUNDS for n_edges >= 2^32.  n_edges = 0 returns GNNMP_OK with *total = 0 and touches nothing. */
+typedef enum { GNNMP_COMPACT_SELF_LOOPS = 0, GNNMP_COMPACT_LIST = 1, GNNMP_COMPACT_RANDOM = 2 } gnnmp_compact_rule;
+typedef struct {
+    const void *s;
+    const void *t;
+    const float *w;
+    int idx_bytes;
+    int index_base;
+    int64_t n_edges;
+    int rule;
+    const void *remove;
+    int64_t n_remove;
+    float p;
+    uint64_t seed;
+    void *s_out;
+    void *t_out;
+    float *w_out;
+    void *eid_out;
+} gnnmp_compact_t;
+/* Synchronises the stream (graph prep). */
+int gnnmp_compact_edges(const gnnmp_compact_t *job, int64_t *total, gnnmp_stream_t stream);
+
+/* has_multi_edges(g) — GNNGraphs/src/query.jl:575-579: fewer distinct (s, t) pairs than edges, i.e. two equal neighbours among the
+ * sorted packed pairs; *result = 0 | 1 (host).  Indices must fit 32 bits (GNNMP_EBOUNDS otherwise).  Synchronises the stream. */
+int gnnmp_has_multi_edges(const void *s, const void *t, int idx_bytes, int index_base, int64_t n_edges, int *result,
+                          gnnmp_stream_t stream);
+/* has_isolated_nodes(g; dir) — GNNGraphs/src/query.jl:420-422: any(iszero, degree(g; dir)), i.e. any empty row of the plan (dir = :in
+ * the graph's plan, dir = :out the plan of the reversed edge index); *result = 0 | 1 (host).  The plan is only read.  Synchronises the
+ * stream. */
+int gnnmp_has_isolated_nodes(gnnmp_graph_t *plan, int *result, gnnmp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
- * Leaf ops: _gather / _scatter  (GNNGraphs/src/gatherscatter.jl:4,12-18)
+ * Leaf ops: _gather / _scatter (GNNGraphs/src/gatherscatter.jl:4,12-18)
  * ---------------------------------------------------------------------------------------------- */
 /* out[k][:] = x[idx[k]][:]  for k in [0,K)  — NNlib.gather; pure copy, bit-exact. */
 int gnnmp_gather_f32(const float *x, const void *idx, int idx_bytes, int index_base, int64_t K,
