@@ -51,8 +51,10 @@ SYMBOLS = (
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
+    "gnnmp_random_walk_pe_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
+    "gnnmp_debug_random_walk_pe_f32",
 )
 
 
@@ -99,6 +101,15 @@ class CompactJob(ctypes.Structure):
                 ("index_base", ctypes.c_int), ("n_edges", ctypes.c_int64), ("rule", ctypes.c_int), ("remove", ctypes.c_void_p),
                 ("n_remove", ctypes.c_int64), ("p", ctypes.c_float), ("seed", ctypes.c_uint64), ("s_out", ctypes.c_void_p),
                 ("t_out", ctypes.c_void_p), ("w_out", ctypes.c_void_p), ("eid_out", ctypes.c_void_p)]
+
+
+RWPE_TILE, RWPE_MAX_WALK = 16, 1024      # include/gnnmp.h: GNNMP_RWPE_TILE, GNNMP_RWPE_MAX_WALK
+
+
+class RwpeJob(ctypes.Structure):
+    """gnnmp_rwpe_t: one gnnmp_random_walk_pe_f32 call"""
+    _fields_ = [("w", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
+                ("walk_length", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -238,6 +249,8 @@ def load():
         "gnnmp_compact_edges": [ctypes.POINTER(CompactJob), ctypes.POINTER(i64), vp],
         "gnnmp_has_multi_edges": [vp, vp, i, i, i64, ctypes.POINTER(i), vp],
         "gnnmp_has_isolated_nodes": [vp, ctypes.POINTER(i), vp],
+        "gnnmp_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), vp],
+        "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
     }
     for name, args in sig.items():
         try:

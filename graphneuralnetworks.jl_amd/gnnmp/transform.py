@@ -1,4 +1,4 @@
-"""The transforms that clean up the edge list itself, on the device (csrc/coalesce.hip):
+"""The transforms that clean up the edge list itself, on the device (csrc/coalesce.hip), and the positional encodings (csrc/rwpe.hip):
 
   remove_self_loops     GNNGraphs/src/transform.jl:49-64
   remove_edges          GNNGraphs/src/transform.jl:121-146
@@ -7,6 +7,7 @@
   to_unidirected        GNNGraphs/src/transform.jl:517-529
   has_multi_edges       GNNGraphs/src/query.jl:575-579
   has_isolated_nodes    GNNGraphs/src/query.jl:420-422
+  random_walk_pe        GNNGraphs/src/transform.jl:975-990
 
 Coalescing parallel edges is a bipartite plan from the input edges to the output edges, and aggregating edge data over it is
 propagate(copy_xj, aggr): `coalesce_edges` returns the new graph together with an `EdgeCoalescing` that holds that plan, and the three
@@ -184,3 +185,35 @@ def has_isolated_nodes(g: GNNGraph, dir: str = "out") -> bool:
     res = ctypes.c_int(0)
     L.check(L.load().gnnmp_has_isolated_nodes(plan.handle, ctypes.byref(res), L.stream_ptr()))
     return bool(res.value)
+
+
+def random_walk_pe(g: GNNGraph, walk_length: int):
+    """random_walk_pe(g, walk_length): pe[c, k - 1] = (RW^k)[c, c] for k = 1 .. walk_length with RW = A * Diagonal(1 ./ outdegree), A
+    the (weighted, when g has weights) adjacency matrix — a Float32 tensor (num_nodes, walk_length), the memory of the reference's
+    (walk_length, num_nodes) matrix.  A batched g is walked member by member (block diagonal); nothing N x N is ever formed."""
+    if getattr(g, "is_hetero", False) or not isinstance(g, GNNGraph):
+        raise TypeError("random_walk_pe: expected a GNNGraph")
+    if isinstance(walk_length, bool) or not isinstance(walk_length, numbers.Integral):
+        raise TypeError(f"random_walk_pe: walk_length must be an integer, got {type(walk_length).__name__}")
+    walk_length = int(walk_length)
+    if not 1 <= walk_length <= L.RWPE_MAX_WALK:
+        raise ValueError(f"random_walk_pe: walk_length {walk_length} outside 1 .. {L.RWPE_MAX_WALK}")
+    out = torch.empty((g.num_nodes, walk_length), dtype=torch.float32, device=g.device)
+    if g.num_nodes == 0:
+        return out
+    sp = None
+    if g.num_graphs > 1 and g.graph_indicator is not None:
+        # the node offsets of the member graphs: a constant of the batch (gnnmp/utils.py caches the same array)
+        sp = g._cache.get("node_ptr")
+        if sp is None:
+            gi = g.graph_indicator
+            sp = torch.empty(g.num_graphs + 1, dtype=torch.int64, device=g.device)
+            L.check(L.load().gnnmp_segment_bounds(L.ptr(gi), gi.element_size(), g.index_base, g.num_nodes, g.num_graphs, L.ptr(sp),
+                                                  L.stream_ptr()))
+            g._cache["node_ptr"] = sp
+    job = L.RwpeJob(L.ptr(g.w), L.ptr(sp), 8, g.num_graphs if sp is not None else 1, walk_length, L.ptr(out))
+    rc = L.load().gnnmp_random_walk_pe_f32(g.plan_transposed().handle, ctypes.byref(job), L.stream_ptr())
+    if rc == L.EINVAL:
+        raise ValueError(L.load().gnnmp_last_error().decode())      # an edge between two member graphs, an indicator that is not sorted
+    L.check(rc)
+    return out

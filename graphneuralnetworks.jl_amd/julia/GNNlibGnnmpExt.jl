@@ -8,7 +8,7 @@
 # the hot path (gcn_conv, graph_conv / sage_conv through `propagate`, gat_conv) to the fused kernels.
 #
 # Julia is NOT available in the build container, so this file is written against the reference's sources but has never
-# been executed.  What IS executed is the C ABI it calls: tests/test_c_harness.py drives the same entry points with the same
+# been executed (that includes the newest method, random_walk_pe at the end of the file).  What IS executed is the C ABI it calls: tests/test_c_harness.py drives the same entry points with the same
 # argument conventions from a plain C program that owns its memory through hipMalloc (no torch anywhere), and
 # graphneuralnetworks.jl_amd/gnnmp/ is the tested mirror of every wrapper below.
 #
@@ -987,6 +987,37 @@ function GNNGraphs.sort_edge_index(u::ROCVector{I}, v::ROCVector{I}) where {I <:
                                                 length(u)::Int64, devptr(uo)::Ptr{Cvoid}, devptr(vo)::Ptr{Cvoid},
                                                 stream_ptr()::Ptr{Cvoid})::Cint)
     return uo, vo
+end
+
+# ---- random-walk positional encodings (GNNGraphs/src/transform.jl:975-990) -------------------------------------------------------------
+# The reference multiplies N x N matrices and keeps their diagonals; the library walks every member graph of a batch inside LDS
+# (gnnmp.h: gnnmp_random_walk_pe_f32).  The job record is gnnmp_rwpe_t, field for field.  (walk_length, num_nodes) column-major is the
+# library's [N][walk_length].  Like the rest of this file: written against the reference's sources, never executed.
+struct RwpeJob
+    w::Ptr{Cvoid}
+    graph_ptr::Ptr{Cvoid}
+    idx_bytes::Cint
+    n_graphs::Int64
+    walk_length::Int64
+    out::Ptr{Cvoid}
+end
+# A method of the reference's own function, random_walk_pe(g::GNNGraph, walk_length::Int) (transform.jl:975): imported by name, so the
+# definition below extends it; graphs that are not on the device go on to the reference's method.
+import GNNGraphs: random_walk_pe
+function random_walk_pe(g::GNNGraph{<:COO_T}, walk_length::Int)
+    s, _ = edge_index(g)
+    s isa ROCVector || return invoke(random_walk_pe, Tuple{GNNGraph, Int}, g, walk_length)
+    out = ROCMatrix{Float32}(undef, walk_length, g.num_nodes)
+    g.num_nodes == 0 && return out
+    w = get_edge_weight(g)
+    w = w === nothing ? nothing : Float32.(w)
+    sp = g.num_graphs > 1 ? segment_bounds(g) : nothing
+    p = plan(g; transposed = true)
+    job = Ref(RwpeJob(devptr(w), devptr(sp), Cint(8), Int64(sp === nothing ? 1 : g.num_graphs), Int64(walk_length), devptr(out)))
+    GC.@preserve w sp out job begin
+        check(@ccall libgnnmp.gnnmp_random_walk_pe_f32(p.handle::Ptr{Cvoid}, job::Ptr{Cvoid}, stream_ptr()::Ptr{Cvoid})::Cint)
+    end
+    return out
 end
 
 end # module

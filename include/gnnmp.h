@@ -399,6 +399,40 @@ int gnnmp_has_multi_edges(const void *s, const void *t, int idx_bytes, int index
  * stream. */
 int gnnmp_has_isolated_nodes(gnnmp_graph_t *plan, int *result, gnnmp_stream_t stream);
 
+/* random_walk_pe(g, walk_length) — GNNGraphs/src/transform.jl:975-990: the random-walk positional encodings of every node,
+ *   A = adjacency_matrix(g, Float32; dir = :out)   A[i, j] = the summed weights of the edges i -> j (1 per edge without weights)
+ *   deg[i] = sum_j A[i, j], dinv = 1 ./ deg with Inf -> 0 (a node without out-edges), RW = A * Diagonal(dinv): RW[i, j] = A[i, j] dinv[j]
+ *   pe[k, c] = (RW^k)[c, c],  k = 1 .. walk_length
+ * The reference forms the N x N powers and keeps their diagonals.  Here column c of RW^k is k propagates of the unit vector e_c,
+ *   v_k[i] = sum over the edges e: i -> j of (w_e * dinv[j]) * v_{k-1}[j]   (fp32, in original edge order, product then sum),
+ * and a batched graph is block diagonal: a workgroup keeps the two [n_g][GNNMP_RWPE_TILE] panels of GNNMP_RWPE_TILE start nodes of one
+ * member graph in LDS and writes only the encodings; a graph whose panels exceed the LDS budget (496 nodes by default) runs the same row
+ * walk over panels in device scratch, with the same bits.  Deterministic, no atomics; bit-identical for a member graph alone and inside
+ * any batch.
+ *   plan_t      the TRANSPOSED plan of g (the plan of (t, s): a row holds the out-edges of a node) WITHOUT added self loops
+ *   job         a host record of device pointers:
+ *     w            [n_edges] edge weights in original edge order, or NULL
+ *     graph_ptr    [n_graphs + 1] 0-based node offsets of the member graphs (idx_bytes 4 | 8; empty graphs allowed), or NULL: one graph
+ *     out          [N][walk_length] — the memory of the reference's (walk_length, N) matrix — every element written, nothing else;
+ *                  4-byte aligned
+ * A set-up call like a plan build: it allocates scratch for the graphs of the scratch path and synchronises the stream.  With a graph_ptr
+ * one check launch verifies that it ascends from 0 to N and that no edge leaves its graph's node range: GNNMP_EINVAL otherwise, with out
+ * untouched.  Refused before any HIP call (GNNMP_EINVAL): a NULL plan_t, job or out, walk_length outside 1 .. GNNMP_RWPE_MAX_WALK,
+ * idx_bytes not 4 | 8, n_graphs < 1 with a graph_ptr, a plan with added self loops or n_src != n_dst.  Float32 only; no adjoint (the
+ * reference marks nothing differentiable here). */
+#define GNNMP_RWPE_TILE 16
+#define GNNMP_RWPE_MAX_WALK 1024
+typedef struct {
+    const float *w;
+    const void *graph_ptr;
+    int idx_bytes;
+    int64_t n_graphs;
+    int64_t walk_length;
+    float *out;
+} gnnmp_rwpe_t;
+/* Synchronises the stream (graph prep). */
+int gnnmp_random_walk_pe_f32(gnnmp_graph_t *plan_t, const gnnmp_rwpe_t *job, gnnmp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Leaf ops: _gather / _scatter (GNNGraphs/src/gatherscatter.jl:4,12-18)
  * ---------------------------------------------------------------------------------------------- */
@@ -1139,12 +1173,15 @@ int gnnmp_plan_reset_counters(gnnmp_graph_t *plan, gnnmp_stream_t stream);
  *   gnnmp_debug_device_once(...)   runs the once-per-device machinery with a counting stand-in (tests/test_multi_device_cpu.py)
  *   gnnmp_debug_plan_block(plan)   the pooled block of a gnnmp_plan_concat / gnnmp_plan_select plan (NULL otherwise)
  *   gnnmp_debug_pool_pick(...)     the block pool's slot choice on host arrays
+ *   gnnmp_debug_random_walk_pe_f32(...)  gnnmp_random_walk_pe_f32 with the LDS budget of a workgroup in bytes (0 = the default, 64 KB): a
+ *                                  small budget sends small graphs through the scratch path (tests/test_rwpe.py)
  * ---------------------------------------------------------------------------------------------- */
 int gnnmp_tune(int knob, int value);
 int gnnmp_debug_mock_device(int dev);
 int gnnmp_debug_device_once(const int *devs, int n, int fail_on, int *n_failed);
 void *gnnmp_debug_plan_block(const gnnmp_graph_t *plan);
 int gnnmp_debug_pool_pick(const uint64_t *caps, int n, uint64_t bytes);
+int gnnmp_debug_random_walk_pe_f32(gnnmp_graph_t *plan_t, const gnnmp_rwpe_t *job, int64_t lds_budget_bytes, gnnmp_stream_t stream);
 
 #ifdef __cplusplus
 }
