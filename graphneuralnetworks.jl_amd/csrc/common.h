@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "gnnmp.h"
+#include "knobs.h"
 
 namespace gnnmp {
 
@@ -71,49 +72,11 @@ inline hipError_t device_once(DeviceOnce &o, F &&f) {
         if (err__ != hipSuccess) return ::gnnmp::hip_fail(err__, "hipFuncSetAttribute(" what ")");                            \
     } while (0)
 
-// ---- tuning knobs (perf experiments; not part of the drop-in surface) -------------------------
-enum Knob {
-    KNOB_FORCE_VEC = 0,    // 0 = auto, else 1|2|4
-    KNOB_FORCE_LOG2G = 1,  // -1 = auto, else 0..6
-    KNOB_UNROLL = 2,       // 0 = auto (8: measured best on both bench shapes), else 2|4|8
-    KNOB_XCD_REMAP = 3,    // 0 = off, 1 = auto (default: only when the gathered matrix fits the Infinity Cache), 2 = on
-    KNOB_LONG_ROW = 4,     // long-row threshold (default GNNMP_LONG_ROW)
-    KNOB_BLOCK_WAVES = 5,  // waves per block in the row kernels: 0 = auto (propagate 4, GAT 1), else 1..4
-    KNOB_DENSE_GENERIC = 6,  // 0 = auto (dense_t16 on its shapes, else W-resident 32x32x2, else K-chunked), 1 = force K-chunked,
-                             // 2 = skip dense_t16 (round-1 kernels only)
-    KNOB_DENSE_PREFETCH = 7,  // W-resident dense kernel scheduling: bit 4 = per-SIMD matrix-pipe token, low 4 bits =
-                              // start skew of waves 4-7 in s_sleep(127) units.  Default 17 (token + 1): 0.83 -> 0.72 ms
-                              // at 2.4M x 100 => 100.  Bit 5 = turn the cross-tile register prefetch OFF (on by default; its
-                              // first version spilled — 270 VGPRs — and was slower: see dense.hip).
-    KNOB_GAT_FAST_EXP = 8,   // retired: the one-pass attention kernel always uses v_exp_f32 now (gat_fused.hip, gexp)
-    KNOB_GRADW_SLABS = 9,    // ΔW kernel: slabs per CU (0 = auto)
-    KNOB_GRADW_RP = 10,      // ΔW kernel: 0 = the 16x16x4 kernel, < 0 = the round-1 32x32x2 kernel (A/B runs)
-    KNOB_GRADW_MIN_ROWS = 11,  // ΔW kernel: rows-per-slab floor (0 = auto: ~3 slabs per CU on small inputs, 512 on large)
-    KNOB_DENSE_T16_WAVES = 12, // dense_t16_kernel: waves per block (0 = auto, else 1..16)
-    KNOB_T16_DEBUG = 13,       // dense_t16_kernel phase ablation (experiments only): 1 = no stores, 2 = no x loads
-    KNOB_FUSED_WAVES = 14,     // fused_conv_kernel: 0 = auto (as many waves as LDS holds tiles for, <= 16), > 0 = cap, < 0 = never fuse
-    KNOB_ROW_ORDER = 15,       // rows by decreasing length in the row kernels that share a wave between rows: 0 (default) = never,
-                               // 1 = when the gathered matrix exceeds the Infinity Cache, 2 = always (use_row_order)
-    KNOB_SOFTMAX_ROWS = 16,    // one-pass narrow-row softmax (softmax_rows.hip): 0 = auto, < 0 = the three-step kernels on every row
-    KNOB_DENSE_SPLIT = 17,     // split-bf16 dense core (msplit.h, dense_split.hip): 0 = auto (on for its shapes), < 0 = the fp32-MFMA
-                               // kernels of rounds 1-2 on every shape
-    KNOB_CHAIN = 18,           // fused GraphConv chain kernel (graph_chain.hip): 0 = auto, < 0 = never (layer-by-layer path)
-    KNOB_VARIANT = 19,         // A/B switches of round 3 (all variants are correct code): low 2 bits = 1: the wave-pair chain kernel with 8 waves
-                               // a block (default 12); 16: dense_split runs its column tiles one after the other; 32: dense_split stores
-                               // straight from the accumulator layout (default: through the per-wave LDS stage); 64: never dense_wreg;
-                               // 128: split rows folded by a second kernel (csr_combine / gat_fused_combine) as in rounds 1-4 instead of
-                               // by the last chunk to arrive inside the row kernel (round 5, use_fold); 512: dense_wreg from 4 096 rows
-                               // on (default 32 768: below that its eight-wave blocks are too few) — so that small tests reach it
-    KNOB_TGCN = 20,            // TGCN recurrence (temporal.hip): 0 = auto (the one-launch kernel for out <= 128), < 0 = the per-step path
-                               // (dense launches + the step pointwise kernels, every out) — read by the host layer (gnnmp/layers_temporal.py)
-    KNOB_EDGE_DOT_GRAD = 21,   // adjoint of the per-edge dot product (linkpred.hip): 0 = auto (the fused kernel for D <= 256), < 0 = two
-                               // w_mul_xj propagates (plan and transposed plan) plus an add — read by the host (gnnmp/linkpred.py)
-    KNOB_HETERO = 22,          // heterograph aggregation (hetero.hip): 0 = auto (one hetero_rows_kernel launch per layer, and HeteroGraphConv's
-                               // transform-first path), < 0 = the composition — propagate per relation, then the same kernel over identity
-                               // relations as the combiner: the A/B baseline — read by the host (gnnmp/hetero.py)
-    KNOB_COUNT = 23
-};
+// ---- tuning knobs: knobs.h holds the table (enum Knob, the VARIANT_* bits); runtime.hip holds the values -------------------------
 int knob(int k);
+// the knobs the host layers gate on are read there by these numbers (gnnmp/knobs.py): KNOB_FUSED_WAVES = 14, KNOB_TGCN = 20,
+// KNOB_EDGE_DOT_GRAD = 21, KNOB_HETERO = 22
+static_assert(KNOB_FUSED_WAVES == 14 && KNOB_TGCN == 20 && KNOB_EDGE_DOT_GRAD == 21 && KNOB_HETERO == 22, "knobs.h: indices never change");
 int device_cus();   // compute units of the current device, queried once (hipDeviceGetAttribute costs microseconds per call)
 
 // ---- device helpers ---------------------------------------------------------------------------
@@ -247,7 +210,7 @@ struct Vec<1> {
 // correct on the ISA of gfx942 / gfx950 ONLY, where (i) s_waitcnt vmcnt(0) also counts STORES (gfx10+ track them in vscnt: the last
 // arriver could fold stale partials there) and (ii) an sc1 access goes through to the device coherence point.  The library therefore
 // refuses to compile its device code for anything else (the Makefile's ARCH is overridable); tests/test_fold_isa.py greps the built
-// code object: the FOLD kernels must contain sc1 loads / stores and no buffer_wbl2 / buffer_inv.  Escape hatches: knob 19 bit 7 or the
+// code object: the FOLD kernels must contain sc1 loads / stores and no buffer_wbl2 / buffer_inv.  Escape hatches: VARIANT_TWO_KERNEL_FOLD or the
 // environment variable GNNMP_NO_FOLD=1 send split rows through the two-kernel path of rounds 1-4 (csr_combine / gat_fused_combine).
 #if defined(__HIP_DEVICE_COMPILE__) && !(defined(__gfx942__) || defined(__gfx950__))
 #error "libgnnmp's cross-workgroup fold (coh_store / coh_load / coh_publish) relies on gfx942 / gfx950 semantics of s_waitcnt vmcnt and sc1; build with ARCH=gfx950"
@@ -401,10 +364,10 @@ int ensure_workspace(gnnmp_graph *p, size_t floats);
 // device poisons the HIP context and with it every later call.  The one remaining way to leave them dirty — a caller breaking (i) — is
 // what gnnmp_plan_reset_counters (gnnmp.h) repairs: a stream-ordered memset of the counters, a few KB.
 int ensure_arrive(gnnmp_graph *p, size_t n, size_t floats, hipStream_t stream);
-// split rows folded inside the row kernels (default) or by the combine kernels of rounds 1-4 (knob 19 bit 7, or GNNMP_NO_FOLD=1 in the
+// split rows folded inside the row kernels (default) or by the combine kernels of rounds 1-4 (VARIANT_TWO_KERNEL_FOLD, or GNNMP_NO_FOLD=1 in the
 // environment of the process, read once)?
 bool fold_disabled_by_env();
-inline bool use_fold() { return (knob(KNOB_VARIANT) & 128) == 0 && !fold_disabled_by_env(); }
+inline bool use_fold() { return (knob(KNOB_VARIANT) & VARIANT_TWO_KERNEL_FOLD) == 0 && !fold_disabled_by_env(); }
 // allocate + zero plan->ticket on first use
 int ensure_ticket(gnnmp_graph *p, hipStream_t stream);
 // build plan->row_order on first use

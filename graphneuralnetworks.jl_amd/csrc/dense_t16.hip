@@ -29,7 +29,7 @@ struct T16Args {
     int64_t N;
     int Dout;
     int waves;              // waves per block
-    int dbg;                // experiment bits: 1 = no stores, 2 = no x loads (same row for every tile)
+    int dbg;                // GNNMP_EXPERIMENTS builds, knob 13: 1 = no stores, 2 = no x loads (same row for every tile); else 0
 };
 
 // threads per block the register budget allows: four waves per SIMD (<= 128 VGPRs) up to seven column blocks; with eight, the
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(t16_max_threads<NCB>()) dense_t16_kernel(const
         // its first tile; rows past the end re-read the last row and are not stored.
         constexpr bool TWO = KQ2 > 0;
         float4 xa[MAXB], xb[MAXB];
-        auto row_of = [&](int64_t t) { return (a.dbg & 2) ? (int64_t)n : min(t * 16 + n, a.N - 1); };
+        auto row_of = [&](int64_t t) { return (GNNMP_ABLATION(a.dbg) & 2) ? (int64_t)n : min(t * 16 + n, a.N - 1); };
         {
             const float *xr = a.x[0] + row_of(tile) * (4 * KQ1);
             t16_load<MAXB, KQ1>(xa, q, [&](int kcol) { return *reinterpret_cast<const float4 *>(xr + kcol); });
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(t16_max_threads<NCB>()) dense_t16_kernel(const
 #pragma unroll
                 for (int j = 0; j < MAXB; ++j) xa[j] = xb[j];
             }
-            t16_store<NCB>(acc, bias4, has_bias, a.act, a.out + row * a.Dout + n0, row < a.N && !((a.dbg & 1) && acc[0][0] != 12345.f), ncols, q);
+            t16_store<NCB>(acc, bias4, has_bias, a.act, a.out + row * a.Dout + n0, row < a.N && !((GNNMP_ABLATION(a.dbg) & 1) && acc[0][0] != 12345.f), ncols, q);
         }
     } else {
         for (; tile < ntiles; tile += stride) {
@@ -140,7 +140,7 @@ static int launch_t16(const T16Args &a0, hipStream_t stream) {
     const int kw = knob(KNOB_DENSE_T16_WAVES);
     if (kw >= 1 && kw <= max_waves) waves = kw;
     a.waves = waves;
-    a.dbg = knob(KNOB_T16_DEBUG);
+    a.dbg = GNNMP_ABLATION(knob(KNOB_T16_DEBUG));
     const int64_t gx = std::min<int64_t>(cus, (ntiles + waves - 1) / waves);
     dim3 grid((unsigned)gx, (unsigned)((a.Dout + DP - 1) / DP));
     dense_t16_kernel<NCB, MAXB, KQ1, KQ2><<<grid, 64 * waves, lds, stream>>>(a);

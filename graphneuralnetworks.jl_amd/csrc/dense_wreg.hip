@@ -210,8 +210,8 @@ static int launch_wreg(const WregArgs &a, hipStream_t stream) {
 
 // Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (dense_split_try goes on with its own kernels).
 int dense_wreg_try(const DenseCall &c, hipStream_t stream) {
-    if (knob(KNOB_VARIANT) & 64) return 1;                    // knob 19 bit 6: never (A/B runs)
-    if (c.Dout != WR_DP || c.N < ((knob(KNOB_VARIANT) & 512) ? 4096 : 32768) || c.N > (int64_t)INT32_MAX - 64) return 1;      // (knob 19 bit 9: tests)      // (row numbers of a tile are 32-bit)
+    if (knob(KNOB_VARIANT) & VARIANT_NO_WREG) return 1;       // (A/B runs)
+    if (c.Dout != WR_DP || c.N < ((knob(KNOB_VARIANT) & VARIANT_WREG_SMALL) ? 4096 : 32768) || c.N > (int64_t)INT32_MAX - 64) return 1;      // (row numbers of a tile are 32-bit)
     const bool two = c.D2 > 0;
     if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 127)) return 1;
     if (two && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;

@@ -77,7 +77,7 @@ struct Chain2Args {
     float *out;
     float *zrows;       // [2][N][nout] z = W_head[:, slab] * h2 of every row: pooled by the finish kernel
     int G, N;
-    long long *trace;   // (GNNMP_CHAIN_TRACE builds: cycle stamps of block (0, 0))
+    long long *trace;   // (GNNMP_EXPERIMENTS builds: cycle stamps of block (0, 0))
     int32_t *bad_count, *bad_ticket, *bad_list;    // the counter of set-aside jobs, the finish kernel's arrival ticket, job * 2 + slab
 };
 
@@ -252,7 +252,7 @@ struct JobPre {
     int m[4];           // the first four in-neighbours (the row itself past the degree)
 };
 
-#ifdef GNNMP_CHAIN_TRACE
+#ifdef GNNMP_EXPERIMENTS
 #define C2_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && kjob < 8) a.trace[(wave * 8 + kjob) * 8 + (i)] = clock64(); } while (0)
 #else
 #define C2_STAMP(i) do { } while (0)
@@ -968,7 +968,7 @@ extern "C" int gnnmp_chain_jobs_info(const gnnmp_chain_jobs_t *J, int64_t *info)
     return GNNMP_OK;
 }
 
-#ifdef GNNMP_CHAIN_TRACE
+#ifdef GNNMP_EXPERIMENTS
 static long long *g_chain_trace = nullptr;
 extern "C" int gnnmp_chain_trace(long long *host) {     // 16 waves x 8 jobs x 8 stamps
     if (!g_chain_trace) return 1;
@@ -1009,13 +1009,13 @@ int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_
     a.bad_list = J->bad + 3;
     a.zrows = J->zrows;
     a.N = (int)J->N;
-#ifdef GNNMP_CHAIN_TRACE
+#ifdef GNNMP_EXPERIMENTS
     if (!g_chain_trace) { (void)hipMalloc(&g_chain_trace, sizeof(long long) * 16 * 8 * 8); (void)hipMemset(g_chain_trace, 0, sizeof(long long) * 16 * 8 * 8); }
     a.trace = g_chain_trace;
 #endif
     a.G = (int)G;
-    // knob 19 (A/B runs): 1 = 8 waves a block (4 pairs, up to 256 registers a wave) instead of 12 (6 pairs, 168 registers)
-    const int waves = (knob(KNOB_VARIANT) & 3) == 1 ? 8 : 12;
+    // VARIANT_CHAIN_8_WAVES (A/B runs): 8 waves a block (4 pairs, up to 256 registers a wave) instead of 12 (6 pairs, 168 registers)
+    const int waves = (knob(KNOB_VARIANT) & VARIANT_CHAIN_WAVES_MASK) == VARIANT_CHAIN_8_WAVES ? 8 : 12;
     const size_t lds = (size_t)3 * C2_UNITS1 * 16 + (size_t)3 * C2_UNITS2 * 16 + C2_D1 * 4 + C2_SLAB * 4 + 8 * C2_SLAB * 4 +
                        (size_t)(waves / 2) * C2_STAGE_BYTES + 4 * 2 * (size_t)waves;
     GNNMP_LDS_OPTIN("graph_chain2_kernel<768>", &graph_chain2_kernel<768>);

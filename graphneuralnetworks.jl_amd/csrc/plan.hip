@@ -2,13 +2,9 @@
 // (add_self_loops, batch).  Reference: GNNGraphs/src/gnngraph.jl:108-117 (COO container),
 // GNNGraphs/src/convert.jl:221-237 (to_sparse, rebuilt per call by the reference fast path),
 // GNNGraphs/src/transform.jl:12-28 (add_self_loops), :682-709 (batch).
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <algorithm>
-#include <atomic>
 #include <vector>
-
 
 #include "common.h"
 #include "launch.h"
@@ -18,49 +14,7 @@
 
 namespace gnnmp {
 
-static thread_local char g_err[512] = "";
-static int g_knobs[KNOB_COUNT] = {0, -1, 0, 1, 0, 0, 0, 17, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-int fail(int status, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return status;
-}
-int hip_fail(hipError_t e, const char *what) {
-    snprintf(g_err, sizeof(g_err), "HIP error %d (%s) at %s", (int)e, hipGetErrorString(e), what);
-    return e == hipErrorOutOfMemory ? GNNMP_EALLOC : GNNMP_ELAUNCH;
-}
-int knob(int k) { return (k >= 0 && k < KNOB_COUNT) ? g_knobs[k] : 0; }
-static thread_local int g_mock_device = -1;
-int current_device() {
-    if (g_mock_device >= 0) return g_mock_device < GNNMP_MAX_DEVICES ? g_mock_device : GNNMP_MAX_DEVICES - 1;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-    return dev < GNNMP_MAX_DEVICES ? dev : GNNMP_MAX_DEVICES - 1;
-}
-int device_cus() {
-    static std::atomic<int> cached[GNNMP_MAX_DEVICES] = {};
-    const int dev = current_device();
-    int cus = cached[dev].load(std::memory_order_relaxed);
-    if (cus == 0) {
-        cus = 256;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cached[dev].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
-}
-
 int ensure_workspace(gnnmp_graph *p, size_t floats) { return grow(p->ws, p->ws_floats, floats, "hipMalloc(plan workspace)"); }
-
-bool fold_disabled_by_env() {
-    static const bool off = [] {
-        const char *e = getenv("GNNMP_NO_FOLD");
-        return e && *e && *e != '0';
-    }();
-    return off;
-}
 
 int ensure_arrive(gnnmp_graph *p, size_t n, size_t floats, hipStream_t stream) {
     GNNMP_TRY(grow(p->spart, p->spart_floats, floats, "hipMalloc(plan slice partials)"));
@@ -278,13 +232,10 @@ int plan_long_thresh(int64_t Etot) {
     return th;
 }
 
-// slots per chunk of a split row (<= the plan's long_thresh); GNNMP_CHUNK_SLOTS in the environment overrides it per plan build (A/B runs)
+// slots per chunk of a split row (<= the plan's long_thresh): 128, or KNOB_CHUNK_SLOTS from 16 up (A/B runs)
 static int plan_chunk_slots() {
-    if (const char *e = getenv("GNNMP_CHUNK_SLOTS")) {
-        const int v = atoi(e);
-        if (v >= 16) return v;
-    }
-    return 128;
+    const int v = knob(KNOB_CHUNK_SLOTS);
+    return v >= 16 ? v : 128;
 }
 
 int plan_build_long_rows(gnnmp_graph *p, hipStream_t stream) {
@@ -348,6 +299,7 @@ int plan_build_long_rows(gnnmp_graph *p, hipStream_t stream) {
     };
     GNNMP_HIP(upload(p->long_rows, rows));
     GNNMP_HIP(upload(p->long_cptr, cptr));
+    // (16 bytes of p->bytes per chunk, the four arrays below: tests/test_chunk_slots.py reads the chunk count of a plan off gnnmp_plan_info's bytes)
     GNNMP_HIP(upload(p->chunk_row, crow));
     GNNMP_HIP(upload(p->chunk_lrow, clrow));
     GNNMP_HIP(upload(p->chunk_beg, cbeg));
@@ -360,51 +312,6 @@ int plan_build_long_rows(gnnmp_graph *p, hipStream_t stream) {
 using namespace gnnmp;
 
 extern "C" {
-
-int gnnmp_version(void) { return GNNMP_VERSION; }
-const char *gnnmp_last_error(void) { return g_err; }
-
-// perf-experiment hook, see common.h Knob (not part of the drop-in surface)
-int gnnmp_tune(int k, int value) {
-    if (k < 0 || k >= KNOB_COUNT) return fail(GNNMP_EINVAL, "gnnmp_tune: bad knob %d", k);
-    g_knobs[k] = value;
-    return GNNMP_OK;
-}
-
-// test hooks (like gnnmp_tune: exported, not part of the drop-in surface).  gnnmp_debug_mock_device(d >= 0) makes `d` the calling
-// thread's "current device" for every per-device table of the library (common.h: current_device), d < 0 restores hipGetDevice.
-int gnnmp_debug_mock_device(int dev) {
-    g_mock_device = dev;
-    return current_device();
-}
-// Runs the per-device machinery with a counting stand-in for hipFuncSetAttribute and returns how often it ran: the sequence of mocked
-// devices devs[0..n) must run it once per DISTINCT device (tests/test_multi_device_cpu.py).  fail_on >= 0: the stand-in fails on that
-// device; *n_failed = calls that reported the failure (every call on that device must, not only the first).
-int gnnmp_debug_device_once(const int *devs, int n, int fail_on, int *n_failed) {
-    DeviceOnce once;
-    int ran = 0, failed = 0;
-    const int keep = g_mock_device;
-    for (int k = 0; k < n; ++k) {
-        g_mock_device = devs[k];
-        const hipError_t e = device_once(once, [&] {
-            ++ran;
-            return current_device() == fail_on ? hipErrorInvalidValue : hipSuccess;
-        });
-        if (e != hipSuccess) ++failed;
-    }
-    g_mock_device = keep;
-    if (n_failed) *n_failed = failed;
-    return ran;
-}
-// the pooled block of a plan made by gnnmp_plan_concat / gnnmp_plan_select (NULL for other plans): lets a test see WHICH block a plan got
-void *gnnmp_debug_plan_block(const gnnmp_graph_t *p) { return p ? p->block : nullptr; }
-// pool.h's slot choice on host arrays
-int gnnmp_debug_pool_pick(const uint64_t *caps, int n, uint64_t bytes) {
-    size_t c[64];
-    if (n < 0 || n > 64) return -2;
-    for (int i = 0; i < n; ++i) c[i] = (size_t)caps[i];
-    return pool_pick(c, n, (size_t)bytes);
-}
 
 int gnnmp_plan_destroy(gnnmp_graph_t *p) { return plan_dispose(p, nullptr, false); }
 

@@ -5,8 +5,11 @@ C ABI; there is NO CPU fallback — if the library is missing or no GPU is visib
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
+
+from .knobs import Knob, Variant  # noqa: F401
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("GNNMP_LIB") or os.path.join(_PKG, "lib", "libgnnmp.so")   # GNNMP_LIB: another build of the same ABI
@@ -53,7 +56,7 @@ SYMBOLS = (
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
-    "gnnmp_tune", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
+    "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32",
 )
 
@@ -230,6 +233,7 @@ def load():
         "gnnmp_graphconv_chain_f32": [vp, vp, vp, i64, vp, i, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                       ctypes.POINTER(vp), ctypes.POINTER(i), i, i, i, vp, vp, i64, vp, vp, vp],
         "gnnmp_tune": [i, i],
+        "gnnmp_tune_get": [i, ctypes.POINTER(i), ctypes.POINTER(i)],
         "gnnmp_plan_reset_counters": [vp, vp],
         "gnnmp_propagate_f64": [vp, i, i, vp, vp, vp, vp, vp, i64, vp],
         "gnnmp_gather_f64": [vp, vp, i, i, i64, vp, i64, vp],
@@ -343,22 +347,39 @@ def set_probe(p):
     _probe = p
 
 
-KNOB_TGCN = 20                            # csrc/common.h: 0 = auto, < 0 = TGCN's per-step path
-KNOB_EDGE_DOT_GRAD = 21                   # csrc/common.h: 0 = auto, < 0 = the edge-dot adjoint as two propagates (gnnmp/linkpred.py)
-KNOB_HETERO = 22                          # csrc/common.h: 0 = auto, < 0 = heterograph aggregation composed from propagate (gnnmp/hetero.py)
-KNOB_DEFAULTS = {1: -1, 3: 1, 7: 17}      # every other knob starts at 0 (csrc/plan.hip g_knobs)
-_knobs = {}
+KNOB_TGCN, KNOB_EDGE_DOT_GRAD, KNOB_HETERO = Knob.TGCN, Knob.EDGE_DOT_GRAD, Knob.HETERO      # (the names older callers use)
 
 
 def knob(k: int) -> int:
-    """the value last set through tune() (or the library's default)"""
-    return _knobs.get(k, KNOB_DEFAULTS.get(k, 0))
+    """the library's current value of a knob (csrc/knobs.h): whoever set it, tune() here or a raw gnnmp_tune"""
+    v = ctypes.c_int()
+    check(load().gnnmp_tune_get(k, ctypes.byref(v), None))
+    return v.value
+
+
+def knob_default(k: int) -> int:
+    """the value a knob starts at (the table of csrc/knobs.h, as compiled into the library)"""
+    d = ctypes.c_int()
+    check(load().gnnmp_tune_get(k, None, ctypes.byref(d)))
+    return d.value
 
 
 def tune(knob: int, value: int):
-    """perf-experiment hook (csrc/common.h Knob); not part of the drop-in surface"""
+    """perf-experiment hook (csrc/knobs.h); not part of the drop-in surface"""
     check(load().gnnmp_tune(knob, value))
-    _knobs[knob] = int(value)
-    if knob == 14:                       # the host mirror of fused_conv's gating follows the knob (gnnmp/layers.py)
-        from . import layers
-        layers._KNOB14[0] = int(value)
+
+
+@contextlib.contextmanager
+def tuned(k: int, value: int):
+    """a knob set to `value` inside the block; the value the library held before comes back on the way out, on an exception too"""
+    before = knob(k)
+    tune(k, value)
+    try:
+        yield
+    finally:
+        tune(k, before)
+
+
+def tuned_bits(k: int, set: int = 0, clear: int = 0):
+    """tuned() for a bit field (Knob.VARIANT): the current value with the bits of `set` on and those of `clear` off"""
+    return tuned(k, (knob(k) | int(set)) & ~int(clear))

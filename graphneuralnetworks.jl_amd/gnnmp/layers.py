@@ -99,7 +99,7 @@ def fused_conv(plan, aggr, xj, W_agg, bias=None, sigma=None, xi=None, W_root=Non
     # the library's default gating, mirrored here so that the shapes it would refuse anyway cost neither two throw-away allocations nor a
     # failed call with a formatted error string: with knob 14 at its default the kernel fuses only a layer without a root term
     # whose aggregate exceeds 128 MiB (csrc/fused_conv.hip); knob 14 > 0 forces it, < 0 disables it
-    k14 = _knob14()
+    k14 = L.knob(L.Knob.FUSED_WAVES)
     # (round 6: sage_conv / graph_conv 100 + 100 => a multiple of 128 outputs has a fused kernel too — fused_cat_kernel — but it loses to
     # the two-kernel path on the products shape, 6.85 against 5.77 ms, and runs only when knob 14 > 0 forces it)
     if k14 < 0 or (k14 == 0 and (D1 > 0 or plan.n_dst * D * 4 < (128 << 20))):
@@ -123,17 +123,10 @@ def fused_conv(plan, aggr, xj, W_agg, bias=None, sigma=None, xi=None, W_root=Non
     return (out, agg) if return_aggregate else out
 
 
-_KNOB14 = [0]
-
-
 def _would_fuse(plan, D):
     """the library's default gating of fused_conv for a layer without a root term (see fused_conv above)"""
-    k14 = _KNOB14[0]
+    k14 = L.knob(L.Knob.FUSED_WAVES)
     return k14 > 0 or (k14 == 0 and plan.n_dst * D * 4 >= (128 << 20))
-
-
-def _knob14():
-    return _KNOB14[0]
 
 
 def bias_act(x, bias, sigma):

@@ -192,8 +192,9 @@ def recurrence(P, Uzr, Uh, h0, h0_stride, need_gates=True):
     o = D3 // 3
     lib = L.load()
     y = torch.empty((N, T, o), dtype=torch.float32, device=P.device)
-    gates = torch.empty((N, T, 3 * o), dtype=torch.float32, device=P.device) if (need_gates or not use_fused(o)) else None
-    if use_fused(o):
+    fused = use_fused(o)                                     # (one read of the knob per recurrence)
+    gates = torch.empty((N, T, 3 * o), dtype=torch.float32, device=P.device) if (need_gates or not fused) else None
+    if fused:
         L.check(lib.gnnmp_tgcn_recurrence_f32(L.ptr(P), L.ptr(Uzr), L.ptr(Uh), L.ptr(h0), h0_stride, L.ptr(y), L.ptr(gates), N, T, o,
                                               L.stream_ptr()))
         return y, gates

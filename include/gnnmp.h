@@ -1167,8 +1167,12 @@ int gnnmp_plan_reset_counters(gnnmp_graph_t *plan, gnnmp_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
  * GNNMP_INTERNAL — exported, NOT part of the drop-in surface: experiment and test hooks.  Declared here so that C callers (tests/c_harness)
  * do not declare them by hand; a Julia / C host has no reason to call them, and their meaning may change between builds.
- *   gnnmp_tune(knob, value)        process-global tuning knobs of the perf experiments (csrc/common.h: enum Knob; every value selects
- *                                  correct code).  Not thread-safe against concurrent compute calls.
+ *   gnnmp_tune(knob, value)        process-global tuning knobs of the perf experiments (csrc/knobs.h: the table of indices, defaults and
+ *                                  meanings).  In the release build every accepted value selects correct code: the one knob whose values
+ *                                  compute garbage on purpose (13, phase ablations) is refused with GNNMP_EUNSUPPORTED unless it is 0; only
+ *                                  a library built with -DGNNMP_EXPERIMENTS (make EXPERIMENTS=1) takes it.  GNNMP_EINVAL for a bad index.
+ *                                  Not thread-safe against concurrent compute calls.
+ *   gnnmp_tune_get(knob, &v, &d)   the knob's current value and its default; either pointer may be NULL.  GNNMP_EINVAL for a bad index.
  *   gnnmp_debug_mock_device(d)     d >= 0: the calling thread's "current device" for the library's per-device tables; d < 0: hipGetDevice
  *   gnnmp_debug_device_once(...)   runs the once-per-device machinery with a counting stand-in (tests/test_multi_device_cpu.py)
  *   gnnmp_debug_plan_block(plan)   the pooled block of a gnnmp_plan_concat / gnnmp_plan_select plan (NULL otherwise)
@@ -1177,6 +1181,7 @@ int gnnmp_plan_reset_counters(gnnmp_graph_t *plan, gnnmp_stream_t stream);
  *                                  small budget sends small graphs through the scratch path (tests/test_rwpe.py)
  * ---------------------------------------------------------------------------------------------- */
 int gnnmp_tune(int knob, int value);
+int gnnmp_tune_get(int knob, int *value, int *default_value);
 int gnnmp_debug_mock_device(int dev);
 int gnnmp_debug_device_once(const int *devs, int n, int fail_on, int *n_failed);
 void *gnnmp_debug_plan_block(const gnnmp_graph_t *plan);

@@ -381,7 +381,7 @@ def plan_threshold(lib, n_edges):
 class Case:
     def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None):
         self.export, self.sid, self.args, self.ref, self.guard, self.status = export, sid, args, ref, guard, status
-        self.knobs = knobs or {}                   # gnnmp_tune settings for the call (reset to 0 after it)
+        self.knobs = knobs or {}                   # gnnmp_tune settings for the call (the previous values come back after it)
         self.align_status = align_status or {}     # {array name: status the header documents for an under-aligned pointer}
         self.arrs = [a for a in args if isinstance(a, Arr)]
         self.uses_plan = any(isinstance(a, Pl) for a in args)
@@ -408,13 +408,17 @@ def bind(case, slab, plans, stream=None):
 
 def call(lib, case, cargs):
     """the one library call of a case, under its tuning knobs"""
+    before = {}
     for k, v in case.knobs.items():
+        was = ctypes.c_int()
+        assert lib.gnnmp_tune_get(k, ctypes.byref(was), None) == OK
+        before[k] = was.value
         assert lib.gnnmp_tune(k, v) == OK
     try:
         return getattr(lib, case.export)(*cargs)
     finally:
-        for k in case.knobs:
-            lib.gnnmp_tune(k, 0)
+        for k, v in before.items():
+            lib.gnnmp_tune(k, v)
 
 
 def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):

@@ -461,7 +461,7 @@ def _chain_batch(gm, rng):
     finally:
         lib.gnnmp_graphconv_chain_f32 = real
     assert calls == [0], calls
-    assert g._cache["chain_jobs"].njobs > 0 and gm.knob(18) == 0
+    assert g._cache["chain_jobs"].njobs > 0 and gm.knob(gm.Knob.CHAIN) == 0
     return members, xs, g, model
 
 
@@ -505,12 +505,8 @@ def test_config5_chain_replayed_on_non_finite_features(gm, oracle, side):
 
     def check(got):
         y = got[0]
-        before = gm.knob(18)
-        gm.tune(18, -1)                                   # the layer-by-layer path on the same values (tests/test_graph_chain.py: run_both)
-        try:
+        with gm.tuned(gm.Knob.CHAIN, -1):                                   # the layer-by-layer path on the same values (tests/test_graph_chain.py: run_both)
             yl = model(g, g.x).cpu().numpy()
-        finally:
-            gm.tune(18, before)
         bad = np.flatnonzero(~np.isfinite(y).all(1)).tolist()
         assert bad == np.flatnonzero(~np.isfinite(yl).all(1)).tolist() == sorted(hit), bad
         assert np.array_equal(np.isnan(y), np.isnan(yl))

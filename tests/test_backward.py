@@ -165,11 +165,8 @@ def test_dense_adjoints_vs_float64(gm, N, K, Dout):
     dW2, db2 = bw.dense_grad_w(dz, dev(x))
     assert bool((dW2 == dW).all()) and bool((db2 == db).all())
     # the round-1 32x32x2 kernel stays behind knob 10 < 0 (A/B runs): same product
-    gm.tune(10, -1)
-    try:
+    with gm.tuned(gm.Knob.GRADW_RP, -1):
         dW3, _ = bw.dense_grad_w(dz, dev(x))
-    finally:
-        gm.tune(10, 0)
     assert np.linalg.norm(dW3.cpu().numpy() - ref_dW) <= 1e-5 * np.linalg.norm(ref_dW)
 
 

@@ -57,12 +57,8 @@ def case(gm, N, K1, K2, Dout, act, has_bias, w_layout, seed, scale_x=1.0):
         mag = mag + b.double().abs()
     ref = torch.relu(pre) if act else pre
     y = run_dense(gm, x, W1, b, act, x2, W2, w_layout)
-    before = gm.knob(17)
-    gm.tune(17, -1)
-    try:
+    with gm.tuned(gm.Knob.DENSE_SPLIT, -1):
         y32 = run_dense(gm, x, W1, b, act, x2, W2, w_layout)
-    finally:
-        gm.tune(17, before)
     e_split = float(((y.double() - ref).abs() / mag).max())
     e_f32 = float(((y32.double() - ref).abs() / mag).max())
     assert torch.equal(run_dense(gm, x, W1, b, act, x2, W2, w_layout), y), "not run-to-run identical"
@@ -127,11 +123,8 @@ def test_non_finite_operands_take_the_exact_path(gm):
     assert torch.isnan(y[37]).all()
     assert torch.equal(torch.isinf(y[120]), torch.isinf(ref[120])) and torch.equal(torch.sign(y[120]), torch.sign(ref[120]).float())
     assert y[121, 3] == -float("inf") and y[121, 4] == -float("inf")
-    gm.tune(17, -1)
-    try:
+    with gm.tuned(gm.Knob.DENSE_SPLIT, -1):
         y32 = run_dense(gm, x, W, None, 0)
-    finally:
-        gm.tune(17, 0)
     assert torch.equal(torch.isnan(y), torch.isnan(y32)) and torch.equal(torch.isinf(y), torch.isinf(y32))
 
 
@@ -141,11 +134,9 @@ WREG_SHAPES = [(100, 100), (64, 64), (64, 100), (100, 64), (64, 128), (128, 64),
 
 @pytest.fixture
 def wreg_small(gm):
-    """knob 19 bit 9: the register-resident kernel from 4 096 rows on (default 32 768), so that these sizes reach it"""
-    before = gm.knob(19)
-    gm.tune(19, before | 512)
-    yield before | 512
-    gm.tune(19, before)
+    """Variant.WREG_SMALL: the register-resident kernel from 4 096 rows on (default 32 768), so that these sizes reach it"""
+    with gm.tuned_bits(gm.Knob.VARIANT, set=gm.Variant.WREG_SMALL):
+        yield
 
 
 def _wreg_case(gm, N, act, has_bias, w_layout, seed, K1=100, K2=100):
@@ -172,11 +163,8 @@ def test_register_resident_kernel_is_bit_identical_to_the_lds_kernel(gm, wreg_sm
     K1, K2 = K
     x, m, W1, W2, b, Wfull = _wreg_case(gm, N, 1, True, w_layout, N + w_layout, K1, K2)
     y = run_dense(gm, x, W1, b, 1, m, W2, w_layout)
-    gm.tune(19, wreg_small | 64)                                 # bit 6: never dense_wreg_kernel
-    try:
+    with gm.tuned_bits(gm.Knob.VARIANT, set=gm.Variant.NO_WREG):                     # never dense_wreg_kernel
         y_lds = run_dense(gm, x, W1, b, 1, m, W2, w_layout)
-    finally:
-        gm.tune(19, wreg_small)
     assert torch.equal(y, y_lds)
     xc = torch.cat([x, m], 1) if K2 else x
     ref = torch.relu(xc.double() @ Wfull.double().t() + b.double())
@@ -200,9 +188,6 @@ def test_register_resident_kernel_non_finite_operands(gm, wreg_small):
     assert float((y[good].double() - ref[good]).abs().max()) <= 1e-5 * float(ref[good].abs().max())
     assert torch.isnan(y[37]).all()
     assert torch.equal(torch.isinf(y[4100]), torch.isinf(ref[4100])) and torch.equal(torch.sign(y[4100]), torch.sign(ref[4100]).float())
-    gm.tune(19, wreg_small | 64)
-    try:
+    with gm.tuned_bits(gm.Knob.VARIANT, set=gm.Variant.NO_WREG):
         y_lds = run_dense(gm, x, W1, None, 0, m, W2, 0)
-    finally:
-        gm.tune(19, wreg_small)
     assert torch.equal(torch.isnan(y), torch.isnan(y_lds)) and torch.equal(y[good], y_lds[good])

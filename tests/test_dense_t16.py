@@ -61,11 +61,8 @@ def test_random_shapes_against_float64_and_the_round1_kernels(gm, seed):
     y = run_dense(gm, x, W1, b, act, x2, W2, w_layout)
     scale = float(ref.abs().max()) + 1e-30
     assert float((y.double() - ref).abs().max()) <= 1e-5 * scale, tag
-    gm.tune(6, 2)
-    try:
+    with gm.tuned(gm.Knob.DENSE_GENERIC, 2):
         y1 = run_dense(gm, x, W1, b, act, x2, W2, w_layout)
-    finally:
-        gm.tune(6, 0)
     assert float((y1.double() - ref).abs().max()) <= 1e-5 * scale, tag + " (round-1 kernels)"
     assert float((y - y1).abs().max()) <= 2e-5 * scale, tag + " (the two kernel families disagree)"
     # run-to-run identical

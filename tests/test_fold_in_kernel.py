@@ -39,15 +39,11 @@ HUBS = [(3, 65), (10, 128), (11, 129), (77, 513), (200, 1500), (201, 4100), (500
 def both(gm, fn):
     """fn() under the folding kernels (twice: the second launch reuses the counters) and under the two-kernel path"""
     import torch
-    before = gm.knob(19)
-    try:
-        gm.tune(19, before & ~128)
+    with gm.tuned_bits(gm.Knob.VARIANT, clear=gm.Variant.TWO_KERNEL_FOLD):
         a1 = fn()
         a2 = fn()
-        gm.tune(19, before | 128)
+    with gm.tuned_bits(gm.Knob.VARIANT, set=gm.Variant.TWO_KERNEL_FOLD):
         b = fn()
-    finally:
-        gm.tune(19, before)
     torch.cuda.synchronize()
     return a1, a2, b
 

@@ -53,7 +53,7 @@ def test_propagate_fold_10000_launches_under_l2_pressure():
     import gnnmp as gm
     from gnnmp import _lib as L
     gm.load()
-    assert (gm.knob(19) & 128) == 0, "the in-kernel fold must be the default path"
+    assert (gm.knob(gm.Knob.VARIANT) & gm.Variant.TWO_KERNEL_FOLD) == 0, "the in-kernel fold must be the default path"
     rng = np.random.default_rng(5)
     n = 4000
     s, t = hub_graph(rng, n, 30000, [(3, 65), (11, 129), (77, 513), (200, 1500), (201, 4100), (500, 20000), (900, 50000)])
@@ -67,13 +67,9 @@ def test_propagate_fold_10000_launches_under_l2_pressure():
         launch = lambda: L.check(lib.gnnmp_propagate_f32(plan.handle, L.COPY_XJ, aggr, L.ptr(x), None, None, None, L.ptr(out), D, L.stream_ptr()))
         first = _stress(gm, launch, out)
         # and the folded result IS the two-kernel result (the combine path of rounds 1-4)
-        before = gm.knob(19)
-        try:
-            gm.tune(19, before | 128)
+        with gm.tuned_bits(gm.Knob.VARIANT, set=gm.Variant.TWO_KERNEL_FOLD):
             ref = torch.empty_like(out)
             L.check(lib.gnnmp_propagate_f32(plan.handle, L.COPY_XJ, aggr, L.ptr(x), None, None, None, L.ptr(ref), D, L.stream_ptr()))
-        finally:
-            gm.tune(19, before)
         torch.cuda.synchronize()
         assert torch.equal(first.view(torch.int32), ref.view(torch.int32))
 

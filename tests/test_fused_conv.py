@@ -20,9 +20,8 @@ def gm():
     gnnmp.load()
     # the library only fuses when the aggregate cannot stay in the Infinity Cache (>= 128 MB); these graphs are small, so
     # force the fused kernel for the whole module (knob 14 > 0 = cap of waves per block, 16 = the automatic maximum)
-    gnnmp.tune(14, 16)
-    yield gnnmp
-    gnnmp.tune(14, 0)
+    with gnnmp.tuned(gnnmp.Knob.FUSED_WAVES, 16):
+        yield gnnmp
 
 
 def dev(a):
@@ -135,8 +134,7 @@ def test_sage_fused_cat_kernel(gm, oracle, variant, Dout):
     plan = g.plan(False)
     assert plan.n_long >= 2
     xd, W1d, W2d, bd = dev(xj), dev(W1), dev(W2), dev(b)
-    gm.tune(14, variant)
-    try:
+    with gm.tuned(gm.Knob.FUSED_WAVES, variant):
         for aggr, name in ((L.SUM, "+"), (L.MEAN, "mean"), (L.MAX, "max"), (L.MIN, "min")):
             res = gm.fused_conv(plan, aggr, xd, W2d, bd, "relu", xi=xd, W_root=W1d, return_aggregate=True)
             assert res is not None, "100 + 100 => a multiple of 128 is inside fused_cat_kernel's envelope"
@@ -174,8 +172,6 @@ def test_sage_fused_cat_kernel(gm, oracle, variant, Dout):
         yl = l(g, xd).cpu().numpy()
         ref = oracle.sage_conv(s, t, n, xj, l.weight.cpu().numpy(), l.bias.cpu().numpy(), "relu", "mean")
         close(yl, ref)
-    finally:
-        gm.tune(14, 16)
 
 
 def test_layers_take_the_fused_kernel_and_fall_back_outside_it(gm, oracle):
@@ -246,14 +242,11 @@ def test_gcn_layer_adjoint_through_the_fused_kernels(gm, oracle, Din, Dout):
     for got, ref in ((xt.grad, dx), (l.weight.grad, dW), (l.bias.grad, db)):
         assert np.linalg.norm(got.cpu().numpy() - ref) <= 1e-5 * np.linalg.norm(ref)
     # and the same gradients as the unfused composition
-    gm.tune(14, -1)
-    try:
+    with gm.tuned(gm.Knob.FUSED_WAVES, -1):
         x2 = dev(x).requires_grad_(True)
         l.weight.grad = None
         l.bias.grad = None
         y2 = gcn_conv_ad(l, g, x2)
         (y2 * dev(r)).sum().backward()
-    finally:
-        gm.tune(14, 16)
     close(xt.grad.cpu().numpy(), x2.grad.cpu().numpy(), 1e-5)
     close(y.detach().cpu().numpy(), y2.detach().cpu().numpy())

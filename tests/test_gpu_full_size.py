@@ -140,11 +140,8 @@ def test_softmax_edge_neighbors_full_size(gm, oracle, products):
     for H in (8, 1):
         e = torch.randn((E, H), device="cuda") * 2.0
         a = gm.softmax_edge_neighbors(g, e)
-        gm.tune(16, -1)
-        try:
+        with gm.tuned(gm.Knob.SOFTMAX_ROWS, -1):
             a3 = gm.softmax_edge_neighbors(g, e)
-        finally:
-            gm.tune(16, 0)
         assert torch.equal(a, a3)
         sums = torch.zeros((N, H), dtype=torch.float64, device="cuda").index_add_(0, tdev, a.double())
         assert float((sums[has] - 1.0).abs().max()) < 1e-5

@@ -601,11 +601,10 @@ def test_dense_julia_weight_layout(gm):
         Wj = dev(np.ascontiguousarray(W.T))            # [Din][Dout]: the bytes Julia holds for a (Dout, Din) matrix
         out = torch.empty((N, Dout), dtype=torch.float32, device="cuda")
         for knob in (0, 1):                            # W-resident and K-chunked kernels
-            gm.tune(6, knob)
-            L.check(gm.load().gnnmp_dense_f32(L.ptr(xd), L.ptr(Wj), Din, Dout, None, None, 0, 0, 1, L.ptr(bd), L.ACT_RELU,
-                                              L.ptr(out), N, Dout, L.stream_ptr()))
-            assert_close(host(out), ref)
-        gm.tune(6, 0)
+            with gm.tuned(gm.Knob.DENSE_GENERIC, knob):
+                L.check(gm.load().gnnmp_dense_f32(L.ptr(xd), L.ptr(Wj), Din, Dout, None, None, 0, 0, 1, L.ptr(bd), L.ACT_RELU,
+                                                  L.ptr(out), N, Dout, L.stream_ptr()))
+                assert_close(host(out), ref)
 
 
 @pytest.mark.gpu

@@ -64,12 +64,8 @@ def run_both(gm, model, g):
     from gnnmp import layers
     assert layers._chain_pattern(model.layers) is not None
     y = model(g, g.x)
-    before = gm.knob(18)
-    gm.tune(18, -1)
-    try:
+    with gm.tuned(gm.Knob.CHAIN, -1):
         y_layers = model(g, g.x)
-    finally:
-        gm.tune(18, before)
     return y, y_layers
 
 
@@ -221,12 +217,8 @@ def test_wave_job_kernel_on_irregular_batches(gm, oracle, aggr, pool, seed):
     y, yl = run_both(gm, model, g)
     jobs = g._cache["chain_jobs"]
     assert jobs.njobs > 0 and jobs.max_graph <= 64 and 0.5 < jobs.fill <= 1.0
-    before = gm.knob(18)
-    gm.tune(18, 1)
-    try:
+    with gm.tuned(gm.Knob.CHAIN, 1):
         y_general = model(g, g.x)
-    finally:
-        gm.tune(18, before)
     ref = oracle_chain(oracle, members, xs, model.layers[:2], pool, model.layers[-1])
     close(y.cpu().numpy(), ref, "wave-job kernel vs oracle")
     close(y_general.cpu().numpy(), ref, "general kernel vs oracle")
@@ -392,12 +384,8 @@ def test_any_input_width_is_zero_padded_into_the_fused_kernels(gm, oracle, din, 
         assert g._cache["chain_jobs"].njobs > 0                # the wave-pair kernel's envelope
     ref = oracle_chain(oracle, members, xs, model.layers[:-2], "mean", model.layers[-1])
     close(y.cpu().numpy(), ref, f"din={din} dims={dims}")
-    before = gm.knob(18)
-    gm.tune(18, -1)
-    try:
+    with gm.tuned(gm.Knob.CHAIN, -1):
         close(model(g, g.x).cpu().numpy(), ref, f"layers din={din}")
-    finally:
-        gm.tune(18, before)
     # replacing a weight in place (an optimiser step) invalidates the cached padded copy
     with torch.no_grad():
         model.layers[0].weight1.mul_(0.5)

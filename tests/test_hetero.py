@@ -239,11 +239,8 @@ def test_the_knob_forces_the_composition(gm, monkeypatch):
     g, x, aggr, ew = build_graph(gm, {"d": (33, rels)})
     one = gm.hetero_propagate(g, x, aggr=aggr, edge_weight=ew)["d"].cpu().numpy()
     counts = spy(monkeypatch, _lib.load(), "gnnmp_hetero_propagate_f32", "gnnmp_propagate_f32")
-    _lib.tune(_lib.KNOB_HETERO, -1)
-    try:
+    with _lib.tuned(_lib.Knob.HETERO, -1):
         two = gm.hetero_propagate(g, x, aggr=aggr, edge_weight=ew)["d"].cpu().numpy()
-    finally:
-        _lib.tune(_lib.KNOB_HETERO, 0)
     assert counts == {"gnnmp_hetero_propagate_f32": 1, "gnnmp_propagate_f32": 3}
     same_bits(two, one, "the composition against the one-launch kernel (no split rows: the same bits)")
 
@@ -591,13 +588,10 @@ def test_graphconv_and_sageconv_on_bipartite_relations(gm, monkeypatch, kind, ag
         for k in y:
             close64_layer(y[k].cpu().numpy(), ref[k], f"{kind} {aggr} sigma={sigma} y.{k}")
         if fused:
-            _lib.tune(_lib.KNOB_HETERO, -1)
-            try:
+            with _lib.tuned(_lib.Knob.HETERO, -1):
                 with monkeypatch.context() as mp:
                     counts = spy(mp, lib, "gnnmp_hetero_propagate_f32", "gnnmp_propagate_f32")
                     y2 = model(g, xd)
-            finally:
-                _lib.tune(_lib.KNOB_HETERO, 0)
             assert counts == {"gnnmp_hetero_propagate_f32": 1, "gnnmp_propagate_f32": 4}, counts
             for k in y:
                 close64_layer(y2[k].cpu().numpy(), ref[k], f"{kind} {aggr} composition y.{k}")

@@ -311,11 +311,8 @@ def test_the_knob_and_the_cap_send_the_call_to_the_composition(gm, cap, monkeypa
     g, args = build_hetero(gm, {"a": (31, x, rels[:6])})
     one = gm.hetero_propagate_grad(g, **args)["a"].cpu().numpy()
     counts = TH.spy(monkeypatch, _lib.load(), *COUNTED)
-    _lib.tune(_lib.KNOB_HETERO, -1)
-    try:
+    with _lib.tuned(_lib.Knob.HETERO, -1):
         two = gm.hetero_propagate_grad(g, **args)["a"].cpu().numpy()
-    finally:
-        _lib.tune(_lib.KNOB_HETERO, 0)
     assert counts == {EXPORT: 0, "gnnmp_propagate_f32": 4, "gnnmp_propagate_maxmin_grad_f32": 2, "gnnmp_hetero_propagate_f32": 1}
     TH.same_bits(two, one, "the composition against the one-launch kernel")
     TH.close64(one, value64(rels[:6], 31, x), "six relations")

@@ -1,4 +1,4 @@
-"""The kernel variants behind the tuning knobs (csrc/common.h) under the DRIVER's test run.  Round 2 swept them by hand
+"""The kernel variants behind the tuning knobs (csrc/knobs.h) under the DRIVER's test run.  Round 2 swept them by hand
 (`GNNMP_KNOBS=... pytest -m gpu`, README.md) — evidence the judge could not see ("weak": the fallbacks are live code
 paths: non-power-of-two heads, K > 128, D % 4 != 0, small graphs).  Here a core subset of the parity suite runs once per knob set:
   14=16            the fused aggregate-then-transform kernel on every graph (default: only where the aggregate exceeds 128 MiB)
@@ -12,22 +12,26 @@ paths: non-power-of-two heads, K > 128, D % 4 != 0, small graphs).  Here a core 
   19=128           split rows folded by the combine kernels of rounds 1-4 (default since round 5: by the last chunk to arrive, inside
                    the row kernel)
 Each case IS the original test function, called with the knobs set."""
+import contextlib
+
 import numpy as np
 import pytest
+
+from gnnmp.knobs import Knob, Variant
 
 pytestmark = pytest.mark.gpu
 
 KNOB_SETS = {
-    "fused-always(14=16)": [(14, 16)],
-    "vec1(0=1)": [(0, 1)],
-    "vec2(0=2)": [(0, 2)],
-    "round1-fallbacks(6=2,10=-1,16=-1)": [(6, 2), (10, -1), (16, -1)],
-    "fp32-mfma-dense(17=-1)": [(17, -1)],
-    "chain-general(18=1)": [(18, 1)],
-    "chain-off(18=-1)": [(18, -1)],
-    "chain-8-waves(19=1)": [(19, 1)],
-    "dense-split-direct-stores-serial-column-tiles(19=48)": [(19, 48)],
-    "two-kernel-long-rows(19=128)": [(19, 128)],
+    "fused-always(14=16)": [(Knob.FUSED_WAVES, 16)],
+    "vec1(0=1)": [(Knob.FORCE_VEC, 1)],
+    "vec2(0=2)": [(Knob.FORCE_VEC, 2)],
+    "round1-fallbacks(6=2,10=-1,16=-1)": [(Knob.DENSE_GENERIC, 2), (Knob.GRADW_RP, -1), (Knob.SOFTMAX_ROWS, -1)],
+    "fp32-mfma-dense(17=-1)": [(Knob.DENSE_SPLIT, -1)],
+    "chain-general(18=1)": [(Knob.CHAIN, 1)],
+    "chain-off(18=-1)": [(Knob.CHAIN, -1)],
+    "chain-8-waves(19=1)": [(Knob.VARIANT, Variant.CHAIN_8_WAVES)],
+    "dense-split-direct-stores-serial-column-tiles(19=48)": [(Knob.VARIANT, Variant.SPLIT_DIRECT_STORES | Variant.SPLIT_SERIAL_TILES)],
+    "two-kernel-long-rows(19=128)": [(Knob.VARIANT, Variant.TWO_KERNEL_FOLD)],
 }
 
 
@@ -42,12 +46,10 @@ def gm():
 
 @pytest.fixture(params=list(KNOB_SETS), ids=list(KNOB_SETS))
 def knobs(gm, request):
-    before = [(k, gm.knob(k)) for k, _ in KNOB_SETS[request.param]]
-    for k, v in KNOB_SETS[request.param]:
-        gm.tune(k, v)
-    yield request.param
-    for k, v in before:
-        gm.tune(k, v)
+    with contextlib.ExitStack() as stack:
+        for k, v in KNOB_SETS[request.param]:
+            stack.enter_context(gm.tuned(k, v))
+        yield request.param
 
 
 def test_propagate_widths(knobs, gm, oracle):
@@ -81,13 +83,9 @@ def test_edge_softmax(knobs, gm, oracle):
 
 def test_fused_conv(knobs, gm, oracle):
     import test_fused_conv as T
-    before = gm.knob(14)
-    gm.tune(14, 16)          # (these graphs are small: the kernel is forced, as in tests/test_fused_conv.py)
-    try:
+    with gm.tuned(gm.Knob.FUSED_WAVES, 16):          # (these graphs are small: the kernel is forced, as in tests/test_fused_conv.py)
         for D, Dout in ((100, 100), (16, 128), (12, 20)):
             T.test_aggregate_is_bit_identical_and_output_matches(gm, oracle, D, Dout)
-    finally:
-        gm.tune(14, before)
 
 
 def test_layers_and_chain(knobs, gm, oracle):

@@ -418,12 +418,9 @@ def test_edge_dot_grad(D):
     assert torch.equal(dxi, dxi2) and torch.equal(dxj, dxj2)
     assert torch.equal(dxa, gnnmp.edge_dot_grad(g, Xi, Xi, Dz, alias=True)[0])
     # the fused kernel agrees with the composition of two propagates (knob 21 < 0: the A/B baseline)
-    _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, -1)
-    try:
+    with _lib.tuned(_lib.Knob.EDGE_DOT_GRAD, -1):
         ci, cj = gnnmp.edge_dot_grad(g, Xi, Xj, Dz)
         ca, _ = gnnmp.edge_dot_grad(g, Xi, Xi, Dz, alias=True)
-    finally:
-        _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, 0)
     # same products, same edge order: bit-identical on the rows the propagate does not split, the hub rows (folded chunk by chunk
     # there) within the float32 reordering of a 3000-term sum
     short_in, short_out = np.bincount(t - 1, minlength=n) <= 64, np.bincount(s - 1, minlength=n) <= 64

@@ -212,11 +212,8 @@ def test_graph_with_more_than_2_pow_31_edges(gm):
     assert torch.equal(got, want.float())
     # the neighbourhood softmax of the same rows: one pass == three steps, every destination with an edge sums to one
     a1 = gm.softmax_edge_neighbors(g, e)
-    gm.tune(16, -1)
-    try:
+    with gm.tuned(gm.Knob.SOFTMAX_ROWS, -1):
         a3 = gm.softmax_edge_neighbors(g, e)
-    finally:
-        gm.tune(16, 0)
     assert torch.equal(a1, a3)
     del a3
     sums = torch.zeros(n, dtype=torch.float64, device="cuda")
@@ -253,14 +250,9 @@ def test_graph_with_more_than_2_pow_31_edges(gm):
     v = torch.tensor([0.5, -1.0, 2.0, 0.25], device="cuda")
     ya = l(g, v.repeat(n, 1))
     assert float((ya[indeg > 0] - v[None, :]).abs().max()) < 1e-5
-    gm.tune(14, 16)
-    try:
+    with gm.tuned(gm.Knob.FUSED_WAVES, 16):
         gcn = gm.GCNConv((4, 4), "relu", add_self_loops=False, seed=4)
         yf = gcn(g, x)
-    finally:
-        gm.tune(14, -1)
-    try:
+    with gm.tuned(gm.Knob.FUSED_WAVES, -1):
         yu = gcn(g, x)
-    finally:
-        gm.tune(14, 0)
     assert float((yf - yu).abs().max()) <= 1e-5 * float(yu.abs().max())

@@ -113,8 +113,7 @@ def test_placed_layers_are_bit_identical(ar, monkeypatch):
     x = torch.from_numpy(synth.features(N, D, seed=4)).cuda()
     gcn = gnnmp.GCNConv((D, D), "relu", seed=1)
     gat = gnnmp.GATConv((D, 16), "relu", heads=8, seed=2)
-    gnnmp.tune(14, 16)                      # the fused layer kernel on this small graph (the path that takes an output buffer)
-    try:
+    with gnnmp.tuned(gnnmp.Knob.FUSED_WAVES, 16):                      # the fused layer kernel on this small graph (the path that takes an output buffer)
         ref_gcn, ref_gat = gcn(g, x).clone(), gat(g, x).clone()
         gcn.place_outputs = gat.place_outputs = True
         cx = ar.class_of(x)
@@ -135,5 +134,3 @@ def test_placed_layers_are_bit_identical(ar, monkeypatch):
         gcn.place_outputs = gat.place_outputs = False
         c, d = gat(g, x), gat(g, x)
         assert torch.equal(c, ref_gat) and c.data_ptr() != d.data_ptr()
-    finally:
-        gnnmp.tune(14, 0)

@@ -17,8 +17,8 @@ def gm():
     assert torch.cuda.is_available()
     import gnnmp
     gnnmp.load()
-    yield gnnmp
-    gnnmp.tune(16, 0)
+    with gnnmp.tuned(gnnmp.Knob.SOFTMAX_ROWS, 0):
+        yield gnnmp
 
 
 def dev(a):
@@ -39,11 +39,10 @@ def hub_graph(rng, n, E, hubs):
 
 def both_paths(gm, fn):
     import torch
-    gm.tune(16, 0)
-    new = fn()
-    gm.tune(16, -1)
-    old = fn()
-    gm.tune(16, 0)
+    with gm.tuned(gm.Knob.SOFTMAX_ROWS, 0):
+        new = fn()
+    with gm.tuned(gm.Knob.SOFTMAX_ROWS, -1):
+        old = fn()
     torch.cuda.synchronize()
     return new, old
 
@@ -83,12 +82,9 @@ def test_rows_exactly_at_the_batch_and_split_boundaries(gm, oracle):
     for H in (8, 1, 4):
         e = (rng.standard_normal((len(t), H)) * 2).astype(np.float32)
         for thresh in (0, 512, 128):                         # 0 = the plan's own choice (64 at this size)
-            gm.tune(4, thresh)
-            try:
+            with gm.tuned(gm.Knob.LONG_ROW, thresh):
                 g = gm.GNNGraph(dev(s + 1), dev(t + 1), num_nodes=n)
                 new, old = both_paths(gm, lambda: gm.softmax_edge_neighbors(g, dev(e)))
-            finally:
-                gm.tune(4, 0)
             assert torch.equal(new, old)
             np.testing.assert_allclose(new.cpu().numpy(), oracle.softmax_edge_neighbors(t + 1, n, e), rtol=2e-6, atol=1e-12)
 

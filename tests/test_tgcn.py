@@ -324,11 +324,8 @@ def test_fused_and_per_step_paths_agree_and_runs_are_bit_identical():
     a, b = run(), run()
     for u, v in zip(a, b):
         assert torch.equal(u, v), "two runs differ"
-    _lib.tune(_lib.KNOB_TGCN, -1)
-    try:
+    with _lib.tuned(_lib.Knob.TGCN, -1):
         c = run()
-    finally:
-        _lib.tune(_lib.KNOB_TGCN, 0)
     for k, (u, v) in enumerate(zip(a, c)):
         close(u, v, f"fused vs per-step, output {k}")
 

@@ -496,11 +496,8 @@ def test_one_launch_and_per_step_paths_agree(out):
         return [y.detach()] + list(torch.autograd.grad(y, [xd, sd] + layer.cell.parameters(), dy))
 
     a = run()
-    _lib.tune(_lib.KNOB_TGCN, -1)
-    try:
+    with _lib.tuned(_lib.Knob.TGCN, -1):
         b = run()
-    finally:
-        _lib.tune(_lib.KNOB_TGCN, 0)
     assert len(a) == 21
     for k, (u, v) in enumerate(zip(a, b)):
         close(u, v, f"one launch vs per step, output {k}", rtol=A.RTOL)

@@ -50,11 +50,11 @@ def ab(fused, composed, reps, warmup):
     """A, B, A, B: (fused ms, composed ms), each the better of its two medians"""
     def with_knob(fn):
         def run():
-            L.tune(L.KNOB_HETERO, -1)
+            L.tune(L.Knob.HETERO, -1)
             try:
                 fn()
             finally:
-                L.tune(L.KNOB_HETERO, 0)
+                L.tune(L.Knob.HETERO, 0)
         return run
     a1 = timed(fused, reps, warmup)
     b1 = timed(with_knob(composed), reps, warmup)

@@ -49,12 +49,12 @@ def adjoint_ab(g, D, reps, warmup):
     outs = {}
     for rnd in range(2):                      # A, B, A, B: the spread between rounds is the box noise
         for path, kv in (("fused", 0), ("composed", -1)):
-            _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, kv)
+            _lib.tune(_lib.Knob.EDGE_DOT_GRAD, kv)
             try:
                 row.setdefault(path + "_ms", []).append(timed(fn, reps, warmup))
                 outs[path] = fn()[0]
             finally:
-                _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, 0)
+                _lib.tune(_lib.Knob.EDGE_DOT_GRAD, 0)
     row["max_rel_diff"] = float((outs["fused"] - outs["composed"]).abs().max() / outs["composed"].abs().max().clamp(min=1e-30))
     row["speedup"] = min(row["composed_ms"]) / min(row["fused_ms"])
     return row
@@ -105,11 +105,11 @@ def main():
 
     for rnd in range(2):                      # the step with the fused adjoint and with the composition, alternated
         for kv, name in ((0, "train_step_ms"), (-1, "train_step_composed_adjoint_ms")):
-            _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, kv)
+            _lib.tune(_lib.Knob.EDGE_DOT_GRAD, kv)
             try:
                 pub.setdefault(name, []).append(timed(step, a.reps, a.warmup))
             finally:
-                _lib.tune(_lib.KNOB_EDGE_DOT_GRAD, 0)
+                _lib.tune(_lib.Knob.EDGE_DOT_GRAD, 0)
     for _ in range(a.reps):
         step(probe=True)
     torch.cuda.synchronize()

@@ -83,13 +83,13 @@ def main():
         row = {"N": g.num_nodes, "E": g.num_edges, "T": T, "in": 2, "out": 100}
         outs = {}
         for path, kv in (("fused", 0), ("per_step", -1)):
-            _lib.tune(_lib.KNOB_TGCN, kv)
+            _lib.tune(_lib.Knob.TGCN, kv)
             try:
                 row[path + "_fwd_ms"] = timed(fwd, a.reps, a.warmup)
                 row[path + "_fwdbwd_ms"] = timed(fwdbwd, a.reps, a.warmup)
                 outs[path] = [fwd()] + list(fwdbwd())
             finally:
-                _lib.tune(_lib.KNOB_TGCN, 0)
+                _lib.tune(_lib.Knob.TGCN, 0)
         row["max_rel_diff"] = max(float((u - v).abs().max() / v.abs().max().clamp(min=1e-30))
                                   for u, v in zip(outs["fused"], outs["per_step"]))
         row["fwd_speedup"] = row["per_step_fwd_ms"] / row["fused_fwd_ms"]

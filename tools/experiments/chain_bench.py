@@ -31,8 +31,8 @@ model = gnnmp.GNNChain(gnnmp.GraphConv((16, 128), "relu", seed=21), gnnmp.GraphC
                        gnnmp.GlobalPool("mean"), gnnmp.Dense((128, 2), seed=23))
 f = lambda: model(g, g.x)
 y = f()
-for name, knobs in (("fused chain kernel", ()), ("layer by layer, split-bf16 dense", ((18, -1),)),
-                    ("layer by layer, fp32-MFMA dense (round 2)", ((18, -1), (17, -1)))):
+for name, knobs in (("fused chain kernel", ()), ("layer by layer, split-bf16 dense", ((gnnmp.Knob.CHAIN, -1),)),
+                    ("layer by layer, fp32-MFMA dense (round 2)", ((gnnmp.Knob.CHAIN, -1), (gnnmp.Knob.DENSE_SPLIT, -1)))):
     for k, v in knobs:
         gnnmp.tune(k, v)
     y2 = f()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Cycle stamps of block (0, 0) of graph_chain2_kernel (library built with EXTRA=-DGNNMP_CHAIN_TRACE): per wave and job, the cycles
+"""Cycle stamps of block (0, 0) of graph_chain2_kernel (library built with make EXPERIMENTS=1, used through GNNMP_LIB): per wave and job, the cycles
 spent in each phase."""
 import os, sys, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

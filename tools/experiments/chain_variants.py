@@ -33,7 +33,7 @@ model = gnnmp.GNNChain(gnnmp.GraphConv((16, 128), "relu", seed=21), gnnmp.GraphC
 y0 = None
 variants = [int(v) for v in os.environ.get('VARIANTS', '3,0,1,2').split(',')]
 for kv in variants:
-    gnnmp.tune(19, kv)
+    gnnmp.tune(gnnmp.Knob.VARIANT, kv)
     g = gnnmp.batch_arrays(members, xs)          # (a fresh graph: the jobs are built under this knob value)
     f = lambda: model(g, g.x)
     y = f()
@@ -41,4 +41,4 @@ for kv in variants:
         y0 = y
     cj = g._cache.get("chain_jobs"); info = (cj.njobs, cj.fill) if cj is not None else None
     print(f"chain2 knob19={kv}: {t(f)*1e3:7.1f} us  max diff {float((y - y0).abs().max()):.1e}  jobs {info}", flush=True)
-gnnmp.tune(19, 0)
+gnnmp.tune(gnnmp.Knob.VARIANT, 0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Chunk length of split rows (GNNMP_CHUNK_SLOTS at plan build: 512 = rounds 1-5, 128 = round 6) on the products shape: the fused GCN layer
+"""Chunk length of split rows (Knob.CHUNK_SLOTS, read at plan build: 512 = rounds 1-5, 128 = round 6) on the products shape: the fused GCN layer
 (whose pre-pass over the split rows runs alone), the scaled propagate, the attention kernel and SAGE's mean aggregation.  One box."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,15 +27,15 @@ def med(fn, it=15):
 
 outs = {}
 for rnd in range(2):
-    for cs in ("512", "128", "64"):
-        os.environ["GNNMP_CHUNK_SLOTS"] = cs
+    for cs in (512, 128, 64):
         g = gnnmp.GNNGraph(sd, td, num_nodes=N, _validated=True)
-        p = g.plan(True)
+        with gnnmp.tuned(gnnmp.Knob.CHUNK_SLOTS, cs):       # every plan the layers below use is built here, under the knob
+            p, p0 = g.plan(True), g.plan(False)
         gcn = gnnmp.GCNConv((D, D), "relu", seed=11)
         gat = gnnmp.GATConv((D, 16), "relu", heads=8, seed=12)
         y = gcn(g, x)
         outs.setdefault(cs, y.clone())
-        print(f"round {rnd} chunk slots {cs:>4s}: GCN layer {med(lambda: gcn(g, x)):.3f} ms | GAT layer {med(lambda: gat(g, x)):.3f} ms | "
+        print(f"round {rnd} chunk slots {cs:>4d}: GCN layer {med(lambda: gcn(g, x)):.3f} ms | GAT layer {med(lambda: gat(g, x)):.3f} ms | "
               f"propagate(mean) {med(lambda: gnnmp.propagate(gnnmp.copy_xj, g, 'mean', xj=x)):.3f} ms | max |y - y_512| / max|y| "
-              f"{float((y - outs['512']).abs().max() / outs['512'].abs().max()):.1e}", flush=True)
-        del g, p
+              f"{float((y - outs[512]).abs().max() / outs[512].abs().max()):.1e}", flush=True)
+        del g, p, p0

@@ -26,10 +26,10 @@ for (N, K, Dout, two) in [(2449029, 100, 100, False), (2449029, 100, 128, False)
     byts = 4.0 * N * ((2 * K if two else K) + Dout)
     res = []
     for name, k6, k7 in (("wlds+pf", 0, 1), ("wlds", 0, 0), ("chunk", 1, 1)):
-        gnnmp.tune(6, k6)
-        gnnmp.tune(7, k7)
+        gnnmp.tune(gnnmp.Knob.DENSE_GENERIC, k6)
+        gnnmp.tune(gnnmp.Knob.DENSE_PREFETCH, k7)
         ms = t(f)
         res.append(f"{name} {ms:7.3f} ms {flops/ms/1e9:6.1f} TF {byts/ms/1e6:6.0f} GB/s")
-    gnnmp.tune(6, 0)
-    gnnmp.tune(7, 1)
+    gnnmp.tune(gnnmp.Knob.DENSE_GENERIC, 0)
+    gnnmp.tune(gnnmp.Knob.DENSE_PREFETCH, 1)
     print(f"N={N} K={K}{'x2' if two else ''} Dout={Dout}: " + " | ".join(res))

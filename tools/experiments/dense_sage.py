@@ -30,12 +30,12 @@ for (N, K, Dout, two) in [(2449029, 100, 128, False), (2449029, 100, 256, True),
     res = {0: [], 32: [], 16: []}
     same = True
     for rep in range(4):                      # interleaved: clocks drift by 10 % over the first seconds of a run
-        for kv in (0, 32, 16):
-            gnnmp.tune(19, kv)
+        for kv in (0, int(gnnmp.Variant.SPLIT_DIRECT_STORES), int(gnnmp.Variant.SPLIT_SERIAL_TILES)):
+            gnnmp.tune(gnnmp.Knob.VARIANT, kv)
             same = same and bool(torch.equal(f(), y0))
             res[kv].append(t(f, 10))
-    for kv in (0, 32, 16):
+    for kv in (0, int(gnnmp.Variant.SPLIT_DIRECT_STORES), int(gnnmp.Variant.SPLIT_SERIAL_TILES)):
         row.append(f"knob19={kv}: {sorted(res[kv])[1]*1e3:8.1f} us")
     row.append(f"equal={same}")
-    gnnmp.tune(19, 0)
+    gnnmp.tune(gnnmp.Knob.VARIANT, 0)
     print(f"N={N} K={K}{'+' + str(K) if two else ''} Dout={Dout}: " + "   ".join(row), flush=True)

@@ -15,7 +15,7 @@ for (N, K, Dout) in [(2449029, 100, 100), (2449029, 100, 128), (169343, 128, 128
     x = torch.randn((N, K), device="cuda"); W = torch.randn((Dout, K), device="cuda") * 0.1; b = torch.randn(Dout, device="cuda")
     res = []
     for sk in (0, 3, 16, 17, 19):
-        gnnmp.tune(7, sk)
+        gnnmp.tune(gnnmp.Knob.DENSE_PREFETCH, sk)
         res.append(f"knob{sk}: {t(lambda: gnnmp.dense(x, W, b, 'relu')):.3f}")
-    gnnmp.tune(7, 0)
+    gnnmp.tune(gnnmp.Knob.DENSE_PREFETCH, 0)
     print(f"N={N} K={K} Dout={Dout}: " + " | ".join(res))

@@ -36,13 +36,13 @@ for (N, K, Dout, two) in [(2449029, 100, 100, False), (2449029, 100, 128, False)
     ref = torch.relu(pre)
     res = []
     for name, k17 in (("split", 0), ("fp32-mfma", -1)):
-        gnnmp.tune(17, k17)
+        gnnmp.tune(gnnmp.Knob.DENSE_SPLIT, k17)
         for wv in ((0, 4, 8) if name == "split" else (0,)):
-            gnnmp.tune(12, wv)
+            gnnmp.tune(gnnmp.Knob.DENSE_T16_WAVES, wv)
             y = f()
             err = float(((y[rows].double() - ref).abs() / mag).max())
             ms = t(f)
             res.append(f"{name}{'' if wv == 0 else f'/w{wv}'} {ms*1e3:7.1f} us {flops/ms/1e9:6.1f} TF-equivalent ({flops/ms/1e9/PEAK*100:5.1f}% of the fp32 "
                        f"MFMA peak) {byts/ms/1e6:5.0f} GB/s  max err/sum|wx| {err:.1e}")
-    gnnmp.tune(17, 0); gnnmp.tune(12, 0)
+    gnnmp.tune(gnnmp.Knob.DENSE_SPLIT, 0); gnnmp.tune(gnnmp.Knob.DENSE_T16_WAVES, 0)
     print(f"N={N} K={K}{'x2' if two else ''} Dout={Dout}:\n   " + "\n   ".join(res), flush=True)

@@ -40,13 +40,13 @@ for (N, K, Dout, two) in [(2449029, 100, 100, False), (2449029, 100, 128, False)
     ref = torch.relu(xin.double() @ W.double().t() + b.double())
     res = []
     for name, k6 in (("t16", 0), ("r1", 2)):
-        gnnmp.tune(6, k6)
+        gnnmp.tune(gnnmp.Knob.DENSE_GENERIC, k6)
         for wv in (sweep if name == "t16" else [0]):
-            gnnmp.tune(12, wv)
+            gnnmp.tune(gnnmp.Knob.DENSE_T16_WAVES, wv)
             y = f()
             err = float((y[rows].double() - ref).abs().max() / ref.abs().max())
             ms = t(f)
             res.append(f"{name}{'' if wv == 0 else f'/w{wv}'} {ms*1e3:7.1f} us {flops/ms/1e9:6.1f} TF ({flops/ms/1e9/PEAK*100:4.1f}%) "
                        f"{byts/ms/1e6:5.0f} GB/s err {err:.1e}")
-    gnnmp.tune(6, 0); gnnmp.tune(12, 0)
+    gnnmp.tune(gnnmp.Knob.DENSE_GENERIC, 0); gnnmp.tune(gnnmp.Knob.DENSE_T16_WAVES, 0)
     print(f"N={N} K={K}{'x2' if two else ''} Dout={Dout}:\n   " + "\n   ".join(res), flush=True)

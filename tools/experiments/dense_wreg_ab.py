@@ -32,11 +32,11 @@ for (N, K1, K2) in SHAPES:
     res = {0: [], 64: []}
     ys = {}
     for rep in range(4):
-        for kv in (0, 64):
-            gnnmp.tune(19, kv)
+        for kv in (0, int(gnnmp.Variant.NO_WREG)):
+            gnnmp.tune(gnnmp.Knob.VARIANT, kv)
             ys[kv] = f()
             res[kv].append(t(f))
-    gnnmp.tune(19, 0)
+    gnnmp.tune(gnnmp.Knob.VARIANT, 0)
     ref = (torch.cat([x, m], 1) if two else x).double() @ W.double().T + b.double()
     ref = torch.relu(ref)
     e0 = (ys[0].double() - ref).abs().max().item(); e64 = (ys[64].double() - ref).abs().max().item()

@@ -20,7 +20,7 @@ x = torch.from_numpy(synth.features(N, D, seed=1)).cuda()
 gcn = gnnmp.GCNConv((D, D), "relu", seed=11); gat = gnnmp.GATConv((D, 16), "relu", heads=8, seed=12)
 p = g.plan(True); print(shape, "thresh", p.long_thresh, "long", p.n_long, "maxdeg", p.max_degree, flush=True)
 fns = {"gcn": lambda: gcn(g, x), "gat": lambda: gat(g, x), "propagate": lambda: gnnmp.propagate(gnnmp.copy_xj, g, "+", xj=x)}
-base = gnnmp.knob(19)
+base = gnnmp.knob(gnnmp.Knob.VARIANT)
 def timed(f):
     for _ in range(10): f()
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -29,8 +29,8 @@ def timed(f):
 for rep in range(3):
     for name, f in fns.items():
         out = {}
-        for label, kv in (("fold", base & ~128), ("two-kernel", base | 128)):
-            gnnmp.tune(19, kv)
+        for label, kv in (("fold", base & ~gnnmp.Variant.TWO_KERNEL_FOLD), ("two-kernel", base | gnnmp.Variant.TWO_KERNEL_FOLD)):
+            gnnmp.tune(gnnmp.Knob.VARIANT, kv)
             out[label] = timed(f)
         print(f"rep {rep} {name:10s} fold {out['fold']:.4f} ms   two-kernel {out['two-kernel']:.4f} ms", flush=True)
-gnnmp.tune(19, base)
+gnnmp.tune(gnnmp.Knob.VARIANT, base)

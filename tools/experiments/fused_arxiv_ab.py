@@ -20,8 +20,8 @@ variants = sys.argv[1:] or ["0", "16", "12", "10", "8", "6"]
 for rep in range(2):
     for v in variants:
         kv = int(v)
-        gnnmp.tune(14, kv)
+        gnnmp.tune(gnnmp.Knob.FUSED_WAVES, kv)
         y = gcn(g, x)
         err = float((y - ref).abs().max())
         print(f"rep {rep} variant {v:>4s}  gcn layer {timed(lambda: gcn(g, x)):.4f} ms   max|diff| vs unfused {err:.2e}", flush=True)
-gnnmp.tune(14, 0)
+gnnmp.tune(gnnmp.Knob.FUSED_WAVES, 0)

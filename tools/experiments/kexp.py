@@ -19,13 +19,13 @@ import gnnmp  # noqa: E402
 from gnnmp import _lib as L  # noqa: E402
 from gnnmp import synth  # noqa: E402
 
-KNOBS = {"vec": 0, "log2g": 1, "unroll": 2, "xcd": 3, "long": 4, "waves": 5}
-DEFAULTS = {"vec": 0, "log2g": -1, "unroll": 0, "xcd": 1, "long": 0, "waves": 0}
+KNOBS = {"vec": gnnmp.Knob.FORCE_VEC, "log2g": gnnmp.Knob.FORCE_LOG2G, "unroll": gnnmp.Knob.UNROLL, "xcd": gnnmp.Knob.XCD_REMAP,
+         "long": gnnmp.Knob.LONG_ROW, "waves": gnnmp.Knob.BLOCK_WAVES}
 
 
 def set_knobs(**kw):
-    for k, v in DEFAULTS.items():
-        gnnmp.tune(KNOBS[k], kw.get(k, v))
+    for name, k in KNOBS.items():
+        gnnmp.tune(k, kw.get(name, L.knob_default(k)))
 
 
 def time_fn(fn, iters=10):

@@ -34,7 +34,7 @@ variants = [("two kernels, fresh buffers", -1, False), ("two kernels, placed m +
             ("fused_cat 8 waves", 8, False)]
 for r in range(rounds):
     for name, k14, placed in variants:
-        gnnmp.tune(14, k14)
+        gnnmp.tune(gnnmp.Knob.FUSED_WAVES, k14)
         sage.place_outputs = sage.persistent_out = placed
         med, avg = measure()
         y = sage(g, x)
@@ -45,9 +45,9 @@ for r in range(rounds):
 # ablations of the fused kernel (knob 13: 1 = no contraction, 2 = no gather, 4 = no stores) — wrong results, timings only
 for k14 in (16, 8):
     for dbg, what in ((0, "whole kernel"), (1, "no contraction"), (2, "no gather"), (3, "neither (hand-out + stores of nothing)"), (4, "no stores")):
-        gnnmp.tune(14, k14); gnnmp.tune(13, dbg)
+        gnnmp.tune(gnnmp.Knob.FUSED_WAVES, k14); gnnmp.tune(gnnmp.Knob.T16_DEBUG, dbg)
         sage.place_outputs = sage.persistent_out = False
         med, avg = measure()
         print(f"ablation knob14={k14:2d} knob13={dbg}: {what:40s} median {med:.3f} ms", flush=True)
-gnnmp.tune(13, 0)
-gnnmp.tune(14, 0)
+gnnmp.tune(gnnmp.Knob.T16_DEBUG, 0)
+gnnmp.tune(gnnmp.Knob.FUSED_WAVES, 0)
