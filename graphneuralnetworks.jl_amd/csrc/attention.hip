@@ -252,8 +252,7 @@ __global__ void __launch_bounds__(1024) gat_long_rows_kernel(const GatArgs a) {
 template <int VEC>
 static int launch_gat(GatArgs a, hipStream_t stream) {
     const int G = 1 << a.geom.log2g;
-    int waves = knob(KNOB_BLOCK_WAVES);
-    if (waves < 1 || waves > 4) waves = 1;   // auto (see gat_fused.hip)
+    const int waves = block_waves(1);   // auto (see gat_fused.hip)
     a.geom.waves = waves;
     const int lanes_needed = (a.D + VEC - 1) / VEC;
     const int tiles = (lanes_needed + G - 1) / G;
@@ -336,8 +335,7 @@ int gnnmp_gat_aggregate_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
     a.D = (int)(H * C);
     a.slope = negative_slope;
     // the lane's VEC features must lie inside one head
-    int vec = pick_vec(a.D, Wx_src, out);
-    while (vec > 1 && (C % vec) != 0) vec >>= 1;
+    const int vec = head_vec(C, pick_vec(a.D, Wx_src, out));
     a.geom = RowGeom{pick_log2g((a.D + vec - 1) / vec), 4, 0, 0};
     return with_vec(vec, [&](auto V) { return launch_gat<decltype(V)::value>(a, stream); });
 }

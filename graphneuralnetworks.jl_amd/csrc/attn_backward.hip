@@ -14,6 +14,7 @@
 // Long rows are chunked into virtual rows; partials are folded in chunk order.  No atomics.
 #include <algorithm>
 
+#include "launch.h"
 #include "rowwalk.h"
 
 namespace gnnmp {
@@ -358,37 +359,6 @@ __global__ void __launch_bounds__(256) attn_bwd_src_combine_kernel(const AttnBwd
     attn_src_store<VEC, MODE>(a, row, f0, dk, dv);
 }
 
-// da[h][c] = Σ_i dA[i][h*C + c]: slab partials, folded in slab order
-__global__ void __launch_bounds__(256) attn_colsum_partial_kernel(const float *x, int64_t N, int D, int64_t R, float *part) {
-    const int64_t r0 = (int64_t)blockIdx.x * R, r1 = min(N, r0 + R);
-    for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        float acc = 0.0f;
-        int64_t r = r0;
-        for (; r + 8 <= r1; r += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = x[(r + u) * D + d];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = acc + v[u];
-        }
-        for (; r < r1; ++r) acc = acc + x[r * D + d];
-        part[(int64_t)blockIdx.x * D + d] = acc;
-    }
-}
-__global__ void __launch_bounds__(256) attn_colsum_fold_kernel(const float *part, int nparts, int D, float *out) {
-    __shared__ float red[256];
-    const int d = blockIdx.x;
-    float acc = 0.0f;
-    for (int p = threadIdx.x; p < nparts; p += 256) acc = acc + part[(int64_t)p * D + d];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[d] = red[0];
-}
-
 template <int VEC, int LPH, int MODE, bool DROP>
 static int launch_attn_bwd(AttnBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *da, hipStream_t stream) {
     g.rows = plan_rows(plan);
@@ -420,32 +390,23 @@ static int launch_attn_bwd(AttnBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t
         }
     }
     if (MODE == GNNMP_ATTN_GATV2 && da) {
+        // da[h][c] = Σ_i dA[i][h*C + c]: slab partials, folded in slab order
         const int64_t N = plan->n_dst;
-        const int64_t R = std::max<int64_t>(256, (N + 2047) / 2048);
-        const int nparts = (int)((N + R - 1) / R);
-        attn_colsum_partial_kernel<<<nparts, 256, 0, stream>>>(g.dA, N, g.D, R, plan->ws);
-        GNNMP_LAUNCH_CHECK("attn_colsum_partial_kernel");
-        attn_colsum_fold_kernel<<<g.D, 256, 0, stream>>>(plan->ws, nparts, g.D, da);
-        GNNMP_LAUNCH_CHECK("attn_colsum_fold_kernel");
+        const int nparts = colsum_parts(N);
+        GNNMP_TRY(colsum_partial(g.dA, nullptr, N, g.D, g.D, colsum_slab_rows(N), nparts, plan->ws, stream));
+        GNNMP_TRY(colsum_tree_fold(plan->ws, nparts, g.D, g.D, g.D, 0, da, stream));
     }
     return GNNMP_OK;
 }
 
 template <int MODE>
-static int dispatch_attn_bwd(const AttnBwdArgs &g, int vec, int lph, gnnmp_graph *plan, gnnmp_graph *plan_t, float *da,
+static int dispatch_attn_bwd(const AttnBwdArgs &g, const HeadGeom &hg, gnnmp_graph *plan, gnnmp_graph *plan_t, float *da,
                              hipStream_t stream) {
-    if (vec == 4) {
-        switch (lph) {
-            case 1: return launch_attn_bwd<4, 1, MODE, false>(g, plan, plan_t, da, stream);
-            case 2: return launch_attn_bwd<4, 2, MODE, false>(g, plan, plan_t, da, stream);
-            case 4: return launch_attn_bwd<4, 4, MODE, false>(g, plan, plan_t, da, stream);
-            case 8: return launch_attn_bwd<4, 8, MODE, false>(g, plan, plan_t, da, stream);
-            case 16: return launch_attn_bwd<4, 16, MODE, false>(g, plan, plan_t, da, stream);
-            default: return launch_attn_bwd<4, 0, MODE, false>(g, plan, plan_t, da, stream);
-        }
-    }
-    if (vec == 2) return launch_attn_bwd<2, 0, MODE, false>(g, plan, plan_t, da, stream);
-    return launch_attn_bwd<1, 0, MODE, false>(g, plan, plan_t, da, stream);
+    return with_vec(hg.vec, [&](auto V) {
+        return with_lph<decltype(V)::value, 16>(hg.lph, [&](auto L) {
+            return launch_attn_bwd<decltype(V)::value, decltype(L)::value, MODE, false>(g, plan, plan_t, da, stream);
+        });
+    });
 }
 
 }  // namespace gnnmp
@@ -473,8 +434,7 @@ static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, AttnG
     if (c.mode != GNNMP_ATTN_GATV2 && c.mode != GNNMP_ATTN_DOT)
         return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: mode %d (GAT has gnnmp_gat_conv_grad_f32; the cosine logit has no pullback yet)", c.mode);
     if (c.H <= 0 || c.C <= 0 || c.H * c.C > (1 << 20)) return fail(GNNMP_EINVAL, "attn_conv_grad: bad H/C");
-    if (plan_t->n_dst != plan->n_src || plan_t->n_src != plan->n_dst || plan_t->n_total != plan->n_total)
-        return fail(GNNMP_EINVAL, "attn_conv_grad: plan_t is not the transpose of plan");
+    GNNMP_TRY(check_transposed("attn_conv_grad", plan, plan_t));
     if (plan->n_dst == 0 && plan->n_src == 0) return GNNMP_OK;
     if (!c.V) c.V = c.K;
     if (c.mode == GNNMP_ATTN_GATV2 && c.V != c.K) return fail(GNNMP_EINVAL, "attn_conv_grad: GATV2 has V = K");
@@ -483,19 +443,12 @@ static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, AttnG
         return fail(GNNMP_EINVAL, "attn_conv_grad: null pointer");
     if ((reinterpret_cast<uintptr_t>(c.line) & 15) != 0) return fail(GNNMP_EINVAL, "attn_conv_grad: line must be 16-byte aligned");
     const int D = (int)(c.H * c.C);
-    int vec = narrow_vec(pick_vec(D, c.K, c.dK), c.Q, c.V, c.dout, c.dQ, c.dV, c.dA);
-    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
-    int lph = (int)(c.C / vec);
-    const int lanes = D / vec;
-    int log2g = 0;
-    while ((1 << log2g) < lanes) ++log2g;
-    if (c.H == 1 && lanes <= 64) lph = 1 << log2g;
-    if (lanes > 64)
+    const HeadGeom hg = head_geom(c.H, c.C, narrow_vec(pick_vec(D, c.K, c.dK), c.Q, c.V, c.dout, c.dQ, c.dV, c.dA));
+    if (!hg.fits_wave)
         return fail(GNNMP_EUNSUPPORTED, "attn_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(c.H * c.C));
     const int NA = c.mode == GNNMP_ATTN_GATV2 ? 4 : 2;
-    const int64_t R = std::max<int64_t>(256, (plan->n_dst + 2047) / 2048);
-    const size_t colsum_need = (size_t)((plan->n_dst + R - 1) / R) * (size_t)D;
-    if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * ((size_t)NA * D + lanes), colsum_need))) return rc;
+    const size_t colsum_need = (size_t)colsum_parts(plan->n_dst) * (size_t)D;
+    if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * ((size_t)NA * D + hg.lanes), colsum_need))) return rc;
     if (plan_t->n_chunks > 0)
         if (int rc = ensure_workspace(plan_t, (size_t)plan_t->n_chunks * 2 * (size_t)D)) return rc;
     AttnBwdArgs g;
@@ -513,16 +466,16 @@ static int attn_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, AttnG
     g.H = (int)c.H;
     g.C = (int)c.C;
     g.D = D;
-    g.geom = RowGeom{log2g, 1, 0, 0};
-    g.lph = lph_code(lph, log2g);
+    g.geom = RowGeom{hg.log2g, 1, 0, 0};
+    g.lph = hg.lph_code;
     g.slope = c.negative_slope;
     g.scale = c.scale;
     g.drop = make_drop(c.drop_p, c.drop_seed);
     if (c.drop_p > 0.0f) {       // (the dropout variants walk the head butterfly with the run-time lane count: one instantiation per width)
-        return with_vec(vec, [&](auto W) { return launch_attn_bwd<decltype(W)::value, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, c.da, stream); });
+        return with_vec(hg.vec, [&](auto W) { return launch_attn_bwd<decltype(W)::value, 0, GNNMP_ATTN_GATV2, true>(g, plan, plan_t, c.da, stream); });
     }
-    if (c.mode == GNNMP_ATTN_GATV2) return dispatch_attn_bwd<GNNMP_ATTN_GATV2>(g, vec, lph, plan, plan_t, c.da, stream);
-    return dispatch_attn_bwd<GNNMP_ATTN_DOT>(g, vec, lph, plan, plan_t, c.da, stream);
+    if (c.mode == GNNMP_ATTN_GATV2) return dispatch_attn_bwd<GNNMP_ATTN_GATV2>(g, hg, plan, plan_t, c.da, stream);
+    return dispatch_attn_bwd<GNNMP_ATTN_DOT>(g, hg, plan, plan_t, c.da, stream);
 }
 
 // what the two exports share (their arguments in the exports' order)

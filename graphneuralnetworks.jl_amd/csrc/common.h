@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "gnnmp.h"
+#include "headgeom.h"
 #include "knobs.h"
 
 namespace gnnmp {
@@ -77,6 +78,11 @@ int knob(int k);
 // the knobs the host layers gate on are read there by these numbers (gnnmp/knobs.py): KNOB_FUSED_WAVES = 14, KNOB_TGCN = 20,
 // KNOB_EDGE_DOT_GRAD = 21, KNOB_HETERO = 22
 static_assert(KNOB_FUSED_WAVES == 14 && KNOB_TGCN == 20 && KNOB_EDGE_DOT_GRAD == 21 && KNOB_HETERO == 22, "knobs.h: indices never change");
+// waves per block of a row kernel: KNOB_BLOCK_WAVES if it lies in 1..4, otherwise the call site's own choice
+inline int block_waves(int auto_value) {
+    const int w = knob(KNOB_BLOCK_WAVES);
+    return w >= 1 && w <= 4 ? w : auto_value;
+}
 int device_cus();   // compute units of the current device, queried once (hipDeviceGetAttribute costs microseconds per call)
 
 // ---- device helpers ---------------------------------------------------------------------------
@@ -262,7 +268,7 @@ template <int LPH>
 __device__ __forceinline__ float group_sum(float d, int lph) {
     if (LPH == 0) {
         if (lph & 0x10000) {
-            // a head of n lanes, n NOT a power of two (lph_code below): every lane reads its head's n lanes in order —
+            // a head of n lanes, n NOT a power of two (headgeom.h: lph_code): every lane reads its head's n lanes in order —
             // n ds_bpermutes instead of log2(n) DPP steps, the price of odd head widths (e.g. C = 7 classes)
             const int n = lph & 0xff, G = 1 << ((lph >> 8) & 0xff);
             const int lane = (int)__lane_id(), lig = lane & (G - 1);
@@ -281,11 +287,6 @@ __device__ __forceinline__ float group_sum(float d, int lph) {
     if (LPH >= 32) d += __shfl_xor(d, 16, 64);
     if (LPH >= 64) d += __shfl_xor(d, 32, 64);
     return d;
-}
-
-// what the kernels get as `lph`: the lane count itself when it is a power of two, otherwise a code group_sum<0> decodes
-inline int lph_code(int lph, int log2g) {
-    return (lph & (lph - 1)) == 0 ? lph : (0x10000 | (log2g << 8) | lph);
 }
 
 // block -> logical chunk remap so that each XCD (block b runs on XCD b % 8) walks a contiguous range of
@@ -449,6 +450,24 @@ inline auto with_vec(int vec, F &&f) {   // 4 | 2 | anything else: 1
         case 2: return f(int_c<2>{});
         default: return f(int_c<1>{});
     }
+}
+// The lane count of one attention head (HeadGeom::lph) as the kernels' LPH: f(int_c<lph>{}) — DPP butterflies — for VEC = 4 and a power
+// of two up to MAX, f(int_c<0>{}) — the butterfly on the run-time count, or the lane-by-lane sum of an odd head width — for the rest.
+// VEC is a template argument so that the 2- and 1-wide instances exist for LPH = 0 only.
+template <int VEC, int MAX, class F>
+inline auto with_lph(int lph, F &&f) {
+    if constexpr (VEC == 4) {
+        switch (lph <= MAX ? lph : 0) {
+            case 1: return f(int_c<1>{});
+            case 2: return f(int_c<2>{});
+            case 4: return f(int_c<4>{});
+            case 8: return f(int_c<8>{});
+            case 16: return f(int_c<16>{});
+            case 32: return f(int_c<(MAX >= 32 ? 32 : 0)>{});
+            case 64: return f(int_c<(MAX >= 64 ? 64 : 0)>{});
+        }
+    }
+    return f(int_c<0>{});
 }
 template <class F>
 inline auto with_op(int op, F &&f) {   // OP_SUM | OP_MAX | anything else: OP_MIN

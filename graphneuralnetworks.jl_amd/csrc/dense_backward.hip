@@ -2,7 +2,7 @@
 //   y = σ.(W * x .+ b)   =>   Δz = Δy .* σ'(z),   ΔW = Δz * x',   Δb = sum(Δz, dims = 2),   Δx = W' * Δz
 // Δx is the FORWARD kernel with the weight read transposed (gnnmp_dense_f32(Δz, W, w_layout = 1)).  New here:
 //   act_grad_kernel   Δz = Δy .* (y > 0)            (NNlib: relu'(x) = x > 0; y > 0 <=> x > 0)
-//   colsum_*          Δb, deterministic two-stage column sums
+//   colsum_*          Δb, deterministic two-stage column sums; shared with the attention pullbacks' da (launch.h: column sums)
 //   dense_gradw_*     ΔW[o][k] = Σ_n Δz[n][o] * x[n][k]: a GEMM whose reduction dimension is N (millions).  Both MFMA
 //                     operands of v_mfma_f32_32x32x2_f32 are then read straight from HBM in their natural row-major
 //                     layout (lane l holds Δz[n + l/32][o0 + l%32] and x[n + l/32][k0 + l%32]: 128-byte segments), no LDS.
@@ -10,7 +10,7 @@
 //                     partials in slab order (no atomics: run-to-run identical).
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -56,24 +56,68 @@ __global__ void __launch_bounds__(256) pool_grad_act_kernel(const float *__restr
     Vec<V>::store(dz + i * D + c, v);
 }
 
-// stage 1: block b sums rows [b*R, (b+1)*R) of x[N][D] for every column -> part[b][D]
-__global__ void __launch_bounds__(256) colsum_partial_kernel(const float *x, int64_t N, int D, int64_t R,
+// stage 1: block b sums rows [b*R, (b+1)*R) of x[N][D] for every column -> part[b][D]; WEIGHTED: of s[r][d / C] * x[r][d]
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(256) colsum_partial_kernel(const float *x, const float *s, int64_t N, int D, int C, int64_t R,
                                                              float *part) {
+    const int H = D / C;
     const int64_t r0 = (int64_t)blockIdx.x * R;
     const int64_t r1 = min(N, r0 + R);
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
+        const int h = WEIGHTED ? d / C : 0;
         float acc = 0.0f;
         int64_t r = r0;
         for (; r + 8 <= r1; r += 8) {          // 8 independent loads in flight, added in row order
-            float v[8];
+            float v[8], sv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = x[(r + u) * D + d];
+            for (int u = 0; u < 8; ++u) {
+                v[u] = x[(r + u) * D + d];
+                sv[u] = WEIGHTED ? s[(r + u) * H + h] : 1.0f;
+            }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) acc = acc + v[u];
+            for (int u = 0; u < 8; ++u) acc = WEIGHTED ? fmaf(sv[u], v[u], acc) : acc + v[u];
         }
-        for (; r < r1; ++r) acc = acc + x[r * D + d];
+        for (; r < r1; ++r) acc = WEIGHTED ? fmaf(s[r * H + h], x[r * D + d], acc) : acc + x[r * D + d];
         part[(int64_t)blockIdx.x * D + d] = acc;
     }
+}
+// The tree fold: one block per column d, thread k adds parts k, k + 256, ... in order, then a fixed-shape tree over the 256 sums in
+// LDS (deterministic; a serial walk over 2048 parts cost 0.48 ms).
+__global__ void __launch_bounds__(256) colsum_tree_fold_kernel(const float *part, int nparts, int D, int C, int out_ld, int off,
+                                                               float *out) {
+    __shared__ float red[256];
+    const int d = blockIdx.x;
+    float acc = 0.0f;
+    for (int p = threadIdx.x; p < nparts; p += 256) acc = acc + part[(int64_t)p * D + d];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int h = d / C;
+        out[(int64_t)h * out_ld + off + (d - h * C)] = red[0];
+    }
+}
+int64_t colsum_slab_rows(int64_t N) { return std::max<int64_t>(256, (N + 2047) / 2048); }
+int colsum_parts(int64_t N) {
+    const int64_t R = colsum_slab_rows(N);
+    return (int)((N + R - 1) / R);
+}
+int colsum_partial(const float *x, const float *s, int64_t N, int D, int C, int64_t R, int nparts, float *part, hipStream_t stream) {
+    if (nparts <= 0) return GNNMP_OK;
+    if (s)
+        colsum_partial_kernel<true><<<(unsigned)nparts, 256, 0, stream>>>(x, s, N, D, C, R, part);
+    else
+        colsum_partial_kernel<false><<<(unsigned)nparts, 256, 0, stream>>>(x, s, N, D, C, R, part);
+    GNNMP_LAUNCH_CHECK("colsum_partial_kernel");
+    return GNNMP_OK;
+}
+int colsum_tree_fold(const float *part, int nparts, int D, int C, int out_ld, int off, float *out, hipStream_t stream) {
+    colsum_tree_fold_kernel<<<(unsigned)D, 256, 0, stream>>>(part, nparts, D, C, out_ld, off, out);
+    GNNMP_LAUNCH_CHECK("colsum_tree_fold_kernel");
+    return GNNMP_OK;
 }
 // out[g][i] = Σ_{p in group g} part[p][i], parts added in order, 8 loads in flight; blockIdx.y = group of `per` parts.
 // Called twice (slabs -> FOLD_GROUPS -> 1) when there are many slabs: a serial walk over 2048 partials cost 0.5 ms.
@@ -470,8 +514,7 @@ int gnnmp_dense_grad_w_f32(const float *dz, const float *x, int64_t N, int64_t D
         const float *pdb = workspace + ((int64_t)slabs + FOLD_GROUPS) * std::max(Dout * K, Dout);
         if (int rc = fold_partials(pdb, slabs, Dout, db, workspace + (int64_t)slabs * Dout * K, stream)) return rc;
     } else if (db) {
-        colsum_partial_kernel<<<(unsigned)slabs, 256, 0, stream>>>(dz, N, (int)Dout, rps, workspace);
-        GNNMP_LAUNCH_CHECK("colsum_partial_kernel");
+        GNNMP_TRY(colsum_partial(dz, nullptr, N, (int)Dout, (int)Dout, rps, slabs, workspace, stream));
         if (int rc = fold_partials(workspace, slabs, Dout, db, workspace + (int64_t)slabs * Dout, stream)) return rc;
     }
     return GNNMP_OK;

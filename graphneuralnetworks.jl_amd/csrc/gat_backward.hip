@@ -13,10 +13,11 @@
 //                        (sd_i, m_i, 1/den_i, D_i) that the second kernel gathers per edge
 //   gat_bwd_src_kernel   source-sorted plan (the transposed one): row j gathers Δ_i + that line for every edge that
 //                        leaves j, accumulates Σ α Δ_i and dss_j, adds the two rank-one terms and stores dWx_j
-//   gat_wcolsum_*        da: two weighted column sums over the nodes, deterministic slab partials
+//   da                   two weighted column sums over the nodes, deterministic slab partials (launch.h: column sums)
 // Long rows are chunked into virtual rows exactly like the forward kernels; partials are folded in chunk order.
 #include <algorithm>
 
+#include "launch.h"
 #include "rowwalk.h"
 
 namespace gnnmp {
@@ -371,57 +372,11 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_rows_kernel(const float *a, c
     out[i] = a[(int64_t)h * 2 * C + (f - h * C)] * dsd[r * H + h];
 }
 
-// stage 1 of da: block b sums s[r][h] * x[r][h*C + c] over its slab of rows
-__global__ void __launch_bounds__(256) gat_wcolsum_partial_kernel(const float *x, const float *s, int64_t N, int H, int C,
-                                                                  int64_t R, float *part) {
-    const int D = H * C;
-    const int64_t r0 = (int64_t)blockIdx.x * R;
-    const int64_t r1 = min(N, r0 + R);
-    for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        const int h = d / C;
-        float acc = 0.0f;
-        int64_t r = r0;
-        for (; r + 8 <= r1; r += 8) {
-            float xv[8], sv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                xv[u] = x[(r + u) * D + d];
-                sv[u] = s[(r + u) * H + h];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fmaf(sv[u], xv[u], acc);
-        }
-        for (; r < r1; ++r) acc = fmaf(s[r * H + h], x[r * D + d], acc);
-        part[(int64_t)blockIdx.x * D + d] = acc;
-    }
-}
-// stage 2: da[h][off + c] = Σ_p part[p][h*C + c].  One block per column: thread k adds parts k, k+256, ... in order,
-// then a fixed-shape tree over the 256 partial sums in LDS (deterministic; a serial walk over 2048 parts cost 0.48 ms).
-__global__ void __launch_bounds__(256) gat_wcolsum_fold_kernel(const float *part, int nparts, int H, int C, int off,
-                                                               float *da) {
-    __shared__ float red[256];
-    const int d = blockIdx.x;
-    const int D = H * C;
-    float acc = 0.0f;
-    for (int p = threadIdx.x; p < nparts; p += 256) acc = acc + part[(int64_t)p * D + d];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int h = d / C;
-        da[(int64_t)h * 2 * C + off + (d - h * C)] = red[0];
-    }
-}
-
 template <int VEC, int LPH, bool DROP>
 static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *dWx_dst, float *da,
                           hipStream_t stream) {
     const int rpw = 64 >> g.geom.log2g;
-    int waves = knob(KNOB_BLOCK_WAVES);
-    if (waves < 1 || waves > 4) waves = 1;
+    const int waves = block_waves(1);
     g.geom.waves = waves;
     const int unroll = knob(KNOB_UNROLL);
     // ---- pass 1: destinations (forward plan)
@@ -480,14 +435,9 @@ static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, 
             const float *x = side == 0 ? g.Wx_dst : g.Wx_src;
             const float *s = side == 0 ? g.dsd : g.dss;
             const int64_t N = side == 0 ? plan->n_dst : plan->n_src;
-            const int64_t R = std::max<int64_t>(256, (N + 2047) / 2048);
-            const int nparts = (int)((N + R - 1) / R);
-            if (nparts > 0) {
-                gat_wcolsum_partial_kernel<<<nparts, 256, 0, stream>>>(x, s, N, g.H, g.C, R, plan->ws);
-                GNNMP_LAUNCH_CHECK("gat_wcolsum_partial_kernel");
-            }
-            gat_wcolsum_fold_kernel<<<g.D, 256, 0, stream>>>(plan->ws, nparts, g.H, g.C, side * g.C, da);
-            GNNMP_LAUNCH_CHECK("gat_wcolsum_fold_kernel");
+            const int nparts = colsum_parts(N);
+            GNNMP_TRY(colsum_partial(x, s, N, g.D, g.C, colsum_slab_rows(N), nparts, plan->ws, stream));
+            GNNMP_TRY(colsum_tree_fold(plan->ws, nparts, g.D, g.C, 2 * g.C, side * g.C, da, stream));
         }
     }
     return GNNMP_OK;
@@ -516,10 +466,7 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGra
     if (!(c.drop_p >= 0.0f && c.drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad: dropout probability %g outside [0, 1)", (double)c.drop_p);
     if (!plan || !plan_t) return fail(GNNMP_EINVAL, "gat_conv_grad: null plan");
     if (c.H <= 0 || c.C <= 0 || c.H * c.C > (1 << 20)) return fail(GNNMP_EINVAL, "gat_conv_grad: bad H/C");
-    if (plan_t->n_dst != plan->n_src || plan_t->n_src != plan->n_dst || plan_t->n_total != plan->n_total)
-        return fail(GNNMP_EINVAL, "gat_conv_grad: plan_t is not the transpose of plan (%lld x %lld, %lld edges vs %lld x %lld, %lld)",
-                    (long long)plan_t->n_dst, (long long)plan_t->n_src, (long long)plan_t->n_total,
-                    (long long)plan->n_dst, (long long)plan->n_src, (long long)plan->n_total);
+    GNNMP_TRY(check_transposed("gat_conv_grad", plan, plan_t));
     const bool same = !c.Wx_dst || c.Wx_dst == c.Wx_src;
     if (same) c.Wx_dst = c.Wx_src;
     if (same && plan->n_src != plan->n_dst) return fail(GNNMP_EINVAL, "gat_conv_grad: bipartite plan needs Wx_dst");
@@ -531,23 +478,15 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGra
     const int D = (int)(c.H * c.C);
     // every array read or written with Vec<VEC> enters the decision (grad2's out / oplus included: an under-aligned one narrows the
     // lanes like any other array, the header promises alignment for `line` only); dWx_dst is written by a scalar kernel
-    int vec = narrow_vec(pick_vec(D, c.Wx_src, c.dWx_src), c.Wx_dst, c.dout, c.outk, c.oplus);
+    const HeadGeom hg = head_geom(c.H, c.C, narrow_vec(pick_vec(D, c.Wx_src, c.dWx_src), c.Wx_dst, c.dout, c.outk, c.oplus));
     if ((reinterpret_cast<uintptr_t>(c.line) & 15) != 0) return fail(GNNMP_EINVAL, "gat_conv_grad: line must be 16-byte aligned");
-    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
-    int lph = (int)(c.C / vec);
-    const int lanes = D / vec;
-    if (c.H == 1 && lanes <= 64) {   // a single head may spill over idle lanes: they carry zeros
-        lph = 1;
-        while (lph < lanes) lph <<= 1;
-    }
-    if (lanes > 64)
+    if (!hg.fits_wave)
         return fail(GNNMP_EUNSUPPORTED, "gat_conv_grad: the feature row must fit one wave (H*C = %lld)", (long long)(c.H * c.C));
     // workspaces: chunk partials of each pass in that plan's workspace; the da partials reuse the forward plan's
-    const int64_t Rd = std::max<int64_t>(256, (plan->n_dst + 2047) / 2048), Rs = std::max<int64_t>(256, (plan->n_src + 2047) / 2048);
-    const size_t colsum_need = (size_t)std::max((plan->n_dst + Rd - 1) / Rd, (plan->n_src + Rs - 1) / Rs) * (size_t)D;
+    const size_t colsum_need = (size_t)std::max(colsum_parts(plan->n_dst), colsum_parts(plan->n_src)) * (size_t)D;
     if (int rc = ensure_workspace(plan, std::max((size_t)plan->n_chunks * (size_t)c.H * 4, c.da ? colsum_need : (size_t)0))) return rc;
     if (plan_t->n_chunks > 0)
-        if (int rc = ensure_workspace(plan_t, (size_t)plan_t->n_chunks * (size_t)(D + lanes))) return rc;
+        if (int rc = ensure_workspace(plan_t, (size_t)plan_t->n_chunks * (size_t)(D + hg.lanes))) return rc;
     GatBwdArgs g;
     g.Wx_src = c.Wx_src;
     g.Wx_dst = c.Wx_dst;
@@ -562,30 +501,21 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGra
     g.H = (int)c.H;
     g.C = (int)c.C;
     g.D = D;
-    g.geom = RowGeom{0, 1, 0, 0};
-    while ((1 << g.geom.log2g) < lanes) ++g.geom.log2g;
-    g.lph = lph_code(lph, g.geom.log2g);   // odd head widths sum their lanes one by one (common.h group_sum<0>)
+    g.geom = RowGeom{hg.log2g, 1, 0, 0};
+    g.lph = hg.lph_code;
     g.slope = c.negative_slope;
     g.drop = make_drop(c.drop_p, c.drop_seed);
     g.outk = c.outk;
     g.bias = c.bias;
     g.oplus = c.oplus;
     g.pplus = c.pplus;
-    if (c.drop_p > 0.0f) {   // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
-        return with_vec(vec, [&](auto V) { return launch_gat_bwd<decltype(V)::value, 0, true>(g, plan, plan_t, c.dWx_dst, c.da, stream); });
-    }
-    if (vec == 4) {   // the usual case (C a multiple of 4): compile-time lane count per head -> DPP butterflies
-        switch (lph) {
-            case 1: return launch_gat_bwd<4, 1, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-            case 2: return launch_gat_bwd<4, 2, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-            case 4: return launch_gat_bwd<4, 4, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-            case 8: return launch_gat_bwd<4, 8, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-            case 16: return launch_gat_bwd<4, 16, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-            default: return launch_gat_bwd<4, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-        }
-    }
-    if (vec == 2) return launch_gat_bwd<2, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
-    return launch_gat_bwd<1, 0, false>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+    return with_vec(hg.vec, [&](auto V) {
+        constexpr int VEC = decltype(V)::value;
+        // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
+        if (c.drop_p > 0.0f) return launch_gat_bwd<VEC, 0, true>(g, plan, plan_t, c.dWx_dst, c.da, stream);
+        // the usual case (C a multiple of 4): compile-time lane count per head -> DPP butterflies
+        return with_lph<VEC, 16>(hg.lph, [&](auto L) { return launch_gat_bwd<VEC, decltype(L)::value, false>(g, plan, plan_t, c.dWx_dst, c.da, stream); });
+    });
 }
 
 // what the three exports share (their arguments in the exports' order)

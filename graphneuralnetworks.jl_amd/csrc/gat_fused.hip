@@ -585,39 +585,23 @@ __global__ void __launch_bounds__(256) gat_fused_combine_kernel(const GatFusedAr
 }
 
 template <int VEC, int U, int MODE, bool FOLD = false>
-static void launch_rows_lph(const GatFusedArgs &a, dim3 grid, int blk, hipStream_t stream) {
+static void launch_rows_lph(const GatFusedArgs &a, int lph, dim3 grid, int blk, hipStream_t stream) {
     // compile-time lane count per head for the usual VEC = 4 shapes (DPP butterflies); anything else walks the xor
     // butterfly with the run-time count
-    if (VEC == 4 && a.lph == 1)
-        gat_fused_rows_kernel<VEC, U, 1, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 2)
-        gat_fused_rows_kernel<VEC, U, 2, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 4)
-        gat_fused_rows_kernel<VEC, U, 4, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 8)
-        gat_fused_rows_kernel<VEC, U, 8, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 16)
-        gat_fused_rows_kernel<VEC, U, 16, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 32)
-        gat_fused_rows_kernel<VEC, U, 32, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else if (VEC == 4 && a.lph == 64)
-        gat_fused_rows_kernel<VEC, U, 64, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
-    else
-        gat_fused_rows_kernel<VEC, U, 0, MODE, FOLD><<<grid, blk, 0, stream>>>(a);
+    with_lph<VEC, 64>(lph, [&](auto L) { gat_fused_rows_kernel<VEC, U, decltype(L)::value, MODE, FOLD><<<grid, blk, 0, stream>>>(a); });
 }
 
 template <int VEC, int MODE>
-static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
-    int waves = knob(KNOB_BLOCK_WAVES);
-    if (waves < 1 || waves > 4) waves = 1;   // auto: single-wave blocks (measured 5.21 vs 5.41 ms on products: finer
-                                              // grained retirement for a kernel whose rows differ 100x in length)
+static int launch_gat_fused(GatFusedArgs a, int lph, hipStream_t stream) {
+    const int waves = block_waves(1);   // auto: single-wave blocks (measured 5.21 vs 5.41 ms on products: finer
+                                        // grained retirement for a kernel whose rows differ 100x in length)
     a.geom.waves = waves;
     const dim3 grid = row_grid(a.rows, a.geom, 1, use_xcd_remap(a.n_src, a.D, row_blocks(a.rows, a.geom)));
     if (grid.x > 0) {
         const int U = knob(KNOB_UNROLL);
         const int blk = 64 * waves;
         if (MODE == GNNMP_ATTN_DOT) {
-            launch_rows_lph<VEC, 4, MODE>(a, grid, blk, stream);   // two rows per edge in flight: half the batch
+            launch_rows_lph<VEC, 4, MODE>(a, lph, grid, blk, stream);   // two rows per edge in flight: half the batch
         } else if (is_gat(MODE) && U == 4) {
             gat_fused_rows_kernel<VEC, 4, 0, MODE><<<grid, blk, 0, stream>>>(a);
         } else if (is_gat(MODE) && U == 2) {
@@ -625,11 +609,11 @@ static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
         } else if (MODE == GNNMP_ATTN_GAT && a.arrive && a.rows.n_long > 0) {
             // GATConv's forward merges its split rows inside the row kernel: no second launch.  (Not the training forward: with the o+ / P
             // accumulators the merge code took the kernel from 86 to 101 registers — 5 -> 4 waves a SIMD.)
-            launch_rows_lph<VEC, 8, MODE, MODE == GNNMP_ATTN_GAT>(a, grid, blk, stream);
+            launch_rows_lph<VEC, 8, MODE, MODE == GNNMP_ATTN_GAT>(a, lph, grid, blk, stream);
             GNNMP_LAUNCH_CHECK("gat_fused_rows_kernel<FOLD>");
             return GNNMP_OK;
         } else {
-            launch_rows_lph<VEC, 8, MODE>(a, grid, blk, stream);
+            launch_rows_lph<VEC, 8, MODE>(a, lph, grid, blk, stream);
         }
         GNNMP_LAUNCH_CHECK("gat_fused_rows_kernel");
     }
@@ -644,8 +628,8 @@ static int launch_gat_fused(GatFusedArgs a, hipStream_t stream) {
 }
 
 template <int MODE>
-static int launch_mode(const GatFusedArgs &g, int vec, hipStream_t stream) {
-    return with_vec(vec, [&](auto V) { return launch_gat_fused<decltype(V)::value, MODE>(g, stream); });
+static int launch_mode(const GatFusedArgs &g, const HeadGeom &hg, hipStream_t stream) {
+    return with_vec(hg.vec, [&](auto V) { return launch_gat_fused<decltype(V)::value, MODE>(g, hg.lph, stream); });
 }
 
 }  // namespace gnnmp
@@ -694,18 +678,12 @@ static int attn_conv_impl(gnnmp_graph_t *plan, AttnCall c, gnnmp_stream_t stream
     const int D = (int)(c.H * c.C);
     // every array the kernel touches with Vec<VEC> loads / stores enters the decision: K and out, Q, V and the training forward's
     // oplus (bias, stats, pplus and escore are scalar accesses and need none)
-    int vec = narrow_vec(pick_vec(D, c.K, c.out), c.Q, c.V, c.oplus);
-    while (vec > 1 && (c.C % vec) != 0) vec >>= 1;
-    int lph = (int)(c.C / vec);
-    const int lanes = D / vec;
-    int log2g = 0;
-    while ((1 << log2g) < lanes) ++log2g;   // one feature tile: the head butterfly needs the whole row in one group
-    if (c.H == 1 && lanes <= 64) lph = 1 << log2g;   // a single head may spill over idle lanes: they carry zeros
-    if (lanes > 64) {
+    const HeadGeom hg = head_geom(c.H, c.C, narrow_vec(pick_vec(D, c.K, c.out), c.Q, c.V, c.oplus));
+    if (!hg.fits_wave) {
         if (c.mode != GNNMP_ATTN_GAT || c.stats || c.escore || c.drop_p > 0.0f || plus)
             return fail(GNNMP_EUNSUPPORTED,
                         "attn_conv: the one-pass kernel needs a feature row that fits one wave (H*C = %lld lanes %d > 64)",
-                        (long long)(c.H * c.C), lanes);
+                        (long long)(c.H * c.C), hg.lanes);
         // GAT rows wider than a wave: three-pass kernels on node scores
         const size_t need = (size_t)(plan->n_dst + plan->n_src) * (size_t)c.H;
         if (int rc = ensure_workspace(plan, need)) return rc;
@@ -715,13 +693,13 @@ static int attn_conv_impl(gnnmp_graph_t *plan, AttnCall c, gnnmp_stream_t stream
         return gnnmp_gat_aggregate_f32(plan, c.K, sdst, ssrc, c.negative_slope, c.bias, c.act, c.out, nullptr, c.H, c.C, stream_);
     }
     if (plan->n_chunks > 0) {
-        if (int rc = ensure_workspace(plan, (size_t)plan->n_chunks * (size_t)(plus ? 2 * D + 3 * lanes : D + 2 * lanes))) return rc;
+        if (int rc = ensure_workspace(plan, (size_t)plan->n_chunks * (size_t)(plus ? 2 * D + 3 * hg.lanes : D + 2 * hg.lanes))) return rc;
     }
     GatFusedArgs g;
     g.oplus = c.oplus;
     g.pplus = c.pplus;
     g.rows = plan_rows(plan);
-    if (use_row_order(plan->n_src, D) && lanes <= 32) {   // two or more rows per wave: pair rows of equal length
+    if (use_row_order(plan->n_src, D) && hg.lanes <= 32) {   // two or more rows per wave: pair rows of equal length
         if (int rc = ensure_row_order(plan, stream)) return rc;
         g.rows.row_order = plan->row_order;
     }
@@ -738,8 +716,8 @@ static int attn_conv_impl(gnnmp_graph_t *plan, AttnCall c, gnnmp_stream_t stream
     g.C = (int)c.C;
     g.D = D;
     g.n_src = (int)plan->n_src;
-    g.geom = RowGeom{log2g, 4, 0, 0};
-    g.lph = lph_code(lph, log2g);   // odd head widths (C = 7 classes, ...) sum their lanes one by one
+    g.geom = RowGeom{hg.log2g, 4, 0, 0};
+    g.lph = hg.lph_code;
     g.act = c.act;
     g.slope = c.negative_slope;
     g.scale = c.scale;
@@ -748,21 +726,21 @@ static int attn_conv_impl(gnnmp_graph_t *plan, AttnCall c, gnnmp_stream_t stream
     g.arrive = nullptr;
     g.spart = nullptr;
     if (plan->n_long > 0 && use_fold() && (c.mode == GNNMP_ATTN_GAT && !c.escore && c.drop_p == 0.0f && !plus)) {   // (plain GAT only)
-        const size_t NG = (size_t)(256 >> log2g);
+        const size_t NG = (size_t)(256 >> hg.log2g);
         if (int rc = ensure_arrive(plan, (size_t)plan->n_long * (NG + 1),
-                                   (size_t)plan->n_long * NG * (size_t)(plus ? 2 * D + 3 * lanes : D + 2 * lanes), stream))
+                                   (size_t)plan->n_long * NG * (size_t)(plus ? 2 * D + 3 * hg.lanes : D + 2 * hg.lanes), stream))
             return rc;
         g.arrive = plan->arrive;
         g.spart = plan->spart;
     }
     if (c.drop_p > 0.0f)
-        return c.mode == GNNMP_ATTN_GATV2 ? launch_mode<ATTN_GATV2_DROP>(g, vec, stream) : launch_mode<ATTN_GAT_DROP>(g, vec, stream);
-    if (plus) return launch_mode<ATTN_GAT_PLUS>(g, vec, stream);
+        return c.mode == GNNMP_ATTN_GATV2 ? launch_mode<ATTN_GATV2_DROP>(g, hg, stream) : launch_mode<ATTN_GAT_DROP>(g, hg, stream);
+    if (plus) return launch_mode<ATTN_GAT_PLUS>(g, hg, stream);
     switch (c.mode) {
-        case GNNMP_ATTN_GATV2: return launch_mode<GNNMP_ATTN_GATV2>(g, vec, stream);
-        case GNNMP_ATTN_DOT: return launch_mode<GNNMP_ATTN_DOT>(g, vec, stream);
-        case GNNMP_ATTN_COS: return launch_mode<GNNMP_ATTN_COS>(g, vec, stream);
-        default: return g.escore ? launch_mode<ATTN_GAT_EDGE>(g, vec, stream) : launch_mode<GNNMP_ATTN_GAT>(g, vec, stream);
+        case GNNMP_ATTN_GATV2: return launch_mode<GNNMP_ATTN_GATV2>(g, hg, stream);
+        case GNNMP_ATTN_DOT: return launch_mode<GNNMP_ATTN_DOT>(g, hg, stream);
+        case GNNMP_ATTN_COS: return launch_mode<GNNMP_ATTN_COS>(g, hg, stream);
+        default: return g.escore ? launch_mode<ATTN_GAT_EDGE>(g, hg, stream) : launch_mode<GNNMP_ATTN_GAT>(g, hg, stream);
     }
 }
 

@@ -1,6 +1,7 @@
 // launch.h — every host function that is called across translation units, declared ONCE, and the request structs those
 // functions take.  The defining .hip and every caller include this header; a prototype is never copied into a .hip.
 // (What common.h declares — fail, knob, the ensure_* plan helpers — stays there: those are the library's plumbing.)
+// Sections: the row reduction, softmax_rows, the dense family, graph_chain2, column sums, plan.
 #pragma once
 #include "common.h"
 
@@ -72,7 +73,19 @@ int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_
                      const int *act, int w_layout, int aggr, int pool_aggr, const float *W_head, const float *b_head, int64_t nout,
                      float *out, hipStream_t stream);
 
+// ---- column sums (dense_backward.hip) -----------------------------------------------------------------------------------------------
+// Deterministic, two stages: every block of stage 1 sums one slab of rows, in row order, into part[slab][D]; the tree fold adds the
+// slabs.  (The dense adjoints fold their slabs with fold_partials instead, in a different order: dense_backward.hip.)
+int64_t colsum_slab_rows(int64_t N);   // rows a slab: at most 2048 slabs, of at least 256 rows
+int colsum_parts(int64_t N);           // slabs of colsum_slab_rows(N) rows that cover N rows: what a workspace holds D floats for
+// stage 1: part[b][d] = Σ_r x[r][d] (s null) or Σ_r s[r][d / C] * x[r][d] over the R rows of slab b < nparts; x [N][D], s [N][D / C]
+int colsum_partial(const float *x, const float *s, int64_t N, int D, int C, int64_t R, int nparts, float *part, hipStream_t stream);
+// the fold: out[(d / C) * out_ld + off + d % C] = Σ_p part[p][d] — thread k of 256 adds parts k, k + 256, ..., then a fixed tree
+int colsum_tree_fold(const float *part, int nparts, int D, int C, int out_ld, int off, float *out, hipStream_t stream);
+
 // ---- plan.hip -------------------------------------------------------------------------------------------------------------------
 int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);
+// GNNMP_OK if plan_t has plan's sizes transposed, GNNMP_EINVAL (message "<who>: ...", with the six sizes) otherwise
+int check_transposed(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t);
 
 }  // namespace gnnmp

@@ -346,6 +346,13 @@ int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known) {
     delete p;
     return GNNMP_OK;
 }
+int check_transposed(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t) {
+    if (plan_t->n_dst != plan->n_src || plan_t->n_src != plan->n_dst || plan_t->n_total != plan->n_total)
+        return fail(GNNMP_EINVAL, "%s: plan_t is not the transpose of plan (%lld x %lld, %lld edges vs %lld x %lld, %lld)", who,
+                    (long long)plan_t->n_dst, (long long)plan_t->n_src, (long long)plan_t->n_total,
+                    (long long)plan->n_dst, (long long)plan->n_src, (long long)plan->n_total);
+    return GNNMP_OK;
+}
 }  // namespace gnnmp
 
 extern "C" {

@@ -226,8 +226,7 @@ __global__ void __launch_bounds__(256) nn_rows_kernel(const ReduceArgs a, const 
 template <int VEC, int OP, bool SCALED, int U, bool EMAT = false, bool EXPSUB = false, int GATED = 0>
 static int launch_reduce(const ReduceArgs &a0, hipStream_t stream) {
     ReduceArgs a = a0;
-    int waves = knob(KNOB_BLOCK_WAVES);
-    if (waves < 1 || waves > 4) waves = 4;
+    const int waves = block_waves(4);
     a.geom.waves = waves;
     const int tiles = feature_tiles(a.D, VEC, a.geom.log2g);
     const dim3 grid = row_grid(a.rows, a.geom, tiles, use_xcd_remap(a.n_src, a.D, row_blocks(a.rows, a.geom)));

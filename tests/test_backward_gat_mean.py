@@ -46,7 +46,8 @@ def test_oracle_gat_mean_heads_adjoint_vs_finite_differences(oracle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("H,C,Din", [(4, 8, 20), (8, 16, 100), (2, 4, 6)])
+@pytest.mark.parametrize("H,C,Din", [(4, 8, 20), (8, 16, 100), (2, 4, 6),
+                                     (2, 12, 9), (2, 6, 5), (1, 20, 7)])   # three lanes a head; two floats a lane; one head over idle lanes
 def test_hip_gat_mean_heads_backward_vs_oracle(oracle, H, C, Din):
     import torch
     import gnnmp
