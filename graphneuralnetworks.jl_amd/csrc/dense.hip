@@ -464,6 +464,13 @@ __global__ void __launch_bounds__(512) dense_wlds_kernel(const DenseWArgs w) {
     }
 }
 
+// dense_wlds_kernel's pf_on on the host, from the same fields (gnnmp_debug_dense_route reports it; the kernel keeps its own expression)
+static bool wlds_prefetch_on(const DenseWArgs &w) {
+    const DenseArgs &a = w.d;
+    return w.prefetch && a.nseg == 1 && w.ks >= ((a.K[0] + 1) & ~1) && (a.K[0] & 3) == 0 &&
+           ((reinterpret_cast<uintptr_t>(a.x[0]) & 15) == 0);
+}
+
 template <int NT>
 static int launch_wlds(const DenseWArgs &w, size_t lds_bytes, int col_tiles, int64_t n_row_tiles, hipStream_t stream) {
     GNNMP_LDS_OPTIN("dense_wlds_kernel", &dense_wlds_kernel<NT>);
@@ -545,18 +552,34 @@ static int dense_narrow_try(const DenseCall &c, hipStream_t stream) {
     else
         dense_narrow_kernel<8><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
     GNNMP_LAUNCH_CHECK("dense_narrow_kernel");
+    dense_route().kernel = DENSE_NARROW;
     return GNNMP_OK;
+}
+
+DenseRoute &dense_route() {
+    static thread_local DenseRoute r = {};
+    return r;
 }
 
 }  // namespace gnnmp
 
 using namespace gnnmp;
 
+// test hook (gnnmp.h, GNNMP_INTERNAL): the calling thread's route record, as eight ints in the order of DenseRoute's fields
+extern "C" int gnnmp_debug_dense_route(int info[8]) {
+    if (!info) return fail(GNNMP_EINVAL, "gnnmp_debug_dense_route: null pointer");
+    const DenseRoute &r = dense_route();
+    const int v[8] = {r.kernel, r.tw, r.waves, r.ks, r.tp, r.rem_nt, r.prefetch, r.full};
+    std::copy(v, v + 8, info);
+    return GNNMP_OK;
+}
+
 extern "C" int gnnmp_dense_f32(const float *x1, const float *W1, int64_t D1, int64_t ldw1,
                                const float *x2, const float *W2, int64_t D2, int64_t ldw2,
                                int w_layout, const float *bias, int act, float *out, int64_t N,
                                int64_t Dout, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    dense_route() = DenseRoute{};
     if (N < 0 || Dout <= 0 || D1 <= 0 || D2 < 0 || Dout > (1 << 20) || D1 > (1 << 20) || D2 > (1 << 20))
         return fail(GNNMP_EINVAL, "dense: bad size");
     if (w_layout != 0 && w_layout != 1) return fail(GNNMP_EINVAL, "dense: bad w_layout %d", w_layout);
@@ -681,11 +704,18 @@ extern "C" int gnnmp_dense_f32(const float *x1, const float *W1, int64_t D1, int
                 }
                 if (rc) return rc;
             }
+            DenseRoute &r = dense_route();
+            r.kernel = DENSE_WLDS;
+            r.tw = c.tw; r.waves = c.waves; r.ks = c.ks; r.tp = c.tp;
+            r.rem_nt = (rem + 31) / 32;
+            r.prefetch = wlds_prefetch_on(w);
+            r.full = full;
             return GNNMP_OK;
         }
     }
     dim3 grid((unsigned)((N + BM - 1) / BM), (unsigned)((Dout + BN - 1) / BN));
     dense_mfma_kernel<<<grid, 256, 0, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_mfma_kernel");
+    dense_route().kernel = DENSE_MFMA;
     return GNNMP_OK;
 }

@@ -266,6 +266,7 @@ static int launch_split_var(const SplitArgs &a0, hipStream_t stream) {
     dim3 grid((unsigned)gx, (unsigned)ny);
     dense_split_kernel<NCB, K0C, K1C, VAR><<<grid, 64 * waves, lds, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_split_kernel");
+    dense_route().kernel = DENSE_SPLIT;
     return GNNMP_OK;
 }
 template <int NCB, int K0C, int K1C>

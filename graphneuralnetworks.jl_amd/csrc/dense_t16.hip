@@ -145,6 +145,7 @@ static int launch_t16(const T16Args &a0, hipStream_t stream) {
     dim3 grid((unsigned)gx, (unsigned)((a.Dout + DP - 1) / DP));
     dense_t16_kernel<NCB, MAXB, KQ1, KQ2><<<grid, 64 * waves, lds, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_t16_kernel");
+    dense_route().kernel = DENSE_T16;
     return GNNMP_OK;
 }
 

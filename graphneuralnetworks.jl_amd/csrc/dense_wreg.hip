@@ -205,6 +205,7 @@ static int launch_wreg(const WregArgs &a, hipStream_t stream) {
     const int64_t gx = std::min<int64_t>(device_cus(), ntiles);
     dense_wreg_kernel<K0C, K1C><<<(unsigned)gx, WR_THREADS, lds, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_wreg_kernel");
+    dense_route().kernel = DENSE_WREG;
     return GNNMP_OK;
 }
 

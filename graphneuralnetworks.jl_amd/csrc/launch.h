@@ -66,6 +66,21 @@ struct DenseCall {
 int dense_split_try(const DenseCall &c, hipStream_t stream);
 int dense_wreg_try(const DenseCall &c, hipStream_t stream);
 int dense_t16_try(const DenseCall &c, hipStream_t stream);
+// What the last gnnmp_dense_f32 call of this thread launched (gnnmp_debug_dense_route, gnnmp.h): a host record that every launch site
+// of the family fills in, so that a test knows which kernel and which configuration its shape reached.  gnnmp_dense_f32 clears it on
+// entry; the fields after `kernel` describe dense_wlds_kernel and are zero for the others.
+enum DenseKernel { DENSE_NONE = 0, DENSE_SPLIT = 1, DENSE_WREG = 2, DENSE_T16 = 3, DENSE_NARROW = 4, DENSE_WLDS = 5, DENSE_MFMA = 6 };
+struct DenseRoute {
+    int kernel;     // DenseKernel
+    int tw;         // column tile of the full launch: 128 | 64
+    int waves;      // waves a block: 8 | 4
+    int ks;         // columns of x staged per k-chunk
+    int tp;         // output column tiles per epilogue pass
+    int rem_nt;     // NT of the remainder launch (0 = Dout is a multiple of tw)
+    int prefetch;   // the kernel's pf_on, restated on the host from the same fields
+    int full;       // column tiles of the full launch (grid.y; 0 = only the remainder launch)
+};
+DenseRoute &dense_route();   // the calling thread's record (dense.hip)
 
 // ---- graph_chain2.hip -----------------------------------------------------------------------------------------------------------
 int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_t *seg_ptr, int64_t G, const float *x, int n_layers,

@@ -57,7 +57,7 @@ SYMBOLS = (
     "gnnmp_random_walk_pe_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
-    "gnnmp_debug_random_walk_pe_f32",
+    "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
 )
 
 
@@ -255,6 +255,7 @@ def load():
         "gnnmp_has_isolated_nodes": [vp, ctypes.POINTER(i), vp],
         "gnnmp_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
+        "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }
     for name, args in sig.items():
         try:

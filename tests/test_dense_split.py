@@ -92,6 +92,8 @@ def test_random_shapes_against_float64(gm, seed):
     e_split, e_f32, scale, eabs = case(gm, N, K1, K2, Dout, act, has_bias, w_layout, seed)
     assert eabs <= 1e-5 * scale, tag
     assert e_split <= SPLIT_BOUND, (tag, e_split, e_f32)
+    # the fp32-MFMA kernels on the same inputs (knob 17 = -1): K products and K + 1 additions in fp32, in any order
+    assert e_f32 <= (K1 + K2 + 2) * 2.0 ** -24, (tag, e_f32)
 
 
 @pytest.mark.parametrize("scale", [1e-30, 1e-12, 1e12, 1e30])
