@@ -5,16 +5,24 @@
 //   dense_x(x)                      :127                              (gat_conv)
 // plus `.+ bias` and σ fused in the epilogue (:71,:107,:147,:281).
 //
-// Shape: tall-skinny, out[N][Dout] with N ~ 1e5..1e7 and K, Dout ~ 16..256.  fp32 in / fp32 accumulate on
-// v_mfma_f32_32x32x2_f32 (exact fp32 fma chain in k order; 157 TF peak = the fp32 vector rate, but it leaves the VALU
-// free and needs one VGPR per operand).  Two kernels:
-//   dense_wlds_kernel  (default) W^T resident in LDS for the lifetime of a persistent block, wave-private x staging, no
-//                      workgroup barrier in the main loop — used whenever W^T for a 128-column tile plus >= 4 wave
-//                      regions fit the 160 KB LDS (all layer shapes of the bench configs);
-//   dense_mfma_kernel  the K-chunked fallback (128 x 128 block tile, x and W^T chunks of 32 k-values through LDS with
-//                      two barriers per chunk) for large K (e.g. Cora's 1433 input features) and tiny N.
-// Both use padded / odd leading dimensions so that the ds_read_b32 of either MFMA operand is bank-conflict free.
+// Shape: tall-skinny, out[N][Dout] with N ~ 1e5..1e7 and K, Dout ~ 16..256.
+//
+// Six kernels.  Which one a call reaches, with which template instance and launch geometry, is decided in ONE place: dense_plan
+// (dense_route.h; DESIGN.md has the table), whose order is the order below.  gnnmp_dense_f32, at the end of this file, validates its
+// arguments, asks the planner, records the route for gnnmp_debug_dense_route and calls the launcher the route names.
+//   dense_wreg_kernel    (dense_wreg.hip)  split-bf16 core, 256 outputs: W in registers, x through LDS once
+//   dense_split_kernel   (dense_split.hip) split-bf16 core (three exact bf16 planes, six bf16 MFMAs per product): W^T planes in LDS
+//   dense_t16_kernel     (dense_t16.hip)   fp32 v_mfma_f32_16x16x4_f32, K <= 128 per segment, operands straight from HBM
+//   dense_narrow_kernel  (here)            Dout <= 8: eight lanes per row, no matrix core
+//   dense_wlds_kernel    (here)            fp32 v_mfma_f32_32x32x2_f32 (exact fp32 fma chain in k order; it leaves the VALU free and needs
+//                        one VGPR per operand): W^T resident in LDS for the lifetime of a persistent block, wave-private x staging,
+//                        no workgroup barrier in the main loop — whenever W^T for a column tile plus >= 4 wave regions fit the 160 KB
+//                        LDS: odd K or Dout, a misaligned operand, K > 128 onto a width that pads badly
+//   dense_mfma_kernel    (here)            the K-chunked fallback (128 x 128 block tile, x and W^T chunks of 32 k-values through LDS
+//                        with two barriers per chunk) for large K (e.g. Cora's 1433 input features) and tiny N: takes everything
+// The two 32x32x2 kernels use padded / odd leading dimensions so that the ds_read_b32 of either MFMA operand is bank-conflict free.
 #include <algorithm>
+#include <cstdint>
 
 #include "common.h"
 #include "launch.h"
@@ -23,7 +31,7 @@ namespace gnnmp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BM = 128, BN = 128, KC = 32;
+constexpr int BM = MFMA_BM, BN = MFMA_BN, KC = 32;   // (the planner sizes the grid with the first two)
 constexpr int XS_LD = KC + 1;   // bank = (row + k) % 32
 constexpr int WS_LD = BN + 1;   // bank = (k + j) % 32
 
@@ -166,7 +174,7 @@ struct DenseWArgs {
     int old_;      // leading dimension of the wave-private output image (multiple of 4)
     int skew;      // s_sleep(127) repetitions for waves 4-7 before their first tile (0 = none)
     int token;     // 1 = serialise the k-loops of the two waves of a SIMD with an LDS token
-    int prefetch;  // 1 = cross-tile register prefetch of the next x block (one-segment, whole-K staging)
+    int prefetch;  // 1 = cross-tile register prefetch of the next x block (final: dense_route.h decides when it may be on)
     int tp;        // output column tiles per epilogue pass
     int ks;        // columns of x staged per k-chunk (multiple of 4; = K rounded up when the whole tile fits)
     int region;    // floats per wave region
@@ -250,8 +258,7 @@ __global__ void __launch_bounds__(512) dense_wlds_kernel(const DenseWArgs w) {
     // 100 => 100: 740 -> 700 us).  The 64 prefetch registers double as the staging batch of the non-prefetch path — kept
     // apart, the kernel needed 270 VGPRs and spilled (-20 %).
     constexpr int PF = 16;                                   // float4 per lane: 32 rows x 128 columns at most
-    const bool pf_on = w.prefetch && a.nseg == 1 && w.ks >= ((a.K[0] + 1) & ~1) && (a.K[0] & 3) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(a.x[0]) & 15) == 0);
+    const bool pf_on = w.prefetch != 0;
     float4 pfv[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) pfv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -464,24 +471,6 @@ __global__ void __launch_bounds__(512) dense_wlds_kernel(const DenseWArgs w) {
     }
 }
 
-// dense_wlds_kernel's pf_on on the host, from the same fields (gnnmp_debug_dense_route reports it; the kernel keeps its own expression)
-static bool wlds_prefetch_on(const DenseWArgs &w) {
-    const DenseArgs &a = w.d;
-    return w.prefetch && a.nseg == 1 && w.ks >= ((a.K[0] + 1) & ~1) && (a.K[0] & 3) == 0 &&
-           ((reinterpret_cast<uintptr_t>(a.x[0]) & 15) == 0);
-}
-
-template <int NT>
-static int launch_wlds(const DenseWArgs &w, size_t lds_bytes, int col_tiles, int64_t n_row_tiles, hipStream_t stream) {
-    GNNMP_LDS_OPTIN("dense_wlds_kernel", &dense_wlds_kernel<NT>);
-    const int cus = device_cus();
-    int64_t gx = (n_row_tiles + w.waves - 1) / w.waves;
-    if (gx > cus) gx = cus;  // one persistent block per CU (the LDS image allows no more)
-    dim3 grid((unsigned)gx, (unsigned)col_tiles);
-    dense_wlds_kernel<NT><<<grid, 64 * w.waves, lds_bytes, stream>>>(w);
-    GNNMP_LAUNCH_CHECK("dense_wlds_kernel");
-    return GNNMP_OK;
-}
 // ---- narrow outputs (a classifier head: Dense(128 => 2) after the pool) ---------------------------------------------------
 // Dout <= 8: no matrix core has anything to do (a 16-wide tile would be 7/8 padding and the whole product is a few MFLOP); the
 // MFMA kernels above spend their time staging W.  Eight lanes per row: lane l of the group reads the row's float4s l, l + 8, ...
@@ -538,25 +527,86 @@ __global__ void __launch_bounds__(256) dense_narrow_kernel(const float *__restri
     }
 }
 
-// Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes.
-static int dense_narrow_try(const DenseCall &c, hipStream_t stream) {
-    if (c.Dout > 8 || (c.D1 & 3) || (c.D2 & 3) || c.D1 > 4096 || c.D2 > 4096) return 1;
-    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (c.D2 > 0 && (reinterpret_cast<uintptr_t>(c.x2) & 15))) return 1;
-    const int64_t sj1 = c.w_layout == 0 ? c.ldw1 : 1, sk1 = c.w_layout == 0 ? 1 : c.ldw1;
-    const int64_t sj2 = c.w_layout == 0 ? c.ldw2 : 1, sk2 = c.w_layout == 0 ? 1 : c.ldw2;
-    const unsigned nb = (unsigned)((c.N * 8 + 255) / 256);
-    if (c.Dout <= 2)
-        dense_narrow_kernel<2><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
-    else if (c.Dout <= 4)
-        dense_narrow_kernel<4><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
-    else
-        dense_narrow_kernel<8><<<nb, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, sj1, sk1, c.x2, c.W2, (int)c.D2, sj2, sk2, c.bias, c.act, c.out, c.N, (int)c.Dout);
+// ---- the launchers of this file's kernels: everything they launch with comes from the route (dense_route.h) ------------------------
+int dense_launch_narrow(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
+    const WStrides s1 = w_strides(c.w_layout, c.ldw1), s2 = w_strides(c.w_layout, c.ldw2);
+    switch (r.nout) {
+#define GNNMP_NARROW_CASE(NOUT)                                                                                                  \
+    case NOUT:                                                                                                                   \
+        dense_narrow_kernel<NOUT><<<r.grid_x, 256, 0, stream>>>(c.x1, c.W1, (int)c.D1, s1.sj, s1.sk, c.x2, c.W2, (int)c.D2, s2.sj, \
+                                                                 s2.sk, c.bias, c.act, c.out, c.N, (int)c.Dout);                  \
+        break;
+        GNNMP_NARROW_CASE(2) GNNMP_NARROW_CASE(4) GNNMP_NARROW_CASE(8)
+#undef GNNMP_NARROW_CASE
+        default: return fail(GNNMP_EUNSUPPORTED, "dense_narrow: no instance <%d>", r.nout);
+    }
     GNNMP_LAUNCH_CHECK("dense_narrow_kernel");
-    dense_route().kernel = DENSE_NARROW;
     return GNNMP_OK;
 }
 
-DenseRoute &dense_route() {
+static DenseArgs dense_args(const DenseCall &c) {
+    DenseArgs a;
+    a.x[0] = c.x1; a.W[0] = c.W1; a.K[0] = (int)c.D1; a.ldw[0] = (int)c.ldw1;
+    a.x[1] = c.x2; a.W[1] = c.W2; a.K[1] = (int)c.D2; a.ldw[1] = (int)c.ldw2;
+    a.nseg = c.D2 > 0 ? 2 : 1;
+    a.w_layout = c.w_layout;
+    a.bias = c.bias;
+    a.act = c.act;
+    a.out = c.out;
+    a.N = c.N;
+    a.Dout = (int)c.Dout;
+    return a;
+}
+
+template <int NT>
+static int launch_wlds(const DenseWArgs &w, const DenseRoute &r, unsigned col_tiles, hipStream_t stream) {
+    GNNMP_LDS_OPTIN("dense_wlds_kernel", &dense_wlds_kernel<NT>);
+    dense_wlds_kernel<NT><<<dim3(r.grid_x, col_tiles), 64 * r.waves, r.lds_bytes, stream>>>(w);
+    GNNMP_LAUNCH_CHECK("dense_wlds_kernel");
+    return GNNMP_OK;
+}
+static int launch_wlds_nt(int nt, const DenseWArgs &w, const DenseRoute &r, unsigned col_tiles, hipStream_t stream) {
+    switch (nt) {
+        case 1: return launch_wlds<1>(w, r, col_tiles, stream);
+        case 2: return launch_wlds<2>(w, r, col_tiles, stream);
+        case 3: return launch_wlds<3>(w, r, col_tiles, stream);
+        case 4: return launch_wlds<4>(w, r, col_tiles, stream);
+        default: return fail(GNNMP_EUNSUPPORTED, "dense_wlds: no instance <%d>", nt);
+    }
+}
+// the full column tiles (r.full of them, r.tw wide) in one launch, the remaining columns in a second one
+int dense_launch_wlds(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
+    DenseWArgs w;
+    w.d = dense_args(c);
+    w.waves = r.waves;
+    w.xld = r.xld;
+    w.old_ = r.old_;
+    w.skew = r.skew;
+    w.token = r.token;
+    w.prefetch = r.prefetch;
+    w.tp = r.tp;
+    w.ks = r.ks;
+    w.region = r.region;
+    w.ktot_pad = r.ktot_pad;
+    if (r.full > 0) {
+        w.n0 = 0;
+        if (int rc = launch_wlds_nt(r.nt_full, w, r, (unsigned)r.full, stream)) return rc;
+    }
+    if (r.rem_nt > 0) {
+        w.n0 = r.full * r.tw;
+        if (int rc = launch_wlds_nt(r.rem_nt, w, r, 1, stream)) return rc;
+    }
+    return GNNMP_OK;
+}
+
+int dense_launch_mfma(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
+    dense_mfma_kernel<<<dim3(r.grid_x, r.grid_y), 256, 0, stream>>>(dense_args(c));
+    GNNMP_LAUNCH_CHECK("dense_mfma_kernel");
+    return GNNMP_OK;
+}
+
+// the calling thread's route record: written by gnnmp_dense_f32 only, read by gnnmp_debug_dense_route
+static DenseRoute &dense_route() {
     static thread_local DenseRoute r = {};
     return r;
 }
@@ -565,12 +615,14 @@ DenseRoute &dense_route() {
 
 using namespace gnnmp;
 
-// test hook (gnnmp.h, GNNMP_INTERNAL): the calling thread's route record, as eight ints in the order of DenseRoute's fields
+// test hook (gnnmp.h, GNNMP_INTERNAL): the calling thread's route record, as eight ints in the order of DenseRoute's first eight fields;
+// the seven after `kernel` describe dense_wlds_kernel and are zero for the others
 extern "C" int gnnmp_debug_dense_route(int info[8]) {
     if (!info) return fail(GNNMP_EINVAL, "gnnmp_debug_dense_route: null pointer");
     const DenseRoute &r = dense_route();
     const int v[8] = {r.kernel, r.tw, r.waves, r.ks, r.tp, r.rem_nt, r.prefetch, r.full};
-    std::copy(v, v + 8, info);
+    std::fill(info, info + 8, 0);
+    std::copy(v, v + (r.kernel == DENSE_WLDS ? 8 : 1), info);
     return GNNMP_OK;
 }
 
@@ -579,143 +631,32 @@ extern "C" int gnnmp_dense_f32(const float *x1, const float *W1, int64_t D1, int
                                int w_layout, const float *bias, int act, float *out, int64_t N,
                                int64_t Dout, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    dense_route() = DenseRoute{};
+    DenseRoute &route = dense_route();
+    route = DenseRoute{};
     if (N < 0 || Dout <= 0 || D1 <= 0 || D2 < 0 || Dout > (1 << 20) || D1 > (1 << 20) || D2 > (1 << 20))
         return fail(GNNMP_EINVAL, "dense: bad size");
     if (w_layout != 0 && w_layout != 1) return fail(GNNMP_EINVAL, "dense: bad w_layout %d", w_layout);
     if (act != GNNMP_ACT_IDENTITY && act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "dense: bad act %d", act);
     if (N == 0) return GNNMP_OK;
     if (!x1 || !W1 || !out || (D2 > 0 && (!x2 || !W2))) return fail(GNNMP_EINVAL, "dense: null pointer");
-    DenseCall c;
-    c.x1 = x1; c.W1 = W1; c.D1 = D1; c.ldw1 = ldw1;
-    c.x2 = x2; c.W2 = W2; c.D2 = D2; c.ldw2 = ldw2;
-    c.w_layout = w_layout;
-    c.bias = bias;
-    c.act = act;
-    c.out = out;
-    c.N = N;
-    c.Dout = Dout;
-    {
-        // round 3: the split-bf16 core (three exact bf16 planes per operand, six bf16 MFMAs per product: fp32-class accuracy at
-        // 2.7x the fp32-MFMA rate) for every shape whose W image fits LDS
-        const int rc = dense_split_try(c, stream);
-        if (rc != 1) return rc;
+    const DenseCall c{x1, W1, D1, ldw1, x2, W2, D2, ldw2, w_layout, bias, act, out, N, Dout};
+    auto aligned = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    const DenseShape shape{N, D1, D2, Dout, aligned(x1, 16), aligned(x2, 16), aligned(out, 16), aligned(out, 128)};
+    DenseKnobs knobs{knob(KNOB_DENSE_GENERIC), knob(KNOB_DENSE_SPLIT), knob(KNOB_VARIANT), knob(KNOB_DENSE_T16_WAVES), knob(KNOB_DENSE_PREFETCH)};
+#ifdef GNNMP_EXPERIMENTS
+    knobs.t16_debug = knob(KNOB_T16_DEBUG);
+#endif
+    route = dense_plan(shape, knobs, device_cus());
+    int rc;
+    switch (route.kernel) {
+        case DENSE_WREG: rc = dense_launch_wreg(c, route, stream); break;
+        case DENSE_SPLIT: rc = dense_launch_split(c, route, stream); break;
+        case DENSE_T16: rc = dense_launch_t16(c, route, stream); break;
+        case DENSE_NARROW: rc = dense_launch_narrow(c, route, stream); break;
+        case DENSE_WLDS: rc = dense_launch_wlds(c, route, stream); break;
+        case DENSE_MFMA: rc = dense_launch_mfma(c, route, stream); break;
+        default: rc = fail(GNNMP_ELAUNCH, "dense: the planner named no kernel"); break;
     }
-    {
-        // the shapes of the hot path (K a multiple of 4, <= 128 per segment): operands straight from HBM, 16x16x4 MFMAs
-        const int rc = dense_t16_try(c, stream);
-        if (rc != 1) return rc;
-    }
-    if (knob(KNOB_DENSE_GENERIC) == 0) {
-        const int rc = dense_narrow_try(c, stream);
-        if (rc != 1) return rc;
-    }
-    DenseArgs a;
-    a.x[0] = x1; a.W[0] = W1; a.K[0] = (int)D1; a.ldw[0] = (int)ldw1;
-    a.x[1] = x2; a.W[1] = W2; a.K[1] = (int)D2; a.ldw[1] = (int)ldw2;
-    a.nseg = D2 > 0 ? 2 : 1;
-    a.w_layout = w_layout;
-    a.bias = bias;
-    a.act = act;
-    a.out = out;
-    a.N = N;
-    a.Dout = (int)Dout;
-    // W-resident kernel when W^T (for one column tile) plus the wave regions fit the 160 KB LDS.  The column tile is 128
-    // wide unless that leaves room for only 4 waves (K1 + K2 around 256): then 64-wide tiles — x is staged twice, but 8
-    // waves (two per SIMD) overlap one wave's staging with the other's MFMAs (GraphConv 128 => 128: see LABNOTES.md).
-    {
-        const int k0p = ((int)D1 + 1) & ~1, k1p = ((int)D2 + 1) & ~1;
-        const int ktot = k0p + (D2 > 0 ? k1p : 0);
-        const int kmax = std::max(k0p, k1p);
-        const size_t budget = 160 * 1024 - 64;   // 4 pipe tokens live after the wave regions
-        struct Cfg { int tw, waves, ks, xld, old_, tp; size_t wbytes, region; };
-        auto size_for = [&](int tw) -> Cfg {
-            Cfg c{};
-            c.tw = tw;
-            const int full = (int)(Dout / tw), rem = (int)(Dout % tw);
-            const int nt_max = full > 0 ? tw / 32 : (rem + 31) / 32;
-            const int ncols_max = full > 0 ? tw : rem;
-            c.wbytes = (size_t)ktot * (size_t)(nt_max * 32 + 1) * sizeof(float);
-            // Wave regions: prefer 8 waves per CU.  If the whole 32 x K image does not leave room for 8 regions, stage x
-            // in k-chunks (ks columns at a time); only if even 48-column chunks do not fit, fall back to 4 waves.
-            for (int wv : {8, 4}) {  // fewer than one wave per SIMD cannot feed the matrix pipe: K-chunked kernel instead
-                if (c.wbytes >= budget) break;
-                const int cols_fit = (int)((budget - c.wbytes) / ((size_t)wv * 32 * sizeof(float)));  // floats per region row
-                int kfit = ((cols_fit - 1) & ~3);               // leave the +1 (odd leading dimension)
-                kfit = std::min(kfit, (kmax + 3) & ~3);
-                kfit = std::min(kfit, 128);                      // <= 32 float4 per staged row (shift-mapped staging)
-                if (kfit >= ((kmax + 3) & ~3) || kfit >= 48) {   // (24-column chunks measured slower than 4 waves x 44)
-                    const int nkc = (kmax + kfit - 1) / kfit;     // balanced chunks, multiple of 4
-                    c.ks = (((kmax + nkc - 1) / nkc) + 3) & ~3;
-                    c.waves = wv;
-                    break;
-                }
-            }
-            c.xld = c.ks + 1;                                   // odd: conflict-free A-operand reads
-            // the wave region is sized for the x image (>= one 32-column output tile); the output tile passes through it
-            // whole if it fits, else tp column tiles at a time
-            const int region_cols = (std::max(c.xld, 32) + 3) & ~3;
-            c.tp = 4;
-            c.old_ = (ncols_max + 3) & ~3;
-            if (c.old_ > region_cols) {
-                c.tp = region_cols / 32;
-                c.old_ = c.tp * 32;
-            }
-            c.region = (size_t)32 * (size_t)region_cols;
-            if (c.waves > 0 && c.wbytes + (size_t)c.waves * c.region * sizeof(float) > budget) c.waves = 0;
-            return c;
-        };
-        Cfg c = size_for(128);
-        if (c.waves < 8 && Dout >= 128) {
-            const Cfg c64 = size_for(64);
-            if (c64.waves == 8) c = c64;
-        }
-        if (c.waves > 0 && N >= 256 && knob(KNOB_DENSE_GENERIC) != 1) {
-            DenseWArgs w;
-            w.d = a;
-            w.waves = c.waves;
-            w.xld = c.xld;
-            w.old_ = c.old_;
-            w.tp = c.tp;
-            w.ks = c.ks;
-            w.skew = knob(KNOB_DENSE_PREFETCH) & 15;          // experiment knob (slot 7): low 4 bits = s_sleep(127) count,
-            w.token = (knob(KNOB_DENSE_PREFETCH) >> 4) & 1;   //                           bit 4 = matrix-pipe token
-            w.prefetch = ((knob(KNOB_DENSE_PREFETCH) >> 5) & 1) ^ 1;   //                  bit 5 = cross-tile prefetch OFF
-            w.region = (int)c.region;
-            w.ktot_pad = ktot;
-            const int64_t n_row_tiles = (N + 31) / 32;
-            const size_t lds_bytes = c.wbytes + (size_t)c.waves * c.region * sizeof(float) + 16;   // + 4 pipe tokens
-            const int full = (int)(Dout / c.tw), rem = (int)(Dout % c.tw);
-            if (full > 0) {
-                w.n0 = 0;
-                int rc = c.tw == 128 ? launch_wlds<4>(w, lds_bytes, full, n_row_tiles, stream)
-                                     : launch_wlds<2>(w, lds_bytes, full, n_row_tiles, stream);
-                if (rc) return rc;
-            }
-            if (rem > 0) {
-                w.n0 = full * c.tw;
-                const int nt = (rem + 31) / 32;
-                int rc = GNNMP_OK;
-                switch (nt) {
-                    case 1: rc = launch_wlds<1>(w, lds_bytes, 1, n_row_tiles, stream); break;
-                    case 2: rc = launch_wlds<2>(w, lds_bytes, 1, n_row_tiles, stream); break;
-                    case 3: rc = launch_wlds<3>(w, lds_bytes, 1, n_row_tiles, stream); break;
-                    default: rc = launch_wlds<4>(w, lds_bytes, 1, n_row_tiles, stream); break;
-                }
-                if (rc) return rc;
-            }
-            DenseRoute &r = dense_route();
-            r.kernel = DENSE_WLDS;
-            r.tw = c.tw; r.waves = c.waves; r.ks = c.ks; r.tp = c.tp;
-            r.rem_nt = (rem + 31) / 32;
-            r.prefetch = wlds_prefetch_on(w);
-            r.full = full;
-            return GNNMP_OK;
-        }
-    }
-    dim3 grid((unsigned)((N + BM - 1) / BM), (unsigned)((Dout + BN - 1) / BN));
-    dense_mfma_kernel<<<grid, 256, 0, stream>>>(a);
-    GNNMP_LAUNCH_CHECK("dense_mfma_kernel");
-    dense_route().kernel = DENSE_MFMA;
-    return GNNMP_OK;
+    if (rc != GNNMP_OK) route = DenseRoute{};   // the record says what was launched
+    return rc;
 }

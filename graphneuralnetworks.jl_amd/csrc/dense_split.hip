@@ -10,8 +10,6 @@
 // activation on the accumulators, one 16-byte store per four outputs.  No barrier after the image.
 // K of a segment: any multiple of 4 (rows are 16-byte aligned); the image must fit LDS: (K1 + K2 rounded to 16) * DP * 6 bytes
 // <= ~158 KB — DP = 128 up to K1 + K2 = 208 (SAGEConv 100 + 100), 64 up to 416, 32 up to 832; beyond that dense.hip's kernels.
-#include <algorithm>
-
 #include "launch.h"
 #include "msplit.h"
 
@@ -61,13 +59,12 @@ __device__ __forceinline__ float4 load_q(const RowPtr<TWO> &r, int c, int K0, in
 //   128 = every tile reads rows 0..31 (operands from L1)
 //   256 = (not an experiment) every column tile is full, Dout % DP == 0: no column test in the epilogue
 //   4096 = (not an experiment) stores through a 4 KB LDS stage per wave (whole 128-byte lines): taken when the stage fits beside the image
-template <int NCB, int VAR>
-constexpr int split_threads() { return (VAR & 4) ? (NCB >= 4 ? 768 : 1024) : 512; }
+// (threads of a block: split_threads(NCB, VAR), dense_route.h)
 
 // K0C > 0: both segment lengths known at compile time (the shapes of the configs): k-blocks fully unrolled, a ring of operand loads
 // in flight that runs ahead into the next tile.  K0C = 0: any K (a.nkb k-blocks, K1C > 0 = two segments), one k-block ahead.
 template <int NCB, int K0C, int K1C, int VAR>
-__global__ void __launch_bounds__((split_threads<NCB, VAR>())) dense_split_kernel(const SplitArgs a) {
+__global__ void __launch_bounds__(split_threads(NCB, VAR)) dense_split_kernel(const SplitArgs a) {
     constexpr int NKB = K0C > 0 ? (K0C + K1C + 15) / 16 : 0;
     constexpr bool TWO = K1C > 0;
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -232,111 +229,56 @@ __global__ void __launch_bounds__((split_threads<NCB, VAR>())) dense_split_kerne
     }
 }
 
+// ---- the launcher: dense_plan (dense_route.h) chose the instance <NCB, K0C, K1C, VAR>, the waves, the grid and the LDS bytes ----------
 template <int NCB, int K0C, int K1C, int VAR>
-static int launch_split_var(const SplitArgs &a0, hipStream_t stream) {
-    SplitArgs a = a0;
-    constexpr int DP = NCB * 32;
-    const size_t lds = split_img_bytes(a.nkb * 16, DP) + (size_t)DP * 4 + ((VAR & 4096) ? (size_t)(split_threads<NCB, VAR>() / 64) * 4096 : 0);
+static int launch_split_var(const SplitArgs &a, const DenseRoute &r, hipStream_t stream) {
     GNNMP_LDS_OPTIN("dense_split_kernel", &dense_split_kernel<NCB, K0C, K1C, VAR>);
-    const int cus = device_cus();
-    const int64_t ntiles = (a.N + 31) / 32;
-    constexpr int max_waves = split_threads<NCB, VAR>() / 64;
-    int waves = (int)std::min<int64_t>(max_waves, std::max<int64_t>(4, (ntiles + cus - 1) / cus));
-    if (ntiles < (int64_t)cus * max_waves * 8) {
-        // few tiles per wave (arxiv shape: 5 292 tiles, 2.6 per wave at 8 waves a block): the last round of the wave-major hand-out is
-        // partly empty — pick the wave count whose rounds are fullest (arxiv: 7 waves -> 2.95 tiles per wave, 98 % instead of 86 %)
-        double best = -1.0;
-        for (int w = max_waves; w >= 4; --w) {
-            const int64_t slots = (int64_t)cus * w;
-            const double eff = (double)ntiles / (double)(((ntiles + slots - 1) / slots) * slots);
-            if (eff > best + 0.02) { best = eff; waves = w; }
-        }
-    }
-    const int kw = knob(KNOB_DENSE_T16_WAVES);
-    if (kw >= 1 && kw <= max_waves) waves = kw;
-    a.waves = waves;
-    // Several column tiles (Dout > DP: SAGEConv's 256 columns are two): a block fills a CU (LDS), so with `cus` blocks per column tile
-    // the tiles ran one after the other and x came from HBM once per column tile.  cus / ny blocks per column tile instead: blocks
-    // (b, 0), (b, 1), ... walk the same row tiles at the same time and — linear block ids b, b + gx, ... with gx a multiple of 8 — on
-    // the same XCD, so every read of x after the first is an L2 hit (VARIANT_SPLIT_SERIAL_TILES = the old grid, for A/B runs).
-    const int ny = (a.Dout + DP - 1) / DP;
-    int64_t bx = cus;
-    if (ny > 1 && !(knob(KNOB_VARIANT) & VARIANT_SPLIT_SERIAL_TILES)) bx = std::max<int64_t>(8, (int64_t)(cus / ny) & ~(int64_t)7);
-    const int64_t gx = std::min<int64_t>(bx, (ntiles + waves - 1) / waves);
-    dim3 grid((unsigned)gx, (unsigned)ny);
-    dense_split_kernel<NCB, K0C, K1C, VAR><<<grid, 64 * waves, lds, stream>>>(a);
+    dense_split_kernel<NCB, K0C, K1C, VAR><<<dim3(r.grid_x, r.grid_y), 64 * r.waves, r.lds_bytes, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_split_kernel");
-    dense_route().kernel = DENSE_SPLIT;
     return GNNMP_OK;
 }
+// the VAR of an instance: every column tile full or not (256), stores through the per-wave LDS stage or not (4096)
 template <int NCB, int K0C, int K1C>
-static int launch_split(const SplitArgs &a, hipStream_t stream) {
+static int launch_split(const SplitArgs &a, const DenseRoute &r, hipStream_t stream) {
+#define V(X) case X: return launch_split_var<NCB, K0C, K1C, X>(a, r, stream);
+    switch (r.var) { V(256 | 4096) V(256) V(4096) V(0) default: break; }
 #ifdef GNNMP_EXPERIMENTS
     if constexpr ((K0C == 100 && K1C == 0) || (K0C == 128 && K1C == 128)) {   // knob 13 selects a variant, on two shapes only (build time)
-        switch (knob(KNOB_T16_DEBUG)) {
-#define V(X) case X: return launch_split_var<NCB, K0C, K1C, X>(a, stream);
-            V(257) V(258) V(260) V(1280) V(2304) V(264) V(272) V(320) V(384) V(400) V(768)
-#undef V
-            default: break;
-        }
+        switch (r.var) { V(257) V(258) V(260) V(1280) V(2304) V(264) V(272) V(320) V(384) V(400) V(768) default: break; }
     }
 #endif
-    // stores through the per-wave LDS stage (whole 128-byte lines) when 8 stages fit beside the image (VARIANT_SPLIT_DIRECT_STORES = never, for A/B runs)
-    const bool staged = split_img_bytes(a.nkb * 16, NCB * 32) + (size_t)NCB * 32 * 4 + 8 * 4096 <= 160 * 1024 && !(knob(KNOB_VARIANT) & VARIANT_SPLIT_DIRECT_STORES);
-    if (a.Dout % (NCB * 32) == 0)
-        return staged ? launch_split_var<NCB, K0C, K1C, 256 | 4096>(a, stream) : launch_split_var<NCB, K0C, K1C, 256>(a, stream);
-    return staged ? launch_split_var<NCB, K0C, K1C, 4096>(a, stream) : launch_split_var<NCB, K0C, K1C, 0>(a, stream);
+#undef V
+    return fail(GNNMP_EUNSUPPORTED, "dense_split: no instance for VAR %d", r.var);
 }
 
-// Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (the caller falls back to the fp32-MFMA kernels).
-int dense_split_try(const DenseCall &c, hipStream_t stream) {
-    if (knob(KNOB_DENSE_GENERIC) != 0 || knob(KNOB_DENSE_SPLIT) < 0) return 1;
+int dense_launch_split(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
     const bool two = c.D2 > 0;
-    if ((c.D1 & 3) || (c.D2 & 3) || (c.Dout & 3) || c.Dout < 4 || c.N < 32) return 1;
-    {
-        // 256 outputs (SAGEConv(100 => 256)): W in registers, x through LDS once (dense_wreg.hip)
-        const int rc = dense_wreg_try(c, stream);
-        if (rc != 1) return rc;
-    }
-    // column blocks are 32 wide: a Dout that pads by more than a tenth (100 -> 128) costs more MFMA work and a select per stored piece
-    // than the fp32 16x16x4 kernel's 16-wide blocks (measured 2.4 M x 100 => 100: 625 us here, 549 us there)
-    if (((c.Dout + 31) & ~(int64_t)31) * 10 > c.Dout * 11) return 1;
-    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 15)) return 1;
-    if (two && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
-    const int kcat = (int)(c.D1 + c.D2), nkb = split_nkb(kcat);
+    const WStrides s1 = w_strides(c.w_layout, c.ldw1), s2 = w_strides(c.w_layout, c.ldw2);
     SplitArgs a;
     a.x[0] = c.x1; a.x[1] = c.x2;
     a.w.W[0] = c.W1; a.w.W[1] = two ? c.W2 : c.W1;
     a.w.K[0] = (int)c.D1; a.w.K[1] = (int)c.D2;
-    a.w.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.w.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
-    a.w.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.w.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
+    a.w.sj[0] = s1.sj; a.w.sk[0] = s1.sk;
+    a.w.sj[1] = s2.sj; a.w.sk[1] = s2.sk;
     a.bias = c.bias;
     a.act = c.act;
     a.out = c.out;
     a.N = c.N;
     a.Dout = (int)c.Dout;
-    a.waves = 12;
-    a.nkb = nkb;
-    // the widest column tile whose image fits: fewer passes over x.  K known at compile time for the shapes of the configs.
-    const size_t budget = 160 * 1024 - 1024;
-    if (c.Dout > 64 && split_img_bytes(kcat, 128) <= budget) {
-        if (two) {
-            if (c.D1 == 16 && c.D2 == 16) return launch_split<4, 16, 16>(a, stream);     // GraphConv 16 + 16 => 128
-            if (c.D1 == 100 && c.D2 == 100) return launch_split<4, 100, 100>(a, stream);   // SAGEConv 100 + 100 => 256 (two column tiles)
-            return launch_split<4, 0, 1>(a, stream);
-        }
-        if (c.D1 == 100) return launch_split<4, 100, 0>(a, stream);        // 100 => 100 | 128 (GCNConv, GATConv dense_x: products)
-        if (c.D1 == 128) return launch_split<4, 128, 0>(a, stream);        // 128 => 128 (arxiv)
-        return launch_split<4, 0, 0>(a, stream);
-    }
-    if (split_img_bytes(kcat, 64) <= budget) {
-        if (two) {
-            if (c.D1 == 128 && c.D2 == 128) return launch_split<2, 128, 128>(a, stream);   // GraphConv 128 + 128 => 128 (two column tiles)
-            return launch_split<2, 0, 1>(a, stream);
-        }
-        return launch_split<2, 0, 0>(a, stream);
-    }
-    return 1;
+    a.waves = r.waves;
+    a.nkb = split_nkb((int)(c.D1 + c.D2));
+#define GNNMP_SPLIT_CASE(NCB, K0C, K1C) if (r.ncb == NCB && r.k0c == K0C && r.k1c == K1C) return launch_split<NCB, K0C, K1C>(a, r, stream)
+    GNNMP_SPLIT_CASE(4, 16, 16);      // GraphConv 16 + 16 => 128
+    GNNMP_SPLIT_CASE(4, 100, 100);    // SAGEConv 100 + 100 => 256 (two column tiles)
+    GNNMP_SPLIT_CASE(4, 0, 1);
+    GNNMP_SPLIT_CASE(4, 100, 0);      // 100 => 100 | 128 (GCNConv, GATConv dense_x: products)
+    GNNMP_SPLIT_CASE(4, 128, 0);      // 128 => 128 (arxiv)
+    GNNMP_SPLIT_CASE(4, 0, 0);
+    GNNMP_SPLIT_CASE(2, 128, 128);    // GraphConv 128 + 128 => 128 (two column tiles)
+    GNNMP_SPLIT_CASE(2, 0, 1);
+    GNNMP_SPLIT_CASE(2, 0, 0);
+#undef GNNMP_SPLIT_CASE
+    return fail(GNNMP_EUNSUPPORTED, "dense_split: no instance <%d, %d, %d>", r.ncb, r.k0c, r.k1c);
 }
 
 }  // namespace gnnmp

@@ -10,8 +10,6 @@
 // waves per SIMD, the next tile's rows in flight during the current tile's MFMAs, a two-deep register pipeline of the A-operand
 // reads; no barrier after the image.  Measured: matrix pipe 74-79 % busy at the 2.25 GHz the chip holds under this load
 // (1 380 W of the 1 400 W socket limit), 89-126 TF by shape (profiles/README.md, round 2).
-#include <algorithm>
-
 #include "launch.h"
 #include "mfma16.h"
 
@@ -32,13 +30,10 @@ struct T16Args {
     int dbg;                // GNNMP_EXPERIMENTS builds, knob 13: 1 = no stores, 2 = no x loads (same row for every tile); else 0
 };
 
-// threads per block the register budget allows: four waves per SIMD (<= 128 VGPRs) up to seven column blocks; with eight, the
-// accumulators (32) + two row buffers (2 x 28-32) + the two-deep A-operand buffer (32) need ~140: three waves per SIMD
-template <int NCB>
-constexpr int t16_max_threads() { return NCB >= 8 ? 768 : 1024; }
+// (threads per block the register budget allows: t16_max_threads(NCB), dense_route.h)
 
 template <int NCB, int MAXB, int KQ1, int KQ2>
-__global__ void __launch_bounds__(t16_max_threads<NCB>()) dense_t16_kernel(const T16Args a) {
+__global__ void __launch_bounds__(t16_max_threads(NCB)) dense_t16_kernel(const T16Args a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr int DP = NCB * 16;
     f32x4 *img = reinterpret_cast<f32x4 *>(lds_raw);
@@ -125,69 +120,46 @@ __global__ void __launch_bounds__(t16_max_threads<NCB>()) dense_t16_kernel(const
     }
 }
 
+// ---- the launcher: dense_plan (dense_route.h) chose the instance <NCB, MAXB, KQ1, KQ2>, the waves, the grid and the LDS bytes ---------
 template <int NCB, int MAXB, int KQ1, int KQ2>
-static int launch_t16(const T16Args &a0, hipStream_t stream) {
-    T16Args a = a0;
-    constexpr int DP = NCB * 16;
-    const int rows = t16_img_rows(a.K[0]) + (a.nseg > 1 ? t16_img_rows(a.K[1]) : 0);
-    const size_t lds = (size_t)rows * DP * 16 + (size_t)DP * 4;
+static int launch_t16(const T16Args &a, const DenseRoute &r, hipStream_t stream) {
     GNNMP_LDS_OPTIN("dense_t16_kernel", &dense_t16_kernel<NCB, MAXB, KQ1, KQ2>);
-    const int cus = device_cus();
-    const int64_t ntiles = (a.N + 15) / 16;
-    // waves per block: 16 (four per SIMD) on large inputs; on small ones fewer, so that every CU gets a block
-    constexpr int max_waves = t16_max_threads<NCB>() / 64;
-    int waves = (int)std::min<int64_t>(max_waves, std::max<int64_t>(4, (ntiles + cus - 1) / cus));
-    const int kw = knob(KNOB_DENSE_T16_WAVES);
-    if (kw >= 1 && kw <= max_waves) waves = kw;
-    a.waves = waves;
-    a.dbg = GNNMP_ABLATION(knob(KNOB_T16_DEBUG));
-    const int64_t gx = std::min<int64_t>(cus, (ntiles + waves - 1) / waves);
-    dim3 grid((unsigned)gx, (unsigned)((a.Dout + DP - 1) / DP));
-    dense_t16_kernel<NCB, MAXB, KQ1, KQ2><<<grid, 64 * waves, lds, stream>>>(a);
+    dense_t16_kernel<NCB, MAXB, KQ1, KQ2><<<dim3(r.grid_x, r.grid_y), 64 * r.waves, r.lds_bytes, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_t16_kernel");
-    dense_route().kernel = DENSE_T16;
     return GNNMP_OK;
 }
 
-// Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (the caller falls back to dense.hip's kernels).
-int dense_t16_try(const DenseCall &c, hipStream_t stream) {
-    if (knob(KNOB_DENSE_GENERIC) != 0) return 1;
-    const int nseg = c.D2 > 0 ? 2 : 1;
-    if ((c.D1 & 3) || (c.D2 & 3) || c.D1 > 128 || c.D2 > 128 || (c.Dout & 3) || c.Dout < 4) return 1;
-    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 15)) return 1;
-    if (nseg > 1 && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
-    if (c.N < 16) return 1;
+int dense_launch_t16(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
+    const WStrides s1 = w_strides(c.w_layout, c.ldw1), s2 = w_strides(c.w_layout, c.ldw2);
     T16Args a;
     a.x[0] = c.x1; a.W[0] = c.W1; a.K[0] = (int)c.D1;
     a.x[1] = c.x2; a.W[1] = c.W2; a.K[1] = (int)c.D2;
-    a.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
-    a.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
-    a.nseg = nseg;
+    a.sj[0] = s1.sj; a.sk[0] = s1.sk;
+    a.sj[1] = s2.sj; a.sk[1] = s2.sk;
+    a.nseg = c.D2 > 0 ? 2 : 1;
     a.bias = c.bias;
     a.act = c.act;
     a.out = c.out;
     a.N = c.N;
     a.Dout = (int)c.Dout;
-    a.waves = 16;
-    // column blocks of 16 per column tile: as few padded columns as the shape allows (100 -> 7 x 16 = 112, not 128)
-    const int cb = (int)((c.Dout + 15) / 16);
-    const int kq1 = (int)c.D1 / 4, kq2 = (int)c.D2 / 4;
-    if (cb > 8 || cb == 8) {
-        // 128-column tiles (grid.y of them): the shapes of the configs first, K known at compile time
-        if (kq1 == 25 && kq2 == 0) return launch_t16<8, 7, 25, 0>(a, stream);     // GATConv dense_x 100 => 128
-        if (kq1 == 32 && kq2 == 0) return launch_t16<8, 8, 32, 0>(a, stream);     // arxiv 128 => 128
-        if (kq1 == 25 && kq2 == 25) return launch_t16<8, 7, 25, 25>(a, stream);   // SAGEConv 100 + 100 => 256
-        if (kq1 == 32 && kq2 == 32) return launch_t16<8, 8, 32, 32>(a, stream);   // GraphConv 128 + 128 => 128
-        if (kq1 == 4 && kq2 == 4) return launch_t16<8, 1, 4, 4>(a, stream);       // GraphConv 16 + 16 => 128
-        return launch_t16<8, 8, -1, -1>(a, stream);
-    }
-    if (cb == 7) {
-        if (kq1 == 25 && kq2 == 0) return launch_t16<7, 7, 25, 0>(a, stream);     // GCNConv 100 => 100
-        return launch_t16<7, 8, -1, -1>(a, stream);
-    }
-    if (cb > 4) return launch_t16<6, 8, -1, -1>(a, stream);
-    if (cb > 2) return launch_t16<4, 8, -1, -1>(a, stream);
-    return launch_t16<2, 8, -1, -1>(a, stream);
+    a.waves = r.waves;
+    a.dbg = r.dbg;
+#define GNNMP_T16_CASE(NCB, MAXB, KQ1, KQ2) \
+    if (r.ncb == NCB && r.maxb == MAXB && r.kq1 == KQ1 && r.kq2 == KQ2) return launch_t16<NCB, MAXB, KQ1, KQ2>(a, r, stream)
+    // 128-column tiles (grid.y of them): the shapes of the configs, K known at compile time
+    GNNMP_T16_CASE(8, 7, 25, 0);      // GATConv dense_x 100 => 128
+    GNNMP_T16_CASE(8, 8, 32, 0);      // arxiv 128 => 128
+    GNNMP_T16_CASE(8, 7, 25, 25);     // SAGEConv 100 + 100 => 256
+    GNNMP_T16_CASE(8, 8, 32, 32);     // GraphConv 128 + 128 => 128
+    GNNMP_T16_CASE(8, 1, 4, 4);       // GraphConv 16 + 16 => 128
+    GNNMP_T16_CASE(8, 8, -1, -1);
+    GNNMP_T16_CASE(7, 7, 25, 0);      // GCNConv 100 => 100
+    GNNMP_T16_CASE(7, 8, -1, -1);
+    GNNMP_T16_CASE(6, 8, -1, -1);
+    GNNMP_T16_CASE(4, 8, -1, -1);
+    GNNMP_T16_CASE(2, 8, -1, -1);
+#undef GNNMP_T16_CASE
+    return fail(GNNMP_EUNSUPPORTED, "dense_t16: no instance <%d, %d, %d, %d>", r.ncb, r.maxb, r.kq1, r.kq2);
 }
 
 }  // namespace gnnmp

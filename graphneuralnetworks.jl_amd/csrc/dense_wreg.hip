@@ -20,9 +20,6 @@
 //     of the block half a tile apart — the partner's ~120-instruction epilogue took 3400 cycles and the whole kernel 1.50 ms;
 //   * s_setprio only swaps which half of the block waits at the barrier (older half 4400 + 1500 waiting, younger 6500, or vice versa);
 //   * under this load the chip clocks at ~1.65 GHz (7900 cycles in 4.8 us): the matrix pipe alone would need 0.9 ms, not 0.62.
-#include <algorithm>
-#include <mutex>
-
 #include "launch.h"
 #include "msplit.h"
 
@@ -38,14 +35,13 @@ struct WregArgs {
     int Dout;               // 256
 };
 
-constexpr int WR_WAVES = 8, WR_THREADS = 64 * WR_WAVES, WR_DP = 32 * WR_WAVES;
+// (WR_WAVES = 8, WR_THREADS, WR_DP = 256 and WR_ROW = 33: dense_route.h, which sizes the launch with them)
 
 // 16-byte unit (k-block kb, half hh, row n) of a plane of the tile image
 // Rows of 32 units padded to 33: the loader's lanes run along r at a fixed n (33 units = 132 dwords apart: the eight lanes of a
 // ds_write_b128 group cover all 32 banks), the MFMA waves' lanes along n at a fixed r (contiguous); and a k-block is a CONSTANT
 // 1056 bytes further on, so that the 39 reads of a tile share one address register (an XOR by r costs one per k-block: 26 VGPRs
 // that this kernel does not have).
-constexpr int WR_ROW = 33;
 __device__ __forceinline__ int wr_unit(int kb, int hh, int n) {
     return (2 * kb + hh) * WR_ROW + n;
 }
@@ -196,54 +192,34 @@ __global__ void __launch_bounds__(WR_THREADS) dense_wreg_kernel(const WregArgs a
     }
 }
 
+// ---- the launcher: dense_plan (dense_route.h) chose the instance <K0C, K1C> (GNNMP_WREG_SHAPES, with the measurements behind the
+// list), the grid and the LDS bytes
 template <int K0C, int K1C>
-static int launch_wreg(const WregArgs &a, hipStream_t stream) {
-    constexpr int NKB = (K0C + K1C + 15) / 16;
-    const size_t lds = (size_t)2 * 3 * NKB * 2 * WR_ROW * 16 + (size_t)WR_DP * 4 + (size_t)WR_WAVES * 4096;
+static int launch_wreg(const WregArgs &a, const DenseRoute &r, hipStream_t stream) {
     GNNMP_LDS_OPTIN("dense_wreg_kernel", &dense_wreg_kernel<K0C, K1C>);
-    const int64_t ntiles = (a.N + 31) / 32;
-    const int64_t gx = std::min<int64_t>(device_cus(), ntiles);
-    dense_wreg_kernel<K0C, K1C><<<(unsigned)gx, WR_THREADS, lds, stream>>>(a);
+    dense_wreg_kernel<K0C, K1C><<<r.grid_x, WR_THREADS, r.lds_bytes, stream>>>(a);
     GNNMP_LAUNCH_CHECK("dense_wreg_kernel");
-    dense_route().kernel = DENSE_WREG;
     return GNNMP_OK;
 }
 
-// Returns GNNMP_OK if it launched, 1 if the shape is not one this kernel takes (dense_split_try goes on with its own kernels).
-int dense_wreg_try(const DenseCall &c, hipStream_t stream) {
-    if (knob(KNOB_VARIANT) & VARIANT_NO_WREG) return 1;       // (A/B runs)
-    if (c.Dout != WR_DP || c.N < ((knob(KNOB_VARIANT) & VARIANT_WREG_SMALL) ? 4096 : 32768) || c.N > (int64_t)INT32_MAX - 64) return 1;      // (row numbers of a tile are 32-bit)
+int dense_launch_wreg(const DenseCall &c, const DenseRoute &r, hipStream_t stream) {
     const bool two = c.D2 > 0;
-    if ((reinterpret_cast<uintptr_t>(c.x1) & 15) || (reinterpret_cast<uintptr_t>(c.out) & 127)) return 1;
-    if (two && (reinterpret_cast<uintptr_t>(c.x2) & 15)) return 1;
+    const WStrides s1 = w_strides(c.w_layout, c.ldw1), s2 = w_strides(c.w_layout, c.ldw2);
     WregArgs a;
     a.x[0] = c.x1; a.x[1] = c.x2;
     a.w.W[0] = c.W1; a.w.W[1] = two ? c.W2 : c.W1;
     a.w.K[0] = (int)c.D1; a.w.K[1] = (int)c.D2;
-    a.w.sj[0] = c.w_layout == 0 ? c.ldw1 : 1; a.w.sk[0] = c.w_layout == 0 ? 1 : c.ldw1;
-    a.w.sj[1] = c.w_layout == 0 ? c.ldw2 : 1; a.w.sk[1] = c.w_layout == 0 ? 1 : c.ldw2;
+    a.w.sj[0] = s1.sj; a.w.sk[0] = s1.sk;
+    a.w.sj[1] = s2.sj; a.w.sk[1] = s2.sk;
     a.bias = c.bias;
     a.act = c.act;
     a.out = c.out;
     a.N = c.N;
     a.Dout = (int)c.Dout;
-    // Instantiated for the layer widths of the reference's examples and benchmarks (64, 100, 128 per segment; one segment up to 256): the
-    // W planes of a wave's 32 columns take 12 VGPRs per 16 positions of the concatenated K — 96 (K = 128) to 192 (K = 256) of the 256 a
-    // wave has at two waves a SIMD.  K = 228 and 256 (100 + 128, 128 + 128, 256) were compiled too and spill 22-34 registers: left to
-    // dense_split's LDS-resident W, like every other shape (return 1).  Measured at N = 2.4 M, => 256 (tools/experiments/dense_wreg_ab.py, one box,
-    // microseconds, this kernel / dense_split): 100+100 1439 / 1578, 64+64 1006 / 1200, 64+100 1326 / 1626, 128+64 1514 / 1701, 200 1572 /
-    // 1670 — and one segment of K <= 128 the other way round (64: 699 / 679, 100: 922 / 871, 128: 988 / 969: not instantiated); at
-    // N = 5 000 the eight-wave blocks are too few (31 / 18): from 32 768 rows on.  Bit-identical to dense_split on every shape.
-#define GNNMP_WREG_CASE(K0, K1) if (c.D1 == K0 && c.D2 == K1) return launch_wreg<K0, K1>(a, stream)
-    GNNMP_WREG_CASE(100, 100);      // SAGEConv(100 => 256), GraphConv(100 => 256): BASELINE config 4
-    GNNMP_WREG_CASE(64, 64);
-    GNNMP_WREG_CASE(64, 100);
-    GNNMP_WREG_CASE(100, 64);
-    GNNMP_WREG_CASE(64, 128);
-    GNNMP_WREG_CASE(128, 64);
-    GNNMP_WREG_CASE(200, 0);        // one segment: only where x is split twice by dense_split's two column passes AND K is large
+#define GNNMP_WREG_CASE(K0, K1) if (r.k0c == K0 && r.k1c == K1) return launch_wreg<K0, K1>(a, r, stream);
+    GNNMP_WREG_SHAPES(GNNMP_WREG_CASE)
 #undef GNNMP_WREG_CASE
-    return 1;
+    return fail(GNNMP_EUNSUPPORTED, "dense_wreg: no instance <%d, %d>", r.k0c, r.k1c);
 }
 
 }  // namespace gnnmp

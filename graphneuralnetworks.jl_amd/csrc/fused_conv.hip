@@ -737,8 +737,9 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
     a.xi = D1 > 0 ? xi : nullptr;
     a.D1 = (int)D1;
     a.W[0] = W_root; a.W[1] = W_agg;
-    a.sj[0] = w_layout == 0 ? ldw_root : 1; a.sk[0] = w_layout == 0 ? 1 : ldw_root;
-    a.sj[1] = w_layout == 0 ? ldw_agg : 1; a.sk[1] = w_layout == 0 ? 1 : ldw_agg;
+    const WStrides s_root = w_strides(w_layout, ldw_root), s_agg = w_strides(w_layout, ldw_agg);
+    a.sj[0] = s_root.sj; a.sk[0] = s_root.sk;
+    a.sj[1] = s_agg.sj; a.sk[1] = s_agg.sk;
     a.bias = bias;
     a.act = act;
     a.out = out;

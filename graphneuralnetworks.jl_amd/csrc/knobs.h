@@ -12,8 +12,9 @@
     X(XCD_REMAP, 3, 1, "0 = off, 1 = auto (default: only when the gathered matrix fits the Infinity Cache), 2 = on")                 \
     X(LONG_ROW, 4, 0, "long-row threshold (0 = auto, at most GNNMP_LONG_ROW)")                                                       \
     X(BLOCK_WAVES, 5, 0, "waves per block in the row kernels: 0 = auto (propagate 4, GAT 1), else 1..4")                             \
-    X(DENSE_GENERIC, 6, 0, "0 = auto (dense_t16 on its shapes, else W-resident 32x32x2, else K-chunked), 1 = force K-chunked, "      \
-                           "2 = skip dense_t16 (round-1 kernels only)")                                                              \
+    X(DENSE_GENERIC, 6, 0, "0 = auto (dense_plan's whole order, dense_route.h), any other value = never dense_wreg, dense_split, "    \
+                           "dense_t16 or dense_narrow (the round-1 kernels only); 1 = not the W-resident 32x32x2 kernel either: "     \
+                           "K-chunked on every shape")                                                                               \
     X(DENSE_PREFETCH, 7, 17, "W-resident dense kernel scheduling: bit 4 = per-SIMD matrix-pipe token, low 4 bits = start skew of "   \
                              "waves 4-7 in s_sleep(127) units.  Default 17 (token + 1): 0.83 -> 0.72 ms at 2.4M x 100 => 100.  "     \
                              "Bit 5 = turn the cross-tile register prefetch OFF (on by default; its first version spilled, 270 "     \

@@ -4,6 +4,7 @@
 // Sections: the row reduction, softmax_rows, the dense family, graph_chain2, column sums, plan.
 #pragma once
 #include "common.h"
+#include "dense_route.h"
 
 namespace gnnmp {
 
@@ -49,9 +50,11 @@ int run_combine(gnnmp_graph_t *p, float *out, int64_t D, int aggr, hipStream_t s
 int softmax_rows_try(gnnmp_graph_t *p, const float *e, float *alpha, int64_t D, float den_add, float *partial, float *mx, float *den,
                      hipStream_t stream);
 
-// ---- the dense family (dense.hip -> dense_split.hip -> dense_wreg.hip, dense_t16.hip) ---------------------------------
-// gnnmp_dense_f32's arguments (gnnmp.h), validated, as its kernels' host paths pass them on.  Every *_try returns GNNMP_OK if
-// it launched, 1 if the shape is not one its kernel takes, or an error status.
+// ---- the dense family (dense.hip, dense_split.hip, dense_wreg.hip, dense_t16.hip) ---------------------------------------
+// gnnmp_dense_f32's arguments (gnnmp.h), validated.  dense_plan (dense_route.h) decides which kernel, which template instance and what
+// launch geometry a call gets; gnnmp_dense_f32 keeps that DenseRoute in the calling thread's record (gnnmp_debug_dense_route) and calls
+// the one launcher the route names.  A launcher maps the route's instance fields onto its template and fills the kernel's argument
+// struct: it decides nothing, and a route that names no compiled instance is an error.
 struct DenseCall {
     const float *x1, *W1;
     int64_t D1, ldw1;
@@ -63,24 +66,15 @@ struct DenseCall {
     float *out;
     int64_t N, Dout;
 };
-int dense_split_try(const DenseCall &c, hipStream_t stream);
-int dense_wreg_try(const DenseCall &c, hipStream_t stream);
-int dense_t16_try(const DenseCall &c, hipStream_t stream);
-// What the last gnnmp_dense_f32 call of this thread launched (gnnmp_debug_dense_route, gnnmp.h): a host record that every launch site
-// of the family fills in, so that a test knows which kernel and which configuration its shape reached.  gnnmp_dense_f32 clears it on
-// entry; the fields after `kernel` describe dense_wlds_kernel and are zero for the others.
-enum DenseKernel { DENSE_NONE = 0, DENSE_SPLIT = 1, DENSE_WREG = 2, DENSE_T16 = 3, DENSE_NARROW = 4, DENSE_WLDS = 5, DENSE_MFMA = 6 };
-struct DenseRoute {
-    int kernel;     // DenseKernel
-    int tw;         // column tile of the full launch: 128 | 64
-    int waves;      // waves a block: 8 | 4
-    int ks;         // columns of x staged per k-chunk
-    int tp;         // output column tiles per epilogue pass
-    int rem_nt;     // NT of the remainder launch (0 = Dout is a multiple of tw)
-    int prefetch;   // the kernel's pf_on, restated on the host from the same fields
-    int full;       // column tiles of the full launch (grid.y; 0 = only the remainder launch)
-};
-DenseRoute &dense_route();   // the calling thread's record (dense.hip)
+int dense_launch_split(const DenseCall &c, const DenseRoute &r, hipStream_t stream);    // dense_split.hip
+int dense_launch_wreg(const DenseCall &c, const DenseRoute &r, hipStream_t stream);     // dense_wreg.hip
+int dense_launch_t16(const DenseCall &c, const DenseRoute &r, hipStream_t stream);      // dense_t16.hip
+int dense_launch_narrow(const DenseCall &c, const DenseRoute &r, hipStream_t stream);   // dense.hip
+int dense_launch_wlds(const DenseCall &c, const DenseRoute &r, hipStream_t stream);     // dense.hip
+int dense_launch_mfma(const DenseCall &c, const DenseRoute &r, hipStream_t stream);     // dense.hip
+// element strides of W(j, k) at W[j * sj + k * sk]: w_layout 0 = W[Dout][K] (row j contiguous in k), 1 = W[K][Dout] (Julia column-major)
+struct WStrides { int64_t sj, sk; };
+inline WStrides w_strides(int w_layout, int64_t ldw) { return w_layout == 0 ? WStrides{ldw, 1} : WStrides{1, ldw}; }
 
 // ---- graph_chain2.hip -----------------------------------------------------------------------------------------------------------
 int graph_chain2_try(gnnmp_graph_t *p, const gnnmp_chain_jobs_t *J, const int64_t *seg_ptr, int64_t G, const float *x, int n_layers,

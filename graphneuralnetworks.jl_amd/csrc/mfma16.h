@@ -19,6 +19,7 @@
 // one MFMA step instead of four.  rem = 2, 3: a block whose lanes q >= rem supply explicit zeros.
 #pragma once
 #include "common.h"
+#include "dense_route.h"
 
 namespace gnnmp {
 
@@ -28,8 +29,7 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// rows of the W image a segment of K floats occupies (multiple of 4: a block never reads another segment's rows)
-__host__ __device__ inline int t16_img_rows(int K) { return ((K / 4) + 3) & ~3; }
+// t16_img_rows (rows of the W image a segment of K floats occupies): dense_route.h
 
 // Fill the W image of one segment: img[(kq0 + kq) * DP + f] = (W(n0 + f, 4 kq + i))_i for f < ncols, kq < K / 4; everything else
 // (padding rows, padding columns) zero.  W(j, k) at W[j * sj + k * sk].  All threads of the block call this; caller barriers.

@@ -32,6 +32,7 @@
 //   The hardware's own k <-> (h, e) assignment does not matter: A and B use the same one, and a sum over k is permutation-free.
 #pragma once
 #include "common.h"
+#include "dense_route.h"
 
 namespace gnnmp {
 
@@ -83,9 +84,7 @@ struct WCat {
     int64_t sj[2], sk[2];
     int K[2];
 };
-__host__ __device__ inline int split_nkb(int kcat) { return (kcat + 15) >> 4; }
-// bytes of the three-plane image of a DP-column tile
-__host__ __device__ inline size_t split_img_bytes(int kcat, int DP) { return (size_t)3 * split_nkb(kcat) * 2 * DP * 16; }
+// split_nkb, split_img_bytes (k-blocks of 16 positions; bytes of the three-plane image of a DP-column tile): dense_route.h
 
 __device__ __forceinline__ float wcat_at(const WCat &w, int j, int c) {
     const int s = c >= w.K[0];

@@ -1179,8 +1179,8 @@ int gnnmp_plan_reset_counters(gnnmp_graph_t *plan, gnnmp_stream_t stream);
  *   gnnmp_debug_pool_pick(...)     the block pool's slot choice on host arrays
  *   gnnmp_debug_random_walk_pe_f32(...)  gnnmp_random_walk_pe_f32 with the LDS budget of a workgroup in bytes (0 = the default, 64 KB): a
  *                                  small budget sends small graphs through the scratch path (tests/test_rwpe.py)
- *   gnnmp_debug_dense_route(info)  what the last gnnmp_dense_f32 call of the calling thread launched (host memory, written at the launch
- *                                  sites: no synchronisation, no allocation, nothing a stream capture sees).  info[0] = the kernel: 0 none
+ *   gnnmp_debug_dense_route(info)  what the last gnnmp_dense_f32 call of the calling thread launched (host memory, written by that
+ *                                  call: no synchronisation, no allocation, nothing a stream capture sees).  info[0] = the kernel: 0 none
  *                                  (the call returned before a launch), 1 dense_split, 2 dense_wreg, 3 dense_t16, 4 dense_narrow,
  *                                  5 dense_wlds, 6 dense_mfma.  For dense_wlds: info[1] = column tile (128 | 64), [2] = waves a block
  *                                  (8 | 4), [3] = ks, the columns of x staged per k-chunk, [4] = tp, the column tiles per epilogue pass,

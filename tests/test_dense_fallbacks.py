@@ -28,8 +28,9 @@ SENTINEL = -3.0e38                                           # no result of thes
 GUARD_ROWS = 32
 U = 2.0 ** -24
 
-# (K1, K2, Dout): tw, waves, k-chunks of the longer segment, tp, NT of the remainder launch, prefetch condition — what dense.hip's
-# size_for gives for the shape (restated by hand); the hook is the authority, every wlds call asserts these against it
+# (K1, K2, Dout): tw, waves, k-chunks of the longer segment, tp, NT of the remainder launch, prefetch condition — what
+# wlds_size_for (csrc/dense_route.h) gives for the shape; the hook is the authority, every wlds call asserts these against it, and
+# tests/test_dense_route_cpu.py asks the planner itself for these sixteen
 TABLE = {
     (100, 0, 111): dict(tw=128, waves=8, chunks=1, tp=3, nt=4, pf=1),       # whole-K staging, two epilogue passes of 96 + 15 columns
     (100, 0, 47): dict(tw=128, waves=8, chunks=1, tp=4, nt=2, pf=1),        # a classifier head
