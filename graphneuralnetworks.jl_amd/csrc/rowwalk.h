@@ -96,7 +96,9 @@ struct VRow {
 //   VROW_ORDER         the host side may set r.row_order
 //   VROW_NO_CHUNK_ROW  the kernel never reads .row of a chunk: skip the chunk_row lookup (.row = 0 there).  The compiler does not
 //                      drop that load by itself — .row merges with the ordinary rows' before the kernel tells the two apart again.
-enum { VROW_REMAP = 1, VROW_ORDER = 2, VROW_NO_CHUNK_ROW = 4 };
+//   VROW_WHOLE         the kernel walks every ordinary row whole, whatever its length (its PlanRows carries n_chunks = 0): a row
+//                      longer than long_thresh is NOT skipped
+enum { VROW_REMAP = 1, VROW_ORDER = 2, VROW_NO_CHUNK_ROW = 4, VROW_WHOLE = 8 };
 template <int FLAGS = 0>
 __device__ __forceinline__ bool decode_vrow(const PlanRows &r, const RowGeom &g, int block, VRow &w) {
     const int lane = threadIdx.x & 63;
@@ -120,7 +122,7 @@ __device__ __forceinline__ bool decode_vrow(const PlanRows &r, const RowGeom &g,
         if ((FLAGS & VROW_ORDER) && r.row_order) w.row = r.row_order[w.row];
         w.beg = r.rowptr[w.row];
         w.end = r.rowptr[w.row + 1];
-        if (w.end - w.beg > (uint32_t)r.long_thresh) return false;   // split row: its chunks are virtual rows
+        if (!(FLAGS & VROW_WHOLE) && w.end - w.beg > (uint32_t)r.long_thresh) return false;   // split row: its chunks are virtual rows
     }
     return true;
 }

@@ -55,6 +55,7 @@ SYMBOLS = (
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32",
+    "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -113,6 +114,17 @@ class RwpeJob(ctypes.Structure):
     """gnnmp_rwpe_t: one gnnmp_random_walk_pe_f32 call"""
     _fields_ = [("w", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
                 ("walk_length", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
+class EdgeConvJob(ctypes.Structure):
+    """gnnmp_edge_conv_t: one gnnmp_edge_conv_f32 call (p [N][2C] planar, y [N][C])"""
+    _fields_ = [("p", ctypes.c_void_p), ("y", ctypes.c_void_p), ("aggr", ctypes.c_int), ("act", ctypes.c_int)]
+
+
+class EdgeConvGradJob(ctypes.Structure):
+    """gnnmp_edge_conv_grad_t: one gnnmp_edge_conv_grad_f32 call (p, y, dy read; dp [N][2C] written)"""
+    _fields_ = [("p", ctypes.c_void_p), ("y", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dp", ctypes.c_void_p),
+                ("aggr", ctypes.c_int), ("act", ctypes.c_int)]
 
 
 class GnnmpError(RuntimeError):
@@ -254,6 +266,8 @@ def load():
         "gnnmp_has_multi_edges": [vp, vp, i, i, i64, ctypes.POINTER(i), vp],
         "gnnmp_has_isolated_nodes": [vp, ctypes.POINTER(i), vp],
         "gnnmp_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), vp],
+        "gnnmp_edge_conv_f32": [vp, ctypes.POINTER(EdgeConvJob), i64, vp],
+        "gnnmp_edge_conv_grad_f32": [vp, vp, ctypes.POINTER(EdgeConvGradJob), i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

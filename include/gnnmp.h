@@ -31,7 +31,8 @@
  *     gnnmp_negative_sample, gnnmp_coalesce_edges, gnnmp_compact_edges, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
- *     two without the eager call, they use no plan scratch.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py),
+ *     likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1135,6 +1136,70 @@ typedef struct {
     const gnnmp_hetero_rel_grad_t *rels;
 } gnnmp_hetero_src_t;
 int gnnmp_hetero_propagate_grad_f32(const gnnmp_hetero_src_t *srcs, int n_srcs, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * EdgeConv with a one-layer nn, forward and pullback — edge_conv, GNNlib/src/layers/conv.jl:237-246:
+ *   propagate(edge_conv_message, g, l.aggr; xi = x, xj = x),  edge_conv_message(l, xi, xj, e) = l.nn(vcat(xi, xj .- xi))
+ * For nn = Dense(2D => C, σ) with W = [W1 | W2]:  nn(vcat(xi, xj - xi)) = σ(W1 xi + b - W2 xi + W2 xj), so the contraction is ONE dense
+ * call of the caller on N rows (gnnmp_dense_f32): P = x [W1; W2]' + [b; 0], and the two exports below do the per-edge rest as passes of a
+ * row kernel over gathered rows of P (csrc/edge_conv.hip).  Nothing of E rows is read or written.
+ *
+ * P is [N][2C] row-major, PLANAR: columns [0, C) are the x_i share with the bias folded in, columns [C, 2C) the x_j share (planar, not
+ * interleaved: the per-edge gather fetches only the x_j share).
+ *
+ * Forward, for destination i and its slots in the plan's order (the original edge order), per channel c:
+ *   a_i[c]   = P[i][c] − P[i][C+c]          one rounded subtraction, once per row, kept in registers
+ *   pre_e[c] = a_i[c] + P[j][C+c]           one rounded add, no contraction
+ *   m_e[c]   = σ(pre_e[c])                  σ ∈ {identity, relu}
+ *   y_i[c]   = aggr_e m_e[c]                +, mean (sum / count, true division), max, min
+ * The fold is sequential in edge order.  Empty rows keep the identity: 0 / 0 / −Inf / +Inf, as everywhere else in the ABI.
+ *
+ * Backward, given Δ [N][C]:
+ *   r_e = Δ_i                               (+)
+ *       = Δ_i / count_i                     (mean; divided once per row)
+ *       = (m_e == y_i) ? Δ_i : 0            (max / min; EVERY maximiser receives Δ, NNlib's rule, as gnnmp_propagate_maxmin_grad_f32)
+ *   g_e = r_e                               (identity)
+ *       = pre_e > 0 ? r_e : 0               (relu; 0 at 0, as gnnmp_act_grad_f32)
+ *   dA_i = Σ_{e into i, edge order} g_e
+ *   dB_j = Σ_{e out of j, edge order} g_e
+ *   dP[i][c]   = dA_i[c]
+ *   dP[j][C+c] = dB_j[c] − dA_j[c]
+ * m_e and pre_e are RECOMPUTED in both backward passes with exactly the two operations above (the tie test is an equality on floats).  The
+ * caller finishes on the dense adjoints: [dW1; dW2] = dP' x (gnnmp_dense_grad_w_f32), db = colsum(dP[:, :C]), dx = dP [W1; W2]
+ * (gnnmp_dense_f32, w_layout = 1), dW = [dW1 | dW2].
+ *
+ *   plan     the graph's plan (rows = destinations); plan_t the plan of the reversed edge index (row j: the edges that leave j, in
+ *            original edge order).  Square (n_src == n_dst = N); plan_t of the same height and edge count.  Both are only READ.
+ *   job      a HOST record of device pointers:
+ *     gnnmp_edge_conv_t       p [N][2C] (read), y [N][C] (every element written), aggr: gnnmp_aggr, act: GNNMP_ACT_IDENTITY | GNNMP_ACT_RELU
+ *     gnnmp_edge_conv_grad_t  p [N][2C], y [N][C] the forward's output, dy [N][C] = Δ (all read), dp [N][2C] (every element written; must
+ *                             not overlap the inputs), aggr and act as in the forward
+ *   C        1 .. 2^20.  Any 4-byte aligned pointers: the kernels use 16- / 8-byte lanes when C % 4 / C % 2 == 0 and every pointer of
+ *            the call AND column C inside a row (p + C, dp + C) are aligned alike, 4-byte lanes otherwise.
+ * Both exports only launch (the gradient: the destination pass over plan, then the source pass over plan_t, on `stream`): no scratch,
+ * no atomics, no host wait; they may be recorded into a HIP graph without an eager call first; N = 0 (an empty graph) launches
+ * nothing.  Every row is walked WHOLE, in edge order, by one lane group, whatever its length (the plan's chunks are ignored): the bits
+ * are those of the sequential fold for every row — slow for hub rows (in a kNN graph only sources can be hubs).
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL plan / plan_t / job / p / y / dy / dp, C outside 1 .. 2^20, an unknown aggr, an act
+ * other than identity / relu, a plan with n_src != n_dst, a plan_t whose height or edge count differs from the plan's.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *p;
+    float *y;
+    int aggr;
+    int act;
+} gnnmp_edge_conv_t;
+typedef struct {
+    const float *p;
+    const float *y;
+    const float *dy;
+    float *dp;
+    int aggr;
+    int act;
+} gnnmp_edge_conv_grad_t;
+int gnnmp_edge_conv_f32(const gnnmp_graph_t *plan, const gnnmp_edge_conv_t *job, int64_t C, gnnmp_stream_t stream);
+int gnnmp_edge_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_edge_conv_grad_t *job, int64_t C,
+                             gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
