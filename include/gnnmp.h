@@ -31,8 +31,8 @@
  *     gnnmp_negative_sample, gnnmp_coalesce_edges, gnnmp_compact_edges, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
- *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py),
- *     likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
+ *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1200,6 +1200,55 @@ typedef struct {
 int gnnmp_edge_conv_f32(const gnnmp_graph_t *plan, const gnnmp_edge_conv_t *job, int64_t C, gnnmp_stream_t stream);
 int gnnmp_edge_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_edge_conv_grad_t *job, int64_t C,
                              gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The pullback of CGConv's gated message — cg_conv, GNNlib/src/layers/conv.jl:304-333:
+ *   propagate(cg_message, g, +; xi = x, xj = x, e),  cg_message(l, xi, xj, e) = dense_f(z) .* dense_s(z),  z = vcat(xi, xj, e)
+ * The forward is gnnmp_propagate_cg_f32 on three PLANAR matrices the caller's dense calls produce from the column blocks of [Wf; Ws]:
+ *   fs_i = x [Wf_i; Ws_i]' + [bf; bs]   [N][2C]        fs_j = x [Wf_j; Ws_j]'   [N][2C]        fs_e = e [Wf_e; Ws_e]'   [E][2C], optional
+ * columns [0, C) are dense_f's share, columns [C, 2C) dense_s's.  For edge k: j -> i and channel c < C:
+ *   f_k = fs_i[i][c]   + fs_j[j][c]   (+ fs_e[k][c])
+ *   s_k = fs_i[i][C+c] + fs_j[j][C+c] (+ fs_e[k][C+c])
+ *   m_k = sigmoid(f_k) * act(s_k),     y_i = Σ_{k into i} m_k
+ *
+ * Backward, given Δ [N][C]: f_k and s_k are RECOMPUTED with the same additions in the same order as the forward, and
+ *   gf_k = Δ_i * act(s_k) * sigmoid'(f_k)         sigmoid'(f) = sigmoid(f) sigmoid(−f)
+ *   gs_k = Δ_i * sigmoid(f_k) * act'(s_k)         act': identity 1 | relu s > 0 (0 at 0, as gnnmp_act_grad_f32) | softplus sigmoid(s) |
+ *                                                       tanh (1 − a)(1 + a), a = tanh(s)
+ *   dfs_i[i] = Σ_{k into i, edge order}   [gf_k | gs_k]
+ *   dfs_j[j] = Σ_{k out of j, edge order} [gf_k | gs_k]
+ *   dfs_e[k] = [gf_k | gs_k]                                  (only when wanted)
+ * The caller finishes on the dense adjoints, on N and E rows: d[Wf_i; Ws_i] = dfs_i' x and [dbf; dbs] = colsum(dfs_i)
+ * (gnnmp_dense_grad_w_f32), d[Wf_j; Ws_j] = dfs_j' x, d[Wf_e; Ws_e] = dfs_e' e, dx = dfs_i [Wf_i; Ws_i] + dfs_j [Wf_j; Ws_j] (+ Δ under
+ * the residual), de = dfs_e [Wf_e; Ws_e] (gnnmp_dense_f32, w_layout = 1), dWf = [dWf_i | dWf_j | dWf_e] and dWs likewise.
+ *
+ *   plan     the graph's plan (rows = destinations); plan_t the plan of the reversed edge index (row j: the edges that leave j, in
+ *            original edge order).  Square (n_src == n_dst = N), built WITHOUT plan-added self loops (fs_e has no row for them);
+ *            plan_t of the same height and edge count.  Both are only READ.
+ *   job      a HOST record of device pointers, gnnmp_cg_conv_grad_t:
+ *              fs_i, fs_j [N][2C], fs_e [E][2C] or NULL (no edge features), dy [N][C] = Δ: read
+ *              dfs_i, dfs_j [N][2C]: every element written (rows without in-edges / without out-edges: zeros)
+ *              dfs_e [E][2C] or NULL (not wanted): every element written, at the edge's ORIGINAL position
+ *              act: gnnmp_act, IDENTITY .. TANH — dense_s's activation, as in gnnmp_propagate_cg_f32
+ *            Outputs must not overlap the inputs or each other.
+ *   C        1 .. 2^19, the forward's bound.  Any 4-byte aligned pointers: the kernels use 16- / 8-byte lanes when C % 4 / C % 2 == 0 and
+ *            every pointer of the call AND column C inside a row are aligned alike, 4-byte lanes otherwise.
+ * The export only launches — the destination pass over plan, then the source pass over plan_t, on `stream` (csrc/cg_grad.hip): no scratch,
+ * no atomics, no host wait, no allocation; it may be recorded into a HIP graph without an eager call first; N = 0 (an empty graph)
+ * launches nothing.  Every row is walked WHOLE, in edge order, by one lane group, whatever its length (the plan's chunks are ignored):
+ * every sum has the bits of the sequential fold and two calls give equal bits — slow for hub rows.
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL plan / plan_t / job / fs_i / fs_j / dy / dfs_i / dfs_j, dfs_e given without fs_e,
+ * C outside 1 .. 2^19, an act outside IDENTITY .. TANH, a plan with n_src != n_dst, a plan_t whose height or edge count differs from
+ * the plan's, a plan built with self loops (n_total != n_edges).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *fs_i, *fs_j, *fs_e;   /* fs_e NULL = no edge features */
+    const float *dy;
+    float *dfs_i, *dfs_j, *dfs_e;      /* dfs_e NULL = not wanted */
+    int act;
+} gnnmp_cg_conv_grad_t;
+int gnnmp_cg_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_cg_conv_grad_t *job, int64_t C,
+                           gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
