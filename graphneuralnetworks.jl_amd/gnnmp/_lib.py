@@ -55,7 +55,7 @@ SYMBOLS = (
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32",
-    "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32",
+    "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -131,6 +131,12 @@ class CGConvGradJob(ctypes.Structure):
     """gnnmp_cg_conv_grad_t: one gnnmp_cg_conv_grad_f32 call (fs_i, fs_j, fs_e | None, dy read; dfs_i, dfs_j, dfs_e | None written)"""
     _fields_ = [("fs_i", ctypes.c_void_p), ("fs_j", ctypes.c_void_p), ("fs_e", ctypes.c_void_p), ("dy", ctypes.c_void_p),
                 ("dfs_i", ctypes.c_void_p), ("dfs_j", ctypes.c_void_p), ("dfs_e", ctypes.c_void_p), ("act", ctypes.c_int)]
+
+
+class NNConvGradJob(ctypes.Structure):
+    """gnnmp_nn_conv_grad_t: one gnnmp_nn_conv_grad_f32 call (x, we | None, dm read; dx | None, dwe | None written)"""
+    _fields_ = [("x", ctypes.c_void_p), ("we", ctypes.c_void_p), ("dm", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+                ("dwe", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -275,6 +281,7 @@ def load():
         "gnnmp_edge_conv_f32": [vp, ctypes.POINTER(EdgeConvJob), i64, vp],
         "gnnmp_edge_conv_grad_f32": [vp, vp, ctypes.POINTER(EdgeConvGradJob), i64, vp],
         "gnnmp_cg_conv_grad_f32": [vp, vp, ctypes.POINTER(CGConvGradJob), i64, vp],
+        "gnnmp_nn_conv_grad_f32": [vp, ctypes.POINTER(NNConvGradJob), i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

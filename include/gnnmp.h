@@ -32,7 +32,7 @@
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
  *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
- *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1248,6 +1248,48 @@ typedef struct {
     int act;
 } gnnmp_cg_conv_grad_t;
 int gnnmp_cg_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_cg_conv_grad_t *job, int64_t C,
+                           gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The pullback of NNConv's per-edge-matrix message — nn_conv, GNNlib/src/layers/conv.jl:260-273:
+ *   m = propagate(message, g, aggr; xj = x, e),  message(xj, e) = W_k x_j,  W_k = reshape(nn(e)_k, Dout, Din)
+ * The forward is gnnmp_propagate_nn_f32 on we = nn(e) [E][Dout * Din], element (o, c) of edge k at we[k][o + Dout * c].  Given the
+ * cotangent Δ = dm [N][Dout] of the aggregate, AT THE DESTINATION, for edge k: j -> i at original position k:
+ *   dwe[k][o + Dout*c] = dm[i][o] * x[j][c]                                   (the gradient arriving at nn(e): E * Dout * Din values)
+ *   dx[j][c]           = Σ_{k out of j} Σ_o we[k][o + Dout*c] * dm[i][o]
+ * The export knows no aggregator: `+` passes Δ through; for `mean` the caller pre-scales Δ's rows by 1 / max(indeg, 1) (as the
+ * adjoint of gnnmp_propagate_f32 under mean does).  The caller chains dwe through nn's dense adjoints on E rows.
+ *
+ *   plan_t   the plan of the REVERSED edge index (row j: the edges that leave j, in original edge order; col = the destination,
+ *            eid = the original position).  Square, built WITHOUT plan-added self loops (we has no row for them).  Only READ.
+ *   job      a HOST record of device pointers, gnnmp_nn_conv_grad_t:
+ *              x [N][Din], dm [N][Dout]: read.  we [E][Dout * Din]: read only when dx is wanted; may be NULL when dx is NULL
+ *              dx  [N][Din] or NULL (not wanted): every element written (rows without out-edges: zeros)
+ *              dwe [E][Dout * Din] or NULL (not wanted): every element written, at the edge's ORIGINAL position
+ *            Whichever of dx and dwe is wanted has the same bits whether or not the other is.  Outputs must not overlap the inputs or
+ *            each other.
+ *   Din, Dout  1 .. 65536, the forward's bounds.  Any 4-byte aligned pointers: the kernel uses 16- / 8-byte lanes when
+ *            Dout % 4 / Dout % 2 == 0 and we (when read), dwe (when written) and dm are aligned alike, 4-byte lanes otherwise.
+ * One launch over plan_t (csrc/nn_grad.hip): a lane group owns source j, holds x_j, and for every edge that leaves j gathers dm[i],
+ * reads W_k once, stores dW_k once and accumulates dx[j] in registers — we is read once, dwe written once, nothing else of E rows
+ * moves.  No scratch, no atomics, no host wait, no allocation, nothing owned by the plan written; it may be recorded into a HIP graph
+ * without an eager call first.  N = 0 launches nothing; E = 0 with N > 0 writes zeros to dx and touches no row of dwe.  Every row is
+ * walked WHOLE by one lane group, whatever its length (the plan's chunks are ignored): two calls give equal bits — slow for hub rows.
+ * Summation order of dx[j][c]: products are rounded, then added.  A lane group has G lanes (a power of two, <= 64) of VEC = 4 | 2 | 1
+ * floats; lane l owns the outputs o = (t G + l) VEC + q, q < VEC, t = 0, 1, ...  Each lane folds its own products sequentially from
+ * 0 — the edges of the row in order, in batches of U (2 for VEC = 4, else 4); within a batch t ascending, then the batch's edges, then
+ * q — and the G lane partials are summed by a butterfly (p[l] + p[l ^ m] for m = G/2, G/4, ..., 1).
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL plan_t / job / x / dm, dx and dwe both NULL, dx given without we, Din or Dout
+ * outside 1 .. 65536, a plan with n_src != n_dst, a plan built with self loops (n_total != n_edges).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *x;    /* [N][Din] */
+    const float *we;   /* [n_edges][Dout*Din], element (o, c) of edge k at we[k][o + Dout*c]; may be NULL when dx is NULL */
+    const float *dm;   /* [N][Dout], the cotangent of the aggregate, at the DESTINATION */
+    float *dx;         /* [N][Din] or NULL */
+    float *dwe;        /* [n_edges][Dout*Din] or NULL */
+} gnnmp_nn_conv_grad_t;
+int gnnmp_nn_conv_grad_f32(const gnnmp_graph_t *plan_t, const gnnmp_nn_conv_grad_t *job, int64_t Din, int64_t Dout,
                            gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
