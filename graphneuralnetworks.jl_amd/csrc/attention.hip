@@ -276,14 +276,7 @@ __global__ void __launch_bounds__(256) bias_act_kernel(const float *x, const flo
     if (i >= total) return;
     float v = x[i];
     if (bias) v = v + bias[i % D];
-    if (act == GNNMP_ACT_RELU) v = v < 0.0f ? 0.0f : v;
-    if (act == GNNMP_ACT_SOFTPLUS) v = log1pf(expf(-fabsf(v))) + (v < 0.0f ? 0.0f : v);   // NNlib.softplus
-    if (act == GNNMP_ACT_TANH) v = tanhf(v);
-    if (act == GNNMP_ACT_SWISH) {                       // NNlib.swish = x * sigmoid(x)
-        const float t = expf(-fabsf(v));
-        v = v * (v >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t));
-    }
-    out[i] = v;
+    out[i] = bias_act_apply(v, act);
 }
 
 }  // namespace gnnmp

@@ -169,6 +169,19 @@ __device__ __forceinline__ float op_apply(float a, float b) {
     return jl_min(a, b);
 }
 
+// The activation of gnnmp_bias_act_f32 (libm forms; SWISH = NNlib.swish = x * sigmoid(x)) — ONE device function for bias_act_kernel
+// (attention.hip) and the edge kernel of EGNNConv (egnn.hip): act(z0) recomputed by the former has the bits the latter stored.
+__device__ __forceinline__ float bias_act_apply(float v, int act) {
+    if (act == GNNMP_ACT_RELU) v = v < 0.0f ? 0.0f : v;
+    if (act == GNNMP_ACT_SOFTPLUS) v = log1pf(expf(-fabsf(v))) + (v < 0.0f ? 0.0f : v);   // NNlib.softplus
+    if (act == GNNMP_ACT_TANH) v = tanhf(v);
+    if (act == GNNMP_ACT_SWISH) {
+        const float t = expf(-fabsf(v));
+        v = v * (v >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t));
+    }
+    return v;
+}
+
 // vector-of-VEC-floats load/store (16/8/4-byte global accesses)
 template <int VEC>
 struct Vec;

@@ -56,6 +56,7 @@ SYMBOLS = (
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32",
     "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
+    "gnnmp_egnn_edge_f32", "gnnmp_egnn_coord_f32", "gnnmp_egnn_coord_grad_f32", "gnnmp_act_grad_z_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -137,6 +138,29 @@ class NNConvGradJob(ctypes.Structure):
     """gnnmp_nn_conv_grad_t: one gnnmp_nn_conv_grad_f32 call (x, we | None, dm read; dx | None, dwe | None written)"""
     _fields_ = [("x", ctypes.c_void_p), ("we", ctypes.c_void_p), ("dm", ctypes.c_void_p), ("dx", ctypes.c_void_p),
                 ("dwe", ctypes.c_void_p)]
+
+
+class EgnnEdgeJob(ctypes.Structure):
+    """gnnmp_egnn_edge_t: one gnnmp_egnn_edge_f32 call (s, t, x, P, Q, F | None, c read; q, a0, z0 | None written)"""
+    _fields_ = [("s", ctypes.c_void_p), ("t", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("index_base", ctypes.c_int),
+                ("x", ctypes.c_void_p), ("P", ctypes.c_void_p), ("Q", ctypes.c_void_p), ("F", ctypes.c_void_p), ("c", ctypes.c_void_p),
+                ("q", ctypes.c_void_p), ("a0", ctypes.c_void_p), ("z0", ctypes.c_void_p), ("act", ctypes.c_int)]
+
+
+class EgnnCoordJob(ctypes.Structure):
+    """gnnmp_egnn_coord_t: one gnnmp_egnn_coord_f32 call (x, mx read; xo = x' written)"""
+    _fields_ = [("x", ctypes.c_void_p), ("mx", ctypes.c_void_p), ("xo", ctypes.c_void_p)]
+
+
+class EgnnCoordGradJob(ctypes.Structure):
+    """gnnmp_egnn_coord_grad_t: one gnnmp_egnn_coord_grad_f32 call (x, dxo, mx | None, dq | None read; dmx | None, dx | None written)"""
+    _fields_ = [("x", ctypes.c_void_p), ("dxo", ctypes.c_void_p), ("mx", ctypes.c_void_p), ("dq", ctypes.c_void_p),
+                ("dmx", ctypes.c_void_p), ("dx", ctypes.c_void_p)]
+
+
+class ActGradZJob(ctypes.Structure):
+    """gnnmp_act_grad_z_t: one gnnmp_act_grad_z_f32 call (dy, z | None read; dz written)"""
+    _fields_ = [("dy", ctypes.c_void_p), ("z", ctypes.c_void_p), ("dz", ctypes.c_void_p), ("act", ctypes.c_int)]
 
 
 class GnnmpError(RuntimeError):
@@ -282,6 +306,10 @@ def load():
         "gnnmp_edge_conv_grad_f32": [vp, vp, ctypes.POINTER(EdgeConvGradJob), i64, vp],
         "gnnmp_cg_conv_grad_f32": [vp, vp, ctypes.POINTER(CGConvGradJob), i64, vp],
         "gnnmp_nn_conv_grad_f32": [vp, ctypes.POINTER(NNConvGradJob), i64, i64, vp],
+        "gnnmp_egnn_edge_f32": [ctypes.POINTER(EgnnEdgeJob), i64, i64, i64, vp],
+        "gnnmp_egnn_coord_f32": [vp, ctypes.POINTER(EgnnCoordJob), i64, vp],
+        "gnnmp_egnn_coord_grad_f32": [vp, vp, ctypes.POINTER(EgnnCoordGradJob), i64, vp],
+        "gnnmp_act_grad_z_f32": [ctypes.POINTER(ActGradZJob), i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

@@ -32,7 +32,8 @@
  *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
  *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
- *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py) and gnnmp_egnn_edge_f32 /
+ *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -89,7 +90,8 @@ typedef enum { GNNMP_COPY_XJ = 0, GNNMP_W_MUL_XJ = 1 } gnnmp_msg;
 
 /* activation fused into gnnmp_dense_f32's epilogue (the layers' `σ`): IDENTITY and RELU everywhere an `act` is taken;
  * SOFTPLUS (NNlib.softplus = log1p(exp(-|x|)) + relu(x)) and TANH also as the second factor of gnnmp_propagate_cg_f32 and
- * in gnnmp_bias_act_f32; SWISH (x * sigmoid(x), egnn_conv's Dense layers) in gnnmp_bias_act_f32 only. */
+ * in gnnmp_bias_act_f32; SWISH (x * sigmoid(x), egnn_conv's Dense layers) in gnnmp_bias_act_f32, gnnmp_egnn_edge_f32 and
+ * gnnmp_act_grad_z_f32 only. */
 typedef enum {
     GNNMP_ACT_IDENTITY = 0, GNNMP_ACT_RELU = 1, GNNMP_ACT_SOFTPLUS = 2, GNNMP_ACT_TANH = 3, GNNMP_ACT_SWISH = 4
 } gnnmp_act;
@@ -1291,6 +1293,89 @@ typedef struct {
 } gnnmp_nn_conv_grad_t;
 int gnnmp_nn_conv_grad_f32(const gnnmp_graph_t *plan_t, const gnnmp_nn_conv_grad_t *job, int64_t Din, int64_t Dout,
                            gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * EGNNConv's edge and coordinate steps, forward and pullback — egnn_conv, GNNlib/src/layers/conv.jl:459-495 (csrc/egnn.hip):
+ *   x_diff = xi_sub_xj, sqnorm = sum(x_diff .^ 2), x_diff ./ (sqrt(sqnorm) + 1f-6), ϕe(vcat(hi, hj, sqnorm, e)), ϕx scaling the normalised
+ *   differences, + for h and mean for x.
+ * Edge k: j -> i.  W0 = [A | B | c | D] is ϕe's first weight, split at columns nin, 2 nin, 2 nin + 1.  The caller's dense calls give
+ *   P = h A' + b0 [N][hid],  Q = h B' [N][hid],  F = e D' [E][hid] (only with edge features), and
+ *   d_k = x_i − x_j    q_k = Σ_a d_k[a]² (a ascending, from 0; products rounded, then added)    r_k = sqrt(q_k)    n_k = d_k / (r_k + 1e-6)
+ *
+ *   gnnmp_egnn_edge_f32   K1, in ORIGINAL edge order from s, t: q [E], z0_k = ((P_i + Q_j) + q_k c) (+ F_k), a0 = act(z0) [E][hid]; z0 is
+ *                         stored only when the pointer is non-NULL (a gradient is wanted).  act: any gnnmp_act, evaluated by the device
+ *                         function of gnnmp_bias_act_f32: a0 has the bits of gnnmp_bias_act_f32(z0, NULL, act).  Indices are not validated.
+ *   gnnmp_egnn_coord_f32  K2, one pass over the plan: x'_i = x_i + (1 / deg_i) Σ_{k into i} mx_k n_k, deg_i = the in-degree; a row without
+ *                         in-edges gets x'_i = x_i.  n_k is recomputed from x; nothing of E rows but mx [E] is read, only x' written.
+ *   gnnmp_egnn_coord_grad_f32   K3, given Δx' = dxo [N][Dx]:
+ *                           dmx_k = (Σ_a n_k[a] Δx'_i[a]) / deg_i                                            (dmx non-NULL)
+ *                           g_k = (mx_k / deg_i) Δx'_i,  den = r_k + 1e-6
+ *                           dd_k = (g_k / den − d_k ((d_k · g_k) / (r_k den²))) + (2 dq_k) d_k
+ *                           dx_i = (Δx'_i + Σ_{k into i} dd_k) − Σ_{k out of i} dd_k                           (dx non-NULL)
+ *                         where dq [E] is the cotangent that reaches q through z0 (dz0 c).  WHERE q_k == 0 (a self loop, coincident points)
+ *                         THE n-PATH TERMS ARE DEFINED AS 0: dd_k = 2 dq_k d_k = 0 and dmx_k = 0.  The reference's AD gives Inf * 0 = NaN
+ *                         there (the derivative of sqrt at 0); this is a convention, not a derivative.  One launch: the lane group of node i
+ *                         walks row i of plan (the edges into i) and, for dx, row i of plan_t (the edges out of i; it gathers x, Δx', the
+ *                         in-degree of the destination from plan, mx[eid] and dq[eid]).  Either output has the same bits whether or not
+ *                         the other is asked for.
+ *   gnnmp_act_grad_z_f32  dz = dy ⊙ act'(z) from the PRE-activation z, n elements, any gnnmp_act: identity 1 | relu z > 0 (0 at 0) |
+ *                         softplus sigmoid(z) | tanh (1 − a)(1 + a), a = tanh(z) | swish σ(z) (1 + z (1 − σ(z))).  (gnnmp_act_grad_f32
+ *                         works from the OUTPUT y and covers identity and relu only.)
+ *
+ * Device pointers travel in const HOST records.  All four only launch on `stream`: no atomics, no scratch, no host wait, no allocation,
+ * nothing owned by a plan written; each may be recorded into a HIP graph without an eager call first; two calls give equal bits.  Outputs must
+ * not overlap the inputs or each other.  Any 4-byte aligned pointers: K1 uses 16- / 8-byte lanes when hid % 4 / hid % 2 == 0 and P, Q, F,
+ * c, a0 and z0 are aligned alike (a second feature tile beyond 256 features), gnnmp_act_grad_z_f32 16-byte lanes when dy, z and dz are
+ * 16-byte aligned; K2 and K3 keep a node's Dx <= 16 coordinates in registers and use 4-byte accesses.
+ * K2 / K3 rows are walked WHOLE by one lane group, whatever their length (the plan's chunks are ignored) — slow for hub rows.  Summation
+ * order of a row: the group has G lanes, G = the smallest power of two >= the plan's mean row length (at most 64); lane l folds the
+ * row's slots l, l + G, l + 2G, ... sequentially from 0, slots in plan order (= original edge order), and the G lane partials are summed
+ * by a butterfly (p[l] + p[l ^ m] for m = G/2, G/4, ..., 1).
+ * N = 0 launches nothing; E = 0 with N > 0 writes x' = x and dx = Δx' and touches no edge array.
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL job or required pointer (K1: s, t, x, P, Q, c, q, a0; K2: plan, x, mx, xo; K3: plan, x,
+ * dxo, dmx and dx both NULL, dx without plan_t / mx / dq; mx and dq may be NULL on a plan without edges; act_grad_z: dy, dz, z unless act is IDENTITY), idx_bytes not 4 | 8, hid
+ * outside 1 .. 2^19, Dx outside 1 .. 16, an act outside IDENTITY .. SWISH, negative E or n, a plan with n_src != n_dst, a plan_t whose
+ * height or edge count differs from the plan's, a plan built with self loops of its own (n_total != n_edges: mx has no entry for them).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void *s, *t;         /* [E] the edge index as the graph holds it: edge k goes s[k] -> t[k] */
+    int idx_bytes, index_base; /* 8 | 4, 1 | 0 */
+    const float *x;            /* [N][Dx] */
+    const float *P, *Q;        /* [N][hid] */
+    const float *F;            /* [E][hid] or NULL (no edge features) */
+    const float *c;            /* [hid] */
+    float *q;                  /* [E] */
+    float *a0;                 /* [E][hid] */
+    float *z0;                 /* [E][hid] or NULL (not wanted) */
+    int act;
+} gnnmp_egnn_edge_t;
+int gnnmp_egnn_edge_f32(const gnnmp_egnn_edge_t *job, int64_t E, int64_t hid, int64_t Dx, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *x;    /* [N][Dx] */
+    const float *mx;   /* [E] */
+    float *xo;         /* [N][Dx] = x' */
+} gnnmp_egnn_coord_t;
+int gnnmp_egnn_coord_f32(const gnnmp_graph_t *plan, const gnnmp_egnn_coord_t *job, int64_t Dx, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *x;    /* [N][Dx] */
+    const float *dxo;  /* [N][Dx] = Δx' */
+    const float *mx;   /* [E]; may be NULL when dx is NULL */
+    const float *dq;   /* [E]; may be NULL when dx is NULL */
+    float *dmx;        /* [E] or NULL (not wanted) */
+    float *dx;         /* [N][Dx] or NULL (not wanted) */
+} gnnmp_egnn_coord_grad_t;
+int gnnmp_egnn_coord_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_egnn_coord_grad_t *job, int64_t Dx,
+                              gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dy;   /* [n] */
+    const float *z;    /* [n] the pre-activation; may be NULL for IDENTITY */
+    float *dz;         /* [n] */
+    int act;
+} gnnmp_act_grad_z_t;
+int gnnmp_act_grad_z_f32(const gnnmp_act_grad_z_t *job, int64_t n, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
