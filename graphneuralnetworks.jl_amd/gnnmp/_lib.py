@@ -57,6 +57,7 @@ SYMBOLS = (
     "gnnmp_random_walk_pe_f32",
     "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
     "gnnmp_egnn_edge_f32", "gnnmp_egnn_coord_f32", "gnnmp_egnn_coord_grad_f32", "gnnmp_act_grad_z_f32",
+    "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -161,6 +162,26 @@ class EgnnCoordGradJob(ctypes.Structure):
 class ActGradZJob(ctypes.Structure):
     """gnnmp_act_grad_z_t: one gnnmp_act_grad_z_f32 call (dy, z | None read; dz written)"""
     _fields_ = [("dy", ctypes.c_void_p), ("z", ctypes.c_void_p), ("dz", ctypes.c_void_p), ("act", ctypes.c_int)]
+
+
+GMM_PARTS, GMM_MAX_K = 256, 16      # include/gnnmp.h: GNNMP_GMM_PARTS; K = 1 .. 16
+
+
+class GmmConvJob(ctypes.Structure):
+    """gnnmp_gmm_conv_t: one gnnmp_gmm_conv_f32 call (w, xk, bias | None read; y, z | None written)"""
+    _fields_ = [("w", ctypes.c_void_p), ("xk", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("z", ctypes.c_void_p),
+                ("act", ctypes.c_int)]
+
+
+class GmmConvGradJob(ctypes.Structure):
+    """gnnmp_gmm_conv_grad_t: one gnnmp_gmm_conv_grad_f32 call (w | None, xk | None, dz read; dxk | None, dw | None written)"""
+    _fields_ = [("w", ctypes.c_void_p), ("xk", ctypes.c_void_p), ("dz", ctypes.c_void_p), ("dxk", ctypes.c_void_p), ("dw", ctypes.c_void_p)]
+
+
+class GmmWeightsGradJob(ctypes.Structure):
+    """gnnmp_gmm_weights_grad_t: one gnnmp_gmm_weights_grad_f32 call (e, mu, sinv, w, dw read; de | None, dmu, dsinv | None, part written)"""
+    _fields_ = [("e", ctypes.c_void_p), ("mu", ctypes.c_void_p), ("sinv", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dw", ctypes.c_void_p),
+                ("de", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("dsinv", ctypes.c_void_p), ("part", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -310,6 +331,9 @@ def load():
         "gnnmp_egnn_coord_f32": [vp, ctypes.POINTER(EgnnCoordJob), i64, vp],
         "gnnmp_egnn_coord_grad_f32": [vp, vp, ctypes.POINTER(EgnnCoordGradJob), i64, vp],
         "gnnmp_act_grad_z_f32": [ctypes.POINTER(ActGradZJob), i64, vp],
+        "gnnmp_gmm_conv_f32": [vp, ctypes.POINTER(GmmConvJob), i64, i64, vp],
+        "gnnmp_gmm_conv_grad_f32": [vp, vp, ctypes.POINTER(GmmConvGradJob), i64, i64, vp],
+        "gnnmp_gmm_weights_grad_f32": [ctypes.POINTER(GmmWeightsGradJob), i64, i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

@@ -33,7 +33,8 @@
  *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
  *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
  *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py) and gnnmp_egnn_edge_f32 /
- *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
+ *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1376,6 +1377,99 @@ typedef struct {
     int act;
 } gnnmp_act_grad_z_t;
 int gnnmp_act_grad_z_f32(const gnnmp_act_grad_z_t *job, int64_t n, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GMMConv (MoNet) on fused mixture-weight kernels, forward and pullback — gmm_conv, GNNlib/src/layers/conv.jl:372-401 (csrc/gmm.hip):
+ *   w = exp(sum over d of ((e − mu)² / 2) .* sigma_inv²)  (1, K, E),  propagate(e_mul_xj, g, mean; xj = dense_x(x) as (out, K, N), e = w),
+ *   mean over the K kernels, σ.(m .+ bias), optional residual.
+ * Edge e: j -> i, kernel k < K, channel c < C.  The caller provides w [E][K] (gnnmp_gmm_weights_f32 with C = 1: one number per edge and
+ * kernel) and xk = x dense_x_weight' [N][K C], kernel k's block at k C (gnnmp_dense_f32).  Neither [E][K C] nor [N][K C] is written.
+ *
+ *   gnnmp_gmm_conv_f32         acc_ikc = Σ_{e into i, edge order, from 0} w[e][k] * xk[j][k C + c]     A MULTIPLY AND AN ADD per edge: the
+ *                                                                                                     product is rounded, then added
+ *                              m_ikc = acc_ikc / deg_i (deg_i = the in-degree; a row without in-edges keeps 0)
+ *                              z_ic = (((m_i0c + m_i1c) + ...) + m_i,K−1,c) / K (+ bias_c)            y = act(z), any gnnmp_act, by the device
+ *                              function of gnnmp_bias_act_f32.  z is stored only when the pointer is non-NULL (a gradient is wanted).
+ *                              One lane group finishes one destination row: its lanes run over the channels, each holds K accumulators per
+ *                              channel in registers; the K weights of an edge are read once per edge, at the edge's original position.
+ *   gnnmp_gmm_conv_grad_f32    given dz [N][C] = Δ ⊙ act'(z) (gnnmp_act_grad_z_f32), with q_i = 1 / (K max(deg_i, 1)), t_ic = q_i * dz_ic:
+ *                              dxk[j][k C + c] = Σ_{e out of j, edge order, from 0} w[e][k] * t_ic    (products rounded, then added)
+ *                              dw[e][k]        = Σ_c xk[j][k C + c] * t_ic
+ *                              One walk of plan_t: the lane group of source j keeps xk[j] in registers and reads, per out-edge, dz_i, w_e
+ *                              and deg_i — the degree from `plan`; plan_t only orders the walk.  dxk[j] is accumulated in registers and
+ *                              written once (a row without out-edges: zeros); dw is written at the edge's original position.  Order of
+ *                              dw's sum: a lane group has G lanes (a power of two <= 64) of VEC = 4 | 2 | 1 channels; lane l owns channels
+ *                              (T G + l) VEC + q, q < VEC, of tile T.  Within a tile the lane adds its products from 0 in ascending q, the
+ *                              G lane sums go through a butterfly (p[l] + p[l ^ m], m = G/2, ..., 1); tiles (more than one only when
+ *                              C > 64 VEC) are added in ascending T.  G and VEC follow from C and the pointers' alignment only.  Whichever
+ *                              of dxk and dw is wanted has the same bits whether or not the other is.
+ *   gnnmp_gmm_weights_grad_f32 the pullback of gnnmp_gmm_weights_f32 (C = 1): with g_ek = dw[e][k] * w[e][k] and δ = e[e][d] − mu[k][d],
+ *                              de[e][d]    =  Σ_k (g_ek δ) * sinv[k][d]²          k ascending from 0; one thread an edge
+ *                              dmu[k][d]   = −Σ_e (g_ek δ) * sinv[k][d]²
+ *                              dsinv[k][d] =  Σ_e (g_ek δ²) * sinv[k][d]
+ *                              dmu / dsinv are a two-stage fold without atomics.  THE SLICE RULE: block b < GNNMP_GMM_PARTS folds the edges
+ *                              [b L, min(E, (b + 1) L)), L = ceil(E / GNNMP_GMM_PARTS), into part[b][0][k][d] (dmu) and part[b][1][k][d]
+ *                              (dsinv): lane l of a wave folds the slice's edges l, l + 64, ... sequentially from 0, the 64 lane sums go
+ *                              through a butterfly; then ONE block adds part[0], part[1], ... in index order from 0.  No value passes
+ *                              through more than ceil(L / 64) + 6 + GNNMP_GMM_PARTS additions — at most L + GNNMP_GMM_PARTS, the depth to
+ *                              put into a summation bound.  Every element of part is written (an empty slice: zeros).
+ *
+ *   plan     the graph's plan (rows = destinations); plan_t the plan of the reversed edge index (row j: the edges that leave j, in
+ *            original edge order).  Square (n_src == n_dst = N), built WITHOUT plan-added self loops (w has no row for them); plan_t of
+ *            the same height and edge count.  Both are only READ; the plans' chunks are ignored.
+ *   job      a const HOST record of device pointers:
+ *              gnnmp_gmm_conv_t          w [E][K], xk [N][K C]: read; bias [C] or NULL; y [N][C]: every element written; z [N][C] or NULL
+ *                                        (not wanted): every element written; act: gnnmp_act, IDENTITY .. SWISH
+ *              gnnmp_gmm_conv_grad_t     dz [N][C]: read; w [E][K]: read only when dxk is wanted; xk [N][K C]: read only when dw is wanted;
+ *                                        dxk [N][K C] or NULL, dw [E][K] or NULL: every element written
+ *              gnnmp_gmm_weights_grad_t  e [E][ein], mu, sinv [K][ein], w, dw [E][K]: read; de [E][ein] or NULL; dmu, dsinv [K][ein], both
+ *                                        or neither; part [GNNMP_GMM_PARTS][2][K][ein] floats, caller-owned, needed with dmu
+ *            Outputs must not overlap the inputs or each other.
+ *   K        1 .. 16.   C  1 .. 2^19 with K C <= 2^20.   ein  1 .. 64.   Any 4-byte aligned pointers: the row kernels use 16- / 8-byte
+ *            lanes when C % 4 / C % 2 == 0 and xk, bias, y, z (forward) or xk, dz, dxk (pullback) are aligned alike, 4-byte lanes otherwise.
+ * All three only launch on `stream`: no atomics, no allocation, no host wait, nothing owned by a plan written; each may be recorded into
+ * a HIP graph without an eager call first; two calls give equal bits.  N = 0 (the row exports) or E = 0 (gnnmp_gmm_weights_grad_f32)
+ * launches nothing and returns GNNMP_OK — the caller zero-fills dmu / dsinv of a graph without edges; E = 0 with N > 0 gives
+ * y = act(bias) and dxk = 0.  Every row is walked WHOLE by one lane group, whatever its length: slow for hub rows.
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL plan / plan_t / job; forward: a NULL xk / y, a NULL w on a plan with edges; pullback:
+ * dxk and dw both NULL, a NULL dz, dxk without w (on a plan with edges), dw without xk; weights: de, dmu and dsinv all NULL, only one of
+ * dmu / dsinv, dmu without part, negative E, and with E > 0 a NULL e / mu / sinv / w / dw; K outside 1 .. 16, C outside 1 .. 2^19 or
+ * K C > 2^20, ein outside 1 .. 64, an act outside IDENTITY .. SWISH, a plan with n_src != n_dst, a plan_t whose height or edge count
+ * differs from the plan's, a plan built with self loops of its own (n_total != n_edges).
+ * ---------------------------------------------------------------------------------------------- */
+#define GNNMP_GMM_PARTS 256 /* partial blocks of gnnmp_gmm_weights_grad_f32's dmu / dsinv fold */
+typedef struct {
+    const float *w;    /* [E][K] */
+    const float *xk;   /* [N][K*C] */
+    const float *bias; /* [C] or NULL */
+    float *y;          /* [N][C] */
+    float *z;          /* [N][C] or NULL (not wanted) */
+    int act;
+} gnnmp_gmm_conv_t;
+int gnnmp_gmm_conv_f32(const gnnmp_graph_t *plan, const gnnmp_gmm_conv_t *job, int64_t K, int64_t C, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *w;    /* [E][K]; may be NULL when dxk is NULL */
+    const float *xk;   /* [N][K*C]; may be NULL when dw is NULL */
+    const float *dz;   /* [N][C] */
+    float *dxk;        /* [N][K*C] or NULL (not wanted) */
+    float *dw;         /* [E][K] or NULL (not wanted) */
+} gnnmp_gmm_conv_grad_t;
+int gnnmp_gmm_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_gmm_conv_grad_t *job, int64_t K, int64_t C,
+                            gnnmp_stream_t stream);
+
+typedef struct {
+    const float *e;    /* [E][ein] */
+    const float *mu;   /* [K][ein] */
+    const float *sinv; /* [K][ein] */
+    const float *w;    /* [E][K] */
+    const float *dw;   /* [E][K] */
+    float *de;         /* [E][ein] or NULL (not wanted) */
+    float *dmu;        /* [K][ein] or NULL (not wanted; then dsinv is NULL too) */
+    float *dsinv;      /* [K][ein] or NULL */
+    float *part;       /* [GNNMP_GMM_PARTS][2][K][ein], needed with dmu / dsinv */
+} gnnmp_gmm_weights_grad_t;
+int gnnmp_gmm_weights_grad_f32(const gnnmp_gmm_weights_grad_t *job, int64_t E, int64_t ein, int64_t K, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
