@@ -75,6 +75,23 @@ __device__ __forceinline__ float nn_tanh(float x) {
     return x < 0.0f ? -r : r;
 }
 
+// dy ⊙ act'(z) from the pre-activation — ONE device function for gnnmp_act_grad_z_f32 (egnn.hip) and the edge-head pullback of
+// MEGNetConv (megnet.hip): the formulas of cg_grad.hip, all five gnnmp_act codes
+template <int ACT>
+__device__ __forceinline__ float act_dz(float dy, float z) {
+    if (ACT == GNNMP_ACT_RELU) return z > 0.0f ? dy : 0.0f;       // 0 at 0, as gnnmp_act_grad_f32
+    if (ACT == GNNMP_ACT_SOFTPLUS) return dy * nn_sigmoid(z);
+    if (ACT == GNNMP_ACT_TANH) {
+        const float t = nn_tanh(z);
+        return dy * ((1.0f - t) * (1.0f + t));
+    }
+    if (ACT == GNNMP_ACT_SWISH) {
+        const float sg = nn_sigmoid(z);
+        return dy * (sg * (1.0f + z * (1.0f - sg)));
+    }
+    return dy;
+}
+
 // dense_s's σ of CGConv (constructor argument `act`, GraphNeuralNetworks/src/layers/conv.jl:925-930)
 __device__ __forceinline__ float cg_act(float x, int act) {
     switch (act) {

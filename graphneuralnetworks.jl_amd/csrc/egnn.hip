@@ -225,22 +225,7 @@ __global__ void __launch_bounds__(256) egnn_coord_grad_kernel(const EgnnCoordGra
 }
 
 // ---- act'(z) ------------------------------------------------------------------------------------------------------------------------
-// nn_sigmoid / nn_tanh of csr_reduce.h (hardware transcendentals), the formulas of cg_grad.hip
-template <int ACT>
-__device__ __forceinline__ float act_dz(float dy, float z) {
-    if (ACT == GNNMP_ACT_RELU) return z > 0.0f ? dy : 0.0f;       // 0 at 0, as gnnmp_act_grad_f32
-    if (ACT == GNNMP_ACT_SOFTPLUS) return dy * nn_sigmoid(z);
-    if (ACT == GNNMP_ACT_TANH) {
-        const float t = nn_tanh(z);
-        return dy * ((1.0f - t) * (1.0f + t));
-    }
-    if (ACT == GNNMP_ACT_SWISH) {
-        const float sg = nn_sigmoid(z);
-        return dy * (sg * (1.0f + z * (1.0f - sg)));
-    }
-    return dy;
-}
-
+// act_dz of csr_reduce.h (hardware transcendentals, the formulas of cg_grad.hip), shared with megnet.hip
 // thread i takes elements [i VEC, i VEC + VEC); the last thread of a VEC > 1 launch finishes the tail element by element
 template <int VEC, int ACT>
 __global__ void __launch_bounds__(256) act_grad_z_kernel(const float *dy, const float *z, float *dz, int64_t n) {

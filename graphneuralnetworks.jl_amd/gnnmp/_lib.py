@@ -58,6 +58,7 @@ SYMBOLS = (
     "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
     "gnnmp_egnn_edge_f32", "gnnmp_egnn_coord_f32", "gnnmp_egnn_coord_grad_f32", "gnnmp_act_grad_z_f32",
     "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
+    "gnnmp_megnet_edge_f32", "gnnmp_megnet_edge_grad_f32", "gnnmp_aggregate_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -182,6 +183,23 @@ class GmmWeightsGradJob(ctypes.Structure):
     """gnnmp_gmm_weights_grad_t: one gnnmp_gmm_weights_grad_f32 call (e, mu, sinv, w, dw read; de | None, dmu, dsinv | None, part written)"""
     _fields_ = [("e", ctypes.c_void_p), ("mu", ctypes.c_void_p), ("sinv", ctypes.c_void_p), ("w", ctypes.c_void_p), ("dw", ctypes.c_void_p),
                 ("de", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("dsinv", ctypes.c_void_p), ("part", ctypes.c_void_p)]
+
+
+class MegnetEdgeJob(ctypes.Structure):
+    """gnnmp_megnet_edge_t: one gnnmp_megnet_edge_f32 call (P, Q, F | None read; a0, z0 | None written)"""
+    _fields_ = [("P", ctypes.c_void_p), ("Q", ctypes.c_void_p), ("F", ctypes.c_void_p), ("a0", ctypes.c_void_p), ("z0", ctypes.c_void_p),
+                ("act", ctypes.c_int)]
+
+
+class MegnetEdgeGradJob(ctypes.Structure):
+    """gnnmp_megnet_edge_grad_t: one gnnmp_megnet_edge_grad_f32 call (da0, z | None read; dz0 | None, dP and dQ | None written)"""
+    _fields_ = [("da0", ctypes.c_void_p), ("z", ctypes.c_void_p), ("dz0", ctypes.c_void_p), ("dP", ctypes.c_void_p), ("dQ", ctypes.c_void_p),
+                ("act", ctypes.c_int)]
+
+
+class AggregateGradJob(ctypes.Structure):
+    """gnnmp_aggregate_grad_t: one gnnmp_aggregate_grad_f32 call (dy, m | None, y | None, acc | None read; dm written)"""
+    _fields_ = [("dy", ctypes.c_void_p), ("m", ctypes.c_void_p), ("y", ctypes.c_void_p), ("acc", ctypes.c_void_p), ("dm", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -334,6 +352,9 @@ def load():
         "gnnmp_gmm_conv_f32": [vp, ctypes.POINTER(GmmConvJob), i64, i64, vp],
         "gnnmp_gmm_conv_grad_f32": [vp, vp, ctypes.POINTER(GmmConvGradJob), i64, i64, vp],
         "gnnmp_gmm_weights_grad_f32": [ctypes.POINTER(GmmWeightsGradJob), i64, i64, i64, vp],
+        "gnnmp_megnet_edge_f32": [vp, ctypes.POINTER(MegnetEdgeJob), i64, vp],
+        "gnnmp_megnet_edge_grad_f32": [vp, vp, ctypes.POINTER(MegnetEdgeGradJob), i64, vp],
+        "gnnmp_aggregate_grad_f32": [vp, ctypes.POINTER(AggregateGradJob), i, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

@@ -34,7 +34,8 @@
  *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
  *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py) and gnnmp_egnn_edge_f32 /
  *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
- *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py) and gnnmp_megnet_edge_f32 / gnnmp_megnet_edge_grad_f32 /
+ *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1470,6 +1471,85 @@ typedef struct {
     float *part;       /* [GNNMP_GMM_PARTS][2][K][ein], needed with dmu / dsinv */
 } gnnmp_gmm_weights_grad_t;
 int gnnmp_gmm_weights_grad_f32(const gnnmp_gmm_weights_grad_t *job, int64_t E, int64_t ein, int64_t K, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MEGNetConv on fused edge-update kernels, forward and pullback — megnet_conv, GNNlib/src/layers/conv.jl:356-368 (csrc/megnet.hip):
+ *   ē = ϕe(vcat(xi, xj, e)),  xᵉ = aggregate_neighbors(g, aggr, ē) (msgpass.jl:145-149),  x̄ = ϕv(vcat(x, xᵉ))  ->  (x̄, ē).
+ * Edge k: j -> i, feature c < hid.  ϕe's first weight W0 = [A | B | D] is split at columns in and 2 in; the caller provides
+ * P = x A' + b0, Q = x B' [N][hid] and F = e D' [E][hid] (gnnmp_dense_f32).  No [E][in] gather of x and no [E][2 in + ein] row exists.
+ *
+ *   gnnmp_megnet_edge_f32       z0_k = (P_i + Q_j) + F_k  (P_i + Q_j alone without F),  a0_k = act(z0_k) by the device function of
+ *                               gnnmp_bias_act_f32: a0 has the bits of gnnmp_bias_act_f32(z0, NULL, act).  One pass over the plan: the
+ *                               lane group of destination i keeps P_i in registers; both outputs are stored at the edge's original
+ *                               position.  z0 is stored only when the pointer is non-NULL (a gradient is wanted).
+ *   gnnmp_megnet_edge_grad_f32  dz0_k = da0_k ⊙ act'(z_k), the formulas of gnnmp_act_grad_z_f32 (its device function); IDENTITY: dz0 = da0
+ *                               and z is not read (it may be NULL).  For RELU a0 MAY BE PASSED AS z: the mask z > 0 is the mask a0 > 0.
+ *                               Pass 1, over plan:   dz0 stored at the edge's original position when wanted, and
+ *                                                    dP_i = Σ_{k into i, plan order, from 0} dz0_k
+ *                               Pass 2, over plan_t: dQ_j = Σ_{k out of j, plan order, from 0} dz0_k, dz0_k recomputed from da0 and z.
+ *                               Each of dz0, dP, dQ has the same bits whether or not the others are asked for; a row without in-edges
+ *                               (out-edges) gets dP_i = 0 (dQ_j = 0).
+ *   gnnmp_aggregate_grad_f32    NNlib's pullback of scatter(aggr, m, t), y = aggregate_neighbors(g, aggr, m), Δ = dy: the term of edge k
+ *                                   + :          Δ_i
+ *                                   mean :       Δ_i / deg_i, divided ONCE per row (deg_i = the row's length), then copied
+ *                                   max / min :  Δ_i where m_k == y_i, 0 elsewhere — EVERY tying copy gets the whole Δ (the reference's rule)
+ *                               dm_k = acc_k + term when acc is given (the cotangent that reaches m directly: summed here, not by a
+ *                               separate add), the term alone otherwise.  One pass over the plan with Δ_i (and y_i) in registers, dm stored
+ *                               at the edge's original position.
+ *
+ *   plan     the graph's plan (rows = destinations); plan_t the plan of the reversed edge index (row j: the edges that leave j).  The two
+ *            MEGNet exports want them square (n_src == n_dst = N) and of the same height and edge count; gnnmp_aggregate_grad_f32 walks
+ *            the n_dst rows of any plan.  All want a plan built WITHOUT plan-added self loops (the E-row arrays have no row for them).
+ *            Plans are only READ; their chunks are ignored.
+ *   job      a const HOST record of device pointers:
+ *              gnnmp_megnet_edge_t       P, Q [N][hid]: read; F [E][hid] or NULL; a0 [E][hid]: every element written; z0 [E][hid] or NULL
+ *                                        (not wanted): every element written; act: gnnmp_act, IDENTITY .. SWISH
+ *              gnnmp_megnet_edge_grad_t  da0, z [E][hid]: read (z: NULL allowed for IDENTITY); dz0 [E][hid] or NULL; dP, dQ [N][hid], both
+ *                                        or neither (then plan_t may be NULL): every element written; at least one output; act as above
+ *              gnnmp_aggregate_grad_t    dy [n_dst][D]: read; m [E][D], y [n_dst][D]: read for max / min only (NULL allowed otherwise);
+ *                                        acc [E][D] or NULL; dm [E][D]: every element written
+ *            Outputs must not overlap the inputs or each other.
+ *   hid, D   1 .. 2^19.  Any 4-byte aligned pointers: 16- / 8-byte lanes when hid % 4 / hid % 2 == 0 and every pointer of the call is
+ *            aligned alike, 4-byte lanes otherwise; lanes run over the features (a second feature tile beyond 64 lanes), a row's slots
+ *            are folded sequentially in plan order.
+ * All three only launch on `stream`: no atomics, no allocation, no host wait, nothing owned by a plan written; each may be recorded into
+ * a HIP graph without an eager call first; two calls give equal bits.  N = 0 launches nothing and returns GNNMP_OK; E = 0 with N > 0
+ * writes zeros to dP / dQ and touches no E-row array (their pointers may then be NULL).  Every row is walked WHOLE by one lane group,
+ * whatever its length: slow for hub rows.
+ * Refused before any HIP call (GNNMP_EINVAL): a NULL plan / job; a NULL P / Q; on a plan with edges a NULL a0, da0, z (act not IDENTITY),
+ * dy, dm, and m / y under max / min; dz0, dP and dQ all NULL, only one of dP / dQ, dQ without plan_t; hid / D outside 1 .. 2^19; an act
+ * outside IDENTITY .. SWISH, an aggr outside GNNMP_SUM .. GNNMP_MIN; a plan with n_src != n_dst (the two MEGNet exports), a plan_t whose
+ * height or edge count differs from the plan's, a plan built with self loops of its own (n_total != n_edges).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *P;    /* [N][hid] */
+    const float *Q;    /* [N][hid] */
+    const float *F;    /* [E][hid] or NULL */
+    float *a0;         /* [E][hid] */
+    float *z0;         /* [E][hid] or NULL (not wanted) */
+    int act;
+} gnnmp_megnet_edge_t;
+int gnnmp_megnet_edge_f32(const gnnmp_graph_t *plan, const gnnmp_megnet_edge_t *job, int64_t hid, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *da0;  /* [E][hid] */
+    const float *z;    /* [E][hid]; NULL allowed for IDENTITY; a0 allowed for RELU */
+    float *dz0;        /* [E][hid] or NULL (not wanted) */
+    float *dP;         /* [N][hid] or NULL (not wanted; then dQ is NULL too) */
+    float *dQ;         /* [N][hid] or NULL */
+    int act;
+} gnnmp_megnet_edge_grad_t;
+int gnnmp_megnet_edge_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, const gnnmp_megnet_edge_grad_t *job, int64_t hid,
+                               gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dy;   /* [n_dst][D] */
+    const float *m;    /* [E][D]; max / min only */
+    const float *y;    /* [n_dst][D]; max / min only */
+    const float *acc;  /* [E][D] or NULL */
+    float *dm;         /* [E][D] */
+} gnnmp_aggregate_grad_t;
+int gnnmp_aggregate_grad_f32(const gnnmp_graph_t *plan, const gnnmp_aggregate_grad_t *job, int aggr, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
