@@ -59,6 +59,7 @@ SYMBOLS = (
     "gnnmp_egnn_edge_f32", "gnnmp_egnn_coord_f32", "gnnmp_egnn_coord_grad_f32", "gnnmp_act_grad_z_f32",
     "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
     "gnnmp_megnet_edge_f32", "gnnmp_megnet_edge_grad_f32", "gnnmp_aggregate_grad_f32",
+    "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -200,6 +201,29 @@ class MegnetEdgeGradJob(ctypes.Structure):
 class AggregateGradJob(ctypes.Structure):
     """gnnmp_aggregate_grad_t: one gnnmp_aggregate_grad_f32 call (dy, m | None, y | None, acc | None read; dm written)"""
     _fields_ = [("dy", ctypes.c_void_p), ("m", ctypes.c_void_p), ("y", ctypes.c_void_p), ("acc", ctypes.c_void_p), ("dm", ctypes.c_void_p)]
+
+
+READOUT_MAX_D = 4096    # GNNMP_READOUT_MAX_D
+
+
+class SegmentAttnJob(ctypes.Structure):
+    """gnnmp_segment_attn_t: one gnnmp_segment_attn_pool_f32 call (x, seg_ptr, q | gate read; r, stats written)"""
+    _fields_ = [("x", ctypes.c_void_p), ("seg_ptr", ctypes.c_void_p), ("q", ctypes.c_void_p), ("gate", ctypes.c_void_p),
+                ("r", ctypes.c_void_p), ("stats", ctypes.c_void_p)]
+
+
+class SegmentAttnGradJob(ctypes.Structure):
+    """gnnmp_segment_attn_grad_t: one gnnmp_segment_attn_pool_grad_f32 call (dr, x, seg_ptr, q | gate, r, stats, base | None read;
+    dq | None, dx | None, dgate | None written)"""
+    _fields_ = [("dr", ctypes.c_void_p), ("x", ctypes.c_void_p), ("seg_ptr", ctypes.c_void_p), ("q", ctypes.c_void_p),
+                ("gate", ctypes.c_void_p), ("r", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("base", ctypes.c_void_p),
+                ("dq", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dgate", ctypes.c_void_p)]
+
+
+class LstmGradJob(ctypes.Structure):
+    """gnnmp_lstm_grad_t: one gnnmp_lstm_pointwise_grad_f32 call (gx, gh, b | None, c, dh, dcn | None read; da, dc written)"""
+    _fields_ = [("gx", ctypes.c_void_p), ("gh", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p), ("dh", ctypes.c_void_p),
+                ("dcn", ctypes.c_void_p), ("da", ctypes.c_void_p), ("dc", ctypes.c_void_p)]
 
 
 class GnnmpError(RuntimeError):
@@ -355,6 +379,9 @@ def load():
         "gnnmp_megnet_edge_f32": [vp, ctypes.POINTER(MegnetEdgeJob), i64, vp],
         "gnnmp_megnet_edge_grad_f32": [vp, vp, ctypes.POINTER(MegnetEdgeGradJob), i64, vp],
         "gnnmp_aggregate_grad_f32": [vp, ctypes.POINTER(AggregateGradJob), i, i64, vp],
+        "gnnmp_segment_attn_pool_f32": [ctypes.POINTER(SegmentAttnJob), i64, i64, i64, i64, vp],
+        "gnnmp_segment_attn_pool_grad_f32": [ctypes.POINTER(SegmentAttnGradJob), i64, i64, i64, i64, vp],
+        "gnnmp_lstm_pointwise_grad_f32": [ctypes.POINTER(LstmGradJob), i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

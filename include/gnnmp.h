@@ -35,7 +35,8 @@
  *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py) and gnnmp_egnn_edge_f32 /
  *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
  *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py) and gnnmp_megnet_edge_f32 / gnnmp_megnet_edge_grad_f32 /
- *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py) and gnnmp_segment_attn_pool_f32 / gnnmp_segment_attn_pool_grad_f32 /
+ *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1550,6 +1551,99 @@ typedef struct {
     float *dm;         /* [E][D] */
 } gnnmp_aggregate_grad_t;
 int gnnmp_aggregate_grad_f32(const gnnmp_graph_t *plan, const gnnmp_aggregate_grad_t *job, int aggr, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attention readouts on fused segment kernels, forward and pullback — GlobalAttentionPool, GNNlib/src/layers/pool.jl:7-12, and Set2Set,
+ * pool.jl:29-43 (csrc/readout.hip).  Both are a per-graph softmax-weighted sum over the graph's CONTIGUOUS rows [seg_ptr[g], seg_ptr[g+1])
+ * (what gnnmp_segment_bounds writes): no [N] array of logits or weights and no [N][D] product is written.  Graph g, row n, feature d.
+ *
+ *   gnnmp_segment_attn_pool_f32   the logits s_n:
+ *                                   QUERY (Dg = 0, q given; pool.jl:37-39)  s_n = Σ_d q_g[d] x_n[d]: each lane sums its own features in
+ *                                                                           ascending d from 0, the lanes' partials are folded by an xor
+ *                                                                           butterfly (a fixed order that depends on D and the alignment)
+ *                                   GATE (gate given; pool.jl:8-10)         s_n = gate_n (Dg = 1, one weight for every feature) or
+ *                                                                           s_n[d] = gate_n[d] (Dg = D, a softmax per channel)
+ *                                 then THREE sweeps over the segment, each in node order (not an online rescaling):
+ *                                   m_g   = max_n s_n                       (from -Inf)
+ *                                   den_g = Σ_n expf(s_n - m_g)             (from 0)
+ *                                   r_g   = Σ_n α_n x_n                     (from 0),  α_n = expf(s_n - m_g) / den_g
+ *                                 stats[g][j] = (m_g, den_g), j < max(Dg, 1): one pair per graph, or per channel for Dg = D.  An EMPTY
+ *                                 segment gives r_g = 0 (NNlib.scatter's zero) and stats (0, 0).
+ *   gnnmp_segment_attn_pool_grad_f32   ONE sweep in node order, α_n recomputed from stats by the expression above (the same bits):
+ *                                   c_g = Σ_d dr_g[d] r_g[d],  t_n = Σ_d dr_g[d] x_n[d]    (summed like the QUERY logit)
+ *                                   QUERY   ds_n = α_n (t_n - c_g),  dq_g = Σ_n ds_n x_n (node order, from 0),
+ *                                           dx_n = (base_n + α_n dr_g) + ds_n q_g
+ *                                   Dg = 1  dgate_n = α_n (t_n - c_g),  dx_n = base_n + α_n dr_g
+ *                                   Dg = D  dgate_n[d] = (α_n[d] dr_g[d]) (x_n[d] - r_g[d]),  dx_n[d] = base_n[d] + α_n[d] dr_g[d]
+ *                                 without base its addition is left out.  base MAY BE dx ITSELF (each element is read, then written, by one
+ *                                 lane): T Set2Set iterations accumulate into one dx with no separate add.  dq, dx, dgate are each optional:
+ *                                 a NULL output is not computed and the others keep their bits.  An empty segment gives dq_g = 0.
+ *   gnnmp_lstm_pointwise_grad_f32      pullback of gnnmp_lstm_pointwise_f32: a = gx + gh + b recomputed by its expressions,
+ *                                   i, f, o = σ(a_i, a_f, a_o), g̃ = tanhf(a_c), T = tanhf(f c + i g̃);   dc'_tot = dc' + dh' o (1 - T²)
+ *                                   (dc' = 0 when dcn is NULL: the last step)
+ *                                   da_i = dc'_tot g̃ (i (1 - i)),  da_f = dc'_tot c (f (1 - f)),  da_c = dc'_tot i (1 - g̃²),
+ *                                   da_o = dh' T (o (1 - o)),  dc = dc'_tot f.     da [N][4D] (gate order i, f, c, o) is the cotangent of gx
+ *                                   AND of gh; colsum(da) that of b.
+ *
+ *   job      a const HOST record of device pointers:
+ *              gnnmp_segment_attn_t       x [N][D], seg_ptr int64 [G+1] (0-based row offsets, ascending; clamped into [0, N] by the kernel):
+ *                                         read; EXACTLY ONE of q [G][D] and gate [N][Dg]; r [G][D], stats [G][max(Dg,1)][2]: every element
+ *                                         written
+ *              gnnmp_segment_attn_grad_t  dr [G][D], x, seg_ptr, q or gate, r, stats (the forward's): read; base [N][D] or NULL (needs dx);
+ *                                         dq [G][D] (QUERY only), dx [N][D], dgate [N][Dg] (GATE only), each or NULL, at least one of the
+ *                                         mode's two: every element written
+ *              gnnmp_lstm_grad_t          gx, gh [N][4D], b [4D] or NULL, c [N][D] (the cell state that ENTERED the step), dh [N][D]: read;
+ *                                         dcn [N][D] or NULL; da [N][4D], dc [N][D]: every element written
+ *            Outputs must not overlap the inputs or each other, base == dx excepted.
+ *   D        1 .. GNNMP_READOUT_MAX_D (the LSTM pullback: 1 .. 2^20).  Any 4-byte aligned pointers: 16- / 8-byte lanes when D % 4 / D % 2
+ *            == 0 and every [·][D] pointer of the call is aligned alike, 4-byte lanes otherwise.  ONE lane group (the smallest power of
+ *            two that holds the row's lanes, at most 64) finishes a graph, 4 rows in flight.  A row wider than 64 lanes is covered in
+ *            feature tiles by the SAME group, and the logit loop then reads the whole row once per tile (quadratic in the tile count).
+ * All three only launch on `stream`: no atomics, no allocation, no host wait, no scratch; each may be recorded into a HIP graph without
+ * an eager call first; two calls give equal bits.  G = 0 or N = 0 launches nothing, writes nothing and returns GNNMP_OK.  A SEGMENT OF ANY
+ * LENGTH IS WALKED BY ITS ONE LANE GROUP: a whole-graph readout of millions of rows is slow.
+ * Refused before any HIP call (GNNMP_EINVAL), each message naming its export: a NULL job; a NULL x (N > 0), seg_ptr, r, stats, dr, gx, gh,
+ * c, dh, da, dc; both or neither of q and gate; Dg outside {0, 1, D}, Dg = 0 with gate or Dg > 0 with q; D outside its range; a negative
+ * N or G; in the pullback no output, dgate in QUERY mode, dq in GATE mode, base without dx.
+ * ---------------------------------------------------------------------------------------------- */
+#define GNNMP_READOUT_MAX_D 4096
+typedef struct {
+    const float *x;          /* [N][D] */
+    const int64_t *seg_ptr;  /* [G+1] */
+    const float *q;          /* [G][D], QUERY mode (Dg = 0); else NULL */
+    const float *gate;       /* [N][Dg], GATE mode (Dg = 1 | D); else NULL */
+    float *r;                /* [G][D] */
+    float *stats;            /* [G][max(Dg,1)][2]: (max, denominator) */
+} gnnmp_segment_attn_t;
+int gnnmp_segment_attn_pool_f32(const gnnmp_segment_attn_t *job, int64_t N, int64_t G, int64_t D, int64_t Dg, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dr;         /* [G][D] */
+    const float *x;          /* [N][D] */
+    const int64_t *seg_ptr;  /* [G+1] */
+    const float *q;          /* [G][D] or NULL */
+    const float *gate;       /* [N][Dg] or NULL */
+    const float *r;          /* [G][D], the forward's */
+    const float *stats;      /* [G][max(Dg,1)][2], the forward's */
+    const float *base;       /* [N][D] or NULL; may be dx */
+    float *dq;               /* [G][D] or NULL; QUERY mode */
+    float *dx;               /* [N][D] or NULL */
+    float *dgate;            /* [N][Dg] or NULL; GATE mode */
+} gnnmp_segment_attn_grad_t;
+int gnnmp_segment_attn_pool_grad_f32(const gnnmp_segment_attn_grad_t *job, int64_t N, int64_t G, int64_t D, int64_t Dg,
+                                     gnnmp_stream_t stream);
+
+typedef struct {
+    const float *gx;         /* [N][4D] */
+    const float *gh;         /* [N][4D] */
+    const float *b;          /* [4D] or NULL */
+    const float *c;          /* [N][D]: the cell state that entered the step */
+    const float *dh;         /* [N][D]: cotangent of h' */
+    const float *dcn;        /* [N][D] or NULL: cotangent of c' from the next step */
+    float *da;               /* [N][4D] */
+    float *dc;               /* [N][D] */
+} gnnmp_lstm_grad_t;
+int gnnmp_lstm_pointwise_grad_f32(const gnnmp_lstm_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
