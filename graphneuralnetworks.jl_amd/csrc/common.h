@@ -490,6 +490,18 @@ inline auto with_op(int op, F &&f) {   // OP_SUM | OP_MAX | anything else: OP_MI
         default: return f(int_c<OP_MIN>{});
     }
 }
+// A gnnmp_act code as a template argument: GNNMP_ACT_RELU .. MAX_ACT as themselves, anything else GNNMP_ACT_IDENTITY.  The arms above
+// MAX_ACT name the identity instance, so a caller instantiates exactly the activations up to its MAX_ACT.
+template <int MAX_ACT, class F>
+inline auto with_act(int act, F &&f) {
+    switch (act <= MAX_ACT ? act : GNNMP_ACT_IDENTITY) {
+        case GNNMP_ACT_RELU: return f(int_c<GNNMP_ACT_RELU>{});
+        case GNNMP_ACT_SOFTPLUS: return f(int_c<(MAX_ACT >= GNNMP_ACT_SOFTPLUS ? GNNMP_ACT_SOFTPLUS : GNNMP_ACT_IDENTITY)>{});
+        case GNNMP_ACT_TANH: return f(int_c<(MAX_ACT >= GNNMP_ACT_TANH ? GNNMP_ACT_TANH : GNNMP_ACT_IDENTITY)>{});
+        case GNNMP_ACT_SWISH: return f(int_c<(MAX_ACT >= GNNMP_ACT_SWISH ? GNNMP_ACT_SWISH : GNNMP_ACT_IDENTITY)>{});
+        default: return f(int_c<GNNMP_ACT_IDENTITY>{});
+    }
+}
 template <class F>
 inline auto with_log2g(int log2g, F &&f) {   // 0 .. 5 | anything else: 6 (a whole wave)
     switch (log2g) {

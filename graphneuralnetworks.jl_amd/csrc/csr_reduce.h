@@ -3,7 +3,7 @@
 // 16-byte row loads in flight per lane group and folds them in ORIGINAL edge order (GNNlib/src/msgpass.jl:71-79,145-149;
 // NNlib's CPU scatter loop order).  See propagate.hip's header for the mapping.
 #pragma once
-#include "rowwalk.h"
+#include "slotwalk.h"
 
 namespace gnnmp {
 

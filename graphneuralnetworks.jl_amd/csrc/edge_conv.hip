@@ -21,18 +21,16 @@
 // differently associated recomputation would be a wrong gradient.  What a pass does not need it does not load (+ / mean with σ =
 // identity: g_e = r_e, no row of P is gathered).
 //
-// No atomics, no plan-owned scratch, every output element written exactly once (rows without in-edges and rows without out-edges
-// included).  All three kernels walk every ordinary row WHOLE, in edge order, whatever its length: their PlanRows carries n_chunks = 0
-// and decode_vrow is told not to skip long rows (VROW_WHOLE) — as hetero_rows_kernel / hetero_grad_rows_kernel do.  Every row therefore
-// has the bits of the sequential fold; the price is that A HUB ROW IS WALKED BY ONE LANE GROUP: correct, slow.  A kNN graph has no hub
-// destination (every row holds exactly k edges); its SOURCES can be hubs (feature-space kNN has them), so the src pass is where that
-// shows.  Chunked hub rows are a later change.
-#include "rowwalk.h"
+// Whole-row walks on the shared pieces and conventions of slotwalk.h (no atomics, every output written once, a hub row by one lane group).
+// A kNN graph has no hub destination (every row holds exactly k edges); its SOURCES can be hubs (feature-space kNN has them), so the src
+// pass is where the one-lane-group hub row shows.
+#include "launch.h"
+#include "slotwalk.h"
 
 namespace gnnmp {
 
 struct EdgeConvArgs {
-    PlanRows rows;               // forward / dst pass: the plan; src pass: the transposed plan.  n_chunks = 0 (rows are walked whole)
+    PlanRows rows;               // forward / dst pass: the plan; src pass: the transposed plan.  Whole rows (plan_rows_whole)
     RowGeom geom;
     const float *p;              // [n][2C]
     const float *y;              // [n][C] the forward output (gradient passes, max / min)
@@ -59,27 +57,17 @@ __device__ __forceinline__ float edge_conv_g(float pre, float yv, float dv, floa
 template <int VEC, int U, class F>
 __device__ __forceinline__ void edge_conv_walk(const int32_t *col, const float *src, int64_t ld, uint32_t beg, uint32_t end, int lig, int gbase,
                                                int G, bool active, F &&f) {
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
-        const uint32_t p = base + lig;
-        const int c = p < end ? col[p] : 0;
-        const int n = (int)min((uint32_t)G, end - base);
-        for (int j = 0; j < n; j += U) {
+    for (uint32_t base = beg; base < end; base += G) {
+        const Slots s = load_slots<true, false>(col, nullptr, base, end, lig, G);
+        for (int j = 0; j < s.n; j += U) {
             float v[U][VEC];
             int cjs[U];
+            bcast_word<U>(s.c, s.n, gbase, j, cjs);
 #pragma unroll
-            for (int u = 0; u < U; ++u) cjs[u] = __shfl(c, gbase + min(j + u, n - 1), 64);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (active) {   // clamped, unconditional within the lane's activity (maxmin_grad.h)
-                    Vec<VEC>::load(src + (int64_t)cjs[u] * ld, v[u]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) v[u][q] = 0.0f;
-                }
-            }
+            for (int u = 0; u < U; ++u) load_or_zero<VEC>(active, src + (int64_t)cjs[u] * ld, v[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (j + u < n) f(v[u]);
+                if (j + u < s.n) f(v[u]);
             }
         }
     }
@@ -87,23 +75,18 @@ __device__ __forceinline__ void edge_conv_walk(const int32_t *col, const float *
 
 template <int VEC, int U, int OP, int ACT>
 __global__ void __launch_bounds__(256) edge_conv_rows_kernel(const EdgeConvArgs a) {
-    VRow vr;
-    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, vr)) return;
-    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
-    const uint32_t beg = vr.beg, end = vr.end;
-    const int f0 = ((int)blockIdx.y * G + lig) * VEC;
-    const bool active = f0 < a.C;
+    RowLane w;
+    if (!decode_row_lane<VEC>(a.rows, a.geom, a.C, w)) return;
+    const int row = w.row, lig = w.lig, gbase = w.gbase, G = w.G, f0 = w.f0;
+    const uint32_t beg = w.beg, end = w.end;
+    const bool active = w.active;
     const int64_t ld = 2 * (int64_t)a.C;
     const float *pj = a.p + a.C + f0;      // the x_j share of row 0
     float ai[VEC], acc[VEC];
     {
         float pi[VEC], ps[VEC];
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) pi[q] = ps[q] = 0.0f;
-        if (active) {
-            Vec<VEC>::load(a.p + (int64_t)row * ld + f0, pi);
-            Vec<VEC>::load(pj + (int64_t)row * ld, ps);
-        }
+        load_or_zero<VEC>(active, a.p + (int64_t)row * ld + f0, pi);
+        load_or_zero<VEC>(active, pj + (int64_t)row * ld, ps);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) {
             ai[q] = pi[q] - ps[q];
@@ -126,12 +109,11 @@ __global__ void __launch_bounds__(256) edge_conv_rows_kernel(const EdgeConvArgs 
 template <int VEC, int U, int OP, int ACT>
 __global__ void __launch_bounds__(256) edge_conv_grad_dst_kernel(const EdgeConvArgs a) {
     constexpr bool NEED_PRE = ACT == GNNMP_ACT_RELU || OP != OP_SUM;
-    VRow vr;
-    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, vr)) return;
-    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
-    const uint32_t beg = vr.beg, end = vr.end;
-    const int f0 = ((int)blockIdx.y * G + lig) * VEC;
-    const bool active = f0 < a.C;
+    RowLane w;
+    if (!decode_row_lane<VEC>(a.rows, a.geom, a.C, w)) return;
+    const int row = w.row, lig = w.lig, gbase = w.gbase, G = w.G, f0 = w.f0;
+    const uint32_t beg = w.beg, end = w.end;
+    const bool active = w.active;
     const int64_t ld = 2 * (int64_t)a.C;
     const float *pj = a.p + a.C + f0;
     float ai[VEC], yv[VEC], dv[VEC], rs[VEC], acc[VEC];
@@ -172,59 +154,43 @@ __global__ void __launch_bounds__(256) edge_conv_grad_dst_kernel(const EdgeConvA
 template <int VEC, int U, int OP, int ACT>
 __global__ void __launch_bounds__(256) edge_conv_grad_src_kernel(const EdgeConvArgs a) {
     constexpr bool NEED_PRE = ACT == GNNMP_ACT_RELU || OP != OP_SUM;
-    VRow vr;
-    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, vr)) return;
-    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
-    const uint32_t beg = vr.beg, end = vr.end;
-    const int f0 = ((int)blockIdx.y * G + lig) * VEC;
-    const bool active = f0 < a.C;
+    RowLane w;
+    if (!decode_row_lane<VEC>(a.rows, a.geom, a.C, w)) return;
+    const int row = w.row, lig = w.lig, gbase = w.gbase, G = w.G, f0 = w.f0;
+    const uint32_t beg = w.beg, end = w.end;
+    const bool active = w.active;
     const int64_t ld = 2 * (int64_t)a.C;
     float bj[VEC], acc[VEC];
 #pragma unroll
-    for (int q = 0; q < VEC; ++q) bj[q] = acc[q] = 0.0f;
-    if (NEED_PRE && active) Vec<VEC>::load(a.p + (int64_t)row * ld + a.C + f0, bj);   // this source's x_j share
+    for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
+    load_or_zero<VEC>(NEED_PRE && active, a.p + (int64_t)row * ld + a.C + f0, bj);   // this source's x_j share
     const bool mean = OP == OP_SUM && a.mean;
     for (uint32_t base = beg; base < end; base += G) {
-        const uint32_t p = base + lig;
-        int c = 0;
+        const Slots s = load_slots<true, false>(a.rows.col, nullptr, base, end, lig, G);      // col: the destination of the edge
         uint32_t cn = 1;
-        if (p < end) {
-            c = a.rows.col[p];                                  // the destination of the edge
-            if (mean) cn = a.dst_rowptr[c + 1] - a.dst_rowptr[c];   // >= 1: this edge is in that row
-        }
-        const int n = (int)min((uint32_t)G, end - base);
-        for (int j = 0; j < n; j += U) {
+        if (mean && base + lig < end) cn = a.dst_rowptr[s.c + 1] - a.dst_rowptr[s.c];   // >= 1: this edge is in that row
+        for (int j = 0; j < s.n; j += U) {
             float pi[NEED_PRE ? U : 1][VEC], ps[NEED_PRE ? U : 1][VEC], yv[OP != OP_SUM ? U : 1][VEC], dv[U][VEC];
             int cjs[U];
+            uint32_t cns[U];
             float cnt[U];
+            bcast_word<U>(s.c, s.n, gbase, j, cjs);
+            if (mean) bcast_word<U>(cn, s.n, gbase, j, cns);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int jj = min(j + u, n - 1);
-                cjs[u] = __shfl(c, gbase + jj, 64);
-                cnt[u] = mean ? (float)(uint32_t)__shfl((int)cn, gbase + jj, 64) : 1.0f;
-            }
+            for (int u = 0; u < U; ++u) cnt[u] = mean ? (float)cns[u] : 1.0f;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t ci = cjs[u];
-                if (active) {
-                    if (NEED_PRE) {
-                        Vec<VEC>::load(a.p + ci * ld + f0, pi[NEED_PRE ? u : 0]);
-                        Vec<VEC>::load(a.p + ci * ld + a.C + f0, ps[NEED_PRE ? u : 0]);
-                    }
-                    if (OP != OP_SUM) Vec<VEC>::load(a.y + ci * a.C + f0, yv[OP != OP_SUM ? u : 0]);
-                    Vec<VEC>::load(a.dy + ci * a.C + f0, dv[u]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < VEC; ++q) {
-                        if (NEED_PRE) pi[NEED_PRE ? u : 0][q] = ps[NEED_PRE ? u : 0][q] = 0.0f;
-                        if (OP != OP_SUM) yv[OP != OP_SUM ? u : 0][q] = 0.0f;
-                        dv[u][q] = 0.0f;
-                    }
+                if (NEED_PRE) {
+                    load_or_zero<VEC>(active, a.p + ci * ld + f0, pi[NEED_PRE ? u : 0]);
+                    load_or_zero<VEC>(active, a.p + ci * ld + a.C + f0, ps[NEED_PRE ? u : 0]);
                 }
+                if (OP != OP_SUM) load_or_zero<VEC>(active, a.y + ci * a.C + f0, yv[OP != OP_SUM ? u : 0]);
+                load_or_zero<VEC>(active, a.dy + ci * a.C + f0, dv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (j + u < n) {
+                if (j + u < s.n) {
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) {
                         const float d = dv[u][q];
@@ -239,49 +205,24 @@ __global__ void __launch_bounds__(256) edge_conv_grad_src_kernel(const EdgeConvA
         }
     }
     float da[VEC];
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) da[q] = 0.0f;
-    if (active) Vec<VEC>::load(a.out + (int64_t)row * ld + f0, da);   // dA_j, written by the dst pass
+    load_or_zero<VEC>(active, a.out + (int64_t)row * ld + f0, da);   // dA_j, written by the dst pass
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = acc[q] - da[q];
     if (active) Vec<VEC>::store(a.out + (int64_t)row * ld + a.C + f0, acc);
 }
 
 // what both exports check of (plan, C, aggr, act) before any HIP call
-static int edge_conv_check(const char *who, const gnnmp_graph_t *plan, int64_t C, int aggr, int act) {
+static int edge_conv_check(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, int64_t C, int aggr, int act) {
     if (C < 1 || C > (1 << 20)) return fail(GNNMP_EINVAL, "%s: bad C %lld", who, (long long)C);
     if (aggr < GNNMP_SUM || aggr > GNNMP_MIN) return fail(GNNMP_EINVAL, "%s: bad aggr %d", who, aggr);
     if (act != GNNMP_ACT_IDENTITY && act != GNNMP_ACT_RELU) return fail(GNNMP_EINVAL, "%s: bad act %d (identity or relu)", who, act);
-    if (plan->n_src != plan->n_dst)
-        return fail(GNNMP_EINVAL, "%s: the plan is not square (%lld sources, %lld destinations)", who, (long long)plan->n_src, (long long)plan->n_dst);
-    return GNNMP_OK;
-}
-
-// the vector width every array of a call admits, and the row walk's geometry for it
-static int edge_conv_geom(const char *who, EdgeConvArgs &a, uintptr_t align, dim3 &grid) {
-    const int vec = pick_vec(a.C, reinterpret_cast<const void *>(align), nullptr);
-    a.geom = RowGeom{pick_log2g((a.C + vec - 1) / vec), 4, 0, 0};
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "%s: too many row blocks", who);
-    grid = row_grid(a.rows, a.geom, feature_tiles(a.C, vec, a.geom.log2g));
-    return vec;
-}
-
-static PlanRows whole_rows(const gnnmp_graph_t *plan) {
-    PlanRows r = plan_rows(plan);
-    r.n_chunks = 0;     // no chunk virtual rows: VROW_WHOLE walks the long rows themselves
-    r.n_long = 0;
-    return r;
+    return check_edge_plan(who, plan, plan_t, true, nullptr);      // no per-edge array: a plan with self loops of its own is welcome
 }
 
 template <class F>
 static void with_aggr_act(int aggr, int act, F &&f) {
     const int op = aggr == GNNMP_MAX ? OP_MAX : (aggr == GNNMP_MIN ? OP_MIN : OP_SUM);
-    with_op(op, [&](auto O) {
-        if (act == GNNMP_ACT_RELU)
-            f(O, int_c<GNNMP_ACT_RELU>{});
-        else
-            f(O, int_c<GNNMP_ACT_IDENTITY>{});
-    });
+    with_op(op, [&](auto O) { with_act<GNNMP_ACT_RELU>(act, [&](auto A) { f(O, A); }); });
 }
 
 }  // namespace gnnmp
@@ -293,18 +234,16 @@ extern "C" int gnnmp_edge_conv_f32(const gnnmp_graph_t *plan, const gnnmp_edge_c
     if (!job) return fail(GNNMP_EINVAL, "edge_conv: null job");
     if (!job->p) return fail(GNNMP_EINVAL, "edge_conv: null p");
     if (!job->y) return fail(GNNMP_EINVAL, "edge_conv: null y");
-    GNNMP_TRY(edge_conv_check("edge_conv", plan, C, job->aggr, job->act));
+    GNNMP_TRY(edge_conv_check("edge_conv", plan, nullptr, C, job->aggr, job->act));
     if (plan->n_dst == 0) return GNNMP_OK;
     EdgeConvArgs a = {};
-    a.rows = whole_rows(plan);
+    a.rows = plan_rows_whole(plan);
     a.p = job->p;
     a.out = job->y;
     a.C = (int)C;
     a.mean = job->aggr == GNNMP_MEAN;
-    // 16 / 8-byte lanes need C % 4 / C % 2 == 0 and every pointer aligned alike — p + C, column C inside a row, included
     dim3 grid;
-    const int vec = edge_conv_geom("edge_conv", a, reinterpret_cast<uintptr_t>(job->p) | reinterpret_cast<uintptr_t>(job->p + C) |
-                                                       reinterpret_cast<uintptr_t>(job->y), grid);
+    const int vec = row_walk_geom("edge_conv", a.rows, C, 0, {job->p, job->y}, a.geom, grid);
     if (vec < 0) return vec;
     with_vec(vec, [&](auto V) {
         with_aggr_act(job->aggr, job->act, [&](auto O, auto A) {
@@ -324,14 +263,10 @@ extern "C" int gnnmp_edge_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_g
     if (!job->y) return fail(GNNMP_EINVAL, "edge_conv_grad: null y");
     if (!job->dy) return fail(GNNMP_EINVAL, "edge_conv_grad: null dy");
     if (!job->dp) return fail(GNNMP_EINVAL, "edge_conv_grad: null dp");
-    GNNMP_TRY(edge_conv_check("edge_conv_grad", plan, C, job->aggr, job->act));
-    if (plan_t->n_dst != plan->n_dst || plan_t->n_src != plan->n_src)
-        return fail(GNNMP_EINVAL, "edge_conv_grad: the transposed plan has %lld rows, the plan %lld", (long long)plan_t->n_dst, (long long)plan->n_dst);
-    if (plan_t->n_edges != plan->n_edges || plan_t->n_total != plan->n_total)
-        return fail(GNNMP_EINVAL, "edge_conv_grad: the transposed plan has %lld edges, the plan %lld", (long long)plan_t->n_total, (long long)plan->n_total);
+    GNNMP_TRY(edge_conv_check("edge_conv_grad", plan, plan_t, C, job->aggr, job->act));
     if (plan->n_dst == 0) return GNNMP_OK;
     EdgeConvArgs a = {};
-    a.rows = whole_rows(plan);
+    a.rows = plan_rows_whole(plan);
     a.p = job->p;
     a.y = job->y;
     a.dy = job->dy;
@@ -340,22 +275,23 @@ extern "C" int gnnmp_edge_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_g
     a.C = (int)C;
     a.mean = job->aggr == GNNMP_MEAN;
     dim3 grid;
-    const int vec = edge_conv_geom("edge_conv_grad", a, reinterpret_cast<uintptr_t>(job->p) | reinterpret_cast<uintptr_t>(job->p + C) |
-                                                            reinterpret_cast<uintptr_t>(job->y) | reinterpret_cast<uintptr_t>(job->dy) |
-                                                            reinterpret_cast<uintptr_t>(job->dp) | reinterpret_cast<uintptr_t>(job->dp + C), grid);
+    const int vec = row_walk_geom("edge_conv_grad", a.rows, C, 0, {job->p, job->y, job->dy, job->dp}, a.geom, grid);
     if (vec < 0) return vec;
-    with_vec(vec, [&](auto V) {
-        with_aggr_act(job->aggr, job->act, [&](auto O, auto A) {
-            edge_conv_grad_dst_kernel<decltype(V)::value, 8, decltype(O)::value, decltype(A)::value><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    auto launch = [&](bool src) {      // the dst pass over a.rows = the plan, then the src pass over the transposed plan
+        with_vec(vec, [&](auto V) {
+            with_aggr_act(job->aggr, job->act, [&](auto O, auto A) {
+                constexpr int VEC = decltype(V)::value, OP = decltype(O)::value, ACT = decltype(A)::value;
+                if (src)
+                    edge_conv_grad_src_kernel<VEC, 4, OP, ACT><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+                else
+                    edge_conv_grad_dst_kernel<VEC, 8, OP, ACT><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+            });
         });
-    });
+    };
+    launch(false);
     GNNMP_LAUNCH_CHECK("edge_conv_grad_dst_kernel");
-    a.rows = whole_rows(plan_t);      // the same heights: the same geometry and grid
-    with_vec(vec, [&](auto V) {
-        with_aggr_act(job->aggr, job->act, [&](auto O, auto A) {
-            edge_conv_grad_src_kernel<decltype(V)::value, 4, decltype(O)::value, decltype(A)::value><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-        });
-    });
+    a.rows = plan_rows_whole(plan_t);      // the same heights: the same geometry and grid
+    launch(true);
     GNNMP_LAUNCH_CHECK("edge_conv_grad_src_kernel");
     return GNNMP_OK;
 }

@@ -15,9 +15,8 @@
 //                           q_k == 0 (a self loop, coincident points): the n-path terms are DEFINED as 0 (dd_k = 2 dq_k d_k = 0, dmx_k = 0
 //                           comes out by itself); the reference's AD gives Inf * 0 there.
 //   act_grad_z_kernel       dz = dy ⊙ act'(z) from the pre-activation, all five gnnmp_act codes
-// No atomics, no scratch, nothing owned by a plan written, every output element written exactly once.  K2 / K3 walk every row WHOLE
-// (PlanRows with n_chunks = 0, VROW_WHOLE), as cg_grad.hip does: A HUB ROW IS WALKED BY ONE LANE GROUP — correct, slow; chunked hub rows
-// are a later change.  Summation order of a row: G lanes, G = the smallest power of two >= the plan's mean row length (<= 64); lane l
+// K2 / K3 are whole-row walks on the conventions of slotwalk.h (a hub row by one lane group); their lanes stride over the edges themselves,
+// so of the shared pieces they take only group_sum.  Summation order of a row: G lanes, G = the smallest power of two >= the plan's mean row length (<= 64); lane l
 // folds slots l, l + G, ... sequentially from 0, then a butterfly p[l] + p[l ^ m], m = G/2 .. 1.  It depends on the plan only: either
 // output of K3 has the same bits whether or not the other is asked for, and two calls give equal bits.
 //
@@ -25,6 +24,7 @@
 // (the smallest one that holds Dx; components beyond Dx are zeros and add exact zeros to q_k).  The compiler's resource report
 // (LABNOTES.md) shows no scratch for any instance.
 #include "csr_reduce.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -115,16 +115,8 @@ __device__ __forceinline__ void egnn_add_dd(const float d[DXC], float q, float r
     }
 }
 
-template <int DXC>
-__device__ __forceinline__ void group_sum(float acc[DXC], int G) {
-    for (int m = G >> 1; m > 0; m >>= 1) {
-#pragma unroll
-        for (int c = 0; c < DXC; ++c) acc[c] = acc[c] + __shfl_xor(acc[c], m, 64);
-    }
-}
-
 struct EgnnCoordArgs {
-    PlanRows rows;      // n_chunks = 0: rows are walked whole
+    PlanRows rows;      // whole rows (plan_rows_whole)
     RowGeom geom;
     const float *x, *mx;
     float *xo;
@@ -243,17 +235,6 @@ __global__ void __launch_bounds__(256) act_grad_z_kernel(const float *dy, const 
     }
 }
 
-template <class F>
-static void with_act5(int act, F &&f) {
-    switch (act) {
-        case GNNMP_ACT_RELU: return f(int_c<GNNMP_ACT_RELU>{});
-        case GNNMP_ACT_SOFTPLUS: return f(int_c<GNNMP_ACT_SOFTPLUS>{});
-        case GNNMP_ACT_TANH: return f(int_c<GNNMP_ACT_TANH>{});
-        case GNNMP_ACT_SWISH: return f(int_c<GNNMP_ACT_SWISH>{});
-        default: return f(int_c<GNNMP_ACT_IDENTITY>{});
-    }
-}
-
 // the register capacity that holds Dx coordinates
 template <class F>
 static void with_dxc(int Dx, F &&f) {
@@ -265,35 +246,10 @@ static void with_dxc(int Dx, F &&f) {
     return f(int_c<16>{});
 }
 
-static PlanRows egnn_whole_rows(const gnnmp_graph_t *plan) {
-    PlanRows r = plan_rows(plan);
-    r.n_chunks = 0;     // no chunk virtual rows: VROW_WHOLE walks the long rows themselves
-    r.n_long = 0;
-    return r;
-}
-
 // lanes per row: the smallest power of two >= the plan's mean row length
 static RowGeom egnn_row_geom(const gnnmp_graph_t *plan) {
     const int64_t mean = plan->n_dst > 0 ? (plan->n_total + plan->n_dst - 1) / plan->n_dst : 1;
     return RowGeom{pick_log2g(mean), 4, 0, 0};
-}
-
-static int egnn_check_plan(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t) {
-    if (plan->n_src != plan->n_dst)
-        return fail(GNNMP_EINVAL, "%s: the plan is not square (%lld sources, %lld destinations)", who, (long long)plan->n_src,
-                    (long long)plan->n_dst);
-    if (plan_t) {
-        if (plan_t->n_dst != plan->n_dst || plan_t->n_src != plan->n_src)
-            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld rows, the plan %lld", who, (long long)plan_t->n_dst,
-                        (long long)plan->n_dst);
-        if (plan_t->n_edges != plan->n_edges || plan_t->n_total != plan->n_total)
-            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld edges, the plan %lld", who, (long long)plan_t->n_total,
-                        (long long)plan->n_total);
-    }
-    if (plan->n_total != plan->n_edges)
-        return fail(GNNMP_EINVAL, "%s: the plan was built with self loops (%lld slots, %lld edges): mx has no entry for them", who,
-                    (long long)plan->n_total, (long long)plan->n_edges);
-    return GNNMP_OK;
 }
 
 }  // namespace gnnmp
@@ -343,7 +299,7 @@ extern "C" int gnnmp_egnn_edge_f32(const gnnmp_egnn_edge_t *job, int64_t E, int6
     const dim3 grid((unsigned)blocks, (unsigned)feature_tiles(hid, vec, a.log2g));
     const bool has_f = job->F != nullptr;
     with_vec(vec, [&](auto V) {
-        with_act5(job->act, [&](auto A) {
+        with_act<GNNMP_ACT_SWISH>(job->act, [&](auto A) {
             if (has_f)
                 egnn_edge_kernel<decltype(V)::value, decltype(A)::value, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
             else
@@ -361,17 +317,17 @@ extern "C" int gnnmp_egnn_coord_f32(const gnnmp_graph_t *plan, const gnnmp_egnn_
     if (!job->mx && plan->n_total > 0) return fail(GNNMP_EINVAL, "egnn_coord: null mx");      // no edge: no entry of mx is read
     if (!job->xo) return fail(GNNMP_EINVAL, "egnn_coord: null xo");
     if (Dx < 1 || Dx > 16) return fail(GNNMP_EINVAL, "egnn_coord: bad Dx %lld", (long long)Dx);
-    GNNMP_TRY(egnn_check_plan("egnn_coord", plan, nullptr));
+    GNNMP_TRY(check_edge_plan("egnn_coord", plan, nullptr, true, "mx has no entry for them"));
     if (plan->n_dst == 0) return GNNMP_OK;
     EgnnCoordArgs a = {};
-    a.rows = egnn_whole_rows(plan);
+    a.rows = plan_rows_whole(plan);
     a.geom = egnn_row_geom(plan);
     a.x = job->x;
     a.mx = job->mx;
     a.xo = job->xo;
     a.Dx = (int)Dx;
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "egnn_coord: too many row blocks");
-    const dim3 grid = row_grid(a.rows, a.geom, 1);
+    dim3 grid;
+    GNNMP_TRY(row_walk_grid("egnn_coord", a.rows, a.geom, 1, grid));
     with_dxc(a.Dx, [&](auto C) { egnn_coord_kernel<decltype(C)::value><<<grid, 256, 0, (hipStream_t)stream>>>(a); });
     GNNMP_LAUNCH_CHECK("egnn_coord_kernel");
     return GNNMP_OK;
@@ -388,10 +344,10 @@ extern "C" int gnnmp_egnn_coord_grad_f32(const gnnmp_graph_t *plan, const gnnmp_
     if (job->dx && !job->mx && plan->n_total > 0) return fail(GNNMP_EINVAL, "egnn_coord_grad: dx without mx");      // no edge: not read
     if (job->dx && !job->dq && plan->n_total > 0) return fail(GNNMP_EINVAL, "egnn_coord_grad: dx without dq");
     if (Dx < 1 || Dx > 16) return fail(GNNMP_EINVAL, "egnn_coord_grad: bad Dx %lld", (long long)Dx);
-    GNNMP_TRY(egnn_check_plan("egnn_coord_grad", plan, plan_t));
+    GNNMP_TRY(check_edge_plan("egnn_coord_grad", plan, plan_t, true, "mx has no entry for them"));
     if (plan->n_dst == 0) return GNNMP_OK;
     EgnnCoordGradArgs a = {};
-    a.rows = egnn_whole_rows(plan);
+    a.rows = plan_rows_whole(plan);
     a.geom = egnn_row_geom(plan);
     if (job->dx) {
         a.t_rowptr = plan_t->rowptr;
@@ -405,8 +361,8 @@ extern "C" int gnnmp_egnn_coord_grad_f32(const gnnmp_graph_t *plan, const gnnmp_
     a.dmx = job->dmx;
     a.dx = job->dx;
     a.Dx = (int)Dx;
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "egnn_coord_grad: too many row blocks");
-    const dim3 grid = row_grid(a.rows, a.geom, 1);
+    dim3 grid;
+    GNNMP_TRY(row_walk_grid("egnn_coord_grad", a.rows, a.geom, 1, grid));
     const bool want_dmx = job->dmx != nullptr, want_dx = job->dx != nullptr;
     with_dxc(a.Dx, [&](auto C) {
         constexpr int DXC = decltype(C)::value;
@@ -435,7 +391,7 @@ extern "C" int gnnmp_act_grad_z_f32(const gnnmp_act_grad_z_t *job, int64_t n, gn
     if (blocks >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "act_grad_z: too many blocks");
     const float *dy = job->dy, *z = job->z;
     float *dz = job->dz;
-    with_act5(job->act, [&](auto A) {
+    with_act<GNNMP_ACT_SWISH>(job->act, [&](auto A) {
         if (vec == 4)
             act_grad_z_kernel<4, decltype(A)::value><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(dy, z, dz, n);
         else

@@ -18,13 +18,14 @@
 //                          l folds the slice's edges l, l + 64, ... sequentially from 0, then a 64-lane butterfly.  Every element of part
 //                          is written (an empty slice: zeros).
 //   gmm_wfinal_kernel      one block: dmu / dsinv [k][d] = part[0] + part[1] + ... in index order, from 0.
-// No atomics, no scratch but the caller's `part`, nothing owned by a plan written.  The row kernels walk every row WHOLE, in edge order,
-// whatever its length (PlanRows with n_chunks = 0, VROW_WHOLE), as cg_grad.hip does: A HUB ROW IS WALKED BY ONE LANE GROUP — correct, slow.
+// No scratch but the caller's `part`.  The row kernels are whole-row walks on the shared pieces and conventions of slotwalk.h (no atomics,
+// every output written once, a hub row by one lane group).
 //
 // Registers: the accumulators (and, in the pullback, xk[j]) live in registers, so the row kernels are instantiated for the capacities
 // KC = 1, 2, 3, 4, 8, 16 (the smallest one that holds K; kernels beyond K load nothing and add nothing).  DESIGN.md §3 has the compiler's
 // resource report: no instance uses scratch.
 #include "csr_reduce.h"
+#include "launch.h"
 
 namespace gnnmp {
 
@@ -36,7 +37,7 @@ constexpr int gmm_u() {
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------
 struct GmmConvArgs {
-    PlanRows rows;      // n_chunks = 0: rows are walked whole
+    PlanRows rows;      // whole rows (plan_rows_whole)
     RowGeom geom;
     const float *w;     // [n_edges][K]
     const float *xk;    // [n][K C]
@@ -48,12 +49,11 @@ struct GmmConvArgs {
 template <int VEC, int KC>
 __global__ void __launch_bounds__(256) gmm_conv_kernel(const GmmConvArgs a) {
     constexpr int U = gmm_u<KC>();
-    VRow vr;
-    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, vr)) return;
-    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
-    const uint32_t beg = vr.beg, end = vr.end;
-    const int f0 = ((int)blockIdx.y * G + lig) * VEC;
-    const bool active = f0 < a.C;      // inactive lanes of the last feature tile load no row and store nothing
+    RowLane w;
+    if (!decode_row_lane<VEC>(a.rows, a.geom, a.C, w)) return;
+    const int row = w.row, f0 = w.f0;
+    const bool active = w.active;
+    const uint32_t beg = w.beg, end = w.end;
     const int64_t ld = (int64_t)a.K * a.C;
     float acc[KC][VEC];
 #pragma unroll
@@ -61,37 +61,20 @@ __global__ void __launch_bounds__(256) gmm_conv_kernel(const GmmConvArgs a) {
 #pragma unroll
         for (int q = 0; q < VEC; ++q) acc[k][q] = 0.0f;
     }
-    for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
-        const uint32_t p = base + lig;
-        int c = 0;
-        uint32_t ev = 0;
-        if (p < end) {
-            c = a.rows.col[p];
-            ev = (uint32_t)a.rows.eid[p];    // < n_edges: the export refuses a plan with self loops of its own
-        }
-        const int n = (int)min((uint32_t)G, end - base);
-        for (int j = 0; j < n; j += U) {
+    for (uint32_t base = beg; base < end; base += w.G) {
+        const Slots sl = load_slots<true, true>(a.rows.col, a.rows.eid, base, end, w.lig, w.G);
+        for (int j = 0; j < sl.n; j += U) {
             float v[U][KC][VEC], wk[U][KC];
             int cjs[U];
             uint32_t ejs[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int jj = min(j + u, n - 1);      // clamped: every load below has a valid address
-                cjs[u] = __shfl(c, gbase + jj, 64);
-                ejs[u] = (uint32_t)__shfl((int)ev, gbase + jj, 64);
-            }
+            bcast_slots<U, true, true>(sl, w.gbase, j, cjs, ejs);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
 #pragma unroll
                 for (int k = 0; k < KC; ++k) {
                     if (k < a.K) {
                         wk[u][k] = a.w[(int64_t)ejs[u] * a.K + k];
-                        if (active) {
-                            Vec<VEC>::load(a.xk + (int64_t)cjs[u] * ld + (int64_t)k * a.C + f0, v[u][k]);
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < VEC; ++q) v[u][k][q] = 0.0f;
-                        }
+                        load_or_zero<VEC>(active, a.xk + (int64_t)cjs[u] * ld + (int64_t)k * a.C + f0, v[u][k]);
                     } else {
                         wk[u][k] = 0.0f;
 #pragma unroll
@@ -101,7 +84,7 @@ __global__ void __launch_bounds__(256) gmm_conv_kernel(const GmmConvArgs a) {
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (j + u < n) {
+                if (j + u < sl.n) {
 #pragma unroll
                     for (int k = 0; k < KC; ++k) {
 #pragma unroll
@@ -151,10 +134,9 @@ struct GmmGradArgs {
 template <int VEC, int KC, bool WANT_DXK, bool WANT_DW>
 __global__ void __launch_bounds__(256) gmm_conv_grad_kernel(const GmmGradArgs a) {
     constexpr int U = 2;
-    VRow vr;
-    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, vr)) return;
-    const int row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
-    const uint32_t beg = vr.beg, end = vr.end;
+    VRow w;      // no RowLane: the lane group walks the feature tiles itself
+    if (!decode_vrow<VROW_WHOLE>(a.rows, a.geom, blockIdx.x, w)) return;
+    const int row = w.row, lig = w.lig, G = w.G;
     const int64_t ld = (int64_t)a.K * a.C;
     const float fk = (float)a.K;
     for (int tt = 0; tt < a.tiles; ++tt) {      // one tile unless C > 64 VEC: dw's sum over channels stays inside this lane group
@@ -170,39 +152,29 @@ __global__ void __launch_bounds__(256) gmm_conv_grad_kernel(const GmmGradArgs a)
             }
             if (WANT_DW && active && k < a.K) Vec<VEC>::load(a.xk + (int64_t)row * ld + (int64_t)k * a.C + f0, xr[WANT_DW ? k : 0]);
         }
-        for (uint32_t base = beg; base < end; base += G) {
-            const uint32_t p = base + lig;
-            int c = 0;
-            uint32_t ev = 0;
+        for (uint32_t base = w.beg; base < w.end; base += G) {
+            const Slots sl = load_slots<true, true>(a.rows.col, a.rows.eid, base, w.end, lig, G);      // col: the destination of the edge
             float qv = 0.0f;
-            if (p < end) {
-                c = a.rows.col[p];                           // the destination of the edge
-                ev = (uint32_t)a.rows.eid[p];
-                const uint32_t deg = a.rowptr[c + 1] - a.rowptr[c];      // >= 1: this edge enters c
+            if (base + lig < w.end) {
+                const uint32_t deg = a.rowptr[sl.c + 1] - a.rowptr[sl.c];      // >= 1: this edge enters c
                 qv = 1.0f / (fk * (float)max(deg, 1u));
             }
-            const int n = (int)min((uint32_t)G, end - base);
-            for (int j = 0; j < n; j += U) {
+            for (int j = 0; j < sl.n; j += U) {
                 float d[U][VEC], wk[U][KC], qs[U];
                 uint32_t ejs[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int jj = min(j + u, n - 1);
-                    const int cj = __shfl(c, gbase + jj, 64);
-                    ejs[u] = (uint32_t)__shfl((int)ev, gbase + jj, 64);
-                    qs[u] = __shfl(qv, gbase + jj, 64);
-                    if (active) {
-                        Vec<VEC>::load(a.dz + (int64_t)cj * a.C + f0, d[u]);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < VEC; ++q) d[u][q] = 0.0f;
-                    }
+                for (int u = 0; u < U; ++u) {      // the broadcast stays here, slot by slot with its loads: bcast_slots ahead of the
+                    const int jj = min(j + u, sl.n - 1);      // loop costs <1, 16, true, true> and <2, 4, true, true> a wave (LABNOTES.md)
+                    const int cj = __shfl(sl.c, w.gbase + jj, 64);
+                    ejs[u] = (uint32_t)__shfl((int)sl.ev, w.gbase + jj, 64);
+                    qs[u] = __shfl(qv, w.gbase + jj, 64);
+                    load_or_zero<VEC>(active, a.dz + (int64_t)cj * a.C + f0, d[u]);
 #pragma unroll
                     for (int k = 0; k < KC; ++k) wk[u][k] = (WANT_DXK && k < a.K) ? a.w[(int64_t)ejs[u] * a.K + k] : 0.0f;     // dw reads no w
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    if (j + u < n) {      // uniform over the lane group: every lane of it takes part in the butterfly
+                    if (j + u < sl.n) {      // uniform over the lane group: every lane of it takes part in the butterfly
                         float t[VEC];
 #pragma unroll
                         for (int q = 0; q < VEC; ++q) t[q] = qs[u] * d[u][q];
@@ -221,10 +193,7 @@ __global__ void __launch_bounds__(256) gmm_conv_grad_kernel(const GmmGradArgs a)
 #pragma unroll
                                 for (int q = 0; q < VEC; ++q) pk[k] = pk[k] + xr[WANT_DW ? k : 0][q] * t[q];
                             }
-                            for (int m = G >> 1; m > 0; m >>= 1) {
-#pragma unroll
-                                for (int k = 0; k < KC; ++k) pk[k] = pk[k] + __shfl_xor(pk[k], m, 64);
-                            }
+                            group_sum<KC>(pk, G);
                             if (lig == 0) {
                                 float *o = a.dw + (int64_t)ejs[u] * a.K;
 #pragma unroll
@@ -329,43 +298,10 @@ static void with_kc(int K, F &&f) {
     return f(int_c<16>{});
 }
 
-static PlanRows gmm_whole_rows(const gnnmp_graph_t *plan) {
-    PlanRows r = plan_rows(plan);
-    r.n_chunks = 0;     // no chunk virtual rows: VROW_WHOLE walks the long rows themselves
-    r.n_long = 0;
-    return r;
-}
-
 static int gmm_check_sizes(const char *who, int64_t K, int64_t C) {
     if (K < 1 || K > 16) return fail(GNNMP_EINVAL, "%s: bad K %lld", who, (long long)K);
     if (C < 1 || C > (1 << 19) || K * C > (1 << 20)) return fail(GNNMP_EINVAL, "%s: bad C %lld", who, (long long)C);
     return GNNMP_OK;
-}
-
-static int gmm_check_plan(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t) {
-    if (plan->n_src != plan->n_dst)
-        return fail(GNNMP_EINVAL, "%s: the plan is not square (%lld sources, %lld destinations)", who, (long long)plan->n_src,
-                    (long long)plan->n_dst);
-    if (plan_t) {
-        if (plan_t->n_dst != plan->n_dst || plan_t->n_src != plan->n_src)
-            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld rows, the plan %lld", who, (long long)plan_t->n_dst,
-                        (long long)plan->n_dst);
-        if (plan_t->n_edges != plan->n_edges || plan_t->n_total != plan->n_total)
-            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld edges, the plan %lld", who, (long long)plan_t->n_total,
-                        (long long)plan->n_total);
-    }
-    if (plan->n_total != plan->n_edges)
-        return fail(GNNMP_EINVAL, "%s: the plan was built with self loops (%lld slots, %lld edges): w has no row for them", who,
-                    (long long)plan->n_total, (long long)plan->n_edges);
-    return GNNMP_OK;
-}
-
-// the vector width every array the kernels touch with Vec<> admits (block k of a row starts at k C: C % vec == 0 keeps it aligned)
-template <class... P>
-static int gmm_vec(int64_t C, const P *...ptr) {
-    uintptr_t align = 0;
-    ((align |= reinterpret_cast<uintptr_t>(ptr)), ...);
-    return pick_vec(C, reinterpret_cast<const void *>(align), nullptr);
 }
 
 }  // namespace gnnmp
@@ -380,10 +316,10 @@ extern "C" int gnnmp_gmm_conv_f32(const gnnmp_graph_t *plan, const gnnmp_gmm_con
     if (!job->y) return fail(GNNMP_EINVAL, "gmm_conv: null y");
     GNNMP_TRY(gmm_check_sizes("gmm_conv", K, C));
     if (job->act < GNNMP_ACT_IDENTITY || job->act > GNNMP_ACT_SWISH) return fail(GNNMP_EINVAL, "gmm_conv: bad act %d", job->act);
-    GNNMP_TRY(gmm_check_plan("gmm_conv", plan, nullptr));
+    GNNMP_TRY(check_edge_plan("gmm_conv", plan, nullptr, true, "w has no row for them"));
     if (plan->n_dst == 0) return GNNMP_OK;
     GmmConvArgs a = {};
-    a.rows = gmm_whole_rows(plan);
+    a.rows = plan_rows_whole(plan);
     a.w = job->w;
     a.xk = job->xk;
     a.bias = job->bias;
@@ -392,10 +328,9 @@ extern "C" int gnnmp_gmm_conv_f32(const gnnmp_graph_t *plan, const gnnmp_gmm_con
     a.K = (int)K;
     a.C = (int)C;
     a.act = job->act;
-    const int vec = gmm_vec(C, job->xk, job->bias, job->y, job->z);
-    a.geom = RowGeom{pick_log2g((C + vec - 1) / vec), 4, 0, 0};
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "gmm_conv: too many row blocks");
-    const dim3 grid = row_grid(a.rows, a.geom, feature_tiles(C, vec, a.geom.log2g));
+    dim3 grid;
+    const int vec = row_walk_geom("gmm_conv", a.rows, C, 0, {job->xk, job->bias, job->y, job->z}, a.geom, grid);
+    if (vec < 0) return vec;
     with_vec(vec, [&](auto V) {
         with_kc(a.K, [&](auto KC) { gmm_conv_kernel<decltype(V)::value, decltype(KC)::value><<<grid, 256, 0, (hipStream_t)stream>>>(a); });
     });
@@ -413,11 +348,11 @@ extern "C" int gnnmp_gmm_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_gr
     if (job->dxk && !job->w && plan->n_total > 0) return fail(GNNMP_EINVAL, "gmm_conv_grad: dxk without w");      // no edge: not read
     if (job->dw && !job->xk) return fail(GNNMP_EINVAL, "gmm_conv_grad: dw without xk");
     GNNMP_TRY(gmm_check_sizes("gmm_conv_grad", K, C));
-    GNNMP_TRY(gmm_check_plan("gmm_conv_grad", plan, plan_t));
+    GNNMP_TRY(check_edge_plan("gmm_conv_grad", plan, plan_t, true, "w has no row for them"));
     if (plan->n_dst == 0) return GNNMP_OK;
     const bool want_dxk = job->dxk != nullptr, want_dw = job->dw != nullptr;
     GmmGradArgs a = {};
-    a.rows = gmm_whole_rows(plan_t);
+    a.rows = plan_rows_whole(plan_t);
     a.rowptr = plan->rowptr;
     a.w = job->w;
     a.xk = job->xk;
@@ -426,11 +361,10 @@ extern "C" int gnnmp_gmm_conv_grad_f32(const gnnmp_graph_t *plan, const gnnmp_gr
     a.dw = job->dw;
     a.K = (int)K;
     a.C = (int)C;
-    const int vec = gmm_vec(C, want_dw ? job->xk : nullptr, job->dz, job->dxk);
-    a.geom = RowGeom{pick_log2g((C + vec - 1) / vec), 4, 0, 0};
+    dim3 grid;      // one block per row group: the lane group walks the feature tiles itself
+    const int vec = row_walk_geom("gmm_conv_grad", a.rows, C, 1, {want_dw ? job->xk : nullptr, job->dz, job->dxk}, a.geom, grid);
+    if (vec < 0) return vec;
     a.tiles = feature_tiles(C, vec, a.geom.log2g);
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "gmm_conv_grad: too many row blocks");
-    const dim3 grid = row_grid(a.rows, a.geom, 1);
     with_vec(vec, [&](auto V) {
         with_kc(a.K, [&](auto KC) {
             constexpr int VEC = decltype(V)::value, KCV = decltype(KC)::value;

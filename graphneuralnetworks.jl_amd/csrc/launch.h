@@ -96,5 +96,9 @@ int colsum_tree_fold(const float *part, int nparts, int D, int C, int out_ld, in
 int plan_dispose(gnnmp_graph_t *p, hipStream_t stream, bool stream_known);
 // GNNMP_OK if plan_t has plan's sizes transposed, GNNMP_EINVAL (message "<who>: ...", with the six sizes) otherwise
 int check_transposed(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t);
+// What the edge-level training exports ask of their plans, GNNMP_EINVAL with "<who>: ..." otherwise: the plan is square (need_square);
+// plan_t, when given, has the plan's rows and edges; and — when the call has per-edge arrays, no_row saying which ("fs_e has no row for
+// them") — the plan was not built with self loops of its own, which lie beyond those arrays' last row.
+int check_edge_plan(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, bool need_square, const char *no_row);
 
 }  // namespace gnnmp

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "slotwalk.h"
 #include "scratch.h"
 #include "sort_scan.h"
 
@@ -192,36 +192,25 @@ __device__ __forceinline__ void row_accumulate(const uint32_t *rowptr, const int
                                                const float *dz, int row, int D, int lig, int gbase, float (&acc)[NT][VEC]) {
     const uint32_t beg = rowptr[row], end = rowptr[row + 1];
     for (uint32_t base = beg; base < end; base += G) {
-        const uint32_t p = base + lig;
-        int c = 0;
-        float w = 0.0f;
-        if (p < end) {
-            c = col[p];
-            w = dz[(uint32_t)eid[p]];
-        }
-        const int n = (int)min((uint32_t)G, end - base);
-        for (int j = 0; j < n; j += U) {
+        const Slots s = load_slots<true, true>(col, eid, base, end, lig, G);
+        const float w = base + lig < end ? dz[s.ev] : 0.0f;
+        for (int j = 0; j < s.n; j += U) {
             float xv[U][NT][VEC];
             float wv[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int src = gbase + min(j + u, n - 1);
-                const int cj = __shfl(c, src, 64);
+            for (int u = 0; u < U; ++u) {      // the broadcast stays here, slot by slot with its loads: bcast_word ahead of the loop
+                const int src = gbase + min(j + u, s.n - 1);      // costs one instance a wave (LABNOTES.md)
+                const int cj = __shfl(s.c, src, 64);
                 wv[u] = __shfl(w, src, 64);
 #pragma unroll
                 for (int tl = 0; tl < NT; ++tl) {
                     const int f = (tl * G + lig) * VEC;
-                    if (f < D) {
-                        Vec<VEC>::load(x + (int64_t)cj * D + f, xv[u][tl]);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < VEC; ++q) xv[u][tl][q] = 0.0f;
-                    }
+                    load_or_zero<VEC>(f < D, x + (int64_t)cj * D + f, xv[u][tl]);
                 }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (j + u < n) {
+                if (j + u < s.n) {
 #pragma unroll
                     for (int tl = 0; tl < NT; ++tl)
 #pragma unroll

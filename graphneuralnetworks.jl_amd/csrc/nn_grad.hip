@@ -23,15 +23,16 @@
 // ascending, then the edges of the batch, then q ascending — from 0.0f; lanes that own no output hold 0.0f.  The G lane partials are
 // then summed by a butterfly: for m = G / 2, G / 4, ..., 1: p[lane] = p[lane] + p[lane ^ m].
 //
-// Rows are walked WHOLE, in edge order, whatever their length (PlanRows with n_chunks = 0, VROW_WHOLE), as cg_grad.hip and edge_conv.hip
-// do: A HUB ROW IS WALKED BY ONE LANE GROUP: correct, slow.  Chunked hub rows are a later change.
+// A whole-row walk on the conventions of slotwalk.h (a hub row by one lane group); its lanes stride over the edges themselves, so of the
+// shared pieces it takes only group_sum.
 // The compiler's resource report (LABNOTES.md) shows no scratch for any instance.
 #include "csr_reduce.h"
+#include "launch.h"
 
 namespace gnnmp {
 
 struct NnGradArgs {
-    PlanRows rows;       // the TRANSPOSED plan, n_chunks = 0 (rows are walked whole)
+    PlanRows rows;       // the TRANSPOSED plan, whole rows (plan_rows_whole)
     RowGeom geom;
     const float *x;      // [n][Din]
     const float *we;     // [n_edges][Dout * Din], read by the WANT_DX instances only
@@ -101,10 +102,7 @@ __global__ void __launch_bounds__(256) nn_grad_rows_kernel(const NnGradArgs a) {
         }
     }
     if (WANT_DX) {
-        for (int m = G >> 1; m >= 1; m >>= 1) {      // xor stays inside the group; its lanes all hold the same row
-#pragma unroll
-            for (int c = 0; c < TC; ++c) acc[c] = acc[c] + __shfl_xor(acc[c], m, 64);
-        }
+        group_sum<TC>(acc, G);      // the group's lanes all hold the same row
         if (lig == 0) {
 #pragma unroll
             for (int c = 0; c < TC; ++c)
@@ -133,18 +131,11 @@ extern "C" int gnnmp_nn_conv_grad_f32(const gnnmp_graph_t *plan_t, const gnnmp_n
     if (job->dx && !job->we) return fail(GNNMP_EINVAL, "nn_conv_grad: dx without we");
     if (Din < 1 || Din > (1 << 16)) return fail(GNNMP_EINVAL, "nn_conv_grad: bad Din %lld", (long long)Din);
     if (Dout < 1 || Dout > (1 << 16)) return fail(GNNMP_EINVAL, "nn_conv_grad: bad Dout %lld", (long long)Dout);
-    if (plan_t->n_src != plan_t->n_dst)
-        return fail(GNNMP_EINVAL, "nn_conv_grad: the plan is not square (%lld sources, %lld destinations)", (long long)plan_t->n_src,
-                    (long long)plan_t->n_dst);
-    if (plan_t->n_total != plan_t->n_edges)
-        return fail(GNNMP_EINVAL, "nn_conv_grad: the plan was built with self loops (%lld slots, %lld edges): we has no row for them",
-                    (long long)plan_t->n_total, (long long)plan_t->n_edges);
+    GNNMP_TRY(check_edge_plan("nn_conv_grad", plan_t, nullptr, true, "we has no row for them"));
     if (plan_t->n_dst == 0) return GNNMP_OK;
     if (!job->dx && plan_t->n_edges == 0) return GNNMP_OK;      // no row of dwe to write
     NnGradArgs a = {};
-    a.rows = plan_rows(plan_t);
-    a.rows.n_chunks = 0;      // no chunk virtual rows: VROW_WHOLE walks the long rows themselves
-    a.rows.n_long = 0;
+    a.rows = plan_rows_whole(plan_t);
     a.x = job->x;
     a.we = job->dx ? job->we : nullptr;
     a.dm = job->dm;
@@ -153,11 +144,9 @@ extern "C" int gnnmp_nn_conv_grad_f32(const gnnmp_graph_t *plan_t, const gnnmp_n
     a.Din = (int)Din;
     a.Dout = (int)Dout;
     // the lane width every vector access admits: o + Dout * c inside an edge's slab, for we (when read), dwe (when written) and Δ
-    const uintptr_t align = reinterpret_cast<uintptr_t>(a.we) | reinterpret_cast<uintptr_t>(a.dwe) | reinterpret_cast<uintptr_t>(a.dm);
-    const int vec = pick_vec(Dout, reinterpret_cast<const void *>(align), nullptr);
-    a.geom = RowGeom{pick_log2g((Dout + vec - 1) / vec), 4, 0, 0};
-    if (row_blocks(a.rows, a.geom) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "nn_conv_grad: too many row blocks");
-    const dim3 grid = row_grid(a.rows, a.geom, (int)((Din + NN_GRAD_TC - 1) / NN_GRAD_TC));
+    dim3 grid;
+    const int vec = row_walk_geom("nn_conv_grad", a.rows, Dout, (int)((Din + NN_GRAD_TC - 1) / NN_GRAD_TC), {a.we, a.dwe, a.dm}, a.geom, grid);
+    if (vec < 0) return vec;
     const bool want_dx = job->dx != nullptr, want_dw = job->dwe != nullptr;
     with_vec(vec, [&](auto V) {
         constexpr int VEC = decltype(V)::value;

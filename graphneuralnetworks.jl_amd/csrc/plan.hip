@@ -353,6 +353,23 @@ int check_transposed(const char *who, const gnnmp_graph_t *plan, const gnnmp_gra
                     (long long)plan->n_dst, (long long)plan->n_src, (long long)plan->n_total);
     return GNNMP_OK;
 }
+int check_edge_plan(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, bool need_square, const char *no_row) {
+    if (need_square && plan->n_src != plan->n_dst)
+        return fail(GNNMP_EINVAL, "%s: the plan is not square (%lld sources, %lld destinations)", who, (long long)plan->n_src,
+                    (long long)plan->n_dst);
+    if (plan_t) {
+        if (plan_t->n_dst != plan->n_dst || plan_t->n_src != plan->n_src)
+            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld rows, the plan %lld", who, (long long)plan_t->n_dst,
+                        (long long)plan->n_dst);
+        if (plan_t->n_edges != plan->n_edges || plan_t->n_total != plan->n_total)
+            return fail(GNNMP_EINVAL, "%s: the transposed plan has %lld edges, the plan %lld", who, (long long)plan_t->n_total,
+                        (long long)plan->n_total);
+    }
+    if (no_row && plan->n_total != plan->n_edges)
+        return fail(GNNMP_EINVAL, "%s: the plan was built with self loops (%lld slots, %lld edges): %s", who, (long long)plan->n_total,
+                    (long long)plan->n_edges, no_row);
+    return GNNMP_OK;
+}
 }  // namespace gnnmp
 
 extern "C" {

@@ -8,6 +8,7 @@
 // the kernel's combine step).  The dominant kernel therefore touches every edge exactly once and has no tail.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
 
 #include "common.h"
 
@@ -54,6 +55,14 @@ inline PlanRows plan_rows(const gnnmp_graph *p) {
     r.n_edges = (uint32_t)p->n_edges;
     return r;
 }
+// The view of a kernel that walks every row WHOLE (decode_vrow<VROW_WHOLE>; slotwalk.h says what that buys and costs): no chunk virtual
+// rows, so the rows longer than long_thresh are walked themselves.
+inline PlanRows plan_rows_whole(const gnnmp_graph *p) {
+    PlanRows r = plan_rows(p);
+    r.n_chunks = 0;
+    r.n_long = 0;
+    return r;
+}
 
 struct RowGeom {
     int log2g;   // lanes per virtual row = 1 << log2g
@@ -80,6 +89,25 @@ inline dim3 row_grid(const PlanRows &r, RowGeom &g, int tiles, bool remap = fals
         gx = (int64_t)g.nbc + (int64_t)g.cpx * 8;
     }
     return dim3((unsigned)gx, (unsigned)tiles);
+}
+// row_grid for an export that chose g.log2g / g.waves itself, or the refusal of a plan with more row blocks than a grid holds
+inline int row_walk_grid(const char *who, const PlanRows &r, RowGeom &g, int tiles, dim3 &grid) {
+    if (row_blocks(r, g) >= INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "%s: too many row blocks", who);
+    grid = row_grid(r, g, tiles);
+    return GNNMP_OK;
+}
+// The geometry of a row walk with one lane group a row and vec floats of `width` a lane.  Returns vec — the widest Vec<vec> access
+// that every array of `arrays` admits (a null one admits any) — or a failure (< 0); fills g (4 waves a block) and the grid over `tiles`
+// feature tiles (0: feature_tiles of the width).  Column k * width inside a row (the planar [n][2C] and [n][K C] matrices) needs no
+// entry of its own: width % vec == 0, so it is aligned whenever the row is.
+inline int row_walk_geom(const char *who, const PlanRows &r, int64_t width, int tiles, std::initializer_list<const float *> arrays,
+                         RowGeom &g, dim3 &grid) {
+    uintptr_t align = 0;
+    for (const float *p : arrays) align |= reinterpret_cast<uintptr_t>(p);
+    const int vec = pick_vec(width, reinterpret_cast<const void *>(align), nullptr);
+    g = RowGeom{pick_log2g((width + vec - 1) / vec), 4, 0, 0};
+    const int rc = row_walk_grid(who, r, g, tiles ? tiles : feature_tiles(width, vec, g.log2g), grid);
+    return rc != GNNMP_OK ? rc : vec;
 }
 
 struct VRow {
