@@ -35,6 +35,8 @@ from .backward_egnn import egnn_conv_ad  # noqa: F401
 from .backward_gmm import gmm_conv_ad  # noqa: F401
 from .backward_megnet import aggregate_neighbors_ad, megnet_conv_ad  # noqa: F401
 from .backward_readout import global_attention_pool_ad, set2set_ad  # noqa: F401
+from .backward_poly import cheb_conv_ad, d_conv_ad  # noqa: F401
+from .backward_gated import gated_graph_conv_ad, res_gated_graph_conv_ad  # noqa: F401
 from .dataset import DataLoader, GraphDataset, concat_plans  # noqa: F401
 from .sampling import (NeighborLoader, NodeSet, has_self_loops, induced_subgraph, is_bidirected, sample_neighbors,  # noqa: F401
                        sort_edge_index)

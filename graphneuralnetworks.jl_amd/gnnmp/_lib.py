@@ -60,6 +60,7 @@ SYMBOLS = (
     "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
     "gnnmp_megnet_edge_f32", "gnnmp_megnet_edge_grad_f32", "gnnmp_aggregate_grad_f32",
     "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
+    "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -226,6 +227,21 @@ class LstmGradJob(ctypes.Structure):
                 ("dcn", ctypes.c_void_p), ("da", ctypes.c_void_p), ("dc", ctypes.c_void_p)]
 
 
+class PolyHopJob(ctypes.Structure):
+    """gnnmp_poly_hop_t: one gnnmp_poly_hop_f32 call (z, w_slot | None, ss_slot | None, scale_dst | None, self | None, prev | None,
+    add | None read; out written; out may be prev or add)"""
+    _fields_ = [("z", ctypes.c_void_p), ("w_slot", ctypes.c_void_p), ("ss_slot", ctypes.c_void_p), ("scale_dst", ctypes.c_void_p),
+                ("self", ctypes.c_void_p), ("prev", ctypes.c_void_p), ("add", ctypes.c_void_p), ("alpha", ctypes.c_float),
+                ("beta", ctypes.c_float), ("gamma", ctypes.c_float), ("out", ctypes.c_void_p)]
+
+
+class GruGradJob(ctypes.Structure):
+    """gnnmp_gru_grad_t: one gnnmp_gru_pointwise_grad_f32 call (gx, gh, b | None, h, dout, base | None read; dgx, dgh, dh written; base
+    may be dh)"""
+    _fields_ = [("gx", ctypes.c_void_p), ("gh", ctypes.c_void_p), ("b", ctypes.c_void_p), ("h", ctypes.c_void_p), ("dout", ctypes.c_void_p),
+                ("base", ctypes.c_void_p), ("dgx", ctypes.c_void_p), ("dgh", ctypes.c_void_p), ("dh", ctypes.c_void_p)]
+
+
 class GnnmpError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libgnnmp status {status}: {msg}")
@@ -382,6 +398,8 @@ def load():
         "gnnmp_segment_attn_pool_f32": [ctypes.POINTER(SegmentAttnJob), i64, i64, i64, i64, vp],
         "gnnmp_segment_attn_pool_grad_f32": [ctypes.POINTER(SegmentAttnGradJob), i64, i64, i64, i64, vp],
         "gnnmp_lstm_pointwise_grad_f32": [ctypes.POINTER(LstmGradJob), i64, i64, vp],
+        "gnnmp_poly_hop_f32": [vp, ctypes.POINTER(PolyHopJob), i64, vp],
+        "gnnmp_gru_pointwise_grad_f32": [ctypes.POINTER(GruGradJob), i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

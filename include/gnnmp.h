@@ -36,7 +36,9 @@
  *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
  *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py) and gnnmp_megnet_edge_f32 / gnnmp_megnet_edge_grad_f32 /
  *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py) and gnnmp_segment_attn_pool_f32 / gnnmp_segment_attn_pool_grad_f32 /
- *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py) and
+ *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
+ *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1644,6 +1646,83 @@ typedef struct {
     float *dc;               /* [N][D] */
 } gnnmp_lstm_grad_t;
 int gnnmp_lstm_pointwise_grad_f32(const gnnmp_lstm_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The polynomial layers and the GRU cell, forward and pullback (csrc/poly_conv.hip) — what cheb_conv, GNNlib/src/layers/conv.jl:83-98,
+ * d_conv, conv.jl:696-724, and gated_graph_conv, conv.jl:218-233, need beyond the existing exports to train.
+ *
+ *   gnnmp_poly_hop_f32   one step of a three-term recurrence over a plan, in one launch.  Row i of the plan, its slots k in plan order:
+ *                            agg_i = Σ_k w_slot[k] * (z[col[k]] * ss_slot[k])          from 0, slot by slot; a NULL factor is left out
+ *                            agg_i = agg_i * scale_dst[i]                              when scale_dst is given
+ *                            out_i = alpha * agg_i
+ *                            out_i = out_i + beta * self_i                             when self is given
+ *                            out_i = out_i + gamma * prev_i                            when prev is given
+ *                            out_i = out_i + add_i                                     when add is given
+ *                        IN THIS ORDER, every product and every sum rounded on its own: the library is built with -ffp-contract=off and
+ *                        the kernel has no fmaf, so no two of these steps are contracted.  w_slot and ss_slot mean what they mean in
+ *                        gnnmp_propagate_slots_f32 (gnnmp_plan_slot_gather_f32 makes them) and the per-slot factor and the fold are
+ *                        that export's expressions: with alpha = 1 and no self, prev or add, out has ITS BITS on every row the plan does
+ *                        not split (1 * agg is agg).  A row without slots gets the epilogue of agg = 0.
+ *                        cheb_conv's order k >= 3 is alpha = -4/λ, beta = 2 (2/λ - 1), gamma = -1 with self = Z_{k-1}, prev = Z_{k-2};
+ *                        d_conv's `2 * step - T0` is alpha = 2, gamma = -1, prev = T0; over the transposed plan, with add = G_k, the same
+ *                        call is a step of the pullback (Clenshaw: B_k = G_k + 2 L̃ᵀ B_{k+1} - B_{k+2}).
+ *   gnnmp_gru_pointwise_grad_f32   pullback of gnnmp_gru_pointwise_f32: with a_r = gx_r + gh_r + b_r, a_z = gx_z + gh_z + b_z,
+ *                        r = σ(a_r), z = σ(a_z), h~ = tanhf(gx_n + r * gh_n + b_n) recomputed by its expressions (its additions, in its
+ *                        order) and Δ = dout:
+ *                            dh     = base + Δ z                         (Δ z alone without base)
+ *                            dz_pre = (Δ (h - h~)) (z (1 - z))
+ *                            dn_pre = (Δ (1 - z)) (1 - h~ h~)
+ *                            dr_pre = (dn_pre gh_n) (r (1 - r))
+ *                            dgx = (dr_pre, dz_pre, dn_pre),   dgh = (dr_pre, dz_pre, dn_pre r)        gate order r, z, candidate
+ *                        dgx is the cotangent of gx = Wi m, dgh that of gh = Wh h; colsum(dgx) is that of b.  dh is only the DIRECT
+ *                        term of h: the caller adds dgh Wh.
+ *
+ *   plan     any plan (rows = n_dst destinations, z has n_src rows); only READ, its chunks are ignored; no eid is read, so a plan built
+ *            with self loops of its own is taken (their w_slot entry is 1, as gnnmp_plan_slot_gather_f32 writes it).
+ *   job      a const HOST record of device pointers and scalars:
+ *              gnnmp_poly_hop_t   z [n_src][D]: read; w_slot, ss_slot [n_total] (plan slot order), scale_dst [n_dst], self, prev, add
+ *                                 [n_dst][D]: read, each may be NULL; alpha, beta, gamma; out [n_dst][D]: every element written.
+ *                                 out MAY BE prev OR add (each element is read by the lane that then writes it); out may NOT be z or
+ *                                 self (z is gathered by other lanes; cheb_conv passes one array as both).  A term is applied when its
+ *                                 pointer is given, whatever its coefficient.
+ *              gnnmp_gru_grad_t   gx, gh [N][3D], b [3D] or NULL, h [N][D] (the state that ENTERED the cell), dout [N][D]: read; base
+ *                                 [N][D] or NULL, MAY BE dh; dgx, dgh [N][3D], dh [N][D]: every element written
+ *            Outputs must not overlap the inputs or each other beyond what is said above.
+ *   D        the hop: 1 .. 2^19; any 4-byte aligned pointers: 16- / 8-byte lanes when D % 4 / D % 2 == 0 and z, self, prev, add and out are
+ *            aligned alike, 4-byte lanes otherwise; lanes run over the features (a second feature tile beyond 64 lanes), a row's slots
+ *            are folded sequentially in plan order.  The GRU pullback: 1 .. 2^20, one thread an element.
+ * Both only launch on `stream`: no atomics, no allocation, no host wait, no scratch, nothing owned by a plan written; each may be
+ * recorded into a HIP graph without an eager call first; two calls give equal bits.  n_dst = 0 / N = 0 launches nothing and returns
+ * GNNMP_OK.  EVERY ROW IS WALKED WHOLE BY ONE LANE GROUP, whatever its length: correct, and slow for hub rows (where
+ * gnnmp_propagate_slots_f32 splits them).
+ * Refused before any HIP call (GNNMP_EINVAL), each message naming its export: a NULL plan or job; a NULL z or out; D outside its range;
+ * out == z or out == self; beta != 0 with a NULL self, gamma != 0 with a NULL prev; a NULL gx, gh, h, dout, dgx, dgh or dh; a negative N.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *z;          /* [n_src][D] */
+    const float *w_slot;     /* [n_total], plan slot order, or NULL */
+    const float *ss_slot;    /* [n_total], plan slot order, or NULL */
+    const float *scale_dst;  /* [n_dst] or NULL */
+    const float *self;       /* [n_dst][D] or NULL */
+    const float *prev;       /* [n_dst][D] or NULL; may be out */
+    const float *add;        /* [n_dst][D] or NULL; may be out */
+    float alpha, beta, gamma;
+    float *out;              /* [n_dst][D] */
+} gnnmp_poly_hop_t;
+int gnnmp_poly_hop_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_t *job, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *gx;         /* [N][3D] */
+    const float *gh;         /* [N][3D] */
+    const float *b;          /* [3D] or NULL */
+    const float *h;          /* [N][D]: the state that entered the cell */
+    const float *dout;       /* [N][D]: cotangent of h' */
+    const float *base;       /* [N][D] or NULL; may be dh */
+    float *dgx;              /* [N][3D] */
+    float *dgh;              /* [N][3D] */
+    float *dh;               /* [N][D] */
+} gnnmp_gru_grad_t;
+int gnnmp_gru_pointwise_grad_f32(const gnnmp_gru_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
