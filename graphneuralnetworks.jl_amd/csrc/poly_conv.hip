@@ -7,6 +7,9 @@
 //                              so the aggregate has gnnmp_propagate_slots_f32's bits on every row that export does not split.
 //   gru_pointwise_grad_kernel  pullback of gru_pointwise_kernel (leaf.hip), the cell of gated_graph_conv (conv.jl:218-233): r, z, h~ by the
 //                              forward's expressions, then the chain rule term by term.  Elementwise.
+// gnnmp_poly_hop_ld_f32 launches the SAME template with a row stride of its own for each of z, self, prev, add and out, so that the basis
+// of a recurrent cell's state lands in the column blocks of one panel [N][B D] (gnnmp/layers_temporal.py); gnnmp_poly_hop_f32 passes D
+// five times and keeps its bits.
 // The hop is a whole-row walk on the shared pieces and conventions of slotwalk.h (no atomics, every output written once, a hub row by one
 // lane group: correct, slow).  It reads col only, never eid: a plan with self loops of its own is fine.
 //
@@ -30,6 +33,7 @@ struct PolyHopArgs {
     float alpha, beta, gamma;
     float *out;                  // [n_dst][D]
     int D;
+    int64_t ldz, lds, ldp, lda, ldo;      // row strides in floats of z, self_, prev, add, out: all D for gnnmp_poly_hop_f32, a panel's for _ld
 };
 
 template <int VEC, int U, bool SCALED>
@@ -38,7 +42,6 @@ __global__ void __launch_bounds__(256) poly_hop_kernel(const PolyHopArgs a) {
     if (!decode_row_lane<VEC>(a.rows, a.geom, a.D, w)) return;
     const int f0 = w.f0;
     const bool active = w.active;
-    const int64_t ld = a.D;
     float acc[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
@@ -62,7 +65,7 @@ __global__ void __launch_bounds__(256) poly_hop_kernel(const PolyHopArgs a) {
                 bcast_word<SCALED ? U : 1>(sv, s.n, w.gbase, j, sj);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) load_or_zero<VEC>(active, a.z + (int64_t)cjs[u] * ld + f0, v[u]);
+            for (int u = 0; u < U; ++u) load_or_zero<VEC>(active, a.z + (int64_t)cjs[u] * a.ldz + f0, v[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (j + u < s.n) {
@@ -85,26 +88,25 @@ __global__ void __launch_bounds__(256) poly_hop_kernel(const PolyHopArgs a) {
 #pragma unroll
         for (int q = 0; q < VEC; ++q) acc[q] = acc[q] * sc;
     }
-    const int64_t o = (int64_t)w.row * ld + f0;
     float r[VEC], t[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) r[q] = a.alpha * acc[q];
     if (a.self_) {
-        Vec<VEC>::load(a.self_ + o, t);
+        Vec<VEC>::load(a.self_ + (int64_t)w.row * a.lds + f0, t);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.beta * t[q];
     }
     if (a.prev) {
-        Vec<VEC>::load(a.prev + o, t);
+        Vec<VEC>::load(a.prev + (int64_t)w.row * a.ldp + f0, t);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.gamma * t[q];
     }
     if (a.add) {
-        Vec<VEC>::load(a.add + o, t);
+        Vec<VEC>::load(a.add + (int64_t)w.row * a.lda + f0, t);
 #pragma unroll
         for (int q = 0; q < VEC; ++q) r[q] = r[q] + t[q];
     }
-    Vec<VEC>::store(a.out + o, r);      // after every load of this lane: out may be prev or add
+    Vec<VEC>::store(a.out + (int64_t)w.row * a.ldo + f0, r);      // after every load of this lane: out may be prev or add
 }
 
 // dh may be base: each element is read, then written, by one thread (no __restrict__ on the two)
@@ -145,6 +147,41 @@ __global__ void __launch_bounds__(256) gru_pointwise_grad_kernel(const float *__
 
 using namespace gnnmp;
 
+namespace gnnmp {
+namespace {
+
+// the launch both hop exports share: `a` is complete but for rows / geom; align_extra carries the row strides' bytes into the lane-width choice
+int launch_poly_hop(const char *who, const gnnmp_graph_t *plan, PolyHopArgs &a, bool scaled, uintptr_t align_extra, hipStream_t stream) {
+    a.rows = plan_rows_whole(plan);
+    dim3 grid;
+    const int vec = row_walk_geom(who, a.rows, a.D, 0, {a.z, a.self_, a.prev, a.add, a.out}, a.geom, grid, align_extra);
+    if (vec < 0) return vec;
+    with_vec(vec, [&](auto V) {
+        if (scaled)
+            poly_hop_kernel<decltype(V)::value, 4, true><<<grid, 256, 0, stream>>>(a);
+        else
+            poly_hop_kernel<decltype(V)::value, 4, false><<<grid, 256, 0, stream>>>(a);
+    });
+    GNNMP_LAUNCH_CHECK("poly_hop_kernel");
+    return GNNMP_OK;
+}
+
+// do the blocks p (rows_p rows of D floats, row stride ldp) and q share an element?  Equal strides: two column blocks of one panel are
+// disjoint when their column ranges are; different strides: whether the two spans meet at all (conservative).
+bool blocks_overlap(const float *p, int64_t ldp, int64_t rows_p, const float *q, int64_t ldq, int64_t rows_q, int64_t D) {
+    if (!p || !q || rows_p < 1 || rows_q < 1) return false;
+    const intptr_t pb = (intptr_t)reinterpret_cast<uintptr_t>(p), qb = (intptr_t)reinterpret_cast<uintptr_t>(q);
+    const intptr_t pe = pb + (intptr_t)(((rows_p - 1) * ldp + D) * 4), qe = qb + (intptr_t)(((rows_q - 1) * ldq + D) * 4);
+    if (pe <= qb || qe <= pb) return false;
+    if (ldp != ldq) return true;
+    const intptr_t ldb = (intptr_t)ldp * 4, Db = (intptr_t)D * 4;
+    const intptr_t r = (((qb - pb) % ldb) + ldb) % ldb;      // q's column offset from p's inside a row, in bytes
+    return r < Db || r > ldb - Db;
+}
+
+}  // namespace
+}  // namespace gnnmp
+
 extern "C" int gnnmp_poly_hop_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_t *job, int64_t D, gnnmp_stream_t stream) {
     const char *who = "poly_hop";
     if (!plan) return fail(GNNMP_EINVAL, "%s: null plan", who);
@@ -158,7 +195,6 @@ extern "C" int gnnmp_poly_hop_f32(const gnnmp_graph_t *plan, const gnnmp_poly_ho
     if (job->gamma != 0.0f && !job->prev) return fail(GNNMP_EINVAL, "%s: gamma != 0 with a null prev", who);
     if (plan->n_dst == 0) return GNNMP_OK;
     PolyHopArgs a = {};
-    a.rows = plan_rows_whole(plan);
     a.z = job->z;
     a.w_slot = job->w_slot;
     a.ss_slot = job->ss_slot;
@@ -171,18 +207,60 @@ extern "C" int gnnmp_poly_hop_f32(const gnnmp_graph_t *plan, const gnnmp_poly_ho
     a.gamma = job->gamma;
     a.out = job->out;
     a.D = (int)D;
-    dim3 grid;
-    const int vec = row_walk_geom(who, a.rows, D, 0, {job->z, job->self, job->prev, job->add, job->out}, a.geom, grid);
-    if (vec < 0) return vec;
-    const bool scaled = job->w_slot || job->ss_slot;
-    with_vec(vec, [&](auto V) {
-        if (scaled)
-            poly_hop_kernel<decltype(V)::value, 4, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-        else
-            poly_hop_kernel<decltype(V)::value, 4, false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    });
-    GNNMP_LAUNCH_CHECK("poly_hop_kernel");
-    return GNNMP_OK;
+    a.ldz = a.lds = a.ldp = a.lda = a.ldo = D;
+    return launch_poly_hop(who, plan, a, job->w_slot || job->ss_slot, 0, (hipStream_t)stream);
+}
+
+extern "C" int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, gnnmp_stream_t stream) {
+    const char *who = "poly_hop_ld";
+    if (!plan) return fail(GNNMP_EINVAL, "%s: null plan", who);
+    if (!job) return fail(GNNMP_EINVAL, "%s: null job", who);
+    if (!job->z) return fail(GNNMP_EINVAL, "%s: null z", who);
+    if (!job->out) return fail(GNNMP_EINVAL, "%s: null out", who);
+    if (D < 1 || D > (1 << 19)) return fail(GNNMP_EINVAL, "%s: bad D %lld (1 .. 2^19)", who, (long long)D);
+    if (job->ld_z < D) return fail(GNNMP_EINVAL, "%s: ld_z %lld below D", who, (long long)job->ld_z);
+    if (job->ld_out < D) return fail(GNNMP_EINVAL, "%s: ld_out %lld below D", who, (long long)job->ld_out);
+    if (job->self && job->ld_self < D) return fail(GNNMP_EINVAL, "%s: ld_self %lld below D", who, (long long)job->ld_self);
+    if (job->prev && job->ld_prev < D) return fail(GNNMP_EINVAL, "%s: ld_prev %lld below D", who, (long long)job->ld_prev);
+    if (job->add && job->ld_add < D) return fail(GNNMP_EINVAL, "%s: ld_add %lld below D", who, (long long)job->ld_add);
+    const int64_t ld_max = (int64_t)1 << 40;
+    if (job->ld_z > ld_max || job->ld_out > ld_max || (job->self && job->ld_self > ld_max) || (job->prev && job->ld_prev > ld_max) ||
+        (job->add && job->ld_add > ld_max))
+        return fail(GNNMP_EINVAL, "%s: a row stride above 2^40", who);
+    if (blocks_overlap(job->out, job->ld_out, plan->n_dst, job->z, job->ld_z, plan->n_src, D))
+        return fail(GNNMP_EINVAL, "%s: out overlaps z (other lanes gather it)", who);
+    if (blocks_overlap(job->out, job->ld_out, plan->n_dst, job->self, job->ld_self, plan->n_dst, D))
+        return fail(GNNMP_EINVAL, "%s: out overlaps self", who);
+    if (!(job->out == job->prev && job->ld_out == job->ld_prev) &&
+        blocks_overlap(job->out, job->ld_out, plan->n_dst, job->prev, job->ld_prev, plan->n_dst, D))
+        return fail(GNNMP_EINVAL, "%s: out overlaps prev without being it (same pointer, same stride)", who);
+    if (!(job->out == job->add && job->ld_out == job->ld_add) &&
+        blocks_overlap(job->out, job->ld_out, plan->n_dst, job->add, job->ld_add, plan->n_dst, D))
+        return fail(GNNMP_EINVAL, "%s: out overlaps add without being it (same pointer, same stride)", who);
+    if (job->beta != 0.0f && !job->self) return fail(GNNMP_EINVAL, "%s: beta != 0 with a null self", who);
+    if (job->gamma != 0.0f && !job->prev) return fail(GNNMP_EINVAL, "%s: gamma != 0 with a null prev", who);
+    if (plan->n_dst == 0) return GNNMP_OK;
+    PolyHopArgs a = {};
+    a.z = job->z;
+    a.w_slot = job->w_slot;
+    a.ss_slot = job->ss_slot;
+    a.sd = job->scale_dst;
+    a.self_ = job->self;
+    a.prev = job->prev;
+    a.add = job->add;
+    a.alpha = job->alpha;
+    a.beta = job->beta;
+    a.gamma = job->gamma;
+    a.out = job->out;
+    a.D = (int)D;
+    a.ldz = job->ld_z;
+    a.ldo = job->ld_out;
+    a.lds = job->self ? job->ld_self : D;
+    a.ldp = job->prev ? job->ld_prev : D;
+    a.lda = job->add ? job->ld_add : D;
+    // a lane's 16- / 8-byte access at row i is aligned when the base and the stride's bytes are: fold the strides into the alignment word
+    const uintptr_t strides = (uintptr_t)(a.ldz | a.ldo | a.lds | a.ldp | a.lda) * 4;
+    return launch_poly_hop(who, plan, a, job->w_slot || job->ss_slot, strides, (hipStream_t)stream);
 }
 
 extern "C" int gnnmp_gru_pointwise_grad_f32(const gnnmp_gru_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream) {

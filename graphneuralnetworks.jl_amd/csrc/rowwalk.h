@@ -99,10 +99,11 @@ inline int row_walk_grid(const char *who, const PlanRows &r, RowGeom &g, int til
 // The geometry of a row walk with one lane group a row and vec floats of `width` a lane.  Returns vec — the widest Vec<vec> access
 // that every array of `arrays` admits (a null one admits any) — or a failure (< 0); fills g (4 waves a block) and the grid over `tiles`
 // feature tiles (0: feature_tiles of the width).  Column k * width inside a row (the planar [n][2C] and [n][K C] matrices) needs no
-// entry of its own: width % vec == 0, so it is aligned whenever the row is.
+// entry of its own: width % vec == 0, so it is aligned whenever the row is.  align_extra: further bits that must be aligned like the
+// pointers — the byte row strides of arrays whose rows are not `width` apart (the panel hop).
 inline int row_walk_geom(const char *who, const PlanRows &r, int64_t width, int tiles, std::initializer_list<const float *> arrays,
-                         RowGeom &g, dim3 &grid) {
-    uintptr_t align = 0;
+                         RowGeom &g, dim3 &grid, uintptr_t align_extra = 0) {
+    uintptr_t align = align_extra;
     for (const float *p : arrays) align |= reinterpret_cast<uintptr_t>(p);
     const int vec = pick_vec(width, reinterpret_cast<const void *>(align), nullptr);
     g = RowGeom{pick_log2g((width + vec - 1) / vec), 4, 0, 0};

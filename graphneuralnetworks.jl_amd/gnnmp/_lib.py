@@ -61,6 +61,7 @@ SYMBOLS = (
     "gnnmp_megnet_edge_f32", "gnnmp_megnet_edge_grad_f32", "gnnmp_aggregate_grad_f32",
     "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
+    "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -242,6 +243,43 @@ class GruGradJob(ctypes.Structure):
                 ("base", ctypes.c_void_p), ("dgx", ctypes.c_void_p), ("dgh", ctypes.c_void_p), ("dh", ctypes.c_void_p)]
 
 
+class PolyHopLdJob(ctypes.Structure):
+    """gnnmp_poly_hop_ld_t: one gnnmp_poly_hop_ld_f32 call — PolyHopJob's fields, then a row stride in floats for z, self, prev, add, out"""
+    _fields_ = PolyHopJob._fields_ + [("ld_z", ctypes.c_int64), ("ld_self", ctypes.c_int64), ("ld_prev", ctypes.c_int64),
+                                      ("ld_add", ctypes.c_int64), ("ld_out", ctypes.c_int64)]
+
+
+class GruCellJob(ctypes.Structure):
+    """gnnmp_gru_cell_t: one gnnmp_gru_cell_f32 call (P, a, h | None read; gates, hout (| None in phase 1), y written)"""
+    _fields_ = [("P", ctypes.c_void_p), ("a", ctypes.c_void_p), ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("gates", ctypes.c_void_p),
+                ("hout", ctypes.c_void_p), ("ldhout", ctypes.c_int64), ("rep", ctypes.c_int), ("y", ctypes.c_void_p)]
+
+
+class GruCellGradJob(ctypes.Structure):
+    """gnnmp_gru_cell_grad_t: one gnnmp_gru_cell_grad_f32 call (dy, carry | None, carry2 | None, gates, h | None, drh read; dP, dac, darz,
+    part written)"""
+    _fields_ = [("dy", ctypes.c_void_p), ("carry", ctypes.c_void_p), ("carry2", ctypes.c_void_p), ("ldc2", ctypes.c_int64),
+                ("gates", ctypes.c_void_p), ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("drh", ctypes.c_void_p),
+                ("lddrh", ctypes.c_int64), ("rep", ctypes.c_int), ("dP", ctypes.c_void_p), ("dac", ctypes.c_void_p),
+                ("darz", ctypes.c_void_p), ("part", ctypes.c_void_p)]
+
+
+class LstmCellJob(ctypes.Structure):
+    """gnnmp_lstm_cell_t: one gnnmp_lstm_cell_f32 call (P, a, w, c | None read; gates, cnew, hout | None, y written)"""
+    _fields_ = [("P", ctypes.c_void_p), ("a", ctypes.c_void_p), ("w", ctypes.c_void_p), ("c", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+                ("gates", ctypes.c_void_p), ("cnew", ctypes.c_void_p), ("hout", ctypes.c_void_p), ("ldhout", ctypes.c_int64),
+                ("y", ctypes.c_void_p)]
+
+
+class LstmCellGradJob(ctypes.Structure):
+    """gnnmp_lstm_cell_grad_t: one gnnmp_lstm_cell_grad_f32 call (dy, carry_h | None, carry_c | None, gates, w, c | None, cnew read; dP, da,
+    dc, peep | None written)"""
+    _fields_ = [("dy", ctypes.c_void_p), ("carry_h", ctypes.c_void_p), ("ldch", ctypes.c_int64), ("carry_c", ctypes.c_void_p),
+                ("gates", ctypes.c_void_p), ("w", ctypes.c_void_p), ("c", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+                ("cnew", ctypes.c_void_p), ("dP", ctypes.c_void_p), ("da", ctypes.c_void_p), ("dc", ctypes.c_void_p),
+                ("peep", ctypes.c_void_p)]
+
+
 class GnnmpError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libgnnmp status {status}: {msg}")
@@ -400,6 +438,11 @@ def load():
         "gnnmp_lstm_pointwise_grad_f32": [ctypes.POINTER(LstmGradJob), i64, i64, vp],
         "gnnmp_poly_hop_f32": [vp, ctypes.POINTER(PolyHopJob), i64, vp],
         "gnnmp_gru_pointwise_grad_f32": [ctypes.POINTER(GruGradJob), i64, i64, vp],
+        "gnnmp_poly_hop_ld_f32": [vp, ctypes.POINTER(PolyHopLdJob), i64, vp],
+        "gnnmp_gru_cell_f32": [i, ctypes.POINTER(GruCellJob), i64, i64, i64, i64, vp],
+        "gnnmp_gru_cell_grad_f32": [i, ctypes.POINTER(GruCellGradJob), i64, i64, i64, i64, vp],
+        "gnnmp_lstm_cell_f32": [ctypes.POINTER(LstmCellJob), i64, i64, i64, i64, vp],
+        "gnnmp_lstm_cell_grad_f32": [ctypes.POINTER(LstmCellGradJob), i64, i64, i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

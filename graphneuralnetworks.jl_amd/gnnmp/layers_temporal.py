@@ -1,4 +1,5 @@
-"""TGCN — the temporal graph convolution of GraphNeuralNetworks/src/layers/temporalconv.jl:
+"""The recurrent layers of GraphNeuralNetworks/src/layers/temporalconv.jl: TGCN, and — further down, with a header of their own —
+GConvGRU, GConvLSTM and DCGRU.
 
   TGCNCell       temporalconv.jl:809-849   conv_g = GNNChain(GCNConv(in => out, relu; kws...), GCNConv(out => out; kws...)) and
                                            dense_g = Dense(2out => out, σ | tanh) for g in z, r, h; one step
@@ -16,6 +17,8 @@ products and two pointwise launches per step.
 Weights keep the Julia shapes (GCNConv weight (out, in), Dense weight (out, 2out)); every arithmetic step is a libgnnmp call.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -83,9 +86,11 @@ class GNNRecurrence:
     def __call__(self, g, x, state=None):
         if isinstance(self.cell, TGCNCell):
             return tgcn_forward(self.cell, g, x, state)
-        ys, h = [], state
+        if isinstance(self.cell, (GConvGRUCell, GConvLSTMCell, DCGRUCell)):
+            return recurrent_forward(self.cell, g, x, state)[0]
+        ys = []
         for t in range(x.shape[1]):
-            h, yt = self.cell(g, x[:, t], h)
+            yt, state = self.cell(g, x[:, t], state)          # the reference's order: (output, state)
             ys.append(yt)
         return torch.stack(ys, 1)
 
@@ -209,6 +214,392 @@ def recurrence(P, Uzr, Uh, h0, h0_stride, need_gates=True):
                                         L.stream_ptr()))
         h = hn
     return y, gates
+
+
+# ---------------------------------------------------------------------------------------------------------
+# GConvGRU, GConvLSTM, DCGRU — temporalconv.jl:143-293, 297-477, 480-613
+#
+# The x side of every gate and every step depends on x only: its Chebyshev / diffusion basis is built ONCE at width T in (the time steps
+# are columns of [N][T in], as in TGCN's phase A) and one dense with the gate-stacked weights gives P [N][T][G out] with every bias
+# folded in.  Per step the basis of the state is built by gnnmp_poly_hop_ld_f32 straight into the column blocks of a panel [N][B out],
+# ONE dense over the panel with the gate-stacked weights follows, then one gate kernel (csrc/recurrent.hip), which writes h' (or r .* h)
+# into block 0 of the panel that is read next.  Launches per step: GConvGRU 2K + 2, GConvLSTM K + 1, DCGRU 4k + 4 (k = 1: 4).
+# Stacking weights is a copy made once per call, never arithmetic (the biases of one gate are added up: two or three [out] vectors).
+# ---------------------------------------------------------------------------------------------------------
+def _blk(panel, j, D):
+    return panel[:, j * D:(j + 1) * D]
+
+
+def poly_hop_ld(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=0.0, self_=None, gamma=0.0, prev=None, add=None, out=None):
+    """gnnmp_poly_hop_ld_f32 on column blocks: every operand a [rows][D] view whose last stride is 1 (its row stride is the panel's);
+    out may be prev or add (the same view), never z or self_"""
+    D = z.shape[1]
+    if plan.n_dst == 0 or D == 0:
+        return out
+    ops = (z, self_, prev, add, out)
+    assert all(o is None or (o.dim() == 2 and o.shape[1] == D and (o.stride(1) == 1 or D == 1) and o.dtype == torch.float32) for o in ops)
+    ld = [D if o is None else (o.stride(0) if o.shape[0] > 1 else max(o.stride(0), D)) for o in ops]
+    job = L.PolyHopLdJob(L.ptr(z), L.ptr(w_slot), L.ptr(ss_slot), L.ptr(scale_dst), L.ptr(self_), L.ptr(prev), L.ptr(add), float(alpha),
+                         float(beta), float(gamma), L.ptr(out), ld[0], ld[1], ld[2], ld[3], ld[4])
+    L.check(L.load().gnnmp_poly_hop_ld_f32(plan.handle, ctypes.byref(job), D, L.stream_ptr()))
+    return out
+
+
+class ChebBasis:
+    """the Chebyshev basis of cheb_conv (conv.jl:83-98) on panels: block k of [N][K D] holds Z_{k+1}; `rep` = 1 (the state is block 0)"""
+
+    rep = 1
+
+    def __init__(self, g, K):
+        from .backward import plan_transposed
+        from .backward_poly import _slot_factors
+        from .layers_more import scaled_laplacian_op
+        self.K = self.B = K
+        self.c, self.ss, self.ws, lam = scaled_laplacian_op(g)
+        self.a, self.b = 2.0 / lam, 2.0 / lam - 1.0
+        self.plan = g.plan(False)
+        self.g, self._t, self._pt, self._sf = g, None, plan_transposed, _slot_factors
+
+    def build(self, panel, D):
+        """blocks 1 .. K - 1 from block 0: K - 1 launches"""
+        a, b = self.a, self.b
+        for k in range(1, self.K):
+            z = _blk(panel, k - 1, D)
+            if k == 1:
+                poly_hop_ld(self.plan, z, -a, self.ws, self.ss, self.c, b, z, out=_blk(panel, 1, D))
+            else:
+                poly_hop_ld(self.plan, z, -2.0 * a, self.ws, self.ss, self.c, 2.0 * b, z, -1.0, _blk(panel, k - 2, D), out=_blk(panel, k, D))
+
+    def pullback(self, G, D):
+        """Clenshaw over the transposed plan, in place on the panel's cotangent (block k = G_{k+1}): afterwards block 0 is the cotangent
+        of the state.  K - 1 launches."""
+        if self.K == 1:
+            return
+        if self._t is None:
+            pt = self._pt(self.g, False)
+            self._t = (pt,) + tuple(self._sf(self.g, pt, "cheb_t", self.c))
+        pt, sst, wst = self._t
+        a, b = self.a, self.b
+        for k in range(self.K - 1, 0, -1):                 # 1-based order k: G_k is block k - 1, B_{k+1} block k, B_{k+2} block k + 1
+            z = _blk(G, k, D)
+            prev = _blk(G, k + 1, D) if k + 1 < self.K else None
+            two = 2.0 if k >= 2 else 1.0
+            tgt = _blk(G, k - 1, D)
+            poly_hop_ld(pt, z, -two * a, wst, sst, self.c, two * b, z, -1.0 if prev is not None else 0.0, prev, tgt, out=tgt)
+
+    def block_slices(self):
+        """the weight slice (a ChebConv's order) of each block"""
+        return list(range(self.K))
+
+
+class DiffusionBasis:
+    """the diffusion basis of d_conv (conv.jl:696-724) on panels: DConv reads T_0 with one weight slice a direction, so the state is held
+    in blocks 0 AND 1 (`rep` = 2); for k >= 2 the k terms T_1 .. T_k of direction 0 (the steps over gᵀ) follow in blocks 2 .., then those
+    of direction 1.  T_0 is never advanced and weight slice 1 is read twice (d_conv_ad: _dconv_slices): the stacked weight repeats it."""
+
+    rep = 2
+
+    def __init__(self, g, k):
+        from .backward_poly import _dconv_ops, _dconv_slices
+        self.k = k
+        self.B = 2 if k == 1 else 2 + 2 * k
+        self.fwd, self.adj = _dconv_ops(g)
+        self.idx = _dconv_slices(k)
+
+    def _term(self, d, j):
+        return 2 + d * self.k + (j - 1)
+
+    def build(self, panel, D):
+        """2k launches (k = 1: none)"""
+        if self.k == 1:
+            return
+        t0 = _blk(panel, 0, D)
+        for d in (0, 1):
+            plan, ws, ss = self.fwd[d]
+            poly_hop_ld(plan, t0, 1.0, ws, ss, out=_blk(panel, self._term(d, 1), D))
+            for j in range(2, self.k + 1):
+                poly_hop_ld(plan, _blk(panel, self._term(d, j - 1), D), 2.0, ws, ss, gamma=-1.0, prev=t0, out=_blk(panel, self._term(d, j), D))
+
+    def pullback(self, G, D):
+        """the adjoint recurrence of d_conv_ad in place: afterwards blocks 0 + 1 are the cotangent of the state.  2k launches, and for
+        k >= 3 one gnnmp_add_f32 per further order and direction (Σ_{j >= 2} C_j, what the `- T_0` terms send back)."""
+        if self.k == 1:
+            return
+        from .layers_more import _add
+        t0 = _blk(G, 0, D)
+        for d in (0, 1):
+            plan, ws, sd = self.adj[d]
+            C = _blk(G, self._term(d, self.k), D)
+            R = None
+            for j in range(self.k - 1, 0, -1):
+                R = C if R is None else _add(R.contiguous(), C.contiguous())
+                Gj = _blk(G, self._term(d, j), D)
+                C = poly_hop_ld(plan, C, 2.0, ws, None, sd, add=Gj, out=Gj)
+            poly_hop_ld(plan, C, 1.0, ws, None, sd, gamma=-1.0 if R is not None else 0.0, prev=R, add=t0, out=t0)
+
+    def block_slices(self):
+        """(direction, weight slice) of each block"""
+        out = [(0, 0), (1, 0)]
+        if self.k > 1:
+            out += [(d, self.idx[j]) for d in (0, 1) for j in range(1, self.k + 1)]
+        return out
+
+
+def _check_cell_args(name, ch, k):
+    cin, out = ch
+    if int(cin) < 1 or int(out) < 1:
+        raise ValueError(f"{name}: channels must be positive, got {cin} => {out}")
+    if int(k) < 1:
+        raise ValueError(f"{name}: k must be at least 1, got {k}")
+    return int(cin), int(out), int(k)
+
+
+class GConvGRUCell:
+    """GConvGRUCell(in => out, k; bias = true) — temporalconv.jl:143-259.  Fields as in the reference: conv_x_r, conv_h_r, conv_x_z,
+    conv_h_z, conv_x_h, conv_h_h (gnnmp.ChebConv), k, in_, out.  cell(g, x [N, in], h = None) -> (h', h'); a state is None
+    (initialstates: zeros), [out] (repeated over the nodes) or [N, out]."""
+
+    takes_graph = True
+    gates = ("r", "z", "h")
+
+    def __init__(self, ch, k, bias=True, device="cuda", seed=None):
+        from .layers_more import ChebConv
+        cin, out, k = _check_cell_args("GConvGRUCell", ch, k)
+        s = 0 if seed is None else int(seed)
+        self.in_, self.out, self.k = cin, out, k
+        for j, n in enumerate(self.gates):
+            setattr(self, "conv_x_" + n, ChebConv((cin, out), k, bias=bias, device=device, seed=s + 100 * j + 1))
+            setattr(self, "conv_h_" + n, ChebConv((out, out), k, bias=bias, device=device, seed=s + 100 * j + 51))
+
+    def parameters(self):
+        """12 tensors in gconv_gru_ad's order: per gate r, z, h — conv_x (weight, bias), conv_h (weight, bias); a bias is None with
+        bias = false"""
+        out = []
+        for n in self.gates:
+            cx, chh = getattr(self, "conv_x_" + n), getattr(self, "conv_h_" + n)
+            out += [cx.weight, cx.bias, chh.weight, chh.bias]
+        return out
+
+    def initialstates(self, device=None):
+        return torch.zeros(self.out, dtype=torch.float32, device=device or self.conv_x_r.weight.device)
+
+    def __call__(self, g, x, state=None):
+        _, h, _, _ = recurrent_forward(self, g, x.reshape(x.shape[0], 1, x.shape[-1]), state)
+        return h, h
+
+
+class GConvLSTMCell:
+    """GConvLSTMCell(in => out, k; bias = true) — temporalconv.jl:297-442.  Fields as in the reference: conv_x_g, conv_h_g
+    (gnnmp.ChebConv), w_g [out] (the peephole, Julia (out, 1)) and b_g [out] (None with bias = false) for g in i, f, c, o; k, in_, out.
+    cell(g, x [N, in], (h, c) = None) -> (h', (h', c')); h and c are each None, [out] or [N, out]."""
+
+    takes_graph = True
+    gates = ("i", "f", "c", "o")
+
+    def __init__(self, ch, k, bias=True, device="cuda", seed=None):
+        from .layers import glorot_uniform
+        from .layers_more import ChebConv
+        cin, out, k = _check_cell_args("GConvLSTMCell", ch, k)
+        s = 0 if seed is None else int(seed)
+        self.in_, self.out, self.k = cin, out, k
+        for j, n in enumerate(self.gates):
+            setattr(self, "conv_x_" + n, ChebConv((cin, out), k, bias=bias, device=device, seed=s + 100 * j + 1))
+            setattr(self, "conv_h_" + n, ChebConv((out, out), k, bias=bias, device=device, seed=s + 100 * j + 51))
+            setattr(self, "w_" + n, glorot_uniform(out, 1, device=device, seed=s + 100 * j + 91).reshape(out).contiguous())
+            setattr(self, "b_" + n, torch.zeros(out, dtype=torch.float32, device=device) if bias else None)
+
+    def parameters(self):
+        """24 tensors in gconv_lstm_ad's order: per gate i, f, c, o — conv_x (weight, bias), conv_h (weight, bias), w, b"""
+        out = []
+        for n in self.gates:
+            cx, chh = getattr(self, "conv_x_" + n), getattr(self, "conv_h_" + n)
+            out += [cx.weight, cx.bias, chh.weight, chh.bias, getattr(self, "w_" + n), getattr(self, "b_" + n)]
+        return out
+
+    def initialstates(self, device=None):
+        z = torch.zeros(self.out, dtype=torch.float32, device=device or self.conv_x_i.weight.device)
+        return z, z.clone()
+
+    def __call__(self, g, x, state=None):
+        _, h, c, _ = recurrent_forward(self, g, x.reshape(x.shape[0], 1, x.shape[-1]), state)
+        return h, (h, c)
+
+
+class DCGRUCell:
+    """DCGRUCell(in => out, k; bias = true) — temporalconv.jl:480-579.  Fields as in the reference: in_, out, k, dconv_u, dconv_r,
+    dconv_c = gnnmp.DConv((in + out, out), k).  cell(g, x [N, in], h = None) -> (h', h')."""
+
+    takes_graph = True
+    gates = ("r", "u", "c")          # the kernels' order (r, z, c): u is the update gate z
+
+    def __init__(self, ch, k, bias=True, device="cuda", seed=None):
+        from .layers_more import DConv
+        cin, out, k = _check_cell_args("DCGRUCell", ch, k)
+        s = 0 if seed is None else int(seed)
+        self.in_, self.out, self.k = cin, out, k
+        for j, n in enumerate(("u", "r", "c")):
+            setattr(self, "dconv_" + n, DConv((cin + out, out), k, bias=bias, device=device, seed=s + 1000 * j + 1))
+
+    def parameters(self):
+        """6 tensors in dcgru_ad's order: dconv_u (weights, bias), dconv_r (weights, bias), dconv_c (weights, bias)"""
+        return [self.dconv_u.weights, self.dconv_u.bias, self.dconv_r.weights, self.dconv_r.bias, self.dconv_c.weights, self.dconv_c.bias]
+
+    def initialstates(self, device=None):
+        return torch.zeros(self.out, dtype=torch.float32, device=device or self.dconv_u.weights.device)
+
+    def __call__(self, g, x, state=None):
+        _, h, _, _ = recurrent_forward(self, g, x.reshape(x.shape[0], 1, x.shape[-1]), state)
+        return h, h
+
+
+def GConvGRU(ch, k, **kw):
+    """GConvGRU(in => out, k; kws...) = GNNRecurrence(GConvGRUCell(...)) — temporalconv.jl:293"""
+    return GNNRecurrence(GConvGRUCell(ch, k, **kw))
+
+
+def GConvLSTM(ch, k, **kw):
+    """GConvLSTM(in => out, k; kws...) = GNNRecurrence(GConvLSTMCell(...)) — temporalconv.jl:477"""
+    return GNNRecurrence(GConvLSTMCell(ch, k, **kw))
+
+
+def DCGRU(ch, k, **kw):
+    """DCGRU(in => out, k; kws...) = GNNRecurrence(DCGRUCell(...)) — temporalconv.jl:613"""
+    return GNNRecurrence(DCGRUCell(ch, k, **kw))
+
+
+def _sum_bias(bs):
+    """the biases of one gate added up (None with bias = false)"""
+    from .layers_more import _add
+    bs = [b for b in bs if b is not None]
+    if not bs:
+        return None
+    tot = bs[0]
+    for b in bs[1:]:
+        tot = _add(tot, b)
+    return tot
+
+
+def cell_basis(cell, g):
+    return DiffusionBasis(g, cell.k) if isinstance(cell, DCGRUCell) else ChebBasis(g, cell.k)
+
+
+def cell_stacked(cell, basis):
+    """(Wx [G out][B in], bias [G out] | None, Wh: list of state-side stacks [Gi out][B out]) — GRU cells: Wh = [r and z, candidate];
+    the LSTM: Wh = [all four gates].  Block b of a stack is the weight slice basis.block_slices()[b]: copies, no arithmetic."""
+    cin = cell.in_
+    sl = basis.block_slices()
+    wx, wh, bs = [], [], []
+    for n in cell.gates:
+        if isinstance(cell, DCGRUCell):
+            W = getattr(cell, "dconv_" + n).weights                                  # [2][k][out][in + out]
+            wx.append(torch.cat([W[d, i][:, :cin] for d, i in sl], 1))
+            wh.append(torch.cat([W[d, i][:, cin:] for d, i in sl], 1))
+            bs.append(getattr(cell, "dconv_" + n).bias)
+        else:
+            cx, chh = getattr(cell, "conv_x_" + n), getattr(cell, "conv_h_" + n)      # weight [K][out][*]
+            wx.append(torch.cat([cx.weight[i] for i in sl], 1))
+            wh.append(torch.cat([chh.weight[i] for i in sl], 1))
+            bs.append(_sum_bias([cx.bias, chh.bias, getattr(cell, "b_" + n, None)]))
+    Wx = torch.cat(wx).contiguous()
+    bias = None if bs[0] is None else torch.cat(bs).contiguous()
+    if isinstance(cell, GConvLSTMCell):
+        return Wx, bias, [torch.cat(wh).contiguous()]
+    return Wx, bias, [torch.cat(wh[:2]).contiguous(), wh[2].contiguous()]
+
+
+def x_side(basis, x, Wx, bias):
+    """P [N][T][G out] for all steps and the stacked basis Xb [N T][B in] it was made from: B - rep hops at width T in, one interleaving
+    copy, one dense — whatever T is"""
+    N, T, cin = x.shape
+    W = T * cin
+    Xp = torch.empty((N, basis.B * W), dtype=torch.float32, device=x.device)
+    for j in range(basis.rep):
+        _blk(Xp, j, W).copy_(x.reshape(N, W))
+    basis.build(Xp, W)
+    Xb = Xp.view(N, basis.B, T, cin).permute(0, 2, 1, 3).contiguous().view(N * T, basis.B * cin)
+    P = dense(Xb, Wx, bias)
+    return P.view(N, T, Wx.shape[0]), Xb
+
+
+def _fill_state(panel, h0, stride, rep, D):
+    for j in range(rep):
+        if h0 is None:
+            _blk(panel, j, D).zero_()
+        else:
+            _blk(panel, j, D).copy_(h0 if stride else h0.expand(panel.shape[0], D))
+
+
+def _at(t, offset_floats):
+    return ctypes.c_void_p(t.data_ptr() + 4 * offset_floats)
+
+
+def _check_recurrent_input(name, cell, g, x):
+    if isinstance(x, (tuple, list)):
+        raise NotImplementedError(f"{name}: a bipartite (xs, xt) input is not covered; pass one feature array")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name}: the HIP kernels are Float32; x is {x.dtype}")
+    if x.dim() != 3 or x.shape[2] != cell.in_:
+        raise ValueError(f"{name}: x must be [N][T][{cell.in_}] for this layer, not {tuple(x.shape)}")
+    check_num_nodes(g, x)
+
+
+def recurrent_forward(cell, g: GNNGraph, x, state=None, keep=False):
+    """(y [N, T, out], h_T [N, out], c_T | None) of GNNRecurrence(cell) for the three graph-convolutional cells; with `keep` also a dict of
+    what the pullback needs (gnnmp/backward_recurrent.py): the panels of all steps, time-major, the gates, the x basis"""
+    name = type(cell).__name__
+    _check_recurrent_input(name, cell, g, x)
+    N, T, _ = x.shape
+    D = cell.out
+    lstm = isinstance(cell, GConvLSTMCell)
+    hs, cs0 = (state if state is not None else (None, None)) if lstm else (state, None)
+    if lstm and state is not None and not (isinstance(state, (tuple, list)) and len(state) == 2):
+        raise ValueError(f"{name}: the state is a pair (h, c)")
+    h0, ldh0 = state_arg(hs, N, D, x.device)
+    c0, ldc0 = state_arg(cs0, N, D, x.device) if lstm else (None, D)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    basis = cell_basis(cell, g)
+    Wx, bias, Wh = cell_stacked(cell, basis)
+    P, Xb = x_side(basis, x.contiguous(), Wx, bias)
+    B, rep = basis.B, basis.rep
+    BD = B * D
+    lib = L.load()
+    G = 4 if lstm else 3
+    y = torch.empty((N, T, D), **f32)
+    gates = torch.empty((N, T, G * D), **f32)
+    n1 = T if keep else min(T, 2)
+    pan1 = torch.empty((n1, N, BD), **f32)                  # the basis of h_{t-1}: kept time-major for the weight gradients, else two
+    _fill_state(pan1[0], h0, ldh0, rep, D)
+    sv = dict(basis=basis, Wx=Wx, Wh=Wh, has_bias=bias is not None, Xb=Xb, gates=gates, pan1=pan1, h0=h0, ldh0=ldh0, c0=c0, ldc0=ldc0)
+    if lstm:
+        w = torch.stack([cell.w_i, cell.w_f, cell.w_c, cell.w_o]).contiguous()
+        cs = torch.empty((N, T, D), **f32)
+        sv.update(w=w, cs=cs)
+        for t in range(T):
+            p1 = pan1[t if keep else t % 2]
+            basis.build(p1, D)
+            a = dense(p1, Wh[0])
+            cp, ldc = (_at(cs, (t - 1) * D), T * D) if t > 0 else (L.ptr(c0), ldc0)
+            nxt = pan1[(t + 1) if keep else (t + 1) % 2] if t + 1 < T else None
+            job = L.LstmCellJob(L.ptr(P), L.ptr(a), L.ptr(w), cp, ldc, L.ptr(gates), L.ptr(cs), L.ptr(nxt), BD, L.ptr(y))
+            if N:
+                L.check(lib.gnnmp_lstm_cell_f32(ctypes.byref(job), N, T, t, D, L.stream_ptr()))
+        return y, y[:, T - 1], cs[:, T - 1], sv
+    pan2 = torch.empty((T if keep else 1, N, BD), **f32)    # the basis of r .* h_{t-1}
+    sv.update(pan2=pan2)
+    for t in range(T):
+        p1, p2 = pan1[t if keep else t % 2], pan2[t if keep else 0]
+        basis.build(p1, D)
+        a = dense(p1, Wh[0])
+        job = L.GruCellJob(L.ptr(P), L.ptr(a), L.ptr(p1), BD, L.ptr(gates), L.ptr(p2), BD, rep, None)
+        if N:
+            L.check(lib.gnnmp_gru_cell_f32(0, ctypes.byref(job), N, T, t, D, L.stream_ptr()))
+        basis.build(p2, D)
+        a = dense(p2, Wh[1])
+        nxt = pan1[(t + 1) if keep else (t + 1) % 2] if t + 1 < T else None
+        job = L.GruCellJob(L.ptr(P), L.ptr(a), L.ptr(p1), BD, L.ptr(gates), L.ptr(nxt), BD, rep, L.ptr(y))
+        if N:
+            L.check(lib.gnnmp_gru_cell_f32(1, ctypes.byref(job), N, T, t, D, L.stream_ptr()))
+    return y, y[:, T - 1], None, sv
 
 
 def tgcn_forward(cell, g: GNNGraph, x, state=None):

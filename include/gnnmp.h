@@ -38,7 +38,8 @@
  *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py) and gnnmp_segment_attn_pool_f32 / gnnmp_segment_attn_pool_grad_f32 /
  *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py) and
  *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
- *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
+ *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1723,6 +1724,148 @@ typedef struct {
     float *dh;               /* [N][D] */
 } gnnmp_gru_grad_t;
 int gnnmp_gru_pointwise_grad_f32(const gnnmp_gru_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The graph-convolutional recurrent cells (csrc/poly_conv.hip, csrc/recurrent.hip) — what GConvGRUCell, GConvLSTMCell and DCGRUCell
+ * (GraphNeuralNetworks/src/layers/temporalconv.jl:237-254, :416-437, :564-575) need beyond the existing exports: the hop on PANELS and the
+ * fused gate kernels, forward and pullback.  A step of a cell is: the Chebyshev / diffusion basis of the state written by the hop
+ * straight into the column blocks of one panel [N][B D]; ONE gnnmp_dense_f32 over the panel with the gate-stacked weights; one gate
+ * kernel, which writes the next state (or r .* h) into block 0 of the panel that is read next.
+ *
+ *   gnnmp_poly_hop_ld_f32   gnnmp_poly_hop_f32 with a row stride (in floats) for each of z, self, prev, add and out: the SAME kernel
+ *                        template, the arithmetic above in the same order, rounded the same way — with every stride = D it has
+ *                        gnnmp_poly_hop_f32's bits.  Row i of an operand starts at ptr + i * ld; D floats of it are used.
+ *                          - every stride of a given pointer is at least D (ld_z and ld_out always);
+ *                          - operands may be column blocks of one allocation; two distinct blocks of one panel do not overlap;
+ *                          - out MAY BE prev OR add, with the same pointer AND the same stride; out may NOT overlap z or self (nor
+ *                            prev or add in any other way).  Overlap of two blocks with equal strides is decided exactly (their byte
+ *                            spans meet and their column ranges inside a row meet); with different strides, by their byte spans;
+ *                          - lanes are 16 / 8 bytes wide only when D % 4 / D % 2 == 0 and EVERY given pointer and EVERY given stride
+ *                            (in bytes) is a multiple of 16 / 8; 4-byte lanes otherwise.
+ *                        Refused before any HIP call (GNNMP_EINVAL, "poly_hop_ld: ..."): everything gnnmp_poly_hop_f32 refuses, a stride
+ *                        below D (or above 2^40), the overlaps above.  n_dst = 0 returns GNNMP_OK.
+ *
+ *   The GRU cell (GConvGRU and DCGRU: `(1 .- z) .* h~ .+ z .* h` and `z .* h + (1 .- z) .* c` are one expression up to a commuted sum).
+ *   Gate order (r, z, c).  P [N][T][3D]: the x-side pre-activations of all steps with all biases; a: the state-side product of THIS
+ *   step, contiguous — [N][2D] in phase 0, [N][D] in phase 1; h: the state that entered the step, row stride ldh (0: one vector for every
+ *   node; NULL: zeros).  Every product and every sum rounded on its own; σ(x) = (t = expf(-|x|); x >= 0 ? 1 / (1 + t) : t / (1 + t)),
+ *   tanh = tanhf, as gnnmp_gru_pointwise_f32.
+ *   gnnmp_gru_cell_f32      phase 0:  r = σ(P_r[t] + a_r),  z = σ(P_z[t] + a_z)  -> gates[t] (slots r, z)
+ *                                     hout = r h                                   (row stride ldhout)
+ *                           phase 1:  c = tanhf(P_c[t] + a_c)                      -> gates[t] (slot c);  z is read from gates[t]
+ *                                     h' = (1 - z) c + z h                         -> y[n][t], and hout when it is given
+ *                           hout is written `rep` (1 or 2) times side by side: hout[n ldhout + j D + d], j < rep — DConv reads the state
+ *                           with two weight slices (one a direction), so its panel holds the state in blocks 0 AND 1.
+ *   gnnmp_gru_cell_grad_f32 phase 1:  Δ = dy[t] + carry + Σ_{j < rep} carry2_j     (carry [N][D] and carry2, row stride ldc2, nullable)
+ *                                     dc_pre = (Δ (1 - z)) (1 - c c)               -> dP[t] slot c and dac [N][D]
+ *                                     dz_pre = (Δ (h - c)) (z (1 - z))             -> dP[t] slot z and darz[:, D:2D]
+ *                                     part   = Δ z                                 -> part [N][D]
+ *                           phase 0:  q = Σ_{j < rep} drh_j                        (drh: row stride lddrh; the panel cotangent's block 0)
+ *                                     dr_pre = (q h) (r (1 - r))                   -> dP[t] slot r and darz[:, 0:D]
+ *                                     part   = part + q r
+ *                           dac [N][D] and darz [N][2D] are contiguous: what the next dense adjoint reads.  The cotangent of h is
+ *                           part + (block 0 of the cotangent of the phase-0 panel): the next (earlier) step takes the two as carry, carry2.
+ *
+ *   The peephole LSTM cell (GConvLSTM).  Gate order (i, f, c, o); w [4][D] the peepholes; P [N][T][4D]; a [N][4D]; c: the cell state
+ *   that entered, row stride ldc (0: one vector; NULL: zeros).
+ *   gnnmp_lstm_cell_f32       i = σ(P_i + a_i + w_i c),  f = σ(P_f + a_f + w_f c),  g = tanhf(P_c + a_c + w_c c),  c' = f c + i g,
+ *                             o = σ(P_o + a_o + w_o c'),  h' = o tanhf(c');   (P + a first, then + w c)
+ *                             gates[t] = (i, f, g, o) and cnew[n][t] = c' are kept for the pullback; h' -> y[n][t] and hout (row
+ *                             stride ldhout) when given.
+ *   gnnmp_lstm_cell_grad_f32  Δh = dy[t] + carry_h (row stride ldch; nullable),  th = tanhf(c')
+ *                             do_pre = (Δh th) (o (1 - o))
+ *                             Δc'    = (Δh o) (1 - th th) + carry_c + do_pre w_o          (carry_c [N][D], nullable)
+ *                             di_pre = (Δc' g) (i (1 - i)),  df_pre = (Δc' c) (f (1 - f)),  dg_pre = (Δc' i) (1 - g g)
+ *                             Δc     = Δc' f + di_pre w_i + df_pre w_f + dg_pre w_c        -> dc [N][D]
+ *                             (di, df, dg, do)_pre -> dP[t] and da [N][4D]; peep [N][T][4D] (nullable) gets (di_pre c, df_pre c,
+ *                             dg_pre c, do_pre c') at [t]: its column sums over all N T rows are the peepholes' gradients.
+ *
+ *   job    const HOST records of device pointers, strides and counts (below).  Outputs must not overlap inputs or each other.
+ *   N, T, t, D   N >= 0 (N = 0 launches nothing), 1 <= T <= 2^20, 0 <= t < T, N T <= 2^40, 1 <= D <= 2^20; one thread an element.
+ * All of them only launch on `stream`: no atomics, every output element written once by one lane, no allocation, no host wait, no
+ * scratch; each may be recorded into a HIP graph without an eager call first; two calls give equal bits.
+ * Refused before any HIP call (GNNMP_EINVAL), by name ("gru_cell: ...", "gru_cell_grad: ...", "lstm_cell: ...", "lstm_cell_grad: ..."): a
+ * NULL job; a phase other than 0 / 1; N, T, t, D outside their ranges; a NULL required pointer (gru_cell: P, a, gates, hout in phase 0, y
+ * in phase 1; gru_cell_grad: gates, dP, darz, part, dy and dac in phase 1, drh in phase 0; lstm_cell: P, a, w, gates, cnew, y;
+ * lstm_cell_grad: dy, gates, w, cnew, dP, da, dc); a state stride that is neither 0 nor at least D; rep outside {1, 2}; an output or
+ * addend stride below rep D (ldhout, ldc2, lddrh) or D (the LSTM's ldhout, ldch).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *z;          /* [n_src] rows of D, stride ld_z */
+    const float *w_slot;     /* [n_total], plan slot order, or NULL */
+    const float *ss_slot;    /* [n_total], plan slot order, or NULL */
+    const float *scale_dst;  /* [n_dst] or NULL */
+    const float *self;       /* [n_dst] rows of D, stride ld_self, or NULL */
+    const float *prev;       /* [n_dst] rows of D, stride ld_prev, or NULL; may be out (same stride) */
+    const float *add;        /* [n_dst] rows of D, stride ld_add, or NULL; may be out (same stride) */
+    float alpha, beta, gamma;
+    float *out;              /* [n_dst] rows of D, stride ld_out */
+    int64_t ld_z, ld_self, ld_prev, ld_add, ld_out;      /* row strides in floats; those of NULL operands are not read */
+} gnnmp_poly_hop_ld_t;
+int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *P;          /* [N][T][3D] */
+    const float *a;          /* phase 0: [N][2D] (r, z); phase 1: [N][D] */
+    const float *h;          /* rows of D, stride ldh (0: one vector), or NULL (zeros) */
+    int64_t ldh;
+    float *gates;            /* [N][T][3D]: phase 0 writes r, z of step t; phase 1 reads z and writes c */
+    float *hout;             /* rows of rep D, stride ldhout; phase 1: or NULL */
+    int64_t ldhout;
+    int rep;                 /* 1 or 2 */
+    float *y;                /* [N][T][D], phase 1 */
+} gnnmp_gru_cell_t;
+int gnnmp_gru_cell_f32(int phase, const gnnmp_gru_cell_t *job, int64_t N, int64_t T, int64_t t, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dy;         /* [N][T][D], phase 1 */
+    const float *carry;      /* [N][D] or NULL, phase 1 */
+    const float *carry2;     /* rows of rep D, stride ldc2, or NULL, phase 1 */
+    int64_t ldc2;
+    const float *gates;      /* [N][T][3D] */
+    const float *h;          /* as in the forward */
+    int64_t ldh;
+    const float *drh;        /* rows of rep D, stride lddrh, phase 0 */
+    int64_t lddrh;
+    int rep;                 /* 1 or 2 */
+    float *dP;               /* [N][T][3D]: step t written (c, z in phase 1; r in phase 0) */
+    float *dac;              /* [N][D], phase 1 */
+    float *darz;             /* [N][2D]: z half in phase 1, r half in phase 0 */
+    float *part;             /* [N][D]: written in phase 1, updated in phase 0 */
+} gnnmp_gru_cell_grad_t;
+int gnnmp_gru_cell_grad_f32(int phase, const gnnmp_gru_cell_grad_t *job, int64_t N, int64_t T, int64_t t, int64_t D,
+                            gnnmp_stream_t stream);
+
+typedef struct {
+    const float *P;          /* [N][T][4D] */
+    const float *a;          /* [N][4D] */
+    const float *w;          /* [4][D] */
+    const float *c;          /* rows of D, stride ldc (0: one vector), or NULL (zeros) */
+    int64_t ldc;
+    float *gates;            /* [N][T][4D]: step t written */
+    float *cnew;             /* [N][T][D]: step t written */
+    float *hout;             /* rows of D, stride ldhout, or NULL */
+    int64_t ldhout;
+    float *y;                /* [N][T][D]: step t written */
+} gnnmp_lstm_cell_t;
+int gnnmp_lstm_cell_f32(const gnnmp_lstm_cell_t *job, int64_t N, int64_t T, int64_t t, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dy;         /* [N][T][D] */
+    const float *carry_h;    /* rows of D, stride ldch, or NULL */
+    int64_t ldch;
+    const float *carry_c;    /* [N][D] or NULL */
+    const float *gates;      /* [N][T][4D] */
+    const float *w;          /* [4][D] */
+    const float *c;          /* as in the forward */
+    int64_t ldc;
+    const float *cnew;       /* [N][T][D] */
+    float *dP;               /* [N][T][4D]: step t written */
+    float *da;               /* [N][4D] */
+    float *dc;               /* [N][D] */
+    float *peep;             /* [N][T][4D] or NULL: step t written */
+} gnnmp_lstm_cell_grad_t;
+int gnnmp_lstm_cell_grad_f32(const gnnmp_lstm_cell_grad_t *job, int64_t N, int64_t T, int64_t t, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64
