@@ -18,10 +18,12 @@ from .layers_khop import (GlobalAttentionPool, ResGatedGraphConv, SGConv, TAGCon
 from .layers_more import (CGConv, ChebConv, DConv, EdgeConv, EGNNConv, GatedGraphConv, GMMConv, MEGNetConv,  # noqa: F401
                           NNConv, Set2Set, cg_conv, cheb_conv, d_conv, edge_conv, egnn_conv, gated_graph_conv, gmm_conv,
                           megnet_conv, nn_conv, set2set_pool)
-from .layers_temporal import (DCGRU, TGCN, DCGRUCell, GConvGRU, GConvGRUCell, GConvLSTM, GConvLSTMCell, GNNRecurrence,  # noqa: F401
-                              TGCNCell, poly_hop_ld, tgcn_forward)
+from .temporal_graph import TemporalSnapshotsGNNGraph, add_snapshot, remove_snapshot  # noqa: F401
+from .layers_temporal import (DCGRU, TGCN, DCGRUCell, EvolveGCNO, EvolveGCNOCell, GConvGRU, GConvGRUCell, GConvLSTM,  # noqa: F401
+                              GConvLSTMCell, GNNRecurrence, LSTMCell, TGCNCell, poly_hop_ld, tgcn_forward)
 from .backward_temporal import tgcn_ad  # noqa: F401
 from .backward_recurrent import dcgru_ad, gconv_gru_ad, gconv_lstm_ad  # noqa: F401
+from .backward_evolve import evolve_gcno_ad, outer_accum  # noqa: F401
 from .linkpred import (DotDecoder, WithGraph, dot_decoder, dot_decoder_ad, edge_dot_ad, edge_dot_grad,  # noqa: F401
                        negative_sample, rand_edge_split)
 from .neighbors import knn_graph, radius_graph  # noqa: F401

@@ -62,6 +62,7 @@ SYMBOLS = (
     "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
     "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
+    "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -280,6 +281,26 @@ class LstmCellGradJob(ctypes.Structure):
                 ("peep", ctypes.c_void_p)]
 
 
+class LstmMatvecJob(ctypes.Structure):
+    """gnnmp_lstm_matvec_t: one gnnmp_lstm_matvec_cell_f32 call (Wi, Wh, x, h | None, c | None, b | None read; h_out, c_out, a_out | None
+    written)"""
+    _fields_ = [("Wi", ctypes.c_void_p), ("Wh", ctypes.c_void_p), ("x", ctypes.c_void_p), ("h", ctypes.c_void_p), ("c", ctypes.c_void_p),
+                ("b", ctypes.c_void_p), ("h_out", ctypes.c_void_p), ("c_out", ctypes.c_void_p), ("a_out", ctypes.c_void_p)]
+
+
+class LstmMatvecGradJob(ctypes.Structure):
+    """gnnmp_lstm_matvec_grad_t: one gnnmp_lstm_matvec_grad_f32 call (Wi, Wh, da, add_x | None, add_h | None read; out_x | None,
+    out_h | None written; ws the scratch of gnnmp_lstm_matvec_grad_workspace(D) floats)"""
+    _fields_ = [("Wi", ctypes.c_void_p), ("Wh", ctypes.c_void_p), ("da", ctypes.c_void_p), ("add_x", ctypes.c_void_p),
+                ("add_h", ctypes.c_void_p), ("out_x", ctypes.c_void_p), ("out_h", ctypes.c_void_p), ("sum", ctypes.c_int),
+                ("ws", ctypes.c_void_p), ("ws_floats", ctypes.c_int64)]
+
+
+class OuterAccumJob(ctypes.Structure):
+    """gnnmp_outer_accum_t: one gnnmp_outer_accum_f32 call (A [T][R], B [T][K] read; dW [R][K], db [R] | None written)"""
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p)]
+
+
 class GnnmpError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libgnnmp status {status}: {msg}")
@@ -443,6 +464,9 @@ def load():
         "gnnmp_gru_cell_grad_f32": [i, ctypes.POINTER(GruCellGradJob), i64, i64, i64, i64, vp],
         "gnnmp_lstm_cell_f32": [ctypes.POINTER(LstmCellJob), i64, i64, i64, i64, vp],
         "gnnmp_lstm_cell_grad_f32": [ctypes.POINTER(LstmCellGradJob), i64, i64, i64, i64, vp],
+        "gnnmp_lstm_matvec_cell_f32": [ctypes.POINTER(LstmMatvecJob), i64, vp],
+        "gnnmp_lstm_matvec_grad_f32": [ctypes.POINTER(LstmMatvecGradJob), i64, vp],
+        "gnnmp_outer_accum_f32": [ctypes.POINTER(OuterAccumJob), i64, i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }
@@ -462,6 +486,12 @@ def load():
     try:
         L.gnnmp_dense_grad_w2_workspace.argtypes = [i64, i64, i64, i64]
         L.gnnmp_dense_grad_w2_workspace.restype = i64
+    except AttributeError:
+        if not os.environ.get("GNNMP_LIB"):
+            raise
+    try:
+        L.gnnmp_lstm_matvec_grad_workspace.argtypes = [i64]
+        L.gnnmp_lstm_matvec_grad_workspace.restype = i64
     except AttributeError:
         if not os.environ.get("GNNMP_LIB"):
             raise

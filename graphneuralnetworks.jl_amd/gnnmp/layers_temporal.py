@@ -1,5 +1,5 @@
-"""The recurrent layers of GraphNeuralNetworks/src/layers/temporalconv.jl: TGCN, and — further down, with a header of their own —
-GConvGRU, GConvLSTM and DCGRU.
+"""The recurrent layers of GraphNeuralNetworks/src/layers/temporalconv.jl: TGCN, and — further down, with headers of their own —
+GConvGRU, GConvLSTM and DCGRU, then EvolveGCNO.
 
   TGCNCell       temporalconv.jl:809-849   conv_g = GNNChain(GCNConv(in => out, relu; kws...), GCNConv(out => out; kws...)) and
                                            dense_g = Dense(2out => out, σ | tanh) for g in z, r, h; one step
@@ -25,6 +25,7 @@ import torch
 from . import _lib as L
 from .graph import GNNGraph, check_num_nodes
 from .layers import Dense, GCNConv, GNNChain, dense, gcn_norm_cache
+from .temporal_graph import TemporalSnapshotsGNNGraph
 
 TGCN_MAX_OUT = 128          # the one-launch recurrence's envelope (csrc/temporal.hip)
 
@@ -76,7 +77,9 @@ class TGCNCell:
 
 class GNNRecurrence:
     """GNNRecurrence(cell) — temporalconv.jl:121-135: layer(g, x [N, T, in], state=None) -> [N, T, out], the cell scanned over the
-    time dimension (the reference's dims = 2 of (in, T, N))."""
+    time dimension (the reference's dims = 2 of (in, T, N)); with a TemporalSnapshotsGNNGraph and a list of x_t [N_t, in] it returns the
+    list of y_t [N_t, out] (the reference's second scan method, :10-19): a step-by-step loop for every cell but EvolveGCNOCell, which
+    takes its fast path in both forms."""
 
     takes_graph = True
 
@@ -84,6 +87,20 @@ class GNNRecurrence:
         self.cell = cell
 
     def __call__(self, g, x, state=None):
+        if isinstance(self.cell, EvolveGCNOCell):
+            return evolve_forward(self.cell, g, x, state)[0]
+        if isinstance(g, TemporalSnapshotsGNNGraph):
+            # the reference's second scan method (temporalconv.jl:10-19): snapshot t with x[t] [N_t, in]; a list of y_t [N_t, out]
+            name = f"GNNRecurrence({type(self.cell).__name__})"
+            if not isinstance(x, (list, tuple)):
+                raise TypeError(f"{name}: with a TemporalSnapshotsGNNGraph x is a list of one feature array a snapshot")
+            if len(x) != g.num_snapshots:
+                raise ValueError(f"{name}: {len(x)} feature arrays for {g.num_snapshots} snapshots")
+            ys = []
+            for gt, xt in zip(g.snapshots, x):
+                yt, state = self.cell(gt, xt, state)
+                ys.append(yt)
+            return ys
         if isinstance(self.cell, TGCNCell):
             return tgcn_forward(self.cell, g, x, state)
         if isinstance(self.cell, (GConvGRUCell, GConvLSTMCell, DCGRUCell)):
@@ -613,5 +630,217 @@ def tgcn_forward(cell, g: GNNGraph, x, state=None):
     h0, stride = state_arg(state, N, cell.out, x.device)
     y, _ = recurrence(P, sp[6], sp[7], h0, stride, need_gates=False)
     return y
+
+
+# ---------------------------------------------------------------------------------------------------------
+# EvolveGCNO — temporalconv.jl:678-752
+#
+# The cell's LSTM evolves the FLATTENED weight of its GCNConv (D = in out; Wi, Wh [4D][D]), at batch one: a step is two matrix-vector
+# products over 8 D^2 floats and one launch of gnnmp_lstm_matvec_cell_f32 (csrc/evolve.hip).  The weight sequence depends on the
+# parameters and the state only — never on x or the graph — so it is made first: Wseq [T + 1][D], row 0 the weight that entered, row t
+# the weight of snapshot t.  The snapshots are independent given their weights: their normalised aggregation is ONE propagate over the
+# block-diagonal batch (TemporalSnapshotsGNNGraph.batched), and the product with W_t one gnnmp_dense_f32 a snapshot on its contiguous row
+# range, reading row t of Wseq in place: flattened in Julia's column-major order (index o + out i) a weight vector IS the [in][out]
+# row-major matrix that gnnmp_dense_f32 reads with w_layout = 1.  2T + 1 launches for T snapshots.
+# ---------------------------------------------------------------------------------------------------------
+class LSTMCell:
+    """Flux.LSTMCell(n_in => n_out; bias): Wi [4 n_out, n_in], Wh [4 n_out, n_out], b [4 n_out] or None; gate order input, forget, cell,
+    output (as in Set2Set).  A bag of parameters: EvolveGCNOCell steps it with gnnmp_lstm_matvec_cell_f32."""
+
+    def __init__(self, ch, bias=True, device="cuda", seed=None):
+        from .layers import glorot_uniform
+        n_in, n_out = ch
+        s = 0 if seed is None else int(seed)
+        self.in_, self.out = n_in, n_out
+        self.Wi = glorot_uniform(4 * n_out, n_in, device=device, seed=s)
+        self.Wh = glorot_uniform(4 * n_out, n_out, device=device, seed=s + 1)
+        self.b = torch.zeros(4 * n_out, dtype=torch.float32, device=device) if bias else None
+
+
+class EvolveGCNOCell:
+    """EvolveGCNOCell(in => out; bias = true) — temporalconv.jl:678-705.  Fields as in the reference: in_, out, conv = GCNConv(in => out;
+    bias) (identity σ, self loops, no edge weights), lstm = LSTMCell(in out => in out; bias).
+    cell(g, x [N, in], state = None) -> (y [N, out], (weight, (h, c))): the LSTM advances the flattened weight, the convolution uses it.
+    A state is (weight [D], (h [D], c [D])), D = in out; None is initialstates()."""
+
+    takes_graph = True
+
+    def __init__(self, ch, bias=True, device="cuda", seed=None):
+        cin, out = ch
+        if int(cin) < 1 or int(out) < 1:
+            raise ValueError(f"EvolveGCNOCell: channels must be positive, got {cin} => {out}")
+        s = 0 if seed is None else int(seed)
+        self.in_, self.out = int(cin), int(out)
+        self.conv = GCNConv((self.in_, self.out), bias=bias, device=device, seed=s + 1)
+        D = self.in_ * self.out
+        self.lstm = LSTMCell((D, D), bias=bias, device=device, seed=s + 2)
+
+    def parameters(self):
+        """5 tensors in evolve_gcno_ad's order: conv.weight [out, in], conv.bias, lstm.Wi, lstm.Wh, lstm.b; a bias is None with bias=false.
+        in out + out + 8 D^2 + 4D numbers: 321 for 2 => 3, 696 for 3 => 3 (the reference docstring's figures)."""
+        return [self.conv.weight, self.conv.bias, self.lstm.Wi, self.lstm.Wh, self.lstm.b]
+
+    def initialstates(self):
+        """(weight, (h, c)) — temporalconv.jl:693-697: weight = reshape(conv.weight, :), COLUMN-MAJOR as in Julia (index o + out i, i.e.
+        conv.weight.T.reshape(-1)), which makes Wi, Wh and b interchangeable with the reference's; h and c zeros of length D"""
+        w = self.conv.weight.t().reshape(-1)
+        z = torch.zeros(self.in_ * self.out, dtype=torch.float32, device=w.device)
+        return w, (z, z.clone())
+
+    def __call__(self, g, x, state=None):
+        x3 = x.reshape(x.shape[0], 1, x.shape[-1]) if torch.is_tensor(x) and x.dim() == 2 else x
+        return evolve_forward(self, g, x3, state, name="EvolveGCNOCell", single=True)
+
+
+def EvolveGCNO(ch, **kw):
+    """EvolveGCNO(in => out; kws...) = GNNRecurrence(EvolveGCNOCell(...)) — temporalconv.jl:752.  layer(tg, [x_t [N_t, in]]) -> [y_t
+    [N_t, out]] over a TemporalSnapshotsGNNGraph; layer(g, x [N, T, in]) -> [N, T, out] over a static graph, which runs as T copies of
+    g through the same path (one block-diagonal propagate, cached on g per T)."""
+    return GNNRecurrence(EvolveGCNOCell(ch, **kw))
+
+
+def _check_evolve_x(name, cell, n_nodes, xt, what):
+    if isinstance(xt, (tuple, list)):
+        raise NotImplementedError(f"{name}: a bipartite (xs, xt) input is not covered; pass one feature array")
+    if not torch.is_tensor(xt):
+        raise TypeError(f"{name}: {what} is a {type(xt).__name__}, not a tensor")
+    if xt.dtype != torch.float32:
+        raise ValueError(f"{name}: the HIP kernels are Float32; {what} is {xt.dtype}")
+    if xt.dim() != 2 or xt.shape[1] != cell.in_:
+        raise ValueError(f"{name}: {what} must be [N][{cell.in_}] for this layer, not {tuple(xt.shape)}")
+    if xt.shape[0] != n_nodes:
+        raise ValueError(f"{name}: {what} has {xt.shape[0]} rows, its snapshot has {n_nodes} nodes")
+
+
+def evolve_inputs(name, cell, g, x):
+    """(tg, xcat [Σ N_t, in], static): both input forms brought to one — a temporal graph and the snapshots' features one under the
+    other.  Static form: the T time slices of x [N, T, in] over T copies of g (the temporal graph is kept on g, one per T)."""
+    if isinstance(g, TemporalSnapshotsGNNGraph):
+        if not isinstance(x, (list, tuple)):
+            raise TypeError(f"{name}: with a TemporalSnapshotsGNNGraph x is a list of one feature array a snapshot")
+        if len(x) != g.num_snapshots:
+            raise ValueError(f"{name}: {len(x)} feature arrays for {g.num_snapshots} snapshots")
+        if g.num_snapshots == 0:
+            raise ValueError(f"{name}: a temporal graph without snapshots")
+        for t, xt in enumerate(x):
+            _check_evolve_x(name, cell, g.num_nodes[t], xt, f"x[{t}]")
+        return g, (x[0] if len(x) == 1 else torch.cat(list(x))).contiguous(), False
+    if not isinstance(g, GNNGraph):
+        raise TypeError(f"{name}: expected a GNNGraph or a TemporalSnapshotsGNNGraph, got {type(g).__name__}")
+    if isinstance(x, (tuple, list)):
+        raise NotImplementedError(f"{name}: a bipartite (xs, xt) input is not covered; pass one feature array")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name}: the HIP kernels are Float32; x is {x.dtype}")
+    if x.dim() != 3 or x.shape[2] != cell.in_ or x.shape[1] < 1:
+        raise ValueError(f"{name}: x must be [N][T][{cell.in_}] for this layer, not {tuple(x.shape)}")
+    if x.shape[0] != g.num_nodes:
+        raise ValueError(f"{name}: x has {x.shape[0]} rows, the graph has {g.num_nodes} nodes")
+    N, T, cin = x.shape
+    key = ("evolve_static", T)
+    tg = g._cache.get(key)
+    if tg is None:
+        tg = g._cache[key] = TemporalSnapshotsGNNGraph([g] * T)
+    return tg, x.permute(1, 0, 2).reshape(T * N, cin).contiguous(), True
+
+
+def evolve_state(name, cell, state, device):
+    """(weight0, h0, c0) of a given state, float32 and contiguous; (None, None, None) for None (initialstates)"""
+    if state is None:
+        return None, None, None
+    D = cell.in_ * cell.out
+    try:
+        w0, (h0, c0) = state
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: the state is (weight, (h, c))") from None
+    out = []
+    for what, v in (("weight", w0), ("h", h0), ("c", c0)):
+        if not torch.is_tensor(v) or v.numel() != D:
+            raise ValueError(f"{name}: the state's {what} must have in * out = {D} elements")
+        if v.dtype != torch.float32:
+            raise ValueError(f"{name}: the HIP kernels are Float32; the state's {what} is {v.dtype}")
+        out.append(v.to(device).reshape(D).contiguous())
+    return tuple(out)
+
+
+def evolve_weights(cell, T, w0, h0, c0, keep=False):
+    """the weight sequence: (Wseq [T + 1][D], Cseq [T + 1][D], A [T][4D] | None).  Row 0 holds what entered (w0: None = the flattened
+    conv.weight; c0: None = zeros), step t reads row t - 1 — as the LSTM's input and, from step 2 on, as its hidden state too — and
+    writes row t: T launches.  `keep`: the pre-activations, for the pullback."""
+    D = cell.in_ * cell.out
+    lstm = cell.lstm
+    dev = lstm.Wi.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    Wseq, Cseq = torch.empty((T + 1, D), **f32), torch.empty((T + 1, D), **f32)
+    Wseq[0].copy_(cell.conv.weight.t().reshape(-1) if w0 is None else w0)
+    if c0 is None:
+        Cseq[0].zero_()
+    else:
+        Cseq[0].copy_(c0)
+    A = torch.empty((T, 4 * D), **f32) if keep else None
+    lib = L.load()
+    for t in range(1, T + 1):
+        h = L.ptr(h0) if t == 1 else _at(Wseq, (t - 1) * D)
+        job = L.LstmMatvecJob(L.ptr(lstm.Wi), L.ptr(lstm.Wh), _at(Wseq, (t - 1) * D), h, _at(Cseq, (t - 1) * D), L.ptr(lstm.b),
+                              _at(Wseq, t * D), _at(Cseq, t * D), None if A is None else _at(A, (t - 1) * 4 * D))
+        L.check(lib.gnnmp_lstm_matvec_cell_f32(ctypes.byref(job), D, L.stream_ptr()))
+    return Wseq, Cseq, A
+
+
+def dense_rows(x, r0, r1, Wflat, cin, out, w_layout, bias, dst):
+    """dst[r0:r1] = x[r0:r1] * M (w_layout = 1, M = Wflat as [in][out]: [., in] -> [., out]) or x[r0:r1] * M' (w_layout = 0, M read as the
+    [Dout = in][K = out] matrix: [., out] -> [., in]) (+ bias): one gnnmp_dense_f32 on a contiguous row range, the weight read in place"""
+    if r1 <= r0:
+        return
+    K, Dout = (cin, out) if w_layout else (out, cin)
+    assert x.shape[1] == K and dst.shape[1] == Dout and x.is_contiguous() and dst.is_contiguous()
+    L.check(L.load().gnnmp_dense_f32(_at(x, r0 * K), L.ptr(Wflat), K, out, None, None, 0, 0, int(w_layout), L.ptr(bias), L.ACT_IDENTITY,
+                                     _at(dst, r0 * Dout), r1 - r0, Dout, L.stream_ptr()))
+
+
+def evolve_conv(cell, tg, xcat, Wseq):
+    """(y [Σ N_t, out], agg | None): gcn_conv of every snapshot with its own weight, row t + 1 of Wseq for snapshot t.  out >= in:
+    aggregate first (one propagate at width in, then T products, the bias in their epilogue; agg is what the ΔW of the pullback reads);
+    out < in: W first (T products, then one propagate at width out with the bias in its epilogue), as gcn_conv does."""
+    gb, seg = tg.batched()
+    cin, out = cell.in_, cell.out
+    conv = cell.conv
+    T = tg.num_snapshots
+    f32 = dict(dtype=torch.float32, device=xcat.device)
+    if out >= cin:
+        agg = gcn_propagate(gb, True, None, xcat)
+        y = torch.empty((xcat.shape[0], out), **f32)
+        for t in range(T):
+            dense_rows(agg, seg[t], seg[t + 1], Wseq[t + 1], cin, out, 1, conv.bias, y)
+        return y, agg
+    u = torch.empty((xcat.shape[0], out), **f32)
+    for t in range(T):
+        dense_rows(xcat, seg[t], seg[t + 1], Wseq[t + 1], cin, out, 1, None, u)
+    return gcn_propagate(gb, True, None, u, bias=conv.bias), None
+
+
+def evolve_output(tg, y, static):
+    """the caller's form back: a list of y_t [N_t, out], or [N, T, out] for the static form"""
+    if static:
+        T, N = tg.num_snapshots, tg.num_nodes[0]
+        return y.view(T, N, y.shape[1]).permute(1, 0, 2).contiguous()
+    return list(y.split(tg.num_nodes))
+
+
+def evolve_forward(cell, g, x, state=None, name="EvolveGCNO", single=False):
+    """(y, (weight_T, (h_T, c_T))) of GNNRecurrence(EvolveGCNOCell) in both input forms (evolve_inputs); `single`: one step of the
+    cell on a plain graph, x [N, 1, in] -> y [N, out]"""
+    if single and isinstance(g, TemporalSnapshotsGNNGraph):
+        raise TypeError(f"{name}: a cell steps on one GNNGraph; scan a TemporalSnapshotsGNNGraph with EvolveGCNO / GNNRecurrence")
+    tg, xcat, static = evolve_inputs(name, cell, g, x)
+    if not (cell.conv.add_self_loops and not cell.conv.use_edge_weight and cell.conv.sigma is None):
+        raise ValueError(f"{name}: the cell's GCNConv must be the reference's (identity σ, self loops, no edge weights)")
+    w0, h0, c0 = evolve_state(name, cell, state, xcat.device)
+    T = tg.num_snapshots
+    Wseq, Cseq, _ = evolve_weights(cell, T, w0, h0, c0)
+    y, _ = evolve_conv(cell, tg, xcat, Wseq)
+    out = evolve_output(tg, y, static)
+    if single:
+        out = out.reshape(out.shape[0], cell.out)
+    return out, (Wseq[T], (Wseq[T], Cseq[T]))
 
 

@@ -39,7 +39,8 @@
  *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py) and
  *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
  *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
- *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_lstm_matvec_cell_f32 /
+ *     gnnmp_lstm_matvec_grad_f32 / gnnmp_outer_accum_f32 (tests/test_evolve_gcno.py: a whole training step), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -1894,6 +1895,85 @@ int gnnmp_scatter_f64(gnnmp_graph_t *plan, int aggr, const double *m, double *ou
  * KB, no synchronisation, a no-op for a plan without split rows.  Never needed by a caller that keeps the rule.
  * ---------------------------------------------------------------------------------------------- */
 int gnnmp_plan_reset_counters(gnnmp_graph_t *plan, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Flux.LSTMCell at batch one on a long vector: the recurrence of EvolveGCNOCell (GraphNeuralNetworks/src/layers/temporalconv.jl:678-705),
+ * whose LSTM evolves the FLATTENED convolution weight — D = in * out, Wi and Wh [4D][D] row-major (Julia (4D, D) read row by row: the
+ * caller's [4D, D] tensors), gate order (input, forget, cell, output), b [4D].  A step is two matrix-vector products that read 8 D^2
+ * floats; csrc/evolve.hip.  σ(x) = (t = expf(-|x|); x >= 0 ? 1 / (1 + t) : t / (1 + t)), tanh = tanhf, as gnnmp_lstm_pointwise_f32;
+ * every product and every sum is rounded on its own.
+ *   gnnmp_lstm_matvec_cell_f32         one whole step:  a = Wi x + Wh h + b,  c' = σ(a_f) c + σ(a_i) tanhf(a_c),  h' = σ(a_o) tanhf(c').
+ *                                      gnnmp_lstm_matvec_t: Wi, x read; Wh and h [D] read, or h NULL (zeros: the Wh product is skipped and
+ *                                      Wh is not read); c [D] or NULL (zeros); b [4D] or NULL; h_out [D], c_out [D] written; a_out [4D]
+ *                                      (the pre-activations, bias included: what the pullback recomputes the gates from) written, or NULL.
+ *                                      x and h may be the same array.  A lane group owns element j and streams the rows j, D + j, 2D + j,
+ *                                      3D + j of both matrices: a_j is the sum of the lanes' partials (each over the columns f, f + G VEC,
+ *                                      ... ascending, the Wi terms of a pass before its Wh terms) folded by an xor butterfly, + b.  The
+ *                                      group is up to a wave; for D <= 2048 a row that fills 256 lanes goes to a whole workgroup, whose
+ *                                      four waves' sums are added in wave order (one wave an element would be too few waves).  Lanes
+ *                                      are 16 / 8 bytes wide only when D % 4 / D % 2 == 0 and Wi, Wh, x, h are aligned to as much.
+ *                                      Refused (GNNMP_EINVAL, "lstm_matvec_cell: ..."): a NULL job; D outside 0 .. 2^20; NULL Wi, x, h_out
+ *                                      or c_out; h without Wh; an output that overlaps x, h or c (other workgroups still read them) or
+ *                                      another output.  D = 0 returns GNNMP_OK.
+ *   gnnmp_lstm_matvec_grad_workspace   floats of scratch gnnmp_lstm_matvec_grad_f32 needs at D: a pure host function (0 for a D outside
+ *                                      1 .. 2^20)
+ *   gnnmp_lstm_matvec_grad_f32         the transposed products:  out_x = Wi' da (+ add_x),  out_h = Wh' da (+ add_h); either output may
+ *                                      be NULL (its matrix is then not read).  sum = 1:  out_x = (Wi' da + Wh' da) + add_x — from the
+ *                                      second step on the LSTM's input and its hidden state are one array (out_h and add_h must be
+ *                                      NULL).  gnnmp_lstm_matvec_grad_t: da [4D]; add_x, add_h [D] or NULL; ws, ws_floats the scratch.
+ *                                      Each matrix is read once, rows coalesced; its 4D rows are cut into slabs whose partial sums (rows
+ *                                      ascending) go to ws, and a SECOND LAUNCH adds the slabs in ascending order: no workgroup waits
+ *                                      on another, equal bits from call to call.  Refused (GNNMP_EINVAL, "lstm_matvec_grad: ..."): a NULL
+ *                                      job; D outside 0 .. 2^20; sum outside {0, 1}; NULL da; both outputs NULL; a wanted matrix NULL; an
+ *                                      addend without its output; out_h or add_h with sum = 1; a NULL or short workspace; an output that
+ *                                      overlaps da, the workspace or the other output; a workspace that overlaps da or an addend.  D = 0
+ *                                      returns GNNMP_OK.
+ *   gnnmp_outer_accum_f32              the rank-T update:  dW[r][k] = Σ_t A[t][r] B[t][k], t ascending, from zero; dW [R][K] written once;
+ *                                      db[r] = Σ_t A[t][r] when db is given.  gnnmp_outer_accum_t: A [T][R], B [T][K] read; dW, db or NULL
+ *                                      written.  ΔWi = (A = the steps' da, B = the steps' inputs), ΔWh = (B = the hidden states that entered).
+ *                                      Write-bound: whole 16-byte lanes side by side when K % 4 == 0 and B, dW are aligned.  Refused
+ *                                      (GNNMP_EINVAL, "outer_accum: ..."): a NULL job; T outside 0 .. 2^20, R outside 0 .. 2^22, K outside
+ *                                      0 .. 2^20; NULL A, B or dW; an output that overlaps an input or the other output.  T = 0 (the empty
+ *                                      sum), R = 0, or K = 0 without db: GNNMP_OK, nothing is launched and NOTHING IS WRITTEN.
+ *   job    const HOST records of device pointers and scalars (below).
+ * All three compute calls only launch on `stream`: no atomics, no allocation, no host wait, nothing owned by a plan; each may be recorded
+ * into a HIP graph without an eager call first; two calls give equal bits.  Element offsets are 64-bit (4D * D passes 2^31 at D = 23 171).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *Wi;         /* [4D][D] */
+    const float *Wh;         /* [4D][D]; may be NULL when h is */
+    const float *x;          /* [D] */
+    const float *h;          /* [D] or NULL (zeros) */
+    const float *c;          /* [D] or NULL (zeros) */
+    const float *b;          /* [4D] or NULL */
+    float *h_out;            /* [D] */
+    float *c_out;            /* [D] */
+    float *a_out;            /* [4D] or NULL */
+} gnnmp_lstm_matvec_t;
+int gnnmp_lstm_matvec_cell_f32(const gnnmp_lstm_matvec_t *job, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *Wi;         /* [4D][D]; read when out_x is given */
+    const float *Wh;         /* [4D][D]; read when out_h is given or sum = 1 */
+    const float *da;         /* [4D] */
+    const float *add_x;      /* [D] or NULL */
+    const float *add_h;      /* [D] or NULL */
+    float *out_x;            /* [D] or NULL */
+    float *out_h;            /* [D] or NULL */
+    int sum;                 /* 1: out_x = Wi' da + Wh' da + add_x */
+    float *ws;               /* ws_floats >= gnnmp_lstm_matvec_grad_workspace(D) floats of scratch */
+    int64_t ws_floats;
+} gnnmp_lstm_matvec_grad_t;
+int64_t gnnmp_lstm_matvec_grad_workspace(int64_t D);
+int gnnmp_lstm_matvec_grad_f32(const gnnmp_lstm_matvec_grad_t *job, int64_t D, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *A;          /* [T][R] */
+    const float *B;          /* [T][K] */
+    float *dW;               /* [R][K] */
+    float *db;               /* [R] or NULL */
+} gnnmp_outer_accum_t;
+int gnnmp_outer_accum_f32(const gnnmp_outer_accum_t *job, int64_t T, int64_t R, int64_t K, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GNNMP_INTERNAL — exported, NOT part of the drop-in surface: experiment and test hooks.  Declared here so that C callers (tests/c_harness)
