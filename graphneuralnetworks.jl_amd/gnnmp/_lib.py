@@ -63,6 +63,7 @@ SYMBOLS = (
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
     "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
+    "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -301,6 +302,23 @@ class OuterAccumJob(ctypes.Structure):
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p)]
 
 
+class AttnEdgeJob(ctypes.Structure):
+    """gnnmp_attn_edge_t: one gnnmp_attn_conv_edge_f32 call (Q | None, K, V | None, F [E][H C], a, bias | None read; out, stats | None
+    written)"""
+    _fields_ = [("Q", ctypes.c_void_p), ("K", ctypes.c_void_p), ("V", ctypes.c_void_p), ("F", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("negative_slope", ctypes.c_float),
+                ("scale", ctypes.c_float), ("act", ctypes.c_int)]
+
+
+class AttnEdgeGradJob(ctypes.Structure):
+    """gnnmp_attn_edge_grad_t: one gnnmp_attn_conv_edge_grad_f32 call (the forward's inputs, stats, dout read; line scratch; dQ, dK,
+    dV (DOT), dF, dA and da | None (GATV2) written)"""
+    _fields_ = [("Q", ctypes.c_void_p), ("K", ctypes.c_void_p), ("V", ctypes.c_void_p), ("F", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("line", ctypes.c_void_p), ("dQ", ctypes.c_void_p),
+                ("dK", ctypes.c_void_p), ("dV", ctypes.c_void_p), ("dF", ctypes.c_void_p), ("dA", ctypes.c_void_p), ("da", ctypes.c_void_p),
+                ("negative_slope", ctypes.c_float), ("scale", ctypes.c_float)]
+
+
 class GnnmpError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libgnnmp status {status}: {msg}")
@@ -467,6 +485,8 @@ def load():
         "gnnmp_lstm_matvec_cell_f32": [ctypes.POINTER(LstmMatvecJob), i64, vp],
         "gnnmp_lstm_matvec_grad_f32": [ctypes.POINTER(LstmMatvecGradJob), i64, vp],
         "gnnmp_outer_accum_f32": [ctypes.POINTER(OuterAccumJob), i64, i64, i64, vp],
+        "gnnmp_attn_conv_edge_f32": [vp, i, ctypes.POINTER(AttnEdgeJob), i64, i64, vp],
+        "gnnmp_attn_conv_edge_grad_f32": [vp, vp, i, ctypes.POINTER(AttnEdgeGradJob), i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

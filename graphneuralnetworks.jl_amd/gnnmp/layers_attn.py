@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .graph import GNNGraph, check_num_nodes
+from .graph import GNNGraph, check_num_edges, check_num_nodes
 from .layers import _act_code, dense, glorot_uniform
 from .msgpass import _fused
 
@@ -37,6 +37,38 @@ def attn_conv(plan, mode, K, Q=None, V=None, a=None, slope=0.2, scale=1.0, bias=
     return out
 
 
+SELF_LOOPS_MSG = "Using edge features and setting add_self_loops=true at the same time is not yet supported."
+
+
+def _split_channels(ch):
+    """in => out or (in, ein) => out, as (in, ein, out)"""
+    cin, cout = ch
+    if isinstance(cin, (tuple, list)):
+        cin, ein = cin
+        return int(cin), int(ein), int(cout)
+    return int(cin), 0, int(cout)
+
+
+def check_edge_row_width(H, C, what):
+    """the edge-featured kernels keep one [H*C] row in one wave, v = 4, 2 or 1 floats a lane as C allows (include/gnnmp.h:
+    gnnmp_gat_conv_stats_f32's rule; the arrays torch allocates are aligned for any v): refused here by name, before any C call"""
+    v = 4 if C % 4 == 0 else 2 if C % 2 == 0 else 1
+    assert H * C // v <= 64, f"{what}: the feature row must fit one wave (heads * out = {H * C} is {H * C // v} lanes of {v}, at most 64)"
+
+
+def attn_conv_edge(plan, mode, K, F, Q=None, V=None, a=None, slope=0.2, scale=1.0, bias=None, act=L.ACT_IDENTITY, H=1, C=None,
+                   stats=None):
+    """attn_conv with a per-edge feature row F [E][H*C] inside the logit (GATV2) or the logit and the value (DOT): one pass over
+    the plan's edges (include/gnnmp.h: gnnmp_attn_conv_edge_f32)"""
+    N = plan.n_dst
+    C = K.shape[1] // H if C is None else C
+    out = torch.empty((N, H * C), dtype=torch.float32, device=K.device)
+    job = L.AttnEdgeJob(L.ptr(Q), L.ptr(K), L.ptr(V), L.ptr(F), L.ptr(a), L.ptr(bias), L.ptr(out), L.ptr(stats), float(slope),
+                        float(scale), int(act))
+    L.check(L.load().gnnmp_attn_conv_edge_f32(plan.handle, mode, job, H, C, L.stream_ptr()))
+    return out
+
+
 def _heads_tail(out, l, N, H, C):
     """concat = true: bias and σ were fused into the kernel; concat = false: mean over heads, then σ.(x .+ bias)"""
     code, post = _act_code(l.sigma)
@@ -52,13 +84,26 @@ def _heads_tail(out, l, N, H, C):
 # GATv2Conv
 # ---------------------------------------------------------------------------------------------------------
 def gatv2_conv(l, g: GNNGraph, x, e=None, seed=None):
-    """conv.jl:171-214 without edge features: logα = sum(a .* leakyrelu.(Wxi + Wxj)), softmax over the neighbourhood,
+    """conv.jl:171-214: logα = sum(a .* leakyrelu.(Wxi + Wxj [+ dense_e(e)])), softmax over the neighbourhood,
     `α = dropout(α, l.dropout)` (:191, inside the kernel; `seed` defaults to the layer's next one), weighted sum of Wxj, optional
-    head mean, σ.(x .+ bias)"""
+    head mean, σ.(x .+ bias).  With `e` the edge row enters the logit inside the kernel of csrc/attn_edge.hip (no dropout there)"""
     check_num_nodes(g, x)
-    assert e is None and l.dense_e is None, "edge features (dense_e) are outside the hot path"
-    plan = g.plan(bool(l.add_self_loops))
+    assert not (e is None and l.dense_e_weight is not None), "Input edge features required for this layer"
+    assert not (e is not None and l.dense_e_weight is None), "Input edge features were not specified in the layer constructor"
+    if l.add_self_loops:
+        assert e is None, SELF_LOOPS_MSG
     H, C = l.heads, l.channel[1]
+    if e is not None:
+        check_num_edges(g, e)
+        assert float(getattr(l, "dropout", 0.0)) == 0.0, "GATv2Conv: attention dropout together with edge features is not supported"
+        check_edge_row_width(H, C, "GATv2Conv with edge features")
+        code, _ = _act_code(l.sigma)
+        fuse = bool(l.concat)
+        out = attn_conv_edge(g.plan(False), ATTN_GATV2, dense(x, l.dense_j_weight), dense(e.contiguous(), l.dense_e_weight),
+                             Q=dense(x, l.dense_i_weight, l.dense_i_bias), a=l.a_hc, slope=l.negative_slope,
+                             bias=l.bias if (fuse and l.bias is not None) else None, act=code if fuse else L.ACT_IDENTITY, H=H, C=C)
+        return _heads_tail(out, l, g.num_nodes, H, C)
+    plan = g.plan(bool(l.add_self_loops))
     Wxi = dense(x, l.dense_i_weight, l.dense_i_bias)
     Wxj = dense(x, l.dense_j_weight)
     code, _ = _act_code(l.sigma)
@@ -77,27 +122,31 @@ def gatv2_conv(l, g: GNNGraph, x, e=None, seed=None):
 
 
 class GATv2Conv:
-    """GATv2Conv(in => out, σ=identity; heads=1, concat=true, negative_slope=0.2, bias=true, add_self_loops=true) —
-    GraphNeuralNetworks/src/layers/conv.jl:435-462.  `a` has the Julia shape (out, heads); dense_i carries a bias iff
-    `bias`, dense_j none."""
+    """GATv2Conv(in => out, σ=identity; heads=1, concat=true, negative_slope=0.2, bias=true, add_self_loops=true) and
+    GATv2Conv((in, ein) => out, ...) — GraphNeuralNetworks/src/layers/conv.jl:435-462.  `a` has the Julia shape (out, heads); dense_i
+    carries a bias iff `bias`, dense_j none; with ein > 0 dense_e_weight [heads * out, ein] (no bias) maps the edge features."""
 
     takes_graph = True
+    PARAMETER_NAMES = ("dense_i_weight", "dense_i_bias", "dense_j_weight", "dense_e_weight", "a", "bias")
 
     def __init__(self, ch, sigma=None, heads=1, concat=True, negative_slope=0.2, bias=True, add_self_loops=True,
                  dropout=0.0, device="cuda", seed=None):
-        cin, cout = ch
+        cin, ein, cout = _split_channels(ch)
         assert 0.0 <= dropout < 1.0
+        if add_self_loops:
+            assert ein == 0, SELF_LOOPS_MSG
         sd = (lambda k: None if seed is None else seed + k)
         self.dropout = float(dropout)
         self.last_seed = None
         self._seed_rng = np.random.default_rng(None if seed is None else seed + 7)
         self.channel = (cin, cout)
+        self.ein = ein
         self.heads, self.concat, self.negative_slope = heads, concat, float(negative_slope)
         self.add_self_loops = add_self_loops
         self.dense_i_weight = glorot_uniform(cout * heads, cin, device=device, seed=sd(0))
         self.dense_i_bias = torch.zeros(cout * heads, dtype=torch.float32, device=device) if bias else None
         self.dense_j_weight = glorot_uniform(cout * heads, cin, device=device, seed=sd(1))
-        self.dense_e = None
+        self.dense_e_weight = glorot_uniform(cout * heads, ein, device=device, seed=sd(3)) if ein > 0 else None
         self.a = glorot_uniform(cout, heads, device=device, seed=sd(2))
         self.bias = torch.zeros(cout * heads if concat else cout, dtype=torch.float32, device=device) if bias else None
         self.sigma = sigma
@@ -109,6 +158,15 @@ class GATv2Conv:
             self._a_hc = self.a.t().contiguous()          # [H][C]
             self._a_hc_key = key
         return self._a_hc
+
+    @property
+    def dense_e(self):
+        """the reference's field: nothing without ein"""
+        return self.dense_e_weight
+
+    def parameters(self):
+        """Flux.trainable(l::GATv2Conv), the 6 tensors gatv2_conv_ad differentiates, in PARAMETER_NAMES' order; None: absent"""
+        return [getattr(self, n) for n in self.PARAMETER_NAMES]
 
     def next_seed(self):
         """a fresh 64-bit mask seed per call (the reference draws a fresh mask from its default RNG on every call)"""
@@ -148,17 +206,27 @@ class AGNNConv:
 # TransformerConv
 # ---------------------------------------------------------------------------------------------------------
 def transformer_conv(l, g: GNNGraph, x, e=None):
-    """conv.jl:553-629 for the configuration without edge features, gating, batch norm and feed-forward block:
-    α = softmax((W3 x_i) . (W4 x_j) / sqrt(out)), h_i = Σ_j α_ij W2 x_j, [mean over heads], + W1 x_i, + x_i"""
+    """conv.jl:553-629 for the configuration without gating, batch norm and feed-forward block:
+    α = softmax((W3 x_i) . (W4 x_j [+ W6 e_ij]) / sqrt(out)), h_i = Σ_j α_ij (W2 x_j [+ W6 e_ij]), [mean over heads], + W1 x_i, + x_i"""
     check_num_nodes(g, x)
-    assert e is None, "edge features (W6) are outside the hot path"
-    plan = g.plan(bool(l.add_self_loops))
+    assert not (e is None and l.W6_weight is not None), "Input edge features required for this layer"
+    assert not (e is not None and l.W6_weight is None), "Input edge features were not specified in the layer constructor"
+    if l.add_self_loops:
+        assert e is None, SELF_LOOPS_MSG
     H, C = l.heads, l.channels[1]
     x = x.contiguous()
+    if e is not None:
+        check_num_edges(g, e)
+        check_edge_row_width(H, C, "TransformerConv with edge features")
+    plan = g.plan(bool(l.add_self_loops))
     W2x = dense(x, l.W2_weight, l.W2_bias)
     W3x = dense(x, l.W3_weight, l.W3_bias)
     W4x = dense(x, l.W4_weight, l.W4_bias)
-    h = attn_conv(plan, ATTN_DOT, W4x, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
+    if e is not None:
+        W6e = dense(e.contiguous(), l.W6_weight, l.W6_bias)
+        h = attn_conv_edge(plan, ATTN_DOT, W4x, W6e, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
+    else:
+        h = attn_conv(plan, ATTN_DOT, W4x, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
     lib = L.load()
     N = g.num_nodes
     if not l.concat:
@@ -176,18 +244,23 @@ def transformer_conv(l, g: GNNGraph, x, e=None):
 
 class TransformerConv:
     """TransformerConv(in => out; heads=1, concat=true, add_self_loops=false, bias_qkv=true, bias_root=true,
-    root_weight=true, skip_connection=false) — GraphNeuralNetworks/src/layers/conv.jl:1501-1536 (gating, batch_norm,
-    ff_channels and edge features are not on the hot path and are rejected)"""
+    root_weight=true, skip_connection=false) and TransformerConv((in, ein) => out; ...) — GraphNeuralNetworks/src/layers/conv.jl:1501-1536
+    (gating, batch_norm and ff_channels are not on the hot path and are rejected).  With ein > 0, W6_weight [heads * out, ein] and
+    W6_bias (iff bias_qkv) map the edge features into the key and the value."""
 
     takes_graph = True
+    PARAMETER_NAMES = ("W1_weight", "W1_bias", "W2_weight", "W2_bias", "W3_weight", "W3_bias", "W4_weight", "W4_bias", "W6_weight", "W6_bias")
 
     def __init__(self, ch, heads=1, concat=True, add_self_loops=False, bias_qkv=True, bias_root=True, root_weight=True,
                  gating=False, skip_connection=False, batch_norm=False, ff_channels=0, device="cuda", seed=None):
-        cin, cout = ch
+        cin, ein, cout = _split_channels(ch)
         assert not gating and not batch_norm and ff_channels == 0, "gating / batch_norm / ff block: outside the hot path"
+        if add_self_loops:
+            assert ein == 0, SELF_LOOPS_MSG
         sd = (lambda k: None if seed is None else seed + k)
         z = (lambda nrow, on: torch.zeros(nrow, dtype=torch.float32, device=device) if on else None)
         self.channels = (cin, cout)
+        self.ein = ein
         self.heads, self.concat, self.add_self_loops, self.skip_connection = heads, concat, add_self_loops, skip_connection
         out_mha = cout * (heads if concat else 1)
         self.W1_weight = glorot_uniform(out_mha, cin, device=device, seed=sd(0)) if root_weight else None
@@ -196,7 +269,13 @@ class TransformerConv:
         self.W3_weight = glorot_uniform(cout * heads, cin, device=device, seed=sd(2))
         self.W4_weight = glorot_uniform(cout * heads, cin, device=device, seed=sd(3))
         self.W2_bias, self.W3_bias, self.W4_bias = (z(cout * heads, bias_qkv) for _ in range(3))
+        self.W6_weight = glorot_uniform(cout * heads, ein, device=device, seed=sd(4)) if ein > 0 else None
+        self.W6_bias = z(cout * heads, bias_qkv and ein > 0)
         self.sqrt_out = float(torch.tensor(float(cout), dtype=torch.float32).sqrt())   # Float32(√out)
+
+    def parameters(self):
+        """the 10 tensors transformer_conv_ad differentiates, in PARAMETER_NAMES' order; None: absent"""
+        return [getattr(self, n) for n in self.PARAMETER_NAMES]
 
     def __call__(self, g, x, e=None):
         return transformer_conv(self, g, x, e)
@@ -230,4 +309,4 @@ class GINConv:
 
 
 __all__ = ["GATv2Conv", "AGNNConv", "TransformerConv", "GINConv", "gatv2_conv", "agnn_conv", "transformer_conv",
-           "gin_conv", "attn_conv", "ATTN_GAT", "ATTN_GATV2", "ATTN_DOT", "ATTN_COS"]
+           "gin_conv", "attn_conv", "attn_conv_edge", "ATTN_GAT", "ATTN_GATV2", "ATTN_DOT", "ATTN_COS"]

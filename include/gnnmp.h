@@ -40,7 +40,8 @@
  *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
  *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
  *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_lstm_matvec_cell_f32 /
- *     gnnmp_lstm_matvec_grad_f32 / gnnmp_outer_accum_f32 (tests/test_evolve_gcno.py: a whole training step), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_lstm_matvec_grad_f32 / gnnmp_outer_accum_f32 (tests/test_evolve_gcno.py: a whole training step) and
+ *     gnnmp_attn_conv_edge_f32 / gnnmp_attn_conv_edge_grad_f32 (tests/test_attn_edge.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -599,7 +600,7 @@ int gnnmp_gat_conv_edge_f32(gnnmp_graph_t *plan, const float *Wx_src, const floa
  * pointer runs with v = 1; GNNMP_EUNSUPPORTED otherwise — so a row of more than 64 floats is refused when a pointer is under-aligned
  * for the v it needs).  The same rule holds for every one-pass attention entry point and pullback below (gnnmp_gat_conv_edge_f32 /
  * _train_f32 / _drop_f32, gnnmp_attn_conv_f32 / _drop_f32, gnnmp_gat_conv_grad_f32 / _grad2_f32 / _grad_drop_f32, gnnmp_attn_conv_grad_f32 /
- * _grad_drop_f32: out, oplus, dout and the [.][H*C] gradient arrays count); gnnmp_gat_conv_f32 falls back to the three-pass kernels instead.
+ * _grad_drop_f32, gnnmp_attn_conv_edge_f32 / _edge_grad_f32: out, oplus, dout, F, dF and the [.][H*C] gradient arrays count); gnnmp_gat_conv_f32 falls back to the three-pass kernels instead.
  * Head widths whose lane count is a power of two reduce with DPP butterflies; any other width (C = 7 classes, ...) is
  * supported too, summing the head's lanes one by one. */
 int gnnmp_gat_conv_stats_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
@@ -692,6 +693,74 @@ int gnnmp_attn_conv_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, int mod
                              const float *V, const float *a, float negative_slope, float scale, const float *stats,
                              const float *dout, float *line, float *dQ, float *dK, float *dV, float *dA, float *da,
                              int64_t H, int64_t C, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attention with a per-edge feature ROW, forward and pullback — gatv2_conv and transformer_conv with `e`, GNNlib/src/layers/conv.jl:171-214
+ * and :553-629 (csrc/attn_edge.hip).  F = dense_e(e) | W6(e), [n_edges][H*C] in ORIGINAL edge order (gnnmp_dense_f32 on the E rows of e);
+ * k = the original position of edge j -> i.  Per head, α_ij = softmax_{j in N(i)} l_ij:
+ *   GNNMP_ATTN_GATV2   z_c = (Q_ic + K_jc) + F_kc,  l_ij = Σ_c a_c leakyrelu(z_c),   o_i = Σ_j α_ij K_j       (the value carries no F: gatv2_message)
+ *   GNNMP_ATTN_DOT     l_ij = Q_i . (K_j + F_k) / scale,                              o_i = Σ_j α_ij (V_j + F_k) (transformer_message_uij / _main)
+ *   gnnmp_attn_conv_edge_f32        out = act(o + bias) (act = identity | relu, bias nullable), stats[i][h] = (m_i, den_i) as in
+ *                                   gnnmp_gat_conv_stats_f32 when the pointer is non-NULL.  One pass over the plan, online softmax; a row
+ *                                   without in-edges gets o_i = 0 and stats (-Inf, 0).
+ *   gnnmp_attn_conv_edge_grad_f32   dout = Δ w.r.t. o.  With g_ij = Δ_i . val_ij (val = K_j | V_j + F_k), D_i = Σ_j α_ij g_ij,
+ *                                   dl_ij = α_ij (g_ij - D_i), s_c = leakyrelu'(z_c), α rebuilt from stats:
+ *                                     GATV2  dQ_ic = a_c Σ_j dl_ij s_c,  dK_jc = Σ_i (a_c dl_ij s_c + α_ij Δ_ic)  (V is K: the whole gradient),
+ *                                            dF_kc = a_c dl_ij s_c,  dA_ic = Σ_j dl_ij leakyrelu(z_c),  da_c = Σ_i dA_ic (rows in order, then a tree)
+ *                                     DOT    dQ_i = Σ_j dl_ij (K_j + F_k) / scale,  dK_j = Σ_i dl_ij Q_i / scale,  dV_j = Σ_i α_ij Δ_i,
+ *                                            dF_k = dl_ij Q_i / scale + α_ij Δ_i
+ *                                   Pass 1 over plan: D_i, dQ_i, dA_i and the line (m, 1/den, D, 0) per (i, h); pass 2 over plan_t: dK_j, dV_j
+ *                                   and dF_k, ONE plain store at the slot's original edge position — an edge is exactly one slot there.
+ *   plan, plan_t   the graph's plan and the plan of the reversed edge index, both built WITHOUT plan-added self loops (conv.jl:178-181
+ *                  forbids edge features with add_self_loops; F has no row for them).  They are only READ and their chunks are ignored:
+ *                  every row is walked whole by one lane group, in slot order — no plan scratch, no atomics, every output element written
+ *                  exactly once, two calls give equal bits, and a capture needs no eager call first.  A hub row is therefore slow.
+ *   job            a const HOST record of device pointers.  Q NULL = K; V NULL = K (a separate V only with DOT).  The gradient record
+ *                  carries the forward's inputs, its stats, dout, the caller's scratch line [n_dst][H][4] (16-byte aligned) and the
+ *                  outputs dQ [n_dst][H*C], dK [n_src][H*C], dF [n_edges][H*C]; DOT: dV [n_src][H*C]; GATV2: dA [n_dst][H*C] and da [H][C]
+ *                  (da nullable).  Every element of every output is written.
+ * The feature row must fit one wave under the rule of gnnmp_gat_conv_stats_f32; F and dF count among the [.][H*C] arrays whose alignment
+ * selects v (GNNMP_EUNSUPPORTED otherwise).  n_edges = 0: the forward writes act(bias) and the empty statistics, the pullback zero dQ, dK,
+ * dV (dA, da) and the line; F and dF may be NULL.  Refused with GNNMP_EINVAL before any HIP call: a NULL plan, job or required pointer; a
+ * NULL F (dF) with n_edges > 0; a mode other than GATV2 / DOT; H or C < 1 or H*C > 2^20; an act other than identity / relu; a plan built
+ * with self loops; a plan_t that is not the plan's transpose; a separate V with GATV2; a line that is not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *Q;    /* [n_dst][H*C] or NULL (= K) */
+    const float *K;    /* [n_src][H*C] */
+    const float *V;    /* [n_src][H*C] or NULL (= K); separate only with DOT */
+    const float *F;    /* [n_edges][H*C], original edge order */
+    const float *a;    /* GATV2: [H][C] */
+    const float *bias; /* [H*C] or NULL */
+    float *out;        /* [n_dst][H*C] */
+    float *stats;      /* [n_dst][H][2] or NULL */
+    float negative_slope;
+    float scale;
+    int act;
+} gnnmp_attn_edge_t;
+int gnnmp_attn_conv_edge_f32(const gnnmp_graph_t *plan, int mode, const gnnmp_attn_edge_t *job, int64_t H, int64_t C,
+                             gnnmp_stream_t stream);
+
+typedef struct {
+    const float *Q;     /* as in the forward */
+    const float *K;
+    const float *V;
+    const float *F;
+    const float *a;
+    const float *stats; /* [n_dst][H][2], from the forward */
+    const float *dout;  /* [n_dst][H*C] */
+    float *line;        /* [n_dst][H][4], 16-byte aligned scratch */
+    float *dQ;          /* [n_dst][H*C] */
+    float *dK;          /* [n_src][H*C] */
+    float *dV;          /* DOT: [n_src][H*C] */
+    float *dF;          /* [n_edges][H*C] */
+    float *dA;          /* GATV2: [n_dst][H*C] */
+    float *da;          /* GATV2: [H][C] or NULL */
+    float negative_slope;
+    float scale;
+} gnnmp_attn_edge_grad_t;
+int gnnmp_attn_conv_edge_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, int mode, const gnnmp_attn_edge_grad_t *job,
+                                  int64_t H, int64_t C, gnnmp_stream_t stream);
 
 /* out[n][c] = act( mean_h y[n][h][c] + bias[c] ) — the concat = false tail of gat_conv (`mean(x, dims = 2)`,
  * GNNlib/src/layers/conv.jl:143-147): heads added in order, one division by H, then σ.(x .+ bias). */
