@@ -27,8 +27,35 @@ HANDLE_TYPES = ("gnnmp_graph_t", "gnnmp_arena_t", "gnnmp_chain_jobs_t")
 HOST_PARAMS = {"result", "result_host", "total", "n_new", "cls", "info", "ptr"}
 
 
+RECORD_TYPE = re.compile(r"\bgnnmp_\w+_t\b")
+
+
+class Header(tuple):
+    """(decls, defines) as it always unpacked, with the header's records on the side: .records = {gnnmp_<x>_t: [(name, is_pointer,
+    is_const, type text)]}, the fields of every `typedef struct { ... } gnnmp_<x>_t;` in declaration order"""
+    records = {}
+
+
+def _fields(body):
+    """the fields of one struct body: `const float *fs_i, *fs_j;` and `float alpha, beta;` are one field a declarator"""
+    out = []
+    for decl in body.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        first, *more = [d.strip() for d in decl.split(",")]
+        m = re.match(r"(.*?)(\**)\s*(\w+)$", first)
+        base, stars, fname = m.group(1).strip(), m.group(2), m.group(3)
+        out.append((fname, bool(stars), base.startswith("const"), f"{base} {stars}{fname}"))
+        for d in more:
+            m = re.match(r"(\**)\s*(\w+)$", d)
+            out.append((m.group(2), bool(m.group(1)), base.startswith("const"), f"{base} {m.group(1)}{m.group(2)}"))
+    return out
+
+
 def parse_header(path=HEADER):
-    """{export: [(name, is_pointer, is_const, type text)]} for every function the header declares, and its #define constants"""
+    """{export: [(name, is_pointer, is_const, type text)]} for every function the header declares, and its #define constants; the
+    result's .records holds the fields of every record type the same way"""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     defines = {m.group(1): m.group(2) for m in re.finditer(r"#define\s+(GNNMP_\w+)\s+(-?\d+)", text)}
@@ -43,7 +70,17 @@ def parse_header(path=HEADER):
                 is_ptr = "*" in p or "[" in p
                 out.append((pname, is_ptr, p.startswith("const"), p))
         decls[name] = out
-    return decls, defines
+    h = Header((decls, defines))
+    h.records = {m.group(2): _fields(m.group(1)) for m in re.finditer(r"typedef struct\s*\{(.*?)\}\s*(gnnmp_\w+_t)\s*;", text, flags=re.S)}
+    return h
+
+
+def record_of(text, records):
+    """the record type a parameter or field of type `text` points at, or None"""
+    for t in RECORD_TYPE.findall(text):
+        if t in records:
+            return t
+    return None
 
 
 def is_host_param(export, pname):
@@ -60,15 +97,50 @@ def device_pointer_params(export, decl):
     return out
 
 
-def must_be_covered(decls, symbols):
-    """the exports the case table owes: in SYMBOLS, take a stream, and write through a device pointer"""
+def record_device_fields(export, rtype, records, seen=()):
+    """[(record type, field, is_const)] of the device-pointer fields a record parameter hands over, nested tables followed (a field that
+    points at another record — the hetero destination's `rels` — is that record's fields, not an array itself)"""
+    out = []
+    for fname, is_ptr, is_const, text in records[rtype]:
+        if not is_ptr or any(h in text for h in HANDLE_TYPES) or is_host_param(export, fname):
+            continue
+        inner = record_of(text, records)
+        if inner is not None:
+            if inner not in seen:
+                out += record_device_fields(export, inner, records, seen + (rtype,))
+            continue
+        out.append((rtype, fname, is_const))
+    return out
+
+
+def writes_of(export, decl, records):
+    """how an export writes device memory: ([non-const pointer parameters], [(record type, non-const pointer field)])"""
+    direct = [n for n, c in device_pointer_params(export, decl) if not c and record_of(dict((p[0], p[3]) for p in decl)[n], records) is None]
+    through = []
+    for pname, is_ptr, is_const, text in decl:
+        rtype = record_of(text, records) if is_ptr else None
+        if rtype is not None:
+            through += [(rt, f) for rt, f, c in record_device_fields(export, rtype, records) if not c]
+    return direct, through
+
+
+def must_be_covered(decls, symbols, records=None, why=None):
+    """the exports the case table owes: in SYMBOLS, take a stream, and write through a device pointer — a non-const pointer parameter, or
+    a non-const pointer field of a record parameter (`const gnnmp_<x>_t *job` is a const HOST record: what it points at is written).
+    records: parse_header().records — the completeness guard passes them; WITHOUT them only the parameters are looked at, which is what
+    the per-family tests mean when they assert that an export "takes const host records" (no device pointer among its parameters).
+    why: a dict that receives {export: 'param' | 'record'}, the first reason an export is owed for"""
+    records = {} if records is None else records
     need = []
     for name in symbols:
         decl = decls.get(name)
         if not decl or not any("gnnmp_stream_t" in p[3] for p in decl):
             continue
-        if any(not c for _, c in device_pointer_params(name, decl)):
+        direct, through = writes_of(name, decl, records)
+        if direct or through:
             need.append(name)
+            if why is not None:
+                why[name] = "param" if direct else "record"
     return need
 
 
@@ -88,9 +160,18 @@ class Arr:
     """one device array of a call.  role: 'in' (const T *: must come back bit for bit), 'out' (every element written), 'inout'
     (initialised by the caller, then compared), 'scratch' (caller-supplied work space: only its guards are checked)"""
 
-    def __init__(self, name, role, data=None, shape=None, dtype=np.float32):
+    def __init__(self, name, role, data=None, shape=None, dtype=np.float32, field=None, base=None, offset=0):
+        """field: the header's name of the parameter / record field when `name` (the slab's key, unique within a call) is another.
+        base, offset: a VIEW — this argument is the pointer `offset` elements into the array `base` (a column block of a panel, a second
+        name for one buffer); it owns no bytes of the slab, its role is what the header says of the field it is passed as, and what may
+        be written where is stated by the role and the reference of the base.  Row strides are scalar fields of the record"""
         assert role in ("in", "out", "inout", "scratch")
-        self.name, self.role = name, role
+        self.name, self.role, self.field, self.base, self.offset = name, role, field or name, base, int(offset)
+        if base is not None:
+            assert data is None and base.base is None and 0 <= self.offset <= max(int(np.prod(base.shape, dtype=np.int64)), 0)
+            assert role == "in" or base.role != "in", f"'{name}' is written through, its base '{base.name}' is an input"
+            self.data, self.shape, self.dtype, self.nbytes, self.off = None, (), base.dtype, 0, None
+            return
         if data is not None:
             self.data = np.ascontiguousarray(data)
             self.shape, self.dtype = self.data.shape, self.data.dtype
@@ -149,6 +230,12 @@ class Slab:
     def ptr(self, name):
         return ctypes.c_void_p(self.t.data_ptr() + self.arrs[name].off)
 
+    def ptr_of(self, a):
+        """the pointer of an argument: an array of the slab, or a view `offset` elements into one"""
+        if a.base is None:
+            return self.ptr(a.name)
+        return ctypes.c_void_p(self.t.data_ptr() + self.arrs[a.base.name].off + a.offset * a.base.dtype.itemsize)
+
     def reload(self, inputs=None):
         """the slab as before a call, at the SAME device addresses: poison in every output, scratch array and guard band, the initial
         data in every in / inout array.  inputs: {name: array} replaces the data of those in / inout arrays (same shape and type)"""
@@ -193,9 +280,13 @@ class Slab:
                 if a.role != "in":
                     owned[a.off:a.off + a.nbytes] = True
         bad = np.flatnonzero((after != self.before) & ~owned)
-        if bad.size:
-            problems.append(f"{bad.size} stray byte(s) written, first {self._where(int(bad[0]))}"
-                            + (" (the call returned an error status)" if untouched else ""))
+        if bad.size:                                # one problem per place: an input array, or the band between two arrays
+            cuts = sorted({0, self.total} | {a.off for a in self.arrs.values()} | {a.off + a.nbytes for a in self.arrs.values()})
+            for lo, hi in zip(cuts, cuts[1:]):
+                here = bad[(bad >= lo) & (bad < hi)]
+                if here.size:
+                    problems.append(f"{here.size} stray byte(s) written, first {self._where(int(here[0]))}"
+                                    + (" (the call returned an error status)" if untouched else ""))
         if untouched:
             return problems
         for name, exp in expected.items():
@@ -311,6 +402,60 @@ class HostOut:
 STREAM = object()
 
 
+class Rec:
+    """a record argument: `const gnnmp_<x>_t *job`, a HOST structure of device pointers and scalars.  fields: in the header's order, each
+    an Arr (or a view of one), None (a NULL pointer), a Pl (a plan handle inside the record), a list of Rec (a nested table: the field
+    points at the first of them) or a scalar"""
+
+    def __init__(rec, ctype, /, **fields):              # positional-only: `self` is a field name of the hop's records
+        rec.ctype, rec.fields = ctype, fields
+
+
+def flat_args(args):
+    """the leaves of an argument list in order, records and nested tables opened"""
+    for a in args:
+        if isinstance(a, Rec):
+            yield from flat_args(a.fields.values())
+        elif isinstance(a, (list, tuple)) and a and all(isinstance(r, Rec) for r in a):
+            yield from flat_args(a)
+        else:
+            yield a
+
+
+def struct_of(ctype):
+    """the ctypes.Structure gnnmp/_lib.py keeps for a record type (its docstring names the type)"""
+    from gnnmp import _lib
+    found = [c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, ctypes.Structure)
+             and (c.__doc__ or "").lstrip().startswith(ctype + ":")]
+    assert len(found) == 1, f"{len(found)} structures of gnnmp/_lib.py say they are {ctype}"
+    return found[0]
+
+
+def _struct(rec, slab, plans, keep):
+    st = struct_of(rec.ctype)()
+    names = [f[0] for f in st._fields_]
+    assert list(rec.fields) == names, f"{rec.ctype}: the case gives {list(rec.fields)}, the structure has {names}"
+    for fname, v in rec.fields.items():
+        if isinstance(v, Arr):
+            setattr(st, fname, slab.ptr_of(v))
+        elif isinstance(v, Pl):
+            setattr(st, fname, plans.get(v))
+        elif isinstance(v, (list, tuple)):
+            setattr(st, fname, _table(v, slab, plans, keep))
+        elif v is not None:
+            setattr(st, fname, v)
+    keep.append(st)
+    return st
+
+
+def _table(recs, slab, plans, keep):
+    assert recs and len({r.ctype for r in recs}) == 1
+    items = [_struct(r, slab, plans, keep) for r in recs]
+    tab = (type(items[0]) * len(items))(*items)          # copies: pointers only, what they point at is kept by `keep`
+    keep.append(tab)
+    return tab
+
+
 def random_graph(name, n, E, seed, n_dst=None):
     rng = np.random.default_rng(seed)
     nd = n if n_dst is None else n_dst
@@ -379,12 +524,19 @@ def plan_threshold(lib, n_edges):
 # a case and its run
 # ------------------------------------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None):
+    def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None, no_warmup=False):
         self.export, self.sid, self.args, self.ref, self.guard, self.status = export, sid, args, ref, guard, status
         self.knobs = knobs or {}                   # gnnmp_tune settings for the call (the previous values come back after it)
         self.align_status = align_status or {}     # {array name: status the header documents for an under-aligned pointer}
-        self.arrs = [a for a in args if isinstance(a, Arr)]
-        self.uses_plan = any(isinstance(a, Pl) for a in args)
+        leaves = list(flat_args(args))
+        self.arrs = []                             # the arrays the slab holds: every Arr of the call, records opened; a view counts as its base
+        for a in leaves:
+            if isinstance(a, Arr):
+                b = a if a.base is None else a.base
+                if not any(b is x for x in self.arrs):
+                    self.arrs.append(b)
+        self.uses_plan = any(isinstance(a, Pl) for a in leaves)
+        self.no_warmup = no_warmup                 # the header: "may be recorded into a HIP graph without an eager call first"
 
 
 def bind(case, slab, plans, stream=None):
@@ -392,7 +544,19 @@ def bind(case, slab, plans, stream=None):
     host, cargs = {}, []
     for a in case.args:
         if isinstance(a, Arr):
-            cargs.append(slab.ptr(a.name))
+            cargs.append(slab.ptr_of(a))
+        elif isinstance(a, Rec) or (isinstance(a, (list, tuple)) and a and isinstance(a[0], Rec)):
+            keep = []                  # the structures live as long as the argument does: byref keeps `obj`, obj keeps the rest
+            if isinstance(a, Rec):
+                obj = _struct(a, slab, plans, keep)
+                arg = ctypes.byref(obj)                                  # (keeps obj)
+            else:
+                obj = _table(a, slab, plans, keep)
+                arg = ctypes.cast(obj, ctypes.POINTER(obj._type_))       # a table is passed as the pointer to its first record (keeps obj)
+            obj._keep = keep
+            if not isinstance(a, Rec):
+                arg._keep_table = obj                                    # the records of the table, for whoever inspects the call
+            cargs.append(arg)
         elif isinstance(a, Pl):
             cargs.append(plans.get(a))
         elif isinstance(a, HostOut):
@@ -1848,6 +2012,550 @@ def _(ctx):
                   Arr("t1", "out", shape=(size1,), dtype=dt), Arr("s2", "out", shape=(E_ - size1,), dtype=dt), Arr("t2", "out", shape=(E_ - size1,), dtype=dt), STREAM], ref)
 
 
+# ---- exports that take a record ----------------------------------------------------------------------------------------------------
+# `const gnnmp_<x>_t *job` is a const HOST structure; what its non-const pointer fields point at is written.  The references are the
+# float64 / exact restatements of tests/*_ref.py that each family's own test file uses (imported, not restated); the operands are drawn
+# here, through rng_of, so that variant 1 of a case is the same call on other values.
+def _mod(name):
+    import importlib
+    return importlib.import_module(name)
+
+
+def part_E(init, mask, value, exact=None, **kw):
+    """an in-out buffer of which the call owes only the elements of `mask` (step t of a [N][T][..] history, a column block of a panel):
+    they are compared with `value` (the caller fills them with NaN, so one that was not written is not finite), every other element must
+    keep the bits of `init`.  exact: the owed elements that are documented exact values (zeros of a NULL state)"""
+    mask = np.broadcast_to(mask, init.shape).copy()
+    kept = np.ascontiguousarray(init).view(np.uint32)[~mask].copy()
+
+    def pred(got):
+        return None if np.array_equal(np.ascontiguousarray(got).view(np.uint32)[~mask], kept) else "an element outside the part the call writes changed"
+    return E(np.where(mask, value, 0.0), rows=mask, pred=pred, exact_rows=None if exact is None else np.broadcast_to(exact, init.shape)[mask], **kw)
+
+
+def _hist(r, shape, t, cols=slice(None), given=None):
+    """a [N][T][W] history: random everywhere, step t's `cols` NaN (to be written) or `given`; returns (array, mask of step t's cols)"""
+    a = F(r, *shape)
+    m = np.zeros(shape, bool)
+    m[:, t, cols] = True
+    a[m] = np.nan if given is None else np.asarray(given, f32).reshape(-1)
+    return a, m
+
+
+def _strided(r, name, role, N, D, ld, off, key=None, block=None):
+    """rows of D floats with stride ld starting `off` floats into a buffer [N][ld] of its own: (buffer Arr, view Arr, mask of the block).
+    block: the values of the block (else random for an input, NaN for an output)"""
+    buf = F(r, N, ld)
+    m = np.zeros((N, ld), bool)
+    m[:, off:off + D] = True
+    if block is not None:
+        buf[m] = np.asarray(block, f32).reshape(-1)
+    elif role != "in":
+        buf[m] = np.nan
+    base = Arr(key or name + "_buf", "in" if role == "in" else "inout", buf)
+    return base, Arr(name, role, base=base, offset=off), m
+
+
+GATE_NS, GATE_T, GATE_TS, GATE_DS = (1, 37, 300), 3, (0, 2), (1, 5, 6, 8, 260)
+GATE_ALIGN = ((37, 5), (37, 6), (37, 8))
+
+
+def _gate_shapes():
+    """(k, N, D, t, state kind, rep, flag, tags): every (N, D); t, the kind of state, rep and the optional fields rotate so that every
+    pair of them occurs"""
+    k = 0
+    for N in GATE_NS:
+        for D in GATE_DS:
+            tags = ({"align"} if (N, D) in GATE_ALIGN else set()) | ({"side"} if k == 0 else set())
+            yield k, N, D, GATE_TS[(k // 2) % 2], ("mat", "vec", "null")[k % 3], 1 + k % 2, (k // 3) % 2 == 0, tags
+            k += 1
+
+
+def _gate_ops(r, N, D, G):
+    """the operands of tests/recurrent_ref.py: gate_case, drawn from the case's generator"""
+    T = GATE_T
+    return dict(P=F(r, N, T, G * D), a=F(r, N, G * D), h=F(r, N, D), hvec=F(r, D), dy=F(r, N, T, D), carry=F(r, N, D), carry2=F(r, N, 2 * D),
+                drh=F(r, N, 2 * D), carry_c=F(r, N, D), w=(0.5 * F(r, 4, D)).astype(f32), cnew_in=F(r, N, T, D))
+
+
+def _state(r, ops, kind, N, D, name):
+    """(extra slab arrays, the field's value, stride): [N][D] inside a wider buffer at an odd column, one vector, NULL"""
+    if kind == "null":
+        return None, 0
+    if kind == "vec":
+        return Arr(name, "in", ops["hvec"]), 0
+    base, view, _ = _strided(r, name, "in", N, D, 2 * D + 3, 3, block=ops["h"])
+    return view, 2 * D + 3
+
+
+@cases_of("gnnmp_gru_cell_f32")
+def _(ctx):
+    RR = _mod("recurrent_ref")
+    for k, N, D, t, hk, rep, flag, tags in _gate_shapes():
+        for phase in (0, 1):
+            r = rng_of("gru_cell", N, D, phase)
+            ops = _gate_ops(r, N, D, 3)
+            T = GATE_T
+            f = RR.gru_forward(ops, hk, t)
+            h, ldh = _state(r, ops, hk, N, D, "h")
+            ldo = rep * D + 5
+            want_hout = phase == 0 or flag
+            hb, hv, hm = _strided(r, "hout", "out", N, rep * D, ldo, 2)
+            if phase == 0:
+                a = ops["a"][:, :2 * D]
+                gates, gm = _hist(r, (N, T, 3 * D), t, slice(0, 2 * D))
+                y = None
+            else:
+                a = ops["a"][:, 2 * D:]
+                gates, gm = _hist(r, (N, T, 3 * D), t, slice(2 * D, 3 * D))
+                gates[:, t, D:2 * D] = f["z"]                    # phase 1 reads z where phase 0 left it
+                yinit, ym = _hist(r, (N, T, D), t)
+                y = Arr("y", "inout", yinit)
+
+            def ref(host, f=f, phase=phase, gates=gates, gm=gm, hb=hb, hm=hm, rep=rep, hk=hk, y=y, t=t, D=D, want_hout=want_hout):
+                g = np.zeros(gates.shape)
+                if phase == 0:
+                    g[:, t, :D], g[:, t, D:2 * D] = f["r"], f["z"]
+                    block = np.tile(f["rh"], (1, rep))
+                else:
+                    g[:, t, 2 * D:] = f["c"]
+                    block = np.tile(f["hn"], (1, rep))
+                out = {"gates": part_E(gates, gm, g)}
+                if want_hout:
+                    full = np.zeros(hb.data.shape)
+                    full[hm] = block.reshape(-1)
+                    out["hout_buf"] = part_E(hb.data, hm, full, exact=(hm if phase == 0 and hk == "null" else None))      # r * 0: an exact zero
+                if phase == 1:
+                    yy = np.zeros(y.data.shape)
+                    yy[:, t] = f["hn"]
+                    out["y"] = part_E(y.data, np.isnan(y.data), yy)
+                return out
+            job = Rec("gnnmp_gru_cell_t", P=Arr("P", "in", ops["P"]), a=Arr("a", "in", a), h=h, ldh=ldh, gates=Arr("gates", "inout", gates),
+                      hout=hv if want_hout else None, ldhout=ldo, rep=rep, y=y)
+            yield mk("gnnmp_gru_cell_f32", f"N{N}_D{D}_t{t}_{hk}_rep{rep}_p{phase}{'' if want_hout else '_nohout'}", tags if phase == 0 else tags - {"side"},
+                     [phase, job, N, T, t, D, STREAM], ref, no_warmup=True)
+
+
+@cases_of("gnnmp_gru_cell_grad_f32")
+def _(ctx):
+    RR = _mod("recurrent_ref")
+    for k, N, D, t, hk, rep, flag, tags in _gate_shapes():
+        for phase in (1, 0):
+            r = rng_of("gru_cell_grad", N, D, phase)
+            ops = _gate_ops(r, N, D, 3)
+            T = GATE_T
+            carries = ((True, True), (False, False), (False, True), (True, False))[k % 4]
+            b = RR.gru_backward(ops, hk, t, rep, carries)
+            gates = F(r, N, T, 3 * D)
+            gates[:, t] = np.concatenate([b["r"], b["z"], b["c"]], 1)                 # what the forward kept
+            h, ldh = _state(r, ops, hk, N, D, "h")
+            ld2 = 2 * D + 1
+            zero_r = hk == "null"                                                        # h = 0: dr_pre is an exact zero
+            if phase == 1:
+                _, c2, _ = _strided(r, "carry2", "in", N, rep * D, ld2, 1, block=ops["carry2"][:, :rep * D])
+                dP, pm = _hist(r, (N, T, 3 * D), t, slice(D, 3 * D))
+                darz = F(r, N, 2 * D)
+                darz[:, D:] = np.nan
+                job = Rec("gnnmp_gru_cell_grad_t", dy=Arr("dy", "in", ops["dy"]), carry=Arr("carry", "in", ops["carry"]) if carries[0] else None,
+                          carry2=c2 if carries[1] else None, ldc2=ld2, gates=Arr("gates", "in", gates), h=h, ldh=ldh, drh=None, lddrh=ld2, rep=rep,
+                          dP=Arr("dP", "inout", dP), dac=Arr("dac", "out", shape=(N, D)), darz=Arr("darz", "inout", darz), part=Arr("part", "out", shape=(N, D)))
+
+                def ref(host, b=b, dP=dP, pm=pm, darz=darz, t=t, D=D):
+                    p = np.zeros(dP.shape)
+                    p[:, t, D:2 * D], p[:, t, 2 * D:] = b["dz"], b["dc"]
+                    return {"dP": part_E(dP, pm, p), "dac": b["dc"], "darz": part_E(darz, np.isnan(darz), np.concatenate([b["dz"], b["dz"]], 1)),
+                            "part": b["part1"]}
+            else:
+                _, dv, _ = _strided(r, "drh", "in", N, rep * D, ld2, 1, block=ops["drh"][:, :rep * D])
+                dP, pm = _hist(r, (N, T, 3 * D), t, slice(0, D))
+                darz = F(r, N, 2 * D)
+                darz[:, :D] = np.nan
+                part0 = F(r, N, D)
+                job = Rec("gnnmp_gru_cell_grad_t", dy=None, carry=None, carry2=None, ldc2=0, gates=Arr("gates", "in", gates), h=h, ldh=ldh, drh=dv,
+                          lddrh=ld2, rep=rep, dP=Arr("dP", "inout", dP), dac=None, darz=Arr("darz", "inout", darz), part=Arr("part", "inout", part0))
+
+                def ref(host, b=b, dP=dP, pm=pm, darz=darz, part0=part0, t=t, D=D, zero_r=zero_r):
+                    p = np.zeros(dP.shape)
+                    p[:, t, :D] = b["dr"]
+                    am = np.isnan(darz)
+                    return {"dP": part_E(dP, pm, p, exact=pm if zero_r else None),
+                            "darz": part_E(darz, am, np.concatenate([b["dr"], b["dr"]], 1), exact=am if zero_r else None),
+                            "part": part0.astype(f64) + (b["part"] - b["part1"])}
+            yield mk("gnnmp_gru_cell_grad_f32", f"N{N}_D{D}_t{t}_{hk}_rep{rep}_p{phase}_c{int(carries[0])}{int(carries[1])}", tags if phase == 1 else tags - {"side"},
+                     [phase, job, N, T, t, D, STREAM], ref, no_warmup=True)
+
+
+@cases_of("gnnmp_lstm_cell_f32")
+def _(ctx):
+    RR = _mod("recurrent_ref")
+    for k, N, D, t, ck, rep, flag, tags in _gate_shapes():
+        r = rng_of("lstm_cell", N, D)
+        ops = _gate_ops(r, N, D, 4)
+        T = GATE_T
+        f = RR.lstm_forward(ops, ck, t)
+        c, ldc = _state(r, ops, ck, N, D, "c")
+        hb, hv, hm = _strided(r, "hout", "out", N, D, D + 5, 2)
+        gates, gm = _hist(r, (N, T, 4 * D), t)
+        cnew, cm = _hist(r, (N, T, D), t)
+        y, ym = _hist(r, (N, T, D), t)
+
+        def ref(host, f=f, gates=gates, gm=gm, cnew=cnew, cm=cm, y=y, ym=ym, hb=hb, hm=hm, t=t, flag=flag):
+            g, cn, yy = np.zeros(gates.shape), np.zeros(cnew.shape), np.zeros(y.shape)
+            g[:, t], cn[:, t], yy[:, t] = np.concatenate([f["i"], f["f"], f["g"], f["o"]], 1), f["cn"], f["hn"]
+            out = {"gates": part_E(gates, gm, g), "cnew": part_E(cnew, cm, cn), "y": part_E(y, ym, yy)}
+            if flag:
+                full = np.zeros(hb.data.shape)
+                full[hm] = f["hn"].reshape(-1)
+                out["hout_buf"] = part_E(hb.data, hm, full)
+            return out
+        job = Rec("gnnmp_lstm_cell_t", P=Arr("P", "in", ops["P"]), a=Arr("a", "in", ops["a"]), w=Arr("w", "in", ops["w"]), c=c, ldc=ldc,
+                  gates=Arr("gates", "inout", gates), cnew=Arr("cnew", "inout", cnew), hout=hv if flag else None, ldhout=D + 5, y=Arr("y", "inout", y))
+        yield mk("gnnmp_lstm_cell_f32", f"N{N}_D{D}_t{t}_{ck}{'' if flag else '_nohout'}", tags, [job, N, T, t, D, STREAM], ref, no_warmup=True)
+
+
+@cases_of("gnnmp_lstm_cell_grad_f32")
+def _(ctx):
+    RR = _mod("recurrent_ref")
+    for k, N, D, t, ck, rep, flag, tags in _gate_shapes():
+        r = rng_of("lstm_cell_grad", N, D)
+        ops = _gate_ops(r, N, D, 4)
+        T = GATE_T
+        carries = ((True, True), (False, False), (True, False), (False, True))[k % 4]
+        b = RR.lstm_backward(ops, ck, t, carries)
+        gates, cnew = F(r, N, T, 4 * D), F(r, N, T, D)
+        gates[:, t], cnew[:, t] = np.concatenate([b["i"], b["f"], b["g"], b["o"]], 1), b["cn"]          # what the forward kept
+        c, ldc = _state(r, ops, ck, N, D, "c")
+        _, chv, _ = _strided(r, "carry_h", "in", N, D, D + 3, 1, block=ops["carry"])
+        dP, pm = _hist(r, (N, T, 4 * D), t)
+        peep, qm = _hist(r, (N, T, 4 * D), t)
+
+        def ref(host, b=b, dP=dP, pm=pm, peep=peep, qm=qm, t=t, D=D, ck=ck, flag=flag):
+            p, q = np.zeros(dP.shape), np.zeros(peep.shape)
+            p[:, t], q[:, t] = b["da"], b["peep"]
+            out = {"dP": part_E(dP, pm, p), "da": b["da"], "dc": b["dc"]}
+            if flag:
+                zero = np.zeros(peep.shape, bool)
+                zero[:, t, :3 * D] = ck == "null"                       # c = 0: the first three products are exact zeros
+                out["peep"] = part_E(peep, qm, q, exact=zero if ck == "null" else None)
+            return out
+        job = Rec("gnnmp_lstm_cell_grad_t", dy=Arr("dy", "in", ops["dy"]), carry_h=chv if carries[0] else None, ldch=D + 3,
+                  carry_c=Arr("carry_c", "in", ops["carry_c"]) if carries[1] else None, gates=Arr("gates", "in", gates), w=Arr("w", "in", ops["w"]), c=c,
+                  ldc=ldc, cnew=Arr("cnew", "in", cnew), dP=Arr("dP", "inout", dP), da=Arr("da", "out", shape=(N, 4 * D)), dc=Arr("dc", "out", shape=(N, D)),
+                  peep=Arr("peep", "inout", peep) if flag else None)
+        yield mk("gnnmp_lstm_cell_grad_f32", f"N{N}_D{D}_t{t}_{ck}_c{int(carries[0])}{int(carries[1])}{'' if flag else '_nopeep'}", tags,
+                 [job, N, T, t, D, STREAM], ref, no_warmup=True)
+
+
+# the hop: every combination class of its nullable factors and terms (tests/test_recurrent_layers.py: HOP_COMBOS), in the order
+# (w_slot, ss_slot, scale_dst, self, prev, add)
+HOP_COMBOS = ((True,) * 6, (False,) * 6, (True, False, True, False, True, False), (False, True, False, True, False, True),
+              (True, True, False, True, True, False), (False, False, True, False, False, True))
+HOP_DS = (1, 3, 6, 8, 129, 260)      # 4-byte lanes (odd), 8-byte (% 2), 16-byte (% 4); a second feature tile at 4-byte (129) and at 16-byte lanes (260)
+
+
+def _hop_operands(r, g, T, D, combo):
+    """(s0, t0, operands in float32, slot order) of a hop over the plan (T: the transposed plan) of g"""
+    s0, t0 = ((g.t, g.s) if T else (g.s, g.t))
+    s0, t0 = s0 - 1, t0 - 1
+    n_src, n_dst = (g.n_dst, g.n_src) if T else (g.n_src, g.n_dst)
+    on = dict(zip(("w", "ss", "sd", "self_", "prev", "add"), combo))
+    ops = dict(z=F(r, n_src, D), w=(1.0 + 0.5 * F(r, g.E)).astype(f32), ss=(1.0 + 0.5 * F(r, g.E)).astype(f32), sd=(1.0 + 0.5 * F(r, n_dst)).astype(f32),
+               self_=F(r, n_dst, D), prev=F(r, n_dst, D), add=F(r, n_dst, D))
+    return s0, t0, n_dst, {k: v for k, v in ops.items() if k == "z" or on[k]}, np.argsort(t0, kind="stable")
+
+
+def _hop_ref(s0, t0, n_dst, ops, coef):
+    R = _mod("poly_conv_ref")
+    kw = {k: v.astype(f64) for k, v in ops.items() if k != "z"}
+    return R.hop(s0, t0, n_dst, ops["z"].astype(f64), alpha=coef[0], beta=coef[1], gam=coef[2], **kw)
+
+
+def _hop_coef(ops):
+    R = _mod("poly_conv_ref")
+    return R.ALPHA, R.BETA if "self_" in ops else 0.0, R.GAMMA if "prev" in ops else 0.0
+
+
+@cases_of("gnnmp_poly_hop_f32")
+def _(ctx):
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(HOP_DS, small=(3, 8), align=(3, 6, 8), ws=(8,), rows300=(1, 260))):
+        T = k % 2 == 1
+        combo = HOP_COMBOS[k % 6]
+        r = rng_of("poly_hop", g.name, D)
+        s0, t0, n_dst, ops, order = _hop_operands(r, g, T, D, combo)
+        coef = _hop_coef(ops)
+        alias = {3: "prev", 4: "add"}.get(k % 5)                   # out MAY BE prev OR add
+        alias = alias if alias in ops else None
+        A_ = lambda nm, key, v: Arr(nm, "in", v) if key in ops else None      # noqa: E731
+        f = dict(z=Arr("z", "in", ops["z"]), w_slot=A_("w_slot", "w", ops.get("w", np.zeros(0))[order] if "w" in ops else None),
+                 ss_slot=A_("ss_slot", "ss", ops["ss"][order] if "ss" in ops else None), scale_dst=A_("scale_dst", "sd", ops.get("sd")),
+                 self=A_("self", "self_", ops.get("self_")), prev=A_("prev", "prev", ops.get("prev")), add=A_("add", "add", ops.get("add")))
+        out = Arr("out", "out", shape=(n_dst, D))
+        name = "out"
+        if alias:
+            both = Arr(alias + "_out", "inout", ops[alias])
+            f[alias], out, name = Arr(alias, "in", base=both), Arr("out", "out", base=both), alias + "_out"
+        ref = lambda host, a=(s0, t0, n_dst, ops, coef), name=name: {name: _hop_ref(*a)}
+        job = Rec("gnnmp_poly_hop_t", **f, alpha=coef[0], beta=coef[1], gamma=coef[2], out=out)
+        yield mk("gnnmp_poly_hop_f32", f"{g.name}_D{D}_{'T' if T else 'P'}_c{k % 6}{'_out_is_' + alias if alias else ''}", tags,
+                 [Pl(g, T=T), job, D, STREAM], ref, no_warmup=True)
+
+
+def _ld_modes(D):
+    """row strides in floats: D itself; odd (4-byte lanes whatever D is); a multiple of 2 and not of 4 (8-byte lanes at most); of 4"""
+    odd = (D + 1) | 1
+    two = D + 1
+    while two % 4 != 2:
+        two += 1
+    return {"ldD": D, "odd": odd, "ld8": two, "ld16": (D + 4) // 4 * 4}
+
+
+@cases_of("gnnmp_poly_hop_ld_f32")
+def _(ctx):
+    # 1. every operand in a buffer of its own with its own stride: each can be shifted alone (the lane width is decided over every given
+    #    pointer AND every given stride)
+    shapes = [(g, D, set(tags), ("ldD", "odd", "ld8", "ld16")[k % 4]) for k, (g, D, tags) in
+              enumerate(ctx.graph_shapes((1, 3, 6, 8, 260), small=(6,), align=(), ws=(8,), rows300=(1,)))]
+    shapes += [(ctx.hub, 8, {"align"}, "ld8"), (ctx.hub, 8, {"align"}, "ld16"), (ctx.hub, 6, {"align"}, "ld8"), (ctx.hub, 6, set(), "odd"),
+               (ctx.hub, 8, set(), "odd"), (ctx.r300, 260, set(), "ld8")]
+    for k, (g, D, tags, mode) in enumerate(shapes):
+        T = k % 2 == 1
+        combo = HOP_COMBOS[k % 6]
+        r = rng_of("poly_hop_ld", g.name, D, mode)
+        s0, t0, n_dst, ops, order = _hop_operands(r, g, T, D, combo)
+        coef = _hop_coef(ops)
+        ld = _ld_modes(D)[mode]
+        lds = {"z": ld, "self": D if k % 3 == 0 else ld, "prev": ld, "add": _ld_modes(D)["ld16"] if k % 3 == 1 else ld, "out": ld}      # the strides of one call need not agree
+        f, held = {}, {}
+        for nm, key in (("z", "z"), ("self", "self_"), ("prev", "prev"), ("add", "add")):
+            if key in ops:
+                n_rows = ops[key].shape[0]
+                held[nm] = _strided(r, nm, "in", n_rows, D, lds[nm], 0, block=ops[key])
+            else:
+                F(r, n_dst, lds[nm])                                # the draws stay in step
+            f[nm] = held[nm][1] if nm in held else None
+        ob, ov, om = _strided(r, "out", "out", n_dst, D, lds["out"], 0)
+
+        def ref(host, a=(s0, t0, n_dst, ops, coef), ob=ob, om=om):
+            full = np.zeros(ob.data.shape)
+            full[om] = _hop_ref(*a).reshape(-1)
+            return {"out_buf": part_E(ob.data, om, full)}
+        job = Rec("gnnmp_poly_hop_ld_t", z=f["z"], w_slot=Arr("w_slot", "in", ops["w"][order]) if "w" in ops else None,
+                  ss_slot=Arr("ss_slot", "in", ops["ss"][order]) if "ss" in ops else None, scale_dst=Arr("scale_dst", "in", ops["sd"]) if "sd" in ops else None,
+                  self=f["self"], prev=f["prev"], add=f["add"], alpha=coef[0], beta=coef[1], gamma=coef[2], out=ov,
+                  ld_z=lds["z"], ld_self=lds["self"], ld_prev=lds["prev"], ld_add=lds["add"], ld_out=lds["out"])
+        yield mk("gnnmp_poly_hop_ld_f32", f"{g.name}_D{D}_{mode}_{'T' if T else 'P'}_c{k % 6}_k{k}", tags, [Pl(g, T=T), job, D, STREAM], ref, no_warmup=True)
+    # 2. column blocks of ONE panel [n][ld] (tests/test_recurrent_layers.py: PANELS); self in a buffer of its own with stride D, or the z
+    #    block itself (cheb_conv's call); out a block of its own, or the prev / add block
+    panels = [(8, 48, dict(z=0, prev=8, add=16, out=24)), (8, 45, dict(z=0, prev=8, add=16, out=24)), (6, 40, dict(z=1, prev=9, add=17, out=25)),
+              (6, 42, dict(z=0, prev=6, add=12, out=18)), (260, 1100, dict(z=4, prev=268, add=532, out=796))]
+    for k, (D, ld, cols) in enumerate(panels):
+        for j, (g, alias) in enumerate(((ctx.hub, None), (ctx.r33, "prev"), (ctx.hub, "add"))):
+            T = (k + j) % 2 == 1
+            r = rng_of("poly_hop_ld_panel", g.name, D, ld, alias)
+            s0, t0, n_dst, ops, order = _hop_operands(r, g, T, D, (True,) * 6)
+            self_is_z = j == 2
+            if self_is_z:
+                ops["self_"] = ops["z"]
+            coef = _hop_coef(ops)
+            pan = F(r, g.n, ld)
+            for nm in ("z", "prev", "add"):
+                pan[:, cols[nm]:cols[nm] + D] = ops[nm]
+            oc = cols[alias or "out"]
+            om = np.zeros(pan.shape, bool)
+            om[:, oc:oc + D] = True
+            if not alias:
+                pan[om] = np.nan
+            P = Arr("panel", "inout", pan)
+            V = lambda nm, role="in": Arr(nm, role, base=P, offset=cols[nm])      # noqa: E731
+
+            def ref(host, a=(s0, t0, n_dst, ops, coef), pan=pan, om=om):
+                full = np.zeros(pan.shape)
+                full[om] = _hop_ref(*a).reshape(-1)
+                return {"panel": part_E(pan, om, full)}
+            job = Rec("gnnmp_poly_hop_ld_t", z=V("z"), w_slot=Arr("w_slot", "in", ops["w"][order]), ss_slot=Arr("ss_slot", "in", ops["ss"][order]),
+                      scale_dst=Arr("scale_dst", "in", ops["sd"]), self=Arr("self", "in", base=P, offset=cols["z"]) if self_is_z else Arr("self", "in", ops["self_"]),
+                      prev=V("prev"), add=V("add"), alpha=coef[0], beta=coef[1], gamma=coef[2], out=Arr("out", "out", base=P, offset=oc),
+                      ld_z=ld, ld_self=ld if self_is_z else D, ld_prev=ld, ld_add=ld, ld_out=ld)
+            tags = ({"align"} if (D, ld) in ((8, 48), (6, 42)) and alias is None else set()) | ({"ws"} if (k, j) == (0, 0) else set())
+            yield mk("gnnmp_poly_hop_ld_f32", f"panel_{g.name}_D{D}_ld{ld}_{'T' if T else 'P'}_out_{alias or 'own'}{'_self_is_z' if self_is_z else ''}", tags,
+                     [Pl(g, T=T), job, D, STREAM], ref, no_warmup=True)
+
+
+def _nd_shapes(Ds, N0=37, align=(), extra=((1, 3), (300, 5), (300, 130))):
+    """(N, D, tags) of a kernel that runs a thread an element over [N][D]"""
+    for k, D in enumerate(Ds):
+        yield N0, D, ({"align"} if D in align else set()) | ({"side"} if k == 0 else set())
+    for N, D in extra:
+        yield N, D, set()
+
+
+@cases_of("gnnmp_gru_pointwise_grad_f32")
+def _(ctx):
+    G = _mod("gated_conv_ref")
+    for k, (N, D, tags) in enumerate(_nd_shapes(G.GRU_DS, G.GRU_N, align=(3, 4, 130))):
+        r = rng_of("gru_pointwise_grad", N, D)
+        gx, gh, b, h, dout, base = F(r, N, 3 * D), F(r, N, 3 * D), F(r, 3 * D), F(r, N, D), F(r, N, D), F(r, N, D)
+        with_b, with_base, alias = k % 2 == 0, k % 3 != 1, k % 3 == 2                     # base MAY BE dh
+        dgx, dgh, dh = G.gru_grad(*[None if a is None else a.astype(f64) for a in (gx, gh, b if with_b else None, h, dout, base if with_base else None)])
+        f = dict(gx=Arr("gx", "in", gx), gh=Arr("gh", "in", gh), b=Arr("b", "in", b) if with_b else None, h=Arr("h", "in", h), dout=Arr("dout", "in", dout),
+                 base=Arr("base", "in", base) if with_base else None, dgx=Arr("dgx", "out", shape=(N, 3 * D)), dgh=Arr("dgh", "out", shape=(N, 3 * D)),
+                 dh=Arr("dh", "out", shape=(N, D)))
+        name = "dh"
+        if alias:
+            both = Arr("base_dh", "inout", base)
+            f["base"], f["dh"], name = Arr("base", "in", base=both), Arr("dh", "out", base=both), "base_dh"
+        yield mk("gnnmp_gru_pointwise_grad_f32", f"N{N}_D{D}_b{int(with_b)}_base{int(with_base)}{'_is_dh' if alias else ''}", tags,
+                 [Rec("gnnmp_gru_grad_t", **f), N, D, STREAM], lambda host, v=(dgx, dgh, dh), name=name: {"dgx": v[0], "dgh": v[1], name: v[2]}, no_warmup=True)
+
+
+@cases_of("gnnmp_lstm_pointwise_grad_f32")
+def _(ctx):
+    R = _mod("readout_ref")
+    for k, (N, D, tags) in enumerate(_nd_shapes((1, 2, 3, 4, 5, 8, 33, 130), align=(3, 4, 130))):
+        r = rng_of("lstm_pointwise_grad", N, D)
+        gx, gh, b, c, dh, dcn = F(r, N, 4 * D), F(r, N, 4 * D), F(r, 4 * D), F(r, N, D), F(r, N, D), F(r, N, D)
+        with_b, with_dcn = k % 2 == 0, k % 3 != 1
+        da, dc = R.lstm_grad(*[None if a is None else a.astype(f64) for a in (gx, gh, b if with_b else None, c, dh, dcn if with_dcn else None)])
+        job = Rec("gnnmp_lstm_grad_t", gx=Arr("gx", "in", gx), gh=Arr("gh", "in", gh), b=Arr("b", "in", b) if with_b else None, c=Arr("c", "in", c),
+                  dh=Arr("dh", "in", dh), dcn=Arr("dcn", "in", dcn) if with_dcn else None, da=Arr("da", "out", shape=(N, 4 * D)), dc=Arr("dc", "out", shape=(N, D)))
+        yield mk("gnnmp_lstm_pointwise_grad_f32", f"N{N}_D{D}_b{int(with_b)}_dcn{int(with_dcn)}", tags, [job, N, D, STREAM],
+                 lambda host, v=(da, dc): {"da": v[0], "dc": v[1]}, no_warmup=True)
+
+
+def _pool_shapes():
+    """(D, Dg code, tags): QUERY (0), one gate weight (1), a gate per channel (2) at every width of tests/readout_ref.py"""
+    R = _mod("readout_ref")
+    k = 0
+    for D in R.WIDTHS:
+        for mode in (0, 1, 2):
+            yield D, mode, ({"align"} if (D, mode) in ((8, 0), (2, 1), (130, 2), (3, 0)) else set()) | ({"side"} if k == 0 else set())
+            k += 1
+
+
+def _pool_operands(r, D, mode):
+    R = _mod("readout_ref")
+    ptr = R.ptr_of(R.SEGS_ABI)                                   # an empty segment in the middle and one at the end
+    N, G = int(ptr[-1]), len(R.SEGS_ABI)
+    Dg = (0, 1, D)[mode]
+    x = F(r, N, D)
+    q = (F(r, G, D) * (2.0 / np.sqrt(D))).astype(f32)            # logits of order one
+    gate = (2.0 * F(r, N, max(Dg, 1))).astype(f32)
+    return ptr, N, G, Dg, x, q if mode == 0 else None, gate if mode else None, F(r, G, D), F(r, N, D)
+
+
+@cases_of("gnnmp_segment_attn_pool_f32")
+def _(ctx):
+    R = _mod("readout_ref")
+    for D, mode, tags in _pool_shapes():
+        r = rng_of("segment_attn_pool", D, mode)
+        ptr, N, G, Dg, x, q, gate, _, _ = _pool_operands(r, D, mode)
+        ref = lambda host, a=(x, ptr, q, gate): dict(zip(("r", "stats"), R.pool(a[0].astype(f64), a[1], *R.cast(f64, a[2], a[3]))))
+        job = Rec("gnnmp_segment_attn_t", x=Arr("x", "in", x), seg_ptr=Arr("seg_ptr", "in", ptr), q=Arr("q", "in", q) if q is not None else None,
+                  gate=Arr("gate", "in", gate) if gate is not None else None, r=Arr("r", "out", shape=(G, D)), stats=Arr("stats", "out", shape=(G, max(Dg, 1), 2)))
+        yield mk("gnnmp_segment_attn_pool_f32", f"D{D}_Dg{Dg}_m{mode}", tags, [job, N, G, D, Dg, STREAM], ref, no_warmup=True)
+
+
+@cases_of("gnnmp_segment_attn_pool_grad_f32")
+def _(ctx):
+    R = _mod("readout_ref")
+    for k, (D, mode, tags) in enumerate(_pool_shapes()):
+        r = rng_of("segment_attn_pool_grad", D, mode)
+        ptr, N, G, Dg, x, q, gate, dr, base = _pool_operands(r, D, mode)
+        x64, q64, g64, dr64, b64 = R.cast(f64, x, q, gate, dr, base)
+        r64, st64 = R.pool(x64, ptr, q64, g64)
+        how = ("base", "none", "base_is_dx", "no_dx", "only_dx")[k % 5]                      # each output is optional, base MAY BE dx
+        dq, dx, dgate = R.pool_grad(dr64, x64, ptr, r64, st64, q64, g64, b64 if how in ("base", "base_is_dx") else None)
+        f = dict(dr=Arr("dr", "in", dr), x=Arr("x", "in", x), seg_ptr=Arr("seg_ptr", "in", ptr), q=Arr("q", "in", q) if q is not None else None,
+                 gate=Arr("gate", "in", gate) if gate is not None else None, r=Arr("r", "in", r64.astype(f32)), stats=Arr("stats", "in", st64.astype(f32)),
+                 base=Arr("base", "in", base) if how == "base" else None,
+                 dq=Arr("dq", "out", shape=(G, D)) if mode == 0 and how != "only_dx" else None, dx=Arr("dx", "out", shape=(N, D)) if how != "no_dx" else None,
+                 dgate=Arr("dgate", "out", shape=(N, Dg)) if mode and how != "only_dx" else None)
+        names = {"dq": "dq", "dx": "dx", "dgate": "dgate"}
+        if how == "base_is_dx":
+            both = Arr("base_dx", "inout", base)
+            f["base"], f["dx"], names["dx"] = Arr("base", "in", base=both), Arr("dx", "out", base=both), "base_dx"
+
+        def ref(host, v=dict(dq=dq, dx=dx, dgate=dgate), f=f, names=names):
+            return {names[nm]: v[nm] for nm in ("dq", "dx", "dgate") if f[nm] is not None}
+        yield mk("gnnmp_segment_attn_pool_grad_f32", f"D{D}_Dg{Dg}_m{mode}_{how}", tags, [Rec("gnnmp_segment_attn_grad_t", **f), N, G, D, Dg, STREAM], ref,
+                 no_warmup=True)
+
+
+# ---- Flux.LSTMCell at batch one (csrc/evolve.hip) --------------------------------------------------------------------------------------
+def _step_operands(r, D):
+    """tests/evolve_ref.py: step_inputs — Wi, Wh within ±1 / sqrt(D) (pre-activations of order one)"""
+    sc = 1.0 / np.sqrt(D)
+    return dict(Wi=(sc * F(r, 4 * D, D)).astype(f32), Wh=(sc * F(r, 4 * D, D)).astype(f32), x=F(r, D), h=F(r, D), c=F(r, D), b=(0.5 * F(r, 4 * D)).astype(f32),
+                da=F(r, 4 * D), add_x=F(r, D), add_h=F(r, D))
+
+
+EVOLVE_ALIGN = (6, 15, 64)      # 8-, 4- and 16-byte lanes: the widths at which the alignment of Wi, Wh, x, h decides
+
+
+@cases_of("gnnmp_lstm_matvec_cell_f32")
+def _(ctx):
+    V = _mod("evolve_ref")
+    k = 0
+    for D in V.STEP_DS:                                            # 1056: the only width that reaches the workgroup-wide path
+        for has_h, has_c, has_b, has_a, x_is_h in ((True, True, True, True, False), (False, False, False, False, False), (True, False, True, False, True)):
+            r = rng_of("lstm_matvec_cell", D, has_h, has_c)
+            p = _step_operands(r, D)
+            if x_is_h:                                             # x and h may be the same array
+                p["h"] = p["x"]
+            hn, cn, a = V.step_ref(p, has_h, has_c, has_b)
+            X = Arr("x", "in", p["x"])
+            job = Rec("gnnmp_lstm_matvec_t", Wi=Arr("Wi", "in", p["Wi"]), Wh=Arr("Wh", "in", p["Wh"]) if has_h else None, x=X,
+                      h=(Arr("h", "in", base=X) if x_is_h else Arr("h", "in", p["h"])) if has_h else None, c=Arr("c", "in", p["c"]) if has_c else None,
+                      b=Arr("b", "in", p["b"]) if has_b else None, h_out=Arr("h_out", "out", shape=(D,)), c_out=Arr("c_out", "out", shape=(D,)),
+                      a_out=Arr("a_out", "out", shape=(4 * D,)) if has_a else None)
+            ref = lambda host, v=(hn, cn, a), has_a=has_a: {"h_out": v[0], "c_out": v[1], **({"a_out": v[2]} if has_a else {})}
+            tags = ({"align"} if D in EVOLVE_ALIGN and has_h and not x_is_h else set()) | ({"side"} if k == 0 else set())
+            yield mk("gnnmp_lstm_matvec_cell_f32", f"D{D}_h{int(has_h)}c{int(has_c)}b{int(has_b)}a{int(has_a)}{'_x_is_h' if x_is_h else ''}", tags,
+                     [job, D, STREAM], ref, no_warmup=True)
+            k += 1
+
+
+@cases_of("gnnmp_lstm_matvec_grad_f32")
+def _(ctx):
+    from gnnmp import _lib
+    V = _mod("evolve_ref")
+    k = 0
+    for D in V.STEP_DS:
+        nws = int(_lib.load().gnnmp_lstm_matvec_grad_workspace(D))
+        for how in ("both_add", "both", "x_only", "h_only_add", "sum_add", "sum"):
+            r = rng_of("lstm_matvec_grad", D, how)
+            p = _step_operands(r, D)
+            gx, gh = V.grad_ref(p)
+            want_x, want_h, add, sm = how != "h_only_add", how in ("both_add", "both", "h_only_add"), how.endswith("add"), how.startswith("sum")
+            ox = (gx + gh if sm else gx) + (p["add_x"].astype(f64) if add else 0.0)
+            oh = gh + (p["add_h"].astype(f64) if add else 0.0)
+            job = Rec("gnnmp_lstm_matvec_grad_t", Wi=Arr("Wi", "in", p["Wi"]) if want_x else None, Wh=Arr("Wh", "in", p["Wh"]) if want_h or sm else None,
+                      da=Arr("da", "in", p["da"]), add_x=Arr("add_x", "in", p["add_x"]) if add and want_x else None,
+                      add_h=Arr("add_h", "in", p["add_h"]) if add and want_h else None, out_x=Arr("out_x", "out", shape=(D,)) if want_x else None,
+                      out_h=Arr("out_h", "out", shape=(D,)) if want_h else None, sum=int(sm), ws=Arr("ws", "scratch", shape=(nws + 3,)), ws_floats=nws + 3)
+            ref = lambda host, v=(ox, oh), w=(want_x, want_h): {**({"out_x": v[0]} if w[0] else {}), **({"out_h": v[1]} if w[1] else {})}
+            tags = ({"align"} if D in EVOLVE_ALIGN and how in ("both_add", "sum") else set()) | ({"side"} if k == 0 else set())
+            yield mk("gnnmp_lstm_matvec_grad_f32", f"D{D}_{how}", tags, [job, D, STREAM], ref, no_warmup=True)
+            k += 1
+
+
+@cases_of("gnnmp_outer_accum_f32")
+def _(ctx):
+    V = _mod("evolve_ref")
+    # K % 4 == 0 (whole 16-byte lanes), == 2 (two floats a lane), odd; K > 1024: more than one column block to a row; R no multiple of 8
+    shapes = [(3, 5, 8, {"align", "side"}), (3, 5, 6, {"align"}), (3, 5, 7, {"align"}), (1, 1, 1, ()), (4, 13, 64, ()), (3, 60, 260, ()), (2, 11, 1026, {"align"}),
+              (3, 9, 1056, ()), (5, 7, 2052, ()), (3, 24, 1031, ()), (4, 4224, 6, ())]
+    for k, (T, Rr, K, tags) in enumerate(shapes):
+        r = rng_of("outer_accum", T, Rr, K)
+        A_, B_ = F(r, T, Rr), F(r, T, K)
+        dW, db = V.outer_ref(A_, B_)
+        with_db = k % 2 == 0
+        job = Rec("gnnmp_outer_accum_t", A=Arr("A", "in", A_), B=Arr("B", "in", B_), dW=Arr("dW", "out", shape=(Rr, K)),
+                  db=Arr("db", "out", shape=(Rr,)) if with_db else None)
+        yield mk("gnnmp_outer_accum_f32", f"T{T}_R{Rr}_K{K}_db{int(with_db)}", tags, [job, T, Rr, K, STREAM],
+                 lambda host, v=(dW, db), with_db=with_db: {"dW": v[0], **({"db": v[1]} if with_db else {})}, no_warmup=True)
+
+
 # exports the table does not cover, each with its reason (the lifecycle calls and the collective are allowed as a class; at most eight more)
 LIFECYCLE = ("gnnmp_plan_", "gnnmp_arena_", "gnnmp_chain_jobs_")
 EXCLUDED = {
@@ -1857,7 +2565,532 @@ EXCLUDED_EXTRA = {
     "gnnmp_graphconv_chain_f32": "NOT covered by this module (host tables of device pointers, a jobs handle per batch): its scratch / out writes stay untested here",
     "gnnmp_negative_sample": "random draws with a host-side trial loop: no deterministic reference for the written prefix (tests/test_linkpred.py: properties)",
     "gnnmp_sample_neighbors": "random draws: parity is distributional (tests/test_graphprep.py); the written prefix has no exact reference",
+    "gnnmp_debug_random_walk_pe_f32": "GNNMP_INTERNAL test hook: gnnmp_random_walk_pe_f32 (which IS in the table) with another LDS budget; the header documents "
+                                      "no stream behaviour of its own for it, so it can be neither recorded nor quoted as exempt (tests/test_rwpe.py drives it)",
 }
+
+
+# ---- MEGNetConv (csrc/megnet.hip) --------------------------------------------------------------------------------------------------------
+ACT_NAMES = ("identity", "relu", "softplus", "tanh", "swish")          # gnnmp_act, IDENTITY .. SWISH
+EDGE_DS = (1, 2, 3, 6, 7, 64, 100, 260)                                # tests/megnet_conv_ref.py: WIDTHS — 4- / 8- / 16-byte lanes, tails, a second feature tile
+EDGE_SHAPES = dict(Ds=EDGE_DS, small=(3, 64), align=(3, 6, 64), ws=(6,), rows300=(1, 260))
+
+
+@cases_of("gnnmp_megnet_edge_f32")
+def _(ctx):
+    M = _mod("megnet_conv_ref")
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(**EDGE_SHAPES)):
+        act, with_F, with_z = k % 5, k % 2 == 0, k % 3 != 1
+        r = rng_of("megnet_edge", g.name, D)
+        P, Q, Fe = F(r, g.n, D), F(r, g.n, D), F(r, g.E, D)
+        a0, z0 = M.edge(g.s - 1, g.t - 1, P.astype(f64), Q.astype(f64), Fe.astype(f64) if with_F else None, ACT_NAMES[act])
+        job = Rec("gnnmp_megnet_edge_t", P=Arr("P", "in", P), Q=Arr("Q", "in", Q), F=Arr("F", "in", Fe) if with_F else None, a0=Arr("a0", "out", shape=(g.E, D)),
+                  z0=Arr("z0", "out", shape=(g.E, D)) if with_z else None, act=act)
+        yield mk("gnnmp_megnet_edge_f32", f"{g.name}_D{D}_act{act}_F{int(with_F)}_z{int(with_z)}", tags, [Pl(g), job, D, STREAM],
+                 lambda host, v=(a0, z0), with_z=with_z: {"a0": v[0], **({"z0": v[1]} if with_z else {})}, no_warmup=True)
+
+
+@cases_of("gnnmp_megnet_edge_grad_f32")
+def _(ctx):
+    M = _mod("megnet_conv_ref")
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(**EDGE_SHAPES)):
+        act = k % 5
+        want = (("dz0", "dP", "dQ"), ("dP", "dQ"), ("dz0",))[k % 3]
+        r = rng_of("megnet_edge_grad", g.name, D)
+        da0, z = F(r, g.E, D), F(r, g.E, D)
+        dz, dP, dQ = M.edge_grad(g.s - 1, g.t - 1, g.n, da0.astype(f64), z.astype(f64), ACT_NAMES[act])
+        job = Rec("gnnmp_megnet_edge_grad_t", da0=Arr("da0", "in", da0), z=Arr("z", "in", z) if act or k % 2 else None,
+                  dz0=Arr("dz0", "out", shape=(g.E, D)) if "dz0" in want else None, dP=Arr("dP", "out", shape=(g.n, D)) if "dP" in want else None,
+                  dQ=Arr("dQ", "out", shape=(g.n, D)) if "dQ" in want else None, act=act)
+        yield mk("gnnmp_megnet_edge_grad_f32", f"{g.name}_D{D}_act{act}_{'_'.join(want)}", tags, [Pl(g), Pl(g, T=True), job, D, STREAM],
+                 lambda host, v=dict(dz0=dz, dP=dP, dQ=dQ), want=want: {nm: v[nm] for nm in want}, no_warmup=True)
+
+
+@cases_of("gnnmp_aggregate_grad_f32")
+def _(ctx):
+    M = _mod("megnet_conv_ref")
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(**EDGE_SHAPES)):
+        aggr, with_acc = k % 4, k % 3 != 0
+        name = M.AGGRS[aggr]
+        r = rng_of("aggregate_grad", g.name, D)
+        dy, m, acc = F(r, g.n_dst, D), F(r, g.E, D), F(r, g.E, D)
+        if k % 2 == 0:
+            m = (np.round(m * 4) / 4).astype(f32)                      # ties inside a row: EVERY tying copy gets the whole Δ
+        y = M.aggregate(g.t - 1, g.n_dst, m, name)                      # float32 max / min: exact
+        dm = M.aggregate_grad(g.t - 1, g.n_dst, dy.astype(f64), m.astype(f64), y.astype(f64), name, acc.astype(f64) if with_acc else None)
+        need = aggr in (MAX, MIN)
+        job = Rec("gnnmp_aggregate_grad_t", dy=Arr("dy", "in", dy), m=Arr("m", "in", m) if need or k % 2 else None, y=Arr("y", "in", y) if need or k % 2 else None,
+                  acc=Arr("acc", "in", acc) if with_acc else None, dm=Arr("dm", "out", shape=(g.E, D)))
+        yield mk("gnnmp_aggregate_grad_f32", f"{g.name}_D{D}_a{aggr}_acc{int(with_acc)}", tags, [Pl(g), job, aggr, D, STREAM], lambda host, dm=dm: {"dm": dm},
+                 no_warmup=True)
+
+
+# ---- EGNNConv (csrc/egnn.hip) ------------------------------------------------------------------------------------------------------------
+DXS = (1, 2, 3, 4, 7, 16)                                               # tests/egnn_conv_ref.py: DXS (a node's coordinates stay in registers: Dx <= 16)
+COORD_SHAPES = dict(Ds=DXS, small=(3, 16), align=(3, 4), ws=(4,), rows300=(1, 16))
+
+
+def _coords(r, n, Dx):
+    """coordinates of order one with one pair of coincident points (q = 0 between them; the graphs' self loops give q = 0 too)"""
+    x = (2.0 * F(r, n, Dx)).astype(f32)
+    if n > 2:
+        x[n // 2] = x[0]
+    return x
+
+
+@cases_of("gnnmp_egnn_edge_f32")
+def _(ctx):
+    G = _mod("egnn_conv_ref")
+    shapes = [(33, hid, ({"align"} if hid in (3, 6, 8) else set()) | ({"side"} if j == 0 else set())) for j, hid in enumerate(G.HIDS)]
+    shapes += [(1, 3, set()), (31, 64, set()), (300, 1, set()), (300, 260, set())]
+    for k, (K, hid, tags) in enumerate(shapes):
+        ib, base = IDX[k % 4]
+        Dx, act, with_F, with_z = DXS[k % 6], k % 5, k % 2 == 0, k % 3 != 1
+        r = rng_of("egnn_edge", K, hid)
+        n = 40
+        s1, t1 = r.integers(1, n + 1, K), r.integers(1, n + 1, K)
+        x, P, Q, Fe, c = _coords(r, n, Dx), F(r, n, hid), F(r, n, hid), F(r, K, hid), (G.C_SCALE * F(r, hid)).astype(f32)
+        q, z0, a0 = G.edge_ref(s1 - 1, t1 - 1, x, P, Q, Fe if with_F else None, c, ACT_NAMES[act])
+        job = Rec("gnnmp_egnn_edge_t", s=Arr("s", "in", IX(s1, ib, base)), t=Arr("t", "in", IX(t1, ib, base)), idx_bytes=ib, index_base=base, x=Arr("x", "in", x),
+                  P=Arr("P", "in", P), Q=Arr("Q", "in", Q), F=Arr("F", "in", Fe) if with_F else None, c=Arr("c", "in", c), q=Arr("q", "out", shape=(K,)),
+                  a0=Arr("a0", "out", shape=(K, hid)), z0=Arr("z0", "out", shape=(K, hid)) if with_z else None, act=act)
+        yield mk("gnnmp_egnn_edge_f32", f"K{K}_hid{hid}_Dx{Dx}_act{act}_F{int(with_F)}_z{int(with_z)}_i{ib}b{base}", tags, [job, K, hid, Dx, STREAM],
+                 lambda host, v=(q, a0, z0), with_z=with_z: {"q": v[0], "a0": v[1], **({"z0": v[2]} if with_z else {})}, no_warmup=True)
+
+
+@cases_of("gnnmp_egnn_coord_f32")
+def _(ctx):
+    G = _mod("egnn_conv_ref")
+    for g, Dx, tags in ctx.graph_shapes(**COORD_SHAPES):
+        r = rng_of("egnn_coord", g.name, Dx)
+        x, mx = _coords(r, g.n, Dx), F(r, g.E)
+        xo = G.coord_ref(g.s - 1, g.t - 1, g.n, x, mx)
+        job = Rec("gnnmp_egnn_coord_t", x=Arr("x", "in", x), mx=Arr("mx", "in", mx), xo=Arr("xo", "out", shape=(g.n, Dx)))
+        yield mk("gnnmp_egnn_coord_f32", f"{g.name}_Dx{Dx}", tags, [Pl(g), job, Dx, STREAM], lambda host, xo=xo: {"xo": xo}, no_warmup=True)
+
+
+@cases_of("gnnmp_egnn_coord_grad_f32")
+def _(ctx):
+    G = _mod("egnn_conv_ref")
+    for k, (g, Dx, tags) in enumerate(ctx.graph_shapes(**COORD_SHAPES)):
+        want = (("dmx", "dx"), ("dx",), ("dmx",))[k % 3]
+        r = rng_of("egnn_coord_grad", g.name, Dx)
+        x, dxo, mx, dq = _coords(r, g.n, Dx), F(r, g.n, Dx), F(r, g.E), F(r, g.E)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dmx, dx = G.coord_grad_ref(g.s - 1, g.t - 1, g.n, x, dxo, mx, dq)
+        job = Rec("gnnmp_egnn_coord_grad_t", x=Arr("x", "in", x), dxo=Arr("dxo", "in", dxo), mx=Arr("mx", "in", mx) if "dx" in want or k % 2 else None,
+                  dq=Arr("dq", "in", dq) if "dx" in want or k % 2 else None, dmx=Arr("dmx", "out", shape=(g.E,)) if "dmx" in want else None,
+                  dx=Arr("dx", "out", shape=(g.n, Dx)) if "dx" in want else None)
+        yield mk("gnnmp_egnn_coord_grad_f32", f"{g.name}_Dx{Dx}_{'_'.join(want)}", tags, [Pl(g), Pl(g, T=True), job, Dx, STREAM],
+                 lambda host, v=dict(dmx=dmx, dx=dx), want=want: {nm: v[nm] for nm in want}, no_warmup=True)
+
+
+@cases_of("gnnmp_act_grad_z_f32")
+def _(ctx):
+    G = _mod("egnn_conv_ref")
+    k = 0
+    for n in G.ACT_NS + (4100,):                                       # 4099: a tail of the 16-byte lanes; 4100: none
+        for act in range(5):
+            r = rng_of("act_grad_z", n, act)
+            dy, z = F(r, n), (3.0 * F(r, n)).astype(f32)
+            dz = G.act_grad_z_ref(dy, z, ACT_NAMES[act])
+            job = Rec("gnnmp_act_grad_z_t", dy=Arr("dy", "in", dy), z=Arr("z", "in", z) if act or n % 2 else None, dz=Arr("dz", "out", shape=(n,)), act=act)
+            tags = ({"align"} if n in (5, 4100) and act in (1, 4) else set()) | ({"side"} if k == 0 else set())
+            yield mk("gnnmp_act_grad_z_f32", f"n{n}_act{act}", tags, [job, n, STREAM], lambda host, dz=dz: {"dz": dz}, no_warmup=True)
+            k += 1
+
+
+# ---- GMMConv (csrc/gmm.hip) ----------------------------------------------------------------------------------------------------------------
+GMM_SHAPES = dict(Ds=(1, 2, 3, 4, 5, 8, 33, 64, 130), small=(3, 8), align=(3, 2, 8), ws=(4,), rows300=(1, 130))      # tests/gmm_conv_ref.py: KERNEL_CS
+
+
+@cases_of("gnnmp_gmm_conv_f32")
+def _(ctx):
+    G = _mod("gmm_conv_ref")
+    for k, (g, C, tags) in enumerate(ctx.graph_shapes(**GMM_SHAPES)):
+        K = G.KERNEL_KS[k % 6] if C <= 33 else 3
+        act, with_b, with_z = k % 5, k % 2 == 0, k % 3 != 1
+        r = rng_of("gmm_conv", g.name, C)
+        w, xk, bias = (0.25 + 0.75 * r.random((g.E, K))).astype(f32), F(r, g.n, K * C), F(r, C)
+        z = G.rows(g.s - 1, g.t - 1, g.n, w.astype(f64), xk.astype(f64), bias.astype(f64) if with_b else None, K, C)
+        y = G.act(z, ACT_NAMES[act])
+        job = Rec("gnnmp_gmm_conv_t", w=Arr("w", "in", w), xk=Arr("xk", "in", xk), bias=Arr("bias", "in", bias) if with_b else None, y=Arr("y", "out", shape=(g.n, C)),
+                  z=Arr("z", "out", shape=(g.n, C)) if with_z else None, act=act)
+        yield mk("gnnmp_gmm_conv_f32", f"{g.name}_C{C}_K{K}_act{act}_b{int(with_b)}_z{int(with_z)}", tags, [Pl(g), job, K, C, STREAM],
+                 lambda host, v=(y, z), with_z=with_z: {"y": v[0], **({"z": v[1]} if with_z else {})}, no_warmup=True)
+
+
+@cases_of("gnnmp_gmm_conv_grad_f32")
+def _(ctx):
+    G = _mod("gmm_conv_ref")
+    for k, (g, C, tags) in enumerate(ctx.graph_shapes(**GMM_SHAPES)):
+        K = G.KERNEL_KS[k % 6] if C <= 33 else 3
+        want = (("dxk", "dw"), ("dxk",), ("dw",))[k % 3]
+        r = rng_of("gmm_conv_grad", g.name, C)
+        w, xk, dz = (0.25 + 0.75 * r.random((g.E, K))).astype(f32), F(r, g.n, K * C), F(r, g.n, C)
+        dxk, dw = G.rows_grad(g.s - 1, g.t - 1, g.n, w.astype(f64), xk.astype(f64), dz.astype(f64), K, C)
+        job = Rec("gnnmp_gmm_conv_grad_t", w=Arr("w", "in", w) if "dxk" in want or k % 2 else None, xk=Arr("xk", "in", xk) if "dw" in want or k % 2 else None,
+                  dz=Arr("dz", "in", dz), dxk=Arr("dxk", "out", shape=(g.n, K * C)) if "dxk" in want else None, dw=Arr("dw", "out", shape=(g.E, K)) if "dw" in want else None)
+        yield mk("gnnmp_gmm_conv_grad_f32", f"{g.name}_C{C}_K{K}_{'_'.join(want)}", tags, [Pl(g), Pl(g, T=True), job, K, C, STREAM],
+                 lambda host, v=dict(dxk=dxk, dw=dw), want=want: {nm: v[nm] for nm in want}, no_warmup=True)
+
+
+# ---- EdgeConv, CGConv, NNConv: the training kernels (csrc/edge_conv.hip, cg_grad.hip, nn_grad.hip) -----------------------------------------
+CONV_SHAPES = dict(Ds=(1, 3, 6, 8, 64, 260), small=(3, 8), align=(3, 6, 8), ws=(6,), rows300=(1, 260))      # tests/cg_conv_ref.py: KERNEL_CS
+
+
+@cases_of("gnnmp_edge_conv_f32")
+def _(ctx):
+    V = _mod("edge_conv_ref")
+    for k, (g, C, tags) in enumerate(ctx.graph_shapes(**CONV_SHAPES)):
+        aggr, act = k % 4, (k // 2) % 2
+        r = rng_of("edge_conv", g.name, C)
+        P = F(r, g.n, 2 * C)
+        # the header: every row is folded sequentially in edge order, each operation rounded on its own — the float32 restatement has the bits
+        y = V.fused(g.s - 1, g.t - 1, g.n, P, C, V.AGGRS[aggr], V.ACTS[act])[0]
+        job = Rec("gnnmp_edge_conv_t", p=Arr("p", "in", P), y=Arr("y", "out", shape=(g.n, C)), aggr=aggr, act=act)
+        yield mk("gnnmp_edge_conv_f32", f"{g.name}_C{C}_a{aggr}_act{act}", tags, [Pl(g), job, C, STREAM], lambda host, y=y: {"y": E(y, "exact")}, no_warmup=True)
+
+
+@cases_of("gnnmp_edge_conv_grad_f32")
+def _(ctx):
+    V = _mod("edge_conv_ref")
+    for k, (g, C, tags) in enumerate(ctx.graph_shapes(**CONV_SHAPES)):
+        aggr, act = k % 4, (k // 2) % 2
+        r = rng_of("edge_conv_grad", g.name, C)
+        P, dy = F(r, g.n, 2 * C), F(r, g.n, C)
+        if k % 3 == 0:
+            P = (np.round(P * 4) / 4).astype(f32)                       # ties under max / min, pre-activations at 0 under relu
+        y = V.fused(g.s - 1, g.t - 1, g.n, P, C, V.AGGRS[aggr], V.ACTS[act])[0]
+        dp = V.grad_p(g.s - 1, g.t - 1, g.n, P, C, y, dy, V.AGGRS[aggr], V.ACTS[act])          # float32: "the bits of the kernels"
+        job = Rec("gnnmp_edge_conv_grad_t", p=Arr("p", "in", P), y=Arr("y", "in", y), dy=Arr("dy", "in", dy), dp=Arr("dp", "out", shape=(g.n, 2 * C)), aggr=aggr, act=act)
+        yield mk("gnnmp_edge_conv_grad_f32", f"{g.name}_C{C}_a{aggr}_act{act}", tags, [Pl(g), Pl(g, T=True), job, C, STREAM],
+                 lambda host, dp=dp: {"dp": E(dp, "exact")}, no_warmup=True)
+
+
+@cases_of("gnnmp_cg_conv_grad_f32")
+def _(ctx):
+    V = _mod("cg_conv_ref")
+    for k, (g, C, tags) in enumerate(ctx.graph_shapes(**CONV_SHAPES)):
+        act, with_e = k % 4, k % 2 == 0
+        want_e = with_e and k % 4 == 0
+        for salt in range(16):                                          # relu: no pre-activation of dense_s within float32 rounding of its kink
+            r = rng_of("cg_conv_grad", g.name, C, salt)
+            fi, fj, fe, dy = F(r, g.n, 2 * C), F(r, g.n, 2 * C), F(r, g.E, 2 * C), F(r, g.n, C)
+            sp = V.pre(g.s - 1, g.t - 1, fi, fj, fe if with_e else None, C)[1]
+            if act != 1 or not sp.size or np.abs(sp).min() > 1e-5:
+                break
+        di, dj, de = V.rows_grad(g.s - 1, g.t - 1, g.n, fi.astype(f64), fj.astype(f64), fe.astype(f64) if with_e else None, dy.astype(f64), C, V.ACTS[act])
+        job = Rec("gnnmp_cg_conv_grad_t", fs_i=Arr("fs_i", "in", fi), fs_j=Arr("fs_j", "in", fj), fs_e=Arr("fs_e", "in", fe) if with_e else None, dy=Arr("dy", "in", dy),
+                  dfs_i=Arr("dfs_i", "out", shape=(g.n, 2 * C)), dfs_j=Arr("dfs_j", "out", shape=(g.n, 2 * C)),
+                  dfs_e=Arr("dfs_e", "out", shape=(g.E, 2 * C)) if want_e else None, act=act)
+        yield mk("gnnmp_cg_conv_grad_f32", f"{g.name}_C{C}_act{act}_e{int(with_e)}{int(want_e)}", tags, [Pl(g), Pl(g, T=True), job, C, STREAM],
+                 lambda host, v=(di, dj, de), want_e=want_e: {"dfs_i": v[0], "dfs_j": v[1], **({"dfs_e": v[2]} if want_e else {})}, no_warmup=True)
+
+
+@cases_of("gnnmp_nn_conv_grad_f32")
+def _(ctx):
+    V = _mod("nn_conv_ref")
+    shapes = [(ctx.hub, Din, Dout, ({"align"} if (Din, Dout) in ((3, 5), (8, 8), (33, 20)) else set()) | ({"side", "ws"} if j == 0 else set()))
+              for j, (Din, Dout) in enumerate(V.KERNEL_SHAPES)]                   # every lane geometry; two feature tiles at (3, 130), (2, 260)
+    shapes += [(ctx.e0, 3, 4, ()), (ctx.one, 4, 3, ()), (ctx.r31, 2, 6, ()), (ctx.r33, 5, 3, ()), (ctx.r300, 4, 8, ()), (ctx.r300, 3, 1, ()), (ctx.r300, 2, 70, ())]
+    for k, (g, Din, Dout, tags) in enumerate(shapes):
+        want = (("dx", "dwe"), ("dx",), ("dwe",))[k % 3]
+        r = rng_of("nn_conv_grad", g.name, Din, Dout)
+        x, we, dm = F(r, g.n, Din), F(r, g.E, Dout * Din), F(r, g.n, Dout)
+        dx, dwe = V.rows_grad64(g.s - 1, g.t - 1, g.n, x, we, dm, Din, Dout)
+        job = Rec("gnnmp_nn_conv_grad_t", x=Arr("x", "in", x), we=Arr("we", "in", we) if "dx" in want or k % 2 else None, dm=Arr("dm", "in", dm),
+                  dx=Arr("dx", "out", shape=(g.n, Din)) if "dx" in want else None, dwe=Arr("dwe", "out", shape=(g.E, Dout * Din)) if "dwe" in want else None)
+        yield mk("gnnmp_nn_conv_grad_f32", f"{g.name}_{Din}x{Dout}_{'_'.join(want)}", tags, [Pl(g, T=True), job, Din, Dout, STREAM],
+                 lambda host, v=dict(dx=dx, dwe=dwe), want=want: {nm: v[nm] for nm in want}, no_warmup=True)
+
+
+# ---- attention with a per-edge feature row (csrc/attn_edge.hip) ------------------------------------------------------------------------------
+EDGE_WIDE = WIDE + ("F", "dF")      # "F and dF count among the [.][H*C] arrays whose alignment selects v"
+
+
+def _attn_edge_operands(r, g, H, C):
+    D = H * C
+    return dict(Q=F(r, g.n, D), K=F(r, g.n, D), V=F(r, g.n, D), F=F(r, g.E, D), a=F(r, H, C), bias=F(r, D), dout=F(r, g.n, D))
+
+
+def _attn_edge_core(g, mode, i, H, C, sepQ, sepV, slope, scale):
+    V = _mod("attn_edge_ref")
+    sh = lambda k: i[k].astype(f64).reshape(-1, H, C)      # noqa: E731
+    Q, K = sh("Q") if sepQ else sh("K"), sh("K")
+    args = ("gatv2" if mode == 1 else "dot", g.s - 1, g.t - 1, g.n, Q, K, sh("V") if sepV else K, sh("F"), i["a"].astype(f64), slope, scale)
+    o, c = V.core(*args)
+    return o, c, args
+
+
+def _edge_align(H, C, base=None):
+    d = dict(base or {})
+    if H * C > 64:
+        d.update({n: EUNSUPPORTED for n in EDGE_WIDE})
+    return d
+
+
+@cases_of("gnnmp_attn_conv_edge_f32")
+def _(ctx):
+    for k, (g, H, C, tags) in enumerate(att_shapes(ctx, False)):
+        mode = 1 + k % 2                                                # GNNMP_ATTN_GATV2 | GNNMP_ATTN_DOT
+        sepQ, sepV, with_b, act, with_stats = k % 3 != 2, mode == 2 and k % 4 < 2, k % 2 == 0 or k % 3 == 0, (k // 2) % 2, k % 3 != 1
+        slope, scale = 0.2, float(np.float32(np.sqrt(np.float32(C))))
+        r = rng_of("attn_conv_edge", g.name, H, C)
+        i = _attn_edge_operands(r, g, H, C)
+        o, c, _ = _attn_edge_core(g, mode, i, H, C, sepQ, sepV, slope, scale)
+        out = o.reshape(g.n, H * C) + (i["bias"].astype(f64) if with_b else 0.0)
+        out = np.maximum(out, 0.0) if act else out
+        stats = np.stack([c["m"], c["den"]], axis=-1)
+        job = Rec("gnnmp_attn_edge_t", Q=Arr("Q", "in", i["Q"]) if sepQ else None, K=Arr("K", "in", i["K"]), V=Arr("V", "in", i["V"]) if sepV else None,
+                  F=Arr("F", "in", i["F"]), a=Arr("a", "in", i["a"]) if mode == 1 or k % 3 == 0 else None, bias=Arr("bias", "in", i["bias"]) if with_b else None,
+                  out=Arr("out", "out", shape=(g.n, H * C)), stats=Arr("stats", "out", shape=(g.n, H, 2)) if with_stats else None,
+                  negative_slope=slope, scale=scale, act=act)
+        yield mk("gnnmp_attn_conv_edge_f32", f"{g.name}_m{mode}_H{H}_C{C}_q{int(sepQ)}v{int(sepV)}", tags, [Pl(g), mode, job, H, C, STREAM],
+                 lambda host, v=(out, stats), with_stats=with_stats: {"out": v[0], **({"stats": v[1]} if with_stats else {})},
+                 align_status=_edge_align(H, C), no_warmup=True)
+
+
+@cases_of("gnnmp_attn_conv_edge_grad_f32")
+def _(ctx):
+    V = _mod("attn_edge_ref")
+    for k, (g, H, C, tags) in enumerate(att_shapes(ctx, False)):
+        mode = 1 + k % 2
+        sepQ, sepV, with_da = k % 3 != 2, mode == 2 and k % 4 < 2, k % 3 != 1
+        slope, scale = 0.2, float(np.float32(np.sqrt(np.float32(C))))
+        D = H * C
+        r = rng_of("attn_conv_edge_grad", g.name, H, C)
+        i = _attn_edge_operands(r, g, H, C)
+        o, c, args = _attn_edge_core(g, mode, i, H, C, sepQ, sepV, slope, scale)
+        gr = V.core_grad(*args, c, i["dout"].astype(f64).reshape(-1, H, C))
+        stats = np.stack([c["m"], c["den"]], axis=-1).astype(f32)
+        want = {nm: gr[nm].reshape(-1, D) for nm in ("dQ", "dK", "dF")}
+        if mode == 2:
+            want["dV"] = gr["dV"].reshape(-1, D)
+        else:
+            want["dA"] = gr["dA"].reshape(-1, D)
+            if with_da:
+                want["da"] = gr["da"]
+        # dl = α (g − D) is a DIFFERENCE of float64 terms that cancels to (almost) zero where a row's edges carry equal values — the
+        # one-node graph's two self loops: float32 rounding lives on the scale of the terms α g and α D times the factor they meet, so
+        # that is the floor of "the reference's scale", per destination row (dQ, dA), source row (dK), edge (dF) or over all (da) —
+        # the floors of the e-less pullbacks above (attn_ref: gscale).  dV = Σ α Δ has no difference in it
+        al = c["al"]
+        gg = (i["dout"].astype(f64).reshape(-1, H, C)[g.t - 1] * c["val"]).sum(-1)
+        big = max([1.0] + [float(np.abs(i[nm]).max()) for nm in ("Q", "K", "V", "F", "a") if i[nm].size])
+        term = big * (np.abs(al * gg) + np.abs(al * gr["D"][g.t - 1])).max(-1) if g.E else np.zeros(0)
+        row_t, row_s = np.zeros(g.n), np.zeros(g.n)
+        np.maximum.at(row_t, g.t - 1, term)
+        np.maximum.at(row_s, g.s - 1, term)
+        floors = dict(dQ=row_t, dA=row_t, dK=row_s, dF=term if g.E else 0.0, da=float(term.max()) if g.E else 0.0, dV=0.0)
+        ref = lambda host, want=want, floors=floors: {nm: E(v, scale=floors[nm]) for nm, v in want.items()}
+        job = Rec("gnnmp_attn_edge_grad_t", Q=Arr("Q", "in", i["Q"]) if sepQ else None, K=Arr("K", "in", i["K"]), V=Arr("V", "in", i["V"]) if sepV else None,
+                  F=Arr("F", "in", i["F"]), a=Arr("a", "in", i["a"]) if mode == 1 else None, stats=Arr("stats", "in", stats), dout=Arr("dout", "in", i["dout"]),
+                  line=Arr("line", "scratch", shape=(g.n, H, 4)), dQ=Arr("dQ", "out", shape=(g.n, D)), dK=Arr("dK", "out", shape=(g.n, D)),
+                  dV=Arr("dV", "out", shape=(g.n, D)) if mode == 2 else None, dF=Arr("dF", "out", shape=(g.E, D)),
+                  dA=Arr("dA", "out", shape=(g.n, D)) if mode == 1 else None, da=Arr("da", "out", shape=(H, C)) if mode == 1 and with_da else None,
+                  negative_slope=slope, scale=scale)
+        yield mk("gnnmp_attn_conv_edge_grad_f32", f"{g.name}_m{mode}_H{H}_C{C}_q{int(sepQ)}v{int(sepV)}", tags, [Pl(g), Pl(g, T=True), mode, job, H, C, STREAM],
+                 ref, align_status=_edge_align(H, C, LINE_ALIGN), no_warmup=True)
+
+
+# ---- heterographs: tables of relation records (csrc/hetero.hip, hetero_backward.hip) ------------------------------------------------------------
+HET_SHAPES = dict(Ds=(1, 3, 6, 8, 129, 260), small=(3, 8), align=(3, 6, 8), ws=(8,), rows300=(1, 260))
+AGGR_NAMES = ("+", "mean", "max", "min")
+
+
+def _bipartite(ctx, name, n_src, n_dst, E_, seed):
+    """a relation between two node types, made once per Ctx (plans are keyed on the Graph object)"""
+    if name not in ctx.cache:
+        ctx.cache[name] = random_graph(name, n_src, E_, seed, n_dst=n_dst)
+    return ctx.cache[name]
+
+
+@cases_of("gnnmp_hetero_propagate_f32")
+def _(ctx):
+    H = _mod("hetero_ref")
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(**HET_SHAPES)):
+        r = rng_of("hetero_propagate", g.name, D)
+        n, m = g.n, 17
+        gb = _bipartite(ctx, f"het_b_{g.name}", m, n, 3 * n, 11)          # type B (17 nodes) -> type A (the graph's nodes)
+        gc = _bipartite(ctx, f"het_c_{g.name}", n, m, 2 * n + 5, 12)      # type A -> type B
+        xa, xb, root, w = F(r, n, D), F(r, m, D), F(r, n, D), F(r, g.E)
+        a1, a2, a3 = AGGR_NAMES[k % 4], AGGR_NAMES[(k + 1) % 4], AGGR_NAMES[(k + 2) % 4]
+        comb0, comb1 = (SUM, MAX, MIN)[k % 3], (SUM, MAX, MIN)[(k + 1) % 3]
+        cname = {SUM: "+", MAX: "max", MIN: "min"}
+        # table order: the root term (an identity relation), the weighted relation inside type A, the relation from type B
+        out0 = H.hetero_ref([(g.s - 1, g.t - 1, xa, w, a1), (gb.s - 1, gb.t - 1, xb, None, a2)], n, cname[comb0], root=root)
+        out1 = H.hetero_ref([(gc.s - 1, gc.t - 1, xa, None, a3)], m, cname[comb1])
+        XA = Arr("x_a", "in", xa, field="x")
+        dsts = [Rec("gnnmp_hetero_dst_t", out=Arr("out_a", "out", shape=(n, D), field="out"), n_dst=n, combine=comb0, n_rel=3, rels=[
+                    Rec("gnnmp_hetero_rel_t", plan=None, x=Arr("root", "in", root, field="x"), w=None, aggr=SUM),
+                    Rec("gnnmp_hetero_rel_t", plan=Pl(g), x=XA, w=Arr("w", "in", w), aggr=k % 4),
+                    Rec("gnnmp_hetero_rel_t", plan=Pl(gb), x=Arr("x_b", "in", xb, field="x"), w=None, aggr=(k + 1) % 4)]),
+                Rec("gnnmp_hetero_dst_t", out=Arr("out_b", "out", shape=(m, D), field="out"), n_dst=m, combine=comb1, n_rel=1, rels=[
+                    Rec("gnnmp_hetero_rel_t", plan=Pl(gc), x=Arr("x_a2", "in", base=XA, field="x"), w=None, aggr=(k + 2) % 4)])]
+        # "bit-identical to the sequential loop": the float32 restatement of tests/hetero_ref.py has the bits, on every row
+        yield mk("gnnmp_hetero_propagate_f32", f"{g.name}_D{D}_a{k % 4}_c{comb0}{comb1}", tags, [dsts, 2, D, STREAM],
+                 lambda host, v=(out0, out1): {"out_a": E(v[0], "exact"), "out_b": E(v[1], "exact")}, no_warmup=True)
+
+
+@cases_of("gnnmp_hetero_propagate_grad_f32")
+def _(ctx):
+    H, HG = _mod("hetero_ref"), _mod("hetero_grad_ref")
+    for k, (g, D, tags) in enumerate(ctx.graph_shapes(**HET_SHAPES)):
+        r = rng_of("hetero_propagate_grad", g.name, D)
+        n, m = g.n, 17
+        gc = _bipartite(ctx, f"het_c_{g.name}", n, m, 2 * n + 5, 12)      # type A -> type B
+        gb = _bipartite(ctx, f"het_b_{g.name}", m, n, 3 * n, 11)          # type B -> type A
+        xa, xb = F(r, n, D), F(r, m, D)
+        if k % 2 == 0:
+            xa = (np.round(xa * 4) / 4).astype(f32)                       # ties: every tie receives the gradient
+        dy_a, dy_b, dy_id, w, sd = F(r, n, D), F(r, m, D), F(r, n, D), F(r, g.E), (0.5 + r.random(n)).astype(f32)
+        mx = "max" if k % 2 == 0 else "min"
+        y_b = H.propagate_ref(gc.s - 1, gc.t - 1, m, xa, None, mx)        # the forward aggregate of A -> B under max / min, float32
+        term = F(r, n, D)
+        out_fold = np.maximum(term, xa) if k % 2 == 0 else np.minimum(term, xa)      # the fold's result: `term` ties with it where it won
+        use_w, use_sd = k % 3 != 1, k % 3 != 2
+        c = [HG.linear_ref(g.s - 1, g.t - 1, n, dy_a, w if use_w else None, sd if use_sd else None),      # + / mean inside type A
+             HG.winners_ref(gc.s - 1, gc.t - 1, n, xa, y_b, dy_b),                                            # max / min towards type B
+             dy_id.copy(),                                                                                    # a root term
+             HG.masked_ref(term, out_fold, dy_id)]                                                            # one term of a max / min fold
+        dxa = HG.sum_ref(c)
+        dxb = HG.sum_ref([HG.linear_ref(gb.s - 1, gb.t - 1, m, dy_a, None, None)])
+        DYA, DYI = Arr("dy_a", "in", dy_a, field="dy"), Arr("dy_id", "in", dy_id, field="dy")
+        R_ = lambda **f: Rec("gnnmp_hetero_rel_grad_t", **f)      # noqa: E731
+        srcs = [Rec("gnnmp_hetero_src_t", dx=Arr("dx_a", "out", shape=(n, D), field="dx"), x=Arr("x_a", "in", xa, field="x"), n_src=n, n_rel=4, rels=[
+                    R_(plan_t=Pl(g, T=True), dy=DYA, w=Arr("w", "in", w) if use_w else None, sd=Arr("sd", "in", sd) if use_sd else None, y=None, out=None),
+                    R_(plan_t=Pl(gc, T=True), dy=Arr("dy_b", "in", dy_b, field="dy"), w=None, sd=None, y=Arr("y_b", "in", y_b, field="y"), out=None),
+                    R_(plan_t=None, dy=DYI, w=None, sd=None, y=None, out=None),
+                    R_(plan_t=None, dy=Arr("dy_id2", "in", base=DYI, field="dy"), w=None, sd=None, y=Arr("term", "in", term, field="y"),
+                       out=Arr("out_fold", "in", out_fold, field="out"))]),
+                Rec("gnnmp_hetero_src_t", dx=Arr("dx_b", "out", shape=(m, D), field="dx"), x=None if k % 2 else Arr("x_b", "in", xb, field="x"), n_src=m, n_rel=1,
+                    rels=[R_(plan_t=Pl(gb, T=True), dy=Arr("dy_a2", "in", base=DYA, field="dy"), w=None, sd=None, y=None, out=None)])]
+        yield mk("gnnmp_hetero_propagate_grad_f32", f"{g.name}_D{D}_{mx}_w{int(use_w)}sd{int(use_sd)}", tags, [srcs, 2, D, STREAM],
+                 lambda host, v=(dxa, dxb): {"dx_a": E(v[0], "exact"), "dx_b": E(v[1], "exact")}, no_warmup=True)
+
+
+# ---- graph prep through records: coalescing, compaction, random-walk encodings (they synchronise: SYNCHRONISES below) ---------------------------
+@cases_of("gnnmp_coalesce_edges")
+def _(ctx):
+    TR = _mod("transforms_ref")
+    k = 0
+    for n, E_ in PREP[:4]:
+        for mode in (0, 1, 2):                                          # DIRECTED, MIRRORED, UNDIRECTED
+            ib, base = IDX[k % 4]
+            r = rng_of("coalesce", n, E_, mode)
+            s1, t1 = r.integers(1, n + 1, E_), r.integers(1, n + 1, E_)
+            s1[E_ // 2:] = s1[:E_ - E_ // 2]                           # parallel edges
+            t1[E_ // 2:] = t1[:E_ - E_ // 2]
+            c = (TR.remove_multi_edges, TR.to_bidirected, TR.to_unidirected)[mode](s1, t1, n)
+            Ev = 2 * E_ if mode == 1 else E_                            # the virtual list of to_bidirected is never materialised
+            tot = len(c.s)
+            colptr = np.concatenate([[0], np.cumsum(c.seg_len)])
+            rowval = np.where(c.perm >= E_, c.perm - E_, c.perm)       # a mirrored position reads the row of the edge it mirrors
+            dt = np.int64 if ib == 8 else np.int32
+
+            def ref(host, c=c, tot=tot, colptr=colptr, rowval=rowval, ib=ib, base=base):
+                assert host["total"] == tot, (host["total"], tot)
+                I = lambda v, b: E((np.asarray(v, np.int64) + b).astype(np.int64 if ib == 8 else np.int32), "exact", prefix=len(v))      # noqa: E731
+                return {"s_out": I(c.s - 1, base), "t_out": I(c.t - 1, base), "colptr": I(colptr, base), "rowval": I(rowval, base)}
+            job = Rec("gnnmp_coalesce_t", s=Arr("s", "in", IX(s1, ib, base)), t=Arr("t", "in", IX(t1, ib, base)), idx_bytes=ib, index_base=base, n_edges=E_, n_nodes=n,
+                      mode=mode, s_out=Arr("s_out", "out", shape=(Ev,), dtype=dt), t_out=Arr("t_out", "out", shape=(Ev,), dtype=dt),
+                      colptr=Arr("colptr", "out", shape=(Ev + 1,), dtype=dt), rowval=Arr("rowval", "out", shape=(Ev,), dtype=dt))
+            yield mk("gnnmp_coalesce_edges", f"n{n}_E{E_}_m{mode}_i{ib}b{base}", ({"align"} if n in (31, 33) else set()) | ({"side"} if k == 4 else set()),
+                     [job, HostOut("total"), STREAM], ref)
+            k += 1
+
+
+@cases_of("gnnmp_compact_edges")
+def _(ctx):
+    TR = _mod("transforms_ref")
+    k = 0
+    for n, E_ in PREP[:4]:
+        for rule in (0, 1, 2):                                          # SELF_LOOPS, LIST, RANDOM
+            ib, base = IDX[k % 4]
+            r = rng_of("compact", n, E_, rule)
+            s1, t1 = r.integers(1, n + 1, E_), r.integers(1, n + 1, E_)
+            t1[::3] = s1[::3]                                           # self loops
+            w = F(r, E_) if k % 2 == 0 else None
+            rem = r.integers(1, E_ + 1, max(1, E_ // 3))                # 1-based positions, repeats allowed
+            pdrop, seed = 0.4, 99 + k
+            if rule == 0:
+                keep = np.flatnonzero(s1 != t1)
+                assert np.array_equal(keep, TR.remove_self_loops(s1, t1)[4])
+            elif rule == 1:
+                keep = TR.remove_edges(s1, t1, rem)[4]
+            else:                                                       # the hash of gnnmp_dropout_keep_u8 at (seed, e, h = 0): the oracle's mask
+                keep = np.flatnonzero(np.asarray(orc().dropout_keep(seed, pdrop, E_, 1)).reshape(E_) != 0)
+            tot = len(keep)
+            dt = np.int64 if ib == 8 else np.int32
+
+            def ref(host, keep=keep, s1=s1, t1=t1, w=w, tot=tot, ib=ib, base=base):
+                assert host["total"] == tot, (host["total"], tot)
+                I = lambda v: E((np.asarray(v, np.int64) + base).astype(np.int64 if ib == 8 else np.int32), "exact", prefix=len(v))      # noqa: E731
+                out = {"s_out": I(s1[keep] - 1), "t_out": I(t1[keep] - 1), "eid_out": I(keep)}
+                if w is not None:
+                    out["w_out"] = E(w[keep], "exact", prefix=tot)
+                return out
+            job = Rec("gnnmp_compact_t", s=Arr("s", "in", IX(s1, ib, base)), t=Arr("t", "in", IX(t1, ib, base)), w=Arr("w", "in", w) if w is not None else None,
+                      idx_bytes=ib, index_base=base, n_edges=E_, rule=rule, remove=Arr("remove", "in", IX(rem, ib, base)) if rule == 1 else None,
+                      n_remove=len(rem) if rule == 1 else 0, p=pdrop, seed=seed, s_out=Arr("s_out", "out", shape=(E_,), dtype=dt),
+                      t_out=Arr("t_out", "out", shape=(E_,), dtype=dt), w_out=Arr("w_out", "out", shape=(E_,)) if w is not None else None,
+                      eid_out=Arr("eid_out", "out", shape=(E_,), dtype=dt))
+            yield mk("gnnmp_compact_edges", f"n{n}_E{E_}_r{rule}_i{ib}b{base}", ({"align"} if n in (31, 33) else set()) | ({"side"} if k == 4 else set()),
+                     [job, HostOut("total"), STREAM], ref)
+            k += 1
+
+
+@cases_of("gnnmp_random_walk_pe_f32")
+def _(ctx):
+    W = _mod("rwpe_ref")
+    T = 16                                                              # GNNMP_RWPE_TILE: members of T - 1, T, T + 1 and 2 T + 1 nodes
+    if "rwpe" not in ctx.cache:
+        (bs, bt, bn, _), off = W.concat(W.batch_members(T))
+        ls, lt, ln, _ = W.random_graph(520, 3, 300)                    # more nodes than the LDS panels hold: the scratch path
+        ctx.cache["rwpe"] = (Graph("rwpe_batch", bs + 1, bt + 1, bn), off, Graph("rwpe_520", ls + 1, lt + 1, ln))
+    gbatch, off, glarge = ctx.cache["rwpe"]
+    shapes = [(ctx.hub, 6, None, {"align", "side", "ws"}), (ctx.e0, 3, None, ()), (ctx.one, 4, None, ()), (ctx.r31, 1, None, {"align"}), (ctx.r33, 5, None, ()),
+              (ctx.r300, 6, None, ()), (gbatch, W.BATCH_WALK, 8, ()), (gbatch, 3, 4, {"align"}), (glarge, 3, None, ())]
+    for k, (g, K, pb, tags) in enumerate(shapes):
+        r = rng_of("rwpe", g.name, K, pb)
+        w = (1.0 + 0.5 * F(r, g.E)).astype(f32)
+        with_w = k % 2 == 0
+        pe = W.dense64(g.s - 1, g.t - 1, g.n, w if with_w else None, K)
+        # tests/test_rwpe.py's bar: 1e-5 norm-wise AND element-wise relative, and exactly 0 where the model is 0
+        ref = lambda host, pe=pe: {"out": E(pred=lambda got, pe=pe: None if W.within_bar(got, pe) else "deviation %r from float64 is not within 1e-5" % (W.deviation(got, pe),))}
+        job = Rec("gnnmp_rwpe_t", w=Arr("w", "in", w) if with_w else None, graph_ptr=Arr("graph_ptr", "in", off.astype(np.int64 if pb == 8 else np.int32)) if pb else None,
+                  idx_bytes=pb or 8, n_graphs=len(off) - 1 if pb else 1, walk_length=K, out=Arr("out", "out", shape=(g.n, K)))
+        yield mk("gnnmp_random_walk_pe_f32", f"{g.name}_K{K}_w{int(with_w)}_p{pb or 0}", tags, [Pl(g, T=True), job, STREAM], ref)
+
+
+@cases_of("gnnmp_gmm_weights_grad_f32")
+def _(ctx):
+    G = _mod("gmm_conv_ref")
+    for k, (E_, ein, K) in enumerate(G.WGRAD_CASES):                    # E = 1, 7, 257 and three slices and a remainder a block
+        how = (("de", "par"), ("par",), ("de",))[k % 3]
+        r = rng_of("gmm_weights_grad", E_, ein, K)
+        e = F(r, E_, ein)
+        sc = np.sqrt(6.0 / (K + ein))
+        mu, sinv = (sc * F(r, K, ein)).astype(f32), (sc * F(r, K, ein)).astype(f32)
+        w, dw = G.weights(e, mu, sinv), F(r, E_, K)
+        de64, dmu64, dsinv64, mag_mu, mag_s = G.wgrad64(e, mu, sinv, w, dw)
+
+        def bounded(v, mag, E_=E_):                                    # tests/test_gmm_conv_ad.py: the fp32 summation bound at the documented fold depth
+            return E(pred=lambda got: None if np.all(np.abs(got.astype(f64) - v) <= G.sum_bound(E_, mag)) else "outside the summation bound")
+
+        def ref(host, how=how, v=(de64, dmu64, dsinv64, mag_mu, mag_s)):
+            out = {"de": E(v[0])} if "de" in how else {}
+            if "par" in how:
+                out.update(dmu=bounded(v[1], v[3]), dsinv=bounded(v[2], v[4]),
+                           part=E(pred=lambda got: None if np.all(np.isfinite(got)) else "non-finite partials"))      # every element written: the slab's check
+            return out
+        par = "par" in how
+        job = Rec("gnnmp_gmm_weights_grad_t", e=Arr("e", "in", e), mu=Arr("mu", "in", mu), sinv=Arr("sinv", "in", sinv), w=Arr("w", "in", w), dw=Arr("dw", "in", dw),
+                  de=Arr("de", "out", shape=(E_, ein)) if "de" in how else None, dmu=Arr("dmu", "out", shape=(K, ein)) if par else None,
+                  dsinv=Arr("dsinv", "out", shape=(K, ein)) if par else None, part=Arr("part", "out", shape=(G.PARTS, 2, K, ein)) if par else None)
+        yield mk("gnnmp_gmm_weights_grad_f32", f"E{E_}_ein{ein}_K{K}_{'_'.join(how)}", ({"align"} if k in (4, 9, 11) else set()) | ({"side"} if k == 0 else set()),
+                 [job, E_, ein, K, STREAM], ref, no_warmup=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -1889,6 +3122,9 @@ SYNCHRONISES = {
     "gnnmp_unique_append": "Synchronises the stream",
     "gnnmp_induced_subgraph": "Synchronises the stream (the count is read on the host)",
     "gnnmp_rand_edge_split": "Synchronisations: 1 (the permutation's sort) + 1 when bidirected",
+    "gnnmp_coalesce_edges": "Synchronises the stream (graph prep)",
+    "gnnmp_compact_edges": "Synchronises the stream (graph prep)",
+    "gnnmp_random_walk_pe_f32": "Synchronises the stream (graph prep)",
 }
 ALLOCATES = {}
 WAITS_OR_ALLOCATES = re.compile(r"synchronis|hipMalloc|allocat", re.I)

@@ -80,6 +80,31 @@ def test_an_export_whose_own_comment_says_it_synchronises_is_not_captured():
     assert sorted(says) == sorted(A.SYNCHRONISES), set(says) ^ set(A.SYNCHRONISES)
 
 
+def _section_comment_of(export):
+    """the whole section comment (the one ruled off with dashes) that governs an export: a sentence about "all of them" stands after
+    the per-export paragraphs"""
+    import re
+    text = open(A.HEADER).read()
+    at = re.search(r"\b%s\s*\(" % re.escape(export), re.sub(r"/\*.*?\*/", lambda c: " " * len(c.group(0)), text, flags=re.S)).start()
+    sections = [c.group(0) for c in re.finditer(r"/\*.*?\*/", text, flags=re.S) if c.end() <= at and "-----" in c.group(0)]
+    return " ".join(sections[-1].replace("*", " ").split()) if sections else ""
+
+
+def test_a_case_is_recorded_cold_only_where_the_header_says_so():
+    """no_warmup (the capture test then records the call without an eager call first) is a promise of the header, quoted here: the
+    export's own comment or its section must say so; all cases of an export agree"""
+    n = 0
+    ctx = _dry_ctx()
+    for export in A.capturable():
+        cold = {c.no_warmup for c in A.TABLE[export](ctx)}
+        assert len(cold) == 1, export
+        if cold == {True}:
+            texts = " ".join(A.header_comments_of(export)) + " " + _section_comment_of(export)
+            assert "without an eager call first" in texts or "needs no eager call first" in texts, export
+            n += 1
+    assert n >= 30
+
+
 def test_variant_zero_is_the_data_the_table_always_had():
     """the salt must not move variant 0: a few cases rebuilt here from numpy's generator alone"""
     ctx = _dry_ctx()
@@ -115,10 +140,20 @@ def test_variant_zero_is_the_data_the_table_always_had():
 def _same_call(c0, c1):
     """problems if two variants of a case are not the same call on other float data; the names of the float inputs that differ"""
     problems, differ, floats = [], [], 0
-    if (c0.sid, c0.status, c0.knobs, len(c0.args)) != (c1.sid, c1.status, c1.knobs, len(c1.args)):
+    args0, args1 = list(A.flat_args(c0.args)), list(A.flat_args(c1.args))          # records opened: their fields are arguments like any other
+    if (c0.sid, c0.status, c0.knobs, len(args0), c0.no_warmup) != (c1.sid, c1.status, c1.knobs, len(args1), c1.no_warmup):
         return [f"{c0.export}[{c0.sid}] is another call in the other variant"], differ, floats
-    for a0, a1 in zip(c0.args, c1.args):
+    seen = set()
+    for a0, a1 in zip(args0, args1):
+        if isinstance(a0, A.Arr) and a0.base is not None:
+            if not (isinstance(a1, A.Arr) and a1.base is not None and (a0.name, a0.role, a0.base.name, a0.offset) == (a1.name, a1.role, a1.base.name, a1.offset)):
+                problems.append(f"view '{a0.name}' is another view")
+                continue
+            a0, a1 = a0.base, a1.base                # the bytes are the base's: compared once, under its name
         if isinstance(a0, A.Arr):
+            if a0.name in seen:
+                continue
+            seen.add(a0.name)
             if not isinstance(a1, A.Arr) or (a0.name, a0.role, a0.shape, a0.dtype) != (a1.name, a1.role, a1.shape, a1.dtype):
                 problems.append(f"array '{a0.name}' has another role, shape or type")
             elif a0.data is not None:
@@ -235,16 +270,20 @@ def _record_and_replay(lib, c0, c1, plans, side):
     assert not host, "an export that hands a result to the host cannot be launch-only"
     torch.cuda.synchronize()
 
-    # 1. eager, on the capture stream: the documented first-use growth of plan scratch and the one-time LDS opt-in happen here
-    rc = A.call(lib, c0, cargs)
-    torch.cuda.synchronize()
-    problems = A.verify(c0, rc, slab, {})
-    if problems:
-        return ["eager warm-up: " + p for p in problems]
-    eager = slab.outputs()
+    # 1. eager, on the capture stream: the documented first-use growth of plan scratch and the one-time LDS opt-in happen here.  An
+    # export whose comment says it "may be recorded into a HIP graph without an eager call first" is recorded cold: its plans are new
+    # (this test's own), nothing has run on them, and the eager bits are taken AFTER the replays instead
+    eager = None
+    if not c0.no_warmup:
+        rc = A.call(lib, c0, cargs)
+        torch.cuda.synchronize()
+        problems = A.verify(c0, rc, slab, {})
+        if problems:
+            return ["eager warm-up: " + p for p in problems]
+        eager = slab.outputs()
+        slab.reload()
 
     # 2. capture: the call is recorded, nothing runs
-    slab.reload()
     graph, rc, err = capture(lambda: A.call(lib, c0, cargs), side)
     if err or rc != c0.status:
         return [f"under stream capture the call returned {rc} (expected {c0.status}); gnnmp_last_error: "
@@ -259,6 +298,16 @@ def _record_and_replay(lib, c0, c1, plans, side):
     graph.replay()
     torch.cuda.synchronize()
     problems = ["replay 1: " + p for p in A.verify(c0, rc, slab, {})]
+    if eager is None and not problems:
+        first = slab.outputs()
+        slab.reload()
+        assert A.call(lib, c0, cargs) == rc
+        torch.cuda.synchronize()
+        eager = slab.outputs()
+        slab.reload()
+        graph.replay()
+        torch.cuda.synchronize()
+        problems += [p + " differs between the cold replay and the one after an eager call" for p in _same_bits(slab.outputs(), first, "replay 1")]
     if "_atomic_" not in c0.export:      # (the header's determinism rule leaves *_atomic_* out: A.verify's bound above is what it owes)
         problems += [p + " differs between the eager call and replay 1" for p in _same_bits(slab.outputs(), eager, "replay 1")]
     if problems:

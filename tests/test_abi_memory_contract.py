@@ -37,10 +37,15 @@ def _all_cases(ctx):
 
 def test_every_pointer_writing_export_is_covered_or_excluded_with_a_reason():
     from gnnmp import _lib
-    decls, _ = A.parse_header()
+    hdr = A.parse_header()
+    decls, _ = hdr
     assert set(decls) == set(_lib.SYMBOLS), set(decls) ^ set(_lib.SYMBOLS)
-    need = A.must_be_covered(decls, _lib.SYMBOLS)
-    assert len(need) > 80                                   # the parser sees the ABI (94 declarations take a stream)
+    why = {}
+    need = A.must_be_covered(decls, _lib.SYMBOLS, hdr.records, why)
+    assert len(need) > 112                                  # the parser sees the ABI: 81 exports write through a parameter, 35 through a record
+    # an export that takes `const gnnmp_<x>_t *job` writes through the record's non-const fields: a parser that lost the records would
+    # file all of them as "writes nothing" again
+    assert sum(w == "record" for w in why.values()) >= 30, why
     assert len(A.EXCLUDED_EXTRA) <= 8, "at most eight exports may be excluded beyond the lifecycle calls and the collective"
     assert all(isinstance(r, str) and len(r) > 20 for r in {**A.EXCLUDED, **A.EXCLUDED_EXTRA}.values())
     missing = []
@@ -54,39 +59,164 @@ def test_every_pointer_writing_export_is_covered_or_excluded_with_a_reason():
     assert set(A.TABLE) <= set(need), set(A.TABLE) - set(need)
 
 
+def test_the_rule_sees_a_write_through_a_record_and_only_that():
+    """the rule on a header of its own: a const record with a non-const pointer field is a write, one level down too; a record of
+    inputs, a host field and a handle are not"""
+    decls = {"f_writes": [("job", True, True, "const gnnmp_w_t *job"), ("stream", False, False, "gnnmp_stream_t stream")],
+             "f_nested": [("tab", True, True, "const gnnmp_outer_t *tab"), ("stream", False, False, "gnnmp_stream_t stream")],
+             "f_reads": [("job", True, True, "const gnnmp_r_t *job"), ("total", True, False, "int64_t *total"),
+                         ("stream", False, False, "gnnmp_stream_t stream")],
+             "f_nostream": [("job", True, True, "const gnnmp_w_t *job")]}
+    records = {"gnnmp_w_t": [("x", True, True, "const float *x"), ("n", False, False, "int64_t n"), ("y", True, False, "float *y")],
+               "gnnmp_r_t": [("x", True, True, "const float *x"), ("plan", True, False, "gnnmp_graph_t *plan"), ("total", True, False, "int64_t *total")],
+               "gnnmp_outer_t": [("n", False, False, "int n"), ("rels", True, True, "const gnnmp_w_t *rels")]}
+    why = {}
+    assert A.must_be_covered(decls, list(decls), records, why) == ["f_writes", "f_nested"]
+    assert why == {"f_writes": "record", "f_nested": "record"}
+    assert A.writes_of("f_nested", decls["f_nested"], records) == ([], [("gnnmp_w_t", "y")])
+
+
+def _check_roles(export, decl_fields, values, records, count):
+    """one level of a call: the parameters of a declaration, or the fields of a record"""
+    assert len(values) == len(decl_fields), (export, len(values), len(decl_fields))
+    for (pname, is_ptr, is_const, text), a in zip(decl_fields, values):
+        rtype = A.record_of(text, records) if is_ptr else None
+        if isinstance(a, A.Arr):
+            count[0] += 1
+            assert is_ptr and rtype is None and not A.is_host_param(export, pname), (export, pname)
+            assert a.field == pname, f"{export}: array '{a.name}' is passed as '{pname}'"
+            assert (a.role == "in") == is_const, f"{export}: '{pname}' is {'const' if is_const else 'non-const'} in the header, the case says '{a.role}'"
+        elif isinstance(a, A.Rec) or (isinstance(a, (list, tuple)) and a and isinstance(a[0], A.Rec)):
+            for r in ([a] if isinstance(a, A.Rec) else a):
+                assert rtype == r.ctype, f"{export}: '{pname}' is {text!r}, the case passes a {r.ctype}"
+                assert list(r.fields) == [f[0] for f in records[rtype]], f"{export}: the fields of {rtype} are {[f[0] for f in records[rtype]]}, the case gives {list(r.fields)}"
+                _check_roles(export, records[rtype], list(r.fields.values()), records, count)
+        elif isinstance(a, A.Pl):
+            assert "gnnmp_graph_t" in text, (export, pname)
+        elif a is A.STREAM:
+            assert "gnnmp_stream_t" in text, (export, pname)
+        elif isinstance(a, A.HostOut):
+            assert A.is_host_param(export, pname) and not is_const, (export, pname)
+        elif a is None:
+            assert is_ptr, (export, pname)
+        else:
+            assert not is_ptr, f"{export}: '{pname}' is a pointer, the case passes {a!r}"
+
+
 def test_case_roles_agree_with_the_header():
-    """const T * is an input; T * is an output, in-out or caller scratch — and every call has as many arguments as the declaration"""
+    """const T * is an input; T * is an output, in-out or caller scratch — for a parameter and for a field of a record alike; every call
+    has as many arguments as the declaration, every record as many fields as the header's, in its order"""
     from gnnmp import _lib
-    decls, _ = A.parse_header()
+    hdr = A.parse_header()
+    decls, _ = hdr
     lib_sig = {}
     try:
         lib = _lib.load()
         lib_sig = {name: len(getattr(lib, name).argtypes) for name in A.TABLE}
     except (ImportError, OSError):
         pass
-    n = 0
+    n, nrec = [0], [0]
     for case in _all_cases(_dry_ctx()):
         decl = decls[case.export]
-        assert len(case.args) == len(decl), (case.export, case.sid, len(case.args), len(decl))
         if lib_sig:
             assert lib_sig[case.export] == len(decl), case.export
-        for (pname, is_ptr, is_const, text), a in zip(decl, case.args):
-            if isinstance(a, A.Arr):
-                n += 1
-                assert is_ptr and not A.is_host_param(case.export, pname), (case.export, pname)
-                assert a.name == pname, f"{case.export}: array '{a.name}' is passed as parameter '{pname}'"
-                assert (a.role == "in") == is_const, f"{case.export}: '{pname}' is {'const' if is_const else 'non-const'} in the header, the case says '{a.role}'"
-            elif isinstance(a, A.Pl):
-                assert "gnnmp_graph_t" in text, (case.export, pname)
-            elif a is A.STREAM:
-                assert "gnnmp_stream_t" in text, (case.export, pname)
-            elif isinstance(a, A.HostOut):
-                assert A.is_host_param(case.export, pname) and not is_const, (case.export, pname)
-            elif a is None:
-                assert is_ptr, (case.export, pname)
-            else:
-                assert not is_ptr, f"{case.export}: '{pname}' is a pointer, the case passes {a!r}"
-    assert n > 2000
+        before = n[0]
+        _check_roles(case.export, decl, case.args, hdr.records, n)
+        if any(isinstance(a, A.Rec) for a in case.args):
+            nrec[0] += n[0] - before
+    assert n[0] > 2000 and nrec[0] > 200
+
+
+class _AnyHost(dict):
+    """the host results of a dry run: whatever the reference expects of them"""
+
+    class _Any:
+        def __eq__(self, other):
+            return True
+
+    def __getitem__(self, key):
+        return self._Any()
+
+
+class _NoPlans:
+    def get(self, p):
+        return ctypes.c_void_p(0x1000)
+
+
+def _bound_into_the_slab(case):
+    """bind() on a CPU slab: the call gets as many arguments as the case, a record argument is a pointer the library's argtypes accept,
+    and every pointer field of every record points into the array the case names (or is NULL where the case says None)"""
+    from gnnmp import _lib
+    slab = A.Slab(case.arrs, device="cpu")
+    cargs, host = A.bind(case, slab, _NoPlans())
+    assert len(cargs) == len(case.args)
+    try:
+        argtypes = getattr(_lib.load(), case.export).argtypes
+    except (ImportError, OSError):
+        argtypes = None
+    for k, (a, c) in enumerate(zip(case.args, cargs)):
+        if not (isinstance(a, A.Rec) or isinstance(a, (list, tuple))):
+            continue
+        if argtypes:
+            argtypes[k].from_param(c)                     # raises where ctypes would refuse the argument
+        recs, objs = ([a], [c._obj]) if isinstance(a, A.Rec) else (list(a), list(c._keep_table))
+        for rec, st in zip(recs, objs):
+            for fname, v in rec.fields.items():
+                if isinstance(v, A.Arr):
+                    b = v if v.base is None else v.base
+                    lo = slab.t.data_ptr() + b.off
+                    assert lo <= getattr(st, fname) <= lo + max(b.nbytes, 0), (case.export, case.sid, fname)
+                elif v is None:
+                    assert not getattr(st, fname), (case.export, case.sid, fname)
+
+
+def test_every_record_case_has_a_finite_reference_for_every_output():
+    """the dry run of the record builders: each case's reference (the float64 / exact restatement of its family's tests/*_ref.py) is
+    evaluated without a GPU, names exactly the out / in-out arrays of the slab, and is finite wherever the call owes a finite value
+    (the identities of empty max / min rows are the documented exceptions: infinities, never NaN)"""
+    n = 0
+    for case in _all_cases(_dry_ctx()):
+        if not any(isinstance(a, A.Rec) or isinstance(a, (list, tuple)) for a in case.args) or case.status != A.OK:
+            continue
+        _bound_into_the_slab(case)
+        ref = case.ref(_AnyHost())
+        owed = {a.name for a in case.arrs if a.role in ("out", "inout")}
+        assert set(ref) == owed, (case.export, case.sid, set(ref) ^ owed)
+        for name, e in ref.items():
+            v = e.value if isinstance(e, A.E) else e
+            if v is None:
+                assert e.pred is not None, (case.export, case.sid, name)
+                continue
+            v = np.asarray(v, np.float64)
+            if isinstance(e, A.E) and e.rows is not None:
+                v = v[e.rows]
+            assert not np.isnan(v).any() or case.export.startswith("gnnmp_hetero_"), (case.export, case.sid, name)      # -Inf + Inf of a + fold over empty max and min rows
+            n += 1
+    assert n > 900
+
+
+_LP64 = {"int": 4, "float": 4, "int32_t": 4, "uint32_t": 4, "int64_t": 8, "uint64_t": 8, "double": 8}
+
+
+def test_every_record_of_the_header_has_its_structure():
+    """gnnmp/_lib.py must lay every `typedef struct { ... } gnnmp_<x>_t;` out as the C compiler does on LP64: the same field names in
+    the same order, every field at the offset its parsed type gives (a pointer 8 bytes, aligned to its size), the same size"""
+    records = A.parse_header().records
+    assert len(records) >= 36
+    for rtype, fields in records.items():
+        st = A.struct_of(rtype)
+        assert [f[0] for f in st._fields_] == [f[0] for f in fields], rtype
+        off, worst = 0, 1
+        for fname, is_ptr, is_const, text in fields:
+            base = text.replace("const", "").split("*")[0].split()
+            size = 8 if is_ptr else _LP64[base[0]]
+            if not is_ptr:
+                assert len(base) == 2 and base[1] == fname, (rtype, text)
+            off = (off + size - 1) // size * size
+            assert getattr(st, fname).offset == off and getattr(st, fname).size == size, (rtype, fname, getattr(st, fname).offset, off)
+            off += size
+            worst = max(worst, size)
+        assert ctypes.sizeof(st) == (off + worst - 1) // worst * worst, rtype
 
 
 def test_the_table_has_the_shapes_the_contract_is_about():
@@ -163,6 +293,53 @@ def test_slab_reports_a_short_write_an_overrun_and_a_written_input(shift):
     _toy_view(slab, "out", np.float32, 12)[0] = 1.0
     p = slab.check({}, untouched=True)
     assert len(p) == 1 and "error status" in p[0], p
+
+    _rec_toy_reports_its_three_faults(shift)                # the same faults behind a record argument
+
+
+def _toy_rec(shifts=None):
+    """a record of four fields carved from a CPU slab: `x` read, `short`, `past` and `ok` written"""
+    x = np.arange(8, dtype=np.float32)
+    rec = A.Rec("gnnmp_toy_t", x=A.Arr("x", "in", x), n=8, short=A.Arr("short", "out", shape=(8,)), past=A.Arr("past", "out", shape=(8,)),
+                ok=A.Arr("ok", "out", shape=(8,)))
+    case = A.Case("toy", "rec", [rec, A.STREAM], None)
+    assert [a.name for a in case.arrs] == ["x", "short", "past", "ok"]           # the slab holds what the record points at
+    return x, case, A.Slab(case.arrs, device="cpu", shifts=shifts)
+
+
+def _rec_toy_reports_its_three_faults(shift):
+    """the toy wrapped in a Rec: one field written one element short, one written one element past its end, and a store into the `in`
+    field — exactly those three problems, so an array that is reached through a record is watched like any other"""
+    shifts = {"x": shift, "short": shift, "past": shift, "ok": shift}
+    x, case, slab = _toy_rec(shifts)
+    ref = {"short": A.E(x, "exact"), "past": A.E(x + 1, "exact"), "ok": A.E(x + 2, "exact")}
+    for name, k in (("short", 0), ("past", 1), ("ok", 2)):
+        _toy_view(slab, name, np.float32, 8)[:] = x + k
+    assert slab.check(ref) == []
+
+    x, case, slab = _toy_rec(shifts)
+    _toy_view(slab, "short", np.float32, 8)[:7] = x[:7]
+    v = _toy_view(slab, "past", np.float32, 9)
+    v[:8] = x + 1
+    v[8] = 7.0
+    _toy_view(slab, "ok", np.float32, 8)[:] = x + 2
+    _toy_view(slab, "x", np.float32, 8)[3] = -1.0
+    p = slab.check(ref)
+    assert len(p) == 3, p
+    assert "stray" in p[0] and "inside in array 'x' (element 3)" in p[0], p
+    assert "stray" in p[1] and "0 bytes past the end of array 'past'" in p[1], p
+    assert "output 'short': 1 of 8 element(s) never written, first at element 7" in p[2], p
+
+
+def test_a_view_is_a_pointer_into_its_base_and_owns_no_bytes():
+    panel = A.Arr("panel", "inout", np.zeros((5, 12), np.float32))
+    z, out = A.Arr("z", "in", base=panel, offset=0), A.Arr("out", "out", base=panel, offset=8)
+    case = A.Case("toy", "view", [A.Rec("gnnmp_toy_t", z=z, out=out, ld=12), A.STREAM], None)
+    assert [a.name for a in case.arrs] == ["panel"]
+    slab = A.Slab(case.arrs, device="cpu", shifts={"panel": 8})
+    assert slab.ptr_of(out).value - slab.ptr_of(z).value == 32 and slab.ptr_of(z).value == slab.ptr("panel").value
+    with pytest.raises(AssertionError):
+        A.Arr("w", "out", base=A.Arr("ro", "in", np.zeros(4, np.float32)))       # nothing is written through an input
 
 
 def test_slab_pattern_is_a_nan_at_every_element_alignment():
