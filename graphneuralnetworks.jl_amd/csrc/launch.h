@@ -101,4 +101,10 @@ int check_transposed(const char *who, const gnnmp_graph_t *plan, const gnnmp_gra
 // them") — the plan was not built with self loops of its own, which lie beyond those arrays' last row.
 int check_edge_plan(const char *who, const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, bool need_square, const char *no_row);
 
+// ---- plan_batch.hip -------------------------------------------------------------------------------------------------------------
+// A square plan of n_rows rows and n_slots slots whose rowptr / col / eid live in ONE block of the stream-ordered pool (pool.h), sizes,
+// self-loop flag and long-row threshold set, index arrays not yet written: gnnmp_plan_select's allocation without a member table, for
+// the plans plan_edit.hip derives.  The caller fills the arrays on `stream`, then sets max_degree / calls plan_build_long_rows.
+int pooled_plan_alloc(gnnmp_graph_t **out, int64_t n_rows, int64_t n_slots, int self_loops, hipStream_t stream);
+
 }  // namespace gnnmp

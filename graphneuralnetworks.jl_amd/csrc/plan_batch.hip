@@ -243,6 +243,11 @@ static int batch_plan_alloc(gnnmp_graph_t **out, BatchTab *tab, int64_t k, int64
     return GNNMP_OK;
 }
 
+int pooled_plan_alloc(gnnmp_graph_t **out, int64_t n_rows, int64_t n_slots, int self_loops, hipStream_t stream) {
+    BatchTab tab = {};   // (k = 0: the member table is three empty pieces of the block)
+    return batch_plan_alloc(out, &tab, 0, n_rows, n_slots, self_loops, stream);
+}
+
 static int batch_plan_fill(gnnmp_graph_t *p, const BatchTab &tab, int64_t k, int32_t *node_map, void *indicator, int ind_bytes,
                            int ind_base, int64_t max_degree_bound, hipStream_t stream) {
     const unsigned row_blocks = (unsigned)((p->n_dst + 1 + 255) / 256);

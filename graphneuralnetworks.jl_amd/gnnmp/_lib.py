@@ -25,6 +25,7 @@ SYMBOLS = (
     "gnnmp_version", "gnnmp_last_error",
     "gnnmp_plan_create", "gnnmp_plan_from_csc", "gnnmp_plan_destroy", "gnnmp_plan_info", "gnnmp_plan_export", "gnnmp_plan_export64",
     "gnnmp_plan_concat", "gnnmp_plan_select", "gnnmp_plan_release", "gnnmp_plan_status", "gnnmp_plan_edge_index",
+    "gnnmp_plan_remove_nodes", "gnnmp_plan_add_edges",
     "gnnmp_chain_jobs_pack", "gnnmp_chain_jobs_release", "gnnmp_chain_jobs_export",
     "gnnmp_arena_create", "gnnmp_arena_destroy", "gnnmp_arena_alloc", "gnnmp_arena_reset", "gnnmp_arena_class_of", "gnnmp_arena_info",
     "gnnmp_add_self_loops", "gnnmp_batch_coo",
@@ -354,6 +355,8 @@ def load():
         "gnnmp_plan_release": [vp, vp],
         "gnnmp_plan_status": [vp, vp],
         "gnnmp_plan_edge_index": [vp, i, i, vp, vp, vp],
+        "gnnmp_plan_remove_nodes": [ctypes.POINTER(vp), vp, vp, i, i, i64, f, u64, vp, vp, vp, ctypes.POINTER(i64), vp],
+        "gnnmp_plan_add_edges": [ctypes.POINTER(vp), vp, vp, vp, i, i, i64, i64, u64, vp, vp, vp],
         "gnnmp_chain_jobs_pack": [ctypes.POINTER(vp), vp, i64, i64, i64, i, vp],
         "gnnmp_chain_jobs_release": [vp, vp],
         "gnnmp_chain_jobs_export": [vp, vp, i64, vp, vp],

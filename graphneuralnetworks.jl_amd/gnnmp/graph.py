@@ -287,9 +287,11 @@ class GNNGraph:
         key = bool(add_self_loops)
         p = self._plans.get(key)
         if p is None:
-            p = Plan(self.s, self.t, self.num_nodes, self.num_nodes, self.index_base, key,
-                     validate=not self._indices_validated)
-            self._indices_validated = True
+            p = self._derive_plan(key)
+            if p is None:
+                p = Plan(self.s, self.t, self.num_nodes, self.num_nodes, self.index_base, key,
+                         validate=not self._indices_validated)
+                self._indices_validated = True
             self._plans[key] = p
         return p
 
@@ -299,11 +301,20 @@ class GNNGraph:
         key = ("T", bool(add_self_loops))
         p = self._plans.get(key)
         if p is None:
-            p = Plan(self.t, self.s, self.num_nodes, self.num_nodes, self.index_base, key[1],
-                     validate=not self._indices_validated)
-            self._indices_validated = True
+            p = self._derive_plan(key)
+            if p is None:
+                p = Plan(self.t, self.s, self.num_nodes, self.num_nodes, self.index_base, key[1],
+                         validate=not self._indices_validated)
+                self._indices_validated = True
             self._plans[key] = p
         return p
+
+    def _derive_plan(self, key):
+        """A graph made by remove_nodes / add_edges / add_nodes / perturb_edges (gnnmp/transform.py) derives the plan `key` from its
+        parent's cached plan of the same kind (gnnmp_plan_remove_nodes / gnnmp_plan_add_edges: no sort); None when it has no parent or
+        the parent holds no such plan — the plan is then built from the COO as for any graph."""
+        src = getattr(self, "_plan_source", None)
+        return None if src is None else src(key)
 
     @property
     def idx_bytes(self):

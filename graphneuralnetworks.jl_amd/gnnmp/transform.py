@@ -8,17 +8,25 @@
   has_multi_edges       GNNGraphs/src/query.jl:575-579
   has_isolated_nodes    GNNGraphs/src/query.jl:420-422
   random_walk_pe        GNNGraphs/src/transform.jl:975-990
+  remove_nodes          GNNGraphs/src/transform.jl:212-276
+  add_edges             GNNGraphs/src/transform.jl:319-353
+  perturb_edges         GNNGraphs/src/transform.jl:385-420
+  add_nodes             GNNGraphs/src/transform.jl:553-561
 
 Coalescing parallel edges is a bipartite plan from the input edges to the output edges, and aggregating edge data over it is
 propagate(copy_xj, aggr): `coalesce_edges` returns the new graph together with an `EdgeCoalescing` that holds that plan, and the three
 reference transforms are thin wrappers.  This container keeps edge data outside the graph (only the weights `g.w` live in it), so every
 transform takes `edata` — a tensor [E, ...] or a dict of them — and returns it transformed next to the new graph.
 
+The four structural augmentations at the end of the list edit the graph's PLAN (csrc/plan_edit.hip): the child's dst-sorted CSR is
+written from the parent's cached plan without a sort, once per kind of plan the parent holds (plain, self-looped, transposed), lazily.
+
 Every index and arithmetic step is a libgnnmp call; torch allocates and slices.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import numbers
 
 import torch
@@ -217,3 +225,228 @@ def random_walk_pe(g: GNNGraph, walk_length: int):
         raise ValueError(L.load().gnnmp_last_error().decode())      # an edge between two member graphs, an indicator that is not sorted
     L.check(rc)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# structural augmentations on derived plans (csrc/plan_edit.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _plain_graph(g, who):
+    """the four augmentations take a COO GNNGraph; the other containers are refused by name"""
+    if getattr(g, "is_hetero", False):
+        raise TypeError(f"{who}: GNNHeteroGraph is not supported")
+    from .temporal_graph import TemporalSnapshotsGNNGraph
+    if isinstance(g, TemporalSnapshotsGNNGraph):
+        raise TypeError(f"{who}: TemporalSnapshotsGNNGraph is not supported")
+    if not isinstance(g, GNNGraph):
+        raise TypeError(f"{who}: expected a GNNGraph, got {type(g).__name__}")
+    if g.graph_type == "sparse":
+        raise TypeError(f"{who}: sparse-matrix graphs (GNNGraph.from_sparse) are not supported")
+
+
+def _idx_dtype(g: GNNGraph):
+    return torch.int64 if g.idx_bytes == 8 else torch.int32
+
+
+def _take(x, idx0):
+    """rows idx0 (int32, 0-based) of a feature tensor / dict of them; index vectors are copied word by word through the float gather"""
+    if x is None:
+        return None
+    if isinstance(x, dict):
+        return {k: _take(v, idx0) for k, v in x.items()}
+    if idx0.numel() == 0:
+        return x[:0].clone()
+    if x.dtype in (torch.int64, torch.int32):
+        words = 2 if x.dtype == torch.int64 else 1
+        src = x.contiguous().view(torch.float32).view(x.shape[0], words)
+        return _gather(src, idx0, 0).view(x.dtype).view(idx0.numel())
+    return _gather(x, idx0, 0)
+
+
+def _cat(a, b):
+    if isinstance(a, dict):
+        if not isinstance(b, dict) or sorted(a) != sorted(b):
+            raise ValueError("cannot concatenate feature data with different keys")
+        return {k: _cat(a[k], b[k]) for k in a}
+    return torch.cat([a, torch.as_tensor(b).to(device=a.device, dtype=a.dtype)])
+
+
+def _seed64(seed):
+    if seed is None:
+        from .linkpred import _next_seed
+        seed = _next_seed()
+    return int(seed) & _MASK64
+
+
+def _plan_remove(pp: Plan, g: GNNGraph, lst, p, seed, maps):
+    """gnnmp_plan_remove_nodes on one of g's plans -> (child plan, kept nodes, kept edge positions): int32, 0-based, None unless `maps`"""
+    h = ctypes.c_void_p()
+    total = (ctypes.c_int64 * 2)()
+    nm = em = None
+    if maps:
+        nm = torch.empty(pp.n_dst, dtype=torch.int32, device=g.device)
+        em = torch.empty(pp.n_edges, dtype=torch.int32, device=g.device)
+    rc = L.load().gnnmp_plan_remove_nodes(ctypes.byref(h), pp.handle, L.ptr(lst), g.idx_bytes, g.index_base,
+                                          0 if lst is None else lst.numel(), float(p), ctypes.c_uint64(seed), L.ptr(nm), None, L.ptr(em),
+                                          total, L.stream_ptr())
+    if rc == L.EBOUNDS:
+        raise IndexError(L.load().gnnmp_last_error().decode())
+    L.check(rc)
+    plan = Plan._adopt(h, g.device)
+    return (plan, nm[:total[0]], em[:total[1]]) if maps else (plan, None, None)
+
+
+def remove_nodes(g: GNNGraph, nodes_or_p, edata=None, seed=None):
+    """remove_nodes(g, nodes_to_remove) / remove_nodes(g, p): the graph without the listed nodes (ids in g's index base, any order,
+    repeats allowed; an id outside the graph is an IndexError) or without the nodes a Bernoulli(p) mask drops (reproducible in `seed`;
+    seed = None draws from the module-level sequence of gnnmp.linkpred), and without every edge that touched one.  The kept nodes and
+    edges keep their order and are renumbered; `.nid` / `.eid` of the result list them in g's numbering, as induced_subgraph sets them.
+    Node features, weights and `edata` follow.  -> g2, or (g2, edata2) when edata is given.
+
+    Deviation: the reference passes g's graph_indicator through unchanged (then longer than the new node count); here it is gathered by
+    `.nid`, and num_graphs is kept.
+
+    g2's plans are derived from g's cached plans of the same kind (gnnmp_plan_remove_nodes: no sort), each on first use."""
+    _plain_graph(g, "remove_nodes")
+    check_num_edges(g, edata)
+    lst, p = None, 0.0
+    if isinstance(nodes_or_p, numbers.Real) and not isinstance(nodes_or_p, numbers.Integral) or (
+            isinstance(nodes_or_p, torch.Tensor) and nodes_or_p.dim() == 0 and nodes_or_p.dtype.is_floating_point):
+        p = float(nodes_or_p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"remove_nodes: probability {p} outside [0, 1]")
+        seed = _seed64(seed)
+    else:
+        idx = nodes_or_p if isinstance(nodes_or_p, torch.Tensor) else torch.as_tensor(nodes_or_p)
+        if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+            if idx.numel() > 0:
+                raise TypeError("remove_nodes: node ids must be integers")
+            idx = idx.to(torch.int64)
+        lst = idx.reshape(-1).to(device=g.device, dtype=_idx_dtype(g)).contiguous()
+        seed = 0
+    plan, nid0, eid0 = _plan_remove(g.plan(False), g, lst, p, seed, True)
+    dt = _idx_dtype(g)
+    child = GNNGraph._from_plan(plan, g.num_graphs, _take(g.graph_indicator, nid0), _take(g.x, nid0), g.index_base, dt)
+    child.w = _take(g.w, eid0)
+    child.nid, child.eid = nid0.to(dt) + g.index_base, eid0.to(dt) + g.index_base
+
+    def derive(key):
+        pp = g._plans.get(key)
+        return None if pp is None else _plan_remove(pp, g, lst, p, seed, False)[0]
+    child._plan_source = derive
+    return child if edata is None else (child, _take(edata, eid0))
+
+
+def _plan_add(pp: Plan, g: GNNGraph, s_new, t_new, m, n_nodes, seed=0, outs=(None, None)):
+    h = ctypes.c_void_p()
+    rc = L.load().gnnmp_plan_add_edges(ctypes.byref(h), pp.handle, L.ptr(s_new), L.ptr(t_new), g.idx_bytes, g.index_base, m, n_nodes,
+                                       ctypes.c_uint64(seed), L.ptr(outs[0]), L.ptr(outs[1]), L.stream_ptr())
+    if rc == L.EBOUNDS:
+        raise AssertionError(L.load().gnnmp_last_error().decode())      # the reference's @assert minimum(snew) >= 1
+    L.check(rc)
+    return Plan._adopt(h, g.device)
+
+
+def _grow(g: GNNGraph, s_new, t_new, w_new, m, n_nodes, x_new=None, gi_new=None, seed=None):
+    """g plus m edges (s_new = None: drawn on the device from `seed`) on n_nodes >= g.num_nodes nodes"""
+    N = g.num_nodes
+    x, gi = g.x, g.graph_indicator
+    if n_nodes > N:
+        if (x is None) != (x_new is None):
+            raise ValueError("node features for the new nodes are needed exactly when the graph has node features"
+                             f" ({n_nodes - N} new nodes)")
+        if x is not None:
+            x_new = torch.as_tensor(x_new).to(device=g.device, dtype=torch.float32)
+            if x_new.shape[0] != n_nodes - N or tuple(x_new.shape[1:]) != tuple(x.shape[1:]):
+                raise ValueError(f"expected node features of shape {(n_nodes - N,) + tuple(x.shape[1:])}, got {tuple(x_new.shape)}")
+            x = torch.cat([x, x_new])
+        if gi is not None:
+            if gi_new is None:
+                raise ValueError("new nodes of a batched graph need their graph_indicator (add_nodes(g, n, graph_indicator = ...))")
+            gi_new = torch.as_tensor(gi_new).reshape(-1).to(device=g.device, dtype=gi.dtype)
+            if gi_new.numel() != n_nodes - N:
+                raise ValueError(f"expected {n_nodes - N} graph_indicator entries, got {gi_new.numel()}")
+            gi = torch.cat([gi, gi_new])
+    dt = _idx_dtype(g)
+    if s_new is None and m > 0:
+        s_new, t_new = torch.empty(m, dtype=dt, device=g.device), torch.empty(m, dtype=dt, device=g.device)
+        plan = _plan_add(g.plan(False), g, None, None, m, n_nodes, seed, (s_new, t_new))
+    else:
+        plan = _plan_add(g.plan(False), g, s_new, t_new, m, n_nodes)
+    child = GNNGraph._from_plan(plan, g.num_graphs, gi, x, g.index_base, dt)
+    if g.w is not None or w_new is not None:                       # cat_features (utils.jl:119-122): a missing side is ones
+        w_old = g.w if g.w is not None else torch.ones(g.num_edges, dtype=torch.float32, device=g.device)
+        child.w = torch.cat([w_old, w_new if w_new is not None else torch.ones(m, dtype=torch.float32, device=g.device)])
+
+    def derive(key):
+        pp = g._plans.get(key)
+        if pp is None:
+            return None
+        return _plan_add(pp, g, t_new, s_new, m, n_nodes) if isinstance(key, tuple) else _plan_add(pp, g, s_new, t_new, m, n_nodes)
+    child._plan_source = derive
+    return child
+
+
+def add_edges(g: GNNGraph, s, t=None, w=None, edata=None, new_edata=None, num_nodes=None):
+    """add_edges(g, s, t) / add_edges(g, (s, t)) / add_edges(g, (s, t, w)): g with the edges s -> t appended to its edge list.  Weights
+    follow the reference's cat_features: when only one side has them the other side weighs 1.  `edata` (g's) and `new_edata` (the new
+    edges') are concatenated and returned next to the graph.  No new edge returns g itself.  An index above g.num_nodes adds nodes
+    (num_nodes = ... says how many the result has and saves reading the maximum back); they need rows of node features when g has
+    them, which add_nodes takes — here that is a ValueError.  An index below the index base is an AssertionError, as in the reference.
+
+    The result's plans are derived from g's cached plans of the same kind (gnnmp_plan_add_edges), each on first use."""
+    _plain_graph(g, "add_edges")
+    if t is None and isinstance(s, (tuple, list)) and len(s) in (2, 3) and not isinstance(s[0], numbers.Number):
+        tup = s
+        s, t = tup[0], tup[1]
+        w = tup[2] if len(tup) == 3 else w
+    if t is None:
+        raise TypeError("add_edges: expected (g, s, t), (g, (s, t)) or (g, (s, t, w))")
+    check_num_edges(g, edata)
+    dt = _idx_dtype(g)
+    s = torch.as_tensor(s).reshape(-1).to(device=g.device, dtype=dt).contiguous()
+    t = torch.as_tensor(t).reshape(-1).to(device=g.device, dtype=dt).contiguous()
+    assert s.numel() == t.numel(), "length(snew) == length(tnew)"
+    m = s.numel()
+    if w is not None:
+        w = torch.as_tensor(w).reshape(-1).to(device=g.device, dtype=torch.float32).contiguous()
+        assert w.numel() == m, "length(wnew) == length(snew)"
+    if m == 0:
+        return g if edata is None else (g, edata)
+    if (edata is None) != (new_edata is None):
+        raise ValueError("add_edges: edata and new_edata go together")
+    if num_nodes is None:
+        n_nodes = max(g.num_nodes, int(torch.maximum(s.max(), t.max())) + 1 - g.index_base)
+    else:
+        n_nodes = int(num_nodes)
+        if n_nodes < g.num_nodes:
+            raise ValueError(f"add_edges: num_nodes = {n_nodes} below the graph's {g.num_nodes} nodes")
+    if n_nodes > g.num_nodes and g.x is not None:
+        raise ValueError(f"add_edges: {n_nodes - g.num_nodes} new nodes without node features (add_nodes(g, n, x) first)")
+    child = _grow(g, s, t, w, m, n_nodes)
+    return child if edata is None else (child, _cat(edata, new_edata))
+
+
+def add_nodes(g: GNNGraph, n: int, x=None, graph_indicator=None):
+    """add_nodes(g, n; ndata): n new, isolated nodes g.num_nodes + 1 .. g.num_nodes + n.  `x` [n, ...] is required exactly when g has
+    node features; a batched g also needs the new nodes' graph_indicator (in g's index base)."""
+    _plain_graph(g, "add_nodes")
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError(f"add_nodes: n must be a non-negative integer, got {n!r}")
+    if n == 0:
+        if x is not None and torch.as_tensor(x).shape[0] != 0:
+            raise ValueError("add_nodes: node features for 0 new nodes")
+        return g
+    return _grow(g, None, None, None, 0, g.num_nodes + int(n), x_new=x, gi_new=graph_indicator)
+
+
+def perturb_edges(g: GNNGraph, perturb_ratio, seed=None):
+    """perturb_edges(g, perturb_ratio): g plus ceil(num_edges * perturb_ratio) random edges without self loops, uniform over the ordered
+    pairs of distinct nodes (the distribution of the reference's rejection loop; the draw is the library's hash, reproducible in
+    `seed`; seed = None draws from the module-level sequence of gnnmp.linkpred).  The new edges of a weighted graph weigh 1."""
+    _plain_graph(g, "perturb_edges")
+    assert 0 <= perturb_ratio <= 1, "perturb_ratio must be between 0 and 1"
+    m = math.ceil(g.num_edges * float(perturb_ratio))
+    if m == 0:
+        return g
+    assert g.num_nodes > 1, "Graph must contain at least 2 nodes to add edges"
+    return _grow(g, None, None, None, m, g.num_nodes, seed=_seed64(seed))

@@ -857,6 +857,76 @@ function register_concat_plan!(gb::GNNGraph{<:COO_T}, gs::Vector{<:GNNGraph}; se
     return p
 end
 
+# ---- the structural augmentations on derived plans (csrc/plan_edit.hip) ------------------------------------------------------------------
+# remove_nodes (GNNGraphs/src/transform.jl:212-276), add_edges (:319-353), perturb_edges (:385-420) and add_nodes (:553-561) are applied to
+# a fresh batch every step of a contrastive training loop and the result is convolved at once.  The child's dst-sorted CSR is a filtered,
+# relabelled copy of the parent's: gnnmp_plan_remove_nodes / gnnmp_plan_add_edges write it from the parent's cached plan without a sort of
+# the parent's edges, and the plan is registered under the child's arrays like batch_from does, so every layer call on the child finds it.
+# The same call on the parent's self-looped or transposed plan (add_edges: with the pair swapped) gives the child's; node data is gathered
+# by the node map, edge weights by the edge map.  p::AbstractFloat draws the library's mask (a function of (seed, node)), not Julia's RNG.
+const GNNMP_EBOUNDS = Cint(-2)      # include/gnnmp.h: gnnmp_status
+
+function register_child_plan!(h::Ptr{Cvoid}, s, t, n::Integer; self_loops::Bool = false)
+    p = adopt_plan(h)
+    lock(PLANS_LOCK) do
+        ent = PlanEntry(p, true)
+        let ent = ent
+            finalizer(_ -> (@atomic ent.alive = false), s)
+            finalizer(_ -> (@atomic ent.alive = false), t)
+        end
+        PLANS[PlanKey(objectid(s), objectid(t), n, self_loops, false)] = ent
+    end
+    return p
+end
+
+function remove_nodes_from(g::GNNGraph{<:COO_T}, nodes::Union{ROCVector{Int64}, Nothing}; p::Float32 = 0.0f0, seed::UInt64 = rand(UInt64))
+    N, E = g.num_nodes, g.num_edges
+    nmap, emap = ROCVector{Int32}(undef, N), ROCVector{UInt32}(undef, E)
+    total = zeros(Int64, 2)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = @ccall libgnnmp.gnnmp_plan_remove_nodes(h::Ptr{Ptr{Cvoid}}, plan(g).handle::Ptr{Cvoid}, devptr(nodes)::Ptr{Cvoid}, 8::Cint, 1::Cint,
+                                                 (nodes === nothing ? 0 : length(nodes))::Int64, p::Cfloat, seed::UInt64,
+                                                 devptr(nmap)::Ptr{Cvoid}, C_NULL::Ptr{Cvoid}, devptr(emap)::Ptr{Cvoid},
+                                                 total::Ptr{Int64}, stream_ptr()::Ptr{Cvoid})::Cint
+    rc == GNNMP_EBOUNDS && throw(BoundsError(1:N, "remove_nodes: a listed node is outside the graph"))
+    check(rc)
+    n2, e2 = total
+    s, t = ROCVector{Int64}(undef, e2), ROCVector{Int64}(undef, e2)
+    check(@ccall libgnnmp.gnnmp_plan_edge_index(h[]::Ptr{Cvoid}, 8::Cint, 1::Cint, devptr(s)::Ptr{Cvoid}, devptr(t)::Ptr{Cvoid},
+                                                stream_ptr()::Ptr{Cvoid})::Cint)
+    register_child_plan!(h[], s, t, n2)
+    w = get_edge_weight(g)
+    w2 = w === nothing ? nothing : similar(w, e2)
+    w === nothing || check(@ccall libgnnmp.gnnmp_gather_f32(devptr(w)::Ptr{Cvoid}, devptr(emap)::Ptr{Cvoid}, 4::Cint, 0::Cint, e2::Int64,
+                                                            devptr(w2)::Ptr{Cvoid}, 1::Int64, stream_ptr()::Ptr{Cvoid})::Cint)
+    x = g.ndata.x
+    D = size(x, 1)
+    x2 = similar(x, D, n2)
+    check(@ccall libgnnmp.gnnmp_gather_f32(devptr(x)::Ptr{Cvoid}, devptr(nmap)::Ptr{Cvoid}, 4::Cint, 0::Cint, n2::Int64,
+                                           devptr(x2)::Ptr{Cvoid}, D::Int64, stream_ptr()::Ptr{Cvoid})::Cint)
+    return GNNGraph((s, t, w2), n2, e2, g.num_graphs, g.graph_indicator, GNNGraphs.DataStore(n2, (; x = x2)), GNNGraphs.DataStore(e2),
+                    g.gdata)
+end
+
+# snew === nothing: perturb_edges — m pairs drawn on the device, uniform over the ordered pairs of distinct nodes, written to snew / tnew
+function add_edges_from(g::GNNGraph{<:COO_T}, snew::Union{ROCVector{Int64}, Nothing}, tnew::Union{ROCVector{Int64}, Nothing}, m::Int,
+                        num_nodes::Int = g.num_nodes; seed::UInt64 = rand(UInt64))
+    so = snew === nothing ? ROCVector{Int64}(undef, m) : nothing
+    to = tnew === nothing ? ROCVector{Int64}(undef, m) : nothing
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    rc = @ccall libgnnmp.gnnmp_plan_add_edges(h::Ptr{Ptr{Cvoid}}, plan(g).handle::Ptr{Cvoid}, devptr(snew)::Ptr{Cvoid},
+                                              devptr(tnew)::Ptr{Cvoid}, 8::Cint, 1::Cint, m::Int64, num_nodes::Int64, seed::UInt64,
+                                              devptr(so)::Ptr{Cvoid}, devptr(to)::Ptr{Cvoid}, stream_ptr()::Ptr{Cvoid})::Cint
+    rc == GNNMP_EBOUNDS && throw(AssertionError("minimum(snew) >= 1 && minimum(tnew) >= 1"))
+    check(rc)
+    E2 = g.num_edges + m
+    s, t = ROCVector{Int64}(undef, E2), ROCVector{Int64}(undef, E2)
+    check(@ccall libgnnmp.gnnmp_plan_edge_index(h[]::Ptr{Cvoid}, 8::Cint, 1::Cint, devptr(s)::Ptr{Cvoid}, devptr(t)::Ptr{Cvoid},
+                                                stream_ptr()::Ptr{Cvoid})::Cint)
+    register_child_plan!(h[], s, t, num_nodes)
+    return s, t      # the caller builds the GNNGraph with cat_features of the weights, edata and ndata, as add_edges does (transform.jl:332-352)
+end
+
 # ---- the fused steps of the graph-classification chain's pullback (INTEGRATION.md §2f; examples/graph_classification_tudataset.jl:79-82) ----
 # Thin wrappers over the three round-5 entry points; a chain-level rrule strings them together exactly like the tested Python mirror
 # (gnnmp/backward.py: _GraphChainFn.backward) — same calls, same order, bit-identical gradients to the layer-by-layer rules above.

@@ -218,6 +218,63 @@ int gnnmp_plan_edge_index(const gnnmp_graph_t *plan, int idx_bytes, int index_ba
                           gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The plan of an EDITED graph from the plan of its parent, without a sort of the parent's edges (csrc/plan_edit.hip): the structural
+ * augmentations remove_nodes, add_edges, add_nodes and perturb_edges (GNNGraphs/src/transform.jl:212-276, 319-353, 385-420, 553-561) are
+ * applied to a fresh batch on every training step, and the child's dst-sorted stable CSR is a filtered, relabelled copy of the parent's:
+ * dropping nodes keeps the surviving slots of every surviving row in their order, appending edges only adds slots at the end of rows.
+ * Both results are bit-identical to gnnmp_plan_create on the child's COO with the parent's self-loop flag (rowptr, col, eid, and
+ * gnnmp_plan_info except the bytes held; tests/test_plan_edit.py), live in ONE block of the stream-ordered pool like the plans of
+ * gnnmp_plan_select (gnnmp_plan_release / gnnmp_plan_destroy both work on them), and leave the parent untouched.  `parent` must be square
+ * (n_src == n_dst = N), with or without plan-added self loops.  Only square-ness is assumed: the same call on the parent's TRANSPOSED plan
+ * (add_edges: with s_new and t_new swapped) gives the child's transposed plan with the same edge numbering.  gnnmp_plan_edge_index gives
+ * the child's s, t.
+ *
+ *   gnnmp_plan_remove_nodes  the plan of remove_nodes(g, nodes) / remove_nodes(g, p).
+ *       remove != NULL (list mode): n_remove node ids (idx_bytes / index_base like every index array), in any order, repeats allowed (the
+ *                      reference's sort(union(...)) allows them); p must be 0.  An id outside index_base .. N - 1 + index_base gives
+ *                      GNNMP_EBOUNDS — the reference does not check this (such an id only lowers its num_nodes).
+ *       remove == NULL (random mode): node i is removed exactly when gnnmp_dropout_keep_u8(seed, p, N, 1) would write keep[i][0] == 0
+ *                      (0 <= p <= 1; p = 1 removes every node) — a pure function of (seed, i), not Julia's RNG stream.
+ *       The kept nodes keep their ascending order and are renumbered 0 .. n_keep - 1; an edge survives iff both its endpoints do, and the
+ *       surviving edges keep their relative order and are renumbered 0 .. E_keep - 1 by their rank in the parent's edge list; a plan-added
+ *       self loop of a kept node stays, at E_keep + its new id.
+ *       Optional outputs (device, NULL to skip): node_map_out int32[n_keep] the old 0-based id of every child node (ascending);
+ *       node_new_out int32[N] the new 0-based id of every parent node, -1 for a removed one (written whole); edge_map_out uint32[E_keep]
+ *       the old 0-based position of every child edge (ascending).  The caller sizes node_map_out / edge_map_out for the worst case (N, E)
+ *       or from a first call; only the first n_keep / E_keep entries are written.
+ *       total (HOST memory, int64[2], required): total[0] = n_keep, total[1] = E_keep, always written.
+ *       ONE host synchronisation of `stream` (the two totals size the allocation); a second one only when a row of the child is longer than
+ *       the child's own long-row threshold (the chunk tables, as in every plan build).  Five integer passes (mark, scan, per-slot keep +
+ *       scans, fill); no float work, no sort.
+ *
+ *   gnnmp_plan_add_edges  the plan of add_edges(g, s_new, t_new) on n_nodes >= N nodes (nodes N .. n_nodes - 1 are new and isolated: with
+ *       m = 0 this is add_nodes), E + m edges: the parent's at their positions, the new ones at E .. E + m - 1.
+ *       s_new, t_new != NULL (list mode): m new edges; indices outside index_base .. n_nodes - 1 + index_base give GNNMP_EBOUNDS (checked
+ *                      on the device before anything is built).  s_new_out / t_new_out are ignored.
+ *       s_new == t_new == NULL (random mode, perturb_edges): new edge k is the ordered pair  s = mulhi32(h(k, 0), N),
+ *                      t' = mulhi32(h(k, 1), N - 1), t = t' + (t' >= s)  with h(k, j) the 32 bits gnnmp_dropout_keep_u8's hash gives for
+ *                      (seed, e = k, head = j) and mulhi32(a, b) = (a * b) >> 32 — uniform over the ordered pairs of the PARENT's nodes with
+ *                      s != t, the distribution of the reference's rejection loop, reproducible on the host.  The pairs are written to
+ *                      s_new_out / t_new_out (required; m entries of idx_bytes each, in index_base).  N < 2 with m > 0 is GNNMP_EINVAL (the
+ *                      reference's assertion).
+ *       Every row of the child is the parent's row followed by its new slots in position order; plan-added self loops are renumbered to
+ *       E + m + node and new nodes get theirs.
+ *       EVERY mode synchronises `stream`: the m new edges are grouped by destination with the stable radix sort (on them only, never on the
+ *       parent's E), and the chunk-table pass reads the child's longest row back, as gnnmp_plan_create does.  There is no
+ *       synchronisation-free path.
+ *
+ *   Refusals (before any device work): out / parent / total NULL, a non-square parent, idx_bytes / index_base, p outside [0, 1] (or p != 0
+ *   in list mode), negative counts, n_nodes < N, one of s_new / t_new alone, a NULL random-mode output: GNNMP_EINVAL; a child of
+ *   GNNMP_MAX_SLOTS slots or more (or 2^31 - 1 nodes): GNNMP_EUNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *remove, int idx_bytes, int index_base,
+                            int64_t n_remove, float p, uint64_t seed, int32_t *node_map_out, int32_t *node_new_out,
+                            uint32_t *edge_map_out, int64_t *total, gnnmp_stream_t stream);
+int gnnmp_plan_add_edges(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *s_new, const void *t_new, int idx_bytes,
+                         int index_base, int64_t m, int64_t n_nodes, uint64_t seed, void *s_new_out, void *t_new_out,
+                         gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * A placement-aware arena for the OUTPUTS of the gather kernels (csrc/arena.hip) — optional: the rule "the caller allocates" stands,
  * this is an allocator the caller may use.  Measured on MI355X (profiles/README.md, round 4): device memory falls into three placement
  * classes of 96 GiB of physical HBM each; a kernel that gathers ~27 random rows per row it writes (propagate, the fused GCN layer, the
