@@ -432,12 +432,17 @@ inline bool use_row_order(int64_t n_src, int64_t D) {
     return n_src * D * (int64_t)sizeof(float) > ((int64_t)128 << 20);
 }
 // lanes per row group: smallest power of two >= D / vec, clamped to [1, 64]
-inline int pick_log2g(int64_t lanes_needed) {
-    int forced = knob(KNOB_FORCE_LOG2G);
-    if (forced >= 0 && forced <= 6) return forced;
+inline int auto_log2g(int64_t lanes_needed) {
     int l = 0;
     while ((1 << l) < lanes_needed && l < 6) ++l;
     return l;
+}
+// the same, unless KNOB_FORCE_LOG2G pins the group.  A kernel without feature tiles cannot honour a forced width: its host path compares
+// the two and refuses (GNNMP_EUNSUPPORTED) before anything is written
+inline int pick_log2g(int64_t lanes_needed) {
+    int forced = knob(KNOB_FORCE_LOG2G);
+    if (forced >= 0 && forced <= 6) return forced;
+    return auto_log2g(lanes_needed);
 }
 // feature tiles (grid.y) of a row walk: groups of 1 << log2g lanes, vec features a lane, to cover D features
 inline int feature_tiles(int64_t D, int vec, int log2g) {

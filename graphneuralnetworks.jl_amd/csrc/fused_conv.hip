@@ -668,6 +668,8 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
         // against 5.77-5.82 (tools/experiments/sage_fused_ab.py, profiles/r06_sage_fused_ab.txt; see the kernel's header for why)
         if (knob(KNOB_FUSED_WAVES) == 0)
             return fail(GNNMP_EUNSUPPORTED, "fused_conv: root term with > 128 outputs, the two-kernel path is faster (knob 14 > 0 forces fused_cat_kernel)");
+        // fused_cat_kernel has no feature tiles either (32 lanes a row): refused before any work, see the main path below
+        if (pick_log2g((D + 3) / 4) != 5) return fail(GNNMP_EUNSUPPORTED, "fused_conv: lane-group width forced by a knob");
         const int NH = (int)(Dout / 128);
         const size_t pc = (size_t)p->n_chunks * (size_t)D, pl = (size_t)p->n_long * (size_t)D;
         const size_t wimg_at = (((pc + 3) & ~(size_t)3) + pl + 255) & ~(size_t)255;        // 1 KB aligned
@@ -680,8 +682,7 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
         ReduceArgs &r = a.r;
         r.rows = plan_rows(p); r.x = xj; r.w = w; r.ss = scale_src; r.w_slot = w_slot; r.ss_slot = ss_slot;
         r.sd = scale_dst; r.D = (int)D; r.n_src = (int)p->n_src; r.mean = (aggr == GNNMP_MEAN);
-        r.geom.log2g = pick_log2g((D + 3) / 4);
-        if (r.geom.log2g != 5) return fail(GNNMP_EUNSUPPORTED, "fused_conv: lane-group width forced by a knob");
+        r.geom.log2g = 5;
         a.agg_long = agg_long; a.agg_out = agg_out; a.xi = xi;
         a.w.W[0] = W_root; a.w.W[1] = W_agg; a.w.K[0] = (int)D1; a.w.K[1] = (int)D;
         a.w.sj[0] = ldw_root; a.w.sk[0] = 1; a.w.sj[1] = ldw_agg; a.w.sk[1] = 1;
@@ -707,6 +708,11 @@ extern "C" int gnnmp_fused_conv_f32(gnnmp_graph_t *p, int aggr, const float *xj,
     // by the LDS image: measured SAGEConv(100 => 128) on the products shape 5.95 ms fused vs 5.79 ms unfused.  Not by default.
     if (knob(KNOB_FUSED_WAVES) == 0 && D1 > 0)
         return fail(GNNMP_EUNSUPPORTED, "fused_conv: root term, unfused path is faster");
+    // fused_conv_kernel has no feature tiles (a lane gathers features lig * 4 .. and stores them to the LDS tile once): a narrower group
+    // than the width needs would leave columns of the tile unwritten, and the tile's rows-per-wave layout is sized for the derived
+    // group.  Refused before any work is launched, like the fused_cat branch above.
+    if (pick_log2g((D + 3) / 4) != auto_log2g((D + 3) / 4))
+        return fail(GNNMP_EUNSUPPORTED, "fused_conv: lane-group width forced by a knob");
     // split rows first: chunk partials + combine into the compact buffer behind the partials
     const size_t pc = (size_t)p->n_chunks * (size_t)D, pl = (size_t)p->n_long * (size_t)D;
     if (int rc = ensure_workspace(p, pc + pl + 4)) return rc;

@@ -7,7 +7,11 @@
 // clang-format off
 #define GNNMP_KNOB_TABLE(X)                                                                                                          \
     X(FORCE_VEC, 0, 0, "0 = auto, else 1|2|4")                                                                                       \
-    X(FORCE_LOG2G, 1, -1, "-1 = auto, else 0..6")                                                                                    \
+    X(FORCE_LOG2G, 1, -1, "lanes per row group = 2^value: -1 = auto, else 0..6 (pick_log2g).  Kernels with feature tiles honour any "    \
+                          "value.  gnnmp_fused_conv_f32 has none (a lane stores its features to the LDS tile once): it answers "     \
+                          "GNNMP_EUNSUPPORTED, nothing written, to any forced width other than the one it derives, and the host "    \
+                          "layers take propagate + dense.  The one-pass attention kernels and softmax_rows need the whole row in "   \
+                          "one group and derive their own (headgeom.h): the knob does not reach them")                               \
     X(UNROLL, 2, 0, "0 = auto (8: measured best on both bench shapes), else 2|4|8")                                                  \
     X(XCD_REMAP, 3, 1, "0 = off, 1 = auto (default: only when the gathered matrix fits the Infinity Cache), 2 = on")                 \
     X(LONG_ROW, 4, 0, "long-row threshold (0 = auto, at most GNNMP_LONG_ROW)")                                                       \

@@ -726,6 +726,114 @@ class Ctx:
         return (g.indeg() + (1 if loops else 0)) <= self.thr
 
 
+# ---- the geometry graphs (tests/test_row_geometry.py) -----------------------------------------------------------------------------------
+CHUNK_SLOTS = 128                 # csrc/plan.hip: plan_chunk_slots' default; the plan's threshold caps it
+GEOM_TAILS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65)       # the tails of U = 2, 4, 8 and of G = 1 .. 64
+GEOM_HUB_CHUNKS = 20              # the large hub spans more chunks than this: several fold slices at G = 32 (NG = 8), one-chunk slices at G = 1
+# destinations: for rows of 21 lanes and more / for rows of one to four lanes (up to 256 to a block).  Chosen so that with 1, 2, 3 and 4
+# waves a block every width of GeomCtx has at least 64 row blocks, a number of ordinary-row blocks that is no multiple of 8 and a partly
+# empty last block (tests/test_row_geometry.py asserts it)
+GEOM_N_WIDE, GEOM_N_NARROW = 1110, 17064
+
+
+def geom_lengths(thr):
+    """the row lengths a geometry graph must contain besides the three empty rows and its short random rest"""
+    clen = min(int(thr), CHUNK_SLOTS)
+    # each length once: at thr = 64 the tails 63, 64, 65 ARE thr - 1, thr, thr + 1.  A second row of thr + 1 would be a fourth split row,
+    # and the first positions of plan->row_order past the split rows (which every row kernel skips) would never be ordinary rows
+    want = GEOM_TAILS + (thr - 1, thr, thr + 1, 5 * thr + 3, GEOM_HUB_CHUNKS * clen + 1)
+    return tuple(dict.fromkeys(want))
+
+
+def geom_graph(name, n, thr, seed):
+    """row lengths as hub_graph builds them: destinations 0, n // 2 and n - 1 empty, geom_lengths(thr) at random interior rows, the
+    rest 1 .. 6; edges in random order.  Two rows hold one source only (multi-edges), and one source has more than thr edges, so the
+    transposed plan has a split row too"""
+    rng = np.random.default_rng(seed)
+    deg = rng.integers(1, 7, n)
+    want = geom_lengths(thr)
+    empty = [0, n // 2, n - 1]
+    free = np.setdiff1d(np.arange(n), empty)
+    at = rng.permutation(free)[:len(want)]
+    deg[at] = want
+    deg[empty] = 0
+    t = np.repeat(np.arange(1, n + 1), deg)
+    t = t[rng.permutation(len(t))]
+    s = rng.integers(1, n + 1, len(t))
+    s[rng.permutation(len(t))[:thr + 40]] = n // 3 + 1                    # one source of more than thr edges
+    for length, src in ((8, 2), (16, n - 1)):                            # multi-edges: a row whose edges all come from one source
+        s[t == at[want.index(length)] + 1] = src
+    g = Graph(name, s, t, n, thr=int(thr), want_split=int((deg > thr).sum()))
+    g.at = dict(zip(want, at))
+    return g
+
+
+def n_chunks_of(lengths, thr):
+    """chunk virtual rows of a plan with these row lengths (csrc/plan.hip: a row longer than thr is cut into balanced chunks of at most
+    min(thr, 128) slots)"""
+    clen = min(int(thr), CHUNK_SLOTS)
+    lengths = np.asarray(lengths, np.int64)
+    return int((-(-lengths[lengths > thr] // clen)).sum())
+
+
+def lanes_of(width, C=None):
+    """(vec, log2g) of a row of `width` floats at 16-byte aligned pointers (csrc/common.h: pick_vec, pick_log2g; C: the head width of
+    an attention row, csrc/headgeom.h: a lane's features lie inside one head)"""
+    vec = 4 if width % 4 == 0 else 2 if width % 2 == 0 else 1
+    while C is not None and vec > 1 and C % vec:
+        vec >>= 1
+    lanes, l = -(-width // vec), 0
+    while (1 << l) < lanes and l < 6:
+        l += 1
+    return vec, l
+
+
+def walk_blocks(n_rows, n_chunks, log2g, waves):
+    """(blocks, nbc, rows in the last block, rows per block) of a row walk (csrc/rowwalk.h: row_blocks, row_grid)"""
+    rpb = (64 >> log2g) * waves
+    total = n_rows + n_chunks
+    blocks = -(-total // rpb)
+    return blocks, min(blocks, -(-n_chunks // rpb)), total - (blocks - 1) * rpb, rpb
+
+
+class GeomCtx:
+    """Ctx for the builders of the kernels that remap, reorder and batch their row walk: the same cases on two graphs built for the
+    walk's edges (geom_graph) — `narrow` for rows of one or two lanes, `wide` for rows of 25 lanes and more.  Float data comes from
+    rng_of like the table's: its variant-0 stream, keyed by the graph's name, so the table's own data is untouched"""
+    variant = 0
+
+    def __init__(self, thr):
+        self.thr = int(thr)
+        self.wide = geom_graph("geom_wide", GEOM_N_WIDE, self.thr, 11)
+        self.narrow = geom_graph("geom_narrow", GEOM_N_NARROW, self.thr, 12)
+        self.cache = {}
+
+    def widths(self):
+        """(graph, row width): 1, 2 and 3 floats (one lane, vec 1 and 2), 100 (25 of 32 lanes, rows that are not whole 128-byte
+        lines: no row order), 128 (row order applies), 260 (two feature tiles of 64 lanes)"""
+        return [(self.narrow, 1), (self.wide, 100), (self.narrow, 3), (self.wide, 128), (self.narrow, 2), (self.wide, 260)]
+
+    def graph_shapes(self, **_):
+        for g, D in self.widths():
+            yield g, D, set()
+
+    def att_shapes(self, loops):
+        """(graph, H, C, tags): 32 lanes with DPP heads, 4 lanes (16 rows to a wave), an odd head width, one lane a row"""
+        yield self.wide, 8, 16, set()
+        yield self.narrow, 2, 8, set()
+        yield self.wide, 3, 7, set()
+        yield self.narrow, 1, 1, set()
+
+    def nn_shapes(self):
+        return [(self.narrow, 3, 1, ()), (self.wide, 2, 70, ()), (self.narrow, 4, 8, ())]
+
+    def fused_shapes(self):
+        return [(self.wide, 100, 0, 100, ()), (self.wide, 128, 0, 128, ()), (self.wide, 64, 64, 128, ())]
+
+    def short_rows(self, g, loops=False):
+        return (g.indeg() + (1 if loops else 0)) <= self.thr
+
+
 def row_shapes(Ds=DS, small=(3, 128), align=(3, 6, 128)):
     first = True
     for D in Ds:
@@ -994,7 +1102,8 @@ def _(ctx):
 
 @cases_of("gnnmp_propagate_nn_f32")
 def _(ctx):
-    shapes = [(ctx.hub, 3, 5, {"align", "side", "ws"}), (ctx.hub, 4, 4, {"align"}), (ctx.hub, 7, 2, ()), (ctx.hub, 1, 1, ()), (ctx.hub, 6, 33, {"align"}),
+    shapes = ctx.nn_shapes() if hasattr(ctx, "nn_shapes") else \
+             [(ctx.hub, 3, 5, {"align", "side", "ws"}), (ctx.hub, 4, 4, {"align"}), (ctx.hub, 7, 2, ()), (ctx.hub, 1, 1, ()), (ctx.hub, 6, 33, {"align"}),
               (ctx.e0, 3, 4, ()), (ctx.one, 4, 3, ()), (ctx.r31, 2, 6, ()), (ctx.r33, 5, 3, ()), (ctx.r300, 4, 8, ()),
               (ctx.r300, 3, 1, ()), (ctx.r300, 2, 70, ())]         # 64 rows to a wave; two feature tiles (a lane per output feature)
     for k, (g, Din, Dout, tags) in enumerate(shapes):
@@ -1310,7 +1419,8 @@ def _(ctx):
 # ---- softmax and attention -------------------------------------------------------------------------------------------------------
 @cases_of("gnnmp_edge_softmax_f32")
 def _(ctx):
-    for g, H, tags in list(ctx.graph_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129), small=(3, 4), ws=(3,))) + [(ctx.r300, 260, set())]:   # (two feature tiles)
+    more = [(ctx.r300, 260, set())] if hasattr(ctx, "r300") else []                                        # (two feature tiles)
+    for g, H, tags in list(ctx.graph_shapes(Ds=(1, 2, 3, 4, 6, 7, 100, 129), small=(3, 4), ws=(3,))) + more:
         lg = F(rng_of("edge_softmax", g.name, H), g.E, H) * f32(3)
         yield mk("gnnmp_edge_softmax_f32", f"{g.name}_H{H}", tags, [Pl(g), Arr("logits", "in", lg), Arr("alpha", "out", shape=(g.E, H)), H, STREAM],
                  lambda host, g=g, lg=lg: {"alpha": orc().softmax_edge_neighbors(g.t, g.n_dst, lg)})
@@ -1445,6 +1555,9 @@ def att_align(H, C, base=None):
 def att_shapes(ctx, loops):
     """(graph, H, C, tags): every head shape on the hub graph, two on the others (the edgeless graph only where the plan adds self loops
     or no statistics are written)"""
+    if hasattr(ctx, "att_shapes"):                       # a context with graphs of its own (GeomCtx)
+        yield from ctx.att_shapes(loops)
+        return
     for k, (H, C) in enumerate(ATT_HC):
         yield ctx.hub, H, C, ({"align"} if k < 4 else set()) | ({"side", "ws"} if k == 0 else set())
     for g in (ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300):
@@ -1672,7 +1785,8 @@ def _(ctx):
     # refuses graphs whose aggregate fits the Infinity Cache (the unfused pair is faster there); knob 14 forces the kernel, as
     # tests/test_fused_conv.py does
     al = {n: EUNSUPPORTED for n in ("xj", "xi", "out", "agg_out")}
-    shapes = [(ctx.hub, 100, 0, 100, {"align", "side", "ws"}), (ctx.hub, 128, 0, 128, {"align"}), (ctx.hub, 64, 64, 128, {"align"}), (ctx.hub, 4, 4, 8, {"align"}), (ctx.r31, 16, 0, 32, ()),
+    shapes = ctx.fused_shapes() if hasattr(ctx, "fused_shapes") else \
+             [(ctx.hub, 100, 0, 100, {"align", "side", "ws"}), (ctx.hub, 128, 0, 128, {"align"}), (ctx.hub, 64, 64, 128, {"align"}), (ctx.hub, 4, 4, 8, {"align"}), (ctx.r31, 16, 0, 32, ()),
               (ctx.r33, 100, 100, 64, ()), (ctx.r300, 64, 64, 128, ()), (ctx.r300, 100, 100, 128, ())]
     for k, (g, D, D1, Dout, tags) in enumerate(shapes):
         layout, scaled, act = k % 2, k % 2 == 0, k % 2

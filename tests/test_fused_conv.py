@@ -250,3 +250,34 @@ def test_gcn_layer_adjoint_through_the_fused_kernels(gm, oracle, Din, Dout):
         (y2 * dev(r)).sum().backward()
     close(xt.grad.cpu().numpy(), x2.grad.cpu().numpy(), 1e-5)
     close(y.detach().cpu().numpy(), y2.detach().cpu().numpy())
+
+
+@pytest.mark.parametrize("log2g", [3, 6])
+def test_a_forced_lane_group_is_refused_and_the_layer_falls_back(gm, oracle, log2g):
+    """fused_conv_kernel has no feature tiles: with FORCE_LOG2G below ceil(log2(D / 4)) the features beyond 4 G would never reach the
+    LDS tile the MFMA phase contracts over.  The export refuses any forced width other than its own (csrc/knobs.h, knob 1) before it
+    writes anything, and the layer takes propagate + dense."""
+    import torch
+    from gnnmp import _lib as L
+    rng = np.random.default_rng(41)
+    s, t, n = hub_graph(rng, n=1200, E=15000)
+    D = Dout = 100
+    x = rng.standard_normal((n, D)).astype(np.float32)
+    g = gm.GNNGraph(dev(s), dev(t), num_nodes=n)
+    l = gm.GCNConv((D, Dout), "relu", seed=5)
+    ref = oracle.gcn_conv(s, t, n, x, l.weight.cpu().numpy(), l.bias.cpu().numpy(), "relu")
+    close(l(g, dev(x)).cpu().numpy(), ref)                        # the fused kernel (module fixture: FUSED_WAVES = 16)
+    with gm.tuned(gm.Knob.FORCE_LOG2G, log2g):
+        close(l(g, dev(x)).cpu().numpy(), ref)                    # the same layer with the group forced
+        # the raw export: GNNMP_EUNSUPPORTED, and neither output touched
+        xd, W = dev(x), dev((rng.standard_normal((Dout, D)) * 0.2).astype(np.float32))
+        poison = float(np.frombuffer(np.uint32(0x7fc0beef).tobytes(), np.float32)[0])
+        out, agg = torch.full((n, Dout), poison, device="cuda"), torch.full((n, D), poison, device="cuda")
+        before_out, before_agg = out.view(torch.int32).clone(), agg.view(torch.int32).clone()
+        rc = L.load().gnnmp_fused_conv_f32(g.plan(False).handle, L.SUM, L.ptr(xd), None, None, None, None, None, D, None, 0, None, 0,
+                                           L.ptr(W), W.stride(0), 0, None, 0, L.ptr(out), Dout, L.ptr(agg), L.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == L.EUNSUPPORTED
+        assert torch.equal(out.view(torch.int32), before_out) and torch.equal(agg.view(torch.int32), before_agg)
+        assert gm.fused_conv(g.plan(False), L.SUM, xd, W) is None
+    assert gm.fused_conv(g.plan(False), L.SUM, xd, W) is not None      # the knob is back: the kernel takes the shape again
