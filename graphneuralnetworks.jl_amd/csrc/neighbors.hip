@@ -1,6 +1,7 @@
 // neighbors.hip — exact neighbour search on the device: the graph constructors
 //   knn_graph(points, k; graph_indicator, self_loops, dir)      GNNGraphs/src/generate.jl:112-145
 //   radius_graph(points, r; graph_indicator, self_loops, dir)   GNNGraphs/src/generate.jl:196-222
+//   hyperbolic_graph(points, R, zeta; ...)                      the N x N loop of rand_temporal_hyperbolic_graph, generate.jl:287-297, 359-369
 // The reference builds a KDTree / BallTree on the CPU (NearestNeighbors.jl).  Here: brute force in fp32, one kernel skeleton for both.
 //
 // Semantics (gnnmp.h states them for callers): d2(i, j) = fma chain over the dimensions in order, a non-finite d2 ranks as +inf,
@@ -18,6 +19,14 @@
 // best 64 keys strictly above the last key of the pass before.
 // radius_graph: the same distances; a count pass (ballot + popcount), an exclusive scan, and a write pass whose position inside a row
 // is the popcount of the lanes below — neighbours ascend in j by construction.  No atomics in any of the search kernels.
+// hyperbolic_graph: the radius skeleton with another pair value.  The reference's rule acosh(cosh a_i cosh a_j - sinh a_i sinh a_j cos(dtheta))
+// <= zeta R (a = zeta r) is, acosh being monotone, 2 v <= 2 cosh(zeta R) with
+//     2 v = (E_i F_j + F_i E_j) + S_i S_j h,   E = e^a, F = e^-a, S = sinh a, h = 4 sin^2(dtheta / 2) = (c_i - c_j)^2 + (s_i - s_j)^2,
+// two non-negative terms: nothing cancels.  A pre-pass computes per NODE, in double, E, F, S (rounded to fp32 once) and c = cos theta,
+// s = sin theta (kept in double: a float32 difference of two angles on either side of the 0 / 2 pi seam has lost the digits that matter;
+// the chord of two unit vectors has not) into scoped scratch, 32 bytes a node; a PAIR is then two double subtractions, a double
+// multiply and multiply-add, one conversion and five fp32 operations — no transcendental.  A lane reads its candidate's record and the wave's four
+// query records straight from that array (one record is everything a pair needs: there is no tile to transpose through LDS).
 // Output.  Edge e = (centre i, its r-th neighbour) of the reference's adjacency list -> COO conversion is destination-sorted as produced,
 // so the kernels write the graph's PLAN directly (row i = centre i, col = neighbour, eid[e] = e): what gnnmp_plan_from_csc would build
 // from (colptr, rowval), without the copy.  (s, t) in any index width and base come from gnnmp_plan_edge_index.
@@ -41,6 +50,16 @@ constexpr uint64_t NB_NONE = ~0ULL;     // "no candidate": above every real key 
 constexpr int NB_MAX_K = 1024;
 
 enum { NB_KNN = 0, NB_COUNT = 1, NB_WRITE = 2 };
+enum { NB_L2 = 0, NB_HYP = 1 };         // the pair value: squared Euclidean distance | 2 cosh(zeta d_hyperbolic)
+
+// what a pair needs of a node of the hyperbolic plane (r, theta): c, s = cos, sin theta in double; E, F, S = e^(zeta r), e^(-zeta r),
+// sinh(zeta r) computed in double and rounded to fp32 once; ok = 0 when r or theta is not finite
+struct HypNode {
+    double c, s;
+    float E, F, S;
+    int ok;
+};
+static_assert(sizeof(HypNode) == 32, "one node is 32 bytes");
 
 struct NbArgs {
     const float *x;           // [N][d]
@@ -55,6 +74,7 @@ struct NbArgs {
     const int64_t *rowptr;    // radius, write pass: first edge of every centre
     int64_t *deg;             // radius, count pass
     int32_t *col, *eid;       // the plan's slots: slot e = edge e (row = centre, col = neighbour)
+    const HypNode *hyp;       // hyperbolic: the per-node records [N] (x is not read by the search then)
 };
 
 // lane r <- lane r - 1 over the whole wave (DPP wave_shr:1; lane 0 keeps its own value, the caller ignores it)
@@ -76,7 +96,32 @@ __device__ __forceinline__ void store_edge(const NbArgs &a, int64_t e, int64_t n
     a.eid[e] = (int32_t)(uint32_t)e;
 }
 
-template <int MODE>
+// the hyperbolic pre-pass: one record a node.  zeta * r is exact in double (two fp32 factors); exp / sinh / sincos in double are
+// within 2 ulp of double, so E, F, S carry the one fp32 rounding and c, s about 2^-52.
+__global__ void hyp_nodes_kernel(const float *points, int64_t N, double zeta, HypNode *out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float r = points[2 * i], th = points[2 * i + 1];
+    const double ar = zeta * (double)r;
+    HypNode n;
+    sincos((double)th, &n.s, &n.c);
+    n.E = (float)exp(ar);
+    n.F = (float)exp(-ar);
+    n.S = (float)sinh(ar);
+    n.ok = (r - r == 0.0f && th - th == 0.0f) ? 1 : 0;
+    out[i] = n;
+}
+
+// 2 v(q, c) for two DISTINCT nodes (see the head of the file); equal radii (E equal in fp32: cosh(zeta dr) - 1 < 2^-46) give the
+// first term as the exact 2, so that coincident points have v = 1 <= cosh(zeta R) at every R >= 0
+__device__ __forceinline__ float hyp_pair(const HypNode &q, const HypNode &c) {
+    const double dc = q.c - c.c, ds = q.s - c.s;
+    const float h = (float)__builtin_fma(ds, ds, dc * dc);
+    const float t = q.E == c.E ? 2.0f : __builtin_fmaf(q.F, c.E, q.E * c.F);
+    return t + (q.S * c.S) * h;
+}
+
+template <int MODE, int METRIC = NB_L2>
 __global__ void __launch_bounds__(256) neighbors_kernel(const NbArgs a) {
     __shared__ float cand[NB_TILE * NB_LD];
     __shared__ float4 qs[NB_WAVES][NB_DCH];
@@ -109,6 +154,11 @@ __global__ void __launch_bounds__(256) neighbors_kernel(const NbArgs a) {
             }
         }
     }
+    HypNode hq[NB_QW];                          // hyperbolic: the wave's queries (wave-uniform)
+    if (METRIC == NB_HYP) {
+#pragma unroll
+        for (int q = 0; q < NB_QW; ++q) hq[q] = a.hyp[live[q] ? qi[q] : qb0];
+    }
     const bool mask_ids = a.gi && !a.seg_ptr;   // unsorted indicator: full range, other graphs masked
     const int n_pass = MODE == NB_KNN ? (a.k + 63) / 64 : 1;
     const bool one_chunk = d <= NB_DCH;
@@ -130,7 +180,16 @@ __global__ void __launch_bounds__(256) neighbors_kernel(const NbArgs a) {
             float acc[NB_QW];
 #pragma unroll
             for (int q = 0; q < NB_QW; ++q) acc[q] = 0.0f;
-            for (int ch0 = 0; ch0 < d; ch0 += NB_DCH) {
+            if (METRIC == NB_HYP) {
+                const int64_t jc = tile0 + lane;
+                const HypNode cn = a.hyp[jc < bhi ? jc : blo];      // (past the range: any record, the lane is masked below)
+#pragma unroll
+                for (int q = 0; q < NB_QW; ++q) {
+                    const bool fin = hq[q].ok && cn.ok;
+                    acc[q] = !fin ? __builtin_nanf("") : (jc == qi[q] ? 2.0f : hyp_pair(hq[q], cn));   // (a node to itself: v = 1)
+                }
+            }
+            for (int ch0 = 0; METRIC == NB_L2 && ch0 < d; ch0 += NB_DCH) {
                 const int cw = min(NB_DCH, d - ch0);
                 __syncthreads();                // the readers of the chunk before are done
                 for (int idx = tid; idx < NB_TILE * cw; idx += 256) {
@@ -183,7 +242,8 @@ __global__ void __launch_bounds__(256) neighbors_kernel(const NbArgs a) {
                         }
                     }
                 } else {
-                    const uint64_t m = __ballot(ok && dd <= a.r2);
+                    // (hyperbolic: a value that is not finite is no edge even when cosh(zeta R) itself overflowed to +inf)
+                    const uint64_t m = __ballot(ok && dd <= a.r2 && (METRIC == NB_L2 || dd < __builtin_inff()));
                     if (MODE == NB_WRITE) {
                         if ((m >> lane) & 1ULL) {
                             const int64_t e = a.rowptr[qi[q]] + cnt[q] + __popcll(m & ((1ULL << lane) - 1ULL));
@@ -309,6 +369,7 @@ NbArgs make_args(const float *points, int64_t N, int64_t d, const void *gi, int 
     a.deg = nullptr;
     a.col = p->col;
     a.eid = p->eid;
+    a.hyp = nullptr;
     return a;
 }
 
@@ -325,6 +386,47 @@ int alloc_plan_slots(gnnmp_graph_t *p, int64_t E) {
     GNNMP_HIP(alloc_into(p->col, epad));
     GNNMP_HIP(alloc_into(p->eid, epad));
     p->bytes = (int64_t)(sizeof(int32_t) * ((size_t)(p->n_dst + 1) + 2 * epad));
+    return GNNMP_OK;
+}
+
+// Every pair whose value is at most `thr`, as a plan: the count pass, the scan (its total is read on the host: it sizes the plan) and the
+// write pass, for either pair value.  The arguments have been checked.  hyp: the per-node records of the hyperbolic value (else nullptr).
+template <int METRIC>
+int threshold_graph(const char *who, gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float thr, const HypNode *hyp,
+                    const void *graph_indicator, int idx_bytes, int index_base, int64_t n_graphs, int self_loops, hipStream_t stream) {
+    PlanPtr p(new gnnmp_graph_t());
+    // (rowptr64 dies when the call returns: after plan_build_long_rows' synchronisation, or its hipFree waits itself)
+    DevBuf<int64_t> rowptr64, seg;
+    if (graph_indicator && N > 0)
+        GNNMP_TRY(prepare_indicator(who, graph_indicator, idx_bytes, index_base, N, n_graphs, 0, stream, seg));
+    GNNMP_TRY(alloc_plan_rows(p.get(), N));
+    GNNMP_HIP(rowptr64.alloc((size_t)(N + 1)));
+    NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg.get(), self_loops, p.get());
+    a.r2 = thr;
+    a.hyp = hyp;
+    GNNMP_HIP(hipMemsetAsync(rowptr64.get() + N, 0, sizeof(int64_t), stream));
+    if (N > 0) {
+        a.deg = rowptr64.get();
+        neighbors_kernel<NB_COUNT, METRIC><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
+        GNNMP_HIP(hipGetLastError());
+    }
+    GNNMP_TRY(exclusive_scan_i64(rowptr64.get(), rowptr64.get(), (size_t)(N + 1), stream));
+    int64_t tot = 0;
+    GNNMP_HIP(hipMemcpyAsync(&tot, rowptr64.get() + N, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    GNNMP_HIP(hipStreamSynchronize(stream));
+    if (tot >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "%s: %lld edges exceed the plan format", who, (long long)tot);
+    GNNMP_TRY(alloc_plan_slots(p.get(), tot));
+    narrow_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(rowptr64.get(), p->rowptr, N);
+    GNNMP_HIP(hipGetLastError());
+    if (tot > 0) {
+        a.col = p->col;
+        a.eid = p->eid;
+        a.rowptr = rowptr64.get();
+        neighbors_kernel<NB_WRITE, METRIC><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
+        GNNMP_HIP(hipGetLastError());
+    }
+    GNNMP_TRY(plan_build_long_rows(p.get(), stream));
+    *out = p.release();
     return GNNMP_OK;
 }
 
@@ -365,43 +467,29 @@ int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int
 
 int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float r, const void *graph_indicator,
                            int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     GNNMP_TRY(check_common("radius_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs));
     if (!(r >= 0.0f)) return fail(GNNMP_EINVAL, "radius_graph: r = %g (negative or NaN)", (double)r);
-    const float r2 = r * r;
-    PlanPtr p(new gnnmp_graph_t());
-    // (rowptr64 dies when the call returns: after plan_build_long_rows' synchronisation, or its hipFree waits itself)
-    DevBuf<int64_t> rowptr64, seg;
-    if (graph_indicator && N > 0)
-        GNNMP_TRY(prepare_indicator("radius_graph", graph_indicator, idx_bytes, index_base, N, n_graphs, 0, stream, seg));
-    GNNMP_TRY(alloc_plan_rows(p.get(), N));
-    GNNMP_HIP(rowptr64.alloc((size_t)(N + 1)));
-    NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg.get(), self_loops, p.get());
-    a.r2 = r2;
-    GNNMP_HIP(hipMemsetAsync(rowptr64.get() + N, 0, sizeof(int64_t), stream));
+    return threshold_graph<NB_L2>("radius_graph", out, points, N, d, r * r, nullptr, graph_indicator, idx_bytes, index_base, n_graphs,
+                                  self_loops, (hipStream_t)stream_);
+}
+
+int gnnmp_hyperbolic_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, float R, float zeta, const void *graph_indicator,
+                               int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GNNMP_TRY(check_common("hyperbolic_graph", out, points, N, 2, graph_indicator, idx_bytes, index_base, n_graphs));
+    if (!(R >= 0.0f)) return fail(GNNMP_EINVAL, "hyperbolic_graph: R = %g (negative or NaN)", (double)R);
+    if (!(zeta > 0.0f) || !std::isfinite(zeta)) return fail(GNNMP_EINVAL, "hyperbolic_graph: zeta = %g (not finite, or <= 0)", (double)zeta);
+    // 2 cosh(zeta R), formed in double and rounded once (+inf above zeta R = 88.7: every pair with a finite value is then an edge)
+    const float thr = (float)(2.0 * std::cosh((double)zeta * (double)R));
+    // (dies when the call returns: after plan_build_long_rows' synchronisation, or its hipFree waits itself)
+    DevBuf<HypNode> nodes;
+    GNNMP_HIP(nodes.alloc((size_t)std::max<int64_t>(N, 1)));
     if (N > 0) {
-        a.deg = rowptr64.get();
-        neighbors_kernel<NB_COUNT><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
+        hyp_nodes_kernel<<<nblk(N), 256, 0, stream>>>(points, N, (double)zeta, nodes.get());
         GNNMP_HIP(hipGetLastError());
     }
-    GNNMP_TRY(exclusive_scan_i64(rowptr64.get(), rowptr64.get(), (size_t)(N + 1), stream));
-    int64_t tot = 0;
-    GNNMP_HIP(hipMemcpyAsync(&tot, rowptr64.get() + N, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    GNNMP_HIP(hipStreamSynchronize(stream));
-    if (tot >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "radius_graph: %lld edges exceed the plan format", (long long)tot);
-    GNNMP_TRY(alloc_plan_slots(p.get(), tot));
-    narrow_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(rowptr64.get(), p->rowptr, N);
-    GNNMP_HIP(hipGetLastError());
-    if (tot > 0) {
-        a.col = p->col;
-        a.eid = p->eid;
-        a.rowptr = rowptr64.get();
-        neighbors_kernel<NB_WRITE><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
-        GNNMP_HIP(hipGetLastError());
-    }
-    GNNMP_TRY(plan_build_long_rows(p.get(), stream));
-    *out = p.release();
-    return GNNMP_OK;
+    return threshold_graph<NB_HYP>("hyperbolic_graph", out, points, N, 2, thr, nodes.get(), graph_indicator, idx_bytes, index_base,
+                                   n_graphs, self_loops, stream);
 }
 
 }  // extern "C"

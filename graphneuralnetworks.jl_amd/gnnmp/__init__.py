@@ -27,6 +27,7 @@ from .backward_evolve import evolve_gcno_ad, outer_accum  # noqa: F401
 from .linkpred import (DotDecoder, WithGraph, dot_decoder, dot_decoder_ad, edge_dot_ad, edge_dot_grad,  # noqa: F401
                        negative_sample, rand_edge_split)
 from .neighbors import knn_graph, radius_graph  # noqa: F401
+from .generate import hyperbolic_graph, rand_temporal_hyperbolic_graph, rand_temporal_radius_graph  # noqa: F401
 from .transform import (EdgeCoalescing, add_edges, add_nodes, coalesce_edges, has_isolated_nodes, has_multi_edges,  # noqa: F401
                         perturb_edges, random_walk_pe, remove_edges, remove_multi_edges, remove_nodes, remove_self_loops,
                         to_bidirected, to_unidirected)

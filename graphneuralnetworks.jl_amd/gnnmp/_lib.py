@@ -52,7 +52,7 @@ SYMBOLS = (
     "gnnmp_propagate_f64", "gnnmp_gather_f64", "gnnmp_scatter_f64",
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
-    "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32",
+    "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32", "gnnmp_hyperbolic_graph_f32",
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32",
@@ -454,6 +454,7 @@ def load():
         "gnnmp_edge_dot_grad_f32": [vp, vp, vp, vp, vp, vp, vp, i64, vp],
         "gnnmp_knn_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, i64, vp, i, i, i64, i, vp],
         "gnnmp_radius_graph_f32": [ctypes.POINTER(vp), vp, i64, i64, f, vp, i, i, i64, i, vp],
+        "gnnmp_hyperbolic_graph_f32": [ctypes.POINTER(vp), vp, i64, f, f, vp, i, i, i64, i, vp],
         "gnnmp_hetero_propagate_f32": [ctypes.POINTER(HeteroDst), i, i64, vp],
         "gnnmp_hetero_propagate_grad_f32": [ctypes.POINTER(HeteroSrc), i, i64, vp],
         "gnnmp_coalesce_edges": [ctypes.POINTER(CoalesceJob), ctypes.POINTER(i64), vp],

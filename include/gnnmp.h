@@ -1181,7 +1181,37 @@ int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_transposed,
  * checked before any HIP call.  Workspace: the segment table, the scan's scratch and int64[N + 1]; no N x N or N x tile array exists
  * in memory.  No atomics in the search kernels (the graph sizes of an UNSORTED indicator are counted with integer adds).
  * N < 2^31 - 1, d <= 2^20, edges < GNNMP_MAX_SLOTS.
+ *
+ *   gnnmp_hyperbolic_graph_f32  the radius search in the hyperbolic plane: the N x N loop of rand_temporal_hyperbolic_graph
+ *                           (generate.jl:287-297, 359-369).  points: [N][2] = (r, theta), r >= 0, any real theta (no wrap is needed or
+ *                           done).  j is a neighbour of i iff the hyperbolic distance at curvature parameter zeta is at most R:
+ *                           acosh(cosh zeta r_i cosh zeta r_j - sinh zeta r_i sinh zeta r_j cos(theta_i - theta_j)) / zeta <= R, evaluated
+ *                           as v(i, j) <= cosh(zeta R) (acosh is monotone) in the cancellation-free form
+ *                               v = cosh(zeta (r_i - r_j)) + 2 sinh zeta r_i sinh zeta r_j sin^2((theta_i - theta_j) / 2)
+ *                                 = ((E_i F_j + F_i E_j) + S_i S_j h) / 2,   E = e^(zeta r), F = e^(-zeta r), S = sinh(zeta r),
+ *                                   h = (cos theta_i - cos theta_j)^2 + (sin theta_i - sin theta_j)^2.
+ *                           E, F, S are computed per node in double and rounded to fp32 once; cos theta and sin theta stay in double
+ *                           and h is rounded to fp32 once (an fp32 difference of two angles across the 0 / 2 pi seam would have lost
+ *                           the digits that count); the rest is fp32: t = fmaf(F_i, E_j, E_i F_j) (t = 2 exactly when E_i == E_j),
+ *                           2 v = t + (S_i S_j) h, compared with fl32(2 cosh(zeta R)) formed in double.  No transcendental per pair.
+ *                           Error, with u = 2^-24, against the exact v of the fp32 inputs (points, R, zeta as passed):
+ *                               |v_dev - v| <= 6 u v + S_i S_j 2^-50 sqrt(h),   and the threshold carries one more u:
+ *                           the answer is the exact one for every pair with |v - cosh(zeta R)| > 8 u cosh(zeta R), the second term being
+ *                           below u v when sqrt(h) >= 2^-25 or zeta (r_i + r_j) <= 36 (S_i S_j <= e^36 / 4).  tests/temporal_gen_ref.py
+ *                           holds the same bound as B = 8.
+ *                           self_loops != 0: every node with finite (r, theta) gets its loop (v = 1 by definition, not computed);
+ *                           == 0: j == i is skipped by index.  Distinct nodes at identical coordinates are joined (v = 1 exactly).
+ *                           A pair whose value is not finite is no edge: a node with NaN or infinite r or theta has none; every value
+ *                           is finite while zeta r <= 44 for all nodes; above, a pair with zeta (r_i + r_j) > 88 may overflow, and a
+ *                           node with zeta r > 88.7 (E = +inf) has no edge but its loop.  A negative r evaluates the same formula, with
+ *                           cancellation (the bound above does not hold).  R < 0 or NaN, zeta <= 0 or not finite: GNNMP_EINVAL, as is
+ *                           everything gnnmp_radius_graph_f32 refuses; zeta R > 88.7 makes the threshold +inf (every finite pair).
+ *                           Shape, order, indicator handling and synchronisations are gnnmp_radius_graph_f32's: a count pass, the scan
+ *                           (total read on the host), a write pass; centres ascend, the neighbours of a centre ascend in j; no atomics,
+ *                           reruns are bit-identical.  One launch more (the per-node pre-pass) and 32 N bytes more workspace.
  * ---------------------------------------------------------------------------------------------- */
+int gnnmp_hyperbolic_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, float R, float zeta, const void *graph_indicator,
+                               int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
 int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, int64_t k, const void *graph_indicator,
                         int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream);
 int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float r, const void *graph_indicator,
