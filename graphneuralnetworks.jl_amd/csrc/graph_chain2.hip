@@ -769,8 +769,13 @@ extern "C" int gnnmp_chain_jobs_create(gnnmp_chain_jobs_t **out, const int64_t *
     std::unique_ptr<gnnmp_chain_jobs> J(new gnnmp_chain_jobs());   // (the handle dies on every exit that does not release() it)
     J->G = G;
     J->N = G > 0 ? sp[(size_t)G] - sp[0] : 0;
-    for (int64_t g = 0; g < G; ++g) J->max_graph = std::max(J->max_graph, sp[(size_t)g + 1] - sp[(size_t)g]);
-    if (J->max_graph > 64 || J->N >= ((int64_t)1 << 31) || G == 0) {   // no jobs: the caller's chain runs on the general kernel
+    for (int64_t g = 0; g < G; ++g) {
+        J->max_graph = std::max(J->max_graph, sp[(size_t)g + 1] - sp[(size_t)g]);
+        if (sp[(size_t)g + 1] == sp[(size_t)g]) J->has_empty = 1;
+    }
+    // no jobs: the caller's chain runs on the general kernel.  (A batch with an empty member used to be packed all the same — a table
+    // the chain then declined: gnnmp.h promises a handle without jobs, as gnnmp_chain_jobs_pack gives.)
+    if (J->max_graph > 64 || J->has_empty || J->N >= ((int64_t)1 << 31) || G == 0) {
         *out = J.release();
         return GNNMP_OK;
     }
@@ -927,8 +932,9 @@ extern "C" int gnnmp_chain_jobs_pack(gnnmp_chain_jobs_t **out, const int64_t *se
     return GNNMP_OK;
 }
 
-/* the job table as the chain kernel sees it: tab_out[cap_rows][64] int32 (device), hdr_out[8] int32 (device; host-packed handles: [0] = jobs,
- * rest 0).  Tests and debugging: asynchronous copies on `stream`. */
+/* the job table as the chain kernel sees it: tab_out[cap_rows][64] int32 (device; the rows past the handle's own table are filled with -1:
+ * every row the caller sized is written), hdr_out[32] int32 (device; host-packed handles: [0] = jobs, [3] = the largest member, [4] =
+ * has_empty, rest 0).  Tests and debugging: asynchronous copies on `stream`. */
 extern "C" int gnnmp_chain_jobs_export(const gnnmp_chain_jobs_t *J, int32_t *tab_out, int64_t cap_rows, int32_t *hdr_out,
                                        gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -936,6 +942,8 @@ extern "C" int gnnmp_chain_jobs_export(const gnnmp_chain_jobs_t *J, int32_t *tab
     const int64_t rows = std::min<int64_t>(cap_rows, J->njobs_cap);
     if (tab_out && rows > 0)
         GNNMP_HIP(hipMemcpyAsync(tab_out, J->tab, sizeof(int32_t) * PACK_ROWS * (size_t)rows, hipMemcpyDeviceToDevice, stream));
+    if (tab_out && cap_rows > rows)      // (a handle without jobs has no table at all: njobs_cap = 0, every row is filled here)
+        GNNMP_HIP(hipMemsetAsync(tab_out + (int64_t)PACK_ROWS * rows, 0xff, sizeof(int32_t) * PACK_ROWS * (size_t)(cap_rows - rows), stream));
     if (hdr_out) {
         if (J->hdr) {
             GNNMP_HIP(hipMemcpyAsync(hdr_out, J->hdr, sizeof(int32_t) * 32, hipMemcpyDeviceToDevice, stream));

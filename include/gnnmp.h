@@ -29,8 +29,9 @@
  *     the calls whose comment says that they synchronise (plan builds and the other graph prep: gnnmp_batch_coo,
  *     gnnmp_sort_edge_index, gnnmp_unique_append, gnnmp_induced_subgraph, gnnmp_sample_neighbors, gnnmp_rand_edge_split,
  *     gnnmp_negative_sample, gnnmp_coalesce_edges, gnnmp_compact_edges, the host-result queries) and the arena.  What is TESTED (tests/test_abi_graph_capture.py, capture mode
- *     thread_local): every other export of the case table of tests/abi_cases.py, gnnmp_graphconv_chain_f32 through the Python
- *     mirror, gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
+ *     thread_local): every other export of the case table of tests/abi_cases.py — gnnmp_graphconv_chain_f32 among them, on both
+ *     of its kernels and with host- and device-packed job handles, and once more through the Python mirror —
+ *     gnnmp_hetero_propagate_f32 (tests/test_hetero.py) and gnnmp_hetero_propagate_grad_f32 (tests/test_hetero_backward.py) — those
  *     two without the eager call, they use no plan scratch — and gnnmp_edge_conv_f32 / gnnmp_edge_conv_grad_f32 (tests/test_edge_conv_ad.py)
  *     and gnnmp_cg_conv_grad_f32 (tests/test_cg_conv_ad.py) and gnnmp_nn_conv_grad_f32 (tests/test_nn_conv_ad.py) and gnnmp_egnn_edge_f32 /
  *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
@@ -940,7 +941,12 @@ int gnnmp_allgather_f32(void *nccl_comm, const float *send, float *recv, int64_t
  * live in `scratch` (L2-resident, never read by another workgroup), the last layer is folded straight into per-row head outputs,
  * and only the (G, nout) result is written for the caller.  Contractions run on the split-bf16 MFMA core (fp32-class accuracy).
  *   plan      : plan of the batched graph's (s, t) WITHOUT self loops
- *   seg_ptr   : DEVICE int64 [G + 1], seg_ptr[k] = first node of member graph k (gnnmp_segment_bounds)
+ *   seg_ptr   : DEVICE int64 [G + 1], seg_ptr[k] = first node of member graph k (gnnmp_segment_bounds); a member graph may be
+ *               empty (seg_ptr[k] == seg_ptr[k + 1]): its row of `out` is b_head (zero without one)
+ *   x         : DEVICE [N][d0], 16-byte aligned (both kernels read its rows with 16-byte loads): an x that is not is refused
+ *               with GNNMP_EUNSUPPORTED and nothing is written; so is an under-aligned `scratch` whenever the call uses it (the
+ *               wave-pair kernel below does not).  Every other array of the call (the weights, the biases, seg_ptr, out) may start
+ *               at any multiple of its element size
  *   dims      : HOST int64 [n_layers + 1] = d0 .. dL;  W_root / W_agg / bias : HOST arrays of n_layers DEVICE pointers
  *               (weight1 / weight2; bias entries may be NULL, `bias` itself may be NULL);  act : HOST int [n_layers] (gnnmp_act:
  *               IDENTITY | RELU)
@@ -964,7 +970,7 @@ int64_t gnnmp_graphconv_chain_scratch_floats(int64_t N, int n_layers, const int6
  * exact fp32 path (non-finite operands), so — like a plan's workspace — it serves ONE stream at a time.  The list's counter is re-armed on
  * the device by the call's own last launch: nothing about it is chosen on the host, and a recorded call may be replayed back to back.
  * Built once per batched graph from the DEVICE seg_ptr; synchronises `stream` (graph prep).  A batch with a member graph of more than
- * 64 nodes, or without any, yields a handle without jobs: the chain then runs on the general kernel.  info[0] = jobs, [1] = member
+ * 64 nodes or of none (an empty member), or without any member, yields a handle without jobs: the chain then runs on the general kernel.  info[0] = jobs, [1] = member
  * graphs, [2] = rows, [3] = largest member graph, [4] = per-mille of the MFMA tiles' rows that are real rows. */
 typedef struct gnnmp_chain_jobs gnnmp_chain_jobs_t;
 int gnnmp_chain_jobs_create(gnnmp_chain_jobs_t **out, const int64_t *seg_ptr, int64_t G, gnnmp_stream_t stream);
@@ -979,9 +985,13 @@ int gnnmp_chain_jobs_info(const gnnmp_chain_jobs_t *jobs, int64_t *info);
  * synchronises the device.  A jobs handle serves ONE stream at a time and one host thread at a time (its z rows and set-aside list are
  * scratch of the running call).
  *   gnnmp_chain_jobs_release  stream-ordered destroy (see gnnmp_plan_release)
- *   gnnmp_chain_jobs_export   the job table as the kernel reads it: tab_out[cap_rows][64] int32 (global row of each slot, -1 = empty),
+ *   gnnmp_chain_jobs_export   the job table as the kernel reads it: tab_out[cap_rows][64] int32 (global row of each slot, -1 = empty;
+ *                             all cap_rows rows are written: a row at or above the job count holds -1 in every slot),
  *                             hdr_out[32] int32 ([0] jobs [1] 32-row tiles [2] poisoned [3] largest member seen [4] empty members,
- *                             [16..29] seven 64-bit phase stamps of the packing kernel, 100 MHz): tests and tools */
+ *                             [16..29] seven 64-bit phase stamps of the packing kernel, 100 MHz; a handle packed on the host
+ *                             (gnnmp_chain_jobs_create) gives [0] jobs, [3] the largest member, [4] 1 if some member is empty, and 0
+ *                             in every other word, and the call then synchronises `stream`): tests and tools.  Either output may
+ *                             be NULL */
 int gnnmp_chain_jobs_pack(gnnmp_chain_jobs_t **out, const int64_t *seg_ptr, int64_t G, int64_t n_rows, int64_t max_graph, int has_empty,
                           gnnmp_stream_t stream);
 int gnnmp_chain_jobs_release(gnnmp_chain_jobs_t *jobs, gnnmp_stream_t stream);

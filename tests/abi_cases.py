@@ -2,7 +2,10 @@
 case table over the C ABI (one builder per export: its arguments at a given shape, the role of every array, the float64 / exact reference).
 
 Everything here calls libgnnmp.so through ctypes with raw pointers INTO the slab — never through the Python wrappers, which allocate
-their own outputs.  Plans (opaque, library-owned) are the only objects created outside the slab."""
+their own outputs.  Plans and the chain's job handles (opaque, library-owned) are the only objects created outside the slab.
+
+TABLE holds the exports that only launch on their stream (and the graph prep the capture test quotes as exempt); PREP_TABLE the plan
+writers and gnnmp_chain_jobs_export, which synchronise: the same cases and the same slab, never recorded into a HIP graph."""
 import ctypes
 import os
 import re
@@ -25,6 +28,8 @@ RTOL64 = 1e-12          # the same for the Float64 entry points (tests/test_floa
 HANDLE_TYPES = ("gnnmp_graph_t", "gnnmp_arena_t", "gnnmp_chain_jobs_t")
 # pointer parameters the header documents as HOST memory (results of calls that synchronise, host tables of device pointers)
 HOST_PARAMS = {"result", "result_host", "total", "n_new", "cls", "info", "ptr"}
+# const HOST arrays of scalars, per export (the header: "dims : HOST int64 [n_layers + 1]", "act : HOST int [n_layers]")
+HOST_ARRAYS = {"gnnmp_graphconv_chain_f32": ("dims", "act")}
 
 
 RECORD_TYPE = re.compile(r"\bgnnmp_\w+_t\b")
@@ -411,13 +416,80 @@ class Rec:
         rec.ctype, rec.fields = ctype, fields
 
 
+class PtrTab:
+    """a HOST table of device pointers (`const float *const *W_root`): a list of Arr | None, one pointer into the slab per entry, a None
+    entry stays NULL.  The arrays belong to the slab like any other argument's"""
+
+    def __init__(self, items):
+        self.items = list(items)
+        assert all(a is None or isinstance(a, Arr) for a in self.items)
+
+
+class HostArr:
+    """a plain HOST array of scalars (`const int64_t *dims`, `const int *act`): a ctypes array made at bind time"""
+
+    def __init__(self, ctype, values):
+        self.ctype, self.values = ctype, tuple(int(v) for v in values)
+
+    def __eq__(self, other):
+        return isinstance(other, HostArr) and (self.ctype, self.values) == (other.ctype, other.values)
+
+    def __repr__(self):
+        return f"HostArr({self.ctype.__name__}, {self.values})"
+
+
+class Jobs:
+    """a `gnnmp_chain_jobs_t *` argument.  mode 'none': NULL; 'host': gnnmp_chain_jobs_create; 'device': gnnmp_chain_jobs_pack with the
+    announcement (rows, largest member, some member empty) computed here from seg_ptr, as a caller computes it from its host integers.
+    The handle is built from a private device copy of seg_ptr (the call's own seg_ptr lives in the slab and may be shifted) and is
+    owned by the Plans object: one handle per (mode, seg_ptr) serves every call of a test, then dies with the plans"""
+
+    def __init__(self, mode, seg_ptr=None):
+        assert mode in ("none", "host", "device") and (mode == "none" or seg_ptr is not None)
+        self.mode = mode
+        self.seg = None if seg_ptr is None else np.ascontiguousarray(seg_ptr, np.int64)
+
+    def announcement(self):
+        sizes = np.diff(self.seg)
+        return int(self.seg[-1] - self.seg[0]), int(sizes.max()) if sizes.size else 0, int((sizes == 0).any())
+
+    def key(self):
+        return ("jobs", self.mode, None if self.seg is None else self.seg.tobytes())
+
+    def __eq__(self, other):
+        return isinstance(other, Jobs) and self.key() == other.key()
+
+    def __repr__(self):
+        return f"Jobs({self.mode!r}, G = {0 if self.seg is None else len(self.seg) - 1})"
+
+
+class PlanTab:
+    """a HOST table of plan handles (`const gnnmp_graph_t *const *members`): a list of Pl"""
+
+    def __init__(self, plans):
+        self.plans = list(plans)
+        assert all(isinstance(p, Pl) for p in self.plans)
+
+
+class NewPlan:
+    """`gnnmp_graph_t **out`: a plan the CALL creates.  Its handle is a host result of the call (host[name]) and belongs to the Plans
+    object from then on, which destroys it with the others"""
+
+    def __init__(self, name="plan"):
+        self.name = name
+
+
 def flat_args(args):
-    """the leaves of an argument list in order, records and nested tables opened"""
+    """the leaves of an argument list in order, records, nested tables and host tables of pointers / plans opened"""
     for a in args:
         if isinstance(a, Rec):
             yield from flat_args(a.fields.values())
         elif isinstance(a, (list, tuple)) and a and all(isinstance(r, Rec) for r in a):
             yield from flat_args(a)
+        elif isinstance(a, PtrTab):
+            yield from a.items
+        elif isinstance(a, PlanTab):
+            yield from a.plans
         else:
             yield a
 
@@ -481,6 +553,7 @@ class Plans:
 
     def __init__(self, lib, stream=None):
         self.lib, self.live, self.stream = lib, {}, stream
+        self.live_jobs, self.created = {}, []      # jobs handles by (mode, seg_ptr); plans that calls of the test created
 
     def get(self, p):
         import torch
@@ -502,10 +575,37 @@ class Plans:
         self.live[key] = (h, sd, td)
         return h
 
+    def jobs(self, j):
+        """the handle of a Jobs argument (None for mode 'none'): made once per (mode, seg_ptr) from a private device copy of seg_ptr"""
+        import torch
+        if j.mode == "none":
+            return None
+        key = j.key()
+        if key not in self.live_jobs:
+            sd = torch.from_numpy(j.seg.copy()).cuda()
+            h, G = ctypes.c_void_p(), len(j.seg) - 1
+            if j.mode == "host":
+                rc = self.lib.gnnmp_chain_jobs_create(ctypes.byref(h), ctypes.c_void_p(sd.data_ptr()), G, self.stream)
+            else:
+                rc = self.lib.gnnmp_chain_jobs_pack(ctypes.byref(h), ctypes.c_void_p(sd.data_ptr()), G, *j.announcement(), self.stream)
+            assert rc == OK, self.lib.gnnmp_last_error()
+            torch.cuda.synchronize()               # (the device packing is asynchronous: the call under test may run on another stream)
+            self.live_jobs[key] = (h, sd)
+        return self.live_jobs[key][0]
+
+    def adopt(self, h):
+        """a plan handle a call of the test will create (a ctypes.c_void_p the call fills in): destroyed with the others"""
+        self.created.append(h)
+
     def close(self):
         for h, _, _ in self.live.values():
             self.lib.gnnmp_plan_destroy(h)
-        self.live = {}
+        for h in self.created:
+            if h.value:
+                self.lib.gnnmp_plan_destroy(h)
+        for h, _ in self.live_jobs.values():
+            self.lib.gnnmp_chain_jobs_destroy(h)
+        self.live, self.live_jobs, self.created = {}, {}, []
 
 
 def plan_threshold(lib, n_edges):
@@ -524,11 +624,14 @@ def plan_threshold(lib, n_edges):
 # a case and its run
 # ------------------------------------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None, no_warmup=False):
+    def __init__(self, export, sid, args, ref, guard=GUARD_MIN, status=OK, align_status=None, knobs=None, no_warmup=False, then=None):
         self.export, self.sid, self.args, self.ref, self.guard, self.status = export, sid, args, ref, guard, status
         self.knobs = knobs or {}                   # gnnmp_tune settings for the call (the previous values come back after it)
         self.align_status = align_status or {}     # {array name: status the header documents for an under-aligned pointer}
-        leaves = list(flat_args(args))
+        # then: (export, args) of a SECOND library call, made after the first returned OK, whose arrays belong to the same slab and whose
+        # outputs the reference states too — gnnmp_plan_export of the plan the call created (args name it: Made(name))
+        self.then = then
+        leaves = list(flat_args(args)) + (list(flat_args(then[1])) if then else [])
         self.arrs = []                             # the arrays the slab holds: every Arr of the call, records opened; a view counts as its base
         for a in leaves:
             if isinstance(a, Arr):
@@ -539,11 +642,38 @@ class Case:
         self.no_warmup = no_warmup                 # the header: "may be recorded into a HIP graph without an eager call first"
 
 
+class Made:
+    """in the arguments of a case's second call (Case.then): the plan the first call created through NewPlan(name)"""
+
+    def __init__(self, name="plan"):
+        self.name = name
+
+
 def bind(case, slab, plans, stream=None):
     """the ctypes arguments of one call: pointers into the slab, plan handles, the stream.  Returns (arguments, host results)"""
-    host, cargs = {}, []
-    for a in case.args:
-        if isinstance(a, Arr):
+    return bind_args(case.args, slab, plans, stream, {})
+
+
+def bind_args(args, slab, plans, stream, host):
+    cargs = []
+    for a in args:
+        if isinstance(a, PtrTab):
+            tab = (ctypes.c_void_p * max(len(a.items), 1))(*[None if v is None else slab.ptr_of(v).value for v in a.items])
+            cargs.append(tab)
+        elif isinstance(a, HostArr):
+            cargs.append((a.ctype * max(len(a.values), 1))(*a.values))
+        elif isinstance(a, Jobs):
+            cargs.append(plans.jobs(a))
+        elif isinstance(a, PlanTab):
+            cargs.append((ctypes.c_void_p * max(len(a.plans), 1))(*[plans.get(p).value for p in a.plans]))
+        elif isinstance(a, NewPlan):
+            h = ctypes.c_void_p()
+            host[a.name] = h
+            plans.adopt(h)
+            cargs.append(ctypes.byref(h))
+        elif isinstance(a, Made):
+            cargs.append(host[a.name])
+        elif isinstance(a, Arr):
             cargs.append(slab.ptr_of(a))
         elif isinstance(a, Rec) or (isinstance(a, (list, tuple)) and a and isinstance(a[0], Rec)):
             keep = []                  # the structures live as long as the argument does: byref keeps `obj`, obj keeps the rest
@@ -562,7 +692,7 @@ def bind(case, slab, plans, stream=None):
         elif isinstance(a, HostOut):
             v = a.ctype(-12345)
             host[a.name] = v
-            cargs.append(ctypes.byref(v))
+            cargs.append(v if isinstance(v, ctypes.Array) else ctypes.byref(v))      # (`int64_t *total` of two words: the array itself)
         elif a is STREAM:
             cargs.append(None if stream is None else ctypes.c_void_p(stream.cuda_stream))
         else:
@@ -594,7 +724,12 @@ def run_case(lib, case, plans, shifts=None, stream=None, device="cuda"):
         torch.cuda.synchronize()       # the default stream is idle while the side stream works
     rc = call(lib, case, cargs)
     torch.cuda.synchronize()
-    return rc, slab, {k: v.value for k, v in host.items()}
+    if rc == OK and case.then is not None:
+        export, args = case.then
+        rc2 = getattr(lib, export)(*bind_args(args, slab, plans, stream, host)[0])
+        torch.cuda.synchronize()
+        assert rc2 == OK, f"{case.export}[{case.sid}]: {export} on the call's result returned {rc2} ({lib.gnnmp_last_error().decode()})"
+    return rc, slab, {k: (v.value if hasattr(v, "value") else list(v)) for k, v in host.items()}
 
 
 def verify(case, rc, slab, host):
@@ -2670,13 +2805,11 @@ def _(ctx):
                  lambda host, v=(dW, db), with_db=with_db: {"dW": v[0], **({"db": v[1]} if with_db else {})}, no_warmup=True)
 
 
-# exports the table does not cover, each with its reason (the lifecycle calls and the collective are allowed as a class; at most eight more)
-LIFECYCLE = ("gnnmp_plan_", "gnnmp_arena_", "gnnmp_chain_jobs_")
+# exports neither TABLE nor PREP_TABLE covers, each with its reason (the collective; at most eight more)
 EXCLUDED = {
     "gnnmp_allgather_f32": "needs an RCCL communicator (tests/test_parallel_two_ranks_gpu.py runs it between two processes)",
 }
 EXCLUDED_EXTRA = {
-    "gnnmp_graphconv_chain_f32": "NOT covered by this module (host tables of device pointers, a jobs handle per batch): its scratch / out writes stay untested here",
     "gnnmp_negative_sample": "random draws with a host-side trial loop: no deterministic reference for the written prefix (tests/test_linkpred.py: properties)",
     "gnnmp_sample_neighbors": "random draws: parity is distributional (tests/test_graphprep.py); the written prefix has no exact reference",
     "gnnmp_debug_random_walk_pe_f32": "GNNMP_INTERNAL test hook: gnnmp_random_walk_pe_f32 (which IS in the table) with another LDS budget; the header documents "
@@ -3207,6 +3340,459 @@ def _(ctx):
                  [job, E_, ein, K, STREAM], ref, no_warmup=True)
 
 
+# ---- the GraphConv chain: graph_chain_kernel (csrc/graph_chain.hip) and the wave-pair kernel (csrc/graph_chain2.hip) ---------------------
+KNOB_CHAIN = 18                      # csrc/knobs.h: 1 = the general kernel only
+CHAIN_ALIGN = {"x": EUNSUPPORTED, "scratch": EUNSUPPORTED}      # include/gnnmp.h: x and scratch are 16-byte aligned, or the call refuses
+
+
+def chain_scratch_floats(N, dims, nout):
+    """gnnmp_graphconv_chain_scratch_floats(N, n_layers, dims, nout), asked of the library: the scratch array of a case has EXACTLY that many
+    floats, so the slab's guard bands say whether the number is enough.  Outside the function's domain (-1: more than four layers) a
+    refusal case gets a token array.  Without a loadable library (a dry run of the table before the build) the header's layout is
+    restated: the widest layer of each of the two buffers, the z rows, 16 floats of padding"""
+    nl = len(dims) - 1
+    try:
+        from gnnmp import _lib
+        need = int(_lib.load().gnnmp_graphconv_chain_scratch_floats(N, nl, (ctypes.c_int64 * (nl + 1))(*dims), nout))
+    except (ImportError, OSError):
+        need = N * (max(dims[1::2]) + max(dims[2::2], default=0) + nout) + 16 if nl <= 4 else -1
+    return need if need > 0 else 64
+
+
+def chain_batch(ctx, name, sizes, seed, hub=None):
+    """(graph, seg_ptr) of a batch of member graphs of `sizes` nodes (0: an empty member), made once per Ctx: random directed edges inside
+    each member (multi-edges and self edges as they fall), the last node of every member of five nodes and more isolated, the edge list
+    shuffled; hub = (member, node, k): k more in-edges for that node"""
+    if ("chain", name) not in ctx.cache:
+        rng = np.random.default_rng(seed)
+        seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        ss, tt = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+        for k, n in enumerate(sizes):
+            if n < 2:
+                continue
+            m = int(rng.integers(n, 3 * n + 1))
+            s, t = rng.integers(0, n, m), rng.integers(0, n, m)
+            if n >= 5:
+                s, t = s[t != n - 1], t[t != n - 1]
+            ss.append(s + seg[k])
+            tt.append(t + seg[k])
+        if hub is not None:
+            k, node, cnt = hub
+            ss.append(rng.integers(0, sizes[k], cnt) + seg[k])
+            tt.append(np.full(cnt, node + seg[k]))
+        s, t = np.concatenate(ss), np.concatenate(tt)
+        perm = rng.permutation(len(s))
+        ctx.cache["chain", name] = (Graph("chain_" + name, s[perm] + 1, t[perm] + 1, int(seg[-1])), seg)
+    return ctx.cache["chain", name]
+
+
+def chain_ref64(g, seg, x, layers, aggr, pool, Wh, bh):
+    """float64: per layer act(W_root x_i + W_agg aggr_j x_j + b), pooled per member graph, then the head.  layers: [(W_root, W_agg, bias |
+    None, act)] with W (dout, din); Wh (nout, dL).  Returns (logits [G][nout], scale [G][nout] = Σ_c |Wh(o, c) p_c| + |b_o|: what a
+    logit's rounding error lives on when its terms cancel)"""
+    s0, t0, N = g.s - 1, g.t - 1, g.n_dst
+    deg = np.bincount(t0, minlength=N).astype(f64)
+    h = np.asarray(x, f64)
+    with np.errstate(invalid="ignore"):
+        for Wr, Wa, b, a in layers:
+            m = seg_sum(t0, h[s0], N)
+            if aggr == MEAN:
+                m = m / np.maximum(deg, 1.0)[:, None]
+            z = h @ np.asarray(Wr, f64).T + m @ np.asarray(Wa, f64).T
+            h = act64(a, z if b is None else z + np.asarray(b, f64))
+        G = len(seg) - 1
+        p = np.zeros((G, h.shape[1]), f64)
+        for k in range(G):
+            rows = h[seg[k]:seg[k + 1]]
+            if len(rows):
+                p[k] = rows.sum(0) / (len(rows) if pool == MEAN else 1)
+        terms = np.asarray(Wh, f64)[None, :, :] * p[:, None, :]
+        b64 = np.zeros(len(Wh), f64) if bh is None else np.asarray(bh, f64)
+        logits, scale = terms.sum(-1) + b64, np.abs(terms).sum(-1) + np.abs(b64)
+    return logits, np.where(np.isfinite(scale), scale, 0.0)
+
+
+def _chain_case(ctx, sid, tags, g, seg, dims, nout, aggr, pool, lay=0, acts=None, bias="all", b_head=True, jobs=None, nan_member=None,
+                knobs=None, status=OK, n_layers=None, w_layout=None, salt=()):
+    """one call of gnnmp_graphconv_chain_f32.  dims, acts, nout, aggr, pool, w_layout go to the library as given (a refusal case gives
+    what the library must refuse); lay in (0, 1) is how the weights are STORED.  bias: 'all' | 'none' (the table itself is NULL) | the
+    layer whose entry is NULL.  salt: added to the key of the float draws (two cases of one sid-independent operand set share it)"""
+    N, G = g.n_dst, len(seg) - 1
+    nl = len(dims) - 1
+    acts = tuple(acts) if acts is not None else (1,) * nl
+    r = rng_of("chain", *(salt or (sid,)))
+    x = F(r, N, dims[0])
+    store = (lambda W: np.ascontiguousarray(W.T)) if lay else (lambda W: W)
+    layers, Wr_a, Wa_a, b_a = [], [], [], []
+    for l in range(nl):
+        din, dout = dims[l], dims[l + 1]
+        Wr, Wa = F(r, dout, din) * f32(1.0 / np.sqrt(din)), F(r, dout, din) * f32(1.0 / np.sqrt(din))
+        b = F(r, dout) * f32(0.5)
+        has_b = bias == "all" or (bias != "none" and bias != l)
+        layers.append((Wr, Wa, b if has_b else None, acts[l]))
+        Wr_a.append(Arr(f"W_root{l}", "in", store(Wr)))
+        Wa_a.append(Arr(f"W_agg{l}", "in", store(Wa)))
+        b_a.append(Arr(f"bias{l}", "in", b) if has_b else None)
+    Wh, bh = F(r, nout, dims[-1]) * f32(1.0 / np.sqrt(dims[-1])), F(r, nout) * f32(0.5)
+    if nan_member is not None:                            # one feature of the member's first node: every logit of that member is NaN, no other
+        x[seg[nan_member], 1] = np.nan
+    ref = None
+    if status == OK:
+        def ref(host, v=(g, seg, x, layers, aggr, pool, Wh, bh if b_head else None)):
+            logits, scale = chain_ref64(*v)
+            return {"out": E(logits, scale=scale)}
+    args = [Pl(g), jobs or Jobs("none"), Arr("seg_ptr", "in", seg), G, Arr("x", "in", x), nl if n_layers is None else n_layers,
+            HostArr(ctypes.c_int64, dims), PtrTab(Wr_a), PtrTab(Wa_a), None if bias == "none" else PtrTab(b_a), HostArr(ctypes.c_int, acts),
+            lay if w_layout is None else w_layout, aggr, pool, Arr("W_head", "in", store(Wh)), Arr("b_head", "in", bh) if b_head else None, nout,
+            Arr("scratch", "scratch", shape=(chain_scratch_floats(N, dims, nout),)), Arr("out", "out", shape=(G, nout)), STREAM]
+    return mk("gnnmp_graphconv_chain_f32", sid, tags, args, ref, status=status, align_status=CHAIN_ALIGN, knobs=knobs)
+
+
+CHAIN_PAIR_SIZES = ([64], [32], [33, 31], [64, 64, 1], [2, 63, 17, 47, 64, 1, 1, 30])      # tests/test_graph_chain.py: the job shapes at the pair kernel's edges
+
+
+@cases_of("gnnmp_graphconv_chain_f32")
+def _(ctx):
+    C = lambda *a, **k: _chain_case(ctx, *a, **k)
+    # ---- the general kernel: jobs NULL ---------------------------------------------------------------------------------------------------
+    # 303 rows in 12 members of 1 .. 70 nodes (one above 64), two blocks (N / 128), node 3 of member 0 with 200 more in-edges (past the
+    # four prefetched neighbour pointers, and a split row of the plan), isolated nodes
+    big, bseg = chain_batch(ctx, "big", [70, 1, 33, 20, 5, 40, 17, 64, 2, 29, 12, 10], 41, hub=(0, 3, 200))
+    yield C("big_16x128x128_sum_mean_n2", {"align", "ws"}, big, bseg, (16, 128, 128), 2, SUM, MEAN)      # Pass<16>, the two-part Pass<128>, FULLCOLS
+    yield C("big_8x32_mean_sum_n1", (), big, bseg, (8, 32), 1, MEAN, SUM, acts=(0,))                      # one layer: never stored, d1 = 0; run-time Din
+    yield C("big_20x64x8x128_sum_sum_n3", (), big, bseg, (20, 64, 8, 128), 3, SUM, SUM)                   # Din % 16 != 0; a stored layer of 8 columns; h[0] shared
+    yield C("big_4x8x8x8x4_lay1_nobias_n8", (), big, bseg, (4, 8, 8, 8, 4), 8, MEAN, MEAN, lay=1, bias="none", b_head=False, acts=(1, 0, 1, 0))
+    yield C("big_4x8x8x8x4_lay1_bias2null_n8", (), big, bseg, (4, 8, 8, 8, 4), 8, SUM, MEAN, lay=1, bias=2, acts=(1, 0, 1, 0))
+    yield C("big_16x128x128_nan_member5", (), big, bseg, (16, 128, 128), 2, SUM, MEAN, nan_member=5)
+    # empty member graphs, first, interior (two in a row) and last: their rows of `out` are b_head
+    emp, eseg = chain_batch(ctx, "empty", [0, 20, 0, 0, 30, 14, 0], 42)
+    yield C("empty_16x64_mean_mean_n3", (), emp, eseg, (16, 64), 3, MEAN, MEAN)
+    yield C("empty_16x128x128_sum_sum_n2", (), emp, eseg, (16, 128, 128), 2, SUM, SUM)
+    yield C("empty_16x128x128_sum_sum_nobhead", (), emp, eseg, (16, 128, 128), 2, SUM, SUM, b_head=False)
+    n32, s32 = chain_batch(ctx, "n32", [32], 43)
+    n33, s33 = chain_batch(ctx, "n33", [20, 13], 44)
+    yield C("n32_G1_12x16_sum_mean_n2", (), n32, s32, (12, 16), 2, SUM, MEAN)
+    yield C("n33_12x16x8_mean_sum_n5", (), n33, s33, (12, 16, 8), 5, MEAN, SUM)
+    # ---- refusals: nothing may be written ---------------------------------------------------------------------------------------------------
+    n31, s31 = chain_batch(ctx, "n31", [31], 45)
+    U = dict(status=EUNSUPPORTED)
+    yield C("refuse_N31", (), n31, s31, (16, 128), 2, SUM, MEAN, **U)
+    yield C("refuse_dout132", (), n33, s33, (16, 132), 2, SUM, MEAN, **U)
+    yield C("refuse_din6", (), n33, s33, (6, 16), 2, SUM, MEAN, **U)
+    yield C("refuse_stored_dout4", (), n33, s33, (16, 4, 8), 2, SUM, MEAN, **U)
+    yield C("refuse_aggr_max", (), n33, s33, (16, 16), 2, MAX, MEAN, **U)
+    yield C("refuse_pool_max", (), n33, s33, (16, 16), 2, SUM, MAX, **U)
+    yield C("refuse_nout9", (), n33, s33, (16, 16), 9, SUM, MEAN, **U)
+    yield C("refuse_5_layers", (), n33, s33, (8, 8, 8, 8, 8, 8), 2, SUM, MEAN, **U)
+    yield C("refuse_act_tanh", (), n33, s33, (16, 16), 2, SUM, MEAN, acts=(3,), **U)
+    yield C("refuse_w_layout2", (), n33, s33, (16, 16), 2, SUM, MEAN, w_layout=2, status=EINVAL)
+    if ("chain", "nonsquare") not in ctx.cache:
+        ctx.cache["chain", "nonsquare"] = random_graph("chain_nonsquare", 40, 90, 46, n_dst=33)
+    yield C("refuse_nonsquare_plan", (), ctx.cache["chain", "nonsquare"], s33, (16, 16), 2, SUM, MEAN, status=EINVAL)
+    # ---- the wave-pair kernel: (16, 128, 128), members of at most 64 nodes, a jobs handle packed on the host and on the device ---------------
+    # each operand set runs three times on the same values (the salt): host-packed jobs, device-packed jobs — bit-equal, asserted in
+    # tests/test_abi_memory_contract.py — and the general kernel (KNOB_CHAIN = 1), all against the float64 reference
+    heads = ((1, SUM, MEAN, 0), (3, MEAN, SUM, 1), (8, SUM, MEAN, 1), (2, MEAN, SUM, 0), (3, SUM, MEAN, 0))      # nout, aggr, pool, layout
+    for k, (sizes, (nout, aggr, pool, lay)) in enumerate(zip(CHAIN_PAIR_SIZES, heads)):
+        name = "-".join(map(str, sizes))
+        g, seg = chain_batch(ctx, "pair_" + name, sizes, 50 + k)
+        what = f"pair_{name}_n{nout}_{'sum' if aggr == SUM else 'mean'}_lay{lay}"
+        for mode in ("host", "device"):
+            tags = {"side"} if (k, mode) == (4, "host") else {"align", "ws"} if (k, mode) == (4, "device") else ()
+            yield C(f"{what}_{mode}", tags, g, seg, (16, 128, 128), nout, aggr, pool, lay=lay, jobs=Jobs(mode, seg), salt=(what,))
+        yield C(f"{what}_general", (), g, seg, (16, 128, 128), nout, aggr, pool, lay=lay, jobs=Jobs("host", seg), salt=(what,), knobs={KNOB_CHAIN: 1})
+    # a NaN member: its job is set aside for the exact path; then the SAME handle on finite values (the device re-armed the counter)
+    g, seg = chain_batch(ctx, "pair_" + "-".join(map(str, CHAIN_PAIR_SIZES[4])), CHAIN_PAIR_SIZES[4], 54)
+    for mode in ("host", "device"):
+        yield C(f"pair_nan_member2_{mode}", (), g, seg, (16, 128, 128), 2, SUM, MEAN, jobs=Jobs(mode, seg), nan_member=2, salt=("pair_nan",))
+        yield C(f"pair_finite_after_nan_{mode}", (), g, seg, (16, 128, 128), 2, SUM, MEAN, jobs=Jobs(mode, seg), salt=("pair_finite",))
+    # a handle the pair kernel must decline: it has no jobs (an empty member; a member above 64 nodes), the general kernel runs
+    for mode in ("host", "device"):
+        yield C(f"declined_empty_member_{mode}", (), emp, eseg, (16, 128, 128), 2, SUM, MEAN, jobs=Jobs(mode, eseg))
+        yield C(f"declined_member_of_70_{mode}", (), big, bseg, (16, 128, 128), 2, MEAN, SUM, jobs=Jobs(mode, bseg))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# PREP_TABLE: the writers that synchronise — plan export, the plans of a batch (csrc/plan_batch.hip), the plans of an edited graph
+# (csrc/plan_edit.hip), the job table of the wave-pair chain kernel.  The same Case objects and the same slab; they are graph prep, not
+# recordable, so tests/test_abi_graph_capture.py and the lane-group sweep leave them alone.  Every reference is exact.
+# ------------------------------------------------------------------------------------------------------------------------------------
+PREP_TABLE = {}
+
+
+def prep_cases_of(export):
+    def deco(fn):
+        PREP_TABLE[export] = fn
+        return fn
+    return deco
+
+
+def csr_of(s1, t1, n, loops):
+    """(rowptr, col, eid) of gnnmp_plan_create on the 1-based COO (s1, t1) over n nodes: slots in destination order, stable in the edge
+    position; a plan-added self loop is edge E + node (it sorts to the end of its row).  All 0-based"""
+    s0, t0 = np.asarray(s1, np.int64) - 1, np.asarray(t1, np.int64) - 1
+    if loops:
+        s0, t0 = np.concatenate([s0, np.arange(n)]), np.concatenate([t0, np.arange(n)])
+    order = np.argsort(t0, kind="stable")
+    return np.concatenate([[0], np.cumsum(np.bincount(t0, minlength=n))]), s0[order], order
+
+
+def batch_of(members):
+    """MLUtils.batch of Graph members: (s, t) 1-based with the nodes offset member after member, node offsets"""
+    off = np.concatenate([[0], np.cumsum([m.n for m in members])]).astype(np.int64)
+    s = np.concatenate([np.zeros(0, np.int64)] + [m.s + off[k] for k, m in enumerate(members)])
+    t = np.concatenate([np.zeros(0, np.int64)] + [m.t + off[k] for k, m in enumerate(members)])
+    return s, t, off
+
+
+def _csr_arrays(n, tot, wide=False, prefix=""):
+    """the three outputs of gnnmp_plan_export(64) of a plan of n rows and tot slots (an array of no element is passed as NULL)"""
+    return [Arr(prefix + "rowptr", "out", shape=(n + 1,), dtype=np.int64 if wide else np.int32, field="rowptr"),
+            Arr(prefix + "col", "out", shape=(tot,), dtype=np.int32, field="col") if tot else None,
+            Arr(prefix + "eid", "out", shape=(tot,), dtype=np.uint32 if wide else np.int32, field="eid") if tot else None]
+
+
+def _csr_ref(csr, prefix=""):
+    rowptr, col, eid = csr
+    return {prefix + "rowptr": E(rowptr, "exact"), **({prefix + "col": E(col, "exact"), prefix + "eid": E(eid, "exact")} if len(col) else {})}
+
+
+def _exported(n, csr):
+    """Case.then: gnnmp_plan_export of the plan the call created, into the slab"""
+    return ("gnnmp_plan_export", [Made("plan")] + _csr_arrays(n, len(csr[1]), prefix="new_") + [STREAM])
+
+
+def _ctx_graphs(ctx):
+    return (ctx.hub, ctx.e0, ctx.one, ctx.r31, ctx.r33, ctx.r300)
+
+
+def _plan_export(export, wide):
+    def build(ctx):
+        for g in _ctx_graphs(ctx):
+            for loops in (False, True):
+                csr = csr_of(g.s, g.t, g.n, loops)
+                tags = {"align", "side"} if (g is ctx.hub and not loops) else {"align"} if (g is ctx.r33 and loops) else ()
+                yield mk(export, f"{g.name}_loops{int(loops)}", tags, [Pl(g, loops=loops)] + _csr_arrays(g.n, len(csr[1]), wide) + [STREAM],
+                         lambda host, csr=csr: _csr_ref(csr))
+        g = ctx.r31                                                    # "any may be NULL": each output alone
+        csr = csr_of(g.s, g.t, g.n, False)
+        for k, name in enumerate(("rowptr", "col", "eid")):
+            arrs = [a if a.field == name else None for a in _csr_arrays(g.n, len(csr[1]), wide)]
+            yield mk(export, f"{g.name}_only_{name}", (), [Pl(g)] + arrs + [STREAM], lambda host, name=name, v=csr[k]: {name: E(v, "exact")})
+    return build
+
+
+PREP_TABLE["gnnmp_plan_export"] = _plan_export("gnnmp_plan_export", False)
+PREP_TABLE["gnnmp_plan_export64"] = _plan_export("gnnmp_plan_export64", True)
+
+
+@prep_cases_of("gnnmp_plan_edge_index")
+def _(ctx):
+    k = 0
+    for g in _ctx_graphs(ctx):
+        for loops in (False, True):
+            for ib, base in (IDX if g is ctx.r33 else (IDX[k % 4],)):
+                k += 1
+                dt = np.int64 if ib == 8 else np.int32
+                tags = {"align", "side"} if (g is ctx.hub and not loops) else {"align"} if (g is ctx.r33 and loops) else ()
+                outs = [Arr("out_src", "out", shape=(g.E,), dtype=dt), Arr("out_dst", "out", shape=(g.E,), dtype=dt)] if g.E else [None, None]
+                yield mk("gnnmp_plan_edge_index", f"{g.name}_loops{int(loops)}_i{ib}b{base}", tags, [Pl(g, loops=loops), ib, base] + outs + [STREAM],
+                         lambda host, g=g, ib=ib, base=base: {"out_src": E(IX(g.s, ib, base), "exact"), "out_dst": E(IX(g.t, ib, base), "exact")} if g.E else {})
+
+
+def _prep_members(ctx):
+    """six member graphs of a dataset: one without edges, one of a single node with a self edge"""
+    if "prep_members" not in ctx.cache:
+        ctx.cache["prep_members"] = [random_graph("m0", 5, 12, 61), Graph("m1", [], [], 4), Graph("m2", [1], [1], 1), random_graph("m3", 33, 100, 62),
+                                     random_graph("m4", 7, 20, 63), random_graph("m5", 12, 30, 64)]
+    return ctx.cache["prep_members"]
+
+
+def _batch_outputs(members, ib, base, want_seg, want_ind, node_ptr=None, ids=None):
+    """(arrays, reference) of the optional outputs of gnnmp_plan_concat / gnnmp_plan_select for the batch `members` (select: the dataset's
+    node offsets and the chosen ids, which add node_map_out)"""
+    s, t, off = batch_of(members)
+    N, dt = int(off[-1]), np.int64 if ib == 8 else np.int32
+    arrs = [Arr("seg_ptr_out", "out", shape=(len(members) + 1,), dtype=np.int64) if want_seg else None]
+    ref = {"seg_ptr_out": E(off, "exact")} if want_seg else {}
+    if node_ptr is not None:
+        want_map = want_ind or not want_seg      # (each of the three is NULL in some case; node_map_out is the only output in one)
+        arrs.append(Arr("node_map_out", "out", shape=(N,), dtype=np.int32) if want_map else None)
+        if want_map:
+            ref["node_map_out"] = E(np.concatenate([np.arange(node_ptr[i], node_ptr[i + 1]) for i in ids]), "exact")
+    arrs.append(Arr("graph_indicator_out", "out", shape=(N,), dtype=dt) if want_ind else None)
+    if want_ind:
+        ref["graph_indicator_out"] = E(IX(np.repeat(np.arange(1, len(members) + 1), [m.n for m in members]), ib, base), "exact")
+    return arrs, ref, (s, t, N)
+
+
+# (self loops, members in batch order — with a repeat where the call allows it —, seg_ptr_out, graph_indicator_out, its width and base)
+PREP_BATCHES = ((False, (0, 1, 2, 3), True, True, 8, 1, {"align", "side"}), (True, (3, 1, 0, 2), True, True, 4, 0, {"align"}), (False, (1, 0, 3), False, True, 4, 1, ()),
+                (True, (2, 3, 1, 0), True, False, 8, 0, ()), (False, (3, 0, 5, 1), False, False, 8, 1, ()), (True, (5, 4, 2), True, True, 8, 0, ()))
+
+
+@prep_cases_of("gnnmp_plan_concat")
+def _(ctx):
+    M = _prep_members(ctx)
+    for loops, order, want_seg, want_ind, ib, base, tags in PREP_BATCHES:
+        members = [M[i] for i in order]
+        arrs, ref, (s, t, N) = _batch_outputs(members, ib, base, want_seg, want_ind)
+        csr = csr_of(s, t, N, loops)
+        yield mk("gnnmp_plan_concat", f"loops{int(loops)}_{''.join(map(str, order))}_seg{int(want_seg)}_ind{int(want_ind)}_i{ib}b{base}", tags,
+                 [NewPlan("plan"), PlanTab([Pl(m, loops=loops) for m in members]), len(members)] + arrs + [ib, base, STREAM],
+                 lambda host, ref=ref, csr=csr: {**ref, **_csr_ref(csr, "new_")}, then=_exported(N, csr))
+
+
+@prep_cases_of("gnnmp_plan_select")
+def _(ctx):
+    M = _prep_members(ctx)
+    if "prep_dataset" not in ctx.cache:
+        s, t, off = batch_of(M)                                         # member-major, as MLUtils.batch makes it
+        ctx.cache["prep_dataset"] = (Graph("prep_dataset", s, t, int(off[-1])), off)
+    ds, node_ptr = ctx.cache["prep_dataset"]
+    for loops, order, want_seg, want_ind, ib, base, tags in PREP_BATCHES:
+        ids = list(order) + [order[0]]                                   # batch(gs[ids]) takes any index vector: one id twice
+        members = [M[i] for i in ids]
+        arrs, ref, (s, t, N) = _batch_outputs(members, ib, base, want_seg, want_ind, node_ptr, ids)
+        csr = csr_of(s, t, N, loops)
+        yield mk("gnnmp_plan_select", f"loops{int(loops)}_{''.join(map(str, ids))}_seg{int(want_seg)}_ind{int(want_ind)}_i{ib}b{base}", tags,
+                 [NewPlan("plan"), Pl(ds, loops=loops), Arr("node_ptr", "in", node_ptr), len(M), Arr("ids", "in", IX(np.asarray(ids) + 1, ib, base)), ib, base,
+                  len(ids), N, len(csr[1])] + arrs + [STREAM],
+                 lambda host, ref=ref, csr=csr: {**ref, **_csr_ref(csr, "new_")}, then=_exported(N, csr))
+
+
+def _totals(host, n_keep, e_keep):
+    assert list(host["total"]) == [n_keep, e_keep], (list(host["total"]), [n_keep, e_keep])
+
+
+@prep_cases_of("gnnmp_plan_remove_nodes")
+def _(ctx):
+    R = _mod("augment_ref")
+    # (graph, self loops, what goes: a descending list with repeats | a probability of the restated node mask, the optional outputs)
+    shapes = ((ctx.r33, False, "list", True, {"align", "side"}), (ctx.r300, True, "list", True, {"align"}), (ctx.r31, True, "list", False, ()),
+              (ctx.r300, False, 0.3, True, ()), (ctx.r33, True, 0.5, True, ()), (ctx.hub, False, "list", True, ()))
+    for k, (g, loops, what, maps, tags) in enumerate(shapes):
+        ib, base = IDX[k % 4]
+        s0, t0, N = g.s - 1, g.t - 1, g.n
+        if what == "list":
+            pick = rng_of("remove_nodes", g.name).permutation(N)[: max(1, N // 4)]
+            lst = np.sort(np.concatenate([pick, pick[: max(1, len(pick) // 2)]]))[::-1]
+            s2, t2, _, n2, nid, eid = R.remove_nodes(s0, t0, None, N, lst, base=0)
+            head = [Arr("remove", "in", IX(lst + 1, ib, base)), ib, base, len(lst), 0.0, 0]
+        else:
+            seed = 0xDEADBEEF12345 + k
+            s2, t2, _, n2, nid, eid = R.remove_nodes_p(s0, t0, None, N, what, seed, base=0)
+            head = [None, ib, base, 0, what, seed]
+        assert 0 < n2 < N and len(s2) > 0
+        new = np.full(N, -1, np.int64)
+        new[nid] = np.arange(n2)
+        csr = csr_of(s2 + 1, t2 + 1, n2, loops)
+        outs = [Arr("node_map_out", "out", shape=(n2,), dtype=np.int32), Arr("node_new_out", "out", shape=(N,), dtype=np.int32),
+                Arr("edge_map_out", "out", shape=(len(s2),), dtype=np.uint32)] if maps else [None, None, None]
+        def ref(host, v=(n2, len(s2), nid, new, eid, csr), maps=maps):
+            _totals(host, v[0], v[1])
+            out = {"node_map_out": E(v[2], "exact"), "node_new_out": E(v[3], "exact"), "edge_map_out": E(v[4], "exact")} if maps else {}
+            return {**out, **_csr_ref(v[5], "new_")}
+        yield mk("gnnmp_plan_remove_nodes", f"{g.name}_loops{int(loops)}_{what}_maps{int(maps)}_i{ib}b{base}", tags,
+                 [NewPlan("plan"), Pl(g, loops=loops)] + head + outs + [HostOut("total", ctypes.c_int64 * 2), STREAM], ref, then=_exported(n2, csr))
+
+
+@prep_cases_of("gnnmp_plan_add_edges")
+def _(ctx):
+    R = _mod("augment_ref")
+    # (graph, self loops, new edges, nodes of the child, list mode | the restated pair draw)
+    shapes = ((ctx.r33, False, 40, 38, "list", {"align", "side"}), (ctx.r300, True, 77, 300, "draw", {"align"}), (ctx.r31, True, 1, 31, "list", ()),
+              (ctx.r33, True, 33, 33, "draw", ()), (ctx.r300, False, 907, 309, "list", ()), (ctx.e0, False, 9, 5, "draw", ()))
+    for k, (g, loops, m, n_nodes, mode, tags) in enumerate(shapes):
+        ib, base = IDX[k % 4]
+        dt = np.int64 if ib == 8 else np.int32
+        seed = (k << 40) + 99
+        if mode == "list":
+            r = rng_of("add_edges", g.name, m)
+            sn, tn = r.integers(0, n_nodes, m), r.integers(0, n_nodes, m)
+            mid = [Arr("s_new", "in", IX(sn + 1, ib, base)), Arr("t_new", "in", IX(tn + 1, ib, base)), ib, base, m, n_nodes, 0, None, None]
+        else:
+            sn, tn = R.rand_pairs(seed, m, g.n)
+            mid = [None, None, ib, base, m, n_nodes, seed, Arr("s_new_out", "out", shape=(m,), dtype=dt), Arr("t_new_out", "out", shape=(m,), dtype=dt)]
+        csr = csr_of(np.concatenate([g.s, sn + 1]), np.concatenate([g.t, tn + 1]), n_nodes, loops)
+        def ref(host, sn=sn, tn=tn, csr=csr, mode=mode, ib=ib, base=base):
+            out = {"s_new_out": E(IX(sn + 1, ib, base), "exact"), "t_new_out": E(IX(tn + 1, ib, base), "exact")} if mode == "draw" else {}
+            return {**out, **_csr_ref(csr, "new_")}
+        yield mk("gnnmp_plan_add_edges", f"{g.name}_loops{int(loops)}_m{m}_n{n_nodes}_{mode}_i{ib}b{base}", tags,
+                 [NewPlan("plan"), Pl(g, loops=loops)] + mid + [STREAM], ref, then=_exported(n_nodes, csr))
+
+
+def bfd_jobs(sizes):
+    """the number of jobs of gnnmp_chain_jobs_create: best fit decreasing into jobs of 64 rows (members by decreasing size, ties by id,
+    each into the fullest job that still takes it)"""
+    room = []
+    for sz in sorted((int(v) for v in sizes if v > 0), reverse=True):
+        fits = [j for j, r in enumerate(room) if r >= sz]
+        if fits:
+            room[min(fits, key=lambda j: room[j])] -= sz
+        else:
+            room.append(64 - sz)
+    return len(room)
+
+
+def _job_table_ref(sizes, njobs, mode):
+    """what gnnmp_chain_jobs_export owes (tests/test_plan_batch.py: check_packing, tests/test_graph_chain.py: test_job_packing): every row of
+    the batch in exactly one slot, members whole, contiguous and in node order, a job filled from slot 0 without holes and of at most 64
+    rows, -1 in every other slot — the header: a row at or above the job count holds -1 throughout.  hdr_out[0..4] exactly: jobs, 32-row
+    tiles (counted on the exported table; 0 from a host-packed handle), not poisoned, the largest member, the empty members.  The phase
+    stamps hdr_out[16..29] are timings: written, not compared"""
+    sizes = np.asarray(sizes, np.int64)
+    seg = np.concatenate([[0], np.cumsum(sizes)])
+    seen_tiles = []
+
+    def tab_pred(tab):
+        seen_tiles.clear()
+        if not (tab[njobs:] == -1).all():
+            return "a row at or above the job count holds something else than -1"
+        count = np.zeros(int(seg[-1]), np.int64)
+        graph_of = np.repeat(np.arange(len(sizes)), sizes)
+        tiles = 0
+        for j in range(njobs):
+            row = tab[j]
+            n = int((row >= 0).sum())
+            if n == 0 or not (row[:n] >= 0).all() or not (row[n:] == -1).all() or row[:n].max() >= len(count):
+                return f"job {j} is empty, has a hole or names a row outside the batch"
+            np.add.at(count, row[:n], 1)
+            at = 0
+            while at < n:
+                k = graph_of[row[at]]
+                if at + sizes[k] > n or not np.array_equal(row[at:at + sizes[k]], np.arange(seg[k], seg[k + 1])):
+                    return f"job {j}: member graph {k} is not whole and in node order"
+                at += sizes[k]
+            tiles += 2 if n > 32 else 1
+        if njobs and not (count == 1).all():
+            return "some row of the batch is in no slot, or in two"
+        seen_tiles.append(tiles)
+        return None
+
+    def hdr_pred(hdr):
+        tiles = (seen_tiles or [None])[0] if mode == "device" and njobs else 0
+        empty = int((sizes == 0).sum()) if (mode == "device" and njobs) else int((sizes == 0).any())
+        want = [njobs, tiles, 0, int(sizes.max()), empty]
+        return None if [int(v) for v in hdr[:5]] == want else f"hdr_out[0..4] = {[int(v) for v in hdr[:5]]}, expected {want}"
+    return {"tab_out": E(pred=tab_pred), "hdr_out": E(pred=hdr_pred)}
+
+
+@prep_cases_of("gnnmp_chain_jobs_export")
+def _(ctx):
+    # the member sizes of the pair kernel's cases: cap_rows equal to the number of jobs and larger; a batch that gets no jobs at all
+    shapes = ((CHAIN_PAIR_SIZES[4], "host", 0, {"align", "side"}), (CHAIN_PAIR_SIZES[4], "device", 0, {"align"}), (CHAIN_PAIR_SIZES[4], "host", 3, ()),
+              (CHAIN_PAIR_SIZES[4], "device", 3, ()), (CHAIN_PAIR_SIZES[2], "device", 7, ()), ([0, 20, 0, 0, 30, 14, 0], "host", 2, ()),
+              ([70, 1, 33], "device", 2, ()))
+    for sizes, mode, more, tags in shapes:
+        seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        njobs = bfd_jobs(sizes) if (max(sizes) <= 64 and min(sizes) > 0) else 0
+        cap = njobs + more
+        yield mk("gnnmp_chain_jobs_export", f"{'-'.join(map(str, sizes))}_{mode}_cap{cap}", tags,
+                 [Jobs(mode, seg), Arr("tab_out", "out", shape=(cap, 64), dtype=np.int32), cap, Arr("hdr_out", "out", shape=(32,), dtype=np.int32), STREAM],
+                 lambda host, v=(sizes, njobs, mode): _job_table_ref(*v))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # variants: TABLE[export](ctx) builds the cases of ctx.variant
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -3222,6 +3808,7 @@ def _of_variant(build):
 
 
 TABLE = {export: _of_variant(build) for export, build in TABLE.items()}
+PREP_TABLE = {export: _of_variant(build) for export, build in PREP_TABLE.items()}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ existing per-kernel tests: bit-equality where they assert it, 1e-5 of the refere
 points), SPLIT_BOUND for the dense core."""
 import ctypes
 import os
+import re
 import sys
 
 import numpy as np
@@ -32,7 +33,7 @@ def _dry_ctx():
 
 
 def _all_cases(ctx):
-    return [c for build in A.TABLE.values() for c in build(ctx)]
+    return [c for table in (A.TABLE, A.PREP_TABLE) for build in table.values() for c in build(ctx)]
 
 
 def test_every_pointer_writing_export_is_covered_or_excluded_with_a_reason():
@@ -46,17 +47,17 @@ def test_every_pointer_writing_export_is_covered_or_excluded_with_a_reason():
     # an export that takes `const gnnmp_<x>_t *job` writes through the record's non-const fields: a parser that lost the records would
     # file all of them as "writes nothing" again
     assert sum(w == "record" for w in why.values()) >= 30, why
-    assert len(A.EXCLUDED_EXTRA) <= 8, "at most eight exports may be excluded beyond the lifecycle calls and the collective"
+    assert len(A.EXCLUDED_EXTRA) <= 8, "at most eight exports may be excluded beyond the collective"
     assert all(isinstance(r, str) and len(r) > 20 for r in {**A.EXCLUDED, **A.EXCLUDED_EXTRA}.values())
-    missing = []
-    for name in need:
-        lifecycle = name.startswith(A.LIFECYCLE) and name != "gnnmp_plan_slot_gather_f32"
-        if not (name in A.TABLE or lifecycle or name in A.EXCLUDED or name in A.EXCLUDED_EXTRA):
-            missing.append(name)
+    # covered by a table, or excluded with its reason: no export is waved through by its name (the plan writers and
+    # gnnmp_chain_jobs_export synchronise, so they live in PREP_TABLE, which the capture test does not record)
+    covered = set(A.TABLE) | set(A.PREP_TABLE)
+    missing = [name for name in need if not (name in covered or name in A.EXCLUDED or name in A.EXCLUDED_EXTRA)]
     assert not missing, f"exports without a case and without a reason: {missing}"
-    assert not (set(A.TABLE) & (set(A.EXCLUDED) | set(A.EXCLUDED_EXTRA)))
-    assert "gnnmp_plan_slot_gather_f32" in A.TABLE
-    assert set(A.TABLE) <= set(need), set(A.TABLE) - set(need)
+    assert not (covered & (set(A.EXCLUDED) | set(A.EXCLUDED_EXTRA)))
+    assert not (set(A.TABLE) & set(A.PREP_TABLE))
+    assert "gnnmp_plan_slot_gather_f32" in A.TABLE and "gnnmp_graphconv_chain_f32" in A.TABLE
+    assert covered <= set(need), covered - set(need)
 
 
 def test_the_rule_sees_a_write_through_a_record_and_only_that():
@@ -81,7 +82,22 @@ def _check_roles(export, decl_fields, values, records, count):
     assert len(values) == len(decl_fields), (export, len(values), len(decl_fields))
     for (pname, is_ptr, is_const, text), a in zip(decl_fields, values):
         rtype = A.record_of(text, records) if is_ptr else None
-        if isinstance(a, A.Arr):
+        if isinstance(a, A.PtrTab):             # a const host table of const device pointers: every entry an input array, or NULL
+            count[0] += sum(v is not None for v in a.items)
+            assert re.fullmatch(r"const \w+ \*const \*\w+", text), f"{export}: '{pname}' is {text!r}, the case passes a table of device pointers"
+            assert all(v is None or (v.role == "in" and v.field.rstrip("0123456789") == pname) for v in a.items), (export, pname)
+        elif isinstance(a, A.HostArr):
+            assert is_ptr and is_const and pname in A.HOST_ARRAYS.get(export, ()), f"{export}: '{pname}' is not documented as a host array"
+            assert text.startswith({ctypes.c_int64: "const int64_t *", ctypes.c_int: "const int *"}[a.ctype]), (export, pname, text)
+        elif isinstance(a, A.Jobs):
+            assert "gnnmp_chain_jobs_t" in text, (export, pname)
+        elif isinstance(a, A.PlanTab):
+            assert re.fullmatch(r"const gnnmp_graph_t \*const \*\w+", text), (export, pname)
+        elif isinstance(a, A.NewPlan):
+            assert re.fullmatch(r"gnnmp_graph_t \*\*\w+", text), (export, pname)
+        elif isinstance(a, A.Made):
+            assert re.fullmatch(r"const gnnmp_graph_t \*\w+", text), (export, pname)
+        elif isinstance(a, A.Arr):
             count[0] += 1
             assert is_ptr and rtype is None and not A.is_host_param(export, pname), (export, pname)
             assert a.field == pname, f"{export}: array '{a.name}' is passed as '{pname}'"
@@ -112,7 +128,7 @@ def test_case_roles_agree_with_the_header():
     lib_sig = {}
     try:
         lib = _lib.load()
-        lib_sig = {name: len(getattr(lib, name).argtypes) for name in A.TABLE}
+        lib_sig = {name: len(getattr(lib, name).argtypes) for name in (*A.TABLE, *A.PREP_TABLE)}
     except (ImportError, OSError):
         pass
     n, nrec = [0], [0]
@@ -122,6 +138,8 @@ def test_case_roles_agree_with_the_header():
             assert lib_sig[case.export] == len(decl), case.export
         before = n[0]
         _check_roles(case.export, decl, case.args, hdr.records, n)
+        if case.then is not None:                             # the second call of a case: the same rules
+            _check_roles(case.then[0], decls[case.then[0]], case.then[1], hdr.records, n)
         if any(isinstance(a, A.Rec) for a in case.args):
             nrec[0] += n[0] - before
     assert n[0] > 2000 and nrec[0] > 200
@@ -232,7 +250,7 @@ def test_the_table_has_the_shapes_the_contract_is_about():
         assert len({c.sid for c in cs}) == len(cs), f"{export}: duplicate case ids"
         assert sum("side" in c.tags for c in cs) == 1, f"{export}: exactly one side-stream case"
         assert any("align" in c.tags for c in cs), f"{export}: no alignment case"
-        if cs[0].uses_plan:
+        if cs[0].uses_plan and export in A.TABLE:       # (the workspace test runs over TABLE: a PREP_TABLE call computes nothing on a plan)
             assert any("ws" in c.tags for c in cs), f"{export}: no workspace case"
     widths = {int(c.sid.split("_D")[1].split("_")[0]) for c in by_export["gnnmp_propagate_f32"] if c.sid.startswith("hub")}
     assert widths == set(A.DS)
@@ -369,11 +387,14 @@ def ctx(lib):
 
 
 def _cases(ctx, export, tag=None):
-    cs = list(A.TABLE[export](ctx))
+    cs = list((A.TABLE if export in A.TABLE else A.PREP_TABLE)[export](ctx))
     return [c for c in cs if tag is None or tag in c.tags]
 
 
 EXPORTS = sorted(A.TABLE)
+# the writers that synchronise (plan export / concat / select / edits, the job table's export) have the same memory contract: the three
+# tests below run over both tables; the workspace test, the capture test and the lane-group sweep stay on TABLE
+WRITERS = EXPORTS + sorted(A.PREP_TABLE)
 
 
 def _fail(case, what, problems):
@@ -381,7 +402,7 @@ def _fail(case, what, problems):
 
 
 @gpu
-@pytest.mark.parametrize("export", EXPORTS)
+@pytest.mark.parametrize("export", WRITERS)
 def test_writes_all_of_its_output_and_nothing_else(lib, ctx, export):
     plans = A.Plans(lib)
     failures = []
@@ -407,7 +428,7 @@ def _shift_sets(case):
 
 
 @gpu
-@pytest.mark.parametrize("export", EXPORTS)
+@pytest.mark.parametrize("export", WRITERS)
 def test_any_element_aligned_pointer(lib, ctx, export):
     plans = A.Plans(lib)
     failures = []
@@ -430,7 +451,7 @@ def test_any_element_aligned_pointer(lib, ctx, export):
 
 
 @gpu
-@pytest.mark.parametrize("export", EXPORTS)
+@pytest.mark.parametrize("export", WRITERS)
 def test_on_a_side_stream(lib, ctx, export):
     import torch
     side = torch.cuda.Stream()
@@ -477,4 +498,34 @@ def test_result_does_not_depend_on_earlier_calls_on_the_plan(lib, ctx, export):
     finally:
         used.close()
         fresh.close()
+    assert not failures, "\n".join(failures)
+
+
+@gpu
+def test_chain_on_host_and_device_packed_jobs_is_bit_equal(lib, ctx):
+    """the wave-pair kernel on a job table packed by gnnmp_chain_jobs_create and on one packed by gnnmp_chain_jobs_pack: the two packings
+    may place a member graph in another job, and a row's arithmetic does not depend on where its tile falls
+    (tests/test_graph_chain.py: test_sharded_equals_unsharded_bit_for_bit) — the same operands give the same bits of `out`"""
+    cases = {c.sid: c for c in _cases(ctx, "gnnmp_graphconv_chain_f32")}
+    # every pair of cases on one operand set runs, in the table's order (a NaN member, then finite values on the same two handles); the
+    # bits are owed where no job is set aside: the fp32 redo of a set-aside job covers ALL members of that job, and which members share a
+    # job is the packing's choice
+    pairs = [(c, cases[sid[:-len("_host")] + "_device"]) for sid, c in cases.items() if sid.startswith("pair_") and sid.endswith("_host")]
+    assert len(pairs) >= len(A.CHAIN_PAIR_SIZES) + 2 and sum("_nan_member" in ch.sid for ch, _ in pairs) == 1
+    plans = A.Plans(lib)
+    failures = []
+    try:
+        for ch, cd in pairs:
+            outs = []
+            for c in (ch, cd):
+                rc, slab, host = A.run_case(lib, c, plans)
+                assert rc == A.OK, (c.sid, rc)
+                info = (ctypes.c_int64 * 8)()
+                assert lib.gnnmp_chain_jobs_info(plans.jobs(c.args[1]), info) == A.OK and info[0] > 0, f"{c.sid}: the handle has no jobs"
+                outs.append(slab.outputs()["out"])
+            assert all(np.array_equal(a0.data, a1.data, equal_nan=True) for a0, a1 in zip(ch.arrs, cd.arrs) if a0.data is not None), ch.sid
+            if "_nan_member" not in ch.sid and not np.array_equal(outs[0], outs[1]):
+                failures.append(f"{ch.sid} / {cd.sid}: `out` differs between the host-packed and the device-packed job table")
+    finally:
+        plans.close()
     assert not failures, "\n".join(failures)

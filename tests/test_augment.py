@@ -22,7 +22,7 @@ def test_header_declares_both_calls_and_the_binding_has_them():
         assert [p[0] for p in decls[name]] == want, name
         assert name in _lib.SYMBOLS
         assert getattr(_lib.load(), name).argtypes is not None
-        assert name.startswith(A.LIFECYCLE) and name not in A.TABLE          # the plan lifecycle family: tests/test_plan_edit.py, not the table
+        assert name in A.PREP_TABLE and name not in A.TABLE          # graph prep that synchronises: the memory-contract table, not the recorded one
     assert "total" in A.HOST_PARAMS
 
 
