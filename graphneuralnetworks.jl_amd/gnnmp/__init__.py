@@ -29,7 +29,7 @@ from .linkpred import (DotDecoder, WithGraph, dot_decoder, dot_decoder_ad, edge_
 from .neighbors import knn_graph, radius_graph  # noqa: F401
 from .generate import hyperbolic_graph, rand_temporal_hyperbolic_graph, rand_temporal_radius_graph  # noqa: F401
 from .transform import (EdgeCoalescing, add_edges, add_nodes, coalesce_edges, has_isolated_nodes, has_multi_edges,  # noqa: F401
-                        perturb_edges, random_walk_pe, remove_edges, remove_multi_edges, remove_nodes, remove_self_loops,
+                        perturb_edges, ppr_diffusion, random_walk_pe, remove_edges, remove_multi_edges, remove_nodes, remove_self_loops,
                         to_bidirected, to_unidirected)
 from .hetero import (GNNHeteroGraph, HeteroGraphConv, edge_type_subgraph, hetero_propagate, num_edge_types,  # noqa: F401
                      num_node_types, rand_bipartite_heterograph, rand_heterograph)

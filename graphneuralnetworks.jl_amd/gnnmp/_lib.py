@@ -55,7 +55,7 @@ SYMBOLS = (
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32", "gnnmp_hyperbolic_graph_f32",
     "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
-    "gnnmp_random_walk_pe_f32",
+    "gnnmp_random_walk_pe_f32", "gnnmp_ppr_diffusion_f32",
     "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
     "gnnmp_egnn_edge_f32", "gnnmp_egnn_coord_f32", "gnnmp_egnn_coord_grad_f32", "gnnmp_act_grad_z_f32",
     "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
@@ -123,6 +123,15 @@ class RwpeJob(ctypes.Structure):
     """gnnmp_rwpe_t: one gnnmp_random_walk_pe_f32 call"""
     _fields_ = [("w", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
                 ("walk_length", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
+PPR_MAX_NODES = 4096                     # include/gnnmp.h: GNNMP_PPR_MAX_NODES
+
+
+class PprJob(ctypes.Structure):
+    """gnnmp_ppr_t: one gnnmp_ppr_diffusion_f32 call"""
+    _fields_ = [("w", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
+                ("alpha", ctypes.c_float), ("lds_budget_bytes", ctypes.c_int64), ("out", ctypes.c_void_p)]
 
 
 class EdgeConvJob(ctypes.Structure):
@@ -462,6 +471,7 @@ def load():
         "gnnmp_has_multi_edges": [vp, vp, i, i, i64, ctypes.POINTER(i), vp],
         "gnnmp_has_isolated_nodes": [vp, ctypes.POINTER(i), vp],
         "gnnmp_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), vp],
+        "gnnmp_ppr_diffusion_f32": [vp, ctypes.POINTER(PprJob), vp],
         "gnnmp_edge_conv_f32": [vp, ctypes.POINTER(EdgeConvJob), i64, vp],
         "gnnmp_edge_conv_grad_f32": [vp, vp, ctypes.POINTER(EdgeConvGradJob), i64, vp],
         "gnnmp_cg_conv_grad_f32": [vp, vp, ctypes.POINTER(CGConvGradJob), i64, vp],

@@ -8,6 +8,7 @@
   has_multi_edges       GNNGraphs/src/query.jl:575-579
   has_isolated_nodes    GNNGraphs/src/query.jl:420-422
   random_walk_pe        GNNGraphs/src/transform.jl:975-990
+  ppr_diffusion         GNNGraphs/src/transform.jl:1026-1051   (csrc/ppr.hip)
   remove_nodes          GNNGraphs/src/transform.jl:212-276
   add_edges             GNNGraphs/src/transform.jl:319-353
   perturb_edges         GNNGraphs/src/transform.jl:385-420
@@ -209,22 +210,63 @@ def random_walk_pe(g: GNNGraph, walk_length: int):
     out = torch.empty((g.num_nodes, walk_length), dtype=torch.float32, device=g.device)
     if g.num_nodes == 0:
         return out
-    sp = None
-    if g.num_graphs > 1 and g.graph_indicator is not None:
-        # the node offsets of the member graphs: a constant of the batch (gnnmp/utils.py caches the same array)
-        sp = g._cache.get("node_ptr")
-        if sp is None:
-            gi = g.graph_indicator
-            sp = torch.empty(g.num_graphs + 1, dtype=torch.int64, device=g.device)
-            L.check(L.load().gnnmp_segment_bounds(L.ptr(gi), gi.element_size(), g.index_base, g.num_nodes, g.num_graphs, L.ptr(sp),
-                                                  L.stream_ptr()))
-            g._cache["node_ptr"] = sp
+    sp = _node_ptr(g)
     job = L.RwpeJob(L.ptr(g.w), L.ptr(sp), 8, g.num_graphs if sp is not None else 1, walk_length, L.ptr(out))
     rc = L.load().gnnmp_random_walk_pe_f32(g.plan_transposed().handle, ctypes.byref(job), L.stream_ptr())
     if rc == L.EINVAL:
         raise ValueError(L.load().gnnmp_last_error().decode())      # an edge between two member graphs, an indicator that is not sorted
     L.check(rc)
     return out
+
+
+def _node_ptr(g: GNNGraph):
+    """the node offsets of the member graphs of a batch (None for one graph): a constant of the batch (gnnmp/utils.py caches the same
+    array)"""
+    if not (g.num_graphs > 1 and g.graph_indicator is not None):
+        return None
+    sp = g._cache.get("node_ptr")
+    if sp is None:
+        gi = g.graph_indicator
+        sp = torch.empty(g.num_graphs + 1, dtype=torch.int64, device=g.device)
+        L.check(L.load().gnnmp_segment_bounds(L.ptr(gi), gi.element_size(), g.index_base, g.num_nodes, g.num_graphs, L.ptr(sp),
+                                              L.stream_ptr()))
+        g._cache["node_ptr"] = sp
+    return sp
+
+
+def ppr_diffusion(g: GNNGraph, alpha=0.85, *, lds_budget_bytes: int = 160 * 1024) -> GNNGraph:
+    """ppr_diffusion(g; alpha = 0.85f0): g with the weight of every edge s -> t replaced by alpha * inv(I + (alpha - 1) * A)[t, s], A the
+    (weighted, when g has weights; parallel edges summed) adjacency matrix with A[t, s] for the edge s -> t — what the reference's CODE
+    computes (its docstring speaks of a column normalisation that the code does not do).  Float32, alpha rounded to float32 once.  Only
+    existing edges are re-weighted; every copy of a multi-edge receives the same value; a graph without weights comes back weighted.
+    A batched g is inverted member by member on the device (block diagonal; csrc/ppr.hip): nothing N x N is formed unless g is one
+    graph, and a member graph may have at most PPR_MAX_NODES nodes.  A singular I + (alpha - 1) * A is a ValueError (the reference's
+    SingularException), as are an edge between two member graphs and an unsorted graph_indicator.  Not differentiable.
+    The result shares g's nodes, features, indicator and plans, as set_edge_weight's does.
+    lds_budget_bytes (keyword only): the record's field of that name, passed through as it is — a tuning knob, the result does not
+    depend on it.  The mirror asks for the largest, 160 KB, which keeps member graphs of up to 201 nodes in LDS (a launch takes only what its largest such graph needs, so a
+    batch of small graphs pays nothing for it; measured, DESIGN.md §5: a batch of 150-node graphs is about 300 times faster than at the
+    record's own default, 0 = 64 KB = 127 nodes, which sends them through device scratch one after another)."""
+    _plain_graph(g, "ppr_diffusion")
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real):
+        raise TypeError(f"ppr_diffusion: alpha must be a real number, got {type(alpha).__name__}")
+    alpha = float(alpha)
+    if not math.isfinite(alpha):
+        raise ValueError(f"ppr_diffusion: alpha {alpha} is not finite")
+    out = torch.empty(g.num_edges, dtype=torch.float32, device=g.device)
+    if g.num_nodes > 0 and g.num_edges > 0:
+        sp = _node_ptr(g)
+        job = L.PprJob(L.ptr(g.w), L.ptr(sp), 8, g.num_graphs if sp is not None else 1, alpha, int(lds_budget_bytes), L.ptr(out))
+        rc = L.load().gnnmp_ppr_diffusion_f32(g.plan_transposed().handle, ctypes.byref(job), L.stream_ptr())
+        if rc == L.EINVAL:
+            raise ValueError(L.load().gnnmp_last_error().decode())      # a singular block, an edge between two member graphs, ...
+        L.check(rc)
+    g2 = GNNGraph(g.s, g.t, out, num_nodes=g.num_nodes, graph_indicator=g.graph_indicator, num_graphs=g.num_graphs, x=g.x,
+                  index_base=g.index_base, device=g.device, _validated=True)
+    g2._plans = g._plans      # same (s, t): the plans are shared, as set_edge_weight shares them
+    if "node_ptr" in g._cache:
+        g2._cache["node_ptr"] = g._cache["node_ptr"]      # same nodes and indicator: a second diffusion or random_walk_pe reuses the offsets
+    return g2
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -502,6 +502,54 @@ typedef struct {
 /* Synchronises the stream (graph prep). */
 int gnnmp_random_walk_pe_f32(gnnmp_graph_t *plan_t, const gnnmp_rwpe_t *job, gnnmp_stream_t stream);
 
+/* ppr_diffusion(g; alpha) — GNNGraphs/src/transform.jl:1026-1051: the personalised-PageRank re-weighting of the existing edges,
+ *   A = sparse(t, s, w, N, N)          A[t, s] = the summed weights of the edges s -> t (1 per edge without weights), Float32
+ *   M = I + (alpha32 - 1) * A          (the product is rounded, then added; alpha32 = alpha rounded to float32, used in both places)
+ *   new_w[e] = alpha32 * inv(M)[t_e, s_e]        (every copy of a multi-edge receives the same value; no column is normalised)
+ * The reference inverts the dense N x N matrix on the host.  A batched graph is block diagonal, so here every member graph of n nodes is
+ * its own n x n block, inverted IN PLACE (n * n floats, no augmented [M | I]) by Gauss-Jordan elimination with partial pivoting:
+ *   build    A[t][s] accumulates in slot order (the original edge order), then M[i][j] = delta_ij + (alpha32 - 1) * A[i][j]
+ *   step k   f_i = a_ik for every row i.  The pivot row p is the row i >= k with the largest |f_i|, the LOWEST such i on a tie.  An
+ *            exactly zero pivot marks the block singular and the step is skipped.  Otherwise rows p and k are exchanged, the pivot
+ *            row becomes r_j = a_kj / piv with a_kk taken as 1 (so r_k = 1 / piv), and every other row i is updated as
+ *              a_ij = fmaf(-f_i, r_j, a_ij)   for j != k,        a_ik = fmaf(-f_i, r_k, 0)
+ *   finish   the row exchanges are undone on the columns, last first (an index map; no element moves or changes)
+ *   write    out[eid] = alpha32 * Minv[t - base][s - base] for every slot of the member graph
+ * Every element sees this one sequence of fp32 operations whichever path runs.  A member graph whose block, a column and the exchange
+ * list ((n * n + 2 n) * 4 bytes) fit the LDS budget of a workgroup — 64 KB by default: n <= 127; at most 160 KB: n <= 201 — is
+ * eliminated by one workgroup in LDS; a larger one in device scratch, one after another on the stream, every step a pivot launch
+ * (search, exchange, scale) and a grid-wide update launch, the pivot index and the singular mark staying on the device.  The two paths,
+ * a member graph alone and the same graph inside any batch give the same bits.  Deterministic.
+ *   plan_t      the TRANSPOSED plan of g (the plan of (t, s): a row holds the out-edges of a node) WITHOUT added self loops
+ *   job         a host record of device pointers:
+ *     w                 [n_edges] edge weights in original edge order, or NULL (all ones)
+ *     graph_ptr         [n_graphs + 1] 0-based node offsets of the member graphs (idx_bytes 4 | 8; empty graphs allowed), or NULL: one graph
+ *     alpha             the damping factor
+ *     lds_budget_bytes  0 = the default (64 KB); a smaller value sends more member graphs through the scratch path, values above
+ *                       160 KB count as 160 KB
+ *     out               [n_edges] the new weights in original edge order — every element written, nothing else; 4-byte aligned
+ * A set-up call like a plan build: it allocates scratch (GNNMP_PPR_MAX_NODES^2 floats at most) and synchronises the stream.  With a
+ * graph_ptr one check launch verifies that it ascends from 0 to N and that no edge leaves its graph's node range: GNNMP_EINVAL
+ * otherwise, with out untouched.  Refused before any HIP call: (GNNMP_EINVAL) a NULL plan_t, job or out (with n_edges > 0), idx_bytes
+ * not 4 | 8, n_graphs < 1 with a graph_ptr, a plan with added self loops or n_src != n_dst, a non-finite alpha, a negative
+ * lds_budget_bytes.  A member graph of more than GNNMP_PPR_MAX_NODES nodes is GNNMP_EUNSUPPORTED (the dense n x n block: 64 MB of
+ * scratch and 8192 launches at the limit), with out untouched.  A singular block — an exactly zero pivot after pivoting, the
+ * reference's SingularException — is GNNMP_EINVAL after the final synchronisation; gnnmp_last_error names the first such member graph
+ * and out is then UNSPECIFIED.  N == 0 or n_edges == 0: GNNMP_OK, nothing is launched.  Float32 only; no adjoint (the reference marks
+ * nothing differentiable here). */
+#define GNNMP_PPR_MAX_NODES 4096
+typedef struct {
+    const float *w;
+    const void *graph_ptr;
+    int idx_bytes;
+    int64_t n_graphs;
+    float alpha;
+    int64_t lds_budget_bytes;
+    float *out;
+} gnnmp_ppr_t;
+/* Synchronises the stream (graph prep). */
+int gnnmp_ppr_diffusion_f32(gnnmp_graph_t *plan_t, const gnnmp_ppr_t *job, gnnmp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Leaf ops: _gather / _scatter (GNNGraphs/src/gatherscatter.jl:4,12-18)
  * ---------------------------------------------------------------------------------------------- */
