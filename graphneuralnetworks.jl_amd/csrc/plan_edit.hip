@@ -71,6 +71,12 @@ __global__ void __launch_bounds__(BS) rm_list_kernel(const void *__restrict__ re
     }
     keep[k] = 0;      // (repeats store the same value)
 }
+// keep[i] = (mask[i] != 0) for i < N, keep[N] = 0: the caller's mask in the 0 / 1 form the scans add up (gnnmp_plan_keep_nodes)
+__global__ void __launch_bounds__(BS) rm_mask_kernel(int64_t N, const uint32_t *__restrict__ mask, uint32_t *__restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x;
+    if (i > N) return;
+    keep[i] = i < N && mask[i] != 0u ? 1u : 0u;
+}
 // slot p of row i holds edge (col[p] -> i): it survives iff both ends do (a plan-added self loop has col = i).  Every original edge
 // owns exactly one slot, so the loop over slots also writes the keep flag of every edge POSITION.  Thread T closes both scans.
 __global__ void __launch_bounds__(BS) rm_slot_kernel(const uint32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -250,24 +256,20 @@ int check_common(const char *who, gnnmp_graph_t **out, const gnnmp_graph_t *pare
     return GNNMP_OK;
 }
 
-}  // namespace
-}  // namespace gnnmp
+// how the keep flags of a call come about: the caller's mask (gnnmp_plan_keep_nodes), or a list / a Bernoulli draw (gnnmp_plan_remove_nodes)
+struct RmMark {
+    bool by_mask = false;
+    const uint32_t *mask = nullptr;
+    const void *remove = nullptr;
+    int idx_bytes = 8, index_base = 0;
+    int64_t n_remove = 0;
+    float p = 0.0f;
+    uint64_t seed = 0;
+};
 
-using namespace gnnmp;
-
-extern "C" {
-
-int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *remove, int idx_bytes, int index_base,
-                            int64_t n_remove, float p, uint64_t seed, int32_t *node_map_out, int32_t *node_new_out,
-                            uint32_t *edge_map_out, int64_t *total, gnnmp_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GNNMP_TRY(check_common("plan_remove_nodes", out, parent, idx_bytes, index_base));
-    if (!total) return fail(GNNMP_EINVAL, "plan_remove_nodes: total is NULL");
-    total[0] = total[1] = 0;
-    if (n_remove < 0) return fail(GNNMP_EINVAL, "plan_remove_nodes: negative n_remove");
-    if (!(p >= 0.0f && p <= 1.0f)) return fail(GNNMP_EINVAL, "plan_remove_nodes: probability %g outside [0, 1]", (double)p);
-    if (remove && p != 0.0f) return fail(GNNMP_EINVAL, "plan_remove_nodes: a remove list and a probability (p must be 0 in list mode)");
-    if (!remove && n_remove != 0) return fail(GNNMP_EINVAL, "plan_remove_nodes: n_remove = %lld without a remove list", (long long)n_remove);
+// the body the two exports share: everything after the argument checks — the mark, the three scans, the one synchronisation, the fill
+int rm_derive(const char *who, gnnmp_graph_t **out, const gnnmp_graph_t *parent, const RmMark &m, int32_t *node_map_out,
+              int32_t *node_new_out, uint32_t *edge_map_out, int64_t *total, hipStream_t stream) {
     const int64_t N = parent->n_dst, T = parent->n_total, E = parent->n_edges;
     const int loops = parent->self_loops;
 
@@ -277,18 +279,23 @@ int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, co
                                     std::max(exclusive_scan_workspace((size_t)T + 1), exclusive_scan_workspace((size_t)E + 1))));
     PoolScratch sc(stream);
     const size_t words = 2 * nN + 2 * nT + 2 * nE + nW + up64(META_WORDS);
-    if (!sc.take(sizeof(uint32_t) * words)) return fail(GNNMP_EALLOC, "plan_remove_nodes: hipMalloc of %zu bytes failed", 4 * words);
+    if (!sc.take(sizeof(uint32_t) * words)) return fail(GNNMP_EALLOC, "%s: hipMalloc of %zu bytes failed", who, 4 * words);
     uint32_t *const keep = static_cast<uint32_t *>(sc.p), *const newid = keep + nN, *const skeep = newid + nN, *const spos = skeep + nT,
                    *const ekeep = spos + nT, *const erank = ekeep + nE, *const scan_ws = erank + nE, *const meta = scan_ws + nW;
     GNNMP_HIP(hipMemsetAsync(meta, 0, sizeof(uint32_t) * META_WORDS, stream));
 
-    const bool random = remove == nullptr;
-    const DropArgs d = make_drop(random && p < 1.0f ? p : 0.0f, seed);
-    rm_mark_kernel<<<nblk(N + 1), BS, 0, stream>>>(N, random ? 1 : 0, random && p >= 1.0f ? 1 : 0, d, keep);
-    GNNMP_LAUNCH_CHECK("rm_mark_kernel");
-    if (n_remove > 0) {
-        rm_list_kernel<<<nblk(n_remove), BS, 0, stream>>>(remove, idx_bytes, index_base, n_remove, N, keep, meta);
-        GNNMP_LAUNCH_CHECK("rm_list_kernel");
+    if (m.by_mask) {
+        rm_mask_kernel<<<nblk(N + 1), BS, 0, stream>>>(N, m.mask, keep);
+        GNNMP_LAUNCH_CHECK("rm_mask_kernel");
+    } else {
+        const bool random = m.remove == nullptr;
+        const DropArgs d = make_drop(random && m.p < 1.0f ? m.p : 0.0f, m.seed);
+        rm_mark_kernel<<<nblk(N + 1), BS, 0, stream>>>(N, random ? 1 : 0, random && m.p >= 1.0f ? 1 : 0, d, keep);
+        GNNMP_LAUNCH_CHECK("rm_mark_kernel");
+        if (m.n_remove > 0) {
+            rm_list_kernel<<<nblk(m.n_remove), BS, 0, stream>>>(m.remove, m.idx_bytes, m.index_base, m.n_remove, N, keep, meta);
+            GNNMP_LAUNCH_CHECK("rm_list_kernel");
+        }
     }
     GNNMP_TRY(exclusive_scan_u32(keep, newid, (size_t)N + 1, stream, scan_ws));
     rm_slot_kernel<<<nblk(T + 1), BS, 0, stream>>>(parent->rowptr, parent->col, parent->eid, N, T, E, keep, skeep, ekeep);
@@ -301,10 +308,10 @@ int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, co
     GNNMP_HIP(hipMemcpyAsync(h, meta, sizeof(h), hipMemcpyDeviceToHost, stream));
     GNNMP_HIP(hipStreamSynchronize(stream));          // the one synchronisation: the totals size the child
     if (h[META_BAD])
-        return fail(GNNMP_EBOUNDS, "plan_remove_nodes: a listed node is outside the %lld nodes of the graph", (long long)N);
+        return fail(GNNMP_EBOUNDS, "%s: a listed node is outside the %lld nodes of the graph", who, (long long)N);
     const int64_t n_keep = h[META_NKEEP], e_keep = h[META_EKEEP], n_slots = h[META_SLOTS];
     if (n_slots != e_keep + (loops ? n_keep : 0))
-        return fail(GNNMP_EINVAL, "plan_remove_nodes: the parent plan is inconsistent (%lld slots kept for %lld edges and %lld nodes)",
+        return fail(GNNMP_EINVAL, "%s: the parent plan is inconsistent (%lld slots kept for %lld edges and %lld nodes)", who,
                     (long long)n_slots, (long long)e_keep, (long long)n_keep);
     total[0] = n_keep;
     total[1] = e_keep;
@@ -336,6 +343,42 @@ int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, co
     }
     *out = c;
     return GNNMP_OK;
+}
+
+}  // namespace
+}  // namespace gnnmp
+
+using namespace gnnmp;
+
+extern "C" {
+
+int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *remove, int idx_bytes, int index_base,
+                            int64_t n_remove, float p, uint64_t seed, int32_t *node_map_out, int32_t *node_new_out,
+                            uint32_t *edge_map_out, int64_t *total, gnnmp_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GNNMP_TRY(check_common("plan_remove_nodes", out, parent, idx_bytes, index_base));
+    if (!total) return fail(GNNMP_EINVAL, "plan_remove_nodes: total is NULL");
+    total[0] = total[1] = 0;
+    if (n_remove < 0) return fail(GNNMP_EINVAL, "plan_remove_nodes: negative n_remove");
+    if (!(p >= 0.0f && p <= 1.0f)) return fail(GNNMP_EINVAL, "plan_remove_nodes: probability %g outside [0, 1]", (double)p);
+    if (remove && p != 0.0f) return fail(GNNMP_EINVAL, "plan_remove_nodes: a remove list and a probability (p must be 0 in list mode)");
+    if (!remove && n_remove != 0) return fail(GNNMP_EINVAL, "plan_remove_nodes: n_remove = %lld without a remove list", (long long)n_remove);
+    RmMark m;
+    m.remove = remove; m.idx_bytes = idx_bytes; m.index_base = index_base; m.n_remove = n_remove; m.p = p; m.seed = seed;
+    return rm_derive("plan_remove_nodes", out, parent, m, node_map_out, node_new_out, edge_map_out, total, stream);
+}
+
+int gnnmp_plan_keep_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const uint32_t *keep, int32_t *node_map_out,
+                          int32_t *node_new_out, uint32_t *edge_map_out, int64_t *total, gnnmp_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GNNMP_TRY(check_common("plan_keep_nodes", out, parent, 8, 0));
+    if (!total) return fail(GNNMP_EINVAL, "plan_keep_nodes: total is NULL");
+    total[0] = total[1] = 0;
+    if (!keep && parent->n_dst > 0) return fail(GNNMP_EINVAL, "plan_keep_nodes: keep is NULL");
+    RmMark m;
+    m.by_mask = true;
+    m.mask = keep;      // (NULL only with N = 0: never read)
+    return rm_derive("plan_keep_nodes", out, parent, m, node_map_out, node_new_out, edge_map_out, total, stream);
 }
 
 int gnnmp_plan_add_edges(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *s_new, const void *t_new, int idx_bytes,

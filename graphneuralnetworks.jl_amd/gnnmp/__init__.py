@@ -31,6 +31,7 @@ from .generate import hyperbolic_graph, rand_temporal_hyperbolic_graph, rand_tem
 from .transform import (EdgeCoalescing, add_edges, add_nodes, coalesce_edges, has_isolated_nodes, has_multi_edges,  # noqa: F401
                         perturb_edges, ppr_diffusion, random_walk_pe, remove_edges, remove_multi_edges, remove_nodes, remove_self_loops,
                         to_bidirected, to_unidirected)
+from .pool_topk import TopKPool, topk_index, topk_pool, topk_pool_ad  # noqa: F401
 from .hetero import (GNNHeteroGraph, HeteroGraphConv, edge_type_subgraph, hetero_propagate, num_edge_types,  # noqa: F401
                      num_node_types, rand_bipartite_heterograph, rand_heterograph)
 from .backward_hetero import hetero_conv_ad, hetero_propagate_ad, hetero_propagate_grad  # noqa: F401

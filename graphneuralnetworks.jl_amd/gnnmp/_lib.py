@@ -25,7 +25,7 @@ SYMBOLS = (
     "gnnmp_version", "gnnmp_last_error",
     "gnnmp_plan_create", "gnnmp_plan_from_csc", "gnnmp_plan_destroy", "gnnmp_plan_info", "gnnmp_plan_export", "gnnmp_plan_export64",
     "gnnmp_plan_concat", "gnnmp_plan_select", "gnnmp_plan_release", "gnnmp_plan_status", "gnnmp_plan_edge_index",
-    "gnnmp_plan_remove_nodes", "gnnmp_plan_add_edges",
+    "gnnmp_plan_remove_nodes", "gnnmp_plan_add_edges", "gnnmp_plan_keep_nodes",
     "gnnmp_chain_jobs_pack", "gnnmp_chain_jobs_release", "gnnmp_chain_jobs_export",
     "gnnmp_arena_create", "gnnmp_arena_destroy", "gnnmp_arena_alloc", "gnnmp_arena_reset", "gnnmp_arena_class_of", "gnnmp_arena_info",
     "gnnmp_add_self_loops", "gnnmp_batch_coo",
@@ -65,6 +65,7 @@ SYMBOLS = (
     "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
     "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32",
+    "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -132,6 +133,31 @@ class PprJob(ctypes.Structure):
     """gnnmp_ppr_t: one gnnmp_ppr_diffusion_f32 call"""
     _fields_ = [("w", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
                 ("alpha", ctypes.c_float), ("lds_budget_bytes", ctypes.c_int64), ("out", ctypes.c_void_p)]
+
+
+TOPK_TIES_FIRST, TOPK_TIES_ALL = 0, 1                                    # include/gnnmp.h: GNNMP_TOPK_TIES_*
+TOPK_ACT_SIGMOID, TOPK_ACT_TANH, TOPK_ACT_IDENTITY = 0, 1, 2             # include/gnnmp.h: GNNMP_TOPK_ACT_*
+TOPK_GRAD_ROWS = 64                                                      # include/gnnmp.h: GNNMP_TOPK_GRAD_ROWS
+
+
+class TopkJob(ctypes.Structure):
+    """gnnmp_topk_t: one gnnmp_topk_select_f32 call"""
+    _fields_ = [("score", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
+                ("k", ctypes.c_int64), ("ratio", ctypes.c_float), ("ties", ctypes.c_int), ("lds_budget_bytes", ctypes.c_int64),
+                ("keep", ctypes.c_void_p), ("rank", ctypes.c_void_p)]
+
+
+class TopkGateJob(ctypes.Structure):
+    """gnnmp_topk_gate_t: one gnnmp_topk_gate_f32 call"""
+    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("node_map", ctypes.c_void_p), ("act", ctypes.c_int),
+                ("out", ctypes.c_void_p)]
+
+
+class TopkGateGradJob(ctypes.Structure):
+    """gnnmp_topk_gate_grad_t: one gnnmp_topk_gate_grad_f32 call (part: ceil(N / TOPK_GRAD_ROWS) * (C + 1) floats when dp is given)"""
+    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("p", ctypes.c_void_p), ("dout", ctypes.c_void_p),
+                ("node_new", ctypes.c_void_p), ("act", ctypes.c_int), ("dx", ctypes.c_void_p), ("dy", ctypes.c_void_p),
+                ("dp", ctypes.c_void_p), ("part", ctypes.c_void_p)]
 
 
 class EdgeConvJob(ctypes.Structure):
@@ -501,6 +527,11 @@ def load():
         "gnnmp_outer_accum_f32": [ctypes.POINTER(OuterAccumJob), i64, i64, i64, vp],
         "gnnmp_attn_conv_edge_f32": [vp, i, ctypes.POINTER(AttnEdgeJob), i64, i64, vp],
         "gnnmp_attn_conv_edge_grad_f32": [vp, vp, i, ctypes.POINTER(AttnEdgeGradJob), i64, i64, vp],
+        "gnnmp_plan_keep_nodes": [ctypes.POINTER(vp), vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp],
+        "gnnmp_topk_score_f32": [vp, vp, vp, i64, i64, vp],
+        "gnnmp_topk_select_f32": [ctypes.POINTER(TopkJob), i64, vp],
+        "gnnmp_topk_gate_f32": [ctypes.POINTER(TopkGateJob), i64, i64, vp],
+        "gnnmp_topk_gate_grad_f32": [ctypes.POINTER(TopkGateGradJob), i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

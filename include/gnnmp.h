@@ -264,6 +264,12 @@ int gnnmp_plan_edge_index(const gnnmp_graph_t *plan, int idx_bytes, int index_ba
  *       parent's E), and the chunk-table pass reads the child's longest row back, as gnnmp_plan_create does.  There is no
  *       synchronisation-free path.
  *
+ *   gnnmp_plan_keep_nodes  gnnmp_plan_remove_nodes with the mask SUPPLIED instead of marked (TopKPool — GNNlib/src/layers/pool.jl:14-27: the
+ *       child of view(A, idx, idx)): node i stays iff keep[i] != 0.  keep is a device array uint32[N] — what gnnmp_topk_select_f32 wrote
+ *       (its closing word keep[N] is not read).  Everything after the mark is the same code as gnnmp_plan_remove_nodes: the same child, the
+ *       same optional outputs and totals, ONE host synchronisation of `stream` (a second one for a child with a long row).  keep == NULL is
+ *       GNNMP_EINVAL unless N = 0.
+ *
  *   Refusals (before any device work): out / parent / total NULL, a non-square parent, idx_bytes / index_base, p outside [0, 1] (or p != 0
  *   in list mode), negative counts, n_nodes < N, one of s_new / t_new alone, a NULL random-mode output: GNNMP_EINVAL; a child of
  *   GNNMP_MAX_SLOTS slots or more (or 2^31 - 1 nodes): GNNMP_EUNSUPPORTED.
@@ -274,6 +280,8 @@ int gnnmp_plan_remove_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, co
 int gnnmp_plan_add_edges(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const void *s_new, const void *t_new, int idx_bytes,
                          int index_base, int64_t m, int64_t n_nodes, uint64_t seed, void *s_new_out, void *t_new_out,
                          gnnmp_stream_t stream);
+int gnnmp_plan_keep_nodes(gnnmp_graph_t **out, const gnnmp_graph_t *parent, const uint32_t *keep, int32_t *node_map_out,
+                          int32_t *node_new_out, uint32_t *edge_map_out, int64_t *total, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * A placement-aware arena for the OUTPUTS of the gather kernels (csrc/arena.hip) — optional: the rule "the caller allocates" stands,
@@ -2188,6 +2196,117 @@ typedef struct {
     float *db;               /* [R] or NULL */
 } gnnmp_outer_accum_t;
 int gnnmp_outer_accum_f32(const gnnmp_outer_accum_t *job, int64_t T, int64_t R, int64_t K, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * TopKPool and topk_index (csrc/topk.hip) — GraphNeuralNetworks/src/layers/pool.jl (TopKPool), GNNlib/src/layers/pool.jl:14-27
+ * (topk_pool, topk_index):
+ *     y = p' * X / norm(p);  idx = topk_index(y, k);  A~ = view(A, idx, idx);  X_ = view(X, :, idx) .* σ.(view(y, idx)')
+ * The reference pools one graph held as a dense matrix.  Here the unit is a batch: selection is per member graph, the child graph's plan
+ * comes from gnnmp_plan_keep_nodes (above) with the keep flags of the selection, and the gate and its pullback are row kernels.  Float32,
+ * device pointers, the caller owns every array.  The four calls of this section only launch on `stream`: no host wait, nothing taken
+ * from a pool, no atomics; each may be recorded into a HIP graph without an eager call first; two calls give equal bits.
+ *
+ * The row kernels give a row of C floats L lanes, L = the power of two >= min(C, 64): lane l adds the channels c = l, l + L, l + 2L, ...
+ * in ascending order, each product rounded before it is added, and the L partial sums fold in a butterfly (lane ^ L/2, ..., lane ^ 1).
+ * This is "the association of the row sum" wherever a row sum is spoken of below; norm(p) = sqrtf of the row sum of p[c] * p[c].
+ * Any C >= 1 works (a row wider than the lanes is walked in strides); 4-byte alignment is all a pointer owes.
+ *
+ * The ORDER of a selection.  key(v) = the monotone map of the fp32 bits to uint32 (b ^ 0xffffffff for a set sign bit, b | 0x80000000
+ * otherwise) after -0.0 is replaced by +0.0; every NaN has key 0, below -Inf.  Inside its member graph, node i has
+ *     rank_i = #{ j : key_j > key_i } + #{ j < i : key_j == key_i }
+ * — larger scores first, equal keys by ascending node id, NaNs after every number and among themselves by id.  A member graph of n_g
+ * nodes has k_g = min(n_g, k), or with k == 0  k_g = min(n_g, (int64) ceil((double) ratio * (double) n_g)).
+ *     ties = GNNMP_TOPK_TIES_FIRST (the layer)     keep[i] = rank_i < k_g: exactly k_g nodes
+ *     ties = GNNMP_TOPK_TIES_ALL (topk_index)      keep[i] = #{ j : key_j > key_i } < k_g: every node whose key is at least the key of rank
+ *                                                  k_g - 1; more than k_g of them when equal keys straddle that rank
+ * An empty member graph keeps nothing and is no error.  Integer work only: the result is exact and the same on both routes.
+ * ---------------------------------------------------------------------------------------------- */
+#define GNNMP_TOPK_TIES_FIRST 0
+#define GNNMP_TOPK_TIES_ALL 1
+#define GNNMP_TOPK_ACT_SIGMOID 0
+#define GNNMP_TOPK_ACT_TANH 1
+#define GNNMP_TOPK_ACT_IDENTITY 2
+#define GNNMP_TOPK_GRAD_ROWS 64
+
+/* y[i] = (sum_c p[c] * x[i][c]) / norm(p) for x [N][C] row-major, p [C], y [N]  (pool.jl:15).  The row sum and norm(p) in the association
+ * stated above; norm(p) is computed inside the kernel from p on the device (no host read of p).  norm(p) = 0 gives what IEEE division
+ * gives (NaN or an infinity), as in the reference.  Refused (GNNMP_EINVAL, before any launch): N < 0, C < 1, p NULL, x or y NULL with
+ * N > 0; N >= 2^31 - 1: GNNMP_EUNSUPPORTED.  N = 0: GNNMP_OK, nothing is launched. */
+int gnnmp_topk_score_f32(const float *x, const float *p, float *y, int64_t N, int64_t C, gnnmp_stream_t stream);
+
+/* The selection: keep flags (and ranks) of the N nodes of a batch from their scores, in the order stated above.
+ *   score             [N]
+ *   graph_ptr         [n_graphs + 1] 0-based node offsets of the member graphs (idx_bytes 4 | 8; empty graphs allowed), or NULL: one graph.
+ *                     It must ascend from 0 to N.  This is NOT checked (a check would need a host wait); the Python layer passes the
+ *                     array gnnmp_segment_bounds wrote.  With another array the result is undefined, but nothing outside the arrays of the
+ *                     call is read or written.
+ *   k, ratio          k >= 1: a fixed k; k == 0: ratio in (0, 1] (a float: k_g is taken from ITS value, so (float) 0.1 of 30 nodes
+ *                     is ceil(3.0000000447) = 4)
+ *   ties              GNNMP_TOPK_TIES_FIRST | GNNMP_TOPK_TIES_ALL
+ *   lds_budget_bytes  0 = the default (1 KB = 256 keys); values above 64 KB count as 64 KB, values below 4 as 4.  A member graph whose
+ *                     keys fit takes the LDS route: the workgroup that owns the 256-node tile a graph STARTS in loads the keys of a run
+ *                     of consecutive such graphs into LDS (as many as fit the budget) and gives every node one thread.  A larger member
+ *                     graph takes the device-memory route: n_g / 256 workgroups, each streaming the graph's keys from device memory.
+ *                     The result does not depend on the budget.
+ *   keep              uint32 [N + 1]: 1 | 0 per node, keep[N] = 0 — the form gnnmp_plan_keep_nodes and its scan consume.  All written.
+ *   rank              int32 [N] or NULL: rank_i, 0-based inside the member graph.  All written.
+ * Needs no scratch.  Refused (GNNMP_EINVAL, before any launch, nothing written): job or keep NULL, score NULL with N > 0, N < 0,
+ * idx_bytes not 4 | 8, n_graphs < 1 with a graph_ptr, k < 0, k == 0 with a ratio outside (0, 1] (a NaN included), a ties value other
+ * than the two, a negative lds_budget_bytes; N >= 2^31 - 1: GNNMP_EUNSUPPORTED. */
+typedef struct {
+    const float *score;
+    const void *graph_ptr;
+    int idx_bytes;
+    int64_t n_graphs;
+    int64_t k;
+    float ratio;
+    int ties;
+    int64_t lds_budget_bytes;
+    uint32_t *keep;
+    int32_t *rank;
+} gnnmp_topk_t;
+int gnnmp_topk_select_f32(const gnnmp_topk_t *job, int64_t N, gnnmp_stream_t stream);
+
+/* out[r][:] = x[node_map[r]][:] * act(y[node_map[r]]) for r < n_keep  (pool.jl:25): gather and gate in one pass.
+ *   x [N][C], y [N], node_map int32 [n_keep] (0-based parent ids: gnnmp_plan_keep_nodes' node_map_out; not range-checked),
+ *   act GNNMP_TOPK_ACT_SIGMOID (the reference: 1 / (1 + expf(-y))) | _TANH (tanhf) | _IDENTITY, out [n_keep][C], all written.
+ * Refused (GNNMP_EINVAL, before any launch): job NULL, n_keep < 0, C < 1, another act, a NULL array with n_keep > 0.  n_keep = 0: GNNMP_OK,
+ * nothing is launched. */
+typedef struct {
+    const float *x;
+    const float *y;
+    const int32_t *node_map;
+    int act;
+    float *out;
+} gnnmp_topk_gate_t;
+int gnnmp_topk_gate_f32(const gnnmp_topk_gate_t *job, int64_t n_keep, int64_t C, gnnmp_stream_t stream);
+
+/* The pullback of score + gate in ONE walk over the parent's N rows.  With r = node_new[i] (int32 [N], -1 for a dropped node:
+ * gnnmp_plan_keep_nodes' node_new_out), g = act(y_i) and dout [n_keep][C] the cotangent of out:
+ *     dy_i    = act'(y_i) * sum_c dout[r][c] * x[i][c]                 (the row sum in the association stated above; 0 for a dropped node)
+ *     dx[i][c] = dout[r][c] * g + (dy_i * p[c]) / norm(p)              (p == NULL — an externally supplied score: the first term alone);
+ *                                                                       a dropped node's row is ZERO; dx [N][C] is written whole
+ *     dp[c]   = (sum_i dy_i * x[i][c]) / norm(p) - ((sum_i dy_i * y_i) * p[c]) / norm(p)^2
+ * dy [N] (optional, NULL to skip) and dp [C] (optional; needs p and part) are written whole.  The two sums over nodes are folded in two
+ * fixed stages: workgroup b adds the kept rows b * GNNMP_TOPK_GRAD_ROWS .. in ascending i into part[b][0 .. C] (column C: dy_i * y_i),
+ * then one launch adds the workgroups in ascending b — no float atomics, equal bits from call to call.  No gradient flows through the
+ * selection (it is piecewise constant).
+ *   part   caller scratch, ceil(N / GNNMP_TOPK_GRAD_ROWS) * (C + 1) floats; read and written only when dp is given
+ * Refused (GNNMP_EINVAL, before any launch): job NULL, N < 0, C < 1, another act, dp without p or without part, a NULL x, y, dout,
+ * node_new or dx with N > 0.  N = 0: GNNMP_OK; dp (when given) is written as zeros. */
+typedef struct {
+    const float *x;
+    const float *y;
+    const float *p;
+    const float *dout;
+    const int32_t *node_new;
+    int act;
+    float *dx;
+    float *dy;
+    float *dp;
+    float *part;
+} gnnmp_topk_gate_grad_t;
+int gnnmp_topk_gate_grad_f32(const gnnmp_topk_gate_grad_t *job, int64_t N, int64_t C, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GNNMP_INTERNAL — exported, NOT part of the drop-in surface: experiment and test hooks.  Declared here so that C callers (tests/c_harness)
