@@ -15,7 +15,14 @@
 //                        leaves j, accumulates Σ α Δ_i and dss_j, adds the two rank-one terms and stores dWx_j
 //   da                   two weighted column sums over the nodes, deterministic slab partials (launch.h: column sums)
 // Long rows are chunked into virtual rows exactly like the forward kernels; partials are folded in chunk order.
+//
+// Edge features (gnnmp_gat_conv_edge_grad_f32; conv.jl:152-167): z_ij gains es_k = a_e . We_k, one float per head at the slot's ORIGINAL
+// edge position k (rows.eid, as DROP fetches it).  EDGE is a compile-time property of the two edge passes beside DROP: both add es_k to z
+// before leakyrelu, the exponential and leakyrelu', and the source pass — where an edge is exactly one slot — stores des_k = dz_ij with
+// one plain store.  The edge side needs no [E][H*C] array: with M[h][:] = Σ_c a_e[h][c] W_e[hC + c][:] (gat_edge_fold_kernel) es = e M',
+// de = des M, dM = des' e are dense calls on the E rows of e, and gat_edge_fold_grad_kernel turns dM into dW_e and da_e.
 #include <algorithm>
+#include <type_traits>
 
 #include "launch.h"
 #include "rowwalk.h"
@@ -45,11 +52,19 @@ struct GatBwdArgs {
     const float *oplus;   // [n_dst][D]
     const float *pplus;   // [n_dst][H]
 };
+// what the EDGE instances take (gnnmp_gat_conv_edge_grad_f32).  A type of its own: the kernel arguments of the e-less instances, and with
+// them their code, stay what they were
+struct GatBwdEdgeArgs : GatBwdArgs {
+    const float *escore;  // [n_edges][H] es_k, original edge order
+    float *dscore;        // [n_edges][H] des_k = dz_ij
+};
+template <bool EDGE>
+using GatBwdArgsOf = std::conditional_t<EDGE, GatBwdEdgeArgs, GatBwdArgs>;
 
 __device__ __forceinline__ float lrelu_b(float x, float slope) { return x > 0.0f ? x : x * slope; }
 
-template <int VEC, int U, int LPH, bool DROP>
-__global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
+template <int VEC, int U, int LPH, bool DROP, bool EDGE = false>
+__global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgsOf<EDGE> a) {
     VRow vr;
     if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
     const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
@@ -86,11 +101,13 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
     for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
         const int c = p < end ? a.rows.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
+        const int ev = ((DROP || EDGE) && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float w[U][VEC];
             float kf[DROP ? U : 1];      // keep_ij / (1 - p) of conv.jl:139's dropout (common.h drop_bits): g_ij becomes kf g_ij
+            float es[EDGE ? U : 1];      // the edge's share of the logit, from the slot's original edge position
+            (void)es;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int cj = __shfl(c, gbase + min(j + u, n - 1), 64);
@@ -98,6 +115,10 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
                 if (DROP) {
                     const uint32_t ej = (uint32_t)__shfl(ev, gbase + min(j + u, n - 1), 64);
                     kf[DROP ? u : 0] = drop_bits(a.drop.seed_lo, a.drop.seed_hi, ej, (uint32_t)h) >= a.drop.thr ? a.drop.inv : 0.0f;
+                }
+                if constexpr (EDGE) {
+                    const uint32_t ej = (uint32_t)__shfl(ev, gbase + min(j + u, n - 1), 64);
+                    es[u] = a.escore[(int64_t)ej * a.H + h];
                 }
             }
             float d[U], g[U];
@@ -118,7 +139,7 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatBwdArgs a) {
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float z = sd + d[u];
+                const float z = EDGE ? (sd + d[u]) + es[EDGE ? u : 0] : sd + d[u];   // the forward's order: (target + source) + edge
                 float al = expf(lrelu_b(z, a.slope) - m) * rden;
                 al = (j + u < n) ? al : 0.0f;
                 const float s = z > 0.0f ? 1.0f : a.slope;
@@ -233,8 +254,8 @@ __device__ __forceinline__ void gat_bwd_src_store(const GatBwdArgs &a, int row, 
     if ((f0 % a.C) == 0) a.dss[(int64_t)row * a.H + h] = dss;
 }
 
-template <int VEC, int U, int LPH, bool DROP>
-__global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
+template <int VEC, int U, int LPH, bool DROP, bool EDGE = false>
+__global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgsOf<EDGE> a) {
     VRow vr;
     if (!decode_vrow(a.rows, a.geom, blockIdx.x, vr)) return;
     const int v = vr.v, row = vr.row, lig = vr.lig, gbase = vr.gbase, G = vr.G;
@@ -267,12 +288,16 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
     for (uint32_t base = beg; base < end; base += G) {   // slots are unsigned 32-bit (rowwalk.h)
         const uint32_t p = base + lig;
         const int c = p < end ? a.rows.col[p] : 0;
-        const int ev = (DROP && p < end) ? a.rows.eid[p] : 0;
+        const int ev = ((DROP || EDGE) && p < end) ? a.rows.eid[p] : 0;
         const int n = (int)min((uint32_t)G, end - base);
         for (int j = 0; j < n; j += U) {
             float dv[U][VEC];
             float4 ln[U];
             float kf[DROP ? U : 1];
+            float es[EDGE ? U : 1];
+            int64_t ek[EDGE ? U : 1];    // where des_k goes: [original edge position][h]
+            (void)es;
+            (void)ek;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int ci = __shfl(c, gbase + min(j + u, n - 1), 64);
@@ -281,6 +306,11 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
                 if (DROP) {    // (the transposed plan's slots carry the same original edge positions)
                     const uint32_t ej = (uint32_t)__shfl(ev, gbase + min(j + u, n - 1), 64);
                     kf[DROP ? u : 0] = drop_bits(a.drop.seed_lo, a.drop.seed_hi, ej, (uint32_t)h) >= a.drop.thr ? a.drop.inv : 0.0f;
+                }
+                if constexpr (EDGE) {
+                    const uint32_t ej = (uint32_t)__shfl(ev, gbase + min(j + u, n - 1), 64);
+                    ek[u] = (int64_t)ej * a.H + h;
+                    es[u] = a.escore[ek[u]];
                 }
             }
             float g[U];
@@ -294,11 +324,15 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatBwdArgs a) {
             for (int u = 0; u < U; ++u) g[u] = group_sum<LPH>(g[u], a.lph);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const float z = ln[u].x + ss;
+                const float z = EDGE ? (ln[u].x + ss) + es[EDGE ? u : 0] : ln[u].x + ss;
                 float al = expf(lrelu_b(z, a.slope) - ln[u].y) * ln[u].z;
                 al = (j + u < n) ? al : 0.0f;
                 const float s = z > 0.0f ? 1.0f : a.slope;
                 const float gk = DROP ? kf[DROP ? u : 0] * g[u] : g[u];
+                // des_k = dz_ij: an edge is exactly one slot of this plan, so one lane of the head stores it once, chunk or whole row alike
+                if constexpr (EDGE) {
+                    if (j + u < n && active && (f0 % a.C) == 0) a.dscore[ek[u]] = (al * (gk - ln[u].w)) * s;
+                }
                 dss = fmaf(al * (gk - ln[u].w), s, dss);
                 const float ak = DROP ? al * kf[DROP ? u : 0] : al;
 #pragma unroll
@@ -372,8 +406,35 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_rows_kernel(const float *a, c
     out[i] = a[(int64_t)h * 2 * C + (f - h * C)] * dsd[r * H + h];
 }
 
-template <int VEC, int LPH, bool DROP>
-static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *dWx_dst, float *da,
+// M[h][k] = Σ_c a_e[h][c] W_e[hC + c][k]: the edge projection folded through the edge third of `a` — es = e M' then is one dense call
+// on the E rows of e, and no [E][H*C] array exists in training.  One thread an element, c in order.
+__global__ void __launch_bounds__(256) gat_edge_fold_kernel(const float *a_e, const float *W_e, float *M, int H, int C, int64_t ein) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)H * ein) return;
+    const int h = (int)(i / ein);
+    const int64_t k = i - (int64_t)h * ein;
+    float acc = 0.0f;
+    for (int c = 0; c < C; ++c) acc = fmaf(a_e[(int64_t)h * C + c], W_e[((int64_t)h * C + c) * ein + k], acc);
+    M[i] = acc;
+}
+// its pullback: dW_e[hC + c][k] = a_e[h][c] dM[h][k] and da_e[h][c] = Σ_k dM[h][k] W_e[hC + c][k] — one thread a row of W_e, k in order
+__global__ void __launch_bounds__(256) gat_edge_fold_grad_kernel(const float *a_e, const float *W_e, const float *dM, float *dW_e,
+                                                                 float *da_e, int H, int C, int64_t ein) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (int64_t)H * C) return;
+    const int64_t h = r / C;
+    const float ar = a_e[r];
+    float acc = 0.0f;
+    for (int64_t k = 0; k < ein; ++k) {
+        const float d = dM[h * ein + k];
+        if (dW_e) dW_e[r * ein + k] = ar * d;
+        acc = fmaf(d, W_e[r * ein + k], acc);
+    }
+    if (da_e) da_e[r] = acc;
+}
+
+template <int VEC, int LPH, bool DROP, bool EDGE = false>
+static int launch_gat_bwd(GatBwdArgsOf<EDGE> g, gnnmp_graph *plan, gnnmp_graph *plan_t, float *dWx_dst, float *da,
                           hipStream_t stream) {
     const int rpw = 64 >> g.geom.log2g;
     const int waves = block_waves(1);
@@ -392,9 +453,9 @@ static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, 
         const unsigned blocks = row_grid(g.rows, g.geom, 1).x;
         if (blocks > 0) {
             if (unroll == 4)
-                gat_bwd_dst_kernel<VEC, 4, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_dst_kernel<VEC, 4, LPH, DROP, EDGE><<<blocks, 64 * waves, 0, stream>>>(g);
             else
-                gat_bwd_dst_kernel<VEC, 8, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_dst_kernel<VEC, 8, LPH, DROP, EDGE><<<blocks, 64 * waves, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_dst_kernel");
         }
         if (g.rows.n_long > 0) {
@@ -412,9 +473,9 @@ static int launch_gat_bwd(GatBwdArgs g, gnnmp_graph *plan, gnnmp_graph *plan_t, 
             // 20 bytes of operands per lane and edge here (Δ slice + the statistics line): 4 in flight keeps 6 waves/SIMD
             // (7.0 ms on the products shape against 8.4 ms with 8 in flight at 4 waves/SIMD)
             if (unroll == 8)
-                gat_bwd_src_kernel<VEC, 8, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_src_kernel<VEC, 8, LPH, DROP, EDGE><<<blocks, 64 * waves, 0, stream>>>(g);
             else
-                gat_bwd_src_kernel<VEC, 4, LPH, DROP><<<blocks, 64 * waves, 0, stream>>>(g);
+                gat_bwd_src_kernel<VEC, 4, LPH, DROP, EDGE><<<blocks, 64 * waves, 0, stream>>>(g);
             GNNMP_LAUNCH_CHECK("gat_bwd_src_kernel");
         }
         if (g.rows.n_long > 0) {
@@ -458,10 +519,15 @@ struct GatGradCall {
     int64_t H = 0, C = 0;
     // grad2 (after gnnmp_gat_conv_train_f32): the forward's out, its bias, o+ and P
     const float *outk = nullptr, *bias = nullptr, *oplus = nullptr, *pplus = nullptr;
+    // gnnmp_gat_conv_edge_grad_f32: the per-edge logit term and its gradient (both null on a plan without edges)
+    bool edge = false;
+    const float *escore = nullptr;
+    float *dscore = nullptr;
 };
 
 static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGradCall c, gnnmp_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    if (c.edge && (c.oplus || c.drop_p > 0.0f)) return fail(GNNMP_EINVAL, "gat_conv_edge_grad: no dropout and no o+ / P shortcut together with edge features");
     if (c.oplus && (!c.outk || !c.pplus || c.drop_p > 0.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad2: needs out, oplus and pplus of gnnmp_gat_conv_train_f32");
     if (!(c.drop_p >= 0.0f && c.drop_p < 1.0f)) return fail(GNNMP_EINVAL, "gat_conv_grad: dropout probability %g outside [0, 1)", (double)c.drop_p);
     if (!plan || !plan_t) return fail(GNNMP_EINVAL, "gat_conv_grad: null plan");
@@ -511,6 +577,13 @@ static int gat_conv_grad_impl(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, GatGra
     g.pplus = c.pplus;
     return with_vec(hg.vec, [&](auto V) {
         constexpr int VEC = decltype(V)::value;
+        if (c.edge) {
+            GatBwdEdgeArgs ge;
+            static_cast<GatBwdArgs &>(ge) = g;
+            ge.escore = c.escore;
+            ge.dscore = c.dscore;
+            return with_lph<VEC, 16>(hg.lph, [&](auto L) { return launch_gat_bwd<VEC, decltype(L)::value, false, true>(ge, plan, plan_t, c.dWx_dst, c.da, stream); });
+        }
         // the dropout variants walk the head butterfly with the run-time lane count (one instantiation per width)
         if (c.drop_p > 0.0f) return launch_gat_bwd<VEC, 0, true>(g, plan, plan_t, c.dWx_dst, c.da, stream);
         // the usual case (C a multiple of 4): compile-time lane count per head -> DPP butterflies
@@ -571,4 +644,40 @@ extern "C" int gnnmp_gat_conv_grad2_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan
     c.oplus = oplus;
     c.pplus = pplus;
     return gat_conv_grad_impl(plan, plan_t, c, stream);
+}
+
+/* GATConv's pullback with edge features (see gnnmp.h): the two edge passes with the per-edge logit term, des written by the source pass */
+extern "C" int gnnmp_gat_conv_edge_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const gnnmp_gat_edge_grad_t *job, int64_t H,
+                                            int64_t C, gnnmp_stream_t stream) {
+    if (!plan || !plan_t) return fail(GNNMP_EINVAL, "gat_conv_edge_grad: null plan");
+    if (!job) return fail(GNNMP_EINVAL, "gat_conv_edge_grad: null job");
+    if (plan->self_loops || plan->n_total != plan->n_edges)
+        return fail(GNNMP_EINVAL, "gat_conv_edge_grad: the plan was built with self loops (%lld slots, %lld edges): edge_score has no row for them "
+                                  "(GNNlib/src/layers/conv.jl:119-121)", (long long)plan->n_total, (long long)plan->n_edges);
+    if (plan->n_edges > 0 && (!job->edge_score || !job->dscore)) return fail(GNNMP_EINVAL, "gat_conv_edge_grad: null edge_score / dscore");
+    GatGradCall c = gat_grad_call(job->Wx_src, job->Wx_dst, job->a, job->negative_slope, job->stats, job->dout, job->line, job->dsd, job->dss,
+                                  job->dWx_src, job->dWx_dst, job->da, H, C);
+    c.edge = true;
+    c.escore = job->edge_score;
+    c.dscore = job->dscore;
+    return gat_conv_grad_impl(plan, plan_t, c, stream);
+}
+
+extern "C" int gnnmp_gat_edge_fold_f32(const float *a_e, const float *W_e, float *M, int64_t H, int64_t C, int64_t ein, gnnmp_stream_t stream) {
+    if (H <= 0 || C <= 0 || ein <= 0 || H * C > (1 << 20) || ein > (1 << 20)) return fail(GNNMP_EINVAL, "gat_edge_fold: bad H/C/ein");
+    if (!a_e || !W_e || !M) return fail(GNNMP_EINVAL, "gat_edge_fold: null pointer");
+    const int64_t n = H * ein;
+    gat_edge_fold_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a_e, W_e, M, (int)H, (int)C, ein);
+    GNNMP_LAUNCH_CHECK("gat_edge_fold_kernel");
+    return GNNMP_OK;
+}
+extern "C" int gnnmp_gat_edge_fold_grad_f32(const float *a_e, const float *W_e, const float *dM, float *dW_e, float *da_e, int64_t H,
+                                            int64_t C, int64_t ein, gnnmp_stream_t stream) {
+    if (H <= 0 || C <= 0 || ein <= 0 || H * C > (1 << 20) || ein > (1 << 20)) return fail(GNNMP_EINVAL, "gat_edge_fold_grad: bad H/C/ein");
+    if (!a_e || !W_e || !dM) return fail(GNNMP_EINVAL, "gat_edge_fold_grad: null pointer");
+    if (!dW_e && !da_e) return GNNMP_OK;
+    const int64_t n = H * C;
+    gat_edge_fold_grad_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(a_e, W_e, dM, dW_e, da_e, (int)H, (int)C, ein);
+    GNNMP_LAUNCH_CHECK("gat_edge_fold_grad_kernel");
+    return GNNMP_OK;
 }

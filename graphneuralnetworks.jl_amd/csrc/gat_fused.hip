@@ -799,6 +799,17 @@ extern "C" int gnnmp_gat_conv_edge_f32(gnnmp_graph_t *plan, const float *Wx_src,
     c.escore = edge_score;
     return attn_conv_impl(plan, c, stream);
 }
+/* the training forward with edge features: the same ATTN_GAT_EDGE instances, which store (m, den) whenever stats is set */
+extern "C" int gnnmp_gat_conv_edge_stats_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
+                                             const float *edge_score, float negative_slope, const float *bias, int act, float *out,
+                                             float *stats, int64_t H, int64_t C, gnnmp_stream_t stream) {
+    if (!edge_score && plan && plan->n_edges > 0) return fail(GNNMP_EINVAL, "gat_conv_edge_stats: null edge_score");
+    if (plan && plan->self_loops)
+        return fail(GNNMP_EINVAL, "gat_conv_edge_stats: edge features and add_self_loops cannot be combined (GNNlib/src/layers/conv.jl:120)");
+    AttnCall c = gat_call(Wx_src, Wx_dst, a, negative_slope, bias, act, out, stats, H, C);
+    c.escore = edge_score;
+    return attn_conv_impl(plan, c, stream);
+}
 extern "C" int gnnmp_gat_conv_drop_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
                                        float negative_slope, float p, uint64_t seed, const float *bias, int act, float *out,
                                        float *stats, int64_t H, int64_t C, gnnmp_stream_t stream) {

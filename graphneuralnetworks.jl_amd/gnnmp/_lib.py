@@ -66,6 +66,7 @@ SYMBOLS = (
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
     "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32",
     "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
+    "gnnmp_gat_conv_edge_stats_f32", "gnnmp_gat_conv_edge_grad_f32", "gnnmp_gat_edge_fold_f32", "gnnmp_gat_edge_fold_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
@@ -355,6 +356,15 @@ class AttnEdgeGradJob(ctypes.Structure):
                 ("negative_slope", ctypes.c_float), ("scale", ctypes.c_float)]
 
 
+class GatEdgeGradJob(ctypes.Structure):
+    """gnnmp_gat_edge_grad_t: one gnnmp_gat_conv_edge_grad_f32 call (Wx_src, Wx_dst | None, a, edge_score, stats, dout read; line scratch;
+    dsd, dss, dWx_src, dWx_dst (bipartite), da | None and dscore written)"""
+    _fields_ = [("Wx_src", ctypes.c_void_p), ("Wx_dst", ctypes.c_void_p), ("a", ctypes.c_void_p), ("edge_score", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p), ("dout", ctypes.c_void_p), ("line", ctypes.c_void_p), ("dsd", ctypes.c_void_p),
+                ("dss", ctypes.c_void_p), ("dWx_src", ctypes.c_void_p), ("dWx_dst", ctypes.c_void_p), ("da", ctypes.c_void_p),
+                ("dscore", ctypes.c_void_p), ("negative_slope", ctypes.c_float)]
+
+
 class GnnmpError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libgnnmp status {status}: {msg}")
@@ -532,6 +542,10 @@ def load():
         "gnnmp_topk_select_f32": [ctypes.POINTER(TopkJob), i64, vp],
         "gnnmp_topk_gate_f32": [ctypes.POINTER(TopkGateJob), i64, i64, vp],
         "gnnmp_topk_gate_grad_f32": [ctypes.POINTER(TopkGateGradJob), i64, i64, vp],
+        "gnnmp_gat_conv_edge_stats_f32": [vp, vp, vp, vp, vp, f, vp, i, vp, vp, i64, i64, vp],
+        "gnnmp_gat_conv_edge_grad_f32": [vp, vp, ctypes.POINTER(GatEdgeGradJob), i64, i64, vp],
+        "gnnmp_gat_edge_fold_f32": [vp, vp, vp, i64, i64, i64, vp],
+        "gnnmp_gat_edge_fold_grad_f32": [vp, vp, vp, vp, vp, i64, i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
     }

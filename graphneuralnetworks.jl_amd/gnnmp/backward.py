@@ -582,12 +582,100 @@ class _GATConvFn(torch.autograd.Function):
         return dx, dW, da_hc.t(), db, None, None, None, None, None, None, None, None
 
 
-def gat_conv_ad(l, g: GNNGraph, x, seed=None):
-    """differentiable GATConv forward (no edge features; concat = true or false): gradients w.r.t. x, l.dense_x_weight,
-    l.a, l.bias.  l.dropout > 0: the attention coefficients are dropped (conv.jl:139) with the mask of `seed` (default: the layer's
-    next seed), in the forward and — recomputed, never stored — in the pullback."""
+class _GATConvEdgeFn(torch.autograd.Function):
+    """gat_conv with e (conv.jl:112-167, l.dense_e !== nothing; add_self_loops = false, no dropout; concat = true or false).  The edge's
+    share of the logit is es = e M' with M[h] = Σ_c a_e[h][c] W_e[hC + c] (gnnmp_gat_edge_fold_f32): no [E][H C] array is formed.  The
+    pullback is gnnmp_gat_conv_edge_grad_f32 (two edge passes, des = Δes written by the second), then the dense adjoints on the node rows
+    and on the E rows of e, and the fold's pullback for dense_e's weight and the edge third of a."""
+
+    @staticmethod
+    def forward(ctx, x, e, weight, weight_e, a, bias, g, sigma, heads, slope, concat):
+        from .layers import dense
+        lib = L.load()
+        plan = g.plan(False)
+        H = heads
+        C = weight.shape[0] // H
+        N, ein = g.num_nodes, weight_e.shape[1]
+        x, e, weight_e = x.contiguous(), e.contiguous(), weight_e.contiguous()
+        f32 = dict(dtype=torch.float32, device=x.device)
+        Wx = dense(x, weight)
+        at = a.t()                                                  # [H][3C]
+        a_hc, a_e = at[:, :2 * C].contiguous(), at[:, 2 * C:].contiguous()
+        M = torch.empty((H, ein), **f32)
+        L.check(lib.gnnmp_gat_edge_fold_f32(L.ptr(a_e), L.ptr(weight_e), L.ptr(M), H, C, ein, L.stream_ptr()))
+        es = dense(e, M)                                            # [E][H], original edge order
+        out = torch.empty((N, H * C), **f32)
+        stats = torch.empty((N, H, 2), **f32)
+        # concat = false: the heads are averaged BEFORE bias and σ (conv.jl:143-147), so the kernel's fused tail is off
+        L.check(lib.gnnmp_gat_conv_edge_stats_f32(plan.handle, L.ptr(Wx), None, L.ptr(a_hc), L.ptr(es), float(slope),
+                                                  L.ptr(bias) if concat else None, _act_code(sigma) if concat else L.ACT_IDENTITY,
+                                                  L.ptr(out), L.ptr(stats), H, C, L.stream_ptr()))
+        if not concat:
+            y = torch.empty((N, C), **f32)
+            L.check(lib.gnnmp_head_mean_f32(L.ptr(out), L.ptr(bias), _act_code(sigma), L.ptr(y), N, H, C, L.stream_ptr()))
+            out = y
+        ctx.save_for_backward(x, e, weight, weight_e, Wx, a_hc, a_e, M, es, stats, out)
+        ctx.g, ctx.sigma, ctx.H, ctx.C, ctx.slope, ctx.concat, ctx.has_bias = g, sigma, H, C, slope, concat, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, e, weight, weight_e, Wx, a_hc, a_e, M, es, stats, y = ctx.saved_tensors
+        g, H, C = ctx.g, ctx.H, ctx.C
+        need = ctx.needs_input_grad
+        lib = L.load()
+        N, E, ein = g.num_nodes, g.num_edges, weight_e.shape[1]
+        dz = act_grad(dy.contiguous(), y, ctx.sigma)
+        db = dense_grad_w(dz, dz, need_w=False, need_b=True)[1] if (ctx.has_bias and need[5]) else None
+        if not (need[0] or need[1] or need[2] or need[3] or need[4]):
+            return None, None, None, None, None, db, None, None, None, None, None
+        if not ctx.concat:                       # pullback of mean(x, dims = 2): every head receives Δ / H
+            dzh = torch.empty((N, H * C), dtype=torch.float32, device=dz.device)
+            L.check(lib.gnnmp_head_mean_grad_f32(L.ptr(dz), L.ptr(dzh), N, H, C, L.stream_ptr()))
+            dz = dzh
+        plan, plan_t = g.plan(False), plan_transposed(g, False)
+        f32 = dict(dtype=torch.float32, device=dz.device)
+        line, dsd, dss = torch.empty((N, H, 4), **f32), torch.empty((N, H), **f32), torch.empty((N, H), **f32)
+        dWx, des = torch.empty((N, H * C), **f32), torch.empty((E, H), **f32)
+        da_hc = torch.empty((H, 2 * C), **f32) if need[4] else None
+        job = L.GatEdgeGradJob(L.ptr(Wx), None, L.ptr(a_hc), L.ptr(es), L.ptr(stats), L.ptr(dz), L.ptr(line), L.ptr(dsd), L.ptr(dss),
+                               L.ptr(dWx), None, L.ptr(da_hc), L.ptr(des), float(ctx.slope))
+        L.check(lib.gnnmp_gat_conv_edge_grad_f32(plan.handle, plan_t.handle, job, H, C, L.stream_ptr()))
+        dW = dense_grad_w(dWx, x, need_b=False)[0] if need[2] else None
+        dx = dense_grad_x(dWx, weight) if need[0] else None
+        de = dense_grad_x(des, M) if need[1] else None
+        dWe = da = None
+        if need[3] or need[4]:
+            dM = dense_grad_w(des, e, need_b=False)[0]              # des' e, [H][ein]
+            dWe = torch.empty_like(weight_e) if need[3] else None
+            da_e = torch.empty((H, C), **f32) if need[4] else None
+            L.check(lib.gnnmp_gat_edge_fold_grad_f32(L.ptr(a_e), L.ptr(weight_e), L.ptr(dM), L.ptr(dWe), L.ptr(da_e), H, C, ein,
+                                                     L.stream_ptr()))
+            if need[4]:
+                da = torch.cat([da_hc, da_e], 1).t()                # the layer's (3C, H)
+        return dx, de, dW, dWe, da, db, None, None, None, None, None
+
+
+def gat_conv_ad(l, g: GNNGraph, x, e=None, seed=None):
+    """differentiable GATConv forward (concat = true or false): gradients w.r.t. x, l.dense_x_weight, l.a, l.bias — and, with edge
+    features, e, l.dense_e_weight and the edge third of l.a.  l.dropout > 0 (without e): the attention coefficients are dropped
+    (conv.jl:139) with the mask of `seed` (default: the layer's next seed), in the forward and — recomputed, never stored — in the
+    pullback."""
+    if e is not None and not torch.is_tensor(e):
+        raise TypeError(f"gat_conv_ad(l, g, x, e=None, seed=None): e must be a tensor of edge features, not {type(e).__name__}; "
+                        "pass the dropout seed by keyword, seed=")
     check_num_nodes(g, x)
-    assert getattr(l, "dense_e_weight", None) is None, "the HIP adjoint does not cover edge features"
+    dense_e = getattr(l, "dense_e_weight", None)
+    assert not (e is None and dense_e is not None), "Input edge features required for this layer"
+    assert not (e is not None and dense_e is None), "Input edge features were not specified in the layer constructor"
+    if e is not None:
+        from .graph import check_num_edges
+        from .layers_attn import SELF_LOOPS_MSG, check_edge_row_width
+        assert not l.add_self_loops, SELF_LOOPS_MSG
+        assert float(getattr(l, "dropout", 0.0)) == 0.0, "GATConv: attention dropout together with edge features is not supported"
+        check_edge_row_width(l.heads, l.channel[1], "GATConv with edge features")
+        check_num_edges(g, e)
+        return _GATConvEdgeFn.apply(x, e, l.dense_x_weight, dense_e, l.a, l.bias, g, l.sigma, l.heads, l.negative_slope, bool(l.concat))
     p_drop = float(getattr(l, "dropout", 0.0))
     if p_drop > 0.0:
         if seed is None:

@@ -876,6 +876,66 @@ typedef struct {
 int gnnmp_attn_conv_edge_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, int mode, const gnnmp_attn_edge_grad_t *job,
                                   int64_t H, int64_t C, gnnmp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training GATConv with edge features — gat_conv with `e`, GNNlib/src/layers/conv.jl:112-167 (csrc/gat_backward.hip; the forward is
+ * csrc/gat_fused.hip).  Per head h, for edge k = (j -> i) at its ORIGINAL position k, with a_d = a[h][0:C], a_s = a[h][C:2C] and
+ * es_k[h] = a_e[h] . We_k[h] the edge's share of the logit (We = dense_e(e), a_e the edge third of the layer's `a`):
+ *     z_ij = (a_d . Wx_dst_i + a_s . Wx_src_j) + es_k,  l_ij = leakyrelu(z_ij),  α_ij = softmax_{j in N(i)} l_ij,  o_i = Σ_j α_ij Wx_src_j
+ *   gnnmp_gat_conv_edge_stats_f32   gnnmp_gat_conv_edge_f32 that also writes stats[i][h] = (m_i, den_i) as gnnmp_gat_conv_stats_f32 does when
+ *                                   the pointer is non-NULL: the training forward.  The same kernels, the same bits in `out`.  The feature
+ *                                   row must fit one wave (GNNMP_EUNSUPPORTED otherwise) and the plan must not add self loops (GNNMP_EINVAL).
+ *   gnnmp_gat_conv_edge_grad_f32    dout = Δ w.r.t. o.  With g_ij = Δ_i . Wx_src_j, D_i = Σ_j α_ij g_ij and α rebuilt from stats:
+ *                                     dz_ij = α_ij (g_ij - D_i) leakyrelu'(z_ij),  dsd_i = Σ_j dz_ij,  dss_j = Σ_i dz_ij,  dscore[k][h] = dz_ij,
+ *                                     dWx_src_j = Σ_i α_ij Δ_i + a_s dss_j (+ a_d dsd_j when Wx_dst is Wx_src),  dWx_dst_i = a_d dsd_i,
+ *                                     da[h] = (Σ_i dsd_i Wx_dst_i, Σ_j dss_j Wx_src_j)
+ *                                   — gnnmp_gat_conv_grad_f32's two passes with es_k inside z: pass 1 over plan (D_i, dsd_i, the line), pass 2
+ *                                   over plan_t (dWx_src, dss, and dscore: ONE plain store at the slot's original edge position — an edge is
+ *                                   exactly one slot there, so every element of dscore is written exactly once).  Rows longer than the plans'
+ *                                   threshold are chunked and folded in chunk order as in gnnmp_gat_conv_grad_f32; no atomics, two calls
+ *                                   give equal bits.
+ *                                   job: a const HOST record of device pointers.  Wx_dst NULL = Wx_src, and dWx_dst is NULL exactly then;
+ *                                   edge_score [n_edges][H] in original edge order; stats from the forward; line [n_dst][H][4] 16-byte
+ *                                   aligned scratch; dsd [n_dst][H], dss [n_src][H], dWx_src [n_src][H*C], dWx_dst [n_dst][H*C],
+ *                                   dscore [n_edges][H] written in full; da [H][2C] nullable.  plan_t = the plan of the reversed edge index.
+ *                                   n_edges = 0: zero dWx, dsd, dss and da and the line are written; edge_score and dscore may be NULL.
+ *                                   Refused with GNNMP_EINVAL before any HIP call: a NULL plan, plan_t, job or required pointer; a NULL
+ *                                   edge_score or dscore with n_edges > 0; H or C < 1 or H*C > 2^20; a plan built with self loops
+ *                                   (conv.jl:119-121 forbids them with edge features; edge_score has no row for them); a plan_t that is not the
+ *                                   plan's transpose; a bipartite plan without Wx_dst; a line that is not 16-byte aligned.  GNNMP_EUNSUPPORTED:
+ *                                   a feature row that does not fit one wave under the rule of gnnmp_gat_conv_stats_f32.
+ *   gnnmp_gat_edge_fold_f32         M[h][:] = Σ_c a_e[h][c] W_e[hC + c][:], [H][ein] from a_e [H][C] and dense_e's weight W_e [H*C][ein], c in
+ *                                   order.  Then es = e M' (gnnmp_dense_f32 on the E rows of e, weight M), de = dscore M and dM = dscore' e
+ *                                   (the dense adjoints): training never forms the [n_edges][H*C] array We.
+ *   gnnmp_gat_edge_fold_grad_f32    dW_e[hC + c][:] = a_e[h][c] dM[h][:] and da_e[h][c] = dM[h] . W_e[hC + c] (k in order); dW_e or da_e may be
+ *                                   NULL, and with both NULL nothing is launched.
+ * Both fold calls only launch; GNNMP_EINVAL for H, C or ein < 1 (or above 2^20) and for a NULL required pointer.  Not here: attention
+ * dropout together with edge features, Float64, the o+ / P shortcut of gnnmp_gat_conv_grad2_f32.
+ * ---------------------------------------------------------------------------------------------- */
+int gnnmp_gat_conv_edge_stats_f32(gnnmp_graph_t *plan, const float *Wx_src, const float *Wx_dst, const float *a,
+                                  const float *edge_score, float negative_slope, const float *bias, int act, float *out,
+                                  float *stats, int64_t H, int64_t C, gnnmp_stream_t stream);
+typedef struct {
+    const float *Wx_src;     /* [n_src][H*C] */
+    const float *Wx_dst;     /* [n_dst][H*C] or NULL (= Wx_src) */
+    const float *a;          /* [H][2C] */
+    const float *edge_score; /* [n_edges][H], original edge order */
+    const float *stats;      /* [n_dst][H][2], from the forward */
+    const float *dout;       /* [n_dst][H*C] */
+    float *line;             /* [n_dst][H][4], 16-byte aligned scratch */
+    float *dsd;              /* [n_dst][H] */
+    float *dss;              /* [n_src][H] */
+    float *dWx_src;          /* [n_src][H*C] */
+    float *dWx_dst;          /* [n_dst][H*C]; NULL exactly when Wx_dst is NULL or Wx_src */
+    float *da;               /* [H][2C] or NULL */
+    float *dscore;           /* [n_edges][H], original edge order */
+    float negative_slope;
+} gnnmp_gat_edge_grad_t;
+int gnnmp_gat_conv_edge_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_t, const gnnmp_gat_edge_grad_t *job, int64_t H, int64_t C,
+                                 gnnmp_stream_t stream);
+int gnnmp_gat_edge_fold_f32(const float *a_e, const float *W_e, float *M, int64_t H, int64_t C, int64_t ein, gnnmp_stream_t stream);
+int gnnmp_gat_edge_fold_grad_f32(const float *a_e, const float *W_e, const float *dM, float *dW_e, float *da_e, int64_t H, int64_t C,
+                                 int64_t ein, gnnmp_stream_t stream);
+
 /* out[n][c] = act( mean_h y[n][h][c] + bias[c] ) — the concat = false tail of gat_conv (`mean(x, dims = 2)`,
  * GNNlib/src/layers/conv.jl:143-147): heads added in order, one division by H, then σ.(x .+ bias). */
 int gnnmp_head_mean_f32(const float *y, const float *bias, int act, float *out, int64_t N, int64_t H,
