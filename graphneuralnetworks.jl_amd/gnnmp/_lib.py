@@ -53,7 +53,7 @@ SYMBOLS = (
     "gnnmp_tgcn_recurrence_f32", "gnnmp_tgcn_recurrence_grad_f32", "gnnmp_tgcn_step_f32", "gnnmp_tgcn_step_grad_f32",
     "gnnmp_negative_sample", "gnnmp_rand_edge_split", "gnnmp_edge_dot_grad_f32",
     "gnnmp_knn_graph_f32", "gnnmp_radius_graph_f32", "gnnmp_hyperbolic_graph_f32",
-    "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32",
+    "gnnmp_hetero_propagate_f32", "gnnmp_hetero_propagate_grad_f32", "gnnmp_hetero_attn_f32",
     "gnnmp_coalesce_edges", "gnnmp_compact_edges", "gnnmp_has_multi_edges", "gnnmp_has_isolated_nodes",
     "gnnmp_random_walk_pe_f32", "gnnmp_ppr_diffusion_f32",
     "gnnmp_edge_conv_f32", "gnnmp_edge_conv_grad_f32", "gnnmp_cg_conv_grad_f32", "gnnmp_nn_conv_grad_f32",
@@ -97,6 +97,18 @@ class HeteroSrc(ctypes.Structure):
     """gnnmp_hetero_src_t: one source type of a gnnmp_hetero_propagate_grad_f32 call"""
     _fields_ = [("dx", ctypes.c_void_p), ("x", ctypes.c_void_p), ("n_src", ctypes.c_int64), ("n_rel", ctypes.c_int),
                 ("rels", ctypes.POINTER(HeteroRelGrad))]
+
+
+class HeteroAttnRel(ctypes.Structure):
+    """gnnmp_hetero_attn_rel_t: one attention relation of a destination type (plan = NULL: an identity relation, row i of K as it is)"""
+    _fields_ = [("plan", ctypes.c_void_p), ("mode", ctypes.c_int), ("Q", ctypes.c_void_p), ("K", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("negative_slope", ctypes.c_float), ("act", ctypes.c_int)]
+
+
+class HeteroAttnDst(ctypes.Structure):
+    """gnnmp_hetero_attn_dst_t: one destination type of a gnnmp_hetero_attn_f32 call"""
+    _fields_ = [("out", ctypes.c_void_p), ("n_dst", ctypes.c_int64), ("combine", ctypes.c_int), ("n_rel", ctypes.c_int),
+                ("rels", ctypes.POINTER(HeteroAttnRel))]
 
 
 COALESCE_DIRECTED, COALESCE_MIRRORED, COALESCE_UNDIRECTED = 0, 1, 2      # include/gnnmp.h: gnnmp_coalesce_mode
@@ -502,6 +514,7 @@ def load():
         "gnnmp_hyperbolic_graph_f32": [ctypes.POINTER(vp), vp, i64, f, f, vp, i, i, i64, i, vp],
         "gnnmp_hetero_propagate_f32": [ctypes.POINTER(HeteroDst), i, i64, vp],
         "gnnmp_hetero_propagate_grad_f32": [ctypes.POINTER(HeteroSrc), i, i64, vp],
+        "gnnmp_hetero_attn_f32": [ctypes.POINTER(HeteroAttnDst), i, i64, i64, vp],
         "gnnmp_coalesce_edges": [ctypes.POINTER(CoalesceJob), ctypes.POINTER(i64), vp],
         "gnnmp_compact_edges": [ctypes.POINTER(CompactJob), ctypes.POINTER(i64), vp],
         "gnnmp_has_multi_edges": [vp, vp, i, i, i64, ctypes.POINTER(i), vp],

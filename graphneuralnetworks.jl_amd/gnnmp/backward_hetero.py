@@ -16,7 +16,8 @@ when knob 22 (KNOB_HETERO) is negative: the A/B baseline.
 
   hetero_propagate_grad(g, dy, ...)     {node_t: Δx} of hetero_propagate(..., combine = "+")
   hetero_propagate_ad(g, x, ...)        differentiable hetero_propagate: gradients to x, root and the edge weights
-  hetero_conv_ad(layer, g, x)           differentiable HeteroGraphConv of GraphConv / SAGEConv members, σ in identity, relu
+  hetero_conv_ad(layer, g, x)           differentiable HeteroGraphConv of GraphConv / SAGEConv members, σ in identity, relu — or of GATConv /
+                                        GATv2Conv members (gnnmp/hetero_attn.py)
 
 Out of scope: Float64, `batch` of heterographs, a fused ΔW.
 """
@@ -342,7 +343,17 @@ class _HeteroConvFn(torch.autograd.Function):
 
 def hetero_conv_ad(layer, g: GNNHeteroGraph, x):
     """differentiable HeteroGraphConv forward of GraphConv / SAGEConv members with σ in identity, relu: gradients w.r.t. every x[node_t]
-    and every member's weights and bias (SAGEConv: l.weight, through its [W_root W_agg] column-block views).  Returns {dst_t: y}."""
+    and every member's weights and bias (SAGEConv: l.weight, through its [W_root W_agg] column-block views).  Returns {dst_t: y}.
+    A layer whose members are ALL GATConv / GATv2Conv is differentiable too (gnnmp/hetero_attn.py: hetero_attn_conv_ad); one that mixes
+    attention members with GraphConv / SAGEConv members is refused here (its forward runs, through the composition)."""
+    from .hetero_attn import hetero_attn_conv_ad, is_attention_layer
+    attn = [is_attention_layer(l) for l in layer.layers]
+    if any(attn):
+        if not all(attn):
+            names = sorted({type(l).__name__ for l in layer.layers})
+            raise NotImplementedError(f"hetero_conv_ad: a layer that mixes attention members with GraphConv / SAGEConv members is not "
+                                      f"differentiable here (members: {', '.join(names)})")
+        return hetero_attn_conv_ad(layer, g, x)
     members = []
     for et, l in zip(layer.etypes, layer.layers):
         if not isinstance(l, _BIPARTITE_LAYERS):

@@ -11,7 +11,8 @@ A relation (src_t, rel, dst_t) is a bipartite COO edge index with its own cached
 num_nodes[dst_t]).  What a destination type receives over all of its relations is ONE gnnmp_hetero_propagate_f32 launch for all
 destination types (csrc/hetero.hip): the per-relation aggregates are never written.  The composition — propagate per relation, then the
 same kernel over identity relations as the combiner — runs instead when a plan has split rows, when the call exceeds the kernel's
-relation cap, or when knob 22 (KNOB_HETERO) is negative: the A/B baseline.  Forward only.
+relation cap, or when knob 22 (KNOB_HETERO) is negative: the A/B baseline.  Forward only.  GATConv / GATv2Conv members of a
+HeteroGraphConv take the attention counterpart of that launch, gnnmp_hetero_attn_f32 (gnnmp/hetero_attn.py, csrc/hetero_attn.hip).
 
 Out of scope: `batch` of heterographs, add_self_loops / add_edges on them, sparse-matrix heterographs.
 """
@@ -434,10 +435,15 @@ class HeteroGraphConv:
         by_dst = {}
         for et, l in zip(self.etypes, self.layers):
             by_dst.setdefault(et[2], []).append((et, l))
-        fused, outs = {}, {}
+        from .hetero_attn import Projections, fused_records, hetero_attn_batches
+        fused, outs, attn = {}, {}, {}
+        proj = Projections(x)      # a projection several relations share (same layer object, same node type) is computed once
         for dst_t, members in by_dst.items():
             plans = [g.plan(et) for et, _ in members]
-            if self._fusable(members, x) and all(p.n_long == 0 for p in plans) and len(members) + 1 <= L.HETERO_MAX_REL:
+            recs = fused_records(members, plans, proj)
+            if recs is not None:      # attention members: ONE gnnmp_hetero_attn_f32 launch per (heads, out), below
+                attn.setdefault(recs[0], []).append((dst_t, recs[1]))
+            elif self._fusable(members, x) and all(p.n_long == 0 for p in plans) and len(members) + 1 <= L.HETERO_MAX_REL:
                 # by linearity: Σ_r (W_root_r x_dst + W_agg_r A_r x_src_r + b_r) = (Σ W_root_r) x_dst + Σ b_r + Σ_r A_r (W_agg_r x_src_r)
                 W_root = bias = None
                 rels = []
@@ -454,6 +460,12 @@ class HeteroGraphConv:
             else:
                 outs[dst_t] = [self._forward(l, g, et, x) for et, l in members]
         result = {}
+        for (H, C), group in attn.items():
+            recs = []
+            for dst_t, rels in group:
+                result[dst_t] = torch.empty((g.num_nodes[dst_t], H * C), dtype=torch.float32, device=g.device)
+                recs.append((result[dst_t], g.num_nodes[dst_t], _COMBINE[self.aggr], rels))
+            hetero_attn_batches(recs, H, C)
         if fused:      # ONE launch for the fused destination types (one per output width, as far as the relation cap allows)
             recs = []
             for dst_t, rels in fused.items():
@@ -474,7 +486,8 @@ class HeteroGraphConv:
 
     @staticmethod
     def _forward(l, g, et, x):
-        if not isinstance(l, _BIPARTITE_LAYERS):
+        from .hetero_attn import is_attention_layer
+        if not isinstance(l, _BIPARTITE_LAYERS) and not is_attention_layer(l):
             raise NotImplementedError(f"HeteroGraphConv: {type(l).__name__} does not take a (x_src, x_dst) pair on a bipartite relation "
-                                      "(supported: GraphConv, SAGEConv)")
+                                      "(supported: GraphConv, SAGEConv, GATConv, GATv2Conv)")
         return l(edge_type_subgraph(g, et), (x[et[0]], x[et[2]]))

@@ -369,7 +369,11 @@ def dropout_keep(seed, p, n_edges, heads, device="cuda"):
 def gat_conv(l, g: GNNGraph, x, e=None, return_alpha=False, exact_order=False, seed=None):
     """GNNlib/src/layers/conv.jl:112-167 (no edge features: dense_e === nothing).  dense_x GEMM -> node scores ->
     one fused edge-softmax + weighted aggregate over the (self-looped) plan.  l.dropout > 0: `α = dropout(α, l.dropout)` (conv.jl:139)
-    inside the same kernel; `seed` (default: the layer's next seed, see GATConv.next_seed) defines the mask."""
+    inside the same kernel; `seed` (default: the layer's next seed, see GATConv.next_seed) defines the mask.
+    x = (x_src, x_dst) on a one-relation heterograph: gnnmp/hetero_attn.py."""
+    if isinstance(x, (tuple, list)):
+        from .hetero_attn import gat_conv_pair
+        return gat_conv_pair(l, g, x, e, return_alpha, exact_order)
     check_num_nodes(g, x)
     dense_e = getattr(l, "dense_e_weight", None)
     assert not (e is None and dense_e is not None), "Input edge features required for this layer"

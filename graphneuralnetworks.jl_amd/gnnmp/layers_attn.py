@@ -86,7 +86,11 @@ def _heads_tail(out, l, N, H, C):
 def gatv2_conv(l, g: GNNGraph, x, e=None, seed=None):
     """conv.jl:171-214: logα = sum(a .* leakyrelu.(Wxi + Wxj [+ dense_e(e)])), softmax over the neighbourhood,
     `α = dropout(α, l.dropout)` (:191, inside the kernel; `seed` defaults to the layer's next one), weighted sum of Wxj, optional
-    head mean, σ.(x .+ bias).  With `e` the edge row enters the logit inside the kernel of csrc/attn_edge.hip (no dropout there)"""
+    head mean, σ.(x .+ bias).  With `e` the edge row enters the logit inside the kernel of csrc/attn_edge.hip (no dropout there).
+    x = (x_src, x_dst) on a one-relation heterograph: gnnmp/hetero_attn.py."""
+    if isinstance(x, (tuple, list)):
+        from .hetero_attn import gatv2_conv_pair
+        return gatv2_conv_pair(l, g, x, e)
     check_num_nodes(g, x)
     assert not (e is None and l.dense_e_weight is not None), "Input edge features required for this layer"
     assert not (e is not None and l.dense_e_weight is None), "Input edge features were not specified in the layer constructor"

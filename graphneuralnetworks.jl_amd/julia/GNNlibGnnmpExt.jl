@@ -1090,4 +1090,36 @@ function random_walk_pe(g::GNNGraph{<:COO_T}, walk_length::Int)
     return out
 end
 
+# ---- heterograph attention (GraphNeuralNetworks/src/layers/heteroconv.jl:57-86 over gat_conv / gatv2_conv, conv.jl:112-214) -----------
+# One launch finishes every destination row over all of its incoming attention relations (gnnmp.h: gnnmp_hetero_attn_f32).  The records
+# are gnnmp_hetero_attn_rel_t and gnnmp_hetero_attn_dst_t, field for field; the tables are host arrays that the call copies into the
+# kernel arguments.  Like the rest of this file: written against the reference's sources, never executed.
+struct HeteroAttnRel
+    plan::Ptr{Cvoid}
+    mode::Cint
+    Q::Ptr{Cvoid}
+    K::Ptr{Cvoid}
+    a::Ptr{Cvoid}
+    bias::Ptr{Cvoid}
+    stats::Ptr{Cvoid}
+    negative_slope::Cfloat
+    act::Cint
+end
+struct HeteroAttnDst
+    out::Ptr{Cvoid}
+    n_dst::Int64
+    combine::Cint
+    n_rel::Cint
+    rels::Ptr{HeteroAttnRel}
+end
+# dsts: one (out, combine code, Vector{HeteroAttnRel}) per destination type, out a (H * C, n_dst) ROCMatrix{Float32}
+function hetero_attn!(dsts::Vector, H::Int, C::Int)
+    tabs = [rels for (_, _, rels) in dsts]
+    GC.@preserve tabs dsts begin
+        recs = [HeteroAttnDst(devptr(out), Int64(size(out, 2)), Cint(combine), Cint(length(rels)), pointer(rels)) for (out, combine, rels) in dsts]
+        check(@ccall libgnnmp.gnnmp_hetero_attn_f32(recs::Ptr{Cvoid}, length(recs)::Cint, H::Int64, C::Int64, stream_ptr()::Ptr{Cvoid})::Cint)
+    end
+    return nothing
+end
+
 end # module

@@ -1429,6 +1429,56 @@ typedef struct {
 int gnnmp_hetero_propagate_grad_f32(const gnnmp_hetero_src_t *srcs, int n_srcs, int64_t D, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Heterograph attention: GATConv / GATv2Conv members of a HeteroGraphConv in ONE launch (csrc/hetero_attn.hip) — what
+ * GraphNeuralNetworks/src/layers/heteroconv.jl:57-86 composes from gat_conv / gatv2_conv on a relation through expand_srcdst
+ * (GNNlib/src/layers/conv.jl:112-214).  For every destination type d of the call and every row i < n_dst:
+ *     out_d[i]     = foldl(combine_d, term_1[i], ..., term_R[i])         table order; the first term is copied, not folded into a zero
+ *     term_r[i]    = act_r(o_r[i] + bias_r)
+ *     o_r[i][h]    = sum_j softmax_{j in N_r(i)}(l_ij[h]) K_j[h]
+ *     l_ij[h]      = GNNMP_ATTN_GAT:   leakyrelu(a[h][0:C] . Q_i[h] + a[h][C:2C] . K_j[h])
+ *                    GNNMP_ATTN_GATV2: sum_c a[h][c] leakyrelu(Q_ic + K_jc)                 (the logits of gnnmp_attn_conv_f32)
+ * A row without an in-edge in relation r has o_r = 0 and statistics (-Inf, 0), as gnnmp_attn_conv_edge_f32 documents.  A lane group owns
+ * one destination row: per relation it walks the row whole with an online softmax, finishes term_r in registers, writes stats_r if asked,
+ * folds into the running value and stores the row once after the last relation; the terms are never written.
+ *   gnnmp_hetero_attn_rel_t  plan: the relation's plan (n_dst = the record's; built without self loops), or NULL = an IDENTITY relation that
+ *                            contributes row i of K [n_dst][H*C] as it is (mode, Q, a, bias, stats, act are then ignored, act must still be
+ *                            valid).  mode: GNNMP_ATTN_GAT | GNNMP_ATTN_GATV2.  Q [n_dst][H*C] (GAT: Wx_dst; GATV2: dense_i(x_dst)),
+ *                            K [n_src][H*C] (GAT: Wx_src; GATV2: dense_j(x_src); also the value), a: GAT [H][2C] (target half first),
+ *                            GATV2 [H][C]; bias [H*C] or NULL; stats [n_dst][H][2] = (m_i, den_i) as gnnmp_gat_conv_stats_f32 writes them,
+ *                            or NULL; act: GNNMP_ACT_IDENTITY | GNNMP_ACT_RELU.
+ *   gnnmp_hetero_attn_dst_t  out [n_dst][H*C], combine: GNNMP_SUM | GNNMP_MAX | GNNMP_MIN, n_rel >= 1 records.
+ * `dsts` and every `rels` are HOST arrays; the tables travel by value in the kernel arguments.  The call neither allocates nor
+ * synchronises, uses no atomics and no plan-owned scratch (plans are only read), may be recorded into a HIP graph without an eager call
+ * first, and two calls give equal bits.  The feature row must fit one wave under the rule of gnnmp_gat_conv_stats_f32: out and every Q
+ * and K of the call are the [.][H*C] arrays whose alignment selects v.  An R-relation call has the bits of the R single-relation calls
+ * folded in table order with one fp32 + / max / min each.  A row longer than the plan's long-row threshold is walked whole by its lane
+ * group: correct, slow (a caller with split rows runs the relations one by one).
+ * Refused before any HIP call: GNNMP_EINVAL for a NULL or empty table, H or C < 1, a bad combine / mode / act, a NULL pointer that would
+ * be dereferenced, a plan whose n_dst is not the record's, a plan with self loops of its own; GNNMP_EUNSUPPORTED for more than
+ * GNNMP_HETERO_MAX_REL records in one call (all destination types together) and for a feature row that does not fit one wave at the v
+ * the pointers allow.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const gnnmp_graph_t *plan;
+    int mode;
+    const float *Q;
+    const float *K;
+    const float *a;
+    const float *bias;
+    float *stats;
+    float negative_slope;
+    int act;
+} gnnmp_hetero_attn_rel_t;
+typedef struct {
+    float *out;
+    int64_t n_dst;
+    int combine;
+    int n_rel;
+    const gnnmp_hetero_attn_rel_t *rels;
+} gnnmp_hetero_attn_dst_t;
+int gnnmp_hetero_attn_f32(const gnnmp_hetero_attn_dst_t *dsts, int n_dsts, int64_t H, int64_t C, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * EdgeConv with a one-layer nn, forward and pullback — edge_conv, GNNlib/src/layers/conv.jl:237-246:
  *   propagate(edge_conv_message, g, l.aggr; xi = x, xj = x),  edge_conv_message(l, xi, xj, e) = l.nn(vcat(xi, xj .- xi))
  * For nn = Dense(2D => C, σ) with W = [W1 | W2]:  nn(vcat(xi, xj - xi)) = σ(W1 xi + b - W2 xi + W2 xj), so the contraction is ONE dense
