@@ -19,6 +19,23 @@
 // Neither the host nor the launch shape knows the graph sizes (that would need a synchronisation): both kernels are launched over node
 // tiles and find their work from graph_ptr.  O(n_g^2) compares a graph — see DESIGN.md §5 for where that loses to a sort.
 //
+// gnnmp_topk_select_radix_f32 writes the same keep words without the n^2: it finds the THRESHOLD key T of rank k_g - 1 by an MSD radix
+// select over the 32-bit key (8 bits a pass, 4 passes) and keeps key > T, and of the nodes with key == T the first
+// need = k_g - #{key > T} by node id (FIRST) or all of them (ALL).  Three routes by the node count n of a member graph:
+//   small   n <= count_nodes             topk_lds_kernel above, unchanged: counting beats four passes at 20 keys a graph
+//   mid     count_nodes < n <= lds_nodes  one workgroup a graph (the one that owns the 256-node tile the graph starts in): keys loaded
+//                                        into LDS once; a pass is an LDS histogram of the keys that still match the prefix (integer
+//                                        LDS atomics), a suffix scan of the 256 bins in one wave (four bins a lane, __shfl_down) and
+//                                        the pick of the digit where the running count crosses the remaining k
+//   tiled   n > lds_nodes                the batch's node range is cut into tiles of GNNMP_TOPK_RADIX_TILE nodes.  A pass is two launches:
+//                                        every tile's workgroup stores the histogram of its keys of a tiled graph to the workspace; the
+//                                        workgroup of the tile a graph STARTS in adds the graph's tile histograms, picks the digit and
+//                                        stores (prefix, remaining k) beside that tile's histograms.  A last launch writes keep.
+// eq_before_i = #{ j < i : key_j == T } is a ballot / popcount inside a wave, a walk over the wave totals inside a workgroup, and on the
+// tiled route the sum of bin T & 255 of the last pass's histograms of the graph's earlier tiles (those bins ARE the tiles' counts of
+// key == T).  Two invariants, not tuning: a tiled graph is longer than a tile (lds_nodes >= the tile), so a tile touches at most two of
+// them — the tail of one (slot 0) and one that starts inside it (slot 1) — and at most one starts in a tile (its state slot).
+//
 // The row kernels (score, gate, gate pullback) give a row L lanes, L = the power of two >= min(C, 64): lane l takes the channels
 // c = l, l + L, ... in ascending order, then the L partial sums fold in a butterfly (xor L/2, ..., 1).  No atomics anywhere.
 #include <algorithm>
@@ -80,10 +97,14 @@ __device__ __forceinline__ void topk_count(uint32_t ki, int64_t i, const uint32_
         eqb += (kj == ki && j0 + t < i) ? 1u : 0u;
     }
 }
-__device__ __forceinline__ void topk_emit(const TopkArgs &a, int64_t i, int64_t n, uint32_t gt, uint32_t eqb) {
+// k_g of a member graph of n nodes (one definition for the counting and the radix export)
+__device__ __forceinline__ int64_t topk_kg(const TopkArgs &a, int64_t n) {
     int64_t kg = a.k;
     if (a.k == 0) kg = (int64_t)ceil(a.ratio * (double)n);
-    if (kg > n) kg = n;
+    return kg > n ? n : kg;
+}
+__device__ __forceinline__ void topk_emit(const TopkArgs &a, int64_t i, int64_t n, uint32_t gt, uint32_t eqb) {
+    const int64_t kg = topk_kg(a, n);
     const uint32_t rank = gt + eqb;
     a.keep[i] = (int64_t)(a.ties == GNNMP_TOPK_TIES_FIRST ? rank : gt) < kg ? 1u : 0u;
     if (a.rank) a.rank[i] = (int32_t)rank;
@@ -152,6 +173,217 @@ __global__ void __launch_bounds__(TOPK_BLOCK) topk_dev_kernel(const TopkArgs a) 
             __syncthreads();
         }
         if (mine) topk_emit(a, i, hi - lo, gt, eqb);
+    }
+}
+
+// ---- radix selection -------------------------------------------------------------------------------------------------------------------
+constexpr int RADIX_TILE = GNNMP_TOPK_RADIX_TILE;   // nodes of a tile of the tiled route
+constexpr int RADIX_BLOCK = 256;                    // threads of the tiled route's kernels: one a bin
+constexpr int RADIX_MID_BLOCK = 1024;               // threads of the mid route's workgroup
+constexpr int RADIX_BINS = 256;                     // 8 bits a pass
+constexpr int RADIX_TILE_WORDS = 2 * RADIX_BINS + 4;      // workspace of a tile: histogram slot 0, slot 1, (prefix, remaining k, 0, 0)
+constexpr int64_t RADIX_LDS_NODES = 15872;          // 62 KB of keys beside the 1.1 KB of static LDS: no opt-in above 64 KB is needed
+static_assert(RADIX_BLOCK == RADIX_BINS && RADIX_TILE % RADIX_BLOCK == 0 && RADIX_LDS_NODES >= RADIX_TILE, "radix geometry");
+
+struct RadixArgs {
+    TopkArgs t;             // t.cap = count_nodes: the graphs of at most that many nodes are topk_lds_kernel's
+    int64_t hi_n;           // lds_nodes (>= RADIX_TILE, >= t.cap): the graphs above it are the tiled route's
+    uint32_t *ws;           // [n_tiles][RADIX_TILE_WORDS]
+};
+
+// wave 0, all 64 lanes: the digit d with #{keys in bins above d} < rem <= #{keys in bins d and above} -> sel[0] = d, sel[1] = rem - #{above}
+__device__ __forceinline__ void radix_pick(const uint32_t *hist, uint32_t rem, int lane, uint32_t *sel) {
+    uint32_t c[4], tot = 0;
+    for (int q = 0; q < 4; ++q) {
+        c[q] = hist[4 * lane + q];
+        tot += c[q];
+    }
+    uint32_t v = tot;                                   // -> the count of the bins of this lane and of every higher lane
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_down(v, o, 64);
+        if (lane + o < 64) v += u;
+    }
+    uint32_t above = v - tot;
+    if (lane == 0) {                                    // (only a graph_ptr that does not ascend leaves these in place)
+        sel[0] = 0u;
+        sel[1] = 1u;
+    }
+    for (int q = 3; q >= 0; --q) {
+        if (above < rem && rem <= above + c[q]) {
+            sel[0] = (uint32_t)(4 * lane + q);
+            sel[1] = rem - above;
+        }
+        above += c[q];
+    }
+}
+// one round of blockDim.x consecutive nodes, thread t the t-th: #{ earlier nodes of the graph with key == T } of this thread's node;
+// base (the count of the rounds before, uniform) moves on by the round's total.  Every thread of the workgroup calls it: two barriers
+template <int NW>
+__device__ __forceinline__ uint32_t radix_eq_before(bool iseq, uint32_t *s_wtot, uint32_t &base) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(iseq);
+    if (lane == 0) s_wtot[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t before = base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < NW; ++w) {
+        const uint32_t c = s_wtot[w];
+        total += c;
+        if (w < wave) before += c;
+    }
+    base += total;
+    __syncthreads();
+    return before;
+}
+
+// mid route: workgroup b owns the graphs of count_nodes < n <= lds_nodes that start in nodes [b * TOPK_TILE, (b + 1) * TOPK_TILE)
+__global__ void __launch_bounds__(RADIX_MID_BLOCK) topk_radix_lds_kernel(const RadixArgs a) {
+    extern __shared__ uint32_t radix_keys[];
+    __shared__ uint32_t s_hist[RADIX_BINS], s_wtot[RADIX_MID_BLOCK / 64], s_sel[2];
+    const TopkArgs &t = a.t;
+    const int tid = threadIdx.x;
+    const int64_t tile_lo = (int64_t)blockIdx.x * TOPK_TILE, tile_hi = min(t.N, tile_lo + (int64_t)TOPK_TILE);
+    if (tile_lo >= t.N) return;
+    int64_t g = 0, ghi = t.G;                           // the first graph that starts at or after tile_lo
+    while (g < ghi) {
+        const int64_t mid = g + (ghi - g) / 2;
+        if (topk_bound(t, mid) < tile_lo) g = mid + 1; else ghi = mid;
+    }
+    // a graph longer than the tile that starts in it holds the tile's last node: the graphs before that one are the small route's
+    if (t.cap >= TOPK_TILE) g = max(g, topk_graph_of(t, tile_hi - 1, 0, t.G));
+    for (; g < t.G; ++g) {
+        const int64_t start = topk_bound(t, g);
+        if (start >= tile_hi) break;
+        const int64_t n = topk_bound(t, g + 1) - start;
+        if (n <= t.cap || n > a.hi_n) continue;
+        const int cnt = (int)n;
+        for (int i = tid; i < cnt; i += RADIX_MID_BLOCK) radix_keys[i] = topk_key(t.score[start + i]);
+        uint32_t prefix = 0u, rem = (uint32_t)topk_kg(t, n);      // the key of rank rem - 1 among the keys that match prefix
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < RADIX_BINS) s_hist[tid] = 0u;
+            __syncthreads();                            // (the keys are in LDS after the first of these)
+            const uint32_t mask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+            for (int i = tid; i < cnt; i += RADIX_MID_BLOCK) {
+                const uint32_t k = radix_keys[i];
+                if ((k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid < 64) radix_pick(s_hist, rem, tid, s_sel);
+            __syncthreads();
+            prefix |= s_sel[0] << shift;
+            rem = s_sel[1];
+        }
+        // prefix = T, rem = need = k_g - #{key > T} (1 <= need <= #{key == T})
+        const bool first = t.ties == GNNMP_TOPK_TIES_FIRST;
+        uint32_t base = 0u;
+        for (int r0 = 0; r0 < cnt; r0 += RADIX_MID_BLOCK) {
+            const int i = r0 + tid;
+            const uint32_t k = i < cnt ? radix_keys[i] : 0u;
+            const bool iseq = i < cnt && k == prefix;
+            const uint32_t eqb = first ? radix_eq_before<RADIX_MID_BLOCK / 64>(iseq, s_wtot, base) : 0u;
+            if (i < cnt) t.keep[start + i] = (k > prefix || (iseq && eqb < rem)) ? 1u : 0u;
+        }
+        __syncthreads();                                // the next graph's keys overwrite these
+    }
+}
+
+// the tiled-route graph of a slot of the tile [tile_lo, tile_hi): slot 0 the graph that holds tile_lo and starts before it, slot 1 the
+// graph that starts in the tile (longer than a tile, it holds the tile's last node).  false: the slot has none
+__device__ __forceinline__ bool radix_span(const RadixArgs &a, int slot, int64_t tile_lo, int64_t tile_hi, int64_t &start, int64_t &end) {
+    const int64_t g = topk_graph_of(a.t, slot ? tile_hi - 1 : tile_lo, 0, a.t.G);
+    start = topk_bound(a.t, g);
+    end = topk_bound(a.t, g + 1);
+    return end - start > a.hi_n && (slot ? start >= tile_lo && start < tile_hi : start < tile_lo);
+}
+__device__ __forceinline__ uint32_t *radix_tile_ws(const RadixArgs &a, int64_t tile) { return a.ws + tile * RADIX_TILE_WORDS; }
+
+// pass `shift` of the tiled route, first launch: ws[tile][slot][bin] = #{ nodes of the tile and of the slot's graph whose key matches the
+// graph's prefix and has digit bin }.  Only the slots that have a graph are written, and only those are read
+__global__ void __launch_bounds__(RADIX_BLOCK) topk_radix_hist_kernel(const RadixArgs a, int shift) {
+    __shared__ uint32_t s_hist[2][RADIX_BINS];
+    const int tid = threadIdx.x;
+    const int64_t tile_lo = (int64_t)blockIdx.x * RADIX_TILE, tile_hi = min(a.t.N, tile_lo + (int64_t)RADIX_TILE);
+    if (tile_lo >= a.t.N) return;
+    s_hist[0][tid] = 0u;
+    s_hist[1][tid] = 0u;
+    __syncthreads();
+    bool has[2];
+    for (int slot = 0; slot < 2; ++slot) {
+        int64_t start, end;
+        has[slot] = radix_span(a, slot, tile_lo, tile_hi, start, end);
+        if (!has[slot]) continue;
+        uint32_t prefix = 0u, mask = 0u;
+        if (shift != 24) {
+            prefix = radix_tile_ws(a, start / RADIX_TILE)[2 * RADIX_BINS];
+            mask = 0xffffffffu << (shift + 8);
+        }
+        const int64_t lo = max(start, tile_lo), hi = min(end, tile_hi);
+        for (int64_t i = lo + tid; i < hi; i += RADIX_BLOCK) {
+            const uint32_t k = topk_key(a.t.score[i]);
+            if ((k & mask) == prefix) atomicAdd(&s_hist[slot][(k >> shift) & 255u], 1u);
+        }
+    }
+    __syncthreads();
+    for (int slot = 0; slot < 2; ++slot)
+        if (has[slot]) radix_tile_ws(a, blockIdx.x)[slot * RADIX_BINS + tid] = s_hist[slot][tid];
+}
+
+// pass `shift`, second launch: the workgroup of the tile a tiled graph starts in adds the graph's tile histograms (ascending tiles: its
+// own slot 1, then slot 0 of the tiles after it), picks the digit and stores (prefix, remaining k) in its tile's state words
+__global__ void __launch_bounds__(RADIX_BLOCK) topk_radix_pick_kernel(const RadixArgs a, int shift) {
+    __shared__ uint32_t s_hist[RADIX_BINS], s_sel[2];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x, tile_lo = b * RADIX_TILE, tile_hi = min(a.t.N, tile_lo + (int64_t)RADIX_TILE);
+    if (tile_lo >= a.t.N) return;
+    int64_t start, end;
+    if (!radix_span(a, 1, tile_lo, tile_hi, start, end)) return;
+    uint32_t *state = radix_tile_ws(a, b) + 2 * RADIX_BINS;
+    const uint32_t prefix = shift == 24 ? 0u : state[0], rem = shift == 24 ? (uint32_t)topk_kg(a.t, end - start) : state[1];
+    const int64_t t_last = (end - 1) / RADIX_TILE;
+    uint32_t c = radix_tile_ws(a, b)[RADIX_BINS + tid];
+    for (int64_t tile = b + 1; tile <= t_last; ++tile) c += radix_tile_ws(a, tile)[tid];
+    s_hist[tid] = c;
+    __syncthreads();
+    if (tid < 64) radix_pick(s_hist, rem, tid, s_sel);
+    __syncthreads();
+    if (tid == 0) {
+        state[0] = prefix | (s_sel[0] << shift);
+        state[1] = s_sel[1];
+    }
+}
+
+// the tiled route's last launch: keep of the tile's nodes of its (at most two) tiled graphs from T and need in the graph's state words
+__global__ void __launch_bounds__(RADIX_BLOCK) topk_radix_emit_kernel(const RadixArgs a) {
+    __shared__ uint32_t s_wtot[RADIX_BLOCK / 64];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x, tile_lo = b * RADIX_TILE, tile_hi = min(a.t.N, tile_lo + (int64_t)RADIX_TILE);
+    if (tile_lo >= a.t.N) return;
+    const bool first = a.t.ties == GNNMP_TOPK_TIES_FIRST;
+    for (int slot = 0; slot < 2; ++slot) {
+        int64_t start, end;
+        if (!radix_span(a, slot, tile_lo, tile_hi, start, end)) continue;
+        const int64_t st = start / RADIX_TILE;
+        const uint32_t T = radix_tile_ws(a, st)[2 * RADIX_BINS], need = radix_tile_ws(a, st)[2 * RADIX_BINS + 1];
+        uint32_t base = 0u;
+        if (first) {
+            // #{key == T} of the graph's earlier tiles: bin T & 255 of the last pass's histograms (thread t takes tiles st + t, + 256, ...;
+            // then every thread holds the workgroup's sum)
+            uint32_t part = 0u;
+            for (int64_t tile = st + tid; tile < b; tile += RADIX_BLOCK)
+                part += radix_tile_ws(a, tile)[(tile == st ? RADIX_BINS : 0) + (T & 255u)];
+            for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o, 64);
+            if ((tid & 63) == 0) s_wtot[tid >> 6] = part;
+            __syncthreads();
+            for (int w = 0; w < RADIX_BLOCK / 64; ++w) base += s_wtot[w];
+            __syncthreads();
+        }
+        const int64_t lo = max(start, tile_lo), hi = min(end, tile_hi);
+        for (int64_t r0 = lo; r0 < hi; r0 += RADIX_BLOCK) {
+            const int64_t i = r0 + tid;
+            const uint32_t k = i < hi ? topk_key(a.t.score[i]) : 0u;
+            const bool iseq = i < hi && k == T;
+            const uint32_t eqb = first ? radix_eq_before<RADIX_BLOCK / 64>(iseq, s_wtot, base) : 0u;
+            if (i < hi) a.t.keep[i] = (k > T || (iseq && eqb < need)) ? 1u : 0u;
+        }
     }
 }
 
@@ -346,6 +578,71 @@ int gnnmp_topk_select_f32(const gnnmp_topk_t *job, int64_t N, gnnmp_stream_t str
     if (N > a.cap) {      // some member graph may be above the budget
         topk_dev_kernel<<<nblk(N, TOPK_TILE), TOPK_BLOCK, 0, stream>>>(a);
         GNNMP_LAUNCH_CHECK("topk_dev_kernel");
+    }
+    return GNNMP_OK;
+}
+
+int64_t gnnmp_topk_select_radix_workspace(int64_t N) {
+    if (N <= (int64_t)RADIX_TILE) return 0;      // no graph is longer than a tile: none is on the tiled route
+    return (N + RADIX_TILE - 1) / RADIX_TILE * (int64_t)(RADIX_TILE_WORDS * sizeof(uint32_t));
+}
+
+int gnnmp_topk_select_radix_f32(const gnnmp_topk_radix_t *job, int64_t N, gnnmp_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!job) return fail(GNNMP_EINVAL, "topk_select_radix: null job");
+    if (N < 0) return fail(GNNMP_EINVAL, "topk_select_radix: negative N");
+    if (N >= (int64_t)INT32_MAX) return fail(GNNMP_EUNSUPPORTED, "topk_select_radix: N = %lld (limit 2^31 - 2)", (long long)N);
+    if (job->idx_bytes != 4 && job->idx_bytes != 8) return fail(GNNMP_EINVAL, "topk_select_radix: idx_bytes %d", job->idx_bytes);
+    if (job->graph_ptr && job->n_graphs < 1)
+        return fail(GNNMP_EINVAL, "topk_select_radix: n_graphs %lld with a graph_ptr", (long long)job->n_graphs);
+    if (job->k < 0) return fail(GNNMP_EINVAL, "topk_select_radix: k = %lld (k >= 1, or 0 with a ratio)", (long long)job->k);
+    if (job->k == 0 && !(job->ratio > 0.0f && job->ratio <= 1.0f))
+        return fail(GNNMP_EINVAL, "topk_select_radix: ratio %g outside (0, 1]", (double)job->ratio);
+    if (job->ties != GNNMP_TOPK_TIES_FIRST && job->ties != GNNMP_TOPK_TIES_ALL)
+        return fail(GNNMP_EINVAL, "topk_select_radix: ties %d", job->ties);
+    if (job->count_nodes < 0 || job->lds_nodes < 0)
+        return fail(GNNMP_EINVAL, "topk_select_radix: negative count_nodes or lds_nodes");
+    if (!job->keep) return fail(GNNMP_EINVAL, "topk_select_radix: null keep");
+    if (N > 0 && !job->score) return fail(GNNMP_EINVAL, "topk_select_radix: null score");
+    RadixArgs a;
+    a.t.score = job->score;
+    a.t.graph_ptr = job->graph_ptr;
+    a.t.idx_bytes = job->idx_bytes;
+    a.t.G = job->graph_ptr ? job->n_graphs : 1;
+    a.t.N = N;
+    a.t.k = job->k;
+    a.t.ratio = (double)job->ratio;
+    a.t.ties = job->ties;
+    a.t.cap = job->count_nodes == 0 ? TOPK_LDS_DEFAULT / 4 : std::min(job->count_nodes, TOPK_LDS_MAX / 4);
+    a.t.keep = job->keep;
+    a.t.rank = nullptr;
+    a.hi_n = job->lds_nodes == 0 ? RADIX_LDS_NODES : std::min(std::max<int64_t>(job->lds_nodes, RADIX_TILE), RADIX_LDS_NODES);
+    a.hi_n = std::max(a.hi_n, a.t.cap);          // (every size has exactly one route)
+    a.ws = job->workspace;
+    const bool tiled = N > a.hi_n;               // some member graph may be on the tiled route
+    if (tiled && (!job->workspace || job->workspace_bytes < gnnmp_topk_select_radix_workspace(N)))
+        return fail(GNNMP_EINVAL, "topk_select_radix: workspace %s, %lld bytes (N = %lld needs %lld)", job->workspace ? "given" : "NULL",
+                    (long long)job->workspace_bytes, (long long)N, (long long)gnnmp_topk_select_radix_workspace(N));
+    // one graph: its size is known here, so only its route is launched (the counting kernel always is: it closes keep[N])
+    const bool one = !job->graph_ptr;
+    TopkArgs small = a.t;
+    if (one && N > a.t.cap) small.cap = 0;
+    topk_lds_kernel<<<one ? 1u : nblk(N, TOPK_TILE), TOPK_BLOCK, (size_t)std::max<int64_t>(small.cap, 1) * sizeof(uint32_t), stream>>>(small);
+    GNNMP_LAUNCH_CHECK("topk_lds_kernel");
+    if (N > a.t.cap && !(one && tiled)) {
+        topk_radix_lds_kernel<<<one ? 1u : nblk(N, TOPK_TILE), RADIX_MID_BLOCK, (size_t)std::min(a.hi_n, N) * sizeof(uint32_t), stream>>>(a);
+        GNNMP_LAUNCH_CHECK("topk_radix_lds_kernel");
+    }
+    if (tiled) {
+        const unsigned tiles = nblk(N, RADIX_TILE);
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            topk_radix_hist_kernel<<<tiles, RADIX_BLOCK, 0, stream>>>(a, shift);
+            GNNMP_LAUNCH_CHECK("topk_radix_hist_kernel");
+            topk_radix_pick_kernel<<<tiles, RADIX_BLOCK, 0, stream>>>(a, shift);
+            GNNMP_LAUNCH_CHECK("topk_radix_pick_kernel");
+        }
+        topk_radix_emit_kernel<<<tiles, RADIX_BLOCK, 0, stream>>>(a);
+        GNNMP_LAUNCH_CHECK("topk_radix_emit_kernel");
     }
     return GNNMP_OK;
 }

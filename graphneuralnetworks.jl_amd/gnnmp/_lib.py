@@ -66,6 +66,7 @@ SYMBOLS = (
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
     "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32",
     "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
+    "gnnmp_topk_select_radix_f32", "gnnmp_topk_select_radix_workspace",
     "gnnmp_gat_conv_edge_stats_f32", "gnnmp_gat_conv_edge_grad_f32", "gnnmp_gat_edge_fold_f32", "gnnmp_gat_edge_fold_grad_f32",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
@@ -151,6 +152,7 @@ class PprJob(ctypes.Structure):
 TOPK_TIES_FIRST, TOPK_TIES_ALL = 0, 1                                    # include/gnnmp.h: GNNMP_TOPK_TIES_*
 TOPK_ACT_SIGMOID, TOPK_ACT_TANH, TOPK_ACT_IDENTITY = 0, 1, 2             # include/gnnmp.h: GNNMP_TOPK_ACT_*
 TOPK_GRAD_ROWS = 64                                                      # include/gnnmp.h: GNNMP_TOPK_GRAD_ROWS
+TOPK_RADIX_TILE = 2048                                                   # include/gnnmp.h: GNNMP_TOPK_RADIX_TILE
 
 
 class TopkJob(ctypes.Structure):
@@ -158,6 +160,13 @@ class TopkJob(ctypes.Structure):
     _fields_ = [("score", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
                 ("k", ctypes.c_int64), ("ratio", ctypes.c_float), ("ties", ctypes.c_int), ("lds_budget_bytes", ctypes.c_int64),
                 ("keep", ctypes.c_void_p), ("rank", ctypes.c_void_p)]
+
+
+class TopkRadixJob(ctypes.Structure):
+    """gnnmp_topk_radix_t: one gnnmp_topk_select_radix_f32 call (workspace: gnnmp_topk_select_radix_workspace(N) bytes)"""
+    _fields_ = [("score", ctypes.c_void_p), ("graph_ptr", ctypes.c_void_p), ("idx_bytes", ctypes.c_int), ("n_graphs", ctypes.c_int64),
+                ("k", ctypes.c_int64), ("ratio", ctypes.c_float), ("ties", ctypes.c_int), ("count_nodes", ctypes.c_int64),
+                ("lds_nodes", ctypes.c_int64), ("keep", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
 
 
 class TopkGateJob(ctypes.Structure):
@@ -553,6 +562,7 @@ def load():
         "gnnmp_plan_keep_nodes": [ctypes.POINTER(vp), vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp],
         "gnnmp_topk_score_f32": [vp, vp, vp, i64, i64, vp],
         "gnnmp_topk_select_f32": [ctypes.POINTER(TopkJob), i64, vp],
+        "gnnmp_topk_select_radix_f32": [ctypes.POINTER(TopkRadixJob), i64, vp],
         "gnnmp_topk_gate_f32": [ctypes.POINTER(TopkGateJob), i64, i64, vp],
         "gnnmp_topk_gate_grad_f32": [ctypes.POINTER(TopkGateGradJob), i64, i64, vp],
         "gnnmp_gat_conv_edge_stats_f32": [vp, vp, vp, vp, vp, f, vp, i, vp, vp, i64, i64, vp],
@@ -573,6 +583,12 @@ def load():
             raise
         fn.argtypes = args
         fn.restype = i
+    try:
+        L.gnnmp_topk_select_radix_workspace.argtypes = [i64]
+        L.gnnmp_topk_select_radix_workspace.restype = i64
+    except AttributeError:
+        if not os.environ.get("GNNMP_LIB"):
+            raise
     L.gnnmp_dense_grad_workspace.argtypes = [i64, i64, i64]
     L.gnnmp_dense_grad_workspace.restype = i64
     try:

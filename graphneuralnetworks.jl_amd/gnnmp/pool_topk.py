@@ -27,6 +27,7 @@ from .transform import _idx_dtype, _node_ptr, _plain_graph, _take
 
 _ACTS = {"sigmoid": L.TOPK_ACT_SIGMOID, "tanh": L.TOPK_ACT_TANH, "identity": L.TOPK_ACT_IDENTITY}
 _TIES = {"first": L.TOPK_TIES_FIRST, "all": L.TOPK_TIES_ALL}
+_AUTO_MEAN_NODES = 256      # route "auto": the counting kernel's LDS route ends here (gnnmp_topk_select_radix_f32: count_nodes' default)
 
 
 def _k_or_ratio(v, who):
@@ -56,12 +57,31 @@ def topk_score(x, p):
     return y
 
 
-def topk_select(y, k=0, ratio=0.0, g=None, ties="first", want_rank=False, lds_budget_bytes=0):
-    """(keep int32 [N + 1] with keep[N] = 0, rank int32 [N] | None) of gnnmp_topk_select_f32; with a batched g, per member graph"""
+def topk_select(y, k=0, ratio=0.0, g=None, ties="first", want_rank=False, lds_budget_bytes=0, route="auto", count_nodes=0, lds_nodes=0):
+    """(keep int32 [N + 1] with keep[N] = 0, rank int32 [N] | None); with a batched g, per member graph.
+    route "count": gnnmp_topk_select_f32 (n^2 compares a member graph; the only one with a rank); "radix": gnnmp_topk_select_radix_f32
+    (a radix select above count_nodes nodes, in LDS up to lds_nodes and over tiles above; 0 = the export's defaults) — the same keep
+    words.  "auto": radix when no rank is wanted, no LDS budget is given and some member graph is certainly above the counting kernel's
+    256 nodes — N > 256 * num_graphs, the largest member being at least the mean (the host knows no more of the sizes).  A batch of
+    small graphs stays on the two launches of "count": the radix export launches up to eleven."""
+    if route not in ("auto", "count", "radix"):
+        raise ValueError(f"topk_select: route {route!r} (expected 'auto', 'count' or 'radix')")
     N = y.numel()
-    keep = torch.empty(N + 1, dtype=torch.int32, device=y.device)      # (the export's uint32 words: 0 | 1)
-    rank = torch.empty(N, dtype=torch.int32, device=y.device) if want_rank else None
     sp = None if g is None else _node_ptr(g)
+    if route == "auto":
+        large = N > _AUTO_MEAN_NODES * (g.num_graphs if sp is not None else 1)
+        route = "radix" if large and not want_rank and not lds_budget_bytes else "count"
+    elif route == "radix" and (want_rank or lds_budget_bytes):
+        raise ValueError("topk_select: the radix route has no rank output and no LDS budget (route='count' has both)")
+    keep = torch.empty(N + 1, dtype=torch.int32, device=y.device)      # (the export's uint32 words: 0 | 1)
+    if route == "radix":
+        nbytes = L.load().gnnmp_topk_select_radix_workspace(N)
+        ws = torch.empty(nbytes // 4, dtype=torch.int32, device=y.device) if nbytes else None
+        job = L.TopkRadixJob(L.ptr(y), L.ptr(sp), 8, g.num_graphs if sp is not None else 1, int(k), float(ratio), _TIES[ties],
+                             int(count_nodes), int(lds_nodes), L.ptr(keep), L.ptr(ws), nbytes)
+        L.check(L.load().gnnmp_topk_select_radix_f32(ctypes.byref(job), N, L.stream_ptr()))
+        return keep, None
+    rank = torch.empty(N, dtype=torch.int32, device=y.device) if want_rank else None
     job = L.TopkJob(L.ptr(y), L.ptr(sp), 8, g.num_graphs if sp is not None else 1, int(k), float(ratio), _TIES[ties],
                     int(lds_budget_bytes), L.ptr(keep), L.ptr(rank))
     L.check(L.load().gnnmp_topk_select_f32(ctypes.byref(job), N, L.stream_ptr()))

@@ -2313,8 +2313,9 @@ int gnnmp_outer_accum_f32(const gnnmp_outer_accum_t *job, int64_t T, int64_t R, 
  *     y = p' * X / norm(p);  idx = topk_index(y, k);  A~ = view(A, idx, idx);  X_ = view(X, :, idx) .* σ.(view(y, idx)')
  * The reference pools one graph held as a dense matrix.  Here the unit is a batch: selection is per member graph, the child graph's plan
  * comes from gnnmp_plan_keep_nodes (above) with the keep flags of the selection, and the gate and its pullback are row kernels.  Float32,
- * device pointers, the caller owns every array.  The four calls of this section only launch on `stream`: no host wait, nothing taken
- * from a pool, no atomics; each may be recorded into a HIP graph without an eager call first; two calls give equal bits.
+ * device pointers, the caller owns every array.  The calls of this section that take a stream only launch on it: no host wait, nothing
+ * taken from a pool, no atomics on device memory; each may be recorded into a HIP graph without an eager call first; two calls give
+ * equal bits.
  *
  * The row kernels give a row of C floats L lanes, L = the power of two >= min(C, 64): lane l adds the channels c = l, l + L, l + 2L, ...
  * in ascending order, each product rounded before it is added, and the L partial sums fold in a butterfly (lane ^ L/2, ..., lane ^ 1).
@@ -2337,6 +2338,7 @@ int gnnmp_outer_accum_f32(const gnnmp_outer_accum_t *job, int64_t T, int64_t R, 
 #define GNNMP_TOPK_ACT_TANH 1
 #define GNNMP_TOPK_ACT_IDENTITY 2
 #define GNNMP_TOPK_GRAD_ROWS 64
+#define GNNMP_TOPK_RADIX_TILE 2048
 
 /* y[i] = (sum_c p[c] * x[i][c]) / norm(p) for x [N][C] row-major, p [C], y [N]  (pool.jl:15).  The row sum and norm(p) in the association
  * stated above; norm(p) is computed inside the kernel from p on the device (no host read of p).  norm(p) = 0 gives what IEEE division
@@ -2376,6 +2378,55 @@ typedef struct {
     int32_t *rank;
 } gnnmp_topk_t;
 int gnnmp_topk_select_f32(const gnnmp_topk_t *job, int64_t N, gnnmp_stream_t stream);
+
+/* One gnnmp_topk_select_radix_f32 call (the comment stands in front of the function). */
+typedef struct {
+    const float *score;
+    const void *graph_ptr;
+    int idx_bytes;
+    int64_t n_graphs;
+    int64_t k;
+    float ratio;
+    int ties;
+    int64_t count_nodes;
+    int64_t lds_nodes;
+    uint32_t *keep;
+    uint32_t *workspace;
+    int64_t workspace_bytes;
+} gnnmp_topk_radix_t;
+/* The same selection without the n^2 (topk_index, pool.jl:14-27, per member graph): for every input, keep[0 .. N] holds the SAME WORDS
+ * gnnmp_topk_select_f32 writes for the same score, graph_ptr, k, ratio and ties — both tie modes, NaN as the lowest key, -0.0 as +0.0,
+ * infinities and subnormals, empty member graphs, k_g >= n_g (all kept), keep[N] = 0, a NULL graph_ptr, 4- and 8-byte offsets.  There is
+ * no rank output (a full rank is a sort: gnnmp_topk_select_f32 has it).  The threshold key T of rank k_g - 1 is found by an MSD radix
+ * select over the 32-bit key, 8 bits a pass: per pass a 256-bin histogram of the keys that still match the prefix, a suffix scan of the
+ * bins, and the digit where the running count crosses the remaining k.  Then need = k_g - #{key > T}, and
+ *     FIRST  keep[i] = key_i > T || (key_i == T && #{ j < i : key_j == T } < need)        ALL  keep[i] = key_i >= T.
+ * A member graph of n nodes takes one of three routes, found from graph_ptr on the device:
+ *   n <= count_nodes               the counting kernel of gnnmp_topk_select_f32's LDS route, as it is
+ *   count_nodes < n <= lds_nodes   one workgroup a graph: the keys are loaded into LDS once, every pass reads them there
+ *   n > lds_nodes                  tiles of GNNMP_TOPK_RADIX_TILE nodes of the batch's node numbering, two launches a pass: every tile's
+ *                                  workgroup stores its histogram, then the workgroup of the tile the graph starts in adds the graph's
+ *                                  tile histograms in ascending tile order and picks the digit; a last launch writes keep, taking the
+ *                                  counts of key == T of a graph's earlier tiles from the last pass's histograms
+ *   count_nodes   0 = the default (256); values above 16384 count as 16384
+ *   lds_nodes     0 = the default (15872: the keys of one graph beside the histogram in 64 KB of LDS); larger values count as the default,
+ *                 values below GNNMP_TOPK_RADIX_TILE as GNNMP_TOPK_RADIX_TILE, values below count_nodes as count_nodes
+ *   workspace     uint32 words, workspace_bytes >= gnnmp_topk_select_radix_workspace(N)
+ *                     = 0 for N <= GNNMP_TOPK_RADIX_TILE, else ceil(N / GNNMP_TOPK_RADIX_TILE) * (2 * 256 + 4) * 4 bytes:
+ *                 per tile two histogram slots and the state words (prefix, remaining k) of the graph that starts in the tile.  Needed
+ *                 (and touched) only when N > lds_nodes; may be NULL otherwise.  Every word that is read was written earlier in the same
+ *                 call: what the workspace held before does not matter.
+ * Two invariants of the design, not tuning: lds_nodes >= GNNMP_TOPK_RADIX_TILE, so a graph of the tiled route is longer than a tile, a
+ * tile touches at most two such graphs (the tail of one, the head of the next: the two slots) and at most one starts in a tile (the one
+ * state slot).  The result does not depend on count_nodes or lds_nodes.
+ * Like the calls above it only launches on `stream`: no host wait, nothing taken from a pool or from the runtime, no memset; integer LDS
+ * atomics only (their sums do not depend on the order), none on device memory.  gnnmp_topk_select_radix_workspace is host arithmetic
+ * (no HIP call).  Refused (before any HIP call, nothing written) with GNNMP_EINVAL: job or keep NULL, score NULL with N > 0, N < 0,
+ * idx_bytes not 4 | 8, n_graphs < 1 with a graph_ptr, k < 0, k == 0 with a ratio outside (0, 1] (a NaN included), a ties value other
+ * than the two, a negative count_nodes or lds_nodes, and with N > lds_nodes a NULL workspace or workspace_bytes below the formula;
+ * N >= 2^31 - 1: GNNMP_EUNSUPPORTED. */
+int gnnmp_topk_select_radix_f32(const gnnmp_topk_radix_t *job, int64_t N, gnnmp_stream_t stream);
+int64_t gnnmp_topk_select_radix_workspace(int64_t N);
 
 /* out[r][:] = x[node_map[r]][:] * act(y[node_map[r]]) for r < n_keep  (pool.jl:25): gather and gate in one pass.
  *   x [N][C], y [N], node_map int32 [n_keep] (0-based parent ids: gnnmp_plan_keep_nodes' node_map_out; not range-checked),

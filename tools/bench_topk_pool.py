@@ -7,6 +7,10 @@ the composition a user would write without it, in one process, alternating.
     <shape>.fwdbwd.composed   the composition under torch autograd
     <shape>.select.b<bytes>   gnnmp_topk_select_f32 alone at lds_budget_bytes = 1 KB (the default), 4 KB, 16 KB and 64 KB: the figures
                               behind the default budget (a member graph above the budget takes the device-memory route)
+    <shape>.select.radix      gnnmp_topk_select_radix_f32 alone at its defaults (what the pool entries run: route "auto"); the budget entries
+                              above pass a budget and so stay on the counting route
+    one<N>.select.lds|tiled   one graph of N nodes on the radix export's one-workgroup LDS route and on its tiled route (lds_nodes = the
+                              tile): the figures behind the default lds_nodes
 ratio = 0.5, C = 64.  Shapes: `qm9`, synth.batched_graphs(G = 4096, nmin = 9, nmax = 29); `clouds`, 32 clouds x 1024 points, knn_graph
 k = 20; `arxiv`, the synth.arxiv_like hub graph, one graph (it takes the device-memory route at every budget).  Every path that builds a
 child graph synchronises the host once, so this is WALL time between two device synchronisations, after --warmup calls, median of
@@ -112,6 +116,17 @@ def shape_entries(tag, g, gen):
                (f"{tag}.fwdbwd.pool", lambda: fwdbwd_fused(l, g, x)), (f"{tag}.fwdbwd.composed", lambda: fwdbwd_composed(l, g, x))]
     for b in BUDGETS:
         entries.append((f"{tag}.select.b{b}", lambda b=b: pool_topk.topk_select(y, 0, RATIO, g, "first", lds_budget_bytes=b)))
+    entries.append((f"{tag}.select.radix", lambda: pool_topk.topk_select(y, 0, RATIO, g, "first", route="radix")))
+    return entries
+
+
+def route_entries(gen):
+    """one graph of N keys on the two radix routes that could take it"""
+    entries = []
+    for n in (4096, 8192, 15872):
+        y = torch.randn(n, generator=gen).cuda()
+        entries.append((f"one{n}.select.lds", lambda y=y: pool_topk.topk_select(y, 0, RATIO, None, "first", route="radix")))
+        entries.append((f"one{n}.select.tiled", lambda y=y: pool_topk.topk_select(y, 0, RATIO, None, "first", route="radix", lds_nodes=1)))
     return entries
 
 
@@ -134,7 +149,7 @@ def main():
     s, t = synth.arxiv_like(N=n, E=int(synth.ARXIV["E"] * n / synth.ARXIV["N"]), seed=7)
     arxiv = gnnmp.GNNGraph(torch.from_numpy(s).cuda(), torch.from_numpy(t).cuda(), num_nodes=n)
     shapes = (("qm9", qm9), ("clouds", clouds), ("arxiv", arxiv))
-    entries = [e for tag, g in shapes for e in shape_entries(tag, g, gen)]
+    entries = [e for tag, g in shapes for e in shape_entries(tag, g, gen)] + route_entries(gen)
     rounds = []
     for _ in range(args.rounds):
         rounds.append({name: timed(fn, args.reps, args.warmup) for name, fn in entries})
