@@ -68,9 +68,10 @@ SYMBOLS = (
     "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
     "gnnmp_topk_select_radix_f32", "gnnmp_topk_select_radix_workspace",
     "gnnmp_gat_conv_edge_stats_f32", "gnnmp_gat_conv_edge_grad_f32", "gnnmp_gat_edge_fold_f32", "gnnmp_gat_edge_fold_grad_f32",
+    "gnnmp_grouped_dense_f32", "gnnmp_grouped_dense_grad_w_f32", "gnnmp_grouped_dense_grad_workspace",
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
-    "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route",
+    "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route", "gnnmp_debug_grouped_dense_route",
 )
 
 
@@ -180,6 +181,20 @@ class TopkGateGradJob(ctypes.Structure):
     _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("p", ctypes.c_void_p), ("dout", ctypes.c_void_p),
                 ("node_new", ctypes.c_void_p), ("act", ctypes.c_int), ("dx", ctypes.c_void_p), ("dy", ctypes.c_void_p),
                 ("dp", ctypes.c_void_p), ("part", ctypes.c_void_p)]
+
+
+class GroupedDenseJob(ctypes.Structure):
+    """gnnmp_grouped_dense_t: one gnnmp_grouped_dense_f32 call (seg_ptr: device int64 [G + 1])"""
+    _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("W", ctypes.c_void_p), ("w_stride", ctypes.c_int64),
+                ("ldw", ctypes.c_int64), ("w_layout", ctypes.c_int), ("bias", ctypes.c_void_p), ("bias_stride", ctypes.c_int64),
+                ("seg_ptr", ctypes.c_void_p), ("act", ctypes.c_int), ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64)]
+
+
+class GroupedDenseGradJob(ctypes.Structure):
+    """gnnmp_grouped_dense_grad_t: one gnnmp_grouped_dense_grad_w_f32 call (workspace: gnnmp_grouped_dense_grad_workspace floats)"""
+    _fields_ = [("dz", ctypes.c_void_p), ("lddz", ctypes.c_int64), ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),
+                ("seg_ptr", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("dw_stride", ctypes.c_int64), ("db", ctypes.c_void_p),
+                ("db_stride", ctypes.c_int64), ("workspace", ctypes.c_void_p), ("workspace_floats", ctypes.c_int64)]
 
 
 class EdgeConvJob(ctypes.Structure):
@@ -571,6 +586,9 @@ def load():
         "gnnmp_gat_edge_fold_grad_f32": [vp, vp, vp, vp, vp, i64, i64, i64, vp],
         "gnnmp_debug_random_walk_pe_f32": [vp, ctypes.POINTER(RwpeJob), i64, vp],
         "gnnmp_debug_dense_route": [ctypes.POINTER(i)],
+        "gnnmp_grouped_dense_f32": [ctypes.POINTER(GroupedDenseJob), i64, i64, i64, i64, vp],
+        "gnnmp_grouped_dense_grad_w_f32": [ctypes.POINTER(GroupedDenseGradJob), i64, i64, i64, i64, vp],
+        "gnnmp_debug_grouped_dense_route": [ctypes.POINTER(i)],
     }
     for name, args in sig.items():
         try:
@@ -586,6 +604,12 @@ def load():
     try:
         L.gnnmp_topk_select_radix_workspace.argtypes = [i64]
         L.gnnmp_topk_select_radix_workspace.restype = i64
+    except AttributeError:
+        if not os.environ.get("GNNMP_LIB"):
+            raise
+    try:
+        L.gnnmp_grouped_dense_grad_workspace.argtypes = [i64, i64, i64, i64]
+        L.gnnmp_grouped_dense_grad_workspace.restype = i64
     except AttributeError:
         if not os.environ.get("GNNMP_LIB"):
             raise

@@ -24,7 +24,8 @@ import torch
 from . import _lib as L
 from .backward import dense_grad_w, propagate_grad_xj
 from .layers import gcn_norm_cache
-from .layers_temporal import (EvolveGCNOCell, _at, dense_rows, evolve_conv, evolve_inputs, evolve_output, evolve_state, evolve_weights)
+from .grouped import grouped_grad_launch
+from .layers_temporal import (EvolveGCNOCell, _at, evolve_conv, evolve_inputs, evolve_output, evolve_products, evolve_state, evolve_weights)
 
 
 def outer_accum(A, B, need_db=False):
@@ -121,13 +122,17 @@ class _EvolveFn(torch.autograd.Function):
         dx = None
         if need[0]:
             dpre = torch.empty((dy.shape[0], cin), **f32)
-            for t in range(T):
-                dense_rows(dz, seg[t], seg[t + 1], Wseq[t + 1], cin, out, 0, None, dpre)
+            evolve_products(cell, tg, dz, Wseq, 0, None, dpre)
             dx = dpre if w_first else PT(dpre)
-        dM = []
-        for t in range(T):
-            r0, r1 = seg[t], seg[t + 1]
-            dM.append(dense_grad_w(saved[r0:r1], dz[r0:r1], need_b=False)[0].view(D) if r1 > r0 else torch.zeros(D, **f32))
+        if cell.grouped:
+            # every ΔM_t in one gnnmp_grouped_dense_grad_w_f32, the operands swapped as below: dM [T][in][out], the flat order of Wseq
+            dM = torch.empty((T, D), **f32)
+            grouped_grad_launch(saved, cin, dz, out, tg.batched_ptr(), dM, D, None, 0, dz.shape[0], T, out, cin)
+        else:
+            dM = []
+            for t in range(T):
+                r0, r1 = seg[t], seg[t + 1]
+                dM.append(dense_grad_w(saved[r0:r1], dz[r0:r1], need_b=False)[0].view(D) if r1 > r0 else torch.zeros(D, **f32))
         want_w0 = need[1] if given else need[4]
         dw0, dh0, dc0, dWi, dWh, db = lstm_pullback(cell, Wseq, Cseq, A, dM, h0, want_w0, given and need[2], given and need[3], need[6], need[7],
                                                     lstm.b is not None and need[8])

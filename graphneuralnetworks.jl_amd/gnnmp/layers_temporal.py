@@ -665,10 +665,13 @@ class EvolveGCNOCell:
 
     takes_graph = True
 
-    def __init__(self, ch, bias=True, device="cuda", seed=None):
+    def __init__(self, ch, bias=True, device="cuda", seed=None, grouped=False):
         cin, out = ch
         if int(cin) < 1 or int(out) < 1:
             raise ValueError(f"EvolveGCNOCell: channels must be positive, got {cin} => {out}")
+        # grouped: the T products of the snapshots (and their adjoints) as ONE gnnmp_grouped_dense_f32 over the batch instead of one
+        # gnnmp_dense_f32 a snapshot.  Off by default: the per-snapshot calls and their bits stay what they are (DESIGN.md §5 has the timings)
+        self.grouped = bool(grouped)
         s = 0 if seed is None else int(seed)
         self.in_, self.out = int(cin), int(out)
         self.conv = GCNConv((self.in_, self.out), bias=bias, device=device, seed=s + 1)
@@ -695,7 +698,9 @@ class EvolveGCNOCell:
 def EvolveGCNO(ch, **kw):
     """EvolveGCNO(in => out; kws...) = GNNRecurrence(EvolveGCNOCell(...)) — temporalconv.jl:752.  layer(tg, [x_t [N_t, in]]) -> [y_t
     [N_t, out]] over a TemporalSnapshotsGNNGraph; layer(g, x [N, T, in]) -> [N, T, out] over a static graph, which runs as T copies of
-    g through the same path (one block-diagonal propagate, cached on g per T)."""
+    g through the same path (one block-diagonal propagate, cached on g per T).
+    grouped=True: the T per-snapshot products, and the 2T of the pullback, run as single gnnmp.grouped_dense calls over the batch (one
+    launch forward, two backward, whatever T is); the default keeps one gnnmp_dense_f32 a snapshot and its bits."""
     return GNNRecurrence(EvolveGCNOCell(ch, **kw))
 
 
@@ -797,6 +802,24 @@ def dense_rows(x, r0, r1, Wflat, cin, out, w_layout, bias, dst):
                                      _at(dst, r0 * Dout), r1 - r0, Dout, L.stream_ptr()))
 
 
+def evolve_products(cell, tg, x, Wseq, w_layout, bias, dst):
+    """dst[rows of snapshot t] = x[rows of snapshot t] * M_t (w_layout = 1) or * M_t' (w_layout = 0), M_t = row t + 1 of Wseq read in
+    place as [in][out] (dense_rows states the two forms): one gnnmp_dense_f32 a snapshot, or with cell.grouped ONE gnnmp_grouped_dense_f32
+    — the weights are the rows of Wseq from row 1 on, D = in out floats apart, the boundaries tg.batched_ptr()"""
+    cin, out = cell.in_, cell.out
+    T = tg.num_snapshots
+    if not cell.grouped:
+        seg = tg.batched()[1]
+        for t in range(T):
+            dense_rows(x, seg[t], seg[t + 1], Wseq[t + 1], cin, out, w_layout, bias, dst)
+        return
+    from .grouped import grouped_launch
+    K, Dout = (cin, out) if w_layout else (out, cin)
+    assert x.shape[1] == K and dst.shape[1] == Dout and x.is_contiguous() and dst.is_contiguous() and Wseq.is_contiguous()
+    grouped_launch(x, K, _at(Wseq, cin * out), cin * out, out, w_layout, bias, 0, tg.batched_ptr(), L.ACT_IDENTITY, dst, Dout,
+                   x.shape[0], T, K, Dout)
+
+
 def evolve_conv(cell, tg, xcat, Wseq):
     """(y [Σ N_t, out], agg | None): gcn_conv of every snapshot with its own weight, row t + 1 of Wseq for snapshot t.  out >= in:
     aggregate first (one propagate at width in, then T products, the bias in their epilogue; agg is what the ΔW of the pullback reads);
@@ -809,12 +832,10 @@ def evolve_conv(cell, tg, xcat, Wseq):
     if out >= cin:
         agg = gcn_propagate(gb, True, None, xcat)
         y = torch.empty((xcat.shape[0], out), **f32)
-        for t in range(T):
-            dense_rows(agg, seg[t], seg[t + 1], Wseq[t + 1], cin, out, 1, conv.bias, y)
+        evolve_products(cell, tg, agg, Wseq, 1, conv.bias, y)
         return y, agg
     u = torch.empty((xcat.shape[0], out), **f32)
-    for t in range(T):
-        dense_rows(xcat, seg[t], seg[t + 1], Wseq[t + 1], cin, out, 1, None, u)
+    evolve_products(cell, tg, xcat, Wseq, 1, None, u)
     return gcn_propagate(gb, True, None, u, bias=conv.bias), None
 
 

@@ -114,6 +114,15 @@ class TemporalSnapshotsGNNGraph:
             self._batched = (gb, seg)
         return self._batched
 
+    def batched_ptr(self):
+        """the row offsets of batched() as a device int64 tensor [T + 1] (what gnnmp.grouped_dense takes): uploaded on the first call and
+        kept beside the batch; a new batch gets a new upload"""
+        gb, seg = self.batched()
+        kept = getattr(self, "_seg_dev", None)
+        if kept is None or kept[0] is not seg:
+            kept = self._seg_dev = (seg, torch.tensor(seg, dtype=torch.int64, device=gb.device))
+        return kept[1]
+
     def __repr__(self):
         return f"TemporalSnapshotsGNNGraph({self.num_snapshots})"
 

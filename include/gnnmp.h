@@ -2470,6 +2470,79 @@ typedef struct {
 int gnnmp_topk_gate_grad_f32(const gnnmp_topk_gate_grad_t *job, int64_t N, int64_t C, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Grouped dense: one weight per row segment (csrc/dense_grouped.hip) — per-snapshot weights (EvolveGCNO, temporalconv.jl:678-705),
+ * per-member-graph or per-node-type linear maps.  With group g the rows seg_ptr[g] <= n < seg_ptr[g + 1]:
+ *     out[n][:] = act(W_g x[n][:] + b_g)                                        gnnmp_grouped_dense_f32
+ *     dW[g][o][k] = sum_{n in g} dz[n][o] x[n][k],  db[g][o] = sum_{n in g} dz[n][o]     gnnmp_grouped_dense_grad_w_f32
+ * dx = dz W_g is the forward export with w_layout flipped (x = dz, K = the forward's Dout, Dout = the forward's K), as for gnnmp_dense_f32.
+ * seg_ptr is a DEVICE array of G + 1 int64 (as gnnmp_segment_pool_ptr_f32 takes it), non-decreasing, seg_ptr[0] = 0, seg_ptr[G] = N.  The
+ * library never brings it to the host, so it cannot check it: this is the caller's contract.  (A seg_ptr that breaks it gives wrong
+ * values or unwritten rows; no row outside 0 .. N - 1 and no weight outside groups 0 .. G - 1 is touched.)  Empty groups are allowed.
+ * Both exports only launch on `stream` — no host wait, nothing taken from a pool or from the runtime, no memset, no atomics — and two
+ * calls on the same inputs give equal bits.
+ *
+ * The forward record:
+ *   x, ldx          [N] rows of K floats, ldx >= K elements between rows (a column block of a panel is a pointer and its ldx)
+ *   W, w_stride     group g's matrix starts at W + g * w_stride (elements; 0: one matrix for all); ldw, w_layout as in gnnmp_dense_f32:
+ *                   0 = [Dout][K] row-major, 1 = [K][Dout] row-major (Julia's (Dout, K) column-major); ldw >= a row of that matrix
+ *   bias            NULL, or group g's [Dout] at bias + g * bias_stride; bias_stride 0 = one bias shared by all groups
+ *   act             GNNMP_ACT_IDENTITY | GNNMP_ACT_RELU
+ *   out, ldo        [N] rows of Dout floats, ldo >= Dout; every row of a group is written, nothing between the rows
+ * K % 4 == 0, Dout % 4 == 0, x / out and ldx / ldo on 16 bytes, and the operand image of a column tile of W within LDS: the fp32
+ * v_mfma_f32_16x16x4_f32 core of gnnmp_dense_f32's 16 x 16 x 4 kernel (an exact fp32 fma chain, its summation order), one persistent
+ * workgroup per contiguous run of row tiles with the current group's W resident in LDS.  Every other shape — any K, any Dout, any
+ * 4-byte alignment — a k-ordered fmaf chain per output.  Nothing is refused for its shape.
+ * Refused with GNNMP_EINVAL before any launch: job NULL; N < 0, G < 0, K or Dout outside 1 .. 2^20; N > 0 with G == 0; another w_layout
+ * or act; ldx < K, ldo < Dout, ldw below a row of W, w_stride < 0, bias_stride neither 0 nor >= Dout; a NULL x, W, seg_ptr or out
+ * with N > 0.  N == 0: GNNMP_OK, nothing is launched.
+ *
+ * The gradient record:
+ *   dz, lddz        [N][Dout], lddz >= Dout          x, ldx   [N][K], ldx >= K (not read when dW is NULL)
+ *   dW, dw_stride   NULL, or group g's [Dout][K] row-major at dW + g * dw_stride, dw_stride >= Dout * K
+ *   db, db_stride   NULL, or group g's [Dout] at db + g * db_stride (db_stride >= Dout); db_stride 0: ONE [Dout] column sum over all rows
+ *   workspace       caller scratch of workspace_floats >= gnnmp_grouped_dense_grad_workspace(N, G, Dout, K) floats (host arithmetic);
+ *                   every word that is read was written earlier in the same call
+ * A group's rows are cut into S slabs (S from N / G and the device's compute units, the same for every group; the slab bounds are
+ * computed from seg_ptr on the device); every slab is reduced into a private partial of the workspace and a second launch adds the S
+ * partials of each group in slab order.  K % 4 == 0, Dout % 4 == 0 and dz / x rows on 16 bytes: fp32 MFMA with both operands read
+ * straight from the row-major matrices; otherwise an fmaf chain in row order.  An empty group's dW and db are written as zeros.
+ * Refused with GNNMP_EINVAL before any launch: job NULL; N < 0, G < 0 (or above 2^21), K or Dout outside 1 .. 2^16; N > 0 with G == 0;
+ * dW and db both NULL; lddz < Dout; with dW: ldx < K or dw_stride < Dout * K; a db_stride neither 0 nor >= Dout; a NULL seg_ptr or
+ * workspace with G > 0, a NULL dz (or x with dW) with N > 0; a workspace below the formula.  G == 0: GNNMP_OK, nothing is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *x;
+    int64_t ldx;
+    const float *W;
+    int64_t w_stride;
+    int64_t ldw;
+    int w_layout;
+    const float *bias;
+    int64_t bias_stride;
+    const int64_t *seg_ptr;
+    int act;
+    float *out;
+    int64_t ldo;
+} gnnmp_grouped_dense_t;
+int gnnmp_grouped_dense_f32(const gnnmp_grouped_dense_t *job, int64_t N, int64_t G, int64_t K, int64_t Dout, gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dz;
+    int64_t lddz;
+    const float *x;
+    int64_t ldx;
+    const int64_t *seg_ptr;
+    float *dW;
+    int64_t dw_stride;
+    float *db;
+    int64_t db_stride;
+    float *workspace;
+    int64_t workspace_floats;
+} gnnmp_grouped_dense_grad_t;
+int gnnmp_grouped_dense_grad_w_f32(const gnnmp_grouped_dense_grad_t *job, int64_t N, int64_t G, int64_t K, int64_t Dout, gnnmp_stream_t stream);
+int64_t gnnmp_grouped_dense_grad_workspace(int64_t N, int64_t G, int64_t Dout, int64_t K);
+
+/* ------------------------------------------------------------------------------------------------
  * GNNMP_INTERNAL — exported, NOT part of the drop-in surface: experiment and test hooks.  Declared here so that C callers (tests/c_harness)
  * do not declare them by hand; a Julia / C host has no reason to call them, and their meaning may change between builds.
  *   gnnmp_tune(knob, value)        process-global tuning knobs of the perf experiments (csrc/knobs.h: the table of indices, defaults and
@@ -2492,6 +2565,12 @@ int gnnmp_topk_gate_grad_f32(const gnnmp_topk_gate_grad_t *job, int64_t N, int64
  *                                  [5] = NT of the remainder launch (0 = none), [6] = 1 if the cross-tile prefetch condition held,
  *                                  [7] = column tiles of the full launch (0 = remainder launch only).  Zero for the other kernels.
  *                                  (tests/test_dense_fallbacks.py)
+ *   gnnmp_debug_grouped_dense_route(info)  the same for the calling thread's last gnnmp_grouped_dense_f32 / gnnmp_grouped_dense_grad_w_f32
+ *                                  call (csrc/dense_grouped_route.h).  info[0] = the kernel: 0 none (the call returned before a launch),
+ *                                  1 grouped_t16 (fp32 MFMA forward), 2 grouped_fma (any-shape forward), 3 grouped_gradw16 (fp32 MFMA
+ *                                  gradient), 4 grouped_gradw_fma (any-shape gradient); info[1] = column blocks of 16 a column tile
+ *                                  (forward MFMA) or S, the slabs a group (gradient); info[2] = waves a block; info[3] = grid.x.
+ *                                  (tests/test_grouped_dense.py)
  * ---------------------------------------------------------------------------------------------- */
 int gnnmp_tune(int knob, int value);
 int gnnmp_tune_get(int knob, int *value, int *default_value);
@@ -2501,6 +2580,7 @@ void *gnnmp_debug_plan_block(const gnnmp_graph_t *plan);
 int gnnmp_debug_pool_pick(const uint64_t *caps, int n, uint64_t bytes);
 int gnnmp_debug_random_walk_pe_f32(gnnmp_graph_t *plan_t, const gnnmp_rwpe_t *job, int64_t lds_budget_bytes, gnnmp_stream_t stream);
 int gnnmp_debug_dense_route(int info[8]);
+int gnnmp_debug_grouped_dense_route(int info[4]);
 
 #ifdef __cplusplus
 }
