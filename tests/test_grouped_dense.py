@@ -1,7 +1,9 @@
 """Grouped dense on the device against float64 numpy, group by group (tests/grouped_dense_cases.py).  Bounds are derived: an fp32 sum of n
 products in any order is within n * 2^-24 of Σ|terms|, so the forward owes (K + 2) * 2^-24 * (Σ_k |x||W| + |b|) element-wise (as in
 tests/test_dense_fallbacks.py) and ΔW (rows of the group + S) * 2^-24 * Σ_n |dz||x|: the slab's chain and the fold of S partials.  Integer
-operands must come out exact: a row under another group's weight cannot hide under a tolerance.  Routes come from the debug export."""
+operands must come out exact: a row under another group's weight cannot hide under a tolerance.  Routes come from the debug export.
+The launch geometries these shapes do not reach on a real device (several waves a super-tile, several super-tiles a block, S > 2 slabs,
+...) are in tests/test_grouped_dense_geometry.py."""
 import os
 import sys
 
@@ -109,9 +111,18 @@ def test_weight_gradient_against_float64(case):
 
 @pytest.mark.parametrize("K,Dout,lay,bias,act", [(20, 12, 0, "group", "relu"), (5, 7, 1, "shared", None), (24, 100, 1, "group", None)])
 def test_grouped_dense_ad_against_float64(K, Dout, lay, bias, act):
+    _ad_against_float64(K, Dout, lay, bias, act, SIZES)
+
+
+def test_grouped_dense_ad_against_float64_cut_multiwave():
+    """Δx — the forward with W read transposed — and ΔW on super-tiles of four waves cut by boundaries (grouped_dense_cases.py: CUT)"""
+    _ad_against_float64(24, 12, 0, "group", "relu", GC.CUT)
+
+
+def _ad_against_float64(K, Dout, lay, bias, act, sizes):
     import gnnmp
     import torch
-    seg, N, G, rows, rng = GC.seg_of(SIZES), sum(SIZES), len(SIZES), np.array(SIZES, np.float64), np.random.default_rng(K + Dout)
+    seg, N, G, rows, rng = GC.seg_of(sizes), sum(sizes), len(sizes), np.array(sizes, np.float64), np.random.default_rng(K + Dout)
     x, W = draw(rng, "gauss", N, K), draw(rng, "gauss", G, *((Dout, K) if lay == 0 else (K, Dout)))
     b, dy = draw(rng, "gauss", *((G, Dout) if bias == "group" else (Dout,))), draw(rng, "gauss", N, Dout)
     tx, tW, tb = (dev(a).requires_grad_() for a in (x, W, b))

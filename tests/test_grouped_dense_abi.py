@@ -35,7 +35,7 @@ def test_header_symbols_library_and_records():
     for rtype, st, size in (("gnnmp_grouped_dense_t", _lib.GroupedDenseJob, 96), ("gnnmp_grouped_dense_grad_t", _lib.GroupedDenseGradJob, 88)):
         assert A.struct_of(rtype) is st and [f[0] for f in h.records[rtype]] == [n for n, _ in st._fields_] and ctypes.sizeof(st) == size
     assert callable(gnnmp.grouped_dense) and callable(gnnmp.grouped_dense_ad)
-    # the planning header has no HIP in it: g++ alone, warnings as errors (the routes it plans are asserted in tests/test_grouped_dense.py)
+    # the planning header has no HIP in it: g++ alone, warnings as errors (the routes it plans are asserted in tests/test_grouped_route_cpu.py)
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "graphneuralnetworks.jl_amd", "csrc"),
                     "-include", "dense_grouped_route.h", "-x", "c++", os.devnull], check=True)
 
