@@ -42,7 +42,7 @@ from .backward_nn import nn_conv_ad  # noqa: F401
 from .backward_egnn import egnn_conv_ad  # noqa: F401
 from .backward_gmm import gmm_conv_ad  # noqa: F401
 from .backward_megnet import aggregate_neighbors_ad, megnet_conv_ad  # noqa: F401
-from .backward_readout import global_attention_pool_ad, set2set_ad  # noqa: F401
+from .backward_readout import global_attention_pool_ad, readout_route, set2set_ad  # noqa: F401
 from .backward_poly import cheb_conv_ad, d_conv_ad  # noqa: F401
 from .backward_gated import gated_graph_conv_ad, res_gated_graph_conv_ad  # noqa: F401
 from .dataset import DataLoader, GraphDataset, concat_plans  # noqa: F401

@@ -61,6 +61,7 @@ SYMBOLS = (
     "gnnmp_gmm_conv_f32", "gnnmp_gmm_conv_grad_f32", "gnnmp_gmm_weights_grad_f32",
     "gnnmp_megnet_edge_f32", "gnnmp_megnet_edge_grad_f32", "gnnmp_aggregate_grad_f32",
     "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
+    "gnnmp_segment_attn_pool_tiled_f32", "gnnmp_segment_attn_pool_tiled_grad_f32", "gnnmp_segment_attn_tiled_workspace",
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
     "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
@@ -295,6 +296,19 @@ class SegmentAttnGradJob(ctypes.Structure):
     _fields_ = [("dr", ctypes.c_void_p), ("x", ctypes.c_void_p), ("seg_ptr", ctypes.c_void_p), ("q", ctypes.c_void_p),
                 ("gate", ctypes.c_void_p), ("r", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("base", ctypes.c_void_p),
                 ("dq", ctypes.c_void_p), ("dx", ctypes.c_void_p), ("dgate", ctypes.c_void_p)]
+
+
+READOUT_TILE_ROWS = 256    # GNNMP_READOUT_TILE_ROWS
+
+
+class SegmentAttnTiledJob(ctypes.Structure):
+    """gnnmp_segment_attn_tiled_t: one gnnmp_segment_attn_pool_tiled_f32 call (gnnmp_segment_attn_t and the workspace)"""
+    _fields_ = SegmentAttnJob._fields_ + [("workspace", ctypes.c_void_p)]
+
+
+class SegmentAttnTiledGradJob(ctypes.Structure):
+    """gnnmp_segment_attn_tiled_grad_t: one gnnmp_segment_attn_pool_tiled_grad_f32 call (gnnmp_segment_attn_grad_t and the workspace)"""
+    _fields_ = SegmentAttnGradJob._fields_ + [("workspace", ctypes.c_void_p)]
 
 
 class LstmGradJob(ctypes.Structure):
@@ -562,6 +576,8 @@ def load():
         "gnnmp_segment_attn_pool_f32": [ctypes.POINTER(SegmentAttnJob), i64, i64, i64, i64, vp],
         "gnnmp_segment_attn_pool_grad_f32": [ctypes.POINTER(SegmentAttnGradJob), i64, i64, i64, i64, vp],
         "gnnmp_lstm_pointwise_grad_f32": [ctypes.POINTER(LstmGradJob), i64, i64, vp],
+        "gnnmp_segment_attn_pool_tiled_f32": [ctypes.POINTER(SegmentAttnTiledJob), i64, i64, i64, i64, vp],
+        "gnnmp_segment_attn_pool_tiled_grad_f32": [ctypes.POINTER(SegmentAttnTiledGradJob), i64, i64, i64, i64, vp],
         "gnnmp_poly_hop_f32": [vp, ctypes.POINTER(PolyHopJob), i64, vp],
         "gnnmp_gru_pointwise_grad_f32": [ctypes.POINTER(GruGradJob), i64, i64, vp],
         "gnnmp_poly_hop_ld_f32": [vp, ctypes.POINTER(PolyHopLdJob), i64, vp],
@@ -610,6 +626,12 @@ def load():
     try:
         L.gnnmp_grouped_dense_grad_workspace.argtypes = [i64, i64, i64, i64]
         L.gnnmp_grouped_dense_grad_workspace.restype = i64
+    except AttributeError:
+        if not os.environ.get("GNNMP_LIB"):
+            raise
+    try:
+        L.gnnmp_segment_attn_tiled_workspace.argtypes = [i64, i64, i64, i64]
+        L.gnnmp_segment_attn_tiled_workspace.restype = i64
     except AttributeError:
         if not os.environ.get("GNNMP_LIB"):
             raise

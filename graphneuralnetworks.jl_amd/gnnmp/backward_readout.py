@@ -16,6 +16,11 @@ from those two numbers.  Nothing of N rows is written by a forward, and nothing 
                   dWi, dWh, db from the T·G stacked rows of da                          gnnmp_dense_grad_w_f32, one call per weight
     global_attention_pool_ad      gate = fgate(x), feats = ffeat(x) through dense_ad; r = Σ_n softmax_n(gate) ⊙ feats in gate mode
 
+Two routes serve the two segment calls (`route`): "whole", one lane group a segment (csrc/readout.hip) — the QM9-shaped batch of many short
+graphs — and "tiled", fixed row tiles and a fold (csrc/readout_tiled.hip, the *_tiled_* exports) — few, long segments: point clouds, a
+whole-graph readout.  "auto" is readout_route(N, G), a function of the shapes alone.  The tiled route's workspace is torch's: one
+buffer per layer call, shared by the forward, Set2Set's iterations and the backward.
+
 torch allocates, slices, stacks and chains; every arithmetic step is a libgnnmp call.  `gnnmp.set2set_pool` and
 `gnnmp.global_attention_pool` are unchanged; the fused forwards sum in another order and owe them the 1e-5 bar, not equal bits.
 """
@@ -49,26 +54,56 @@ def node_ptr(g: GNNGraph):
     return sp
 
 
-def segment_attn_pool(x, sp, q=None, gate=None):
-    """(r [G][D], stats [G][max(Dg,1)][2]) of gnnmp_segment_attn_pool_f32: q [G][D] (query mode) or gate [N][1 | D] (gate mode)"""
+ROUTES = ("auto", "whole", "tiled")
+TILED_MEAN_ROWS = 704      # the tiled route wins from a mean of a few hundred rows a graph on; the whole route keeps N < 704 G
+
+
+def readout_route(N, G):
+    """the route "auto" takes: "tiled" when the N rows are at least TILED_MEAN_ROWS a graph, "whole" otherwise"""
+    return "tiled" if N >= TILED_MEAN_ROWS * G else "whole"
+
+
+def _resolve(who, route, N, G):
+    if route not in ROUTES:
+        raise ValueError(f"{who}: route {route!r} is none of {ROUTES}")
+    return readout_route(N, G) if route == "auto" else route
+
+
+def tiled_workspace(x, G, Dg):
+    """the float scratch of one tiled call on x [N][D]; any later tiled call of the same shapes may reuse it"""
+    n = L.load().gnnmp_segment_attn_tiled_workspace(x.shape[0], G, x.shape[1], Dg)
+    return torch.empty(max(1, n), dtype=torch.float32, device=x.device)
+
+
+def segment_attn_pool(x, sp, q=None, gate=None, route="auto", workspace=None):
+    """(r [G][D], stats [G][max(Dg,1)][2]) of gnnmp_segment_attn_pool_f32 (route "whole") or gnnmp_segment_attn_pool_tiled_f32 ("tiled";
+    `workspace`: a tiled_workspace to reuse): q [G][D] (query mode) or gate [N][1 | D] (gate mode)"""
     N, D = x.shape
     G = sp.numel() - 1
     Dg = 0 if gate is None else gate.shape[1]
+    route = _resolve("segment_attn_pool", route, N, G)
     r = torch.empty((G, D), dtype=torch.float32, device=x.device)
     stats = torch.empty((G, max(Dg, 1), 2), dtype=torch.float32, device=x.device)
     if N == 0 or G == 0:      # nothing is launched: every segment is empty
         return r.zero_(), stats.zero_()
-    job = L.SegmentAttnJob(_p(x), _p(sp), _p(q), _p(gate), _p(r), _p(stats))
-    L.check(L.load().gnnmp_segment_attn_pool_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
+    if route == "tiled":
+        ws = tiled_workspace(x, G, Dg) if workspace is None else workspace
+        job = L.SegmentAttnTiledJob(_p(x), _p(sp), _p(q), _p(gate), _p(r), _p(stats), _p(ws))
+        L.check(L.load().gnnmp_segment_attn_pool_tiled_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
+    else:
+        job = L.SegmentAttnJob(_p(x), _p(sp), _p(q), _p(gate), _p(r), _p(stats))
+        L.check(L.load().gnnmp_segment_attn_pool_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
     return r, stats
 
 
-def segment_attn_pool_grad(dr, x, sp, r, stats, q=None, gate=None, base=None, want_dq=True, want_dx=True, want_dgate=True):
-    """(dq [G][D] | None, dx [N][D] | None, dgate [N][Dg] | None) of gnnmp_segment_attn_pool_grad_f32.  `base` [N][D] is added into dx
-    and BECOMES dx (the kernel reads and writes it in place)."""
+def segment_attn_pool_grad(dr, x, sp, r, stats, q=None, gate=None, base=None, want_dq=True, want_dx=True, want_dgate=True, route="auto",
+                           workspace=None):
+    """(dq [G][D] | None, dx [N][D] | None, dgate [N][Dg] | None) of gnnmp_segment_attn_pool_grad_f32 or, route "tiled", of
+    gnnmp_segment_attn_pool_tiled_grad_f32.  `base` [N][D] is added into dx and BECOMES dx (the kernel reads and writes it in place)."""
     N, D = x.shape
     G = sp.numel() - 1
     Dg = 0 if gate is None else gate.shape[1]
+    route = _resolve("segment_attn_pool_grad", route, N, G)
     dq = torch.empty((G, D), dtype=torch.float32, device=x.device) if (gate is None and want_dq) else None
     dx = (base if base is not None else torch.empty_like(x)) if want_dx else None
     dgate = torch.empty_like(gate) if (gate is not None and want_dgate) else None
@@ -76,9 +111,14 @@ def segment_attn_pool_grad(dr, x, sp, r, stats, q=None, gate=None, base=None, wa
         return None, None, None
     if N == 0 or G == 0:
         return (None if dq is None else dq.zero_()), dx, dgate
-    job = L.SegmentAttnGradJob(_p(dr), _p(x), _p(sp), _p(q), _p(gate), _p(r), _p(stats), _p(base) if want_dx else None, _p(dq), _p(dx),
-                               _p(dgate))
-    L.check(L.load().gnnmp_segment_attn_pool_grad_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
+    fields = (_p(dr), _p(x), _p(sp), _p(q), _p(gate), _p(r), _p(stats), _p(base) if want_dx else None, _p(dq), _p(dx), _p(dgate))
+    if route == "tiled":
+        ws = tiled_workspace(x, G, Dg) if workspace is None else workspace
+        job = L.SegmentAttnTiledGradJob(*fields, _p(ws))
+        L.check(L.load().gnnmp_segment_attn_pool_tiled_grad_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
+    else:
+        job = L.SegmentAttnGradJob(*fields)
+        L.check(L.load().gnnmp_segment_attn_pool_grad_f32(ctypes.byref(job), N, G, D, Dg, L.stream_ptr()))
     return dq, dx, dgate
 
 
@@ -97,10 +137,11 @@ class _Set2SetFn(torch.autograd.Function):
     """(x, Wi, Wh, b) -> vcat(q_T, r_T) [G][2 n_in]"""
 
     @staticmethod
-    def forward(ctx, x, Wi, Wh, b, g, num_iters):
+    def forward(ctx, x, Wi, Wh, b, g, num_iters, route):
         N, n = x.shape
         G = g.num_graphs
         sp = node_ptr(g)
+        ws = tiled_workspace(x, G, 0) if route == "tiled" else None      # one buffer for every iteration, forward and backward
         lib = L.load()
         z = lambda: torch.zeros((G, n), dtype=torch.float32, device=x.device)
         q, r, c = z(), z(), z()
@@ -111,11 +152,11 @@ class _Set2SetFn(torch.autograd.Function):
             hn, cn = torch.empty_like(q), torch.empty_like(c)
             if G > 0:
                 L.check(lib.gnnmp_lstm_pointwise_f32(L.ptr(gx), L.ptr(gh), L.ptr(b), L.ptr(c), L.ptr(hn), L.ptr(cn), G, n, L.stream_ptr()))
-            rn, stats = segment_attn_pool(x, sp, q=hn)
+            rn, stats = segment_attn_pool(x, sp, q=hn, route=route, workspace=ws)
             steps.append((gx, gh, c, q, r, hn, rn, stats))       # c, q, r: what ENTERED the step; hn, rn: what it made
             q, r, c = hn, rn, cn
         ctx.save_for_backward(x, Wi, Wh, b)
-        ctx.steps, ctx.sp = steps, sp
+        ctx.steps, ctx.sp, ctx.route, ctx.ws = steps, sp, route, ws
         return torch.cat([q, r], dim=1)                           # vcat(q, r): memory plumbing
 
     @staticmethod
@@ -126,14 +167,15 @@ class _Set2SetFn(torch.autograd.Function):
         n = x.shape[1]
         T = len(ctx.steps)
         if T == 0 or not (need_x or need_w):
-            return (torch.zeros_like(x) if need_x else None), None, None, None, None, None
+            return (torch.zeros_like(x) if need_x else None), None, None, None, None, None, None
         dout = dout.contiguous()
         dh_out, dr = dout[:, :n].contiguous(), dout[:, n:].contiguous()      # what reaches q_t = h_t from later steps, and r_t
         dcn, dx, das = None, None, []
         for t in range(T - 1, -1, -1):
             gx, gh, c_in, q_in, r_in, q, r, stats = ctx.steps[t]
             first = t == 0      # its dq reaches the weights only: q_0 = r_0 = h_0 = c_0 = 0 carry nothing further back
-            dq, dx, _ = segment_attn_pool_grad(dr, x, ctx.sp, r, stats, q=q, base=dx, want_dq=need_w or not first, want_dx=need_x)
+            dq, dx, _ = segment_attn_pool_grad(dr, x, ctx.sp, r, stats, q=q, base=dx, want_dq=need_w or not first, want_dx=need_x,
+                                               route=ctx.route, workspace=ctx.ws)
             if first and not need_w:
                 break
             da, dcn = lstm_pointwise_grad(gx, gh, b, c_in, _add(dh_out, dq), dcn)
@@ -152,13 +194,13 @@ class _Set2SetFn(torch.autograd.Function):
                 dWh = dense_grad_w(DA, torch.cat([s[3] for s in ctx.steps], dim=0), need_b=False)[0]
         if need_x and dx is None:
             dx = torch.zeros_like(x)
-        return dx, dWi, dWh, db, None, None
+        return dx, dWi, dWh, db, None, None, None
 
 
-def set2set_ad(l, g: GNNGraph, x):
+def set2set_ad(l, g: GNNGraph, x, route="auto"):
     """differentiable Set2Set forward -> [num_graphs][2 n_in]: gradients w.r.t. x, l.Wi, l.Wh and l.b.  One fused segment kernel per
     iteration in place of broadcast_nodes, rowdot, softmax_nodes, mul_rows and reduce_nodes; the outputs agree with gnnmp.set2set_pool to
-    the 1e-5 bar, not bit for bit."""
+    the 1e-5 bar, not bit for bit.  route: "whole", "tiled" or "auto" (readout_route of the batch's shape)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
         raise ValueError("set2set_ad: x must be an [N][n_in] matrix")
     if x.dtype != torch.float32:
@@ -169,26 +211,28 @@ def set2set_ad(l, g: GNNGraph, x):
     if not 1 <= n <= L.READOUT_MAX_D:
         raise ValueError(f"set2set_ad: n_in = {n} outside 1 .. {L.READOUT_MAX_D}")
     check_num_nodes(g, x)
-    return _Set2SetFn.apply(x.contiguous(), l.Wi, l.Wh, l.b, g, l.num_iters)
+    return _Set2SetFn.apply(x.contiguous(), l.Wi, l.Wh, l.b, g, l.num_iters, _resolve("set2set_ad", route, x.shape[0], g.num_graphs))
 
 
 class _GateAttnPoolFn(torch.autograd.Function):
     """(feats [N][D], gate [N][1 | D]) -> r [G][D]"""
 
     @staticmethod
-    def forward(ctx, feats, gate, g):
+    def forward(ctx, feats, gate, g, route):
         sp = node_ptr(g)
-        r, stats = segment_attn_pool(feats, sp, gate=gate)
+        ws = tiled_workspace(feats, g.num_graphs, gate.shape[1]) if route == "tiled" else None
+        r, stats = segment_attn_pool(feats, sp, gate=gate, route=route, workspace=ws)
         ctx.save_for_backward(feats, gate, r, stats)
-        ctx.sp = sp
+        ctx.sp, ctx.route, ctx.ws = sp, route, ws
         return r
 
     @staticmethod
     def backward(ctx, dr):
         feats, gate, r, stats = ctx.saved_tensors
         need_f, need_g = ctx.needs_input_grad[:2]
-        _, dfeats, dgate = segment_attn_pool_grad(dr.contiguous(), feats, ctx.sp, r, stats, gate=gate, want_dx=need_f, want_dgate=need_g)
-        return dfeats, dgate, None
+        _, dfeats, dgate = segment_attn_pool_grad(dr.contiguous(), feats, ctx.sp, r, stats, gate=gate, want_dx=need_f, want_dgate=need_g,
+                                                  route=ctx.route, workspace=ctx.ws)
+        return dfeats, dgate, None, None
 
 
 def _dense_chain(name, chain):
@@ -207,9 +251,10 @@ def _dense_chain(name, chain):
     return layers
 
 
-def global_attention_pool_ad(l, g: GNNGraph, x):
+def global_attention_pool_ad(l, g: GNNGraph, x, route="auto"):
     """differentiable GlobalAttentionPool forward -> [num_graphs][D']: gradients w.r.t. x and every weight and bias of l.fgate and
-    l.ffeat, each a gnnmp.Dense or a list of them (σ identity or relu; ffeat = None is the identity).  The gate has one channel or D'."""
+    l.ffeat, each a gnnmp.Dense or a list of them (σ identity or relu; ffeat = None is the identity).  The gate has one channel or D'.
+    route: "whole", "tiled" or "auto" (readout_route of the batch's shape)."""
     fgate = _dense_chain("fgate", l.fgate)
     ffeat = [] if l.ffeat is None else _dense_chain("ffeat", l.ffeat)
     if not isinstance(x, torch.Tensor) or x.dim() != 2:
@@ -229,4 +274,4 @@ def global_attention_pool_ad(l, g: GNNGraph, x):
         gate = dense_ad(layer, gate)
     for layer in ffeat:
         feats = dense_ad(layer, feats)
-    return _GateAttnPoolFn.apply(feats.contiguous(), gate.contiguous(), g)
+    return _GateAttnPoolFn.apply(feats.contiguous(), gate.contiguous(), g, _resolve("global_attention_pool_ad", route, x.shape[0], g.num_graphs))

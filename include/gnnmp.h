@@ -37,7 +37,8 @@
  *     gnnmp_egnn_coord_f32 / gnnmp_egnn_coord_grad_f32 / gnnmp_act_grad_z_f32 (tests/test_egnn_conv_ad.py) and gnnmp_gmm_conv_f32 / gnnmp_gmm_conv_grad_f32 /
  *     gnnmp_gmm_weights_grad_f32 (tests/test_gmm_conv_ad.py) and gnnmp_megnet_edge_f32 / gnnmp_megnet_edge_grad_f32 /
  *     gnnmp_aggregate_grad_f32 (tests/test_megnet_conv_ad.py) and gnnmp_segment_attn_pool_f32 / gnnmp_segment_attn_pool_grad_f32 /
- *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py) and
+ *     gnnmp_lstm_pointwise_grad_f32 (tests/test_readout_ad.py) and gnnmp_segment_attn_pool_tiled_f32 /
+ *     gnnmp_segment_attn_pool_tiled_grad_f32 (tests/test_readout_tiled.py) and
  *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
  *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
  *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_lstm_matvec_cell_f32 /
@@ -1937,7 +1938,7 @@ int gnnmp_aggregate_grad_f32(const gnnmp_graph_t *plan, const gnnmp_aggregate_gr
  *            feature tiles by the SAME group, and the logit loop then reads the whole row once per tile (quadratic in the tile count).
  * All three only launch on `stream`: no atomics, no allocation, no host wait, no scratch; each may be recorded into a HIP graph without
  * an eager call first; two calls give equal bits.  G = 0 or N = 0 launches nothing, writes nothing and returns GNNMP_OK.  A SEGMENT OF ANY
- * LENGTH IS WALKED BY ITS ONE LANE GROUP: a whole-graph readout of millions of rows is slow.
+ * LENGTH IS WALKED BY ITS ONE LANE GROUP: FOR FEW, LONG SEGMENTS (N >= 704 G) AND WHOLE-GRAPH READOUTS USE THE TILED PAIR BELOW.
  * Refused before any HIP call (GNNMP_EINVAL), each message naming its export: a NULL job; a NULL x (N > 0), seg_ptr, r, stats, dr, gx, gh,
  * c, dh, da, dc; both or neither of q and gate; Dg outside {0, 1, D}, Dg = 0 with gate or Dg > 0 with q; D outside its range; a negative
  * N or G; in the pullback no output, dgate in QUERY mode, dq in GATE mode, base without dx.
@@ -1980,6 +1981,75 @@ typedef struct {
     float *dc;               /* [N][D] */
 } gnnmp_lstm_grad_t;
 int gnnmp_lstm_pointwise_grad_f32(const gnnmp_lstm_grad_t *job, int64_t N, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The attention readouts on ROW TILES (csrc/readout_tiled.hip): the pair above for few, long segments — 32 point clouds of 1024 points,
+ * a whole-graph readout — where one lane group a segment leaves the device idle.  The same operands, modes, outputs and layouts (r and
+ * stats of either forward feed either pullback); the results agree to rounding, not bit for bit: the folds run in another order.
+ * The N rows are cut into tiles of R = GNNMP_READOUT_TILE_ROWS rows; a PIECE is (tile t) ∩ (segment g), non-empty.  The pieces form a
+ * monotone staircase in (t, g): slot = t + g is unique, and n_tiles + G slots, n_tiles = ceil(N / R), always suffice.  The launch shape
+ * depends on N, G, D and the alignment only; seg_ptr is read on the device.
+ *
+ *   gnnmp_segment_attn_pool_tiled_f32   two launches.
+ *                                 TILE PASS, one workgroup of 256 lanes a tile (and feature tile): it finds its first segment by binary
+ *                                 search in seg_ptr (clamped into [0, N]) and walks the segments that meet the tile.  Per piece, the logits
+ *                                 s_n as above, x read ONCE per row, in node order from m = -Inf, den = 0, u = 0:
+ *                                   s_n > m:   f = expf(m - s_n);  den = den f + 1,  u = u f + x_n,  m = s_n
+ *                                   else:      p = expf(s_n - m);  den = den + p,    u = u + p x_n
+ *                                 A piece of 32 rows or more is shared by the block's NG = 256 / (lanes of a group) lane groups, group k
+ *                                 taking rows [k c, (k + 1) c) of it, c = ceil(rows / NG); their partials are merged in group order,
+ *                                   m_p = max_k m_k,  den_p = Σ_k den_k expf(m_k - m_p),  u_p = Σ_k expf(m_k - m_p) u_k     (from 0)
+ *                                 Shorter pieces are dealt whole to the lane groups, round robin in segment order.  (m_p, den_p, u_p [D])
+ *                                 goes to the workspace at slot t + g.
+ *                                 FOLD PASS, one lane group a graph, its tiles beg / R .. (end - 1) / R in tile order:
+ *                                   m_g = max_p m_p,  den_g = Σ_p den_p expf(m_p - m_g),  r_g = (Σ_p expf(m_p - m_g) u_p) / den_g
+ *                                 stats[g][j] = (m_g, den_g) as above; an EMPTY segment gives r_g = 0 and stats (0, 0).
+ *   gnnmp_segment_attn_pool_tiled_grad_f32   TILE PASS: per piece c_g, then per row α_n, t_n, ds_n, dx_n, dgate_n by the expressions of
+ *                                 gnnmp_segment_attn_pool_grad_f32, rows stored as they are met; base may be dx; a NULL output is not
+ *                                 computed and the others keep their bits.  QUERY mode with dq: dq_p = Σ_n ds_n x_n (node order within
+ *                                 a lane group, then group order, from 0) goes to the workspace at slot t + g, and a FOLD PASS, one
+ *                                 lane group a graph, gives dq_g = Σ_p dq_p in tile order (an empty segment: 0).
+ *   gnnmp_segment_attn_tiled_workspace   host arithmetic: (ceil(N / R) + G) * (D + 2 max(Dg, 1)) floats — u_p / dq_p [slots][D], then
+ *                                 (m_p, den_p) [slots][max(Dg, 1)][2]; 0 for a negative N, G or Dg or D < 1.
+ *
+ *   job      const HOST records: the fields of gnnmp_segment_attn_t / gnnmp_segment_attn_grad_t with the same roles, then
+ *            workspace: caller scratch of gnnmp_segment_attn_tiled_workspace(N, G, D, Dg) floats, its contents undefined before and after;
+ *            nothing is written behind it.  It counts among the [.][D] pointers whose alignment selects the lane width.
+ * Both only launch on `stream`: no atomics, no host wait, no device memory obtained or released; each may be recorded into a HIP graph
+ * without an eager call first; two calls give equal bits; every owed element is written and, outside the workspace, nothing else.
+ * G = 0 or N = 0 launches nothing, writes nothing and returns GNNMP_OK.  Refused before any HIP call (GNNMP_EINVAL), each message naming
+ * its export: what the pair above refuses, and a NULL workspace.  GNNMP_EUNSUPPORTED: N >= 2^31 R.
+ * ---------------------------------------------------------------------------------------------- */
+#define GNNMP_READOUT_TILE_ROWS 256
+typedef struct {
+    const float *x;          /* [N][D] */
+    const int64_t *seg_ptr;  /* [G+1] */
+    const float *q;          /* [G][D], QUERY mode (Dg = 0); else NULL */
+    const float *gate;       /* [N][Dg], GATE mode (Dg = 1 | D); else NULL */
+    float *r;                /* [G][D] */
+    float *stats;            /* [G][max(Dg,1)][2]: (max, denominator) */
+    float *workspace;        /* gnnmp_segment_attn_tiled_workspace floats */
+} gnnmp_segment_attn_tiled_t;
+int gnnmp_segment_attn_pool_tiled_f32(const gnnmp_segment_attn_tiled_t *job, int64_t N, int64_t G, int64_t D, int64_t Dg,
+                                      gnnmp_stream_t stream);
+
+typedef struct {
+    const float *dr;         /* [G][D] */
+    const float *x;          /* [N][D] */
+    const int64_t *seg_ptr;  /* [G+1] */
+    const float *q;          /* [G][D] or NULL */
+    const float *gate;       /* [N][Dg] or NULL */
+    const float *r;          /* [G][D], a forward's */
+    const float *stats;      /* [G][max(Dg,1)][2], a forward's */
+    const float *base;       /* [N][D] or NULL; may be dx */
+    float *dq;               /* [G][D] or NULL; QUERY mode */
+    float *dx;               /* [N][D] or NULL */
+    float *dgate;            /* [N][Dg] or NULL; GATE mode */
+    float *workspace;        /* gnnmp_segment_attn_tiled_workspace floats */
+} gnnmp_segment_attn_tiled_grad_t;
+int gnnmp_segment_attn_pool_tiled_grad_f32(const gnnmp_segment_attn_tiled_grad_t *job, int64_t N, int64_t G, int64_t D, int64_t Dg,
+                                           gnnmp_stream_t stream);
+int64_t gnnmp_segment_attn_tiled_workspace(int64_t N, int64_t G, int64_t D, int64_t Dg);
 
 /* ------------------------------------------------------------------------------------------------
  * The polynomial layers and the GRU cell, forward and pullback (csrc/poly_conv.hip) — what cheb_conv, GNNlib/src/layers/conv.jl:83-98,

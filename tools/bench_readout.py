@@ -1,18 +1,24 @@
-"""Attention readout timing at two shapes, 64 channels: the existing compositions (gnnmp.set2set_pool: per iteration broadcast_nodes,
+"""Attention readout timing at five shapes, 64 channels: the existing compositions (gnnmp.set2set_pool: per iteration broadcast_nodes,
 rowdot, softmax_nodes, mul_rows, reduce_nodes; gnnmp.global_attention_pool: softmax_nodes, mul_rows, reduce_nodes) against the fused
 forwards (gnnmp.set2set_ad / gnnmp.global_attention_pool_ad under torch.no_grad(): one gnnmp_segment_attn_pool_f32 per softmax-weighted
 sum) and the trained readouts (forward + backward) against the same readout written in torch ops with torch autograd on the device — what
 a user could do before — in one process, alternating.
     s2s_forward        gnnmp.set2set_pool(l, g, x) under torch.no_grad()                           the yardstick
-    s2s_fused_forward  gnnmp.set2set_ad(l, g, x) under torch.no_grad()
-    s2s_train          gnnmp.set2set_ad forward + backward: gradients of x, Wi, Wh, b
+    s2s_fused_forward  gnnmp.set2set_ad(l, g, x, route="whole") under torch.no_grad(): one lane group a segment
+    s2s_tiled_forward  the same with route="tiled": row tiles and a fold (gnnmp_segment_attn_pool_tiled_f32)
+    s2s_train          gnnmp.set2set_ad(route="whole") forward + backward: gradients of x, Wi, Wh, b
+    s2s_tiled_train    the same with route="tiled"
     s2s_torch_train    the same in torch ops (index_select, scatter_reduce, index_add) with torch autograd
     gap_forward        gnnmp.global_attention_pool(l, g, x) under torch.no_grad()                  the yardstick
-    gap_fused_forward  gnnmp.global_attention_pool_ad(l, g, x) under torch.no_grad()
-    gap_train          gnnmp.global_attention_pool_ad forward + backward: gradients of x and of fgate's and ffeat's weights and biases
+    gap_fused_forward  gnnmp.global_attention_pool_ad(l, g, x, route="whole") under torch.no_grad()
+    gap_tiled_forward  the same with route="tiled"
+    gap_train          gnnmp.global_attention_pool_ad(route="whole") forward + backward: gradients of x and of fgate's and ffeat's weights
+                       and biases
+    gap_tiled_train    the same with route="tiled"
     gap_torch_train    the same in torch ops with torch autograd
-Shapes: `qm9`, synth.batched_graphs(G = 4096, nmin = 9, nmax = 29) — molecules of 9 to 29 atoms; `clouds`, 32 clouds x 1024 points (ONE
-lane group walks each cloud: 32 lane groups on the whole device — the documented weak spot).  Set2Set with 3 iterations;
+Shapes: `qm9`, synth.batched_graphs(G = 4096, nmin = 9, nmax = 29) — molecules of 9 to 29 atoms; `clouds`, 32 clouds x 1024 points (route
+"whole": ONE lane group walks each cloud, 32 lane groups on the whole device); between them `len128`, `len256`, `len512`, the same 32768
+rows in 256, 128 and 64 graphs of equal length, to locate where the routes cross (readout_route's threshold).  Set2Set with 3 iterations;
 GlobalAttentionPool(fgate = Dense(64 => 1), ffeat = Dense(64 => 64, relu)).  Device events after --warmup calls, median of --reps, rounds
 alternate the entries; every round is reported (a single run is a record, not a claim).  Before timing, the forwards and the gradients are
 compared at the timed size (norm-wise).  Prints ONE JSON line.
@@ -105,26 +111,31 @@ def shape_entries(tag, g, gen):
             out.backward(dout)
             return out
         return run
-    s2s_forward, s2s_fused = no_grad(gnnmp.set2set_pool, s2s, g, x), no_grad(gnnmp.set2set_ad, s2s, g, x)
-    gap_forward, gap_fused = no_grad(gnnmp.global_attention_pool, gap, g, x), no_grad(gnnmp.global_attention_pool_ad, gap, g, x)
-    fwd = max(rel(s2s_fused(), s2s_forward()), rel(gap_fused(), gap_forward()))
+    s2s_forward, gap_forward = no_grad(gnnmp.set2set_pool, s2s, g, x), no_grad(gnnmp.global_attention_pool, gap, g, x)
+    s2s_fused, s2s_tiled = (no_grad(gnnmp.set2set_ad, s2s, g, x, route) for route in ("whole", "tiled"))
+    gap_fused, gap_tiled = (no_grad(gnnmp.global_attention_pool_ad, gap, g, x, route) for route in ("whole", "tiled"))
+    fwd = max(rel(s2s_fused(), s2s_forward()), rel(gap_fused(), gap_forward()), rel(s2s_tiled(), s2s_forward()), rel(gap_tiled(), gap_forward()))
     assert fwd <= 1e-4, f"{tag}: a fused forward differs from the existing one by {fwd:.2e} norm-wise"
     for p in ps_s + ps_g:
         p.requires_grad_(True)
-    s2s_train = train(lambda: gnnmp.set2set_ad(s2s, g, xg), [xg] + ps_s, d2)
+    s2s_train, s2s_ttiled = (train(lambda route=route: gnnmp.set2set_ad(s2s, g, xg, route), [xg] + ps_s, d2) for route in ("whole", "tiled"))
     s2s_torch = train(lambda: set2set_torch(xg, gi, G, s2s.Wi, s2s.Wh, s2s.b), [xg] + ps_s, d2)
-    gap_train = train(lambda: gnnmp.global_attention_pool_ad(gap, g, xg), [xg] + ps_g, d1)
+    gap_train, gap_tiled_train = (train(lambda route=route: gnnmp.global_attention_pool_ad(gap, g, xg, route), [xg] + ps_g, d1)
+                                  for route in ("whole", "tiled"))
     gap_ttrain = train(lambda: gap_torch(xg, gi, G, fgate, ffeat), [xg] + ps_g, d1)
     grads = 0.0
     # (the gate's one bias shifts every logit of a softmax alike: its gradient is zero but for rounding, and is left out of the comparison)
-    for ours, theirs, leaves in ((s2s_train, s2s_torch, [xg] + ps_s), (gap_train, gap_ttrain, [xg, fgate.weight, ffeat.weight, ffeat.bias])):
+    gap_leaves = [xg, fgate.weight, ffeat.weight, ffeat.bias]
+    for ours, theirs, leaves in ((s2s_train, s2s_torch, [xg] + ps_s), (s2s_ttiled, s2s_torch, [xg] + ps_s), (gap_train, gap_ttrain, gap_leaves),
+                                 (gap_tiled_train, gap_ttrain, gap_leaves)):
         ours()
         mine = [v.grad.clone() for v in leaves]
         theirs()
         grads = max([grads] + [rel(a, v.grad) for a, v in zip(mine, leaves)])
     assert grads <= 1e-3, f"{tag}: a gradient differs from torch autograd's by {grads:.2e} norm-wise"
-    entries = [("s2s_forward", s2s_forward), ("s2s_fused_forward", s2s_fused), ("s2s_train", s2s_train), ("s2s_torch_train", s2s_torch),
-               ("gap_forward", gap_forward), ("gap_fused_forward", gap_fused), ("gap_train", gap_train), ("gap_torch_train", gap_ttrain)]
+    entries = [("s2s_forward", s2s_forward), ("s2s_fused_forward", s2s_fused), ("s2s_tiled_forward", s2s_tiled), ("s2s_train", s2s_train),
+               ("s2s_tiled_train", s2s_ttiled), ("s2s_torch_train", s2s_torch), ("gap_forward", gap_forward), ("gap_fused_forward", gap_fused),
+               ("gap_tiled_forward", gap_tiled), ("gap_train", gap_train), ("gap_tiled_train", gap_tiled_train), ("gap_torch_train", gap_ttrain)]
     return [(f"{tag}.{k}", fn) for k, fn in entries], fwd, grads
 
 
@@ -140,10 +151,13 @@ def main():
     qm9 = gnnmp.batch_arrays(synth.batched_graphs(G=4096, nmin=9, nmax=29, deg=2, seed=3))
     clouds, points = 32, 1024
     one = torch.zeros(1, dtype=torch.int64, device="cuda")
-    cl = gnnmp.GNNGraph(one, one + 1, num_nodes=clouds * points, graph_indicator=torch.arange(clouds).repeat_interleave(points).cuda(),
-                        num_graphs=clouds, index_base=0)
+
+    def equal(n_graphs):      # the clouds' rows in n_graphs graphs of equal length
+        gi = torch.arange(n_graphs).repeat_interleave(clouds * points // n_graphs).cuda()
+        return gnnmp.GNNGraph(one, one + 1, num_nodes=clouds * points, graph_indicator=gi, num_graphs=n_graphs, index_base=0)
+    shapes = (("qm9", qm9), ("len128", equal(256)), ("len256", equal(128)), ("len512", equal(64)), ("clouds", equal(clouds)))
     entries, fwd, grads = [], 0.0, 0.0
-    for tag, g in (("qm9", qm9), ("clouds", cl)):
+    for tag, g in shapes:
         e, f, gr = shape_entries(tag, g, gen)
         entries, fwd, grads = entries + e, max(fwd, f), max(grads, gr)
     rounds = []
@@ -151,13 +165,16 @@ def main():
         rounds.append({name: timed(fn, args.reps, args.warmup) for name, fn in entries})
     ms = {k: min(r[k] for r in rounds) for k in rounds[0]}
     ratios = {}
-    for tag in ("qm9", "clouds"):
+    for tag, _ in shapes:
         for kind in ("s2s", "gap"):
             ratios[f"{tag}.{kind}_forward_over_fused"] = ms[f"{tag}.{kind}_forward"] / ms[f"{tag}.{kind}_fused_forward"]
+            ratios[f"{tag}.{kind}_forward_over_tiled"] = ms[f"{tag}.{kind}_forward"] / ms[f"{tag}.{kind}_tiled_forward"]
             ratios[f"{tag}.{kind}_torch_train_over_train"] = ms[f"{tag}.{kind}_torch_train"] / ms[f"{tag}.{kind}_train"]
+            ratios[f"{tag}.{kind}_torch_train_over_tiled_train"] = ms[f"{tag}.{kind}_torch_train"] / ms[f"{tag}.{kind}_tiled_train"]
     print(json.dumps({"tool": "bench_readout", "device": torch.cuda.get_device_name(0), "reps": args.reps, "rounds": args.rounds,
                       "channels": D, "set2set_iters": ITERS, "qm9": {"G": qm9.num_graphs, "N": qm9.num_nodes},
-                      "clouds": {"G": clouds, "N": clouds * points}, "ms_per_round": rounds, "ms": ms, "ratios": ratios,
+                      "clouds": {"G": clouds, "N": clouds * points},
+                      "tile_rows": gnnmp._lib.READOUT_TILE_ROWS, "ms_per_round": rounds, "ms": ms, "ratios": ratios,
                       "worst_rel_between_forwards": fwd, "worst_rel_against_torch_autograd": grads}))
 
 
