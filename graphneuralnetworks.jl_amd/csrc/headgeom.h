@@ -39,4 +39,26 @@ inline HeadGeom head_geom(int64_t H, int64_t C, int vec0) {
     return g;
 }
 
+// Rows WIDER than a wave (attn_wide.hip): attention is independent per head, so a wave needs a whole number of heads, not the whole row.
+// A wave takes one (row, head tile): hpt heads of lph lanes each, lanes [0, hpt * lph) of the wave; the last tile may hold fewer heads.
+struct HeadTiles {
+    int vec;          // features a lane holds (head_vec)
+    int lph;          // C / vec: lanes that hold one head
+    int lph_code;     // lph as the kernels take it, for a lane group of 64
+    int hpt;          // min(H, 64 / lph): heads a tile
+    int tiles;        // ceil(H / hpt)
+    bool fits;        // lph <= 64: a head fits a wave; the rest of the struct is for heads that do
+};
+inline HeadTiles head_tiles(int64_t H, int64_t C, int vec0) {
+    HeadTiles t;
+    t.vec = head_vec(C, vec0);
+    const int64_t lph = C / t.vec;
+    t.fits = lph <= 64;
+    t.lph = t.fits ? (int)lph : 0;
+    t.lph_code = t.fits ? lph_code(t.lph, 6) : 0;
+    t.hpt = t.fits ? (int)(H < 64 / lph ? H : 64 / lph) : 0;
+    t.tiles = t.fits ? (int)((H + t.hpt - 1) / t.hpt) : 0;
+    return t;
+}
+
 }  // namespace gnnmp

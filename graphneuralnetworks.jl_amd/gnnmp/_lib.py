@@ -65,7 +65,7 @@ SYMBOLS = (
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
     "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
-    "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32",
+    "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32", "gnnmp_attn_conv_wide_f32", "gnnmp_attn_conv_wide_grad_f32",
     "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
     "gnnmp_topk_select_radix_f32", "gnnmp_topk_select_radix_workspace",
     "gnnmp_gat_conv_edge_stats_f32", "gnnmp_gat_conv_edge_grad_f32", "gnnmp_gat_edge_fold_f32", "gnnmp_gat_edge_fold_grad_f32",
@@ -406,6 +406,22 @@ class AttnEdgeGradJob(ctypes.Structure):
                 ("negative_slope", ctypes.c_float), ("scale", ctypes.c_float)]
 
 
+class AttnWideJob(ctypes.Structure):
+    """gnnmp_attn_wide_t: one gnnmp_attn_conv_wide_f32 call (Q | None, K, V | None, a, bias | None read; out, stats | None written)"""
+    _fields_ = [("Q", ctypes.c_void_p), ("K", ctypes.c_void_p), ("V", ctypes.c_void_p), ("a", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("negative_slope", ctypes.c_float), ("scale", ctypes.c_float),
+                ("act", ctypes.c_int)]
+
+
+class AttnWideGradJob(ctypes.Structure):
+    """gnnmp_attn_wide_grad_t: one gnnmp_attn_conv_wide_grad_f32 call (the forward's inputs, stats, dout read; line and dA scratch; dQ,
+    dK, dV (DOT) and da | None (GAT, GATV2) written)"""
+    _fields_ = [("Q", ctypes.c_void_p), ("K", ctypes.c_void_p), ("V", ctypes.c_void_p), ("a", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+                ("dout", ctypes.c_void_p), ("line", ctypes.c_void_p), ("dQ", ctypes.c_void_p), ("dK", ctypes.c_void_p),
+                ("dV", ctypes.c_void_p), ("dA", ctypes.c_void_p), ("da", ctypes.c_void_p), ("negative_slope", ctypes.c_float),
+                ("scale", ctypes.c_float)]
+
+
 class GatEdgeGradJob(ctypes.Structure):
     """gnnmp_gat_edge_grad_t: one gnnmp_gat_conv_edge_grad_f32 call (Wx_src, Wx_dst | None, a, edge_score, stats, dout read; line scratch;
     dsd, dss, dWx_src, dWx_dst (bipartite), da | None and dscore written)"""
@@ -590,6 +606,8 @@ def load():
         "gnnmp_outer_accum_f32": [ctypes.POINTER(OuterAccumJob), i64, i64, i64, vp],
         "gnnmp_attn_conv_edge_f32": [vp, i, ctypes.POINTER(AttnEdgeJob), i64, i64, vp],
         "gnnmp_attn_conv_edge_grad_f32": [vp, vp, i, ctypes.POINTER(AttnEdgeGradJob), i64, i64, vp],
+        "gnnmp_attn_conv_wide_f32": [vp, i, ctypes.POINTER(AttnWideJob), i64, i64, vp],
+        "gnnmp_attn_conv_wide_grad_f32": [vp, vp, i, ctypes.POINTER(AttnWideGradJob), i64, i64, vp],
         "gnnmp_plan_keep_nodes": [ctypes.POINTER(vp), vp, vp, vp, vp, vp, ctypes.POINTER(i64), vp],
         "gnnmp_topk_score_f32": [vp, vp, vp, i64, i64, vp],
         "gnnmp_topk_select_f32": [ctypes.POINTER(TopkJob), i64, vp],

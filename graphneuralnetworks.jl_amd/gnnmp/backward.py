@@ -677,6 +677,13 @@ def gat_conv_ad(l, g: GNNGraph, x, e=None, seed=None):
         check_num_edges(g, e)
         return _GATConvEdgeFn.apply(x, e, l.dense_x_weight, dense_e, l.a, l.bias, g, l.sigma, l.heads, l.negative_slope, bool(l.concat))
     p_drop = float(getattr(l, "dropout", 0.0))
+    from .layers_attn import row_is_wide
+    if row_is_wide(l.heads, l.channel[1], "GATConv"):              # wider than a wave: the head-tiled kernels (csrc/attn_wide.hip)
+        if p_drop > 0.0:
+            from .layers import _check_drop_width
+            _check_drop_width(l.heads, l.channel[1], "GATConv")
+        from .backward_attn_wide import gat_conv_wide_ad
+        return gat_conv_wide_ad(l, g, x)
     if p_drop > 0.0:
         if seed is None:
             seed = l.next_seed()

@@ -13,7 +13,7 @@ from . import _lib as L
 from .backward import _act_code, act_grad, dense_grad_w, dense_grad_x, plan_transposed
 from .graph import GNNGraph, check_num_edges, check_num_nodes
 from .layers import dense
-from .layers_attn import ATTN_DOT, ATTN_GATV2, SELF_LOOPS_MSG, check_edge_row_width
+from .layers_attn import ATTN_DOT, ATTN_GATV2, SELF_LOOPS_MSG, check_edge_row_width, row_is_wide
 
 
 def _attn_forward(plan, mode, Q, K, V, a, slope, scale, bias, act, H, C, p_drop=0.0, seed=0):
@@ -188,6 +188,12 @@ def gatv2_conv_ad(l, g: GNNGraph, x, e=None, seed=None):
         return _GATv2ConvEdgeFn.apply(x, e, l.dense_i_weight, l.dense_i_bias, l.dense_j_weight, l.dense_e_weight, l.a, l.bias, g,
                                       l.sigma, l.heads, l.negative_slope, bool(l.concat))
     p_drop = float(getattr(l, "dropout", 0.0))
+    if row_is_wide(l.heads, l.channel[1], "GATv2Conv"):            # wider than a wave: the head-tiled kernels (csrc/attn_wide.hip)
+        if p_drop > 0.0:
+            from .layers import _check_drop_width
+            _check_drop_width(l.heads, l.channel[1], "GATv2Conv")
+        from .backward_attn_wide import gatv2_conv_wide_ad
+        return gatv2_conv_wide_ad(l, g, x)
     if p_drop > 0.0:
         if seed is None:
             seed = l.next_seed()
@@ -352,6 +358,9 @@ def transformer_conv_ad(l, g: GNNGraph, x, e=None):
         return _TransformerConvEdgeFn.apply(x, e, l.W1_weight, l.W1_bias, l.W2_weight, l.W2_bias, l.W3_weight, l.W3_bias, l.W4_weight,
                                             l.W4_bias, l.W6_weight, l.W6_bias, g, l.heads, l.sqrt_out, bool(l.skip_connection),
                                             bool(l.concat))
+    if row_is_wide(l.heads, l.channels[1], "TransformerConv"):     # wider than a wave: the head-tiled kernels (csrc/attn_wide.hip)
+        from .backward_attn_wide import transformer_conv_wide_ad
+        return transformer_conv_wide_ad(l, g, x)
     return _TransformerConvFn.apply(x, l.W1_weight, l.W1_bias, l.W2_weight, l.W2_bias, l.W3_weight, l.W3_bias, l.W4_weight,
                                     l.W4_bias, g, l.heads, l.sqrt_out, bool(l.add_self_loops), bool(l.skip_connection),
                                     bool(l.concat))

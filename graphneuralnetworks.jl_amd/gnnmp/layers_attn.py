@@ -37,6 +37,38 @@ def attn_conv(plan, mode, K, Q=None, V=None, a=None, slope=0.2, scale=1.0, bias=
     return out
 
 
+def head_tiles(H, C):
+    """(v, lanes a head, heads a tile, tiles) of csrc/headgeom.h's head_tiles at the 16-byte aligned arrays torch allocates"""
+    v = 4 if C % 4 == 0 else 2 if C % 2 == 0 else 1
+    lph = C // v
+    hpt = max(1, min(H, 64 // lph))
+    return v, lph, hpt, -(-H // hpt)
+
+
+def row_is_wide(H, C, what):
+    """does the [H*C] row need the head-tiled kernels of csrc/attn_wide.hip (it does not fit one wave)?  Refuses by name, before any C
+    call, a single head that does not fit one wave either"""
+    v, lph, _, _ = head_tiles(H, C)
+    if H * C // v <= 64:
+        return False
+    if lph > 64:
+        raise ValueError(f"{what}: a head of out = {C} channels is {lph} lanes of {v} floats; a head must fit one wave (at most 64)")
+    return True
+
+
+def attn_conv_wide(plan, mode, K, Q=None, V=None, a=None, slope=0.2, scale=1.0, bias=None, act=L.ACT_IDENTITY, H=1, C=None,
+                   stats=None):
+    """attn_conv for rows wider than a wave: one wave a (row, head tile), logits GAT | GATV2 | DOT (include/gnnmp.h:
+    gnnmp_attn_conv_wide_f32); no dropout and no edge features there"""
+    N = plan.n_dst
+    C = K.shape[1] // H if C is None else C
+    out = torch.empty((N, H * C), dtype=torch.float32, device=K.device)
+    job = L.AttnWideJob(L.ptr(Q), L.ptr(K), L.ptr(V), L.ptr(a), L.ptr(bias), L.ptr(out), L.ptr(stats), float(slope), float(scale),
+                        int(act))
+    L.check(L.load().gnnmp_attn_conv_wide_f32(plan.handle, mode, job, H, C, L.stream_ptr()))
+    return out
+
+
 SELF_LOOPS_MSG = "Using edge features and setting add_self_loops=true at the same time is not yet supported."
 
 
@@ -120,6 +152,10 @@ def gatv2_conv(l, g: GNNGraph, x, e=None, seed=None):
         if seed is None:
             seed = l.next_seed()
         l.last_seed = int(seed)
+    if p_drop == 0.0 and row_is_wide(H, C, "GATv2Conv"):
+        out = attn_conv_wide(plan, ATTN_GATV2, Wxj, Q=Wxi, a=l.a_hc, slope=l.negative_slope, bias=b,
+                             act=code if fuse else L.ACT_IDENTITY, H=H, C=C)
+        return _heads_tail(out, l, g.num_nodes, H, C)
     out = attn_conv(plan, ATTN_GATV2, Wxj, Q=Wxi, a=l.a_hc, slope=l.negative_slope, bias=b,
                     act=code if fuse else L.ACT_IDENTITY, H=H, C=C, dropout=p_drop, seed=0 if seed is None else seed)
     return _heads_tail(out, l, g.num_nodes, H, C)
@@ -229,6 +265,8 @@ def transformer_conv(l, g: GNNGraph, x, e=None):
     if e is not None:
         W6e = dense(e.contiguous(), l.W6_weight, l.W6_bias)
         h = attn_conv_edge(plan, ATTN_DOT, W4x, W6e, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
+    elif row_is_wide(H, C, "TransformerConv"):
+        h = attn_conv_wide(plan, ATTN_DOT, W4x, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
     else:
         h = attn_conv(plan, ATTN_DOT, W4x, Q=W3x, V=W2x, scale=l.sqrt_out, H=H, C=C)
     lib = L.load()

@@ -43,7 +43,8 @@
  *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
  *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_lstm_matvec_cell_f32 /
  *     gnnmp_lstm_matvec_grad_f32 / gnnmp_outer_accum_f32 (tests/test_evolve_gcno.py: a whole training step) and
- *     gnnmp_attn_conv_edge_f32 / gnnmp_attn_conv_edge_grad_f32 (tests/test_attn_edge.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
+ *     gnnmp_attn_conv_edge_f32 / gnnmp_attn_conv_edge_grad_f32 (tests/test_attn_edge.py) and gnnmp_attn_conv_wide_f32 / gnnmp_attn_conv_wide_grad_f32
+ *     (tests/test_attn_wide.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
  *     no host synchronisation when the pool holds a stream-released block that fits (a warm pool), but a miss is a hipMalloc and a
  *     block parked by a plain destroy costs a device synchronisation: create such objects outside a capture.
  *   - a plan carries scratch of its own (the partials of split rows, the tile ticket of the fused layer kernel, cached
@@ -875,6 +876,69 @@ typedef struct {
     float scale;
 } gnnmp_attn_edge_grad_t;
 int gnnmp_attn_conv_edge_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, int mode, const gnnmp_attn_edge_grad_t *job,
+                                  int64_t H, int64_t C, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attention on feature rows WIDER than a wave, forward and pullback — gat_conv, gatv2_conv and transformer_conv at heads * out > 256
+ * (csrc/attn_wide.hip).  The logits, the softmax and the arrays are those of gnnmp_attn_conv_f32 for GNNMP_ATTN_GAT, _GATV2 and _DOT;
+ * what differs is the split of the work: a wave takes one (row, head tile) of min(H, 64 / lph) whole heads, lph = C / v lanes a head,
+ * v = 4, 2 or 1 floats a lane by the rule of gnnmp_gat_conv_stats_f32 (the alignment of ALL [.][H*C] arrays of the call, then halved
+ * until it divides C).  A HEAD must fit one wave: lph > 64 (C = 130; C = 100 at 4-byte aligned pointers) is GNNMP_EUNSUPPORTED with
+ * nothing written.  A row that fits one wave is accepted too (one tile).
+ *   gnnmp_attn_conv_wide_f32        out = act(o + bias) (act = identity | relu, bias nullable), stats[i][h] = (m_i, den_i) when the
+ *                                   pointer is non-NULL.  One pass, online softmax; a row without in-edges gets act(bias) and (-Inf, 0).
+ *   gnnmp_attn_conv_wide_grad_f32   dout = Δ w.r.t. o; g_ij = Δ_i . V_j, D_i = Σ_j α_ij g_ij, dl_ij = α_ij (g_ij - D_i), α rebuilt from
+ *                                   stats.  GATV2 and DOT: the formulas of gnnmp_attn_conv_grad_f32.  GAT, with z_ij = a_d . Q_i +
+ *                                   a_s . K_j and dz_ij = dl_ij leakyrelu'(z_ij):  dQ_i = a_d Σ_j dz_ij,  dK_j = Σ_i α_ij Δ_i + a_s Σ_i dz_ij,
+ *                                   da[h] = [Σ_i (Σ_j dz_ij) Q_i | Σ_j (Σ_i dz_ij) K_j].  Pass 1 over plan: D_i, dQ_i, the destinations'
+ *                                   terms of da and the line (m, 1/den, D, a_d . Q_i) per (i, h); pass 2 over plan_t: dK_j, DOT dV_j,
+ *                                   GAT the sources' terms of da; da is folded from the per-node terms, rows in order, then a tree.
+ *                                   With Q NULL (= K) on a square plan dK holds the WHOLE gradient of that one array (dQ is written too).
+ *   plan, plan_t   the graph's plan (with or without plan-added self loops) and the plan of the reversed edge index, built alike.
+ *                  They are only READ and their chunks are ignored: every row is walked whole by one wave a head tile, in slot order —
+ *                  no plan scratch, no atomics, every output element written exactly once, two calls give equal bits, and a capture
+ *                  needs no eager call first.  A hub row is therefore slow.  The lane group is the head tile: the geometry knobs of
+ *                  gnnmp_tune (FORCE_LOG2G, UNROLL, BLOCK_WAVES) change nothing here and refuse nothing.
+ *   job            a const HOST record of device pointers.  Q NULL = K; V NULL = K (a separate V only with DOT).  The gradient record
+ *                  carries the forward's inputs, its stats, dout, the caller's scratch line [n_dst][H][4] (16-byte aligned) and the
+ *                  outputs dQ [n_dst][H*C], dK [n_src][H*C]; DOT: dV [n_src][H*C]; GATV2: dA [n_dst][H*C] and da [H][C]; GAT: dA
+ *                  [n_dst + n_src][H*C] and da [H][2C] (da nullable; dA is scratch the call fills).  Every element of every output is written.
+ * Refused before any HIP call — GNNMP_EINVAL: a NULL plan, job or required pointer; a mode outside the enum; H or C < 1 or H*C > 2^20;
+ * an act other than identity / relu; a plan_t that is not the plan's transpose; a separate V without DOT; a bipartite plan without a
+ * separate Q; a line that is not 16-byte aligned.  GNNMP_EUNSUPPORTED: GNNMP_ATTN_COS (single-head: its head is the row); lph > 64.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *Q;    /* [n_dst][H*C] or NULL (= K) */
+    const float *K;    /* [n_src][H*C] */
+    const float *V;    /* [n_src][H*C] or NULL (= K); separate only with DOT */
+    const float *a;    /* GAT: [H][2C]; GATV2: [H][C] */
+    const float *bias; /* [H*C] or NULL */
+    float *out;        /* [n_dst][H*C] */
+    float *stats;      /* [n_dst][H][2] or NULL */
+    float negative_slope;
+    float scale;
+    int act;
+} gnnmp_attn_wide_t;
+int gnnmp_attn_conv_wide_f32(const gnnmp_graph_t *plan, int mode, const gnnmp_attn_wide_t *job, int64_t H, int64_t C,
+                             gnnmp_stream_t stream);
+
+typedef struct {
+    const float *Q;     /* as in the forward */
+    const float *K;
+    const float *V;
+    const float *a;
+    const float *stats; /* [n_dst][H][2], from the forward */
+    const float *dout;  /* [n_dst][H*C] */
+    float *line;        /* [n_dst][H][4], 16-byte aligned scratch */
+    float *dQ;          /* [n_dst][H*C] */
+    float *dK;          /* [n_src][H*C] */
+    float *dV;          /* DOT: [n_src][H*C] */
+    float *dA;          /* GATV2: [n_dst][H*C]; GAT: [n_dst + n_src][H*C] */
+    float *da;          /* GATV2: [H][C], GAT: [H][2C], or NULL */
+    float negative_slope;
+    float scale;
+} gnnmp_attn_wide_grad_t;
+int gnnmp_attn_conv_wide_grad_f32(const gnnmp_graph_t *plan, const gnnmp_graph_t *plan_t, int mode, const gnnmp_attn_wide_grad_t *job,
                                   int64_t H, int64_t C, gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
