@@ -10,20 +10,28 @@
 // gnnmp_poly_hop_ld_f32 launches the SAME template with a row stride of its own for each of z, self, prev, add and out, so that the basis
 // of a recurrent cell's state lands in the column blocks of one panel [N][B D] (gnnmp/layers_temporal.py); gnnmp_poly_hop_f32 passes D
 // five times and keeps its bits.
-// The hop is a whole-row walk on the shared pieces and conventions of slotwalk.h (no atomics, every output written once, a hub row by one
-// lane group: correct, slow).  It reads col only, never eid: a plan with self loops of its own is fine.
+// The hop is a row walk on the shared pieces and conventions of slotwalk.h (no atomics, every output written once).  It reads col only,
+// never eid: a plan with self loops of its own is fine.  It has TWO ROUTES:
+//   whole   gnnmp_poly_hop_f32 / gnnmp_poly_hop_ld_f32: plan_rows_whole, a hub row by one lane group — correct, slow on hubs.
+//   split   gnnmp_poly_hop_split_f32, two launches.  CHUNK PASS: the same template over plan_rows(plan) (SPLIT = true): a chunk virtual
+//           row accumulates its slots exactly as a row does and stores its unscaled partial to the caller's workspace [n_chunks][D]
+//           (store_partial); a row up to long_thresh runs the whole route's instructions and epilogue and keeps its bits; the virtual
+//           row of a split row does nothing.  FOLD PASS: poly_hop_fold_kernel, one lane group a split row and feature tile, adds the
+//           row's partials in chunk order, U = 4 partial rows in flight (fold_partials), then runs hop_epilogue — the ONE epilogue of
+//           both kernels.  A hub of 12 389 slots is ~100 lane groups of work instead of one; the fold reads ~100 rows of D floats.
+//           Nothing is cleared, nothing of the plan is written, every partial the fold reads was stored by the launch before it.
 //
 // The epilogue's products and sums are separate roundings in the order of the header: this file is compiled with -ffp-contract=off like
 // the rest of the library (Makefile), nothing here is an fmaf.
 // Registers: U = 4 slots in flight, one gathered vector a slot — 16 VGPRs of loads with 16-byte lanes.  The compiler's resource report
-// (LABNOTES.md) shows no scratch for any instance.
+// (LABNOTES.md) shows no scratch for any instance, the SPLIT ones and the fold included.
 #include "csr_reduce.h"
 #include "launch.h"
 
 namespace gnnmp {
 
 struct PolyHopArgs {
-    PlanRows rows;               // the plan or the transposed plan, whole rows (plan_rows_whole)
+    PlanRows rows;               // the plan or the transposed plan: whole rows (plan_rows_whole), or plan_rows for the split route
     RowGeom geom;
     const float *z;              // [n_src][D]
     const float *w_slot;         // [n_total] or null, read by the SCALED instances only
@@ -34,12 +42,45 @@ struct PolyHopArgs {
     float *out;                  // [n_dst][D]
     int D;
     int64_t ldz, lds, ldp, lda, ldo;      // row strides in floats of z, self_, prev, add, out: all D for gnnmp_poly_hop_f32, a panel's for _ld
+    float *partial;              // [n_chunks][D] the split route's workspace (the SPLIT instances and the fold only)
 };
 
-template <int VEC, int U, bool SCALED>
+// out_row = alpha (agg scale_dst) + beta self + gamma prev + add for the lane's VEC features of `row`, every product and sum rounded on its
+// own, in the header's order; the store comes after every load of this lane: out may be prev or add
+template <int VEC>
+__device__ __forceinline__ void hop_epilogue(const PolyHopArgs &a, int row, int f0, float acc[VEC]) {
+    if (a.sd) {
+        const float sc = a.sd[row];
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) acc[q] = acc[q] * sc;
+    }
+    float r[VEC], t[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) r[q] = a.alpha * acc[q];
+    if (a.self_) {
+        Vec<VEC>::load(a.self_ + (int64_t)row * a.lds + f0, t);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.beta * t[q];
+    }
+    if (a.prev) {
+        Vec<VEC>::load(a.prev + (int64_t)row * a.ldp + f0, t);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.gamma * t[q];
+    }
+    if (a.add) {
+        Vec<VEC>::load(a.add + (int64_t)row * a.lda + f0, t);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) r[q] = r[q] + t[q];
+    }
+    Vec<VEC>::store(a.out + (int64_t)row * a.ldo + f0, r);
+}
+
+// SPLIT: the chunk pass of the split route — the rows are plan_rows(plan), a chunk stores its partial, a split row's own virtual row
+// returns in the decode
+template <int VEC, int U, bool SCALED, bool SPLIT = false>
 __global__ void __launch_bounds__(256) poly_hop_kernel(const PolyHopArgs a) {
     RowLane w;
-    if (!decode_row_lane<VEC>(a.rows, a.geom, a.D, w)) return;
+    if (!decode_row_lane<VEC, SPLIT ? VROW_NO_CHUNK_ROW : VROW_WHOLE>(a.rows, a.geom, a.D, w)) return;
     const int f0 = w.f0;
     const bool active = w.active;
     float acc[VEC];
@@ -83,30 +124,21 @@ __global__ void __launch_bounds__(256) poly_hop_kernel(const PolyHopArgs a) {
         }
     }
     if (!active) return;
-    if (a.sd) {
-        const float sc = a.sd[w.row];
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) acc[q] = acc[q] * sc;
+    if (SPLIT && w.is_chunk) {
+        store_partial<VEC>(a.partial, a.D, w, acc);
+        return;
     }
-    float r[VEC], t[VEC];
-#pragma unroll
-    for (int q = 0; q < VEC; ++q) r[q] = a.alpha * acc[q];
-    if (a.self_) {
-        Vec<VEC>::load(a.self_ + (int64_t)w.row * a.lds + f0, t);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.beta * t[q];
-    }
-    if (a.prev) {
-        Vec<VEC>::load(a.prev + (int64_t)w.row * a.ldp + f0, t);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) r[q] = r[q] + a.gamma * t[q];
-    }
-    if (a.add) {
-        Vec<VEC>::load(a.add + (int64_t)w.row * a.lda + f0, t);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) r[q] = r[q] + t[q];
-    }
-    Vec<VEC>::store(a.out + (int64_t)w.row * a.ldo + f0, r);      // after every load of this lane: out may be prev or add
+    hop_epilogue<VEC>(a, w.row, f0, acc);
+}
+
+// the fold pass of the split route: split row long_rows[l] = its partials added in chunk order, then the epilogue
+template <int VEC, int U>
+__global__ void __launch_bounds__(256) poly_hop_fold_kernel(const PolyHopArgs a) {
+    LongLane w;
+    if (!decode_long_lane<VEC>(a.rows, a.geom, a.D, w) || !w.active) return;
+    float acc[VEC];
+    fold_partials<VEC, U>(a.partial, a.D, w, acc);
+    hop_epilogue<VEC>(a, w.row, w.f0, acc);
 }
 
 // dh may be base: each element is read, then written, by one thread (no __restrict__ on the two)
@@ -150,19 +182,35 @@ using namespace gnnmp;
 namespace gnnmp {
 namespace {
 
-// the launch both hop exports share: `a` is complete but for rows / geom; align_extra carries the row strides' bytes into the lane-width choice
+// the launch the hop exports share: `a` is complete but for rows / geom; align_extra carries the row strides' bytes into the lane-width
+// choice.  a.partial given and a plan with split rows: the split route's two launches (the workspace takes part in the lane-width
+// choice like any operand); otherwise the whole-row kernel.
 int launch_poly_hop(const char *who, const gnnmp_graph_t *plan, PolyHopArgs &a, bool scaled, uintptr_t align_extra, hipStream_t stream) {
-    a.rows = plan_rows_whole(plan);
+    const bool split = a.partial && plan->n_long > 0;
+    a.rows = split ? plan_rows(plan) : plan_rows_whole(plan);
     dim3 grid;
-    const int vec = row_walk_geom(who, a.rows, a.D, 0, {a.z, a.self_, a.prev, a.add, a.out}, a.geom, grid, align_extra);
+    const int vec = row_walk_geom(who, a.rows, a.D, 0, {a.z, a.self_, a.prev, a.add, a.out, a.partial}, a.geom, grid, align_extra);
     if (vec < 0) return vec;
+    if (!split) {
+        with_vec(vec, [&](auto V) {
+            if (scaled)
+                poly_hop_kernel<decltype(V)::value, 4, true><<<grid, 256, 0, stream>>>(a);
+            else
+                poly_hop_kernel<decltype(V)::value, 4, false><<<grid, 256, 0, stream>>>(a);
+        });
+        GNNMP_LAUNCH_CHECK("poly_hop_kernel");
+        return GNNMP_OK;
+    }
     with_vec(vec, [&](auto V) {
         if (scaled)
-            poly_hop_kernel<decltype(V)::value, 4, true><<<grid, 256, 0, stream>>>(a);
+            poly_hop_kernel<decltype(V)::value, 4, true, true><<<grid, 256, 0, stream>>>(a);
         else
-            poly_hop_kernel<decltype(V)::value, 4, false><<<grid, 256, 0, stream>>>(a);
+            poly_hop_kernel<decltype(V)::value, 4, false, true><<<grid, 256, 0, stream>>>(a);
     });
-    GNNMP_LAUNCH_CHECK("poly_hop_kernel");
+    GNNMP_LAUNCH_CHECK("poly_hop_kernel (chunk pass)");
+    const dim3 fold = long_grid(a.rows, a.geom, (int)grid.y);
+    with_vec(vec, [&](auto V) { poly_hop_fold_kernel<decltype(V)::value, 4><<<fold, 256, 0, stream>>>(a); });
+    GNNMP_LAUNCH_CHECK("poly_hop_fold_kernel");
     return GNNMP_OK;
 }
 
@@ -211,8 +259,11 @@ extern "C" int gnnmp_poly_hop_f32(const gnnmp_graph_t *plan, const gnnmp_poly_ho
     return launch_poly_hop(who, plan, a, job->w_slot || job->ss_slot, 0, (hipStream_t)stream);
 }
 
-extern "C" int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, gnnmp_stream_t stream) {
-    const char *who = "poly_hop_ld";
+namespace gnnmp {
+namespace {
+
+// every refusal gnnmp_poly_hop_ld_f32 makes, under the name `who`
+int check_hop_ld(const char *who, const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D) {
     if (!plan) return fail(GNNMP_EINVAL, "%s: null plan", who);
     if (!job) return fail(GNNMP_EINVAL, "%s: null job", who);
     if (!job->z) return fail(GNNMP_EINVAL, "%s: null z", who);
@@ -239,8 +290,12 @@ extern "C" int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly
         return fail(GNNMP_EINVAL, "%s: out overlaps add without being it (same pointer, same stride)", who);
     if (job->beta != 0.0f && !job->self) return fail(GNNMP_EINVAL, "%s: beta != 0 with a null self", who);
     if (job->gamma != 0.0f && !job->prev) return fail(GNNMP_EINVAL, "%s: gamma != 0 with a null prev", who);
-    if (plan->n_dst == 0) return GNNMP_OK;
-    PolyHopArgs a = {};
+    return GNNMP_OK;
+}
+
+// the kernel's arguments of a checked strided record; returns the row strides' bytes or-ed together: a lane's 16- / 8-byte access at row
+// i is aligned when the base and the stride's bytes are, so they go into the alignment word
+uintptr_t fill_hop_ld(const gnnmp_poly_hop_ld_t *job, int64_t D, PolyHopArgs &a) {
     a.z = job->z;
     a.w_slot = job->w_slot;
     a.ss_slot = job->ss_slot;
@@ -258,8 +313,60 @@ extern "C" int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly
     a.lds = job->self ? job->ld_self : D;
     a.ldp = job->prev ? job->ld_prev : D;
     a.lda = job->add ? job->ld_add : D;
-    // a lane's 16- / 8-byte access at row i is aligned when the base and the stride's bytes are: fold the strides into the alignment word
-    const uintptr_t strides = (uintptr_t)(a.ldz | a.ldo | a.lds | a.ldp | a.lda) * 4;
+    return (uintptr_t)(a.ldz | a.ldo | a.lds | a.ldp | a.lda) * 4;
+}
+
+// do the byte spans [p, p + pbytes) and (rows rows of D floats, row stride ld, from q) meet?
+bool span_meets(const void *p, int64_t pbytes, const float *q, int64_t ld, int64_t rows, int64_t D) {
+    if (!p || !q || pbytes < 1 || rows < 1) return false;
+    const uintptr_t pb = reinterpret_cast<uintptr_t>(p), qb = reinterpret_cast<uintptr_t>(q);
+    return pb < qb + (uintptr_t)(((rows - 1) * ld + D) * 4) && qb < pb + (uintptr_t)pbytes;
+}
+
+}  // namespace
+}  // namespace gnnmp
+
+extern "C" int gnnmp_poly_hop_ld_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, gnnmp_stream_t stream) {
+    const char *who = "poly_hop_ld";
+    const int rc = check_hop_ld(who, plan, job, D);
+    if (rc != GNNMP_OK) return rc;
+    if (plan->n_dst == 0) return GNNMP_OK;
+    PolyHopArgs a = {};
+    const uintptr_t strides = fill_hop_ld(job, D, a);
+    return launch_poly_hop(who, plan, a, job->w_slot || job->ss_slot, strides, (hipStream_t)stream);
+}
+
+extern "C" int gnnmp_poly_hop_split_workspace(const gnnmp_graph_t *plan, int64_t D, int64_t *bytes) {
+    const char *who = "poly_hop_split_workspace";
+    if (!plan) return fail(GNNMP_EINVAL, "%s: null plan", who);
+    if (!bytes) return fail(GNNMP_EINVAL, "%s: null bytes", who);
+    if (D < 1 || D > (1 << 19)) return fail(GNNMP_EINVAL, "%s: bad D %lld (1 .. 2^19)", who, (long long)D);
+    *bytes = plan->n_long > 0 ? (int64_t)plan->n_chunks * D * 4 : 0;
+    return GNNMP_OK;
+}
+
+extern "C" int gnnmp_poly_hop_split_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, void *workspace,
+                                        int64_t workspace_bytes, gnnmp_stream_t stream) {
+    const char *who = "poly_hop_split";
+    const int rc = check_hop_ld(who, plan, job, D);
+    if (rc != GNNMP_OK) return rc;
+    const int64_t need = plan->n_long > 0 ? (int64_t)plan->n_chunks * D * 4 : 0;
+    if (need > 0) {
+        if (!workspace) return fail(GNNMP_EINVAL, "%s: null workspace (the plan splits %d rows)", who, plan->n_long);
+        if (workspace_bytes < need)
+            return fail(GNNMP_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
+        if (reinterpret_cast<uintptr_t>(workspace) % 4) return fail(GNNMP_EINVAL, "%s: workspace not 4-byte aligned", who);
+        const struct { const char *name; const float *p; int64_t ld, rows; } ops[] = {
+            {"z", job->z, job->ld_z, plan->n_src},        {"self", job->self, job->ld_self, plan->n_dst},
+            {"prev", job->prev, job->ld_prev, plan->n_dst}, {"add", job->add, job->ld_add, plan->n_dst},
+            {"out", job->out, job->ld_out, plan->n_dst}};
+        for (const auto &o : ops)
+            if (span_meets(workspace, need, o.p, o.ld, o.rows, D)) return fail(GNNMP_EINVAL, "%s: workspace overlaps %s", who, o.name);
+    }
+    if (plan->n_dst == 0) return GNNMP_OK;
+    PolyHopArgs a = {};
+    const uintptr_t strides = fill_hop_ld(job, D, a);
+    a.partial = need > 0 ? static_cast<float *>(workspace) : nullptr;
     return launch_poly_hop(who, plan, a, job->w_slot || job->ss_slot, strides, (hipStream_t)stream);
 }
 

@@ -63,7 +63,7 @@ SYMBOLS = (
     "gnnmp_segment_attn_pool_f32", "gnnmp_segment_attn_pool_grad_f32", "gnnmp_lstm_pointwise_grad_f32",
     "gnnmp_segment_attn_pool_tiled_f32", "gnnmp_segment_attn_pool_tiled_grad_f32", "gnnmp_segment_attn_tiled_workspace",
     "gnnmp_poly_hop_f32", "gnnmp_gru_pointwise_grad_f32",
-    "gnnmp_poly_hop_ld_f32", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
+    "gnnmp_poly_hop_ld_f32", "gnnmp_poly_hop_split_f32", "gnnmp_poly_hop_split_workspace", "gnnmp_gru_cell_f32", "gnnmp_gru_cell_grad_f32", "gnnmp_lstm_cell_f32", "gnnmp_lstm_cell_grad_f32",
     "gnnmp_lstm_matvec_cell_f32", "gnnmp_lstm_matvec_grad_workspace", "gnnmp_lstm_matvec_grad_f32", "gnnmp_outer_accum_f32",
     "gnnmp_attn_conv_edge_f32", "gnnmp_attn_conv_edge_grad_f32", "gnnmp_attn_conv_wide_f32", "gnnmp_attn_conv_wide_grad_f32",
     "gnnmp_topk_score_f32", "gnnmp_topk_select_f32", "gnnmp_topk_gate_f32", "gnnmp_topk_gate_grad_f32",
@@ -597,6 +597,8 @@ def load():
         "gnnmp_poly_hop_f32": [vp, ctypes.POINTER(PolyHopJob), i64, vp],
         "gnnmp_gru_pointwise_grad_f32": [ctypes.POINTER(GruGradJob), i64, i64, vp],
         "gnnmp_poly_hop_ld_f32": [vp, ctypes.POINTER(PolyHopLdJob), i64, vp],
+        "gnnmp_poly_hop_split_f32": [vp, ctypes.POINTER(PolyHopLdJob), i64, vp, i64, vp],
+        "gnnmp_poly_hop_split_workspace": [vp, i64, ctypes.POINTER(i64)],
         "gnnmp_gru_cell_f32": [i, ctypes.POINTER(GruCellJob), i64, i64, i64, i64, vp],
         "gnnmp_gru_cell_grad_f32": [i, ctypes.POINTER(GruCellGradJob), i64, i64, i64, i64, vp],
         "gnnmp_lstm_cell_f32": [ctypes.POINTER(LstmCellJob), i64, i64, i64, i64, vp],

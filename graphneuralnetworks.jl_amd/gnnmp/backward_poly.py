@@ -21,7 +21,8 @@ needs_input_grad says is not needed is not computed.
 
 The fused forward rounds differently from gnnmp.cheb_conv / gnnmp.d_conv (one epilogue instead of two or three elementwise passes): the
 *_ad functions owe them and the oracle the 1e-5 bar, NOT equal bits.  `gnnmp.cheb_conv` / `gnnmp.d_conv` are unchanged.
-Every row is walked whole by one lane group: slow on hub rows.
+On a plan that splits rows (plan.n_long > 0) every hop takes the split route (poly_hop: route="auto"): hub rows are summed chunk by
+chunk in two launches; on any other plan every call and every bit is the whole-row route's.
 """
 from __future__ import annotations
 
@@ -36,16 +37,47 @@ from .layers import dense
 from .layers_more import _add, scaled_laplacian_op
 
 
-def poly_hop(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=0.0, self_=None, gamma=0.0, prev=None, add=None, out=None):
-    """out [n_dst][D] of gnnmp_poly_hop_f32; out may be prev or add (then the result replaces it), never z or self_"""
+HOP_ROUTES = ("auto", "whole", "split")
+ROUTES_TAKEN = {"whole": 0, "split": 0}      # calls per route since import: what a test or a benchmark reads to see which kernel ran
+
+
+def hop_route(plan, route):
+    """the route a hop over `plan` takes: "auto" is "split" iff the plan splits a row (plan.n_long > 0).  "split" on a plan without split
+    rows is allowed — the split export is the whole-row launch there."""
+    if route not in HOP_ROUTES:
+        raise ValueError(f"poly_hop: route {route!r} is not one of {HOP_ROUTES}")
+    return ("split" if plan.n_long > 0 else "whole") if route == "auto" else route
+
+
+def hop_split(plan, job, D, like):
+    """gnnmp_poly_hop_split_f32 on a strided record: the workspace is a torch allocation of this call, sized by the query export"""
+    lib = L.load()
+    need = ctypes.c_int64()
+    L.check(lib.gnnmp_poly_hop_split_workspace(plan.handle, D, ctypes.byref(need)))
+    ws = torch.empty(need.value // 4, dtype=torch.float32, device=like.device) if need.value else None
+    L.check(lib.gnnmp_poly_hop_split_f32(plan.handle, ctypes.byref(job), D, L.ptr(ws), need.value, L.stream_ptr()))
+    ROUTES_TAKEN["split"] += 1
+
+
+def poly_hop(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=0.0, self_=None, gamma=0.0, prev=None, add=None, out=None,
+             route="auto"):
+    """out [n_dst][D] of gnnmp_poly_hop_f32; out may be prev or add (then the result replaces it), never z or self_.
+    route: "whole" — that export, every row by one lane group; "split" — gnnmp_poly_hop_split_f32 with every stride D: the rows the plan
+    splits are summed chunk by chunk (1e-5 of float64, not the whole route's bits; every other row keeps them); "auto" — hop_route"""
+    route = hop_route(plan, route)
     D = z.shape[1]
     if out is None:
         out = torch.empty((plan.n_dst, D), dtype=torch.float32, device=z.device)
     if plan.n_dst == 0 or D == 0:      # (an empty tensor has no address: nothing to launch, nothing to refuse)
         return out
-    job = L.PolyHopJob(L.ptr(z), L.ptr(w_slot), L.ptr(ss_slot), L.ptr(scale_dst), L.ptr(self_), L.ptr(prev), L.ptr(add), float(alpha),
-                       float(beta), float(gamma), L.ptr(out))
+    args = (L.ptr(z), L.ptr(w_slot), L.ptr(ss_slot), L.ptr(scale_dst), L.ptr(self_), L.ptr(prev), L.ptr(add), float(alpha), float(beta),
+            float(gamma), L.ptr(out))
+    if route == "split":
+        hop_split(plan, L.PolyHopLdJob(*args, D, D, D, D, D), D, z)
+        return out
+    job = L.PolyHopJob(*args)
     L.check(L.load().gnnmp_poly_hop_f32(plan.handle, ctypes.byref(job), D, L.stream_ptr()))
+    ROUTES_TAKEN["whole"] += 1
     return out
 
 

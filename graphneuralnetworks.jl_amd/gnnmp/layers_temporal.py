@@ -247,9 +247,13 @@ def _blk(panel, j, D):
     return panel[:, j * D:(j + 1) * D]
 
 
-def poly_hop_ld(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=0.0, self_=None, gamma=0.0, prev=None, add=None, out=None):
+def poly_hop_ld(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=0.0, self_=None, gamma=0.0, prev=None, add=None, out=None,
+                route="auto"):
     """gnnmp_poly_hop_ld_f32 on column blocks: every operand a [rows][D] view whose last stride is 1 (its row stride is the panel's);
-    out may be prev or add (the same view), never z or self_"""
+    out may be prev or add (the same view), never z or self_.  route: as backward_poly.poly_hop — "split" is gnnmp_poly_hop_split_f32 on
+    the same record, "auto" takes it iff the plan splits a row"""
+    from .backward_poly import ROUTES_TAKEN, hop_route, hop_split
+    route = hop_route(plan, route)
     D = z.shape[1]
     if plan.n_dst == 0 or D == 0:
         return out
@@ -258,7 +262,11 @@ def poly_hop_ld(plan, z, alpha, w_slot=None, ss_slot=None, scale_dst=None, beta=
     ld = [D if o is None else (o.stride(0) if o.shape[0] > 1 else max(o.stride(0), D)) for o in ops]
     job = L.PolyHopLdJob(L.ptr(z), L.ptr(w_slot), L.ptr(ss_slot), L.ptr(scale_dst), L.ptr(self_), L.ptr(prev), L.ptr(add), float(alpha),
                          float(beta), float(gamma), L.ptr(out), ld[0], ld[1], ld[2], ld[3], ld[4])
+    if route == "split":
+        hop_split(plan, job, D, z)
+        return out
     L.check(L.load().gnnmp_poly_hop_ld_f32(plan.handle, ctypes.byref(job), D, L.stream_ptr()))
+    ROUTES_TAKEN["whole"] += 1
     return out
 
 

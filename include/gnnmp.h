@@ -41,7 +41,8 @@
  *     gnnmp_segment_attn_pool_tiled_grad_f32 (tests/test_readout_tiled.py) and
  *     gnnmp_poly_hop_f32 (tests/test_poly_conv_ad.py: over the plan and the transposed plan) and
  *     gnnmp_gru_pointwise_grad_f32 (tests/test_poly_conv_ad.py) and gnnmp_poly_hop_ld_f32 / gnnmp_gru_cell_f32 / gnnmp_gru_cell_grad_f32 /
- *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_lstm_matvec_cell_f32 /
+ *     gnnmp_lstm_cell_f32 / gnnmp_lstm_cell_grad_f32 (tests/test_recurrent_layers.py) and gnnmp_poly_hop_split_f32
+ *     (tests/test_poly_hop_split.py) and gnnmp_lstm_matvec_cell_f32 /
  *     gnnmp_lstm_matvec_grad_f32 / gnnmp_outer_accum_f32 (tests/test_evolve_gcno.py: a whole training step) and
  *     gnnmp_attn_conv_edge_f32 / gnnmp_attn_conv_edge_grad_f32 (tests/test_attn_edge.py) and gnnmp_attn_conv_wide_f32 / gnnmp_attn_conv_wide_grad_f32
  *     (tests/test_attn_wide.py), likewise.  Not tested and not promised: the lifecycle calls — gnnmp_plan_concat / gnnmp_plan_select / gnnmp_chain_jobs_pack make
@@ -2161,8 +2162,8 @@ int64_t gnnmp_segment_attn_tiled_workspace(int64_t N, int64_t G, int64_t D, int6
  *            are folded sequentially in plan order.  The GRU pullback: 1 .. 2^20, one thread an element.
  * Both only launch on `stream`: no atomics, no allocation, no host wait, no scratch, nothing owned by a plan written; each may be
  * recorded into a HIP graph without an eager call first; two calls give equal bits.  n_dst = 0 / N = 0 launches nothing and returns
- * GNNMP_OK.  EVERY ROW IS WALKED WHOLE BY ONE LANE GROUP, whatever its length: correct, and slow for hub rows (where
- * gnnmp_propagate_slots_f32 splits them).
+ * GNNMP_OK.  EVERY ROW IS WALKED WHOLE BY ONE LANE GROUP, whatever its length: correct, and slow for hub rows —
+ * gnnmp_poly_hop_split_f32 (below) is the same call with those rows cut into the plan's chunks.
  * Refused before any HIP call (GNNMP_EINVAL), each message naming its export: a NULL plan or job; a NULL z or out; D outside its range;
  * out == z or out == self; beta != 0 with a NULL self, gamma != 0 with a NULL prev; a NULL gx, gh, h, dout, dgx, dgh or dh; a negative N.
  * ---------------------------------------------------------------------------------------------- */
@@ -2333,6 +2334,44 @@ typedef struct {
     float *peep;             /* [N][T][4D] or NULL: step t written */
 } gnnmp_lstm_cell_grad_t;
 int gnnmp_lstm_cell_grad_f32(const gnnmp_lstm_cell_grad_t *job, int64_t N, int64_t T, int64_t t, int64_t D, gnnmp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The hop with split hub rows (csrc/poly_conv.hip; the shared pieces in csrc/slotwalk.h) — the hop of cheb_conv, GNNlib/src/layers/conv.jl:83-98,
+ * and d_conv, conv.jl:696-724, on graphs with hubs: gnnmp_poly_hop_f32 / gnnmp_poly_hop_ld_f32 walk every row whole with one lane group;
+ * this export cuts the rows longer than the plan's threshold (gnnmp_plan_info: info[7]) into the plan's chunks.
+ *
+ *   gnnmp_poly_hop_split_f32   gnnmp_poly_hop_ld_f32's call — the same record, the same arithmetic in the same order — in two launches:
+ *                        (1) every row of at most long_thresh slots is computed by the whole-row kernel's instructions and HAS
+ *                            gnnmp_poly_hop_ld_f32's BITS; every chunk c of a split row i (the plan's chunks: consecutive slot ranges of
+ *                            the row, in slot order) gets its partial
+ *                                part_c = Σ_{k in chunk c} w_slot[k] * (z[col[k]] * ss_slot[k])     from 0, slot by slot, as a row does
+ *                            stored to workspace[c][D];
+ *                        (2) agg_i = ((0 + part_c0) + part_c0+1) + ... over the row's chunks IN CHUNK ORDER — a fixed order — then
+ *                            the epilogue of gnnmp_poly_hop_f32 (scale_dst, alpha, beta self, gamma prev, add; every product and
+ *                            every sum rounded on its own, in that order) by the same device function.
+ *                        A split row's sum is grouped by chunk: it owes float64 the 1e-5 bar of the hop, NOT the whole-row bits.
+ *                        out MAY BE prev OR add as in gnnmp_poly_hop_ld_f32: each lane reads its own element before it stores it.
+ *                        On a plan without split rows the call IS gnnmp_poly_hop_ld_f32's launch and the workspace is not touched
+ *                        (it may be NULL).
+ *   gnnmp_poly_hop_split_workspace   *bytes = n_chunks * D * 4 for a plan with split rows, 0 for one without.  Host only: no stream
+ *                        work, nothing launched.  GNNMP_EINVAL for a NULL plan or bytes or D outside 1 .. 2^19.
+ *
+ *   plan       any plan, only READ (its chunk tables too); z has n_src rows.
+ *   job        gnnmp_poly_hop_ld_t, as gnnmp_poly_hop_ld_f32 takes it (every stride = D: the layout of gnnmp_poly_hop_f32).
+ *   workspace  device memory of at least gnnmp_poly_hop_split_workspace bytes, 4-byte aligned (16- / 8-byte lanes also ask it to be
+ *              aligned like the operands); the caller's, written in its first n_chunks * D floats only and never read before it is
+ *              written: it needs no clearing.  It must not overlap z, self, prev, add or out.
+ * Launch-only, capturable: it only launches on `stream` — no atomics, no host wait, no plan-owned scratch, nothing owned by the plan
+ * written, so two streams may run it on one plan with a workspace each; it may be recorded into a HIP graph without an eager call
+ * first; two calls give equal bits; every value depends on the plan and the inputs only.  n_dst = 0 launches nothing and returns GNNMP_OK.
+ * Refused before any HIP call (GNNMP_EINVAL, "poly_hop_split: ..."), nothing written: everything gnnmp_poly_hop_ld_f32 refuses, its
+ * overlaps included; with split rows a NULL workspace, workspace_bytes below the query's answer, a workspace that is not 4-byte aligned
+ * or whose first `bytes` bytes meet the span of z, self, prev, add or out.
+ * Tested in tests/test_poly_hop_split.py (memory contract, refusals, capture without an eager call, the layers).
+ * ---------------------------------------------------------------------------------------------- */
+int gnnmp_poly_hop_split_workspace(const gnnmp_graph_t *plan, int64_t D, int64_t *bytes);
+int gnnmp_poly_hop_split_f32(const gnnmp_graph_t *plan, const gnnmp_poly_hop_ld_t *job, int64_t D, void *workspace, int64_t workspace_bytes,
+                             gnnmp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Float64 features (round 6).  The reference's message passing is eltype-generic, and its own micro-benchmark runs in Float64

@@ -11,6 +11,10 @@ GatedGraphConv — on the same device, in one process, alternating.
     gru_grad            gnnmp_gru_pointwise_grad_f32 alone on [N][64]
     ggc_forward         gnnmp.gated_graph_conv(l, g, x), 2 layers, +
     ggc_train           gnnmp.gated_graph_conv_ad(l, g, x).backward(Δ)
+    *_whole / *_split   the fused forwards, the trained layers and the bare hop (`hop`: poly_hop(plan, x, 1.0), one order without factors) with
+                        every hop forced onto route="whole" / route="split" (gnnmp/backward_poly.py: hop_route); the plain names above run
+                        route="auto".  A library without gnnmp_poly_hop_split_f32 (an older build named by GNNMP_LIB) has no *_split entries:
+                        its *_whole entries are the figures to hold this tree's against.
 Workloads, 64 channels: `clouds` — 32 clouds x 1024 points in R^3, knn_graph k = 20 per cloud, made bidirected; `arxiv` — one
 synth.arxiv_like graph (a ring added so that no node is isolated), made bidirected: its hubs are rows that the existing forwards split
 and the fused hop walks with one lane group, so the price of whole-row walks is on record beside the gain.  Device events after --warmup
@@ -30,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "graphneuralnetworks.jl_amd"))
 
 import gnnmp  # noqa: E402
 from gnnmp import synth  # noqa: E402
+from gnnmp import backward_poly as BP  # noqa: E402
 from gnnmp.backward_gated import gru_pointwise_grad  # noqa: E402
 
 C = 64
@@ -73,6 +78,19 @@ def workload(name, g, args, gen):
             return out
         return run
 
+    def forced(route, fn):
+        """fn with every hop of the layers on `route`"""
+        def run():
+            auto, BP.hop_route = BP.hop_route, lambda plan, _: route
+            try:
+                return fn()
+            finally:
+                BP.hop_route = auto
+        return run
+
+    routes = ("whole", "split") if hasattr(gnnmp.load(), "gnnmp_poly_hop_split_f32") else ("whole",)
+    if "split" not in routes:      # an older library: "auto" can only be the whole-row route
+        BP.hop_route = lambda plan, _: "whole"
     gx, gh, b, h = rnd(N, 3 * C), rnd(N, 3 * C), rnd(3 * C), rnd(N, C)
     rel = lambda a, b_: float((a.double() - b_.double()).norm() / b_.double().norm())      # noqa: E731
     worst = max(rel(plain(gnnmp.cheb_conv_ad, cheb)(), plain(gnnmp.cheb_conv, cheb)()),
@@ -87,6 +105,11 @@ def workload(name, g, args, gen):
                ("dconv_train", train(gnnmp.d_conv_ad, dconv)),
                ("gru_grad", lambda: gru_pointwise_grad(gx, gh, b, h, dy)),
                ("ggc_forward", plain(gnnmp.gated_graph_conv, ggc)), ("ggc_train", train(gnnmp.gated_graph_conv_ad, ggc)))
+    hop_plan = g.plan(False)
+    fused = entries[1:3] + entries[4:6]
+    by_route = tuple((f"{k}_{route}", forced(route, fn)) for route in routes for k, fn in fused)
+    by_route += tuple((f"hop_{route}", forced(route, lambda: BP.poly_hop(hop_plan, x, 1.0))) for route in routes)
+    entries = entries[:6] + by_route + entries[6:]
     for _, fn in entries:      # every path once: caches on the graph (slot factors, λmax), and a check that the gradients exist
         fn()
     assert all(v.grad is not None and bool(torch.isfinite(v.grad).all()) for v in [xg] + params[4:])
@@ -99,7 +122,8 @@ def workload(name, g, args, gen):
             "split_rows": int(plan.n_long), "split_rows_transposed": int(pt.n_long), "ms_per_round": rounds, "ms": ms,
             "cheb_forward_over_fused": ms["cheb_forward"] / ms["cheb_fused_forward"],
             "dconv_forward_over_fused": ms["dconv_forward"] / ms["dconv_fused_forward"],
-            "worst_rel_between_forwards": worst}
+            "split_over_whole": {k[:-6]: ms[k] / ms[k[:-6] + "_whole"] for k in ms if k.endswith("_split")},
+            "auto_route": BP.hop_route(plan, "auto"), "worst_rel_between_forwards": worst}
 
 
 def main():
