@@ -2,7 +2,8 @@
 //   knn_graph(points, k; graph_indicator, self_loops, dir)      GNNGraphs/src/generate.jl:112-145
 //   radius_graph(points, r; graph_indicator, self_loops, dir)   GNNGraphs/src/generate.jl:196-222
 //   hyperbolic_graph(points, R, zeta; ...)                      the N x N loop of rand_temporal_hyperbolic_graph, generate.jl:287-297, 359-369
-// The reference builds a KDTree / BallTree on the CPU (NearestNeighbors.jl).  Here: brute force in fp32, one kernel skeleton for both.
+// The reference builds a KDTree / BallTree on the CPU (NearestNeighbors.jl).  Here: brute force in fp32, one kernel skeleton for both
+// (radius_graph on d <= 3 also has the cell-grid route of neighbors_grid.hip, chosen in threshold_graph below: the same plan, bit for bit).
 //
 // Semantics (gnnmp.h states them for callers): d2(i, j) = fma chain over the dimensions in order, a non-finite d2 ranks as +inf,
 // candidates are ordered by the pair (d2, j) — a total order, so the result does not depend on the tiling and reruns are bit-identical.
@@ -34,6 +35,8 @@
 #include <cmath>
 
 #include "common.h"
+#include "neighbors_grid.h"
+#include "neighbors_route.h"
 #include "scratch.h"
 #include "sort_scan.h"
 
@@ -389,41 +392,112 @@ int alloc_plan_slots(gnnmp_graph_t *p, int64_t E) {
     return GNNMP_OK;
 }
 
+// the calling thread's record of its last threshold search (gnnmp_debug_neighbors_route) and the route it asked for
+// (gnnmp_debug_neighbors_force): {route, cells per axis x 3, points in the fullest cell, reason code, spare, spare}
+int (&nb_route_record())[8] {
+    static thread_local int r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    return r;
+}
+int &nb_forced_route() {
+    static thread_local int f = NB_FORCE_AUTO;
+    return f;
+}
+const char *nb_why_text(int why) {
+    switch (why) {
+        case NB_WHY_DIM: return "d > 3";
+        case NB_WHY_UNSORTED: return "the graph_indicator is not sorted";
+        case NB_WHY_R2_INF: return "r * r overflows float32";
+        case NB_WHY_N_RANGE: return "N is outside the grid's range";
+        case NB_WHY_GRAPHS: return "more graphs than the cell table holds";
+        case NB_WHY_METRIC: return "the hyperbolic metric has no grid";
+        default: return "the call cannot take the grid";
+    }
+}
+
+// points in the fullest cell: the largest difference of two neighbouring entries of the cell-start table (debug record only)
+__global__ void grid_fullest_kernel(const uint32_t *start, int64_t cells, unsigned long long *out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < cells && start[k + 1] > start[k]) atomicMax(out, (unsigned long long)(start[k + 1] - start[k]));
+}
+
 // Every pair whose value is at most `thr`, as a plan: the count pass, the scan (its total is read on the host: it sizes the plan) and the
 // write pass, for either pair value.  The arguments have been checked.  hyp: the per-node records of the hyperbolic value (else nullptr).
+// r: the caller's radius (Euclidean only): with it neighbors_route.h decides between the brute kernels below and the cell grid of
+// neighbors_grid.hip, which fills the same deg / rowptr64 / col / eid — the two routes mix (route 3: grid count, brute write).
 template <int METRIC>
-int threshold_graph(const char *who, gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float thr, const HypNode *hyp,
+int threshold_graph(const char *who, gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, float thr, float r, const HypNode *hyp,
                     const void *graph_indicator, int idx_bytes, int index_base, int64_t n_graphs, int self_loops, hipStream_t stream) {
+    int(&rec)[8] = nb_route_record();
+    std::fill(rec, rec + 8, 0);
     PlanPtr p(new gnnmp_graph_t());
     // (rowptr64 dies when the call returns: after plan_build_long_rows' synchronisation, or its hipFree waits itself)
     DevBuf<int64_t> rowptr64, seg;
     if (graph_indicator && N > 0)
         GNNMP_TRY(prepare_indicator(who, graph_indicator, idx_bytes, index_base, N, n_graphs, 0, stream, seg));
+    // the route: the cheap test first — a call that fails it runs the brute search with its launches and synchronisations as they were
+    const NbShape shape{N, d, graph_indicator ? n_graphs : 1, r, !graph_indicator || N == 0 || seg.get() != nullptr, METRIC == NB_L2,
+                        nb_forced_route()};
+    int why = nb_cheap_test(shape);
+    if (shape.force == NB_FORCE_GRID && why != NB_WHY_NONE && N > 0)
+        return fail(GNNMP_EUNSUPPORTED, "%s: the grid route was forced, but %s", who, nb_why_text(why));
+    GridIndex ix;
+    bool grid = false;
+    if (why == NB_WHY_NONE) {
+        NbBox box;
+        GNNMP_TRY(grid_bbox(points, N, (int)d, stream, box));
+        const NbGrid geo = nb_plan_grid(shape, box);
+        grid = geo.route == NB_ROUTE_GRID;
+        why = geo.why;
+        if (grid) {
+            GNNMP_TRY(grid_build(ix, geo, points, N, (int)d, graph_indicator, idx_bytes, index_base, stream));
+            std::copy(geo.nc, geo.nc + 3, rec + 1);
+        }
+    }
+    rec[5] = why;
     GNNMP_TRY(alloc_plan_rows(p.get(), N));
-    GNNMP_HIP(rowptr64.alloc((size_t)(N + 1)));
+    GNNMP_HIP(rowptr64.alloc((size_t)(N + 2)));   // [N]: the total after the scan; [N + 1]: the largest degree (grid route)
     NbArgs a = make_args(points, N, d, graph_indicator, idx_bytes, index_base, seg.get(), self_loops, p.get());
     a.r2 = thr;
     a.hyp = hyp;
-    GNNMP_HIP(hipMemsetAsync(rowptr64.get() + N, 0, sizeof(int64_t), stream));
-    if (N > 0) {
+    GNNMP_HIP(hipMemsetAsync(rowptr64.get() + N, 0, 2 * sizeof(int64_t), stream));
+    if (grid) {
+        GNNMP_TRY(grid_count(ix, thr, self_loops, rowptr64.get(), rowptr64.get() + N + 1, stream));
+    } else if (N > 0) {
         a.deg = rowptr64.get();
         neighbors_kernel<NB_COUNT, METRIC><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
         GNNMP_HIP(hipGetLastError());
     }
     GNNMP_TRY(exclusive_scan_i64(rowptr64.get(), rowptr64.get(), (size_t)(N + 1), stream));
-    int64_t tot = 0;
-    GNNMP_HIP(hipMemcpyAsync(&tot, rowptr64.get() + N, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    int64_t tot[2] = {0, 0};   // the total and, on the grid route, the largest degree
+    DevBuf<unsigned long long> fullest;
+    unsigned long long h_fullest = 0;
+    if (grid) {
+        GNNMP_HIP(fullest.alloc(1));
+        GNNMP_HIP(hipMemsetAsync(fullest.get(), 0, sizeof(unsigned long long), stream));
+        grid_fullest_kernel<<<nblk(ix.geo.table - 1), 256, 0, stream>>>(ix.start.get(), ix.geo.table - 1, fullest.get());
+        GNNMP_HIP(hipGetLastError());
+        GNNMP_HIP(hipMemcpyAsync(&h_fullest, fullest.get(), sizeof(h_fullest), hipMemcpyDeviceToHost, stream));
+    }
+    GNNMP_HIP(hipMemcpyAsync(tot, rowptr64.get() + N, (grid ? 2 : 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     GNNMP_HIP(hipStreamSynchronize(stream));
-    if (tot >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "%s: %lld edges exceed the plan format", who, (long long)tot);
-    GNNMP_TRY(alloc_plan_slots(p.get(), tot));
+    if (tot[0] >= (int64_t)GNNMP_MAX_SLOTS) return fail(GNNMP_EUNSUPPORTED, "%s: %lld edges exceed the plan format", who, (long long)tot[0]);
+    GNNMP_TRY(alloc_plan_slots(p.get(), tot[0]));
     narrow_rowptr_kernel<<<nblk(N + 1), 256, 0, stream>>>(rowptr64.get(), p->rowptr, N);
     GNNMP_HIP(hipGetLastError());
-    if (tot > 0) {
+    const bool grid_write_pass = grid && tot[1] <= NB_GRID_ROW_CAP;
+    if (tot[0] > 0 && grid_write_pass) {
+        GNNMP_TRY(grid_write(ix, thr, self_loops, rowptr64.get(), p->col, p->eid, tot[1], stream));
+    } else if (tot[0] > 0) {
         a.col = p->col;
         a.eid = p->eid;
         a.rowptr = rowptr64.get();
         neighbors_kernel<NB_WRITE, METRIC><<<nblk(N, NB_QB), 256, 0, stream>>>(a);
         GNNMP_HIP(hipGetLastError());
+    }
+    if (N > 0) rec[0] = !grid ? NB_ROUTE_BRUTE : grid_write_pass ? NB_ROUTE_GRID : NB_ROUTE_GRID_COUNT_BRUTE_WRITE;
+    if (grid) {
+        rec[4] = (int)std::min<unsigned long long>(h_fullest, (unsigned long long)INT32_MAX);
+        if (!grid_write_pass) rec[5] = NB_WHY_ROW_CAP;
     }
     GNNMP_TRY(plan_build_long_rows(p.get(), stream));
     *out = p.release();
@@ -436,6 +510,19 @@ int threshold_graph(const char *who, gnnmp_graph_t **out, const float *points, i
 using namespace gnnmp;
 
 extern "C" {
+
+// test hooks (gnnmp.h, GNNMP_INTERNAL): host memory of the calling thread, no stream, no device pointer
+int gnnmp_debug_neighbors_route(int info[8]) {
+    if (!info) return fail(GNNMP_EINVAL, "gnnmp_debug_neighbors_route: null pointer");
+    std::copy(nb_route_record(), nb_route_record() + 8, info);
+    return GNNMP_OK;
+}
+int gnnmp_debug_neighbors_force(int route) {
+    if (route != NB_FORCE_AUTO && route != NB_FORCE_BRUTE && route != NB_FORCE_GRID)
+        return fail(GNNMP_EINVAL, "gnnmp_debug_neighbors_force: route %d is not 0 (auto), 1 (brute) or 2 (grid)", route);
+    nb_forced_route() = route;
+    return GNNMP_OK;
+}
 
 int gnnmp_knn_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, int64_t d, int64_t k, const void *graph_indicator,
                         int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
@@ -469,7 +556,7 @@ int gnnmp_radius_graph_f32(gnnmp_graph_t **out, const float *points, int64_t N, 
                            int idx_bytes, int index_base, int64_t n_graphs, int self_loops, gnnmp_stream_t stream_) {
     GNNMP_TRY(check_common("radius_graph", out, points, N, d, graph_indicator, idx_bytes, index_base, n_graphs));
     if (!(r >= 0.0f)) return fail(GNNMP_EINVAL, "radius_graph: r = %g (negative or NaN)", (double)r);
-    return threshold_graph<NB_L2>("radius_graph", out, points, N, d, r * r, nullptr, graph_indicator, idx_bytes, index_base, n_graphs,
+    return threshold_graph<NB_L2>("radius_graph", out, points, N, d, r * r, r, nullptr, graph_indicator, idx_bytes, index_base, n_graphs,
                                   self_loops, (hipStream_t)stream_);
 }
 
@@ -488,7 +575,7 @@ int gnnmp_hyperbolic_graph_f32(gnnmp_graph_t **out, const float *points, int64_t
         hyp_nodes_kernel<<<nblk(N), 256, 0, stream>>>(points, N, (double)zeta, nodes.get());
         GNNMP_HIP(hipGetLastError());
     }
-    return threshold_graph<NB_HYP>("hyperbolic_graph", out, points, N, 2, thr, nodes.get(), graph_indicator, idx_bytes, index_base,
+    return threshold_graph<NB_HYP>("hyperbolic_graph", out, points, N, 2, thr, 0.0f, nodes.get(), graph_indicator, idx_bytes, index_base,
                                    n_graphs, self_loops, stream);
 }
 

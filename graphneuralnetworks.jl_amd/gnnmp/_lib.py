@@ -73,6 +73,7 @@ SYMBOLS = (
     # the GNNMP_INTERNAL section of the header: experiment / test hooks, exported but not part of the drop-in surface
     "gnnmp_tune", "gnnmp_tune_get", "gnnmp_debug_mock_device", "gnnmp_debug_device_once", "gnnmp_debug_plan_block", "gnnmp_debug_pool_pick",
     "gnnmp_debug_random_walk_pe_f32", "gnnmp_debug_dense_route", "gnnmp_debug_grouped_dense_route",
+    "gnnmp_debug_neighbors_route", "gnnmp_debug_neighbors_force",
 )
 
 
@@ -625,6 +626,8 @@ def load():
         "gnnmp_grouped_dense_f32": [ctypes.POINTER(GroupedDenseJob), i64, i64, i64, i64, vp],
         "gnnmp_grouped_dense_grad_w_f32": [ctypes.POINTER(GroupedDenseGradJob), i64, i64, i64, i64, vp],
         "gnnmp_debug_grouped_dense_route": [ctypes.POINTER(i)],
+        "gnnmp_debug_neighbors_route": [ctypes.POINTER(i)],
+        "gnnmp_debug_neighbors_force": [i],
     }
     for name, args in sig.items():
         try:

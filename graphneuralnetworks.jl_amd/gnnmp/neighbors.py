@@ -3,6 +3,8 @@
 The reference searches NearestNeighbors.jl trees on the CPU; here the search is an exact brute-force kernel (csrc/neighbors.hip,
 include/gnnmp.h states the semantics: fp32 fma chain, ties to the lower index, `self_loops=False` excludes a node by index, the
 candidates of a node are the nodes of its graph on the raw coordinates).  torch allocates; the indices are libgnnmp's.
+radius_graph has a second route with the same answer bit for bit: a uniform cell grid for up to three dimensions (csrc/neighbors_grid.hip,
+chosen by csrc/neighbors_route.h from 32 768 points on; `route=` forces one, last_route() tells which ran).
 
 The edges come out destination-sorted (edge i k + r joins centre i and its r-th neighbour), so the two entry points write the
 graph's PLAN themselves — no sort, no gnnmp_plan_create on first use — and (s, t) are read off it by gnnmp_plan_edge_index in the
@@ -20,6 +22,16 @@ from . import _lib as L
 from .graph import GNNGraph, Plan, _as_f32, _as_index
 
 MAX_K = 1024
+ROUTES = {"auto": 0, "brute": 1, "grid": 2}                           # gnnmp_debug_neighbors_force
+ROUTE_NONE, ROUTE_BRUTE, ROUTE_GRID, ROUTE_GRID_COUNT_BRUTE_WRITE = 0, 1, 2, 3   # gnnmp_debug_neighbors_route's info[0]
+
+
+def last_route():
+    """[route, cells per axis x 3, points in the fullest cell, reason code, 0, 0] of the calling thread's last radius_graph /
+    hyperbolic_graph call (gnnmp_debug_neighbors_route; csrc/neighbors_route.h names the reason codes)"""
+    info = (ctypes.c_int * 8)()
+    L.check(L.load().gnnmp_debug_neighbors_route(info))
+    return list(info)
 
 
 def _prepare(points, graph_indicator, dir, index_base, idx_dtype):
@@ -93,9 +105,14 @@ def knn_graph(points, k, graph_indicator=None, self_loops=False, dir="in", index
     return _graph(h, n, gi, G, dir, index_base, idx_dtype, device, kws)
 
 
-def radius_graph(points, r, graph_indicator=None, self_loops=False, dir="in", index_base=1, idx_dtype=torch.int64, **kws) -> GNNGraph:
+def radius_graph(points, r, graph_indicator=None, self_loops=False, dir="in", index_base=1, idx_dtype=torch.int64, route="auto",
+                 **kws) -> GNNGraph:
     """radius_graph(points, r; graph_indicator = nothing, self_loops = false, dir = :in, kws...) — generate.jl:196-222: every node is
-    linked to the points (of its own graph) within distance r: d2 <= r^2 in float32.  Nodes ascend, the neighbours of a node ascend."""
+    linked to the points (of its own graph) within distance r: d2 <= r^2 in float32.  Nodes ascend, the neighbours of a node ascend.
+    route: "auto" (the library picks), "brute" or "grid" — the same graph bit for bit; a forced "grid" on a call that cannot take it
+    (more than 3 dimensions, an unsorted graph_indicator) raises GnnmpError(EUNSUPPORTED).  last_route() tells what ran."""
+    if route not in ROUTES:
+        raise ValueError(f"radius_graph: route = {route!r} is not one of {sorted(ROUTES)}")
     r = float(r)
     if not r >= 0.0 or math.isnan(r):
         raise ValueError(f"radius_graph: r = {r} (negative or NaN)")
@@ -103,6 +120,11 @@ def radius_graph(points, r, graph_indicator=None, self_loops=False, dir="in", in
     if x.shape[1] < 1:
         raise ValueError("radius_graph: points have no features")
     h = ctypes.c_void_p()
-    _status(L.load().gnnmp_radius_graph_f32(ctypes.byref(h), L.ptr(x), n, x.shape[1], ctypes.c_float(r),
-                                            *_indicator_args(gi, index_base, G), int(bool(self_loops)), L.stream_ptr()))
+    lib = L.load()
+    L.check(lib.gnnmp_debug_neighbors_force(ROUTES[route]))
+    try:
+        _status(lib.gnnmp_radius_graph_f32(ctypes.byref(h), L.ptr(x), n, x.shape[1], ctypes.c_float(r),
+                                           *_indicator_args(gi, index_base, G), int(bool(self_loops)), L.stream_ptr()))
+    finally:
+        lib.gnnmp_debug_neighbors_force(ROUTES["auto"])
     return _graph(h, n, gi, G, dir, index_base, idx_dtype, device, kws)

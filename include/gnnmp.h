@@ -1369,7 +1369,19 @@ int gnnmp_edge_dot_grad_f32(gnnmp_graph_t *plan, gnnmp_graph_t *plan_transposed,
  *   gnnmp_radius_graph_f32  j is a neighbour of i iff d2(i, j) <= r2, r2 = r * r formed once in fp32 (r >= 0; r < 0 or NaN:
  *                           GNNMP_EINVAL).  Centres ascend, the neighbours of a centre ascend in j.  A count pass, an exclusive scan
  *                           (the total is read on the host: it sizes the plan) and a write pass.
- * Both synchronise the stream, as every plan build does (+ once for an indicator's checks, twice when it is unsorted).  Arguments are
+ *                           Two routes, ONE answer (csrc/neighbors_route.h decides on the host and holds the argument): the brute
+ *                           search above, and for d <= 3 with an absent or non-decreasing indicator a uniform CELL GRID
+ *                           (csrc/neighbors_grid.hip): the points are binned by (graph, cell) with a cell side h >= r (1 + 2^-10) and
+ *                           cell coordinates computed in double, so that every hit of the fp32 chain lies within +-1 cell per axis;
+ *                           a centre then meets the 3^d cells around its own — work N 3^d (points a cell) instead of sum n_g^2 —
+ *                           with the same fma chain, and a row-order pass puts every row into ascending j.  The plan (rowptr, col,
+ *                           eid, the long-row tables) is bit-identical to the brute route's.  A point with a non-finite coordinate is
+ *                           in no cell: degree 0, as on the brute route.  Rows longer than 1024 (NB_GRID_ROW_CAP) anywhere: the grid
+ *                           counts and the brute kernel writes.  auto takes the grid from 32 768 points and 32 768 a graph
+ *                           when the box holds at least four 3^d neighbourhoods of cells; r * r = +inf stays brute.  Workspace of
+ *                           the grid: 32 N bytes of keys, order and records + the cell-start table, at most 2 N + 4096 entries.
+ * Both synchronise the stream, as every plan build does (+ once for an indicator's checks, twice when it is unsorted; the grid route of
+ * gnnmp_radius_graph_f32 once more to read the bounding box of the finite points, and inside its radix sort).  Arguments are
  * checked before any HIP call.  Workspace: the segment table, the scan's scratch and int64[N + 1]; no N x N or N x tile array exists
  * in memory.  No atomics in the search kernels (the graph sizes of an UNSORTED indicator are counted with integer adds).
  * N < 2^31 - 1, d <= 2^20, edges < GNNMP_MAX_SLOTS.
@@ -2744,6 +2756,15 @@ int64_t gnnmp_grouped_dense_grad_workspace(int64_t N, int64_t G, int64_t Dout, i
  *                                  gradient), 4 grouped_gradw_fma (any-shape gradient); info[1] = column blocks of 16 a column tile
  *                                  (forward MFMA) or S, the slabs a group (gradient); info[2] = waves a block; info[3] = grid.x.
  *                                  (tests/test_grouped_dense.py)
+ *   gnnmp_debug_neighbors_route(info)  what the calling thread's last gnnmp_radius_graph_f32 / gnnmp_hyperbolic_graph_f32 call launched
+ *                                  (csrc/neighbors_route.h; host memory of the thread).  info[0] = 0 nothing, 1 the brute search, 2 the
+ *                                  cell grid, 3 grid count + brute write (a row above NB_GRID_ROW_CAP); info[1..3] = cells per axis;
+ *                                  info[4] = points in the fullest cell; info[5] = why the grid was not (fully) taken (NbWhy: 1 d > 3,
+ *                                  2 unsorted indicator, 3 r * r overflows, 4 N out of range, 5 too many graphs, 6 below the crossover,
+ *                                  7 too few cells to prune, 8 brute forced, 9 row cap, 10 hyperbolic metric); info[6..7] spare.
+ *   gnnmp_debug_neighbors_force(route) the calling thread's route until called again: 0 auto, 1 brute, 2 grid.  A forced grid on a call
+ *                                  that cannot take it (reasons 1 - 5 and 10) returns GNNMP_EUNSUPPORTED, names the reason and leaves
+ *                                  *out NULL.  Any other value: GNNMP_EINVAL.  (tests/test_neighbors_grid.py)
  * ---------------------------------------------------------------------------------------------- */
 int gnnmp_tune(int knob, int value);
 int gnnmp_tune_get(int knob, int *value, int *default_value);
@@ -2754,6 +2775,8 @@ int gnnmp_debug_pool_pick(const uint64_t *caps, int n, uint64_t bytes);
 int gnnmp_debug_random_walk_pe_f32(gnnmp_graph_t *plan_t, const gnnmp_rwpe_t *job, int64_t lds_budget_bytes, gnnmp_stream_t stream);
 int gnnmp_debug_dense_route(int info[8]);
 int gnnmp_debug_grouped_dense_route(int info[4]);
+int gnnmp_debug_neighbors_route(int info[8]);
+int gnnmp_debug_neighbors_force(int route);
 
 #ifdef __cplusplus
 }

@@ -9,10 +9,20 @@ time-to-first-propagate (graph + plan + one propagate(copy_xj, max)); A, B, A, B
 --reps.  The call builds a plan (allocations, one synchronisation), so its time is an UPPER bound of the search kernel's; pair
 evaluations per second and the share of the fp32 vector peak (3 d flops a pair: sub, fma; peak = 256 CUs x 4 SIMDs x 32 lanes x
 2 flop x 2.4 GHz = 157 Tflop/s) are computed from it and are lower bounds.  Prints ONE JSON line.
-    python tools/bench_neighbors.py [--reps 20] [--warmup 3]"""
+    python tools/bench_neighbors.py [--reps 20] [--warmup 3]
+
+--routes: radius_graph's two routes instead (csrc/neighbors_route.h: where is the crossover?).  Single clouds of 2^14 .. 2^20 points in the
+unit box, d = 2 and 3, uniform and clustered (64 Gaussian blobs, sigma 0.02), at cutoffs calibrated to about 16 and 64 neighbours a
+point; route = brute and route = grid of the SAME build through the C ABI (gnnmp_radius_graph_f32 + gnnmp_plan_destroy: the whole plan
+build, synchronisations included), A, B, A, B in one process, median of --reps per round (brute: fewer repetitions as N grows — a call
+is seconds at 2^20).  "spread" is the larger relative gap between the two rounds of either route: a difference inside it is no
+difference.  With GNNMP_LIB naming a build without the route hook (the parent commit's) only its one route is timed, as "brute": run
+both on one box and compare the brute columns to see that the brute route did not move.
+    python tools/bench_neighbors.py --routes [--log2n 14,15,16,17,18,19,20]"""
 import argparse
 import ctypes
 import json
+import math
 import os
 import sys
 
@@ -57,14 +67,73 @@ def torch_knn(x, B, n, k):
     return s, t
 
 
+def cloud(n, d, kind, gen):
+    if kind == "uniform":
+        return torch.rand((n, d), device="cuda", generator=gen)
+    centres = torch.rand((64, d), device="cuda", generator=gen)
+    pick = torch.randint(0, 64, (n,), device="cuda", generator=gen)
+    return (centres[pick] + 0.02 * torch.randn((n, d), device="cuda", generator=gen)).contiguous()
+
+
+def routes(a, lib):
+    """brute against grid on single clouds: one JSON line, a row per (log2 N, d, kind, target degree)"""
+    hook = getattr(lib, "gnnmp_debug_neighbors_force", None)
+    out = {"bench": "neighbors_routes", "reps": a.reps, "hook": hook is not None, "rows": []}
+
+    def call(x, r, route):
+        h = ctypes.c_void_p()
+        if hook is not None:
+            L.check(hook(route))
+        try:
+            L.check(lib.gnnmp_radius_graph_f32(ctypes.byref(h), L.ptr(x), x.shape[0], x.shape[1], ctypes.c_float(r), None, 0, 1, 1, 0, L.stream_ptr()))
+        finally:
+            if hook is not None:
+                hook(0)
+        info = (ctypes.c_int64 * 8)()
+        L.check(lib.gnnmp_plan_info(h, info))
+        L.check(lib.gnnmp_plan_destroy(h))
+        return info[2]
+
+    for lg in (int(v) for v in a.log2n.split(",")):
+        n = 1 << lg
+        for d in (2, 3):
+            for kind in ("uniform", "clustered"):
+                x = cloud(n, d, kind, torch.Generator(device="cuda").manual_seed(11))
+                for target in (16, 64):
+                    # the uniform cutoff, then one secant step on the measured mean degree (a blob is far denser than the box)
+                    unit = math.pi if d == 2 else 4.0 / 3.0 * math.pi
+                    r = (target / (unit * n)) ** (1.0 / d)
+                    fast = 2 if hook is not None else 1
+                    if kind == "clustered":
+                        r *= 0.02 * 64 ** (1.0 / d)
+                    for _ in range(2):
+                        r *= (target / max(call(x, r, fast if n > 65536 else 1) / n, 1e-3)) ** (1.0 / d)
+                    row = {"log2n": lg, "d": d, "kind": kind, "target": target, "r": r, "mean_degree": call(x, r, fast if n > 65536 else 1) / n}
+                    breps = a.reps if n <= 1 << 16 else max(2, a.reps >> (lg - 15))
+                    for rnd in range(2):
+                        row.setdefault("brute_ms", []).append(timed(lambda: call(x, r, 1), breps, 1))
+                        if hook is not None:
+                            row.setdefault("grid_ms", []).append(timed(lambda: call(x, r, 2), a.reps, a.warmup))
+                    gaps = [abs(v[0] - v[1]) / min(v) for v in (row["brute_ms"], row.get("grid_ms", [1.0, 1.0]))]
+                    row["spread"] = max(gaps)
+                    if hook is not None:
+                        row["grid_speedup"] = min(row["brute_ms"]) / min(row["grid_ms"])
+                    out["rows"].append(row)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default="modelnet,dgcnn,cloud64k")
+    ap.add_argument("--routes", action="store_true")
+    ap.add_argument("--log2n", default="14,15,16,17,18,19,20")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_neighbors needs the GPU: there is no CPU fallback and no CPU timing"
     lib = L.load()
+    if a.routes:
+        return routes(a, lib)
     out = {"bench": "neighbors", "reps": a.reps, "shapes": {}}
     for name, B, n, d, k in SHAPES:
         if name not in a.shapes.split(","):
